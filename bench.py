@@ -8,7 +8,10 @@ frames already resident in HBM:
          all-reduce + clip + Adam]
 value = (T * N_total * steps) / wall time, max over ranks, barrier+sync bracketed.
 
-    python bench.py                            # 1 GPU, 256 actors, K=2 W=1
+    python bench.py                            # 1 GPU, 256 actors, K=2 W=1: the headline line alone
+    python bench.py --full                     # + the secondary measurements (sync_actions, h2d_inclusive, plugin_path,
+                                               #   cpu_baseline; weak + all-reduce timing with a collective)
+    python bench.py --dump-outputs DIR         # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus 8                   # spawns its own 8 ranks (file-store rendezvous, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8  # ... or is launched one rank per GPU by torchrun
@@ -225,6 +228,42 @@ def _time_iterations(w, steps, warmup, barrier):
     return time.perf_counter() - t0
 
 
+DUMP_SAMPLE = 1 << 20                 # elements per dumped array; a larger one is written as a fixed, seeded sample of this many
+DUMP_PARAMS_MAX = 1 << 22             # ... except the flat policy parameters (3.48 M for the RN50 policy: written whole)
+
+
+def _dump_sample(x: torch.Tensor, k: int, seed: int) -> torch.Tensor:
+    """``x`` itself when it has at most ``k`` elements, else ``k`` elements of it at seeded random flat positions (sorted)."""
+    if x.numel() <= k:
+        return x
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, x.numel(), (k,), generator=g).sort().values
+    return x.reshape(-1)[idx.to(x.device)]
+
+
+def dump_outputs(w, out_dir: str) -> None:
+    """What the timed path computed in its last step, i.e. what a caller reads from the worker after ``iteration()``, as
+    ``out_dir/<name>.npy``: the updated flat policy parameters, the rollout's sampled actions, log-probs, value estimates,
+    returns and advantages, the recurrent state the next rollout starts from, the loss terms of the last minibatch
+    (float64: action, value, entropy, ratio, ppo_total, grad_norm) and a seeded sample of the rollout's encoder features.
+    float32 otherwise; at most ~45 MB whatever the sizes (the inputs are seeded: same arguments, same inputs)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"policy_params": _dump_sample(w.params, DUMP_PARAMS_MAX, 0)}
+    for i, (name, t) in enumerate((("actions", w.actions), ("log_probs", w.logp), ("values", w.values),
+                                   ("returns", w.returns), ("advantages", w.adv), ("hidden_state", w.h))):
+        arrays[name] = _dump_sample(t, DUMP_SAMPLE, 1 + i)
+    # the feature maps of all T + 1 encodes of the rollout (6.6 GB in bf16 at the default size): the same positions every run
+    per = DUMP_SAMPLE // len(w.slices)
+    arrays["features_sample"] = torch.cat([_dump_sample(sl.feat, per, 100 + i).reshape(-1).float()
+                                           for i, sl in enumerate(w.slices)])
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    loss = w.loss_info()
+    np.save(os.path.join(out_dir, "loss.npy"),
+            np.array([loss[k] for k in ("action", "value", "entropy", "ratio", "ppo_total", "grad_norm")], dtype=np.float64))
+
+
 _LINE_OUT = None     # the process's REAL stdout, kept aside by _claim_stdout(): only the JSON line is written to it
 
 
@@ -325,6 +364,8 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
 
     # ---- the headline measurement -----------------------------------------------------------------------------------
     dt = maxreduce(_time_iterations(w, a.steps, a.warmup, barrier))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(w, a.dump_outputs)
     # dominant kernel family: the RN50 trunk's MFMA implicit-GEMM convs, one ec_rn50_forward per env step
     trunk_ms = [e0.elapsed_time(e1) for e0, e1 in w.trunk_events]
     avg_trunk_ms = sum(trunk_ms) / max(1, len(trunk_ms))
@@ -465,7 +506,8 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
             "loss": {k: round(v, 6) for k, v in info.items()},
         }
 
-    # ---- secondary measurements: each fails SOFT (its key carries {"error": ...}) and the whole block runs under a watchdog
+    # ---- secondary measurements (--full; --phase-times on request): each fails SOFT (its key carries {"error": ...}) and the
+    # whole block runs under a watchdog
     import threading
     out_lock = threading.Lock()          # `out` is written by the main thread (put) and read by the watchdog's timer thread (emit)
     emitted = [False]
@@ -500,7 +542,7 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
         put("phases", _soft("phases", leg_phases, agree))
 
     # the single exchange step, timed alone on every rank (HIP events on the current stream, 20 calls)
-    if use_dist:
+    if a.full and use_dist:
         def leg_allreduce():
             from embodied_clip_amd.dist import allreduce_flat
             for _ in range(3):
@@ -542,7 +584,7 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
         w = None             # free the previous worker's ~11 GB before building the next
         gc.collect(); torch.cuda.empty_cache()
 
-    if not a.no_sync_actions and not a.sync_actions and not a.frames_host:
+    if a.full and not a.no_sync_actions and not a.sync_actions and not a.frames_host:
         def leg_sync():
             free_worker()
             ws_ = Worker(per_gpu, frames_host=False, sync_actions=True, **wkw)
@@ -573,7 +615,7 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
         dog.leg = "sync_actions"
         put("sync_actions", _soft("sync_actions", leg_sync, agree))
         gc.collect(); torch.cuda.empty_cache()
-    if not a.no_h2d and not a.frames_host:
+    if a.full and not a.no_h2d and not a.frames_host:
         def leg_h2d():
             free_worker()
             u8 = a.encoder != "vit"          # (the ViT patch-embed kernel takes the sensor's fp32 frames only)
@@ -589,7 +631,7 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
         dog.leg = "h2d_inclusive"
         put("h2d_inclusive", _soft("h2d_inclusive", leg_h2d, agree))
         gc.collect(); torch.cuda.empty_cache()
-    if world > 1 and a.scaling == "strong" and not a.no_weak:
+    if a.full and world > 1 and a.scaling == "strong" and not a.no_weak:
         def leg_weak():
             free_worker()
             ww = Worker(total, frames_host=a.frames_host, **wkw)
@@ -601,7 +643,7 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
         dog.leg = "weak"
         put("weak", _soft("weak", leg_weak, agree))
         gc.collect(); torch.cuda.empty_cache()
-    if world == 1 and a.encoder == "rn50" and not a.no_plugin:
+    if a.full and world == 1 and a.encoder == "rn50" and not a.no_plugin:
         def leg_plugin():
             free_worker()
             from embodied_clip_amd.plugin_path import time_plugin_path
@@ -620,7 +662,7 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
         dog.leg = "plugin_path"
         put("plugin_path", _soft("plugin_path", leg_plugin))
         gc.collect(); torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         def leg_cpu():
             r = cpu_baseline(a.cpu_actors, a.cpu_rollout, a.update_repeats)
             r["gpu_over_cpu"] = round(value / r["value"], 1)
@@ -641,8 +683,13 @@ def run_rank(a, rank: int, local_rank: int, world: int, init_method=None):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=2, help="timed iterations (the line's ms_per_step = timed wall clock / steps)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed iterations before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements after the headline: sync_actions, h2d_inclusive, plugin_path, "
+                         "cpu_baseline (1 GPU), weak (N > 1) and the all-reduce timing (with a collective); each --no-X skips one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--actors", type=int, default=256, help="synthetic actors in total (strong) / per GPU (weak)")
     ap.add_argument("--actors-total", type=int, default=0,
                     help="global actor count, overrides --actors (512 = BASELINE config 4: 64 per GPU at 8 GPUs)")
@@ -696,6 +743,8 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check only: rendezvous + one flat-bucket all-reduce over gloo on CPU, no GPU work")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error(f"--steps must be >= 1 and --warmup >= 0 (got {a.steps}, {a.warmup})")
     return a
 
 

@@ -46,6 +46,58 @@ def test_bench_defaults_are_the_metric_configuration():
     assert a.actors_total == 512 and a.scaling == "strong"       # config 4: 64 actors per GPU
 
 
+def test_plain_run_is_lean_by_default_and_steps_are_checked():
+    """The secondary measurements run with --full only; --steps sets the timed iterations and must be at least one."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 0)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_writes_seeded_bounded_arrays(tmp_path):
+    """bench.dump_outputs on a stand-in worker (CPU tensors of the real worker's attribute names): small arrays whole with their
+    shapes, large ones as a fixed seeded sample, float32 (loss terms float64), the same files from the same state."""
+    sys.path.insert(0, ROOT)
+    import types
+    import numpy as np
+    import torch
+    import bench
+    T, N, H = 4, 6, 8
+    g = torch.Generator().manual_seed(0)
+    big = bench.DUMP_SAMPLE + 1000
+    sl = [types.SimpleNamespace(feat=torch.randn(T + 1, 3, 49, 64, generator=g).to(torch.bfloat16)) for _ in range(2)]
+    w = types.SimpleNamespace(params=torch.randn(big, generator=g), actions=torch.randint(0, 6, (T, N), generator=g),
+                              logp=torch.randn(T, N, generator=g), values=torch.randn(T + 1, N, generator=g),
+                              returns=torch.randn(T + 1, N, generator=g), adv=torch.randn(T, N, generator=g),
+                              h=torch.randn(N, H, generator=g), slices=sl,
+                              loss_info=lambda: {"action": 0.5, "value": 1.5, "entropy": 1.75, "ratio": 1.0, "ppo_total": 1.26,
+                                                 "grad_norm": 0.25})
+    bench.dump_outputs(w, str(tmp_path / "a"))
+    bench.dump_outputs(w, str(tmp_path / "b"))
+    names = {"policy_params", "actions", "log_probs", "values", "returns", "advantages", "hidden_state", "features_sample", "loss"}
+    assert {p.name for p in (tmp_path / "a").iterdir()} == {n + ".npy" for n in names}
+    ld = lambda d, n: np.load(str(tmp_path / d / (n + ".npy")))   # noqa: E731
+    for n in names:
+        assert np.array_equal(ld("a", n), ld("b", n)), n
+        assert ld("a", n).dtype == (np.float64 if n == "loss" else np.float32), n
+    assert np.array_equal(ld("a", "policy_params"), w.params.numpy())                  # under DUMP_PARAMS_MAX: whole
+    assert np.array_equal(ld("a", "actions"), w.actions.float().numpy()) and ld("a", "values").shape == (T + 1, N)
+    assert np.array_equal(ld("a", "hidden_state"), w.h.numpy())
+    feats = torch.cat([s.feat.reshape(-1).float() for s in sl]).numpy()
+    assert ld("a", "features_sample").shape == (feats.size,)   # smaller than the sample: whole, slice by slice
+    assert np.array_equal(ld("a", "features_sample"), feats)
+    assert ld("a", "loss").tolist() == [0.5, 1.5, 1.75, 1.0, 1.26, 0.25]
+    # an array above the sample size: DUMP_SAMPLE elements of it, the same ones every call
+    s1 = bench._dump_sample(w.params, bench.DUMP_SAMPLE, 3)
+    assert s1.shape == (bench.DUMP_SAMPLE,) and torch.equal(s1, bench._dump_sample(w.params, bench.DUMP_SAMPLE, 3))
+    assert np.isin(s1.numpy(), w.params.numpy()).all()
+
+
 def test_secondary_legs_fail_soft_and_under_a_watchdog():
     """nothing a secondary leg raises may cost the headline line, and a hung leg is cut off by the
     watchdog, which prints the line with what is there."""

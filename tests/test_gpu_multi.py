@@ -19,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(*flags, timeout=1500):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags, "--no-cpu-baseline", "--no-h2d", "--no-traffic"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags, "--full", "--no-cpu-baseline", "--no-h2d",
+                        "--no-traffic"],
                        capture_output=True, text=True, timeout=timeout, cwd=ROOT,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -243,7 +244,8 @@ def test_bench_py_launched_as_the_driver_launches_it_with_two_ranks_sharing_one_
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--actors", "33", "--rollout", "8",
-           "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-h2d", "--no-traffic", "--no-plugin", "--no-sync-actions"]
+           "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-h2d", "--no-traffic", "--no-plugin",
+           "--no-sync-actions"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

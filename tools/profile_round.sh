@@ -2,6 +2,7 @@
 # Regenerates the evidence under gpurun_out/ for profiles/ (one gpurun call):  bash tools/profile_round.sh r02
 R=${1:-r03}
 cd $GRAFT_REPO_ROOT
+ROOT=$PWD
 O=gpurun_out/$R; mkdir -p $O
 # the launch the ENGINE issues (bench.py: two slices of 128 frames, dispatch threshold 50): same plan hash as bench.py's handles
 bash tools/pmc_collect.sh trunk_$R tools/bench_trunk.py --batch 128 --min-tiles 50 --iters 1 > $O/pmc_trunk.log 2>&1
@@ -41,12 +42,12 @@ json.dump(t, open("profiles/trunk_hbm_traffic.json", "w"), indent=1)
 json.dump(json.load(open(f"{O}/vit_b128_hbm_traffic.json")), open("profiles/vit_hbm_traffic.json", "w"), indent=1)
 PY
 bash tools/calibrate_fetch.sh $O/fetch_calibration.json > $O/fetch_calibration.log 2>&1
-python bench.py --steps 3 --warmup 1 > $O/bench_line.json 2> $O/bench.err
-python bench.py --steps 2 --warmup 1 --encoder vit --no-cpu-baseline > $O/bench_vit_line.json 2> $O/bench_vit.err
-python bench.py --steps 2 --warmup 1 --encoder zeroshot --no-cpu-baseline > $O/bench_zeroshot_line.json 2> $O/bench_zs.err
-python bench.py --steps 1 --warmup 1 --encoder rn50x16 --no-cpu-baseline --no-h2d --no-plugin > $O/bench_rn50x16_line.json 2> $O/bench_x16.err
+python bench.py --steps 3 --warmup 1 --full > $O/bench_line.json 2> $O/bench.err
+python bench.py --steps 2 --warmup 1 --full --encoder vit --no-cpu-baseline > $O/bench_vit_line.json 2> $O/bench_vit.err
+python bench.py --steps 2 --warmup 1 --full --encoder zeroshot --no-cpu-baseline > $O/bench_zeroshot_line.json 2> $O/bench_zs.err
+python bench.py --steps 1 --warmup 1 --full --encoder rn50x16 --no-cpu-baseline --no-h2d --no-plugin > $O/bench_rn50x16_line.json 2> $O/bench_x16.err
 for A in 128 64 32; do
-  python bench.py --steps 3 --warmup 1 --actors $A --no-cpu-baseline --no-h2d --no-plugin > $O/bench_${A}actors_line.json 2> $O/bench$A.err
+  python bench.py --steps 3 --warmup 1 --full --actors $A --no-cpu-baseline --no-h2d --no-plugin > $O/bench_${A}actors_line.json 2> $O/bench$A.err
 done
 python - <<PY
 import json
@@ -66,7 +67,7 @@ json.dump(proj, open(f"{O}/strong_scaling_projection.json", "w"), indent=1)
 print(proj)
 PY
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof_bench -o b -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-h2d --no-plugin > $GRAFT_REPO_ROOT/$O/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/prof_bench -o b -- python $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-h2d --no-plugin > $ROOT/$O/bench_under_rocprof.log 2>&1
 cd $GRAFT_REPO_ROOT
 find $O/prof_bench -name "*kernel_stats.csv" -exec cp {} $O/bench_kernel_stats.csv \;
 rm -rf $O/prof_bench
@@ -78,7 +79,7 @@ rm -rf $O/prof_upd
 python tools/bench_update.py --iters 3 | tail -1 > $O/update_ms.txt
 python tools/bench_img3x3.py 2>&1 | grep -v amdgpu.ids > $O/img3x3_vs_conv_igemm.txt
 # the exchange step at world size 1 through RCCL (communicator + kernel really run): per-call time of the 13.9 MB bucket all-reduce
-python bench.py --gpus 1 --force-dist --actors 32 --steps 2 --warmup 1 --no-cpu-baseline --no-h2d --no-plugin --no-sync-actions --no-traffic > $O/bench_32actors_forcedist_line.json 2> $O/bench32fd.err
+python bench.py --gpus 1 --force-dist --actors 32 --steps 2 --warmup 1 --full --no-cpu-baseline --no-h2d --no-plugin --no-sync-actions --no-traffic > $O/bench_32actors_forcedist_line.json 2> $O/bench32fd.err
 # the plugin route's phases (one full iteration, fp32 and uint8 sensor frames)
 python tools/plugin_iter_phases.py 2>&1 | grep -v amdgpu.ids > $O/plugin_iteration_phases.txt
 U8=1 python tools/plugin_iter_phases.py 2>&1 | grep -v amdgpu.ids >> $O/plugin_iteration_phases.txt
