@@ -52,6 +52,9 @@ SIGNATURES = {
     "ec_rn50tv_create": (c_int, [C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_void_p, c_void_p, c_size_t, c_void_p,
                                  c_size_t]),
     "ec_conv_bf16_s2": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
+    "ec_basic_tail_s2_bf16": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
+    "ec_tvresnet_basic_create": (c_int, [C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_void_p, c_void_p, c_size_t,
+                                         c_void_p, c_size_t]),
     "ec_stem7_pool": (c_int, [c_void_p, c_int, C.POINTER(c_float), C.POINTER(c_float), c_void_p, c_void_p, c_void_p,
                               c_int, c_int, c_int, c_void_p]),
     "ec_rn50_destroy": (None, [c_void_p]),

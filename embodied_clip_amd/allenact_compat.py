@@ -252,6 +252,9 @@ _PATCH_TARGETS = (
     ("allenact_plugins.robothor_plugin.robothor_models", ("ResnetTensorObjectNavActorCritic",)),
     ("allenact.algorithms.onpolicy_sync.losses.ppo", ("PPO",)),
     ("allenact.algorithms.onpolicy_sync.losses", ("PPO",)),
+    # the ImageNet baselines (objectnav_robothor_rgb_resnet{18,50}gru_ddppo: readme_files/imagenet_vs_objectnav.md,
+    # baselines_robothor_objectnav.md:47)
+    ("allenact.embodiedai.preprocessors.resnet", ("ResNetPreprocessor",)),
 )
 
 
@@ -261,10 +264,12 @@ def install_into_allenact(verbose: bool = False) -> List[str]:
     unchanged.  Call before the experiment config module is imported (``python -m embodied_clip_amd.allenact_main``
     does).  Returns the ``module.attr`` names that were patched; modules that are not installed are skipped."""
     from . import clip_preprocessors as cp
+    from . import imagenet_preprocessors as ip
     from . import policy as pol
     from . import ppo
     ours = {"ClipResNetPreprocessor": cp.ClipResNetPreprocessor, "ClipViTPreprocessor": cp.ClipViTPreprocessor,
-            "ResnetTensorObjectNavActorCritic": pol.ResnetTensorObjectNavActorCritic, "PPO": ppo.PPO}
+            "ResnetTensorObjectNavActorCritic": pol.ResnetTensorObjectNavActorCritic, "PPO": ppo.PPO,
+            "ResNetPreprocessor": ip.ResNetPreprocessor}
     done = []
     for modname, attrs in _PATCH_TARGETS:
         try:

@@ -22,7 +22,7 @@
 
 namespace {
 
-enum OpKind { OP_STEM1, OP_CONV, OP_POOL, OP_PAIR, OP_BNECK, OP_STEM7 };
+enum OpKind { OP_STEM1, OP_CONV, OP_POOL, OP_PAIR, OP_BNECK, OP_STEM7, OP_BTAIL };
 
 struct Op {
     OpKind kind;
@@ -50,7 +50,8 @@ struct Op {
 
 struct ec_rn50 {
     int width, res, out_c, out_sp;
-    int tv = 0;                   // 1: torchvision ResNet (7x7 stem + max-pool, stride inside conv2 / the downsample conv): ec_rn50tv_create
+    int tv = 0;                   // 1: torchvision ResNet (7x7 stem + max-pool, stride inside conv2 / the downsample conv): ec_rn50tv_create;
+                                  // 2: torchvision BasicBlock ResNet (ResNet-18 / 34): ec_tvresnet_basic_create
     std::vector<Op> ops;
     size_t max_elems_per_frame;   // largest activation (bf16 elements) per frame
     const float* stem_w;
@@ -77,6 +78,7 @@ extern "C" int ec_conv_bf16_s2(const void* in, const void* w, const float* bias,
                                int Cin, int Cout, int ksize, int act, ec_stream_t stream);
 
 namespace {
+int pack_plan_weights(ec_rn50* h);
 int rn50_build(ec_rn50_t** out, bool tv, int width, const int* layers4, int input_resolution, const void* stem_w,
                const void* w_bf16, size_t n_w, const float* bias, size_t n_bias);
 }
@@ -305,6 +307,14 @@ int rn50_build(ec_rn50_t** out, bool tv, int width, const int* layers4, int inpu
     h->max_elems_per_frame = mx;
     h->n_w = wo; h->n_b = bo;
     if (n_w != wo || n_bias != bo) { delete h; return EC_ERR_SHAPE; }
+    const int rc = pack_plan_weights(h);
+    if (rc != EC_OK) { delete h; return rc; }
+    *out = h;
+    return EC_OK;
+}
+
+// Weights the plan's fused / K-concatenated launches read in their own layout (device copies owned by the handle)
+int pack_plan_weights(ec_rn50* h) {
     {   // fused bottleneck launches: their conv2 + conv3 weights in streaming order, one packed block per op (w2_off = its offset)
         size_t tot = 0, btot = 0;
         for (Op& o : h->ops)
@@ -312,18 +322,19 @@ int rn50_build(ec_rn50_t** out, bool tv, int width, const int* layers4, int inpu
                 o.wcat_off = (long)tot; tot += (size_t)o.Cout * o.Cin;
                 o.bcat_off = (long)btot; btot += (size_t)o.Cout;
             }
-        if (btot && hipMalloc(&h->bias_cat, btot * sizeof(float)) != hipSuccess) { h->bias_cat = nullptr; delete h; return EC_ERR_LAUNCH; }
+        if (btot && hipMalloc(&h->bias_cat, btot * sizeof(float)) != hipSuccess) { h->bias_cat = nullptr; return EC_ERR_LAUNCH; }
         for (Op& o : h->ops) {
             if (o.kind == OP_BNECK) { o.w2_off = tot; o.wimg_off = (long)tot; tot += ec_bneck3_packed_elems(o.Cin); }   // (packed conv2 comes first; room for conv1 too)
             // the un-pooled 3x3 convs of the 7x7 stage: streaming-order weights for the small-launch kernel (conv3x3_img_kernel)
-            if (o.kind == OP_CONV && o.ks == 3 && o.Cin == 512 && o.Cout == 512 && ec_config().rn50_img3 &&
+            // (that kernel has no residual input: a BasicBlock's conv2 stays on conv_igemm)
+            if (o.kind == OP_CONV && o.ks == 3 && o.Cin == 512 && o.Cout == 512 && o.res < 0 && ec_config().rn50_img3 &&
                 ((!o.pool && o.H == 7 && o.W == 7) || (o.pool && o.H == 14 && o.W == 14))) {   // (layer4.0's conv2 + AvgPool2d: the chunked variant)
                 o.wimg_off = (long)tot;
                 tot += (size_t)o.Cout * 9 * o.Cin;
             }
         }
         if (tot) {
-            if (hipMalloc(&h->wbneck, tot * sizeof(uint16_t)) != hipSuccess) { h->wbneck = nullptr; delete h; return EC_ERR_LAUNCH; }
+            if (hipMalloc(&h->wbneck, tot * sizeof(uint16_t)) != hipSuccess) { h->wbneck = nullptr; return EC_ERR_LAUNCH; }
             for (const Op& o : h->ops) {
                 int rc = EC_OK;
                 if (o.wcat_off >= 0) {
@@ -332,27 +343,102 @@ int rn50_build(ec_rn50_t** out, bool tv, int width, const int* layers4, int inpu
                     if (hipMemcpy2D(wc, (size_t)o.Cin * 2, h->w + o.w_off, (size_t)K1 * 2, (size_t)K1 * 2, (size_t)o.Cout,
                                     hipMemcpyDeviceToDevice) != hipSuccess ||
                         hipMemcpy2D(wc + K1, (size_t)o.Cin * 2, h->w + o.w1_off, (size_t)K2 * 2, (size_t)K2 * 2, (size_t)o.Cout,
-                                    hipMemcpyDeviceToDevice) != hipSuccess) { delete h; return EC_ERR_LAUNCH; }
+                                    hipMemcpyDeviceToDevice) != hipSuccess) return EC_ERR_LAUNCH;
                     std::vector<float> b3((size_t)o.Cout), bd((size_t)o.Cout);
                     if (hipMemcpy(b3.data(), h->bias + o.b_off, (size_t)o.Cout * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(bd.data(), h->bias + o.b1_off, (size_t)o.Cout * 4, hipMemcpyDeviceToHost) != hipSuccess) { delete h; return EC_ERR_LAUNCH; }
+                        hipMemcpy(bd.data(), h->bias + o.b1_off, (size_t)o.Cout * 4, hipMemcpyDeviceToHost) != hipSuccess) return EC_ERR_LAUNCH;
                     for (int i = 0; i < o.Cout; ++i) b3[(size_t)i] += bd[(size_t)i];
-                    if (hipMemcpy(h->bias_cat + o.bcat_off, b3.data(), (size_t)o.Cout * 4, hipMemcpyHostToDevice) != hipSuccess) { delete h; return EC_ERR_LAUNCH; }
+                    if (hipMemcpy(h->bias_cat + o.bcat_off, b3.data(), (size_t)o.Cout * 4, hipMemcpyHostToDevice) != hipSuccess) return EC_ERR_LAUNCH;
                     continue;
                 }
                 if (o.kind == OP_BNECK)
                     rc = o.wc1_off >= 0 ? ec_bneck3_pack_weights(h->w + o.wc1_off, h->w + o.w_off, h->w + o.w1_off, h->wbneck + o.w2_off, o.Cin, nullptr)
                                         : ec_bneck_pack_weights(h->w + o.w_off, h->w + o.w1_off, h->wbneck + o.w2_off, o.Cin, nullptr);
                 else if (o.wimg_off >= 0) rc = ec_conv3x3_img_pack(h->w + o.w_off, h->wbneck + o.wimg_off, o.Cin, nullptr);
-                if (rc != EC_OK) { delete h; return EC_ERR_LAUNCH; }
+                if (rc != EC_OK) return EC_ERR_LAUNCH;
             }
             (void)hipStreamSynchronize(nullptr);
         }
     }
-    *out = h;
     return EC_OK;
 }
 }  // namespace
+
+// torchvision BasicBlock ResNet (ResNet-18: 2,2,2,2 / ResNet-34: 3,4,6,3) without avgpool / fc, behind the same handle:
+// the 7x7 stem launch of ec_rn50tv_create, then per block
+//   conv1: 3x3 + ReLU (stride 2 in the first block of layers 2-4: ec_conv_bf16_s2)
+//   conv2: stride-1 blocks  3x3 + identity + ReLU (ec_conv_bf16 with a residual)
+//          transition blocks 3x3 over conv1's output + the 1x1 stride-2 downsample conv of the block input + ReLU as ONE
+//                            K-concatenated GEMM (OP_BTAIL, conv_basic.hip)
+// Buffers: the block input / output ping-pong between 0 and 4, conv1's output goes to 1; buffer 3 holds the downsample
+// output of a transition tail that runs as two launches (rn50_run).
+extern "C" int ec_tvresnet_basic_create(ec_rn50_t** out, const int* layers4, int input_resolution, const void* stem_w_bf16,
+                                        const void* w_bf16, size_t n_w, const float* bias, size_t n_bias) {
+    if (!out || !layers4 || !stem_w_bf16 || !w_bf16 || !bias) return EC_ERR_ARG;
+    if (input_resolution % 32 != 0 || input_resolution < 32) return EC_ERR_SHAPE;
+    for (int li = 0; li < 4; ++li)
+        if (layers4[li] < 1) return EC_ERR_SHAPE;
+    const int width = 64;
+    ec_rn50* h = new (std::nothrow) ec_rn50();
+    if (!h) return EC_ERR_ALLOC;
+    h->width = width; h->res = input_resolution; h->tv = 2;
+    h->stem_w = (const float*)stem_w_bf16; h->w = (const uint16_t*)w_bf16; h->bias = bias;
+    size_t wo = 0, bo = 0, mx = 0;
+    auto track = [&](int H, int W, int C) { mx = std::max(mx, (size_t)H * W * C); };
+    int R = input_resolution / 4;
+    {   // conv1 7x7 s2 + bn1 + relu + maxpool 3x3 s2 in one launch: frame -> buffer 0 at R x R x 64
+        Op o{OP_STEM7, -2, 0, -1, input_resolution, input_resolution, 3, width, 7, 0, EC_ACT_RELU, 0, bo};
+        bo += width;
+        h->ops.push_back(o);
+        track(R, R, width);
+    }
+    int inplanes = width, x = 0;
+    for (int li = 0; li < 4; ++li) {
+        const int planes = width << li;
+        for (int b = 0; b < layers4[li]; ++b) {
+            const int stride = (b == 0 && li > 0) ? 2 : 1;
+            const int y = (x == 0) ? 4 : 0;
+            const int Ro = R / stride;
+            {   // conv1 (H, W of a stride-2 op are its INPUT dims)
+                Op o{OP_CONV, x, 1, -1, R, R, inplanes, planes, 3, 0, EC_ACT_RELU, wo, bo};
+                o.stride = stride;
+                wo += (size_t)planes * 9 * inplanes; bo += planes;
+                h->ops.push_back(o);
+                track(Ro, Ro, planes);
+            }
+            if (stride == 1 && inplanes == planes) {   // conv2 + identity + ReLU
+                Op o{OP_CONV, 1, y, x, R, R, planes, planes, 3, 0, EC_ACT_RELU, wo, bo};
+                wo += (size_t)planes * 9 * planes; bo += planes;
+                h->ops.push_back(o);
+            } else {
+                if (stride != 2) { delete h; return EC_ERR_SHAPE; }   // (torchvision downsamples exactly where it strides)
+                // conv2 | downsample over K = 9 planes + inplanes: Cin = the concatenated K, N2 = conv2's share (the layout the
+                // K-concatenated convs of the CLIP plan use, so pack_plan_weights builds W_cat and the summed bias)
+                Op o{OP_BTAIL, 1, y, -1, Ro, Ro, 9 * planes + inplanes, planes, 3, 0, EC_ACT_RELU, wo, bo};
+                o.src1 = x;
+                o.N2 = 9 * planes;
+                wo += (size_t)planes * 9 * planes; bo += planes;
+                o.w1_off = wo; o.b1_off = bo;
+                wo += (size_t)planes * inplanes; bo += planes;
+                o.wcat_off = 0;                          // (assigned by pack_plan_weights)
+                h->ops.push_back(o);
+            }
+            track(Ro, Ro, planes);
+            x = y;
+            inplanes = planes;
+            R = Ro;
+        }
+    }
+    h->ops.back().dst = -3;
+    h->out_c = inplanes; h->out_sp = R;
+    h->max_elems_per_frame = mx;
+    h->n_w = wo; h->n_b = bo;
+    if (n_w != wo || n_bias != bo) { delete h; return EC_ERR_SHAPE; }
+    const int rc = pack_plan_weights(h);
+    if (rc != EC_OK) { delete h; return rc; }
+    *out = h;
+    return EC_OK;
+}
 
 extern "C" void ec_rn50_destroy(ec_rn50_t* h) { delete h; }
 extern "C" int ec_rn50_out_channels(const ec_rn50_t* h) { return h ? h->out_c : 0; }
@@ -500,6 +586,23 @@ int rn50_run(const ec_rn50_t* h, const void* rgb, bool u8, const float* mean3, c
                                                  o.W, o.Cin, o.Cout, 1, 0, EC_ACT_RELU, stream);
                     }
                     break;
+                case OP_BTAIL: {
+                    // the one-launch tail where it measured faster than the two launches (profiles/basic_tail_ab.txt): layer2.0
+                    // at every frame count, layer3.0 up to 32 frames.  Deeper-K / larger launches: the downsample conv into
+                    // buffer 3, then conv2 with it as the residual (the 8-wave and ring instances of conv_igemm win there).
+                    const int planes = o.N2 / 9, inplanes = o.Cin - o.N2;
+                    if (planes <= 128 || (planes <= 256 && nb <= 32)) {
+                        rc = ec_basic_tail_s2_bf16(buf(o.src), buf(o.src1), h->wbneck + o.wcat_off, h->bias_cat + o.bcat_off, buf(o.dst), nb,
+                                                   o.H, o.W, planes, inplanes, o.Cout, stream);
+                        break;
+                    }
+                    rc = ec_conv_bf16_s2(buf(o.src1), h->w + o.w1_off, h->bias + o.b1_off, nullptr, buf(3), nb, 2 * o.H, 2 * o.W, inplanes,
+                                         o.Cout, 1, EC_ACT_NONE, stream);
+                    if (rc == EC_OK)
+                        rc = ec_conv_bf16(buf(o.src), h->w + o.w_off, h->bias + o.b_off, buf(3), buf(o.dst), nb, o.H, o.W, planes, o.Cout,
+                                          3, 0, EC_ACT_RELU, stream);
+                    break;
+                }
                 default:
                     if (o.stride == 2) {
                         rc = ec_conv_bf16_s2(buf(o.src), h->w + o.w_off, h->bias + o.b_off, o.res >= 0 ? buf(o.res) : nullptr, buf(o.dst),

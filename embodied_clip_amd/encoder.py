@@ -305,6 +305,48 @@ class ImageNetRN50Trunk(RN50Trunk):
         return super().forward_u8(rgb_u8, out=out, mean=mean, std=std)
 
 
+def pack_tv_basic(sd: Dict[str, torch.Tensor]):
+    """``torchvision.models.resnet18/34().state_dict()`` (``fc.*`` ignored) -> (cfg, stem_w, w, bias) as
+    ``ec_tvresnet_basic_create`` documents: ``pack_tv_resnet``'s layout, per block conv1, conv2, [downsample]."""
+    if any(".conv3." in k for k in sd):
+        raise ValueError("pack_tv_basic: a Bottleneck state dict (conv3 present); use pack_tv_resnet / ImageNetRN50Trunk")
+    return pack_tv_resnet(sd)
+
+
+class ImageNetBasicTrunk(ImageNetRN50Trunk):
+    """Frozen torchvision ResNet-18 / 34 (BasicBlock) without avgpool / fc: the network AllenAct's ``ResNetPreprocessor``
+    runs (``[U] allenact/embodiedai/preprocessors/resnet.py``, ``torchvision_resnet_model=models.resnet18``).
+    ``forward(rgb_nhwc_f32 ImageNet-normalised) -> bf16 [B,7,7,512]``; ``forward_u8`` fuses ToTensor + Normalize(ImageNet)
+    into the stem; ``spatial_mean`` == AdaptiveAvgPool2d(1).  Same executor and handle type as the CLIP trunk."""
+
+    _pack = staticmethod(pack_tv_basic)
+
+    def _create(self, width, layers, input_resolution):
+        if width != 64:
+            raise _lib.EcError("ec_tvresnet_basic_create: the 7x7 stem kernel is built for 64 channels (torchvision resnet18/34)")
+        h = C.c_void_p()
+        arr = (C.c_int * 4)(*layers)
+        _lib.check(self.lib.ec_tvresnet_basic_create(C.byref(h), arr, input_resolution, self.stem_w.data_ptr(), self.w.data_ptr(),
+                                                     self.w.numel(), self.bias.data_ptr(), self.bias.numel()),
+                   "ec_tvresnet_basic_create")
+        return h
+
+
+def basic_tail_s2_bf16(c1, x, w_cat, bias_cat, out=None):
+    """``ec_basic_tail_s2_bf16``: relu(conv3x3(c1) + conv1x1_s2(x) + bias_cat) with w_cat [Cout, 9*planes + inplanes]."""
+    B, Ho, Wo, planes = c1.shape
+    inplanes = x.shape[3]
+    assert x.shape[:3] == (B, 2 * Ho, 2 * Wo) and w_cat.shape[1] == 9 * planes + inplanes
+    Cout = w_cat.shape[0]
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cout), dtype=torch.bfloat16, device=c1.device)
+    lib = _lib.load()
+    with _lib.tensor_guard(c1):
+        _lib.check(lib.ec_basic_tail_s2_bf16(c1.data_ptr(), x.data_ptr(), w_cat.data_ptr(), bias_cat.data_ptr(), out.data_ptr(),
+                                             B, Ho, Wo, planes, inplanes, Cout, _lib.stream_ptr()), "ec_basic_tail_s2_bf16")
+    return out
+
+
 class AttentionPool:
     """[U] CLIP ``AttentionPool2d`` on bf16 NHWC trunk features (the ``clip_pool`` the reference detaches at
     primitive_probing/generate_data/thor_image_features.py:62 and calls at :112)."""

@@ -33,9 +33,16 @@ from . import _lib
 from . import synthetic as syn
 from .dist import (allreduce_flat, check_job_seed, collective_active, gather_actor_counts, global_minibatch_sizes,
                    minibatch_bounds)
-from .encoder import AttentionPool, ClipTextEncoder, RN50Trunk, ViTEmbedder
+from .encoder import AttentionPool, ClipTextEncoder, ImageNetBasicTrunk, ImageNetRN50Trunk, RN50Trunk, ViTEmbedder
 from .policy import PolicyHandle
 from .ppo import FlatAdam, linear_decay_lr, ppo_loss_raw
+
+# encoder name -> (blocks per layer, torchvision block type, trunk class) of the ImageNet-feature agents
+IMAGENET_ENCODERS = {
+    "imagenet_rn18": ((2, 2, 2, 2), "basic", ImageNetBasicTrunk),
+    "imagenet_rn34": ((3, 4, 6, 3), "basic", ImageNetBasicTrunk),
+    "imagenet_rn50": ((3, 4, 6, 3), "bottleneck", ImageNetRN50Trunk),
+}
 
 
 class SyntheticEnv:
@@ -162,6 +169,15 @@ class Worker:
                 pools += [AttentionPool(sd, device=d, weights_from=pools[0] if share else None) for _ in range(ns - 1)]
                 self.trunk_S, self.trunk_C = self.S, self.C
                 self.S, self.C = 1, pools[0].out_dim
+        elif encoder in IMAGENET_ENCODERS:
+            # the ImageNet baselines' torchvision trunks ([U] allenact ResNetPreprocessor: objectnav_robothor_rgb_resnet18gru_ddppo
+            # / ..._resnet50gru_ddppo): ResNet-18 / 34 -> 512 x 7 x 7, ResNet-50 -> 2048 x 7 x 7, same policy and PPO
+            layers, block, cls = IMAGENET_ENCODERS[encoder]
+            sd = encoder_sd if encoder_sd is not None else syn.tv_resnet_state_dict(0, layers=layers, block=block)
+            share = os.environ.get("EC_SHARE_WEIGHTS", "1") != "0"
+            encs = [cls(sd, device=d, chunk=encoder_chunk)]
+            encs += [cls(sd, device=d, chunk=encoder_chunk, weights_from=encs[0] if share else None) for _ in range(ns - 1)]
+            self.S, self.C = encs[0].out_spatial, encs[0].out_channels
         elif encoder == "vit":
             # BASELINE config 3 (builder-defined fusion, SURVEY.md §8d note): ClipViTEmbedder tokens, CLS dropped,
             # the 49 patch tokens are the 7x7 channels-last "feature map" [n,49,768] of the goal encoder
@@ -330,7 +346,7 @@ class Worker:
         if self.zeroshot:
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.trunk_out)
             sl.pool.forward(sl.trunk_out, sl.feat[t].view(sl.n, self.C))     # AttentionPool2d -> rollout slice
-        elif self.encoder in ("rn50", "rn50x16"):
+        elif self.encoder in ("rn50", "rn50x16") or self.encoder in IMAGENET_ENCODERS:
             # the last conv writes straight into the rollout slice
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.feat[t])
         else:

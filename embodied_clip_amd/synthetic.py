@@ -153,11 +153,17 @@ IMAGENET_RGB_STDS = (0.229, 0.224, 0.225)
 
 
 def tv_resnet_state_dict(seed: int = 0, width: int = 64, layers: Sequence[int] = (3, 4, 6, 3),
-                         with_fc: bool = False) -> "OrderedDict[str, torch.Tensor]":
+                         with_fc: bool = False, block: str = "bottleneck") -> "OrderedDict[str, torch.Tensor]":
     """Synthetic ``torchvision.models.resnet50().state_dict()`` (the network behind ``imagenet_conv`` /
     ``imagenet_avgpool``: primitive_probing/generate_data/thor_image_features.py:46-49).  Key layout: ``conv1.weight``
     [w,3,7,7], ``bn1.*``, ``layer{1..4}.{b}.conv{1,2,3}.weight`` / ``bn{1,2,3}.*`` / ``downsample.{0,1}.*`` (+ ``fc.*``
-    with ``with_fc``; the reference drops avgpool and fc).  ResNet-50: 23,508,032 parameters without fc."""
+    with ``with_fc``; the reference drops avgpool and fc).  ResNet-50: 23,508,032 parameters without fc.
+    ``block="basic"``: torchvision's BasicBlock networks instead (``resnet18`` with layers (2, 2, 2, 2), ``resnet34`` with
+    (3, 4, 6, 3)): per block ``conv1`` 3x3 (stride 2 in the first block of layers 2-4), ``conv2`` 3x3, a 1x1 stride-2
+    ``downsample`` where the shape changes, expansion 1."""
+    if block == "basic":
+        return _tv_basic_state_dict(seed, width, layers, with_fc)
+    assert block == "bottleneck", block
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     _conv(sd, seed, "tv.conv1.weight", width, 3, 7)
     sd["conv1.weight"] = sd.pop("tv.conv1.weight")
@@ -178,6 +184,31 @@ def tv_resnet_state_dict(seed: int = 0, width: int = 64, layers: Sequence[int] =
                 _conv(sd, seed, p + ".downsample.0.weight", planes * 4, inplanes, 1)
                 _bn(sd, seed, p + ".downsample.1", planes * 4, gamma_scale=0.7)
             inplanes = planes * 4
+    if with_fc:
+        sd["fc.weight"] = _normal(seed, "fc.weight", (1000, inplanes), inplanes ** -0.5)
+        sd["fc.bias"] = _normal(seed, "fc.bias", (1000,), 0.01)
+    return sd
+
+
+def _tv_basic_state_dict(seed, width, layers, with_fc):
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    _conv(sd, seed, "tv.conv1.weight", width, 3, 7)
+    sd["conv1.weight"] = sd.pop("tv.conv1.weight")
+    _bn(sd, seed, "bn1", width)
+    inplanes = width
+    for li, (nblocks, mult) in enumerate(zip(layers, (1, 2, 4, 8)), start=1):
+        planes = width * mult
+        for b in range(nblocks):
+            stride = 2 if (b == 0 and li > 1) else 1
+            p = f"layer{li}.{b}"
+            _conv(sd, seed, p + ".conv1.weight", planes, inplanes, 3)
+            _bn(sd, seed, p + ".bn1", planes)
+            _conv(sd, seed, p + ".conv2.weight", planes, planes, 3)
+            _bn(sd, seed, p + ".bn2", planes, gamma_scale=0.3)          # damped residual branch
+            if stride > 1 or inplanes != planes:
+                _conv(sd, seed, p + ".downsample.0.weight", planes, inplanes, 1)
+                _bn(sd, seed, p + ".downsample.1", planes, gamma_scale=0.7)
+            inplanes = planes
     if with_fc:
         sd["fc.weight"] = _normal(seed, "fc.weight", (1000, inplanes), inplanes ** -0.5)
         sd["fc.bias"] = _normal(seed, "fc.bias", (1000,), 0.01)

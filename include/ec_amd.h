@@ -196,6 +196,15 @@ int ec_conv3x3_img_bf16_ld(const void* in, const void* packed, const float* bias
  * even); w bf16 [Cout][k*k*Cin]; res / out bf16 [B,H/2,W/2,Cout].  Cin % 8 == 0, Cout % 64 == 0; act NONE or RELU. */
 int ec_conv_bf16_s2(const void* in, const void* w, const float* bias, const void* res, void* out, int B, int H, int W,
                     int Cin, int Cout, int ksize, int act, ec_stream_t stream);
+/* torchvision BasicBlock transition tail (ResNet-18 / 34, first block of layers 2-4) in ONE launch:
+ *   out = relu(conv3x3(c1) + conv1x1_stride2(x) + bias_cat)
+ * as one implicit GEMM over K = 9*planes + inplanes (conv_basic.hip).  c1 bf16 [B,Ho,Wo,planes] (conv1's output),
+ * x bf16 [B,2Ho,2Wo,inplanes] (the block input), w_cat bf16 [Cout][9*planes + inplanes] = [conv2 (ky,kx,ci) | downsample
+ * (ci)] with BN folded, bias_cat f32 [Cout] = b2 + bd; out bf16 [B,Ho,Wo,Cout], rounded once.  planes, inplanes and
+ * Cout are multiples of 64.  Replaces conv2 + bn2 + downsample + `out += identity` + relu of [U] torchvision
+ * models/resnet.py BasicBlock.forward. */
+int ec_basic_tail_s2_bf16(const void* c1, const void* x, const void* w_cat, const float* bias_cat, void* out, int B, int Ho,
+                          int Wo, int planes, int inplanes, int Cout, ec_stream_t stream);
 /* conv1 (7x7, stride 2, pad 3, 3 -> 64) + bn1 (folded) + ReLU + MaxPool2d(3, 2, 1) in one launch (the conv output never
  * touches HBM).  rgb: fp32 NHWC [B,H,W,3], ImageNet-normalised (u8 == 0), or raw uint8 NHWC with ToTensor +
  * Normalize(mean, std) of `resnet_preprocess` (thor_image_features.py:36-44) fused (u8 == 1; h_mean3 / h_std3 HOST
@@ -246,6 +255,13 @@ int ec_rn50_create(ec_rn50_t** out, int width, const int* layers4, int input_res
  * (thor_image_features.py:105,130) before its `.float()` / NCHW view. */
 int ec_rn50tv_create(ec_rn50_t** out, const int* layers4, int input_resolution, const void* stem_w_bf16,
                      const void* w_bf16, size_t n_w, const float* bias, size_t n_bias);
+/* The torchvision BasicBlock ResNet trunk (ResNet-18: layers4 = 2,2,2,2; ResNet-34: 3,4,6,3) behind the same handle
+ * type: every ec_rn50_* function below applies.  stem_w_bf16 as for ec_rn50tv_create; `w_bf16` / `bias` hold per block
+ * conv1, conv2, [downsample] (bias: stem first), BN folded.  ResNet-18 at 224: 11,157,504 weights + the stem's 9,408,
+ * 4,800 biases.  Output bf16 NHWC [B,R/32,R/32,512] == `Sequential(*list(resnet18().children())[:-2])` before the
+ * NCHW view ([U] allenact embodiedai/preprocessors/resnet.py ResNetEmbedder with pool=False). */
+int ec_tvresnet_basic_create(ec_rn50_t** out, const int* layers4, int input_resolution, const void* stem_w_bf16,
+                             const void* w_bf16, size_t n_w, const float* bias, size_t n_bias);
 void ec_rn50_destroy(ec_rn50_t* h);
 size_t ec_rn50_workspace_bytes(const ec_rn50_t* h, int batch);
 int ec_rn50_out_channels(const ec_rn50_t* h);
