@@ -36,6 +36,7 @@ SIGNATURES = {
     "ec_clip_resize_table_ints": (c_size_t, [c_int, c_int, c_int]),
     "ec_clip_resize_table": (c_int, [c_int, c_int, c_int, c_void_p, c_size_t]),
     "ec_clip_resize_crop_u8": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ec_semantic_labels_u8": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "ec_gemm_bf16": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "ec_split3_bf16": (c_int, [c_void_p] * 2 + [C.c_long, c_int, c_void_p]),
     "ec_gemm_bf16a_x3": (c_int, [c_void_p] * 4 + [C.c_long, c_int, c_int, c_int, c_void_p]),

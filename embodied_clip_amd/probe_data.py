@@ -15,8 +15,9 @@ The encoders run on the MI355X: CLIP -- ``RN50Trunk.forward_u8`` with the CLIP n
 thor_image_features.py:111-113); ImageNet -- ``ImageNetRN50Trunk.forward_u8`` (torchvision ResNet-50 minus avgpool / fc,
 ImageNet mean / std fused into its 7x7 stem; the reference runs this tower in fp32, here bf16 storage with fp32
 accumulation like every other conv of the path).  Both share ONE Pillow-exact Resize(224, BICUBIC) + CenterCrop(224) pass
-over the raw frame (``resnet_preprocess`` and ``clip_preprocess`` apply the same geometry, :36-39,108).  Out of scope
-here: rendering / semantic-mask labelling (thor_frames.py, thor_image_features.py:70-127 -- simulator + numpy data prep).
+over the raw frame (``resnet_preprocess`` and ``clip_preprocess`` apply the same geometry, :36-39,108).  The labels of
+thor_image_features.py:70-127 come from ``probe_labels`` (semantic frame -> presence / localisation on the GPU) and the
+scene files are walked by the ``probe_extract`` CLI.  Out of scope here: rendering (thor_frames.py -- the simulator).
 
 Reader == ``primitive_probing/data.py:9-47`` (``THOREmbeddingsDataset``) and the DataLoader collate of
 ``THOREmbeddingsDataModule`` (data.py:50-88) without pytorch-lightning.
@@ -124,8 +125,11 @@ def build_reachable_features(extractor, images: Dict[str, torch.Tensor]) -> Dict
 
 
 def write_reachable_cache(output_dir: str, image_features, split_triples: Dict[str, Sequence[Tuple[str, int, bool]]]):
+    """``image_features`` None: only the ``reachable_{split}.pkl`` files (the two halves come from two scripts of the
+    reference, reachable_image_features.py and reachable_metadata.py, and ``probe_extract`` keeps them apart)."""
     os.makedirs(output_dir, exist_ok=True)
-    torch.save(image_features, os.path.join(output_dir, "reachable_image_features.pt"))
+    if image_features is not None:
+        torch.save(image_features, os.path.join(output_dir, "reachable_image_features.pt"))
     for split, triples in split_triples.items():
         with open(os.path.join(output_dir, f"reachable_{split}.pkl"), "wb") as f:
             pickle.dump(list(triples), f)

@@ -103,6 +103,22 @@ int ec_clip_resize_table(int H, int W, int n_px, int* host_table, size_t n_ints)
 int ec_clip_resize_crop_u8(const uint8_t* frames_u8, const int* table_dev, int table_max_rows, uint8_t* out_u8, int B,
                            int H, int W, int n_px, ec_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Probe labels from the simulator's semantic-segmentation frame (labels.hip).  Replaces the numpy labelling of
+ * primitive_probing/generate_data/thor_image_features.py:71-88,115-127: `class_mask` (all three channels equal the
+ * class colour; a class without a colour has an empty mask, :72-73), `obj_presence` over the whole frame (:122) and
+ * over the nine `grid_bboxes` cells (:80-88,123-127; cell (i, j) = rows [floor(i*H/3), floor((i+1)*H/3)), columns
+ * likewise).
+ *   sem_u8       uint8 [B, H, W, 3]   point['semantic_frame']
+ *   colors_u8    uint8 [B, C, 4]      r, g, b, valid per target class of THAT frame (object_id_to_color is stored per
+ *                                     point, :118); valid == 0: the class has no colour.  Classes may share a colour.
+ *   presence     int64 [B, C]         0 / 1
+ *   localization int64 [B, 9, C]      0 / 1, cells row-major over (y, x)
+ * Integer equality throughout: exact, and independent of how frames are batched.  Each frame is read once; any byte
+ * alignment of the frames.  EC_ERR_SHAPE unless 1 <= C <= 64, H >= 3, W >= 3, 1 <= B <= 65535. */
+int ec_semantic_labels_u8(const uint8_t* sem_u8, const uint8_t* colors_u8, int64_t* presence, int64_t* localization,
+                          int B, int H, int W, int C, ec_stream_t stream);
+
 
 /* out[M, N] (fp32) = act(A[M, K] (bf16) @ W^T + bias), W an fp32 [N, K] matrix handed over as the three bf16 planes
  * ec_split3_bf16 writes ([N][3][K]): the exact-fp32 product of stored bf16 features with fp32 weights -- the first
