@@ -22,17 +22,10 @@
 
 #include "common.h"
 
-extern "C" int ec_dw_tn_x3_splits(long M, int NX);
-extern "C" int ec_dw_tn_x3(const void* dYplanes, const void* X, float* part, float* dW, long M, int NX, ec_stream_t stream);
+// C++-linkage internals of the library (every extern "C" entry this file calls is declared in include/ec_amd.h, via common.h)
 int ec_dw_tn_xp(const void* dYplanes, const void* X, float* part, float* dW, long M, int NX, int planes, ec_stream_t stream);   // dw_tn.hip
 int ec_gemm_bf16a_xp(const void* A, const void* Wplanes, const float* bias, float* out, long M, int N, int K, int act, int planes,
                      ec_stream_t stream);                                                                                        // conv_igemm.hip
-extern "C" int ec_split3_bf16(const float* W, void* planes, long rows, int K, ec_stream_t stream);
-extern "C" int ec_gemm_bf16a_x3(const void* A, const void* Wplanes, const float* bias, float* out, long M, int N, int K,
-                                int act, ec_stream_t stream);
-extern "C" int ec_gemm_f32(const void* A, const void* B, float* Cp, int M, int N, int K, long sam, long sak, long sbk,
-                           long sbn, int ldc, int flags, const float* bias, const float* gbias, const int* gidx,
-                           int group, const float* dmask, const float* rowscale, int splitk, ec_stream_t stream);
 
 namespace {
 
@@ -1382,82 +1375,17 @@ struct ec_policy {
     ec_policy_cfg c;
     size_t off[P_COUNT], num[P_COUNT], total;
     const float* goal_table = nullptr;   // fusion == 1: borrowed f32 [num_goals, in_channels]
-    // EC_POLICY_INFER_REUSE bookkeeping: which (T, N, feature dtype) the weight-derived tables in a given act workspace were
-    // built for.  The tables' offsets and WHICH of them exist (E1, W1's planes in fragment order, the re-ordered weight_ih and
-    // its fragment-order copy) follow from exactly these three values, so a REUSE call with another geometry or dtype than the
-    // call that built them (fp32 features first, bf16 next) rebuilds instead of reading uninitialised tables.
-    struct Built { int T, N, bf16; };
+    // EC_POLICY_INFER_REUSE bookkeeping: the key of the launch plan (make_plan) that built the weight-derived tables in a given
+    // act workspace.  Which tables exist and where (E1, W1's planes in fragment order, the re-ordered weight_ih and its
+    // fragment-order copy) are plan fields, and an inference plan is a function of exactly (handle, T, N, feature dtype): a
+    // REUSE call whose plan has another key (fp32 features first, bf16 next; another N) rebuilds instead of reading
+    // uninitialised tables.
+    struct Built { int T, N, bf16; bool operator==(const Built&) const = default; };
     mutable std::mutex tables_mu;
     mutable std::unordered_map<const void*, Built> tables;
 };
 
 namespace {
-
-struct Ws {   // float offsets into the workspace
-    size_t E1, c1, c2, m1, x4, x, gi, gh, gates, hn, hp, hs, goal32, w1p;
-    size_t E1d, c1d, c2d, m1d, x4d;   // the depth stream's copies (dual encoder)
-    size_t wihA;                      // act step: weight_ih in pixel-major column order (valid while E1 is)
-    size_t wihF, w1pF;                // ... and the same / W1's planes in MFMA-FRAGMENT order for gi_act_kernel / c1_act_kernel
-    size_t dhs, dhc, dgi, dghb, dx, dx4, dm1, dc2, dc1, dE1, tpart, tpartE, whhT, wihP, gwihP, tA, tB, end;
-};
-
-Ws layout(const ec_policy* h, int T, int N, bool bwd) {
-    const ec_policy_cfg& c = h->c;
-    const size_t B = (size_t)T * N, S = (size_t)c.spatial * c.spatial, M49 = c.fusion ? 0 : B * S, H = c.hidden;
-    const size_t nstream = (c.dual && !c.fusion) ? 2 : 1;
-    const size_t flat = c.fusion ? (size_t)c.in_channels : nstream * c.comb_out * S;
-    Ws w; size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o += al(n * 4) / 4; return r; };
-    w.E1 = take((size_t)c.num_goals * c.comb_hid);
-    // small launches (the act step): room for the split-K partial matrices of c1 and gi (see ec_policy_forward)
-    const size_t parts = (M49 > 0 && M49 <= (size_t)ACT_MAX_ROWS) ? ACT_PARTS : 1;
-    w.c1 = take(M49 * c.compress_hid * parts);
-    w.c2 = take(M49 * c.compress_out);
-    w.m1 = take(M49 * c.comb_hid);
-    w.x4 = take(M49 * c.comb_out);
-    w.E1d = w.c1d = w.c2d = w.m1d = w.x4d = o;
-    if (nstream == 2) {
-        w.E1d = take((size_t)c.num_goals * c.comb_hid);
-        w.c1d = take(M49 * c.compress_hid * parts);
-        w.c2d = take(M49 * c.compress_out);
-        w.m1d = take(M49 * c.comb_hid);
-        w.x4d = take(M49 * c.comb_out);
-    }
-    w.x = take(B * flat);
-    w.gi = take(B * 3 * H * parts);
-    w.gh = take((size_t)N * 3 * H);
-    w.gates = take(B * 3 * H);
-    w.hn = take(B * H);
-    w.hp = take(B * H);
-    w.hs = take(B * H);
-    w.goal32 = take(B);
-    w.w1p = take(c.fusion ? 0 : ((size_t)c.compress_hid * 3 * c.in_channels + 1) / 2);   // W1 as three bf16 planes
-    w.wihA = take((c.fusion || c.dual) ? 0 : 3 * H * flat);
-    w.wihF = take((c.fusion || c.dual) ? 0 : 3 * H * flat);
-    w.w1pF = take(c.fusion ? 0 : ((size_t)c.compress_hid * 3 * c.in_channels + 1) / 2);
-    w.dhs = w.dhc = w.dgi = w.dghb = w.dx = w.dx4 = w.dm1 = w.dc2 = w.dc1 = w.dE1 = w.tpart = w.tpartE = w.whhT = w.wihP = w.gwihP = w.tA = w.tB = o;
-    if (bwd) {
-        w.dhs = take(B * H);
-        w.dhc = take((size_t)N * H);
-        w.dgi = take(B * 3 * H);
-        w.dghb = take(B * 3 * H);
-        w.dx = take(B * flat);
-        w.dx4 = take(M49 * c.comb_out);
-        w.dm1 = take(M49 * c.comb_hid);
-        w.dc2 = take(M49 * c.compress_out);
-        w.dc1 = take(M49 * c.compress_hid * 3 / 2 + 4);   // fp32 [M49][hid], or its three bf16 planes [M49][3][hid]
-        w.dE1 = take((size_t)c.num_goals * c.comb_hid);
-        w.tpart = take(c.fusion ? 0 : (size_t)TB_MAX_WG * 4 * TB_PART);              // tail_bwd_kernel's partial sets
-        w.tpartE = take(c.fusion ? 0 : (size_t)TB_MAX_WG * 4 * c.num_goals * 128);   // ... and its per-wave dE1 tables
-        w.whhT = take(H * 3 * H);                                                       // W_hh^T (fused backward step)
-        w.wihP = take(c.fusion ? 0 : 3 * H * flat);                                     // weight_ih in pixel-major column order (EC_WIH_PERM)
-        w.gwihP = take(c.fusion ? 0 : 3 * H * flat);                                    // ... and its gradient
-        w.tA = take(B * 3 * H);                                                         // transposed operands of the GRU's weight-gradient GEMMs
-        w.tB = take(B * (flat > H ? flat : H));
-    }
-    w.end = o;
-    return w;
-}
 
 int pick_splitk(long M, long N, long K) {
     const long tiles = ((M + 127) / 128) * ((N + 127) / 128);
@@ -1561,6 +1489,568 @@ int step_splitk(long M, long N, long K) {
 
 #define RC(x) do { int rc__ = (x); if (rc__ != EC_OK) return rc__; } while (0)
 
+// ---- the launch plan --------------------------------------------------------------------------------------------------------
+// Every size and every path decision of one entry-point call, made ONCE (make_plan) from the handle, (T, N), the mode and the
+// feature dtype.  The workspace layout, the forward and the backward all read this one value, so they cannot disagree about how
+// large an area is or which kernel wrote it.  A stack value: building it allocates nothing and takes no lock (it sits on the
+// act step's serial launch chain).
+constexpr size_t LDS_LIMIT = 160 * 1024;      // dynamic LDS a workgroup may ask for
+
+struct Geo {
+    int T, N, B;                  // B = T * N rows through the GRU and the heads
+    int S, M49;                   // pixels per frame; B * S rows through compressor and combiner (0 in fusion mode)
+    int H, A, A1, C, cat;         // hidden size; actions, actions + critic; feature channels; compress_out + goal_dims
+    int nstream, flat1, flat;     // encoder streams (2: dual RGB + depth); one stream's / the whole GRU input width
+};
+
+struct Ws {   // float offsets into the workspace
+    struct Stream { size_t E1, c1, c2, m1, x4; } st[2];   // per encoder stream ([1]: the dual encoder's depth stream)
+    size_t x, gi, gh, gates, hn, hp, hs, goal32, w1p;
+    // act step: weight_ih in pixel-major column order (valid while E1 is); the same / W1's planes in MFMA-FRAGMENT order (gi_act_kernel / c1_act_kernel)
+    size_t wihA, wihF, w1pF;
+    size_t dhs, dhc, dgi, dghb, dx, dx4, dm1, dc2, dc1, dE1, tpart, tpartE, whhT, wihP, gwihP, tA, tB, end;
+};
+
+enum class C1 { pingpong, act_kernel, split_parts, plain };      // compressor conv 1
+enum class Gi { act7, act8, split_parts, plain };                // GRU input projection (act7 / act8: gi_act_kernel<7 | 8>)
+enum class Wih { plain, perm_learn, perm_act };                  // weight_ih as stored / re-ordered per learn pass / per act-table build
+enum class Step { gemm_gates, fused32, fused16 };                // a recurrence step: GEMM + gate kernel / 32-tile / 16-tile fused kernel
+
+struct Plan {
+    Geo g;
+    bool infer, feat_bf16;        // infer: EC_POLICY_INFER or _REUSE (stated by the caller, never inferred from the workspace size)
+    ec_policy::Built key;         // what a REUSE call must match
+    int act_parts;                // partial matrices the c1 / gi areas hold: ACT_PARTS for the act step's few rows, else 1
+    C1 c1; int c1_mblk, c1_fold;  // c1_act_kernel's <MBLK, U> variant; partial matrices of c1 the fused tail folds
+    int planes;                   // bf16 planes of the fp32 operand in the compressor conv and its weight gradient (EC_POLICY_FAST: 2 of 3)
+    bool tail_fwd, tail_bwd;      // EC_TAIL_FUSED: c2 / m1 / x4 in one pass over c1, and its backward
+    size_t tail_fwd_lds, tail_bwd_lds;
+    Wih wih; bool goal_direct;    // the fused tail reads the low words of the int64 goal ids itself: no conversion launch
+    Gi gi; int gi_fold;           // partial matrices of gi the step kernel folds
+    Step step_fwd, step_bwd; size_t gru_lds;   // (gru_step_fwd_kernel's tiles)
+    bool hs_direct;               // T == 1 inference: the new state goes straight to h_final, the heads read it there
+    bool dw_t, dw1_planes;        // EC_DW_TRANSPOSED; EC_DW1_TR (dc1 then only exists as bf16 planes)
+    int bwd3;                     // EC_GEMM_3PRODUCTS or 0 for the backward's large gradient GEMMs
+    Ws w;
+};
+
+Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
+    const size_t B = g.B, M49 = g.M49, H = g.H, N = g.N, flat = g.flat, E1 = (size_t)c.num_goals * c.comb_hid;
+    const size_t w1planes = c.fusion ? 0 : ((size_t)c.compress_hid * 3 * c.in_channels + 1) / 2;   // W1 as three bf16 planes
+    const size_t wih = c.fusion ? 0 : 3 * H * flat;                                                  // a re-ordered copy of weight_ih
+    Ws w; size_t o = 0;
+    auto take = [&](size_t n) { size_t r = o; o += al(n * 4) / 4; return r; };
+    auto take_if = [&](bool on, size_t n) { return take(on ? n : 0); };   // an area that is not needed: empty, at the running offset
+    for (int i = 0; i < 2; ++i) {
+        const bool on = i < g.nstream;
+        w.st[i].E1 = take_if(on, E1);
+        w.st[i].c1 = take_if(on, M49 * c.compress_hid * parts);   // the act step: room for the split-K partial matrices of c1 (and of gi below)
+        w.st[i].c2 = take_if(on, M49 * c.compress_out);
+        w.st[i].m1 = take_if(on, M49 * c.comb_hid);
+        w.st[i].x4 = take_if(on, M49 * c.comb_out);
+    }
+    w.x = take(B * flat);
+    w.gi = take(B * 3 * H * parts);
+    w.gh = take(N * 3 * H);
+    w.gates = take(B * 3 * H);
+    w.hn = take(B * H); w.hp = take(B * H); w.hs = take(B * H);
+    w.goal32 = take(B);
+    w.w1p = take(w1planes);
+    w.wihA = take_if(!c.dual, wih); w.wihF = take_if(!c.dual, wih);
+    w.w1pF = take(w1planes);
+    // what only the learn pass and its backward need
+    w.dhs = take_if(bwd, B * H);
+    w.dhc = take_if(bwd, N * H);
+    w.dgi = take_if(bwd, B * 3 * H); w.dghb = take_if(bwd, B * 3 * H);
+    w.dx = take_if(bwd, B * flat);
+    w.dx4 = take_if(bwd, M49 * c.comb_out);
+    w.dm1 = take_if(bwd, M49 * c.comb_hid);
+    w.dc2 = take_if(bwd, M49 * c.compress_out);
+    w.dc1 = take_if(bwd, M49 * c.compress_hid * 3 / 2 + 4);   // fp32 [M49][hid], or its three bf16 planes [M49][3][hid]
+    w.dE1 = take_if(bwd, E1);
+    w.tpart = take_if(bwd && !c.fusion, (size_t)TB_MAX_WG * 4 * TB_PART);              // tail_bwd_kernel's partial sets
+    w.tpartE = take_if(bwd && !c.fusion, (size_t)TB_MAX_WG * 4 * c.num_goals * 128);   // ... and its per-wave dE1 tables
+    w.whhT = take_if(bwd, H * 3 * H);                                                     // W_hh^T (fused backward step)
+    w.wihP = take_if(bwd, wih); w.gwihP = take_if(bwd, wih);                              // weight_ih in pixel-major column order (EC_WIH_PERM) and its gradient
+    w.tA = take_if(bwd, B * 3 * H);                                                       // transposed operands of the GRU's weight-gradient GEMMs
+    w.tB = take_if(bwd, B * (flat > H ? flat : H));
+    w.end = o;
+    return w;
+}
+
+// The one reader of ec_config() in this file, and the one place a path predicate is written.  `mode`: EC_POLICY_LEARN / _INFER /
+// _INFER_REUSE; the backward builds the plan of the learn-pass forward whose workspace it reads.
+Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
+    const ec_policy_cfg& c = h->c;
+    const EcConfig& cfg = ec_config();
+    Plan p;
+    Geo& g = p.g;
+    g.T = T; g.N = N; g.B = T * N;
+    g.S = c.spatial * c.spatial; g.M49 = c.fusion ? 0 : g.B * g.S;
+    g.H = c.hidden; g.A = c.num_actions; g.A1 = g.A + 1; g.C = c.in_channels; g.cat = c.compress_out + c.goal_dims;
+    g.nstream = (c.dual && !c.fusion) ? 2 : 1; g.flat1 = c.comb_out * g.S; g.flat = c.fusion ? c.in_channels : g.nstream * g.flat1;
+    const int B = g.B, S = g.S, M49 = g.M49, H = g.H, C = g.C, flat = g.flat;
+    p.infer = mode != EC_POLICY_LEARN; p.feat_bf16 = feat_bf16;
+    p.key = ec_policy::Built{T, N, feat_bf16 ? 1 : 0};
+    // Act step: so few rows that the two long-K, small-M GEMMs (compressor conv 1, GRU input projection) run as ACT_PARTS K
+    // slices whose partial matrices the consuming kernels fold in a fixed order (no float atomics: rollouts stay bit-reproducible)
+    const bool small = M49 > 0 && M49 <= ACT_MAX_ROWS;
+    p.act_parts = small ? ACT_PARTS : 1;
+    const bool act_on = cfg.act_split && p.infer && small;
+    // EC_TAIL_FUSED (default 1): the fused tail kernels are written for the reference's widths
+    const bool tail_widths = cfg.tail_fused && !c.fusion && c.compress_hid == 128 && c.compress_out == 32 && c.comb_hid == 128 && c.comb_out == 32;
+    p.tail_fwd_lds = ((size_t)2 * 32 * TL_P128 + 128 * TL_P32 + (size_t)c.num_goals * 128 + 64 + 4 * (size_t)(32 * TL_P128 + 32 * TL_P32)) * sizeof(float);
+    p.tail_fwd = tail_widths && p.tail_fwd_lds <= LDS_LIMIT;
+    p.tail_bwd_lds = ((size_t)2 * 128 * TL_P32 + 32 * TL_P128 + std::max<size_t>((size_t)c.num_goals * 128, 4 * 256) +
+                      4 * (size_t)(32 * TL_P128 + 32 * TL_P32)) * sizeof(float);   // (the sE area: four wave-private 256-float lines)
+    p.tail_bwd = tail_widths && S >= 32 && p.tail_bwd_lds <= LDS_LIMIT && c.num_goals <= TB_MAXG;
+    p.goal_direct = p.infer && p.tail_fwd; p.hs_direct = p.infer && T == 1;
+    // EC_WIH_PERM: the GRU's input projection reads the combiner output where it lies (pixel-major rows) against a re-ordered weight_ih
+    // (permute_row_kernel, one row in LDS), no activation transposes.  Learn pass: per call; act step: by the first call after a parameter
+    // update, kept in the workspace like E1
+    const bool wih_ok = cfg.wih_perm && !c.fusion && !c.dual && (size_t)c.comb_out * S * 4 <= 64 * 1024;
+    p.wih = !wih_ok ? Wih::plain : !p.infer ? Wih::perm_learn : p.tail_fwd ? Wih::perm_act : Wih::plain;
+    // Compressor conv 1.  EC_C1_PINGPONG (default 1): bf16 features x fp32 W1 as bf16 planes on the 8-wave ping-pong kernel
+    // (conv_igemm8, X3 mode) once there are enough 256-row tiles to fill the chip.  EC_POLICY_FAST: its two leading planes (16
+    // mantissa bits) instead of all three, a third fewer MFMAs in a launch that is MFMA-bound; learn pass only (the conv and
+    // its weight gradient), the act step stays exact
+    const bool c1_split = act_on && p.tail_fwd && (C % 32) == 0 && C / 32 >= ACT_PARTS;
+    if (cfg.c1_pingpong && feat_bf16 && c.compress_hid % 128 == 0 && C % 64 == 0 && M49 >= 256 * 128) p.c1 = C1::pingpong;
+    else if (c1_split && feat_bf16 && !c.dual && (C % 128) == 0 && (c.compress_hid % 32) == 0) p.c1 = C1::act_kernel;
+    else p.c1 = c1_split ? C1::split_parts : C1::plain;
+    p.c1_mblk = M49 <= 2048 ? 1 : (M49 <= 4096 ? 2 : 4); p.c1_fold = p.c1 == C1::split_parts ? ACT_PARTS : 1;
+    p.planes = (cfg.policy_fast && !p.infer) ? 2 : 3;
+    // EC_GRU_FUSED (default 2): one fused launch per step where the geometry allows (forward: H % 32 == 0 and the tiles fit
+    // the LDS; backward: H % 256 == 0, T > 1).  The update's recurrences at H == 512 run the 16 x 16-tile kernels, one workgroup
+    // per CU with 140 KB of LDS; the act step keeps the 66-KB kernel, which co-resides with the other actor slice's encoder
+    p.gru_lds = std::max((size_t)2 * 32 * (((H & 255) == 0 ? 256 : H) + 4) * sizeof(float),      // operand tiles (K chunk) ...
+                         (size_t)4 * 32 * 32 * sizeof(float));                                   // ... reused for the 4 partial tiles
+    const bool step_ok = cfg.gru_fused && (H % 32) == 0 && p.gru_lds <= LDS_LIMIT;
+    const Step fused = (cfg.gru_fused >= 2 && H == 512 && !p.infer) ? Step::fused16 : Step::fused32;
+    p.step_fwd = step_ok ? fused : Step::gemm_gates;
+    p.step_bwd = (cfg.gru_fused && (H % 256) == 0 && T > 1) ? fused : Step::gemm_gates;
+    // GRU input projection.  Act step with a handful of rows: one launch, K split over the waves of a workgroup and folded
+    // in-kernel (gi_act_kernel); else split-K only as separate partial matrices folded by the step kernel
+    const int gi_nw = (flat % 56 == 0) ? 7 : ((flat % 64 == 0) ? 8 : 0);
+    if (cfg.act_split && p.wih == Wih::perm_act && T == 1 && B <= 256 && gi_nw != 0 && (3 * H) % 32 == 0) p.gi = gi_nw == 7 ? Gi::act7 : Gi::act8;
+    else p.gi = (act_on && step_ok && (flat + 31) / 32 >= ACT_PARTS) ? Gi::split_parts : Gi::plain;
+    p.gi_fold = p.gi == Gi::split_parts ? ACT_PARTS : 1;
+    // EC_GEMM_BWD3 / EC_POLICY_FAST: the large gradient GEMMs (weight gradients over all T*N rows, dx = dgi @ W_ih) on the three
+    // leading products of the bf16x3 split (relative product error 2^-16; gradients agree with the fp32 oracle to ~1e-5, not ~1e-6)
+    p.bwd3 = (cfg.gemm_bwd3 || cfg.policy_fast) ? EC_GEMM_3PRODUCTS : 0;
+    // EC_DW_TRANSPOSED (default 1): the GRU's two weight-gradient GEMMs contract over the T*N rows, i.e. BOTH operands are strided in K, the
+    // slowest staging of gemm_x3 (1.02 ms for dW_ih at 128 actors, 0.49 ms for the same-size input projection); transposed first (~0.1 ms)
+    p.dw_t = cfg.dw_transposed && B >= 1024;
+    // EC_DW1_TR (default 1): dW1 through the transpose-read kernel (dw_tn.hip), its partial tiles in the tail's partial sets
+    p.dw1_planes = p.tail_bwd && cfg.dw1_tr && feat_bf16 && C % 256 == 0 && M49 >= 2048 &&
+                   (size_t)ec_dw_tn_x3_splits(M49, C) * 128 * C <= (size_t)TB_MAX_WG * 4 * TB_PART;
+    p.w = layout(c, g, p.act_parts, mode == EC_POLICY_LEARN);
+    return p;
+}
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for a kernel that asks for more than 64 KB: once per device (ec_attr_needed)
+template <auto Kernel>
+void allow_big_lds() {
+    static std::atomic<uint64_t> done{0};
+    if (auto guard = ec_attr_needed(done))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
+}
+
+// One entry-point call: the plan and the caller's buffers.  The stages of the forward (Fwd) and of the backward (Bwd) are
+// members: each a linear list of launches that switches on plan fields only.
+struct Ctx {
+    const ec_policy* h; const ec_policy_cfg& c;
+    const Plan& p; const Geo& g; const Ws& w;      // (g, w: the plan's)
+    const float* params;
+    float* ws;
+    ec_stream_t stream; hipStream_t s;             // (one stream, under both of its types)
+    Ctx(const ec_policy* h_, const Plan& p_, const float* params_, void* workspace, ec_stream_t stream_)
+        : h(h_), c(h_->c), p(p_), g(p_.g), w(p_.w), params(params_), ws((float*)workspace), stream(stream_), s((hipStream_t)stream_) {}
+    // stream 1 (the dual encoder's depth stream) has its own compressor / combiner tensors
+    size_t off(int i, int sidx = 0) const { return h->off[(sidx && i >= P_W1 && i <= P_B4) ? i + (P_W1D - P_W1) : i]; }
+    const float* W(int i, int sidx = 0) const { return params + off(i, sidx); }
+    // ec_gemm_f32 without its extras (row-group bias, ReLU mask, row scale, split-K)
+    int gemm(const void* A, const void* B, float* Cp, int M, int N, int K, long sam, long sak, long sbk, long sbn, int ldc, int flags = 0,
+             const float* bias = nullptr) const {
+        return ec_gemm_f32(A, B, Cp, M, N, K, sam, sak, sbk, sbn, ldc, flags, bias, nullptr, nullptr, 0, nullptr, nullptr, 1, stream);
+    }
+};
+
+struct Fwd : Ctx {
+    using Ctx::Ctx;
+    const int* goal_ids = nullptr;   // int32 ids in the workspace, or (goal_direct) the caller's int64 ids
+    bool reuse = false;              // EC_POLICY_INFER_REUSE, and this workspace holds the tables of this plan
+
+    int goal_and_fusion(const void* feat, const int64_t* goal) {
+        int* goal32 = (int*)(ws + w.goal32);
+        goal_ids = p.goal_direct ? (const int*)goal : goal32;
+        if (!p.goal_direct)
+            hipLaunchKernelGGL(goal_to_i32_kernel, dim3((g.B + 255) / 256), dim3(256), 0, s, (const long long*)goal, goal32, g.B);
+        if (!c.fusion) return EC_OK;
+        if (!h->goal_table) return EC_ERR_ARG;
+        hipLaunchKernelGGL(p.feat_bf16 ? fuse_goal_kernel<true> : fuse_goal_kernel<false>, dim3((unsigned)((g.B + 3) / 4)), dim3(256), 0, s, feat,
+                           h->goal_table, goal32, ws + w.x, (long)g.B, g.flat, c.num_goals);
+        return EC_OK;
+    }
+
+    template <int MBLK, int U>
+    void c1_act(const void* featS, const float* b1, float* c1) {
+        hipLaunchKernelGGL((c1_act_kernel<MBLK, U>), dim3((unsigned)(c.compress_hid / 32), (unsigned)((g.M49 + 32 * MBLK - 1) / (32 * MBLK))),
+                           dim3(512), 0, s, (const uint16_t*)featS, (const uint16_t*)(ws + w.w1pF), b1, c1, (long)g.M49, g.C, c.compress_hid);
+    }
+
+    // resnet_compressor + target_obs_combiner of one encoder stream, up to this stream's block of the GRU input
+    int encoder_stream(int sidx, const void* featS) {
+        const Ws::Stream& o = w.st[sidx];
+        const int M49 = g.M49, C = g.C, cat = g.cat;
+        auto WS = [&](int i) { return W(i, sidx); };
+        // E1 = embed_class @ W3[:, co:]^T + b3
+        if (!reuse)
+            RC(gemm(WS(P_EMB), WS(P_W3) + c.compress_out, ws + o.E1, c.num_goals, c.comb_hid, c.goal_dims, c.goal_dims, 1, 1, cat, c.comb_hid, 0, WS(P_B3)));
+        if (p.c1 == C1::pingpong) {
+            RC(ec_split3_bf16(WS(P_W1), ws + w.w1p, c.compress_hid, C, stream));
+            RC(ec_gemm_bf16a_xp(featS, ws + w.w1p, WS(P_B1), ws + o.c1, M49, c.compress_hid, C, 1 /* EC_ACT_RELU */, p.planes, stream));
+        } else if (p.c1 == C1::act_kernel) {
+            // act step: one launch, K split over the waves of a workgroup, W1's three bf16 planes cached in the workspace with
+            // E1; c1 leaves with bias + ReLU (no partial matrices to fold)
+            if (!reuse) {
+                RC(ec_split3_bf16(WS(P_W1), ws + w.w1p, c.compress_hid, C, stream));
+                const long nu = (long)c.compress_hid * 3 * C / 8;
+                hipLaunchKernelGGL(frag_pack_planes_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, (const uint4*)(ws + w.w1p),
+                                   (uint4*)(ws + w.w1pF), c.compress_hid, C);
+            }
+            if (p.c1_mblk == 1) c1_act<1, 8>(featS, WS(P_B1), ws + o.c1);
+            else if (p.c1_mblk == 2) c1_act<2, 4>(featS, WS(P_B1), ws + o.c1);
+            else c1_act<4, 4>(featS, WS(P_B1), ws + o.c1);
+        } else if (p.c1 == C1::split_parts) {
+            // act step: K = C is long and M small (196 workgroups walking 64 K-steps each): four K slices write four
+            // partial matrices, tail_fwd_kernel folds them (+ b1, ReLU) in a fixed order -- no atomics, bit-reproducible,
+            // and independent of how the actors are sliced
+            RC(ec_gemm_f32(featS, WS(P_W1), ws + o.c1, M49, c.compress_hid, C, C, 1, 1, C, c.compress_hid,
+                           EC_GEMM_SPLIT_PARTS | (p.feat_bf16 ? EC_GEMM_A_BF16 : 0), nullptr, nullptr, nullptr, 0, nullptr, nullptr, ACT_PARTS, stream));
+        } else {
+            RC(gemm(featS, WS(P_W1), ws + o.c1, M49, c.compress_hid, C, C, 1, 1, C, c.compress_hid, EC_GEMM_RELU | (p.feat_bf16 ? EC_GEMM_A_BF16 : 0), WS(P_B1)));
+        }
+        if (p.tail_fwd) {
+            allow_big_lds<tail_fwd_kernel>();
+            const long nwg = std::min<long>(512, (((long)M49 + 31) / 32 + 3) / 4);   // 4 tiles of 32 rows per workgroup
+            hipLaunchKernelGGL(tail_fwd_kernel, dim3((unsigned)nwg), dim3(256), p.tail_fwd_lds, s, ws + o.c1, WS(P_W2), WS(P_B2), WS(P_W3), cat,
+                               ws + o.E1, goal_ids, g.S, c.num_goals, WS(P_W4), WS(P_B4), ws + o.c2, ws + o.m1, ws + o.x4, (long)M49,
+                               p.c1_fold, (long)M49 * c.compress_hid, WS(P_B1), p.goal_direct ? 2 : 1);
+        } else {
+            RC(gemm(ws + o.c1, WS(P_W2), ws + o.c2, M49, c.compress_out, c.compress_hid, c.compress_hid, 1, 1, c.compress_hid, c.compress_out, EC_GEMM_RELU, WS(P_B2)));
+            // target_obs_combiner (goal half folded into the row-group bias E1[goal])
+            RC(ec_gemm_f32(ws + o.c2, WS(P_W3), ws + o.m1, M49, c.comb_hid, c.compress_out, c.compress_out, 1, 1, cat,
+                           c.comb_hid, EC_GEMM_RELU, nullptr, ws + o.E1, goal_ids, g.S, nullptr, nullptr, 1, stream));
+            RC(gemm(ws + o.m1, WS(P_W4), ws + o.x4, M49, c.comb_out, c.comb_hid, c.comb_hid, 1, 1, c.comb_hid, c.comb_out, 0, WS(P_B4)));
+        }
+        if (p.wih == Wih::plain) {
+            const long total = (long)g.B * g.flat1;
+            hipLaunchKernelGGL(to_cmajor_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws + o.x4, ws + w.x,
+                               g.S, c.comb_out, total, g.flat, sidx * g.flat1);
+        } else if (p.wih == Wih::perm_learn || !reuse) {
+            hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * g.H)), dim3(256), g.flat * sizeof(float), s, W(P_WIH),
+                               ws + (p.wih == Wih::perm_learn ? w.wihP : w.wihA), g.S, c.comb_out, 0);
+        }
+        return EC_OK;
+    }
+
+    // GRU input projection for all T at once
+    int input_projection() {
+        const int B = g.B, H = g.H, flat = g.flat;
+        if (p.gi == Gi::act7 || p.gi == Gi::act8) {
+            const float* xin = ws + w.st[0].x4;
+            const float* win = ws + w.wihF;                              // the re-ordered weight_ih in fragment order
+            if (!reuse) {
+                const long nu = (long)3 * H * flat / 4;
+                hipLaunchKernelGGL(frag_pack_f32_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, (const float4*)(ws + w.wihA),
+                                   (float4*)(ws + w.wihF), 3 * H, flat);
+            }
+            const int nw = p.gi == Gi::act7 ? 7 : 8;                     // waves of a workgroup
+            hipLaunchKernelGGL(nw == 7 ? gi_act_kernel<7> : gi_act_kernel<8>, dim3((unsigned)(3 * H / 32), (unsigned)((B + 31) / 32)), dim3(64 * nw), 0, s,
+                               xin, win, W(P_BIH), ws + w.gi, B, flat, 3 * H);
+            return EC_OK;
+        }
+        const float* xin = p.wih == Wih::plain ? ws + w.x : ws + w.st[0].x4;
+        const float* win = p.wih == Wih::perm_learn ? ws + w.wihP : (p.wih == Wih::perm_act ? ws + w.wihA : W(P_WIH));
+        return ec_gemm_f32(xin, win, ws + w.gi, B, 3 * H, flat, flat, 1, 1, flat, 3 * H, p.gi == Gi::split_parts ? EC_GEMM_SPLIT_PARTS : 0,
+                           W(P_BIH), nullptr, nullptr, 0, nullptr, nullptr, p.gi_fold, stream);
+    }
+
+    // the sequential recurrence; step t's new state goes to hs + t * N * H
+    int recurrence(const float* h0, const float* masks, float* hs) {
+        const int N = g.N, H = g.H;
+        const size_t gru16_lds = (size_t)(4 * 64 * 128 + 4 * 3 * 256) * sizeof(float);
+        if (p.step_fwd == Step::fused32) allow_big_lds<gru_step_fwd_kernel>();
+        if (p.step_fwd == Step::fused16) allow_big_lds<gru_step_fwd512_kernel>();
+        for (int t = 0; t < g.T; ++t) {
+            const float* hprev = (t == 0) ? h0 : hs + (size_t)(t - 1) * N * H;
+            const float* m = masks + (size_t)t * N;
+            const size_t o3 = (size_t)t * N * 3 * H, o1 = (size_t)t * N * H;
+            if (p.step_fwd == Step::fused16) {
+                hipLaunchKernelGGL(gru_step_fwd512_kernel, dim3(32u, (unsigned)((N + 15) / 16)), dim3(256), gru16_lds, s,
+                                   ws + w.gi + o3, W(P_WHH), W(P_BHH), hprev, m, hs + o1, ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, N);
+            } else if (p.step_fwd == Step::fused32) {
+                hipLaunchKernelGGL(gru_step_fwd_kernel, dim3((unsigned)(H / 8), (unsigned)((N + 31) / 32)), dim3(256), p.gru_lds, s,
+                                   ws + w.gi + o3, W(P_WHH), W(P_BHH), hprev, m, hs + o1, ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1,
+                                   N, H, p.gi_fold, (long)g.B * 3 * H);
+            } else {
+                RC(gemm(hprev, W(P_WHH), ws + w.gh, N, 3 * H, H, H, 1, 1, H, 3 * H));
+                hipLaunchKernelGGL(gru_gates_fwd_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, ws + w.gi + o3, ws + w.gh,
+                                   W(P_BHH), hprev, m, hs + o1, ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, N, H);
+            }
+        }
+        return EC_OK;
+    }
+
+    // heads: hv[:, :A] = actor logits, hv[:, A] = critic value; then the final state, unless the recurrence left it there
+    int heads(const float* hs, float* hv, float* h_final, const SampleArgs& smp) {
+        const int B = g.B, H = g.H, A = g.A, A1 = g.A1;
+        if (A1 <= 8) {
+            hipLaunchKernelGGL(heads_fwd_kernel<8>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, hs, W(P_WA), W(P_BA), W(P_WC), W(P_BC), hv, (long)B, H, A, smp);
+        } else {
+            RC(gemm(hs, W(P_WA), hv, B, A, H, H, 1, 1, H, A1, 0, W(P_BA)));
+            RC(gemm(hs, W(P_WC), hv + A, B, 1, H, H, 1, 1, H, A1, 0, W(P_BC)));
+        }
+        if (h_final && hs != h_final)
+            (void)hipMemcpyAsync(h_final, ws + w.hs + (size_t)(g.T - 1) * g.N * H, (size_t)g.N * H * 4, hipMemcpyDeviceToDevice, s);
+        return EC_OK;
+    }
+};
+
+// EC_POLICY_INFER_REUSE bookkeeping (ec_policy::Built): is what an earlier EC_POLICY_INFER call left in this workspace valid
+// for plan `p`?  Records `p` as the builder when it is not; a learn pass overwrites the workspace and drops the record.
+bool tables_reusable(const ec_policy* h, const void* workspace, const Plan& p, int mode) {
+    std::lock_guard<std::mutex> lk(h->tables_mu);
+    if (!p.infer) { h->tables.erase(workspace); return false; }
+    const auto it = h->tables.find(workspace);
+    if (mode == EC_POLICY_INFER_REUSE && it != h->tables.end() && it->second == p.key) return true;
+    // bounded: a caller that allocates a fresh act workspace per call would otherwise add an entry per allocator address for
+    // the life of the handle.  Dropping every record is always safe -- a REUSE call that finds none rebuilds its tables.
+    if (h->tables.size() >= 64 && it == h->tables.end()) h->tables.clear();
+    h->tables[workspace] = p.key;
+    return false;
+}
+
+int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16, const int64_t* goal,
+                        const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int mode, float* hv,
+                        float* h_final, const SampleArgs& smp, ec_stream_t stream) {
+    if (!h || !params || !feat || !goal || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
+    if (h->c.dual && !feat2) return EC_ERR_ARG;
+    if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
+    if (mode < 0 || mode > EC_POLICY_INFER_REUSE) return EC_ERR_ARG;
+    const Plan p = make_plan(h, T, N, mode, feat_bf16 != 0);
+    if (ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
+    Fwd f(h, p, params, workspace, stream);
+    f.reuse = tables_reusable(h, workspace, p, mode);
+    RC(f.goal_and_fusion(feat, goal));
+    if (!h->c.fusion)
+        for (int sidx = 0; sidx < p.g.nstream; ++sidx)   // dual encoder: the RGB stream, then the depth stream (own weights, own activations)
+            RC(f.encoder_stream(sidx, sidx ? feat2 : feat));
+    RC(f.input_projection());
+    float* hs = (p.hs_direct && h_final && h_final != h0) ? h_final : f.ws + p.w.hs;
+    RC(f.recurrence(h0, masks, hs));
+    RC(f.heads(hs, hv, h_final, smp));
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
+
+struct Bwd : Ctx {
+    using Ctx::Ctx;
+    float* grads = nullptr;
+    bool parts_ok = true;         // the dx area is free for partial matrices (cleared once dx occupies it)
+    float* G(int i, int sidx = 0) const { return grads + off(i, sidx); }
+
+    // column sums (bias gradients) without atomics: row block y leaves its sums in cpart[y][Ncol] (the forward's per-step `gh`
+    // scratch: N x 3H floats, idle in the backward), colsum_fold_kernel adds the row blocks in order onto the gradient
+    void colsum(const float* Y, float* out, long M, int Ncol, int ld) {
+        float* cpart = ws + w.gh;
+        const size_t cpart_cap = (size_t)g.N * 3 * g.H;
+        const bool wide = (Ncol & 3) == 0 && (ld & 3) == 0 && Ncol >= 256 && M >= 1024;
+        long nby = (M + (wide ? 255 : 2047)) / (wide ? 256 : 2048);
+        const long fit = (long)(cpart_cap / (size_t)Ncol);
+        nby = std::max<long>(1, std::min(nby, fit));            // (Ncol <= 3H always: at least one row block fits)
+        const int rpb = (int)(((M + nby - 1) / nby + 3) / 4 * 4);
+        nby = (M + rpb - 1) / rpb;
+        if (wide) hipLaunchKernelGGL(colsum4_kernel, dim3((unsigned)((Ncol + 255) / 256), (unsigned)nby), dim3(256), 0, s, Y, cpart, M, Ncol, ld, rpb);
+        else hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((Ncol + 63) / 64), (unsigned)nby), dim3(256), 0, s, Y, cpart, M, Ncol, ld, rpb);
+        hipLaunchKernelGGL(colsum_fold_kernel, dim3((unsigned)((Ncol + 255) / 256)), dim3(256), 0, s, cpart, (int)nby, Ncol, out);
+    }
+    // weight-gradient GEMMs that split K: every K slice writes its own partial matrix (EC_GEMM_SPLIT_PARTS) into `sparts` and
+    // splitk_fold_kernel adds the slices in order onto the gradient -- the fp32 atomics this replaces made two runs from one
+    // seed differ in the last bits.  sparts: the dx area (free until dx / dx4 is computed, behind the weight gradients; with
+    // the re-ordered weight_ih and in fusion mode it is never used at all).
+    int gemm_acc_split(const void* A_, const void* B_, float* dW, int Mo, int No, long K, long sam, long sak, long sbk, long sbn,
+                       int ldc, int flags, int sk) {
+        float* sparts = ws + w.dx;
+        const size_t sparts_cap = (size_t)g.B * g.flat;
+        // every K slice costs a partial matrix written and read back: no more slices than fill the chip twice with 128 x 128 tiles
+        const long tiles_ = (long)((Mo + 127) / 128) * ((No + 127) / 128);
+        const int sk_cap = (int)std::max<long>(2, 512 / (tiles_ > 0 ? tiles_ : 1));
+        if (sk > sk_cap) sk = sk_cap;
+        while (sk > 1 && (size_t)sk * Mo * No > sparts_cap) --sk;
+        if (sk <= 1) return gemm(A_, B_, dW, Mo, No, (int)K, sam, sak, sbk, sbn, ldc, EC_GEMM_ACCUMULATE | flags);
+        RC(ec_gemm_f32(A_, B_, sparts, Mo, No, (int)K, sam, sak, sbk, sbn, No, EC_GEMM_SPLIT_PARTS | flags, nullptr, nullptr, nullptr, 0, nullptr, nullptr, sk, stream));
+        const long nq = (long)Mo * No;
+        hipLaunchKernelGGL(splitk_fold_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, sparts, sk, Mo, No, ldc, dW);
+        return EC_OK;
+    }
+    // dW += dY^T X over K rows: K slices into partial matrices folded in order while the dx area is free (`parts_ok`); the
+    // tail's unfused fallback GEMMs (EC_TAIL_FUSED=0, the dual encoder) run after dx exists and keep the atomic split
+    int tn(const float* dY, int ldy, const void* X, int ldx, int x_bf16, float* dW, int Mo, int No, long K, int ldc) {
+        const int sk = pick_splitk(Mo, No, K), flags = (x_bf16 ? EC_GEMM_B_BF16 : 0) | p.bwd3;
+        if (parts_ok) return gemm_acc_split(dY, X, dW, Mo, No, K, 1, ldy, ldx, 1, ldc, flags, sk);
+        return ec_gemm_f32(dY, X, dW, Mo, No, (int)K, 1, ldy, ldx, 1, ldc, EC_GEMM_ACCUMULATE | flags, nullptr, nullptr, nullptr, 0, nullptr,
+                           nullptr, sk, stream);
+    }
+    // the same for the GRU's two weight gradients (ld(dY) == Mo, ld(X) == ld(dW) == No): on transposed operands if the plan says so
+    int tn_gru(const float* dY, const float* X, float* dW, int Mo, int No, long K) {
+        if (!p.dw_t) return tn(dY, Mo, X, No, 0, dW, Mo, No, K, No);
+        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((Mo + 31) / 32), (unsigned)((K + 31) / 32)), dim3(256), 0, s, dY,
+                           ws + w.tA, (int)K, Mo);
+        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((No + 31) / 32), (unsigned)((K + 31) / 32)), dim3(256), 0, s, X,
+                           ws + w.tB, (int)K, No);
+        return gemm_acc_split(ws + w.tA, ws + w.tB, dW, Mo, No, K, K, 1, 1, K, No, p.bwd3, pick_splitk(Mo, No, K));
+    }
+
+    int heads(const float* dhv) {
+        const int B = g.B, H = g.H, A = g.A, A1 = g.A1;
+        RC(gemm(dhv, W(P_WA), ws + w.dhs, B, H, A, A1, 1, H, 1, H));
+        RC(gemm(dhv + A, W(P_WC), ws + w.dhs, B, H, 1, A1, 1, H, 1, H, EC_GEMM_ACCUMULATE));
+        RC(gemm_acc_split(dhv, ws + w.hs, G(P_WA), A, H, B, 1, A1, H, 1, H, 0, pick_splitk(A, H, B)));
+        RC(gemm_acc_split(dhv + A, ws + w.hs, G(P_WC), 1, H, B, 1, A1, H, 1, H, 0, pick_splitk(1, H, B)));
+        colsum(dhv, G(P_BA), B, A, A1);
+        colsum(dhv + A, G(P_BC), B, 1, A1);
+        return EC_OK;
+    }
+
+    // GRU, reverse time.  Fused: step T-1 is the plain gate kernel (its carry is dh_final), every earlier step ONE fused launch
+    // (back-projection of step t+1 + gates of step t); else gate kernel + GEMM per step
+    int recurrence(const float* masks, const float* dh_final) {
+        const int T = g.T, N = g.N, H = g.H;
+        const size_t gb_lds = (size_t)2 * 32 * (256 + 4) * sizeof(float), gb16_lds = (size_t)(4 * 2 * 32 * 128 + 4 * 256) * sizeof(float);
+        if (dh_final) (void)hipMemcpyAsync(ws + w.dhc, dh_final, (size_t)N * H * 4, hipMemcpyDeviceToDevice, s);
+        else (void)hipMemsetAsync(ws + w.dhc, 0, (size_t)N * H * 4, s);
+        if (p.step_bwd != Step::gemm_gates)
+            hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)(H / 32), (unsigned)(3 * H / 32)), dim3(256), 0, s, W(P_WHH), ws + w.whhT, 3 * H, H);
+        if (p.step_bwd == Step::fused32) allow_big_lds<gru_step_bwd_kernel>();
+        if (p.step_bwd == Step::fused16) allow_big_lds<gru_step_bwd512_kernel>();
+        for (int t = T - 1; t >= 0; --t) {
+            const size_t o3 = (size_t)t * N * 3 * H, o1 = (size_t)t * N * H;
+            const float* m = masks + (size_t)t * N;
+            if (p.step_bwd == Step::gemm_gates || t == T - 1) {
+                hipLaunchKernelGGL(gru_gates_bwd_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, ws + w.dhs + o1, ws + w.dhc,
+                                   ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N, H);
+                // dh_carry += m * (dghb @ W_hh)   (fused: step T-1's back-projection runs inside the next launch)
+                if (p.step_bwd == Step::gemm_gates)
+                    RC(ec_gemm_f32(ws + w.dghb + o3, W(P_WHH), ws + w.dhc, N, H, 3 * H, 3 * H, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr,
+                                   nullptr, nullptr, 0, nullptr, m, step_splitk(N, H, 3 * H), stream));
+            } else if (p.step_bwd == Step::fused16) {
+                hipLaunchKernelGGL(gru_step_bwd512_kernel, dim3(32u, (unsigned)((N + 15) / 16)), dim3(256), gb16_lds, s,
+                                   ws + w.dghb + o3 + (size_t)N * 3 * H, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dhc,
+                                   ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N);
+            } else {
+                hipLaunchKernelGGL(gru_step_bwd_kernel, dim3((unsigned)(H / 32), (unsigned)((N + 31) / 32)), dim3(256), gb_lds, s,
+                                   ws + w.dghb + o3 + (size_t)N * 3 * H, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dhc,
+                                   ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N, H);
+            }
+        }
+        return EC_OK;
+    }
+
+    // weight and bias gradients of the recurrence and of the input projection (TN over all T*N rows)
+    int gru_grads() {
+        const int B = g.B, H = g.H, flat = g.flat;
+        RC(tn_gru(ws + w.dghb, ws + w.hp, G(P_WHH), 3 * H, H, B));
+        colsum(ws + w.dghb, G(P_BHH), B, 3 * H, 3 * H);
+        if (p.wih == Wih::perm_learn) {   // gradient in the re-ordered weight's column order, then added back in the parameter's order
+            (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)3 * H * flat * 4, s);
+            RC(tn_gru(ws + w.dgi, ws + w.st[0].x4, ws + w.gwihP, 3 * H, flat, B));
+            hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * H)), dim3(256), flat * sizeof(float), s, ws + w.gwihP,
+                               G(P_WIH), g.S, c.comb_out, 1);
+        } else {
+            RC(tn_gru(ws + w.dgi, ws + w.x, G(P_WIH), 3 * H, flat, B));
+        }
+        colsum(ws + w.dgi, G(P_BIH), B, 3 * H, 3 * H);
+        return EC_OK;
+    }
+
+    // dx = dgi @ W_ih (channel-major), or dx4 = dgi @ (re-ordered weight_ih): already pixel-major
+    int input_grad() {
+        const int B = g.B, H = g.H, flat = g.flat;
+        if (p.wih != Wih::perm_learn)
+            return gemm(ws + w.dgi, W(P_WIH), ws + w.dx, B, flat, 3 * H, 3 * H, 1, flat, 1, flat, p.bwd3);
+        // The weight is transposed first (9.6 MB, into the gradient staging buffer, free again by now) so that BOTH operands are
+        // K-contiguous: the GEMM's strided-B staging runs at half the rate (263 vs ~130 us at 32 actors, 770 vs ~540 at 128)
+        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((flat + 31) / 32), (unsigned)(3 * H / 32)), dim3(256), 0, s,
+                           ws + w.wihP, ws + w.gwihP, 3 * H, flat);
+        return gemm(ws + w.dgi, ws + w.gwihP, ws + w.dx4, B, flat, 3 * H, 3 * H, 1, 1, 3 * H, flat, p.bwd3);
+    }
+
+    // goal half of target_obs_combiner.0 (dE1 = row-group sums of dm1 scattered by goal id)
+    int goal_half(int sidx) {
+        float* dE1 = ws + w.dE1;
+        colsum(dE1, G(P_B3, sidx), c.num_goals, c.comb_hid, c.comb_hid);
+        RC(tn(dE1, c.comb_hid, W(P_EMB, sidx), c.goal_dims, 0, G(P_W3, sidx) + c.compress_out, c.comb_hid, c.goal_dims, c.num_goals, g.cat));
+        return gemm(dE1, W(P_W3, sidx) + c.compress_out, G(P_EMB, sidx), c.num_goals, c.goal_dims, c.comb_hid, c.comb_hid, 1, g.cat, 1, c.goal_dims,
+                    EC_GEMM_ACCUMULATE);
+    }
+
+    // combiner and compressor of one encoder stream (the depth stream re-uses the gradient temporaries: one HIP stream)
+    int encoder_stream(int sidx, const void* featS) {
+        const Ws::Stream& o = w.st[sidx];
+        const int B = g.B, S = g.S, M49 = g.M49, C = g.C, cat = g.cat;
+        const int* goal32 = (const int*)(ws + w.goal32);
+        auto WS = [&](int i) { return W(i, sidx); };
+        auto GS = [&](int i) { return G(i, sidx); };
+        if (p.wih != Wih::perm_learn) {
+            const long total = (long)B * g.flat1;
+            hipLaunchKernelGGL(from_cmajor_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws + w.dx,
+                               ws + w.dx4, S, c.comb_out, total, g.flat, sidx * g.flat1);
+        }
+        (void)hipMemsetAsync(ws + w.dE1, 0, (size_t)c.num_goals * c.comb_hid * 4, s);
+        if (p.tail_bwd) {
+            // dm1 / dc2 / dc1 and all small weight gradients of the tail in one pass
+            allow_big_lds<tail_bwd_kernel>();
+            const long nwg = std::min<long>(TB_MAX_WG, (((long)M49 + 31) / 32 + 3) / 4);
+            hipLaunchKernelGGL(tail_bwd_kernel, dim3((unsigned)nwg), dim3(256), p.tail_bwd_lds, s, ws + w.dx4, ws + o.m1, ws + o.c2, ws + o.c1,
+                               WS(P_W2), WS(P_W3), cat, WS(P_W4), goal32, S, c.num_goals, ws + w.dc1,
+                               p.dw1_planes ? (uint16_t*)(ws + w.dc1) : nullptr, ws + w.tpart, ws + w.tpartE, (long)M49);
+            const int ne = TB_PART + c.num_goals * 128;
+            // the y-slices' sums: behind the used partial sets when there is room (nwg < TB_MAX_WG), else in the dm1 area, which
+            // the fused path never materialises (nwg == TB_MAX_WG means M49 >= 32,768 rows: 4 M floats)
+            float* red = (nwg < TB_MAX_WG) ? ws + w.tpart + (size_t)nwg * 4 * TB_PART : ws + w.dm1;
+            const size_t red_cap = (nwg < TB_MAX_WG) ? (size_t)(TB_MAX_WG - nwg) * 4 * TB_PART : (size_t)M49 * c.comb_hid;
+            int ny = (int)std::min<size_t>(8, red_cap / (size_t)ne);
+            if (ny < 1) return EC_ERR_WORKSPACE;
+            hipLaunchKernelGGL(tail_bwd_reduce_kernel, dim3((unsigned)((ne + 255) / 256), (unsigned)ny), dim3(256), 0, s, ws + w.tpart,
+                               (int)nwg * 4, ws + w.tpartE, c.num_goals, red);
+            hipLaunchKernelGGL(tail_bwd_fold_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, red, ny, c.num_goals, GS(P_W4),
+                               GS(P_W3), cat, GS(P_W2), GS(P_B4), GS(P_B2), GS(P_B1), ws + w.dE1);
+        } else {
+            // ---- target_obs_combiner ----
+            RC(tn(ws + w.dx4, c.comb_out, ws + o.m1, c.comb_hid, 0, GS(P_W4), c.comb_out, c.comb_hid, M49, c.comb_hid));
+            colsum(ws + w.dx4, GS(P_B4), M49, c.comb_out, c.comb_out);
+            RC(ec_gemm_f32(ws + w.dx4, WS(P_W4), ws + w.dm1, M49, c.comb_hid, c.comb_out, c.comb_out, 1, c.comb_hid, 1, c.comb_hid,
+                           0, nullptr, nullptr, nullptr, 0, ws + o.m1, nullptr, 1, stream));
+            RC(tn(ws + w.dm1, c.comb_hid, ws + o.c2, c.compress_out, 0, GS(P_W3), c.comb_hid, c.compress_out, M49, cat));
+            hipLaunchKernelGGL(group_sum_scatter_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.dm1, goal32, ws + w.dE1, S,
+                               c.comb_hid, (long)B);
+            // ---- resnet_compressor ----
+            RC(ec_gemm_f32(ws + w.dm1, WS(P_W3), ws + w.dc2, M49, c.compress_out, c.comb_hid, c.comb_hid, 1, cat, 1,
+                           c.compress_out, 0, nullptr, nullptr, nullptr, 0, ws + o.c2, nullptr, 1, stream));
+            RC(tn(ws + w.dc2, c.compress_out, ws + o.c1, c.compress_hid, 0, GS(P_W2), c.compress_out, c.compress_hid, M49, c.compress_hid));
+            colsum(ws + w.dc2, GS(P_B2), M49, c.compress_out, c.compress_out);
+            RC(ec_gemm_f32(ws + w.dc2, WS(P_W2), ws + w.dc1, M49, c.compress_hid, c.compress_out, c.compress_out, 1,
+                           c.compress_hid, 1, c.compress_hid, 0, nullptr, nullptr, nullptr, 0, ws + o.c1, nullptr, 1, stream));
+            colsum(ws + w.dc1, GS(P_B1), M49, c.compress_hid, c.compress_hid);
+        }
+        RC(goal_half(sidx));
+        if (p.dw1_planes) return ec_dw_tn_xp(ws + w.dc1, featS, ws + w.tpart, GS(P_W1), M49, C, p.planes, stream);   // (tpart: free again after the reducer)
+        return tn(ws + w.dc1, c.compress_hid, featS, C, p.feat_bf16, GS(P_W1), c.compress_hid, C, M49, C);
+    }
+};
+
 }  // namespace
 
 extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) {
@@ -1616,27 +2106,18 @@ extern "C" int ec_policy_param_offset(const ec_policy_t* h, int idx, size_t* off
 }
 extern "C" size_t ec_policy_workspace_bytes(const ec_policy_t* h, int T, int N, int for_backward) {
     if (!h || T <= 0 || N <= 0) return 0;
-    return layout(h, T, N, for_backward != 0).end * 4;
+    return make_plan(h, T, N, for_backward != 0 ? EC_POLICY_LEARN : EC_POLICY_INFER, false).w.end * 4;
 }
 
-extern "C" int ec_policy_forward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,
-                                 const int64_t* goal, const float* h0, const float* masks, int T, int N,
-                                 void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final,
-                                 ec_stream_t stream) {
-    return ec_policy_forward2(h, params, feat, nullptr, feat_bf16, goal, h0, masks, T, N, workspace, ws_bytes, for_backward, hv,
-                              h_final, stream);
+extern "C" int ec_policy_forward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16, const int64_t* goal,
+                                 const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int for_backward,
+                                 float* hv, float* h_final, ec_stream_t stream) {
+    return ec_policy_forward2(h, params, feat, nullptr, feat_bf16, goal, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final, stream);
 }
 
-namespace {
-int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
-                        const int64_t* goal, const float* h0, const float* masks, int T, int N,
-                        void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final, const SampleArgs& smp,
-                        ec_stream_t stream);
-}
 extern "C" int ec_policy_forward2(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
-                                  const int64_t* goal, const float* h0, const float* masks, int T, int N,
-                                  void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final,
-                                  ec_stream_t stream) {
+                                  const int64_t* goal, const float* h0, const float* masks, int T, int N, void* workspace,
+                                  size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream) {
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final,
                                SampleArgs{}, stream);
 }
@@ -1650,266 +2131,10 @@ extern "C" int ec_policy_act(const ec_policy_t* h, const float* params, const vo
                              uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream) {
     if (!actions || !logp) return EC_ERR_ARG;
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;       // (the one-wave-per-row heads launch)
-    SampleArgs smp;
-    smp.actions = (long long*)actions; smp.logp = logp; smp.values = values; smp.seed = seed; smp.step = step; smp.first_actor = first_actor;
+    const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, h0, masks, 1, N, workspace, ws_bytes,
                                reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
 }
-
-namespace {
-int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
-                        const int64_t* goal, const float* h0, const float* masks, int T, int N,
-                        void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final, const SampleArgs& smp,
-                        ec_stream_t stream) {
-    if (!h || !params || !feat || !goal || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
-    if (h->c.dual && !feat2) return EC_ERR_ARG;
-    if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
-    const ec_policy_cfg& c = h->c;
-    const Ws w = layout(h, T, N, false);
-    if (for_backward < 0 || for_backward > EC_POLICY_INFER_REUSE) return EC_ERR_ARG;
-    if (ws_bytes < layout(h, T, N, for_backward == EC_POLICY_LEARN).end * 4) return EC_ERR_WORKSPACE;
-    float* ws = (float*)workspace;
-    hipStream_t s = (hipStream_t)stream;
-    const int B = T * N, S = c.spatial * c.spatial, H = c.hidden, A1 = c.num_actions + 1;
-    const int M49 = B * S, C = c.in_channels, cat = c.compress_out + c.goal_dims;
-    const int nstream = (c.dual && !c.fusion) ? 2 : 1, flat1 = c.comb_out * S;
-    const int flat = c.fusion ? c.in_channels : nstream * flat1;
-    const float* P = params;
-    auto W = [&](int i) { return P + h->off[i]; };
-    int* goal32 = (int*)(ws + w.goal32);
-    // Act-step path (for_backward == 0, stated by the caller -- never inferred from the workspace size): inference only,
-    // so c1 need not be materialised and the two long-K, small-M GEMMs (compressor conv 1, GRU input projection) run as
-    // ACT_PARTS K slices whose partial matrices the consuming kernels fold in a fixed order.
-    const bool infer_only = for_backward == 0 || for_backward == EC_POLICY_INFER_REUSE;
-    // EC_POLICY_INFER_REUSE: the weight-derived table E1 that an EC_POLICY_INFER call left in THIS workspace is still valid
-    // (same parameters: every act step of a rollout after the first) -- one GEMM launch less on the act step's chain
-    bool reuse_tables = for_backward == EC_POLICY_INFER_REUSE;
-    {
-        std::lock_guard<std::mutex> lk(h->tables_mu);
-        if (!infer_only) {
-            h->tables.erase(workspace);                          // a learn pass overwrites the workspace
-        } else {
-            auto it = h->tables.find(workspace);
-            if (reuse_tables && (it == h->tables.end() || it->second.T != T || it->second.N != N || it->second.bf16 != (feat_bf16 ? 1 : 0)))
-                reuse_tables = false;                            // nothing valid for THIS geometry / dtype in this workspace: build
-            if (!reuse_tables) {
-                // bounded: a caller that allocates a fresh act workspace per call would otherwise add an entry per allocator
-                // address for the life of the handle.  Dropping every record is always safe -- a REUSE call that
-                // finds none rebuilds its tables.
-                if (h->tables.size() >= 64 && h->tables.find(workspace) == h->tables.end()) h->tables.clear();
-                h->tables[workspace] = ec_policy::Built{T, N, feat_bf16 ? 1 : 0};
-            }
-        }
-    }
-    // learn pass: the GRU's input projection reads the combiner output where it lies (pixel-major rows) against a re-ordered
-    // weight_ih (permute_row_kernel) -- no activation transposes in either direction
-    const bool wih_perm = ec_config().wih_perm && !infer_only && !c.fusion && !c.dual && (size_t)c.comb_out * S * 4 <= 64 * 1024;
-    const Ws wb = layout(h, T, N, !infer_only);
-    const bool small = !c.fusion && M49 > 0 && M49 <= ACT_MAX_ROWS;            // (== the condition in layout())
-    const size_t tail_lds_ = ((size_t)2 * 32 * TL_P128 + 128 * TL_P32 + (size_t)c.num_goals * 128 + 64 +
-                              4 * (size_t)(32 * TL_P128 + 32 * TL_P32)) * sizeof(float);
-    const int act_parts_on = ec_config().act_split;
-    const int tail_fused_ = ec_config().tail_fused;
-    const int gru_fused_ = ec_config().gru_fused;
-    const bool tail_ok = tail_fused_ && c.compress_hid == 128 && c.compress_out == 32 && c.comb_hid == 128 &&
-                         c.comb_out == 32 && tail_lds_ <= 160 * 1024;
-    const size_t gru_lds_ = std::max((size_t)2 * 32 * (((H & 255) == 0 ? 256 : H) + 4) * sizeof(float), (size_t)4 * 32 * 32 * sizeof(float));
-    const bool step_ok = gru_fused_ && (H % 32) == 0 && gru_lds_ <= 160 * 1024;
-    const bool act_split = act_parts_on && infer_only && small && tail_ok && (C % 32) == 0 && C / 32 >= ACT_PARTS;
-    const bool gi_split = act_parts_on && infer_only && small && step_ok && (flat + 31) / 32 >= ACT_PARTS;
-    // act step: the fused tail reads the low words of the int64 goal ids itself (== the conversion kernel's truncation): one
-    // launch less on the act step's chain; and its GRU input projection runs against the re-ordered weight_ih (built by the
-    // first act step after a parameter update, kept in the workspace like E1), so the channel-major transpose goes too
-    const bool goal_direct = infer_only && !c.fusion && tail_ok;
-    const bool wih_act = infer_only && !c.fusion && !c.dual && tail_ok && ec_config().wih_perm && (size_t)c.comb_out * S * 4 <= 64 * 1024;
-    if (!goal_direct)
-    hipLaunchKernelGGL(goal_to_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, (const long long*)goal, goal32, B);
-    if (c.fusion) {
-        if (!h->goal_table) return EC_ERR_ARG;
-        if (feat_bf16)
-            hipLaunchKernelGGL(fuse_goal_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, feat, h->goal_table,
-                               goal32, ws + w.x, (long)B, flat, c.num_goals);
-        else
-            hipLaunchKernelGGL(fuse_goal_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, feat, h->goal_table,
-                               goal32, ws + w.x, (long)B, flat, c.num_goals);
-    } else {
-    for (int sidx = 0; sidx < nstream; ++sidx) {   // dual encoder: the RGB stream, then the depth stream (own weights, own activations)
-    const void* featS = sidx ? feat2 : feat;
-    auto WS = [&](int i) { return P + h->off[(sidx && i >= P_W1 && i <= P_B4) ? i + (P_W1D - P_W1) : i]; };
-    const size_t o_E1 = sidx ? w.E1d : w.E1, o_c1 = sidx ? w.c1d : w.c1, o_c2 = sidx ? w.c2d : w.c2, o_m1 = sidx ? w.m1d : w.m1,
-                 o_x4 = sidx ? w.x4d : w.x4;
-    // E1 = embed_class @ W3[:, co:]^T + b3
-    if (!reuse_tables)
-    RC(ec_gemm_f32(WS(P_EMB), WS(P_W3) + c.compress_out, ws + o_E1, c.num_goals, c.comb_hid, c.goal_dims, c.goal_dims, 1,
-                   1, cat, c.comb_hid, 0, WS(P_B3), nullptr, nullptr, 0, nullptr, nullptr, 1, stream));
-    // resnet_compressor
-    // EC_C1_PINGPONG (default 1): bf16 features x fp32 W1 as three bf16 planes on the 8-wave ping-pong kernel
-    // (conv_igemm8, X3 mode) once there are enough 256-row tiles to fill the chip; else the generic x3 GEMM
-    const int c1_pp = ec_config().c1_pingpong;
-    bool c1_final = false;                                       // c1 already carries bias + ReLU (no partial matrices to fold)
-    if (c1_pp && feat_bf16 && c.compress_hid % 128 == 0 && C % 64 == 0 && M49 >= 256 * 128) {
-        RC(ec_split3_bf16(WS(P_W1), ws + w.w1p, c.compress_hid, C, stream));
-        // (EC_POLICY_FAST: the two leading planes of W1 -- 16 mantissa bits -- instead of all three: a third fewer MFMAs in a
-        //  launch that is MFMA-bound at three products per feature byte; learn pass only, the act step stays exact)
-        RC(ec_gemm_bf16a_xp(featS, ws + w.w1p, WS(P_B1), ws + o_c1, M49, c.compress_hid, C, 1 /* EC_ACT_RELU */,
-                            (ec_config().policy_fast && !infer_only) ? 2 : 3, stream));
-    } else if (act_split && feat_bf16 && !c.dual && (C % 128) == 0 && (c.compress_hid % 32) == 0) {
-        // act step: one launch, K split over the waves of a workgroup, W1's three bf16 planes cached in the workspace with E1
-        if (!reuse_tables) {
-            RC(ec_split3_bf16(WS(P_W1), ws + w.w1p, c.compress_hid, C, stream));
-            const long nu = (long)c.compress_hid * 3 * C / 8;
-            hipLaunchKernelGGL(frag_pack_planes_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, (const uint4*)(ws + w.w1p),
-                               (uint4*)(ws + w.w1pF), c.compress_hid, C);
-        }
-        {
-            const uint16_t* fa_ = (const uint16_t*)featS;
-            const uint16_t* wp_ = (const uint16_t*)(ws + w.w1pF);
-            const unsigned nx = (unsigned)(c.compress_hid / 32);
-            if (M49 <= 2048)
-                hipLaunchKernelGGL((c1_act_kernel<1, 8>), dim3(nx, (unsigned)((M49 + 31) / 32)), dim3(512), 0, s, fa_, wp_, WS(P_B1),
-                                   ws + o_c1, (long)M49, C, c.compress_hid);
-            else if (M49 <= 4096)
-                hipLaunchKernelGGL((c1_act_kernel<2, 4>), dim3(nx, (unsigned)((M49 + 63) / 64)), dim3(512), 0, s, fa_, wp_, WS(P_B1),
-                                   ws + o_c1, (long)M49, C, c.compress_hid);
-            else
-                hipLaunchKernelGGL((c1_act_kernel<4, 4>), dim3(nx, (unsigned)((M49 + 127) / 128)), dim3(512), 0, s, fa_, wp_, WS(P_B1),
-                                   ws + o_c1, (long)M49, C, c.compress_hid);
-        }
-        c1_final = true;
-    } else if (act_split) {
-        // act step: K = C is long and M small (196 workgroups walking 64 K-steps each): four K slices write four
-        // partial matrices, tail_fwd_kernel folds them (+ b1, ReLU) in a fixed order -- no atomics, bit-reproducible,
-        // and independent of how the actors are sliced
-        RC(ec_gemm_f32(featS, WS(P_W1), ws + o_c1, M49, c.compress_hid, C, C, 1, 1, C, c.compress_hid,
-                       EC_GEMM_SPLIT_PARTS | (feat_bf16 ? EC_GEMM_A_BF16 : 0), nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                       ACT_PARTS, stream));
-    } else
-    RC(ec_gemm_f32(featS, WS(P_W1), ws + o_c1, M49, c.compress_hid, C, C, 1, 1, C, c.compress_hid,
-                   EC_GEMM_RELU | (feat_bf16 ? EC_GEMM_A_BF16 : 0), WS(P_B1), nullptr, nullptr, 0, nullptr, nullptr, 1,
-                   stream));
-    // EC_TAIL_FUSED (default 1): c2 / m1 / x4 in one pass over c1 for the reference's widths
-    const int tail_fused = ec_config().tail_fused;
-    const size_t tail_lds = ((size_t)2 * 32 * TL_P128 + 128 * TL_P32 + (size_t)c.num_goals * 128 + 64 +
-                             4 * (size_t)(32 * TL_P128 + 32 * TL_P32)) * sizeof(float);
-    if (tail_fused && c.compress_hid == 128 && c.compress_out == 32 && c.comb_hid == 128 && c.comb_out == 32 &&
-        tail_lds <= 160 * 1024) {
-        static std::atomic<uint64_t> attr_done{0};
-        if (auto attr_g_ = ec_attr_needed(attr_done))
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tail_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024);
-        const long ntiles = ((long)M49 + 31) / 32;
-        long nwg = (ntiles + 3) / 4;
-        if (nwg > 512) nwg = 512;
-        hipLaunchKernelGGL(tail_fwd_kernel, dim3((unsigned)nwg), dim3(256), tail_lds, s, ws + o_c1, WS(P_W2), WS(P_B2), WS(P_W3), cat,
-                           ws + o_E1, goal_direct ? (const int*)goal : goal32, S, c.num_goals, WS(P_W4), WS(P_B4), ws + o_c2, ws + o_m1, ws + o_x4, (long)M49,
-                           (act_split && !c1_final) ? ACT_PARTS : 1, (long)M49 * c.compress_hid, WS(P_B1), goal_direct ? 2 : 1);
-    } else {
-    RC(ec_gemm_f32(ws + o_c1, WS(P_W2), ws + o_c2, M49, c.compress_out, c.compress_hid, c.compress_hid, 1, 1,
-                   c.compress_hid, c.compress_out, EC_GEMM_RELU, WS(P_B2), nullptr, nullptr, 0, nullptr, nullptr, 1,
-                   stream));
-    // target_obs_combiner (goal half folded into the row-group bias E1[goal])
-    RC(ec_gemm_f32(ws + o_c2, WS(P_W3), ws + o_m1, M49, c.comb_hid, c.compress_out, c.compress_out, 1, 1, cat,
-                   c.comb_hid, EC_GEMM_RELU, nullptr, ws + o_E1, goal32, S, nullptr, nullptr, 1, stream));
-    RC(ec_gemm_f32(ws + o_m1, WS(P_W4), ws + o_x4, M49, c.comb_out, c.comb_hid, c.comb_hid, 1, 1, c.comb_hid,
-                   c.comb_out, 0, WS(P_B4), nullptr, nullptr, 0, nullptr, nullptr, 1, stream));
-    }
-    if (wih_perm) {
-        hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * H)), dim3(256), flat * sizeof(float), s, W(P_WIH),
-                           ws + wb.wihP, S, c.comb_out, 0);
-    } else if (wih_act) {
-        if (!reuse_tables)
-            hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * H)), dim3(256), flat * sizeof(float), s, W(P_WIH),
-                               ws + w.wihA, S, c.comb_out, 0);
-    } else {
-        const long total = (long)B * flat1;
-        hipLaunchKernelGGL(to_cmajor_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws + o_x4, ws + w.x,
-                           S, c.comb_out, total, flat, sidx * flat1);
-    }
-    }   // streams
-    }   // !fusion
-    // GRU: input projection for all T at once, then the sequential recurrence
-    // (split-K only as separate partial matrices folded by the step kernel: the act step stays free of float atomics, so
-    //  rollouts are bit-reproducible)
-    // act step with a handful of rows: one launch, K split over the waves of a workgroup, folded in-kernel (gi_act_kernel)
-    const int gi_nw = (flat % 56 == 0) ? 7 : ((flat % 64 == 0) ? 8 : 0);
-    const bool gi_small = infer_only && wih_act && T == 1 && B <= 256 && gi_nw != 0 && (3 * H) % 32 == 0 && ec_config().act_split;
-    if (gi_small) {
-        const float* xin = ws + w.x4;
-        const float* win = ws + w.wihF;                              // the re-ordered weight_ih in fragment order
-        if (!reuse_tables) {
-            const long nu = (long)3 * H * flat / 4;
-            hipLaunchKernelGGL(frag_pack_f32_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, (const float4*)(ws + w.wihA),
-                               (float4*)(ws + w.wihF), 3 * H, flat);
-        }
-        const dim3 grid((unsigned)(3 * H / 32), (unsigned)((B + 31) / 32));
-        if (gi_nw == 7) hipLaunchKernelGGL(gi_act_kernel<7>, grid, dim3(448), 0, s, xin, win, W(P_BIH), ws + w.gi, B, flat, 3 * H);
-        else hipLaunchKernelGGL(gi_act_kernel<8>, grid, dim3(512), 0, s, xin, win, W(P_BIH), ws + w.gi, B, flat, 3 * H);
-    } else
-    RC(ec_gemm_f32((wih_perm || wih_act) ? ws + w.x4 : ws + w.x, wih_perm ? ws + wb.wihP : (wih_act ? ws + w.wihA : W(P_WIH)), ws + w.gi, B, 3 * H, flat, flat, 1, 1, flat, 3 * H,
-                   gi_split ? EC_GEMM_SPLIT_PARTS : 0, W(P_BIH), nullptr, nullptr, 0, nullptr, nullptr, gi_split ? ACT_PARTS : 1,
-                   stream));
-    // EC_GRU_FUSED (default 1): one fused launch per step where the geometry allows (H % 32 == 0, tiles fit the LDS)
-    const int gru_fused = ec_config().gru_fused;
-    size_t gru_lds = (size_t)2 * 32 * (((H & 255) == 0 ? 256 : H) + 4) * sizeof(float);      // operand tiles (K chunk) ...
-    if (gru_lds < 4 * 32 * 32 * sizeof(float)) gru_lds = 4 * 32 * 32 * sizeof(float);   // ... reused for the 4 partial tiles
-    const bool fused_step = gru_fused && (H % 32) == 0 && gru_lds <= 160 * 1024;
-    if (fused_step) {
-        static std::atomic<uint64_t> attr_done{0};
-        if (auto attr_g_ = ec_attr_needed(attr_done))
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gru_step_fwd_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-    // inference with T == 1 (the act step): the new state goes straight to h_final (no copy launch afterwards) and the
-    // heads read it there
-    float* hs_base = (infer_only && T == 1 && h_final && h_final != h0) ? h_final : ws + w.hs;
-    // the update's recurrences (learn pass, H == 512): 16 x 16-tile kernel, one workgroup per CU with 140 KB of LDS; the act
-    // step keeps the 66-KB kernel, which co-resides with the encoder launches of the other actor slice
-    const bool tile16 = fused_step && gru_fused >= 2 && H == 512 && !infer_only;
-    const size_t gru16_lds = (size_t)(4 * 64 * 128 + 4 * 3 * 256) * sizeof(float);
-    if (tile16) {
-        static std::atomic<uint64_t> attr16_done{0};
-        if (auto attr_g_ = ec_attr_needed(attr16_done))
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gru_step_fwd512_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-    for (int t = 0; t < T; ++t) {
-        const float* hprev = (t == 0) ? h0 : hs_base + (size_t)(t - 1) * N * H;
-        const size_t o3 = (size_t)t * N * 3 * H, o1 = (size_t)t * N * H;
-        if (tile16) {
-            hipLaunchKernelGGL(gru_step_fwd512_kernel, dim3(32u, (unsigned)((N + 15) / 16)), dim3(256), gru16_lds, s,
-                               ws + w.gi + o3, W(P_WHH), W(P_BHH), hprev, masks + (size_t)t * N, hs_base + o1,
-                               ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, N);
-            continue;
-        }
-        if (fused_step) {
-            hipLaunchKernelGGL(gru_step_fwd_kernel, dim3((unsigned)(H / 8), (unsigned)((N + 31) / 32)), dim3(256), gru_lds, s,
-                               ws + w.gi + o3, W(P_WHH), W(P_BHH), hprev, masks + (size_t)t * N, hs_base + o1,
-                               ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, N, H, (gi_split && !gi_small) ? ACT_PARTS : 1,
-                               (long)B * 3 * H);
-            continue;
-        }
-        RC(ec_gemm_f32(hprev, W(P_WHH), ws + w.gh, N, 3 * H, H, H, 1, 1, H, 3 * H, 0, nullptr, nullptr, nullptr, 0,
-                       nullptr, nullptr, 1, stream));
-        hipLaunchKernelGGL(gru_gates_fwd_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, ws + w.gi + o3, ws + w.gh,
-                           W(P_BHH), hprev, masks + (size_t)t * N, hs_base + o1, ws + w.gates + o3, ws + w.hn + o1,
-                           ws + w.hp + o1, N, H);
-    }
-    // heads: hv[:, :A] = actor logits, hv[:, A] = critic value
-    if (A1 <= 8) {
-        hipLaunchKernelGGL(heads_fwd_kernel<8>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, hs_base, W(P_WA), W(P_BA),
-                           W(P_WC), W(P_BC), hv, (long)B, H, c.num_actions, smp);
-    } else {
-        RC(ec_gemm_f32(hs_base, W(P_WA), hv, B, c.num_actions, H, H, 1, 1, H, A1, 0, W(P_BA), nullptr, nullptr, 0,
-                       nullptr, nullptr, 1, stream));
-        RC(ec_gemm_f32(hs_base, W(P_WC), hv + c.num_actions, B, 1, H, H, 1, 1, H, A1, 0, W(P_BC), nullptr, nullptr, 0,
-                       nullptr, nullptr, 1, stream));
-    }
-    if (h_final && hs_base != h_final)
-        (void)hipMemcpyAsync(h_final, ws + w.hs + (size_t)(T - 1) * N * H, (size_t)N * H * 4, hipMemcpyDeviceToDevice, s);
-    EC_CHECK_LAUNCH();
-    return EC_OK;
-}
-}  // namespace
 
 extern "C" int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,
                                   const float* masks, int T, int N, void* workspace, size_t ws_bytes, const float* dhv,
@@ -1920,260 +2145,33 @@ extern "C" int ec_policy_backward(const ec_policy_t* h, const float* params, con
 extern "C" int ec_policy_backward2(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                    const float* masks, int T, int N, void* workspace, size_t ws_bytes, const float* dhv,
                                    const float* dh_final, float* grads, ec_stream_t stream) {
-    return ec_policy_backward3(h, params, feat, feat2, feat_bf16, masks, T, N, workspace, ws_bytes, dhv, dh_final, grads, nullptr,
-                               stream);
+    return ec_policy_backward3(h, params, feat, feat2, feat_bf16, masks, T, N, workspace, ws_bytes, dhv, dh_final, grads, nullptr, stream);
 }
 
+// Reads what ec_policy_forward2(.., EC_POLICY_LEARN) left in `workspace`: built from the same (handle, T, N, dtype), the plan
+// here IS that forward's plan -- in particular which of ws.x / ws.x4 holds the GRU input.
 extern "C" int ec_policy_backward3(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                    const float* masks, int T, int N, void* workspace, size_t ws_bytes, const float* dhv,
                                    const float* dh_final, float* grads, ec_event_t recurrent_grads_ready, ec_stream_t stream) {
     if (!h || !params || !feat || !masks || !workspace || !dhv || !grads) return EC_ERR_ARG;
     if (h->c.dual && !feat2) return EC_ERR_ARG;
     if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
-    const ec_policy_cfg& c = h->c;
-    const Ws w = layout(h, T, N, true);
-    if (ws_bytes < w.end * 4) return EC_ERR_WORKSPACE;
-    float* ws = (float*)workspace;
-    hipStream_t s = (hipStream_t)stream;
-    const int B = T * N, S = c.spatial * c.spatial, H = c.hidden, A = c.num_actions, A1 = A + 1;
-    const int M49 = B * S, C = c.in_channels, cat = c.compress_out + c.goal_dims;
-    const int nstream = (c.dual && !c.fusion) ? 2 : 1, flat1 = c.comb_out * S;
-    const int flat = c.fusion ? c.in_channels : nstream * flat1;
-    auto W = [&](int i) { return params + h->off[i]; };
-    auto G = [&](int i) { return grads + h->off[i]; };
-    const int* goal32 = (const int*)(ws + w.goal32);
-    // column sums (bias gradients) without atomics: row block y leaves its sums in cpart[y][Ncol] (the forward's per-step `gh`
-    // scratch: N x 3H floats, idle in the backward), colsum_fold_kernel adds the row blocks in order onto the gradient
-    float* cpart = ws + w.gh;
-    const size_t cpart_cap = (size_t)N * 3 * H;
-    auto colsum = [&](const float* Y, float* out, long M, int Ncol, int ld) {
-        const bool wide = (Ncol & 3) == 0 && (ld & 3) == 0 && Ncol >= 256 && M >= 1024;
-        long nby = (M + (wide ? 255 : 2047)) / (wide ? 256 : 2048);
-        const long fit = (long)(cpart_cap / (size_t)Ncol);
-        if (nby > fit) nby = fit;
-        if (nby < 1) nby = 1;                                   // (Ncol <= 3H always: at least one row block fits)
-        const int rpb = (int)(((M + nby - 1) / nby + 3) / 4 * 4);
-        nby = (M + rpb - 1) / rpb;
-        if (wide) hipLaunchKernelGGL(colsum4_kernel, dim3((unsigned)((Ncol + 255) / 256), (unsigned)nby), dim3(256), 0, s, Y, cpart, M, Ncol, ld, rpb);
-        else hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((Ncol + 63) / 64), (unsigned)nby), dim3(256), 0, s, Y, cpart, M, Ncol, ld, rpb);
-        hipLaunchKernelGGL(colsum_fold_kernel, dim3((unsigned)((Ncol + 255) / 256)), dim3(256), 0, s, cpart, (int)nby, Ncol, out);
-    };
-    // weight-gradient GEMMs that split K: every K slice writes its own partial matrix (EC_GEMM_SPLIT_PARTS) into `sparts` and
-    // splitk_fold_kernel adds the slices in order onto the gradient -- the fp32 atomics this replaces made two runs from one
-    // seed differ in the last bits.  sparts: the dx area (free until dx / dx4 is computed, behind the weight gradients; with
-    // the re-ordered weight_ih and in fusion mode it is never used at all).
-    float* sparts = ws + w.dx;
-    const size_t sparts_cap = (size_t)B * flat;
-    auto gemm_acc_split = [&](const void* A_, const void* B_, float* dW, int Mo, int No, long K, long sam, long sak, long sbk, long sbn,
-                              int ldc, int flags, int sk) {
-        // every K slice costs a partial matrix written and read back: no more slices than fill the chip twice with 128 x 128 tiles
-        const long tiles_ = (long)((Mo + 127) / 128) * ((No + 127) / 128);
-        const int sk_cap = (int)std::max<long>(2, 512 / (tiles_ > 0 ? tiles_ : 1));
-        if (sk > sk_cap) sk = sk_cap;
-        while (sk > 1 && (size_t)sk * Mo * No > sparts_cap) --sk;
-        if (sk <= 1)
-            return ec_gemm_f32(A_, B_, dW, Mo, No, (int)K, sam, sak, sbk, sbn, ldc, EC_GEMM_ACCUMULATE | flags, nullptr, nullptr, nullptr, 0,
-                               nullptr, nullptr, 1, stream);
-        const int rc = ec_gemm_f32(A_, B_, sparts, Mo, No, (int)K, sam, sak, sbk, sbn, No, EC_GEMM_SPLIT_PARTS | flags, nullptr, nullptr,
-                                   nullptr, 0, nullptr, nullptr, sk, stream);
-        if (rc != EC_OK) return rc;
-        const long nq = (long)Mo * No;
-        hipLaunchKernelGGL(splitk_fold_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, sparts, sk, Mo, No, ldc, dW);
-        return (int)EC_OK;
-    };
-    // ---- heads ----
-    RC(ec_gemm_f32(dhv, W(P_WA), ws + w.dhs, B, H, A, A1, 1, H, 1, H, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                   1, stream));
-    RC(ec_gemm_f32(dhv + A, W(P_WC), ws + w.dhs, B, H, 1, A1, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr, nullptr, nullptr,
-                   0, nullptr, nullptr, 1, stream));
-    RC(gemm_acc_split(dhv, ws + w.hs, G(P_WA), A, H, B, 1, A1, H, 1, H, 0, pick_splitk(A, H, B)));
-    RC(gemm_acc_split(dhv + A, ws + w.hs, G(P_WC), 1, H, B, 1, A1, H, 1, H, 0, pick_splitk(1, H, B)));
-    colsum(dhv, G(P_BA), B, A, A1);
-    colsum(dhv + A, G(P_BC), B, 1, A1);
-    // ---- GRU, reverse time ----
-    if (dh_final) (void)hipMemcpyAsync(ws + w.dhc, dh_final, (size_t)N * H * 4, hipMemcpyDeviceToDevice, s);
-    else (void)hipMemsetAsync(ws + w.dhc, 0, (size_t)N * H * 4, s);
-    // EC_GRU_FUSED (default 1) and H % 256 == 0: step T-1 is the plain gate kernel (its carry is dh_final), every earlier
-    // step ONE fused launch (gru_step_bwd_kernel: back-projection of step t+1 + gates of step t); else GEMM + gate kernel
-    const bool fused_bstep = ec_config().gru_fused && (H % 256) == 0 && T > 1;
-    if (fused_bstep) {
-        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)(H / 32), (unsigned)(3 * H / 32)), dim3(256), 0, s, W(P_WHH),
-                           ws + w.whhT, 3 * H, H);
-        static std::atomic<uint64_t> attr_done{0};
-        if (auto attr_g_ = ec_attr_needed(attr_done))
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gru_step_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024);
-    }
-    const size_t gb_lds = (size_t)2 * 32 * (256 + 4) * sizeof(float);
-    const bool btile16 = fused_bstep && ec_config().gru_fused >= 2 && H == 512;
-    const size_t gb16_lds = (size_t)(4 * 2 * 32 * 128 + 4 * 256) * sizeof(float);
-    if (btile16) {
-        static std::atomic<uint64_t> attr16_done{0};
-        if (auto attr_g_ = ec_attr_needed(attr16_done))
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gru_step_bwd512_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-    for (int t = T - 1; t >= 0; --t) {
-        const size_t o3 = (size_t)t * N * 3 * H, o1 = (size_t)t * N * H;
-        if (btile16 && t < T - 1) {
-            hipLaunchKernelGGL(gru_step_bwd512_kernel, dim3(32u, (unsigned)((N + 15) / 16)), dim3(256), gb16_lds, s,
-                               ws + w.dghb + o3 + (size_t)N * 3 * H, ws + w.whhT, masks + (size_t)(t + 1) * N, ws + w.dhs + o1,
-                               ws + w.dhc, ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, masks + (size_t)t * N,
-                               ws + w.dgi + o3, ws + w.dghb + o3, N);
-            continue;
-        }
-        if (fused_bstep && t < T - 1) {
-            hipLaunchKernelGGL(gru_step_bwd_kernel, dim3((unsigned)(H / 32), (unsigned)((N + 31) / 32)), dim3(256), gb_lds, s,
-                               ws + w.dghb + o3 + (size_t)N * 3 * H, ws + w.whhT, masks + (size_t)(t + 1) * N, ws + w.dhs + o1,
-                               ws + w.dhc, ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, masks + (size_t)t * N,
-                               ws + w.dgi + o3, ws + w.dghb + o3, N, H);
-            continue;
-        }
-        hipLaunchKernelGGL(gru_gates_bwd_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, ws + w.dhs + o1, ws + w.dhc,
-                           ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, masks + (size_t)t * N, ws + w.dgi + o3,
-                           ws + w.dghb + o3, N, H);
-        if (fused_bstep) continue;          // (step T-1: its back-projection runs inside the next launch)
-        // dh_carry += m * (dghb @ W_hh)
-        RC(ec_gemm_f32(ws + w.dghb + o3, W(P_WHH), ws + w.dhc, N, H, 3 * H, 3 * H, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr,
-                       nullptr, nullptr, 0, nullptr, masks + (size_t)t * N, step_splitk(N, H, 3 * H), stream));
-    }
-    // EC_GEMM_BWD3: the large gradient GEMMs (weight gradients over all T*N rows, dx = dgi @ W_ih) on the three leading bf16
-    // products of the bf16x3 split (relative product error 2^-16; the parameters' gradients then agree with the fp32 oracle to
-    // ~1e-5 instead of ~1e-6)
-    const int bwd3 = (ec_config().gemm_bwd3 || ec_config().policy_fast) ? EC_GEMM_3PRODUCTS : 0;
-    // weight grads of the recurrence / input projection (TN over all T*N rows)
-    bool parts_ok = true;       // (cleared once dx / dx4 occupies the partial-matrix area)
-    auto tn = [&](const float* dY, int ldy, const void* X, int ldx, int x_bf16, float* dW, int Mo, int No, long K,
-                  int ldc) {
-        // grads += ...: K slices into partial matrices folded in order while the dx area is free (`parts_ok`); the tail's
-        // unfused fallback GEMMs (EC_TAIL_FUSED=0, the dual encoder) run after dx exists and keep the atomic split
-        const int sk = pick_splitk(Mo, No, K);
-        if (parts_ok) return gemm_acc_split(dY, X, dW, Mo, No, K, 1, ldy, ldx, 1, ldc, (x_bf16 ? EC_GEMM_B_BF16 : 0) | bwd3, sk);
-        return ec_gemm_f32(dY, X, dW, Mo, No, (int)K, 1, ldy, ldx, 1, ldc,
-                           EC_GEMM_ACCUMULATE | (x_bf16 ? EC_GEMM_B_BF16 : 0) | bwd3, nullptr, nullptr, nullptr, 0, nullptr,
-                           nullptr, sk, stream);
-    };
-    // EC_DW_TRANSPOSED (default 1): the GRU's two weight-gradient GEMMs contract over the T*N rows, i.e. BOTH operands are
-    // strided in K -- the slowest staging of gemm_x3 (1.02 ms for dW_ih at 128 actors against 0.49 ms for the same-size input
-    // projection).  Transposing both operands first (two bandwidth-bound passes, ~0.1 ms) makes it the K-contiguous case.
-    const bool dw_t = ec_config().dw_transposed && B >= 1024;
-    auto tn_t = [&](const float* dY, const float* X, float* dW, int Mo, int No, long K, int ldc) {   // ld(dY) == Mo, ld(X) == No
-        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((Mo + 31) / 32), (unsigned)((K + 31) / 32)), dim3(256), 0, s, dY,
-                           ws + w.tA, (int)K, Mo);
-        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((No + 31) / 32), (unsigned)((K + 31) / 32)), dim3(256), 0, s, X,
-                           ws + w.tB, (int)K, No);
-        return gemm_acc_split(ws + w.tA, ws + w.tB, dW, Mo, No, K, K, 1, 1, K, ldc, bwd3, pick_splitk(Mo, No, K));
-    };
-    if (dw_t) RC(tn_t(ws + w.dghb, ws + w.hp, G(P_WHH), 3 * H, H, B, H));
-    else
-    RC(tn(ws + w.dghb, 3 * H, ws + w.hp, H, 0, G(P_WHH), 3 * H, H, B, H));
-    colsum(ws + w.dghb, G(P_BHH), B, 3 * H, 3 * H);
-    const bool wih_perm = ec_config().wih_perm && !c.fusion && !c.dual && (size_t)c.comb_out * S * 4 <= 64 * 1024;   // (== ec_policy_forward's)
-    if (wih_perm) {   // gradient in the re-ordered weight's column order, then added back in the parameter's order
-        (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)3 * H * flat * 4, s);
-        if (dw_t) RC(tn_t(ws + w.dgi, ws + w.x4, ws + w.gwihP, 3 * H, flat, B, flat));
-        else
-        RC(tn(ws + w.dgi, 3 * H, ws + w.x4, flat, 0, ws + w.gwihP, 3 * H, flat, B, flat));
-        hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * H)), dim3(256), flat * sizeof(float), s, ws + w.gwihP,
-                           G(P_WIH), S, c.comb_out, 1);
-    } else
-    if (dw_t) RC(tn_t(ws + w.dgi, ws + w.x, G(P_WIH), 3 * H, flat, B, flat));
-    else
-    RC(tn(ws + w.dgi, 3 * H, ws + w.x, flat, 0, G(P_WIH), 3 * H, flat, B, flat));
-    colsum(ws + w.dgi, G(P_BIH), B, 3 * H, 3 * H);
+    const Plan p = make_plan(h, T, N, EC_POLICY_LEARN, feat_bf16 != 0);
+    if (ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
+    Bwd b(h, p, params, workspace, stream);
+    b.grads = grads;
+    RC(b.heads(dhv));
+    RC(b.recurrence(masks, dh_final));
+    RC(b.gru_grads());
     // the gradients of the GRU and of both heads (tensors rnn.weight_ih_l0 .. critic.fc.bias: 92 % of the bucket) are final
     // here; what follows only writes the goal encoder's.  A caller that sums the bucket over ranks starts that section's
     // all-reduce behind this event, under the rest of this backward
-    if (recurrent_grads_ready && hipEventRecord((hipEvent_t)recurrent_grads_ready, s) != hipSuccess) return EC_ERR_LAUNCH;
-    if (c.fusion) {   // the image embedding and the goal table are frozen: nothing trainable upstream of the GRU
-        EC_CHECK_LAUNCH();
-        return EC_OK;
+    if (recurrent_grads_ready && hipEventRecord((hipEvent_t)recurrent_grads_ready, b.s) != hipSuccess) return EC_ERR_LAUNCH;
+    if (!h->c.fusion) {   // (fusion: the image embedding and the goal table are frozen, nothing trainable upstream of the GRU)
+        b.parts_ok = p.wih == Wih::perm_learn;   // the plain path writes dx into the partial-matrix area now
+        RC(b.input_grad());
+        for (int sidx = 0; sidx < p.g.nstream; ++sidx) RC(b.encoder_stream(sidx, sidx ? feat2 : feat));
     }
-    parts_ok = wih_perm;        // (the plain path writes dx into the partial-matrix area now; with the re-ordered weight_ih it stays free)
-    // dx = dgi @ W_ih
-    if (wih_perm) { // dx4 = dgi @ (re-ordered weight_ih): already pixel-major.  The weight is transposed first (9.6 MB, into
-                    // the gradient staging buffer, free again by now) so that BOTH operands are K-contiguous: the GEMM's
-                    // strided-B staging runs at half the rate (263 vs ~130 us at 32 actors, 770 vs ~540 at 128)
-        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((flat + 31) / 32), (unsigned)(3 * H / 32)), dim3(256), 0, s,
-                           ws + w.wihP, ws + w.gwihP, 3 * H, flat);
-        RC(ec_gemm_f32(ws + w.dgi, ws + w.gwihP, ws + w.dx4, B, flat, 3 * H, 3 * H, 1, 1, 3 * H, flat, bwd3, nullptr, nullptr,
-                       nullptr, 0, nullptr, nullptr, 1, stream));
-    }
-    else
-        RC(ec_gemm_f32(ws + w.dgi, W(P_WIH), ws + w.dx, B, flat, 3 * H, 3 * H, 1, flat, 1, flat, bwd3, nullptr, nullptr, nullptr,
-                       0, nullptr, nullptr, 1, stream));
-    for (int sidx = 0; sidx < nstream; ++sidx) {   // dual encoder: the depth stream re-uses the gradient temporaries (one HIP stream)
-    const void* featS = sidx ? feat2 : feat;
-    auto WS = [&](int i) { return params + h->off[(sidx && i >= P_W1 && i <= P_B4) ? i + (P_W1D - P_W1) : i]; };
-    auto GS = [&](int i) { return grads + h->off[(sidx && i >= P_W1 && i <= P_B4) ? i + (P_W1D - P_W1) : i]; };
-    const size_t o_c1 = sidx ? w.c1d : w.c1, o_c2 = sidx ? w.c2d : w.c2, o_m1 = sidx ? w.m1d : w.m1;
-    if (!wih_perm) {
-        const long total = (long)B * flat1;
-        hipLaunchKernelGGL(from_cmajor_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws + w.dx,
-                           ws + w.dx4, S, c.comb_out, total, flat, sidx * flat1);
-    }
-    const int tail_fused = ec_config().tail_fused;
-    const size_t tb_lds = ((size_t)2 * 128 * TL_P32 + 32 * TL_P128 + std::max<size_t>((size_t)c.num_goals * 128, 4 * 256) +
-                           4 * (size_t)(32 * TL_P128 + 32 * TL_P32)) * sizeof(float);   // (the sE area: four wave-private 256-float lines)
-    const bool fused_bwd = tail_fused && c.compress_hid == 128 && c.compress_out == 32 && c.comb_hid == 128 &&
-                           c.comb_out == 32 && S >= 32 && tb_lds <= 160 * 1024 && c.num_goals <= TB_MAXG;
-    // EC_DW1_TR (default 1): dW1 through the transpose-read kernel (dw_tn.hip); dc1 then only exists as bf16 planes
-    const int dw1_tr = ec_config().dw1_tr;
-    const bool dw1_planes = fused_bwd && dw1_tr && feat_bf16 && C % 256 == 0 && M49 >= 2048 &&
-                            (size_t)ec_dw_tn_x3_splits(M49, C) * 128 * C <= (size_t)TB_MAX_WG * 4 * TB_PART;
-    (void)hipMemsetAsync(ws + w.dE1, 0, (size_t)c.num_goals * c.comb_hid * 4, s);
-    if (fused_bwd) {
-        // EC_TAIL_FUSED (default 1): dm1 / dc2 / dc1 and all small weight gradients of the tail in one pass
-        static std::atomic<uint64_t> attr_done{0};
-        if (auto attr_g_ = ec_attr_needed(attr_done))
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tail_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024);
-        const long ntiles = ((long)M49 + 31) / 32;
-        long nwg = (ntiles + 3) / 4;
-        if (nwg > TB_MAX_WG) nwg = TB_MAX_WG;
-        hipLaunchKernelGGL(tail_bwd_kernel, dim3((unsigned)nwg), dim3(256), tb_lds, s, ws + w.dx4, ws + o_m1, ws + o_c2, ws + o_c1,
-                           WS(P_W2), WS(P_W3), cat, WS(P_W4), goal32, S, c.num_goals, ws + w.dc1,
-                           dw1_planes ? (uint16_t*)(ws + w.dc1) : nullptr, ws + w.tpart, ws + w.tpartE,
-                           (long)M49);
-        const int ne = TB_PART + c.num_goals * 128;
-        // the y-slices' sums: behind the used partial sets when there is room (nwg < TB_MAX_WG), else in the dm1 area, which
-        // the fused path never materialises (nwg == TB_MAX_WG means M49 >= 32,768 rows: 4 M floats)
-        float* red = (nwg < TB_MAX_WG) ? ws + w.tpart + (size_t)nwg * 4 * TB_PART : ws + w.dm1;
-        const size_t red_cap = (nwg < TB_MAX_WG) ? (size_t)(TB_MAX_WG - nwg) * 4 * TB_PART : (size_t)M49 * c.comb_hid;
-        int ny = (int)std::min<size_t>(8, red_cap / (size_t)ne);
-        if (ny < 1) return EC_ERR_WORKSPACE;
-        hipLaunchKernelGGL(tail_bwd_reduce_kernel, dim3((unsigned)((ne + 255) / 256), (unsigned)ny), dim3(256), 0, s, ws + w.tpart,
-                           (int)nwg * 4, ws + w.tpartE, c.num_goals, red);
-        hipLaunchKernelGGL(tail_bwd_fold_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, red, ny, c.num_goals, GS(P_W4),
-                           GS(P_W3), cat, GS(P_W2), GS(P_B4), GS(P_B2), GS(P_B1), ws + w.dE1);
-    } else {
-    // ---- target_obs_combiner ----
-    RC(tn(ws + w.dx4, c.comb_out, ws + o_m1, c.comb_hid, 0, GS(P_W4), c.comb_out, c.comb_hid, M49, c.comb_hid));
-    colsum(ws + w.dx4, GS(P_B4), M49, c.comb_out, c.comb_out);
-    RC(ec_gemm_f32(ws + w.dx4, WS(P_W4), ws + w.dm1, M49, c.comb_hid, c.comb_out, c.comb_out, 1, c.comb_hid, 1, c.comb_hid,
-                   0, nullptr, nullptr, nullptr, 0, ws + o_m1, nullptr, 1, stream));
-    RC(tn(ws + w.dm1, c.comb_hid, ws + o_c2, c.compress_out, 0, GS(P_W3), c.comb_hid, c.compress_out, M49, cat));
-    hipLaunchKernelGGL(group_sum_scatter_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.dm1, goal32, ws + w.dE1, S,
-                       c.comb_hid, (long)B);
-    // ---- resnet_compressor ----
-    RC(ec_gemm_f32(ws + w.dm1, WS(P_W3), ws + w.dc2, M49, c.compress_out, c.comb_hid, c.comb_hid, 1, cat, 1,
-                   c.compress_out, 0, nullptr, nullptr, nullptr, 0, ws + o_c2, nullptr, 1, stream));
-    RC(tn(ws + w.dc2, c.compress_out, ws + o_c1, c.compress_hid, 0, GS(P_W2), c.compress_out, c.compress_hid, M49,
-          c.compress_hid));
-    colsum(ws + w.dc2, GS(P_B2), M49, c.compress_out, c.compress_out);
-    RC(ec_gemm_f32(ws + w.dc2, WS(P_W2), ws + w.dc1, M49, c.compress_hid, c.compress_out, c.compress_out, 1,
-                   c.compress_hid, 1, c.compress_hid, 0, nullptr, nullptr, nullptr, 0, ws + o_c1, nullptr, 1, stream));
-    colsum(ws + w.dc1, GS(P_B1), M49, c.compress_hid, c.compress_hid);
-    }
-    // goal half of target_obs_combiner.0 (dE1 = row-group sums of dm1 scattered by goal id)
-    colsum(ws + w.dE1, GS(P_B3), c.num_goals, c.comb_hid, c.comb_hid);
-    RC(tn(ws + w.dE1, c.comb_hid, WS(P_EMB), c.goal_dims, 0, GS(P_W3) + c.compress_out, c.comb_hid, c.goal_dims,
-          c.num_goals, cat));
-    RC(ec_gemm_f32(ws + w.dE1, WS(P_W3) + c.compress_out, GS(P_EMB), c.num_goals, c.goal_dims, c.comb_hid, c.comb_hid, 1,
-                   cat, 1, c.goal_dims, EC_GEMM_ACCUMULATE, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1, stream));
-    if (dw1_planes) RC(ec_dw_tn_xp(ws + w.dc1, featS, ws + w.tpart, GS(P_W1), M49, C, ec_config().policy_fast ? 2 : 3, stream));   // (tpart: free again after the reducer)
-    else RC(tn(ws + w.dc1, c.compress_hid, featS, C, feat_bf16, GS(P_W1), c.compress_hid, C, M49, C));
-    }   // streams
     EC_CHECK_LAUNCH();
     return EC_OK;
 }
