@@ -51,6 +51,8 @@ EcConfig read_config() {
     c.dw1_tr = env_int("EC_DW1_TR", 1);
     c.wih_perm = env_int("EC_WIH_PERM", 1);
     c.dw_transposed = env_int("EC_DW_TRANSPOSED", 1);
+    c.vit_wide = env_int("EC_VIT_WIDE", 1);
+    c.vit_bm192 = env_int("EC_VIT_BM192", 1);
     return c;
 }
 }  // namespace
@@ -67,7 +69,8 @@ uint64_t ec_config_hash() {
     auto mix = [&](long v) {
         for (int i = 0; i < 8; ++i) { x ^= (uint64_t)((v >> (8 * i)) & 0xff); x *= 1099511628211ull; }
     };
-    // EVERY field selects kernels: all of them key the profiles under profiles/ (ec_rn50_plan_hash / ec_vit_plan_hash)
+    // The fields that select kernels key the profiles under profiles/ (ec_rn50_plan_hash / ec_vit_plan_hash); vit_wide / vit_bm192
+    // stay out, so that the hash -- and with it the committed summaries' key -- is what it was before they moved into EcConfig
     mix(c.conv_narrow); mix(c.conv_rowsn); mix(c.conv_big); mix(c.conv8_min_tiles); mix(c.conv8_bn128); mix(c.conv8_longseg);
     mix(c.conv_t224); mix(c.conv_t64); mix(c.conv_ring); mix(c.conv_regw); mix(c.rn50_fuse); mix(c.rn50_bneck); mix(c.rn50_bneck3);
     mix(c.rn50_img3); mix(c.rn50_dscat); mix(c.rn50_poolout); mix(c.gemm_no_x3); mix(c.gemm_bwd3); mix(c.policy_fast); mix(c.act_split); mix(c.tail_fused); mix(c.gru_fused); mix(c.c1_pingpong);

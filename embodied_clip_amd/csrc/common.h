@@ -108,7 +108,7 @@ static inline ec_attr_guard ec_attr_needed(std::atomic<uint64_t>& done) {
     return ec_attr_guard(&done, bit);
 }
 
-// Fewest 256-row output tiles for which the conv / GEMM dispatch takes the 8-wave kernel (conv_igemm.hip dispatch_tile).
+// Fewest 256-row output tiles for which the conv / GEMM dispatch takes the 8-wave kernel (conv_igemm.hip conv_route).
 // A property of the encoder HANDLE (ec_rn50_set_conv8_min_tiles / ec_vit_set_conv8_min_tiles), in force for the calling
 // thread while that handle's forward issues its launches; everything else sees the default.
 constexpr int EC_CONV8_MIN_TILES_DEFAULT = 150;
@@ -179,13 +179,29 @@ struct EcConfig {
     int dw1_tr;           // EC_DW1_TR        (1)   dW1 on the transpose-read kernel
     int wih_perm;         // EC_WIH_PERM      (1)   learn pass: re-ordered weight_ih instead of activation transposes
     int dw_transposed;    // EC_DW_TRANSPOSED (1)   GRU weight-gradient GEMMs on transposed (K-contiguous) operands
+    // --- ViT / text GEMMs (ec_gemm_bf16_ln8).  NOT part of ec_config_hash(): the profile summaries under profiles/ are keyed by the hash as it was ---
+    int vit_wide;         // EC_VIT_WIDE      (1)   0: 128-wide tiles only, 2: 256-wide wherever N allows
+    int vit_bm192;        // EC_VIT_BM192     (1)   0: no 192-row tiles
 };
 // Fixed since round 5 (measured winners; the A/B numbers live in docs/experiments.md): 768 persistent workgroups, residual 1x1
 // launches of K 512..2047 with < 100 256-wide tiles on 128-wide 8-wave tiles, low-fill limits 100 tiles / K >= 1024, ring-mode
 // LDS-DMA pieces interleaved with the MFMAs, 128 x 128 ring tiles on 8 waves.
 constexpr int EC_CONV8_LOWFILL = 100, EC_CONV8_LOWFILL_K = 1024;
 const EcConfig& ec_config();          // api.hip
-uint64_t ec_config_hash();            // FNV-1a over the fields above
+uint64_t ec_config_hash();            // FNV-1a over the fields above (all but vit_wide / vit_bm192)
+
+// Library-internal entry points (C++ linkage, not part of include/ec_amd.h); EC_ERR_SHAPE from the first three = not handled
+int ec_conv3x3_narrow(const void* in, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
+                      int pool, hipStream_t s);   // conv3x3_narrow.hip: resident-weight kernel for the narrow early 3x3 layers
+int ec_conv1x1_regw(const void* a, const void* w, const float* bias, const void* res, void* y, long M, int K, int N, int act,
+                    hipStream_t s);               // conv_pair.hip: register-weight kernel for a few bandwidth-bound 1x1 shapes
+int ec_conv1x1_regw_pool(const void* a, const void* w, const float* bias, const void* res, void* y, void* y_pooled, int B, int H,
+                         int W, int K, int N, int act, int ld_pooled, hipStream_t s);   // conv_pair.hip: ... also emitting AvgPool2d(2) of y
+int ec_gemm_bf16a_xp(const void* A, const void* Wplanes, const float* bias, float* out, long M, int N, int K, int act, int planes,
+                     ec_stream_t stream);         // conv_igemm.hip: ec_gemm_bf16a_x3 over the 2 or 3 leading weight planes
+int ec_gemm_bf16_ln8(const void* A, const void* Wt, const float* bias, const void* res, void* out, int M, int N, int K, int act,
+                     const float* ln_s, const float* ln_stats, int ln_np, float* stats_out, int* np_out,
+                     ec_stream_t stream);         // conv_igemm.hip: the 8-wave GEMM with LayerNorm folded in / emitting its row records
 
 #define EC_CHECK_LAUNCH()                                   \
     do {                                                    \

@@ -38,7 +38,7 @@
 // at 760-850 TFLOP/s; the mid-size layers sit at 570-680 because of (a) the L2->LDS operand feed (3x3 256->256
 // @14x14, B=256: MFMA alone 33 us, operand loads alone 42 us, together ~the sum) and (b) tile quantisation (784 tiles
 // on 768 workgroups cost 98 us where 766 tiles cost 72 us).  (b) is what the 196-of-224-row tile configuration
-// (template parameter MV, see dispatch_tile) removes for single 256-frame launches.  Measured without effect:
+// (template parameter MV, see conv_route) removes for single 256-frame launches.  Measured without effect:
 // loads two tiles ahead, double vs single LDS stage, fat 128x256 / 256x128 tiles, 8-wave workgroups,
 // all-fragments-up-front MFMA scheduling, LDS-DMA pieces interleaved between MFMA groups, start skew between
 // co-resident workgroups, wave specialisation, a split-K tail reduced by the last arriver, 64-row tiles.
@@ -279,7 +279,7 @@ __device__ __forceinline__ void fr_step(FragRing<R>& ring, AddrFn& addr, MmaFn& 
     }
 }
 
-// MV = rows of the tile that are real output rows (tile stride in M); MV < BM pads the tile (see dispatch_tile:
+// MV = rows of the tile that are real output rows (tile stride in M); MV < BM pads the tile (see conv_route:
 // 196-of-224-row tiles make every RN50 layer's tile count a multiple of the CU count).
 // NS >= 3: RING mode for launches with at most 1-2 workgroups per CU (small per-GPU batches, the 7x7 maps): NS LDS stages,
 // the LDS-DMA of K-tile kt+NS-1 is issued while K-tile kt computes, each wave waits for its OWN pieces of K-tile kt with a
@@ -1265,67 +1265,146 @@ int launch8(const ConvArgs& a, hipStream_t s) {
     return EC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Host dispatch: conv_args() fills the kernel arguments, conv_route() picks kernel family and tile, launch_route() turns the
+// pick into a template instance.  tests/test_conv_routes.py pins every launch of a recorded list of shapes and trunk forwards
+// (kernel instance, grid, block, LDS bytes) under every switch below; the rule names are the ones its table is keyed by.
 
-template <int KS, bool POOL>
-int dispatch_tile(const ConvArgs& a, hipStream_t s) {
-    // Tile choice: 128x128 wherever Cout allows; 256-row tiles for the narrow early layers.
-    // (Fatter 128x256 / 256x128 tiles were measured: no gain, and they spill once loads run two tiles ahead.)
-    // EC_CONV_BIG: 0 off; 1 (default) the 8-wave ping-pong kernel (conv_igemm8) where it was measured to win; 4 conv_igemm8
-    // wherever its preconditions hold (tests / A-B).  Measured and removed again: the plain
-    // double-buffered 256x256 configuration of conv_igemm_kernel (8 waves, one barrier per K-tile: 77.9 us where the
-    // ping-pong schedule takes 72-75) and a one-wave-per-SIMD 4-wave kernel with in-wave software pipelining (87.8 us:
-    // every LDS-DMA piece blocks its issuing wave for ~150 clk and there is no partner wave to keep the matrix pipe busy).
-    const int big = ec_config().conv_big;
-    if (big == 1 && a.Cin % 64 == 0 && (KS == 1 || a.cin_log2 >= 0) && a.K >= 512 && a.M % (POOL ? 4 : 1) == 0) {
+// The one place a ConvArgs is filled.  in: in_rows pixels of H x W frames, Cin channels; w: [Cout][planes][ksize^2 Cin];
+// res / out: m_rows rows (the GEMM's M: output pixels, before pooling) of Cout, `out` with row stride ldo.  EC_ERR_SHAPE when an
+// operand does not fit its 32-bit buffer descriptor.
+int conv_args(ConvArgs& a, const void* in, const void* w, const float* bias, const void* res, void* out, long in_rows, int H, int W,
+              int Cin, int Cout, int ksize, long m_rows, int ldo, int act, int planes = 1) {
+    a = ConvArgs{};
+    a.in = (const uint16_t*)in;
+    a.w = (const uint16_t*)w;
+    a.bias = bias;
+    a.res = (const uint16_t*)res;
+    a.out = (uint16_t*)out;
+    a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ldo = ldo;
+    a.K = ksize * ksize * Cin;
+    a.M = (int)m_rows;
+    a.cin_log2 = (Cin & (Cin - 1)) == 0 ? ec_ilog2(Cin) : -1;   // (read by the 3x3 instances only)
+    a.act = act;
+    // (the plane-walking instances address A with unsigned offsets: their caller cuts the rows into slabs below 4 GiB)
+    const long in_bytes = in_rows * Cin * 2, w_bytes = (long)Cout * planes * a.K * 2, res_bytes = m_rows * Cout * 2;
+    if (in_bytes >= (planes > 1 ? 1L << 32 : 1L << 31) || w_bytes >= (1L << 31)) return EC_ERR_SHAPE;
+    if (res && res_bytes >= (1L << 32) - 16) return EC_ERR_SHAPE;
+    a.in_bytes = (unsigned)in_bytes;
+    a.w_bytes = (unsigned)w_bytes;
+    a.res_bytes = res ? (unsigned)res_bytes : 0u;
+    return EC_OK;
+}
+
+// What the route choice reads besides the launch itself: ec_config() and the calling thread's 8-wave threshold.
+struct RouteSwitches {
+    int big;          // EC_CONV_BIG: 0 no 8-wave kernel; 1 (default) where it was measured to win; 4 wherever its preconditions hold (tests / A-B)
+    long min_tiles;   // fewest 256-row tiles for the 8-wave kernel: EC_CONV8_MIN_TILES, else the handle's (ec_min_tiles_scope), else 150
+    int bn128, t224, t64, ring;   // EC_CONV8_BN128, EC_CONV_T224, EC_CONV_T64, EC_CONV_RING
+    int vit_wide, vit_bm192;      // EC_VIT_WIDE, EC_VIT_BM192 (ec_gemm_bf16_ln8's own tile choice)
+};
+RouteSwitches route_switches() {
+    const EcConfig& c = ec_config();
+    return {c.conv_big, c.conv8_min_tiles > 0 ? c.conv8_min_tiles : (long)ec_tls_conv8_min_tiles, c.conv8_bn128, c.conv_t224,
+            c.conv_t64, c.conv_ring, c.vit_wide, c.vit_bm192};
+}
+
+// Kernel family (C8: conv_igemm8_kernel, C4: conv_igemm_kernel) and tile configuration.
+enum Route {
+    ROUTE_NONE,        // no tile divides Cout: EC_ERR_SHAPE
+    C8_WIDE,           // 256 x 256 tiles
+    C8_NARROW,         // 256 x 128 tiles (long segments under EC_CONV8_LONGSEG)
+    C4_T224,           // 196-of-224 x 128 tiles, one wave row
+    C4_64_RING,        // 64 x 64 tiles, four-stage ring
+    C4_64,             // 64 x 64 tiles, single-stage loop
+    C4_128_RING,       // 128 x 128 tiles on 8 waves, three-stage ring, pieces between the MFMAs
+    C4_128_PREFETCH,   // 128 x 128 tiles, residual register prefetch
+    C4_128,            // 128 x 128 tiles
+    C4_256x64,
+    C4_256x32,
+};
+
+// Pure: no HIP call, no environment.  `a` as conv_args() filled it.
+// Tile choice: 128x128 wherever Cout allows; 256-row tiles for the narrow early layers.
+// (Fatter 128x256 / 256x128 tiles were measured: no gain, and they spill once loads run two tiles ahead.)
+// Measured and removed again: the plain double-buffered 256x256 configuration of conv_igemm_kernel
+// (8 waves, one barrier per K-tile: 77.9 us where the ping-pong schedule takes 72-75) and a one-wave-per-SIMD 4-wave kernel
+// with in-wave software pipelining (87.8 us: every LDS-DMA piece blocks its issuing wave for ~150 clk and there is no partner
+// wave to keep the matrix pipe busy).
+Route conv_route(const ConvArgs& a, int ksize, bool pool, bool s2, const RouteSwitches& sw) {
+    const bool k3 = ksize == 3, k1 = !k3, res = a.res != nullptr;
+    const bool div256 = a.Cout % 256 == 0, div128 = a.Cout % 128 == 0;
+    const long rt = (a.M + 255) / 256, nt256 = rt * (a.Cout / 256), nt128 = rt * (a.Cout / 128);   // 8-wave tiles, 256 / 128 wide
+    const long t128 = (long)((a.M + 127) / 128) * (a.Cout / 128);                                   // 128 x 128 tiles
+    // fits the 8-wave kernel: a K-tile never straddles a 3x3 tap, shift / mask tap decode, pooling windows whole
+    const bool fits8 = a.Cin % 64 == 0 && (k1 || a.cin_log2 >= 0) && a.K >= 512 && a.M % (pool ? 4 : 1) == 0;
+    // residual register prefetch only for the short-K, bandwidth-bound expanding 1x1 convs
+    const bool prefetch = k1 && !pool && res && a.K <= 256;
+
+    if (s2) {
+        // torchvision's strided convs.  The 8-wave kernel where the CLIP trunk's rules would take it: 256-wide tiles from 150
+        // tiles on, 128-wide ones when only those reach 150; then 128 x 128 tiles (three workgroups per CU) where Cout allows,
+        // 64 x 64 ring tiles for launches that would leave CUs idle.  Differences from the stride-1 rules below:
+        const long mint = EC_CONV8_MIN_TILES_DEFAULT;   // the constant, not sw.min_tiles: kept as found, not measured
+        if (fits8 && sw.big != 0) {                     // EC_CONV_BIG = 4 acts as 1 here; no K / residual conditions on the wide tiles: kept as found, not measured
+            if (div256 && nt256 >= mint) return C8_WIDE;                        // rule s2_c8_wide
+            if (div128 && nt128 >= mint && (k3 || !res)) return C8_NARROW;      // rule s2_c8_narrow
+        }
+        if (div128) {
+            // EC_CONV_RING is not read (the ring tiles at every setting) and there is no t224 / prefetch rule: kept as found, not measured
+            if (t128 < sw.t64 && a.K >= 512) return C4_64_RING;                 // rule s2_tile64 (its instance has ILV off: launch_route)
+            if (!prefetch && a.K >= 512 && t128 <= 256) return C4_128_RING;     // rule s2_tile128_ring: one workgroup per CU
+            return C4_128;                                                      // rule s2_tile128
+        }
+        return C4_256x64;                                                       // rule s2_tile256x64 (the entry point requires Cout % 64 == 0)
+    }
+
+    if (sw.big == 1 && fits8) {
         // measured (B = 256, tools/bench_big.sh): wins on the 3x3 convs with Cout % 256 == 0 once there are enough
-        // 256-row tiles to occupy most CUs; loses on N = 128, on the short launches of 7x7 maps and ties on 1x1
-        const long nt256 = (long)((a.M + 255) / 256) * (a.Cout / 256), nt128 = (long)((a.M + 255) / 256) * (a.Cout / 128);
-        // fewest 256-row tiles for the 8-wave kernel: 150 for a launch that has the chip to itself; a caller that keeps two
-        // launches in flight (the engine's two slices) lowers it on its encoder handles (ec_rn50_set_conv8_min_tiles): alone a 50-100-tile launch of the
+        // 256-row tiles to occupy most CUs; loses on N = 128, on the short launches of 7x7 maps and ties on 1x1.
+        // Fewest 256-row tiles: 150 for a launch that has the chip to itself; a caller that keeps two launches in flight (the
+        // engine's two slices) lowers it on its encoder handles (ec_rn50_set_conv8_min_tiles): alone a 50-100-tile launch of the
         // 8-wave kernel is 30-40 % slower than the 4-wave kernel, but it leaves the other launch 150-200 whole CUs instead of
         // sharing all of them (same-box A/B at 2 x 128 frames: +0.4..1.5 % RN50, +3.5 % ViT-B/32 end to end; at 2 x 64: -1.1 %)
-        const long mint_env = ec_config().conv8_min_tiles;
-        const long mint = mint_env > 0 ? mint_env : (long)ec_tls_conv8_min_tiles;
-        // 3x3 launches whose 256-wide tiles would fill only a fraction of the chip take 128-wide ones (twice the tiles; with
-        // long segments, EC_CONV8_LONGSEG, a 128-wide K-tile costs half a 256-wide one): EC_CONV8_LOWFILL = tile-count limit
-        if (KS == 3 && !POOL && a.Cout % 256 == 0 && a.K >= 2304 && nt256 >= mint && nt256 < EC_CONV8_LOWFILL && nt128 >= mint)
-            return launch8<128, KS, POOL>(a, s);
-        if (KS == 3 && a.Cout % 256 == 0 && nt256 >= mint) return launch8<256, KS, POOL>(a, s);
-        // 3x3 convs with too few 256-wide tiles (layer 4 @7x7 in a single 256-frame launch: 98) but enough 128-wide ones:
-        // 196 tiles x 72 K-tiles, 84.7 -> 64.6 us (tools/bench_shapes.py, B = 256)
-        if (KS == 3 && !POOL && a.Cout % 256 == 0 && nt256 < mint && nt128 >= mint && a.K >= 2304) return launch8<128, KS, POOL>(a, s);
-        // 128-channel 3x3 convs (layer 2): 128-wide tiles of the 8-wave kernel (same-box A/B in the engine, round 3:
-        // +0.4..0.8 % at 2 x 128 frames, neutral at 2 x 32; alone 52 -> 42 us at 128 frames).  EC_CONV8_BN128 = -1: off
-        if (KS == 3 && a.Cout == 128 && ec_config().conv8_bn128 >= 0 && nt128 >= 2 * mint) return launch8<128, KS, POOL>(a, s);
+        const long mint = sw.min_tiles;
+        // rule c8_3x3_lowfill: 3x3 launches whose 256-wide tiles would fill only a fraction of the chip take 128-wide ones (twice
+        // the tiles; with long segments, EC_CONV8_LONGSEG, a 128-wide K-tile costs half a 256-wide one): EC_CONV8_LOWFILL = tile-count limit
+        if (k3 && !pool && div256 && a.K >= 2304 && nt256 >= mint && nt256 < EC_CONV8_LOWFILL && nt128 >= mint) return C8_NARROW;
+        // rule c8_3x3_wide
+        if (k3 && div256 && nt256 >= mint) return C8_WIDE;
+        // rule c8_3x3_few_wide: 3x3 convs with too few 256-wide tiles (layer 4 @7x7 in a single 256-frame launch: 98) but enough
+        // 128-wide ones: 196 tiles x 72 K-tiles, 84.7 -> 64.6 us (tools/bench_shapes.py, B = 256)
+        if (k3 && !pool && div256 && nt256 < mint && nt128 >= mint && a.K >= 2304) return C8_NARROW;
+        // rule c8_3x3_c128: 128-channel 3x3 convs (layer 2): 128-wide tiles of the 8-wave kernel (same-box A/B in the engine,
+        // round 3: +0.4..0.8 % at 2 x 128 frames, neutral at 2 x 32; alone 52 -> 42 us at 128 frames).  EC_CONV8_BN128 = -1: off
+        if (k3 && a.Cout == 128 && sw.bn128 >= 0 && nt128 >= 2 * mint) return C8_NARROW;
+        // rule c8_1x1_lowfill: long-K 1x1 launches that would fill less than ~40 % of the chip with 256-wide tiles take 128-wide
+        // ones (twice the tiles, same per-tile efficiency): ViT-B/32 c_proj at 6,400 tokens is 75 tiles x 48 K-tiles (same-box
+        // A/B: +2.4 % on the ViT config, +0.4 % RN50)
+        if (k1 && !pool && sw.bn128 >= 0 && a.K >= EC_CONV8_LOWFILL_K && div256 && nt256 >= mint && nt256 < 100 && nt128 >= mint)
+            return C8_NARROW;
+        // rule c8_1x1_res_lowfill: residual 1x1 launches with K = 512 .. 2047 that would fill less than ~40 % of the chip with
+        // 256-wide tiles (ViT-B/32 out_proj at 6,400 tokens: 75 tiles x 12 K-tiles) on the long-segment 128-wide tiles: same-box
+        // A/B 74.9 -> 76.3 k env-frames/s on the ViT config, forward 2.10 -> 2.05 ms; with the limit at 150 tiles the rule also
+        // caught layer 4's conv3 at 2 x 64 frames (104 tiles) and cost the RN50 config 0.4-1.3 % there
+        if (k1 && !pool && res && a.K >= 512 && a.K < 2048 && div128 && nt256 < 100 && nt128 >= mint) return C8_NARROW;
         // long-K 1x1 convs (tools/bench_l4.sh, B = 256): 1024->2048 @7x7 83.7 -> 70.5 us, 1024->512 @14x14 82.9 -> 70.5,
-        // 1024->256 @14x14 40.6 -> 37.0 with 256-wide tiles; 2048->512 @7x7 46.4 -> 40.1 with 128-wide tiles (196 of them);
-        // K = 512 and residual launches stay on the 4-wave kernel (slower here)
-        // K = 512 and short-K residual launches stay on the 4-wave kernel (slower here).  ViT-B/32 GEMMs (tools/bench_vitgemm.sh,
-        // 12800 tokens): in_proj 768->2304 78.6 -> 57.6 us, c_fc 768->3072 105 -> 82, c_proj 3072->768 + residual 91.7 -> 85.1;
-        // out_proj 768->768 + residual is slower (31 -> 35) and keeps the 4-wave kernel
-        // long-K 1x1 launches that would fill less than ~40 % of the chip with 256-wide tiles take 128-wide ones (twice the
-        // tiles, same per-tile efficiency): ViT-B/32 c_proj at 6,400 tokens is 75 tiles x 48 K-tiles (same-box A/B: +2.4 % on the ViT config, +0.4 % RN50)
-        if (KS == 1 && !POOL && ec_config().conv8_bn128 >= 0 && a.K >= EC_CONV8_LOWFILL_K && a.Cout % 256 == 0 && nt256 >= mint && nt256 < 100 &&
-            nt128 >= mint)
-            return launch8<128, KS, POOL>(a, s);
-        // residual 1x1 launches with K = 512 .. 2047 that would fill less than ~40 % of the chip with 256-wide tiles (ViT-B/32
-        // out_proj at 6,400 tokens: 75 tiles x 12 K-tiles) on the long-segment 128-wide tiles: same-box A/B 74.9 -> 76.3 k
-        // env-frames/s on the ViT config, forward 2.10 -> 2.05 ms; with the limit at 150 tiles the rule also caught layer 4's
-        // conv3 at 2 x 64 frames (104 tiles) and cost the RN50 config 0.4-1.3 % there.  EC_CONV8_RES128 = 0: off
-        if (KS == 1 && !POOL && a.res && a.K >= 512 && a.K < 2048 && a.Cout % 128 == 0 && nt256 < 100 && nt128 >= mint)
-            return launch8<128, KS, POOL>(a, s);
-        if (KS == 1 && !POOL && ((!a.res && a.K >= 768) || (a.res && (a.K >= 2048 || (a.K >= 512 && nt256 >= 150))))) {   // (residual, K = 512: 49.5 -> 45.7 us on 512 -> 2048 @7x7; ViT out_proj, 75 tiles x 12 K-tiles, stays on the 4-wave kernel: 19.8 vs 23.3 us)
-            if (a.Cout % 256 == 0 && nt256 >= mint) return launch8<256, KS, POOL>(a, s);
-            if (!a.res && a.K >= 1024 && a.Cout % 128 == 0 && nt256 < mint && nt128 >= mint) return launch8<128, KS, POOL>(a, s);
+        // 1024->256 @14x14 40.6 -> 37.0 with 256-wide tiles; 2048->512 @7x7 46.4 -> 40.1 with 128-wide tiles (196 of them).
+        // ViT-B/32 GEMMs (tools/bench_vitgemm.sh, 12800 tokens): in_proj 768->2304 78.6 -> 57.6 us, c_fc 768->3072 105 -> 82,
+        // c_proj 3072->768 + residual 91.7 -> 85.1.  K = 512 and short-K residual launches stay on the 4-wave kernel (slower
+        // here): residual, K = 512 from 150 tiles on, 49.5 -> 45.7 us on 512 -> 2048 @7x7; ViT out_proj 768->768 + residual with
+        // 75 tiles x 12 K-tiles of 256 is slower (31 -> 35 us at 12800 tokens, 19.8 -> 23.3 at 6,400): rule c8_1x1_res_lowfill or the 4-wave kernel
+        if (k1 && !pool && ((!res && a.K >= 768) || (res && (a.K >= 2048 || (a.K >= 512 && nt256 >= 150))))) {
+            if (div256 && nt256 >= mint) return C8_WIDE;                                                   // rule c8_1x1_wide
+            if (!res && a.K >= 1024 && div128 && nt256 < mint && nt128 >= mint) return C8_NARROW;          // rule c8_1x1_few_wide
         }
     }
-    if (big == 4 && a.Cin % 64 == 0 && (KS == 1 || a.cin_log2 >= 0) && a.K >= 512 && a.M >= 256 * 32 && a.M % (POOL ? 4 : 1) == 0) {
-        const int bn128 = ec_config().conv8_bn128;
-        if (a.Cout % 256 == 0 && !bn128) return launch8<256, KS, POOL>(a, s);     // (A/B: everywhere its preconditions hold)
-        if (a.Cout % 128 == 0) return launch8<128, KS, POOL>(a, s);
+    if (sw.big == 4 && fits8 && a.M >= 256 * 32) {   // (A/B: everywhere its preconditions hold)
+        if (div256 && !sw.bn128) return C8_WIDE;     // rule c8_all_wide
+        if (div128) return C8_NARROW;                // rule c8_all_narrow (EC_CONV8_BN128 = 1: also where 256 divides Cout)
     }
-    if (a.Cout % 128 == 0) {
-        // 196-of-224-row tiles: 196 = 14^2 divides every RN50 feature map (56^2, 28^2, 14^2, 4 x 7^2), so the tile count
+    if (div128) {
+        // rule t224, 196-of-224-row tiles: 196 = 14^2 divides every RN50 feature map (56^2, 28^2, 14^2, 4 x 7^2), so the tile count
         // becomes a multiple of the frame count -- e.g. layer 3 at 256 frames: 512 tiles = 2 per CU instead of 784
         // tiles on 768 workgroups (16 tail tiles running alone).  Costs 12.5 % padding and runs 2 workgroups per CU, so
         // it only pays where quantisation hurts most: measured 3x3 256->256 @14x14 100.9 -> 79.3 us, 1x1 1024->256
@@ -1334,57 +1413,58 @@ int dispatch_tile(const ConvArgs& a, hipStream_t s) {
         // padded tiles cost ~0.7 % (measured on the 28x28 3x3 convs, which also have 512 padded tiles at 128 frames):
         // the rule is therefore limited to 14x14 maps, i.e. to single launches of 256 frames.
         // EC_CONV_T224: 0 off, 1 everywhere (tests/experiments), 2 (default) the rule below, 3 also 256-tile launches.
-        const int t224 = ec_config().conv_t224;
-        if constexpr (!POOL) {
-            const long t196 = (long)(a.M / 196) * (a.Cout / 128), t128 = (long)((a.M + 127) / 128) * (a.Cout / 128);
-            if (a.M % 196 == 0 &&
-                (t224 == 1 || (t224 >= 2 && !a.res && a.K >= 1024 && (t196 == 256 || t196 == 512) && (t128 % 768) != 0 &&
-                               (t224 == 3 || (t196 == 512 && (long)a.H * a.W == 196)))))
-                return launch<224, 128, 1, 4, KS, POOL, false, 196>(a, s);
-        }
-        // Small launches (strong scaling: 32-64 frames per GPU): with fewer 128x128 tiles than CUs every workgroup is one
-        // long serial K chain and most of the chip idles -> 64x64 tiles give 4x the workgroups for the long-K layers
+        const long t196 = (long)(a.M / 196) * (a.Cout / 128);
+        if (!pool && a.M % 196 == 0 &&
+            (sw.t224 == 1 || (sw.t224 >= 2 && !res && a.K >= 1024 && (t196 == 256 || t196 == 512) && (t128 % 768) != 0 &&
+                              (sw.t224 == 3 || (t196 == 512 && (long)a.H * a.W == 196)))))
+            return C4_T224;
+        // rule tile64, small launches (strong scaling: 32-64 frames per GPU): with fewer 128x128 tiles than CUs every workgroup
+        // is one long serial K chain and most of the chip idles -> 64x64 tiles give 4x the workgroups for the long-K layers
         // (batch 32: layer-4 3x3 52 tiles x 72 K-tiles = 76 us).  EC_CONV_T64: tile-count threshold (0 = off).
-        const int t64 = ec_config().conv_t64;
         // EC_CONV_RING (default 1): those launches, and 128x128 launches with at most one workgroup per CU, run the
         // multi-stage ring pipeline (conv_igemm_kernel NS >= 3): with so few waves per CU nothing hides the L2 round trip
         // of the single-stage loop.  2: every non-prefetching 128x128 launch (A/B).
-        const int ring = ec_config().conv_ring;
-        if constexpr (!POOL) {
-            const long t128 = (long)((a.M + 127) / 128) * (a.Cout / 128);
-            if (t128 < t64 && a.K >= 512 && a.Cout % 64 == 0)
-                // (deeper rings -- 6 / 8 stages for launches with at most one workgroup per CU, 4 stages for the 128x128 ring --
-                //  measured round 3: 0.944 -> 0.95-0.96 ms at 32 frames, 1.50 -> 1.50-1.51 at 64: stages in flight are not
-                //  what bounds these launches any more; what is left per K-tile is barrier + piece issue)
-                return ring ? launch<64, 64, 2, 2, KS, POOL, false, 64, 4, true>(a, s) : launch<64, 64, 2, 2, KS, POOL>(a, s);
-        }
-        {
-            const long t128 = (long)((a.M + 127) / 128) * (a.Cout / 128);
-            const bool pf = (KS == 1 && !POOL && a.res && a.K <= 256);
-            if (!pf && a.K >= 512 && ((ring == 1 && t128 <= 256) || ring == 2)) {
-                // the one-workgroup-per-CU ring launches run on 8 waves (2 x 4, wave tile 64 x 32): two waves per SIMD, so one
-                // wave's fragment reads / piece issue run beside the other's MFMAs; pieces interleaved with the MFMAs (ILV)
-                return launch<128, 128, 2, 4, KS, POOL, false, 128, 3, true>(a, s);
-            }
-        }
-        // residual register prefetch only for the short-K, bandwidth-bound expanding 1x1 convs
-        if (KS == 1 && !POOL && a.res && a.K <= 256) return launch<128, 128, 2, 2, KS, POOL, (KS == 1 && !POOL)>(a, s);
-        return launch<128, 128, 2, 2, KS, POOL>(a, s);
+        // (deeper rings -- 6 / 8 stages for launches with at most one workgroup per CU, 4 stages for the 128x128 ring --
+        //  measured round 3: 0.944 -> 0.95-0.96 ms at 32 frames, 1.50 -> 1.50-1.51 at 64: stages in flight are not
+        //  what bounds these launches any more; what is left per K-tile is barrier + piece issue)
+        if (!pool && t128 < sw.t64 && a.K >= 512) return sw.ring ? C4_64_RING : C4_64;
+        // rule tile128_ring: the one-workgroup-per-CU ring launches run on 8 waves (2 x 4, wave tile 64 x 32): two waves per
+        // SIMD, so one wave's fragment reads / piece issue run beside the other's MFMAs; pieces interleaved with the MFMAs (ILV)
+        if (!prefetch && a.K >= 512 && ((sw.ring == 1 && t128 <= 256) || sw.ring == 2)) return C4_128_RING;
+        return prefetch ? C4_128_PREFETCH : C4_128;   // rules tile128_prefetch, tile128
     }
-    if (a.Cout % 64 == 0) return launch<256, 64, 4, 1, KS, POOL>(a, s);
-    if (a.Cout % 32 == 0) return launch<256, 32, 4, 1, KS, POOL>(a, s);   // (one stem layer; 32 B rows < 8-wave loader pass)
+    if (a.Cout % 64 == 0) return C4_256x64;           // rule tile256x64
+    if (a.Cout % 32 == 0) return C4_256x32;           // rule tile256x32 (one stem layer; 32 B rows < 8-wave loader pass)
+    return ROUTE_NONE;
+}
+
+// Route -> template instance; combinations no rule produces are not instantiated.
+template <int KS, bool POOL, bool S2>
+int launch_route(Route r, const ConvArgs& a, hipStream_t s) {
+    switch (r) {
+        case C8_WIDE: return launch8<256, KS, POOL, false, S2>(a, s);
+        case C8_NARROW: return launch8<128, KS, POOL, false, S2>(a, s);
+        case C4_T224: if constexpr (!POOL && !S2) return launch<224, 128, 1, 4, KS, false, false, 196>(a, s); break;
+        case C4_64_RING: if constexpr (!POOL) return launch<64, 64, 2, 2, KS, false, false, 64, 4, !S2, S2>(a, s); break;   // (stride 2: ILV off, kept as found)
+        case C4_64: if constexpr (!POOL && !S2) return launch<64, 64, 2, 2, KS, false>(a, s); break;
+        case C4_128_RING: return launch<128, 128, 2, 4, KS, POOL, false, 128, 3, true, S2>(a, s);
+        case C4_128_PREFETCH: if constexpr (KS == 1 && !POOL && !S2) return launch<128, 128, 2, 2, 1, false, true>(a, s); break;
+        case C4_128: return launch<128, 128, 2, 2, KS, POOL, false, 128, 0, false, S2>(a, s);
+        case C4_256x64: return launch<256, 64, 4, 1, KS, POOL, false, 256, 0, false, S2>(a, s);
+        case C4_256x32: if constexpr (!S2) return launch<256, 32, 4, 1, KS, POOL>(a, s); break;
+        case ROUTE_NONE: break;
+    }
     return EC_ERR_SHAPE;
 }
 
+int conv_dispatch(const ConvArgs& a, int ksize, bool pool, bool s2, hipStream_t s) {
+    const Route r = conv_route(a, ksize, pool, s2, route_switches());
+    if (s2) return ksize == 3 ? launch_route<3, false, true>(r, a, s) : launch_route<1, false, true>(r, a, s);
+    if (ksize == 3) return pool ? launch_route<3, true, false>(r, a, s) : launch_route<3, false, false>(r, a, s);
+    return pool ? launch_route<1, true, false>(r, a, s) : launch_route<1, false, false>(r, a, s);
+}
+
 }  // namespace
-
-// conv3x3_narrow.hip: resident-weight kernel for the narrow early 3x3 layers (EC_ERR_SHAPE = not handled)
-int ec_conv3x3_narrow(const void* in, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
-                      int pool, hipStream_t s);
-
-// conv_pair.hip: register-weight kernel for a few bandwidth-bound 1x1 shapes (EC_ERR_SHAPE = not handled)
-int ec_conv1x1_regw(const void* a, const void* w, const float* bias, const void* res, void* y, long M, int K, int N, int act,
-                    hipStream_t s);
 
 #ifdef EC_TOOLS   // tools-only build (`make tools`): the stamp read-back of the 8-wave kernel's profiling instances
 extern "C" int ec_debug_stamps(unsigned long long* host_dst, int n) {
@@ -1413,33 +1493,17 @@ extern "C" int ec_conv_bf16_ld(const void* in, const void* w, const float* bias,
     if (pool && ((H & 1) || (W & 1) || res != nullptr || act != EC_ACT_RELU)) return EC_ERR_SHAPE;
     if (res && act == EC_ACT_QUICKGELU) return EC_ERR_UNSUPPORTED;   // (no caller: CLIP applies QuickGELU to c_fc only)
     if (H >= 4096 || W >= 65536) return EC_ERR_SHAPE;
-    if ((long)B * H * W >= (1L << 31) / 4) return EC_ERR_SHAPE;
+    const long M = (long)B * H * W;
+    if (M >= (1L << 31) / 4) return EC_ERR_SHAPE;
     ConvArgs a;
-    a.in = (const uint16_t*)in;
-    a.w = (const uint16_t*)w;
-    a.bias = bias;
-    a.res = (const uint16_t*)res;
-    a.out = (uint16_t*)out;
-    a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ldo = Cout;
-    a.K = ksize * ksize * Cin;
-    a.M = B * H * W;
-    a.cin_log2 = (Cin & (Cin - 1)) == 0 ? ec_ilog2(Cin) : -1;
-    a.act = act;
-    a.ntn = 0;
-    if ((long)B * H * W * Cin * 2 >= (1L << 31) || (long)Cout * a.K * 2 >= (1L << 31)) return EC_ERR_SHAPE;
-    a.in_bytes = (unsigned)((long)B * H * W * Cin * 2);
-    a.w_bytes = (unsigned)((long)Cout * a.K * 2);
-    if (res && (long)B * H * W * Cout * 2 >= (1L << 32) - 16) return EC_ERR_SHAPE;
-    a.res_bytes = res ? (unsigned)((long)B * H * W * Cout * 2) : 0u;
-    a.ldo = out_row_stride;
+    if (int rc = conv_args(a, in, w, bias, res, out, M, H, W, Cin, Cout, ksize, M, out_row_stride, act)) return rc;
     hipStream_t s = (hipStream_t)stream;
     // (the register-weight and resident-weight kernels write dense tensors only)
-    if (dense && ksize == 1 && !pool && ec_conv1x1_regw(in, w, bias, res, out, (long)B * H * W, Cin, Cout, act, s) == EC_OK) return EC_OK;
+    if (dense && ksize == 1 && !pool && ec_conv1x1_regw(in, w, bias, res, out, M, Cin, Cout, act, s) == EC_OK) return EC_OK;
     if (dense && ksize == 3 && !res && act == EC_ACT_RELU && Cin <= 64 && Cout <= 64 &&
         ec_conv3x3_narrow(in, w, bias, out, B, H, W, Cin, Cout, pool, s) == EC_OK)
         return EC_OK;
-    if (ksize == 3) return pool ? dispatch_tile<3, true>(a, s) : dispatch_tile<3, false>(a, s);
-    return pool ? dispatch_tile<1, true>(a, s) : dispatch_tile<1, false>(a, s);
+    return conv_dispatch(a, ksize, pool != 0, false, s);
 }
 
 // Stride-2 convolution (1x1, or 3x3 pad 1) + folded BatchNorm + residual + activation: torchvision's ResNet v1.5 strides inside
@@ -1454,56 +1518,16 @@ extern "C" int ec_conv_bf16_s2(const void* in, const void* w, const float* bias,
     if (Cin < 8 || Cin % 8 != 0 || Cout % 64 != 0) return EC_ERR_SHAPE;
     if (act != EC_ACT_RELU && act != EC_ACT_NONE) return EC_ERR_UNSUPPORTED;
     if (H >= 4096 || W >= 65536) return EC_ERR_SHAPE;
-    const int Ho = H / 2, Wo = W / 2;
     ConvArgs a;
-    a.in = (const uint16_t*)in;
-    a.w = (const uint16_t*)w;
-    a.bias = bias;
-    a.res = (const uint16_t*)res;
-    a.out = (uint16_t*)out;
-    a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ldo = Cout;
-    a.K = ksize * ksize * Cin;
-    a.M = B * Ho * Wo;
-    a.cin_log2 = (Cin & (Cin - 1)) == 0 ? ec_ilog2(Cin) : -1;
-    a.act = act;
-    a.ntn = 0;
-    if ((long)B * H * W * Cin * 2 >= (1L << 31) || (long)Cout * a.K * 2 >= (1L << 31)) return EC_ERR_SHAPE;
-    a.in_bytes = (unsigned)((long)B * H * W * Cin * 2);
-    a.w_bytes = (unsigned)((long)Cout * a.K * 2);
-    if (res && (long)B * Ho * Wo * Cout * 2 >= (1L << 32) - 16) return EC_ERR_SHAPE;
-    a.res_bytes = res ? (unsigned)((long)B * Ho * Wo * Cout * 2) : 0u;
-    hipStream_t s = (hipStream_t)stream;
-    // the 8-wave ping-pong kernel where the CLIP trunk's rule would take it (Cin % 64 == 0, K >= 512, enough tiles to fill the chip):
-    // 256-wide tiles from 150 tiles on, 128-wide ones when only those reach 150
-    if (Cin % 64 == 0 && a.K >= 512 && (ksize == 1 || a.cin_log2 >= 0) && ec_config().conv_big != 0) {
-        const long rt = (a.M + 255) / 256, nt256 = rt * (Cout / 256), nt128 = rt * (Cout / 128);
-        if (Cout % 256 == 0 && nt256 >= EC_CONV8_MIN_TILES_DEFAULT)
-            return ksize == 3 ? launch8<256, 3, false, false, true>(a, s) : launch8<256, 1, false, false, true>(a, s);
-        if (Cout % 128 == 0 && nt128 >= EC_CONV8_MIN_TILES_DEFAULT && (ksize == 3 || !res))
-            return ksize == 3 ? launch8<128, 3, false, false, true>(a, s) : launch8<128, 1, false, false, true>(a, s);
-    }
-    // 128 x 128 tiles (three workgroups per CU) where Cout allows, 64 x 64 ring tiles for launches that would leave CUs idle
-    if (Cout % 128 == 0) {
-        const long t128 = (long)((a.M + 127) / 128) * (Cout / 128);
-        if (t128 < ec_config().conv_t64 && a.K >= 512)       // (the CLIP trunk's rule: dispatch_tile)
-            return ksize == 3 ? launch<64, 64, 2, 2, 3, false, false, 64, 4, false, true>(a, s)
-                              : launch<64, 64, 2, 2, 1, false, false, 64, 4, false, true>(a, s);
-        if (t128 <= 256 && a.K >= 512 && !(ksize == 1 && res && a.K <= 256))   // one workgroup per CU: 8-wave ring tiles, pieces between the MFMAs
-            return ksize == 3 ? launch<128, 128, 2, 4, 3, false, false, 128, 3, true, true>(a, s)
-                              : launch<128, 128, 2, 4, 1, false, false, 128, 3, true, true>(a, s);
-        return ksize == 3 ? launch<128, 128, 2, 2, 3, false, false, 128, 0, false, true>(a, s)
-                          : launch<128, 128, 2, 2, 1, false, false, 128, 0, false, true>(a, s);
-    }
-    return ksize == 3 ? launch<256, 64, 4, 1, 3, false, false, 256, 0, false, true>(a, s)
-                      : launch<256, 64, 4, 1, 1, false, false, 256, 0, false, true>(a, s);
+    if (int rc = conv_args(a, in, w, bias, res, out, (long)B * H * W, H, W, Cin, Cout, ksize, (long)B * (H / 2) * (W / 2), Cout, act))
+        return rc;
+    return conv_dispatch(a, ksize, false, true, (hipStream_t)stream);
 }
 
 // out[M, N] (fp32) = act(A[M, K] (bf16) @ W^T + bias) with W given as three bf16 planes [N][3][K] (ec_split3_bf16):
 // the exact-fp32 product of a bf16 activation matrix with an fp32 weight matrix, on the 8-wave ping-pong kernel.
 // Replaces the resnet_compressor's first 1x1 conv over the stored features
 // (allenact_plugins/.../resnet_tensor... ResnetTensorGoalEncoder.resnet_compressor[0], SURVEY.md section 8 row a).
-int ec_gemm_bf16a_xp(const void* A, const void* Wplanes, const float* bias, float* out, long M, int N, int K, int act, int planes,
-                     ec_stream_t stream);
 extern "C" int ec_gemm_bf16a_x3(const void* A, const void* Wplanes, const float* bias, float* out, long M, int N, int K,
                                 int act, ec_stream_t stream) {
     return ec_gemm_bf16a_xp(A, Wplanes, bias, out, M, N, K, act, 3, stream);
@@ -1513,25 +1537,14 @@ int ec_gemm_bf16a_xp(const void* A, const void* Wplanes, const float* bias, floa
                      ec_stream_t stream) {
     if (!A || !Wplanes || !out || (planes != 2 && planes != 3)) return EC_ERR_ARG;
     if (M <= 0 || N % 128 != 0 || K % 64 != 0 || K < 64) return EC_ERR_SHAPE;
-    if ((long)N * 3 * K * 2 >= (1L << 31)) return EC_ERR_SHAPE;
     // 32-bit byte offsets inside a launch: rows are processed in slabs of < 4 GiB of A
     const long slab = (((1L << 32) - 1) / ((long)K * 2)) / 256 * 256;
     for (long r0 = 0; r0 < M; r0 += slab) {
         const long rows = (M - r0 < slab) ? M - r0 : slab;
         ConvArgs a;
-        a.in = (const uint16_t*)A + r0 * K;
-        a.w = (const uint16_t*)Wplanes;
-        a.bias = bias;
-        a.res = nullptr;
-        a.out = reinterpret_cast<uint16_t*>(out + r0 * N);
-        a.H = 1; a.W = (int)rows; a.Cin = K; a.Cout = N; a.ldo = N;
-        a.K = K; a.M = (int)rows;
-        a.cin_log2 = 0;
-        a.act = act;
-        a.ntn = 0;
-        a.in_bytes = (unsigned)(rows * K * 2);
-        a.w_bytes = (unsigned)((long)N * 3 * K * 2);
-        a.res_bytes = 0u;
+        if (int rc = conv_args(a, (const uint16_t*)A + r0 * K, Wplanes, bias, nullptr, out + r0 * N, rows, 1, (int)rows, K, N, 1, rows, N,
+                               act, 3))
+            return rc;
         int rc = planes == 3 ? launch8<128, 1, false, true>(a, (hipStream_t)stream)
                              : launch8<128, 1, false, true, false, 256, 2>(a, (hipStream_t)stream);
         if (rc != EC_OK) return rc;
@@ -1553,30 +1566,16 @@ int ec_gemm_bf16_ln8(const void* A, const void* Wt, const float* bias, const voi
     if (res && act == EC_ACT_QUICKGELU) return EC_ERR_UNSUPPORTED;
     if (ln_s && (res || !bias || !ln_stats || ln_np < 1 || ln_np > 8)) return EC_ERR_ARG;   // (plain calls -- the patch embedding -- may come without a bias)
     ConvArgs a;
-    a.in = (const uint16_t*)A;
-    a.w = (const uint16_t*)Wt;
-    a.bias = bias;
-    a.res = (const uint16_t*)res;
-    a.out = (uint16_t*)out;
-    a.H = 1; a.W = M; a.Cin = K; a.Cout = N; a.ldo = N;
-    a.K = K; a.M = M;
-    a.cin_log2 = 0;
-    a.act = act;
-    a.ntn = 0;
-    if ((long)M * K * 2 >= (1L << 31) || (long)N * K * 2 >= (1L << 31)) return EC_ERR_SHAPE;
-    a.in_bytes = (unsigned)((long)M * K * 2);
-    a.w_bytes = (unsigned)((long)N * K * 2);
-    if (res && (long)M * N * 2 >= (1L << 32) - 16) return EC_ERR_SHAPE;
-    a.res_bytes = res ? (unsigned)((long)M * N * 2) : 0u;
+    if (int rc = conv_args(a, A, Wt, bias, res, out, M, 1, M, K, N, 1, M, N, act)) return rc;
     a.ln_s = ln_s; a.ln_stats = ln_s ? ln_stats : nullptr; a.ln_np = ln_np; a.stats_out = stats_out;
+    const RouteSwitches sw = route_switches();
     // Tile width: 256 where it divides N and leaves at least 100 tiles (QKV / c_fc at 6,400 rows: 225 / 300), 128-wide
     // long-segment tiles otherwise (out_proj / c_proj: N = D).  Measured and rejected (same box, round 6): choosing the width by
     // rounds of workgroups -- c_fc as 600 narrow tiles (three half rounds) instead of 300 wide ones (two rounds, the second
     // 17 % full) -- loses alone (1.905 -> 1.969 ms per 128 frames) and with two launches in flight (81.1 -> 79.2 k
     // env-frames/s): the 256-wide tile is the cheaper one per flop.  EC_VIT_WIDE: 0 = always 128-wide, 2 = 256-wide wherever N allows.
     const long rt = (M + 255) / 256;
-    static const int wide_mode = [] { const char* e = getenv("EC_VIT_WIDE"); return e ? atoi(e) : 1; }();
-    bool wide = (N % 256 == 0) && ((wide_mode == 1 && rt * (N / 256) >= 100) || wide_mode == 2);
+    bool wide = (N % 256 == 0) && ((sw.vit_wide == 1 && rt * (N / 256) >= 100) || sw.vit_wide == 2);
     if (stats_out && N / 128 > 8 && N % 256 == 0) wide = true;        // (a producer's records must fit the consumer's 8 slots)
     if (stats_out && N / (wide ? 256 : 128) > 8) return EC_ERR_SHAPE;
     if (np_out) *np_out = N / (wide ? 256 : 128);
@@ -1585,9 +1584,8 @@ int ec_gemm_bf16_ln8(const void* A, const void* Wt, const float* bias, const voi
     // N = 768 at 6,400 rows is 150 tiles (one round on 59 % of the CUs) against 204 (one round at 0.75).  Same box, round 6: the
     // forward alone 1.905 -> 1.80 ms per 128 frames; with two launches in flight (whose idle CUs the other launch fills) neutral
     // (81.1 / 80.6 -> 81.1 / 80.7 k env-frames/s).  EC_VIT_BM192 = 0: off
-    static const int bm192 = [] { const char* e = getenv("EC_VIT_BM192"); return e ? atoi(e) : 1; }();
     const long t256 = rt * (N / 128), t192 = ((M + 191) / 192) * (long)(N / 128);
-    if (bm192 && ((t192 + 255) / 256) * 3 < ((t256 + 255) / 256) * 4)
+    if (sw.vit_bm192 && ((t192 + 255) / 256) * 3 < ((t256 + 255) / 256) * 4)
         return launch8<128, 1, false, false, false, 192>(a, (hipStream_t)stream);
     return launch8<128, 1, false>(a, (hipStream_t)stream);
 }
@@ -1599,20 +1597,6 @@ extern "C" int ec_gemm_bf16(const void* A, const void* Wt, const float* bias, co
     if (res && act == EC_ACT_QUICKGELU) return EC_ERR_UNSUPPORTED;
     // GEMM = 1x1 conv over a [1, 1, M] "image" with Cin = K (no power-of-two need: KS==1 never splits k).
     ConvArgs a;
-    a.in = (const uint16_t*)A;
-    a.w = (const uint16_t*)Wt;
-    a.bias = bias;
-    a.res = (const uint16_t*)res;
-    a.out = (uint16_t*)out;
-    a.H = 1; a.W = M; a.Cin = K; a.Cout = N; a.ldo = N;
-    a.K = K; a.M = M;
-    a.cin_log2 = 0;
-    a.act = act;
-    a.ntn = 0;
-    if ((long)M * K * 2 >= (1L << 31) || (long)N * K * 2 >= (1L << 31)) return EC_ERR_SHAPE;
-    a.in_bytes = (unsigned)((long)M * K * 2);
-    a.w_bytes = (unsigned)((long)N * K * 2);
-    if (res && (long)M * N * 2 >= (1L << 32) - 16) return EC_ERR_SHAPE;
-    a.res_bytes = res ? (unsigned)((long)M * N * 2) : 0u;
-    return dispatch_tile<1, false>(a, (hipStream_t)stream);
+    if (int rc = conv_args(a, A, Wt, bias, res, out, M, 1, M, K, N, 1, M, N, act)) return rc;
+    return conv_dispatch(a, 1, false, false, (hipStream_t)stream);
 }

@@ -22,10 +22,8 @@
 
 #include "common.h"
 
-// C++-linkage internals of the library (every extern "C" entry this file calls is declared in include/ec_amd.h, via common.h)
+// C++-linkage internal of the library (ec_gemm_bf16a_xp and every extern "C" entry this file calls are declared in common.h)
 int ec_dw_tn_xp(const void* dYplanes, const void* X, float* part, float* dW, long M, int NX, int planes, ec_stream_t stream);   // dw_tn.hip
-int ec_gemm_bf16a_xp(const void* A, const void* Wplanes, const float* bias, float* out, long M, int N, int K, int act, int planes,
-                     ec_stream_t stream);                                                                                        // conv_igemm.hip
 
 namespace {
 

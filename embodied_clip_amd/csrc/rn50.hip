@@ -72,11 +72,6 @@ constexpr int NBUF = 5;
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 }  // namespace
 
-extern "C" int ec_stem7_pool(const void* rgb, int u8, const float* h_mean3, const float* h_std3, const void* w,
-                             const float* bias, void* out, int B, int H, int W, ec_stream_t stream);
-extern "C" int ec_conv_bf16_s2(const void* in, const void* w, const float* bias, const void* res, void* out, int B, int H, int W,
-                               int Cin, int Cout, int ksize, int act, ec_stream_t stream);
-
 namespace {
 int pack_plan_weights(ec_rn50* h);
 int rn50_build(ec_rn50_t** out, bool tv, int width, const int* layers4, int input_resolution, const void* stem_w,
@@ -472,11 +467,6 @@ extern "C" size_t ec_rn50_workspace_bytes(const ec_rn50_t* h, int batch) {
     if (!h || batch <= 0) return 0;
     return NBUF * align_up(h->max_elems_per_frame * 2 * (size_t)batch, 256);
 }
-
-int ec_conv1x1_regw_pool(const void* a, const void* w, const float* bias, const void* res, void* y, void* y_pooled, int B, int H,
-                         int W, int K, int N, int act, int ld_pooled, hipStream_t s);   // conv_pair.hip
-extern "C" int ec_stem_conv1_u8(const uint8_t* rgb_u8, const float* mean3, const float* std3, const float* w,
-                                const float* bias, void* out, int B, int H, int W, int Cout, ec_stream_t stream);
 
 namespace {
 int rn50_run(const ec_rn50_t* h, const void* rgb, bool u8, const float* mean3, const float* std3, int batch,

@@ -23,10 +23,6 @@ extern "C" int ec_gemm_bf16(const void* A, const void* Wt, const float* bias, co
 
 extern "C" int ec_bf16_to_f32(const void* in, float* out, long rows, long row_len, long in_stride, ec_stream_t stream);
 
-// conv_igemm.hip: the 8-wave GEMM with LayerNorm folded in (consumer) / emitting the rows' LayerNorm records (producer)
-int ec_gemm_bf16_ln8(const void* A, const void* Wt, const float* bias, const void* res, void* out, int M, int N, int K, int act,
-                     const float* ln_s, const float* ln_stats, int ln_np, float* stats_out, int* np_out, ec_stream_t stream);
-
 namespace {
 
 __device__ __forceinline__ float wave_sum_f(float v) {

@@ -1,0 +1,186 @@
+// Launch recorder: which kernel instance, grid, block and dynamic LDS size does libec_amd.so launch for a call?  Host only, no
+// GPU and no HIP headers: this program DEFINES the HIP runtime entry points the library imports (`nm -D --undefined-only`),
+// loads the library with dlopen and drives it with fake device addresses.  Linked with -rdynamic, so the definitions here
+// come first in the library's symbol lookup.
+//
+//   c++ -O1 -std=c++17 -rdynamic -o launch_log tools/launch_log.cpp -ldl
+//   launch_log LIB [--args N] < commands
+//
+// Commands, one per line (tests/golden/make_conv_routes_golden.py writes them):
+//   conv  B H W Cin Cout ksize pool act res ldo     ec_conv_bf16 (ldo = 0) / ec_conv_bf16_ld
+//   s2    B H W Cin Cout ksize act res              ec_conv_bf16_s2
+//   gemm  M N K act res                             ec_gemm_bf16
+//   x3    M N K act                                 ec_gemm_bf16a_x3
+//   trunk clip50|tv50|tv18|vitb32 frames min_tiles  create + ec_*_set_conv8_min_tiles + one forward + destroy
+// Output: `K <kernel>` per registered kernel, then per command `C <command>`, one `L <kernel>|<grid>|<block>|<lds>` per
+// launch (with --args N: `|` + the first N bytes of the first kernel argument in hex, for the conv_igemm kernels) and `R <rc>`.
+#include <cxxabi.h>
+#include <dlfcn.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <map>
+#include <sstream>
+#include <string>
+#include <vector>
+
+struct dim3 { unsigned x, y, z; };
+
+static std::map<const void*, std::string> g_kernels;
+static struct { dim3 grid, block; size_t lds; void* stream; } g_cfg;
+static int g_dump_args = 0;
+static uintptr_t g_next = 0x100000000000ull;   // fake device addresses; never dereferenced
+static void* fake(size_t bytes) { void* p = (void*)g_next; g_next += (bytes + 0xfffff) & ~(size_t)0xfffff; return p; }
+
+extern "C" {
+void** __hipRegisterFatBinary(const void*) { static void* h; return &h; }
+void __hipUnregisterFatBinary(void**) {}
+void __hipRegisterFunction(void**, const void* host_fn, char*, const char* device_name, unsigned, void*, void*, void*, void*, int*) {
+    int st = 0;
+    char* d = abi::__cxa_demangle(device_name, nullptr, nullptr, &st);
+    g_kernels[host_fn] = st == 0 ? d : device_name;
+    free(d);
+}
+void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
+int __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, void* stream) { g_cfg = {grid, block, lds, stream}; return 0; }
+int __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* lds, void** stream) {
+    *grid = g_cfg.grid; *block = g_cfg.block; *lds = g_cfg.lds; *stream = g_cfg.stream;
+    return 0;
+}
+int hipLaunchKernel(const void* fn, dim3 g, dim3 b, void** args, size_t lds, void*) {
+    auto it = g_kernels.find(fn);
+    const std::string name = it == g_kernels.end() ? "?" : it->second;
+    printf("L %s|%u,%u,%u|%u,%u,%u|%zu", name.c_str(), g.x, g.y, g.z, b.x, b.y, b.z, lds);
+    if (g_dump_args && name.find("conv_igemm") != std::string::npos) {
+        printf("|");
+        for (int i = 0; i < g_dump_args; ++i) printf("%02x", ((const unsigned char*)args[0])[i]);
+    }
+    printf("\n");
+    return 0;
+}
+int hipGetLastError() { return 0; }
+int hipGetDevice(int* d) { *d = 0; return 0; }
+int hipFuncSetAttribute(const void*, int, int) { return 0; }
+int hipMalloc(void** p, size_t n) { *p = fake(n); return 0; }
+int hipFree(void*) { return 0; }
+int hipMemcpy(void*, const void*, size_t, int) { return 0; }
+int hipMemcpy2D(void*, size_t, const void*, size_t, size_t, size_t, int) { return 0; }
+int hipMemcpyAsync(void*, const void*, size_t, int, void*) { return 0; }
+int hipMemsetAsync(void*, int, size_t, void*) { return 0; }
+int hipDeviceSynchronize() { return 0; }
+int hipStreamSynchronize(void*) { return 0; }
+int hipStreamWaitEvent(void*, void*, unsigned) { return 0; }
+int hipEventCreate(void** e) { *e = nullptr; return 0; }
+int hipEventDestroy(void*) { return 0; }
+int hipEventRecord(void*, void*) { return 0; }
+int hipEventElapsedTime(float* ms, void*, void*) { *ms = 1.f; return 0; }
+}
+
+static void* g_lib;
+template <class F>
+static F sym(const char* name) {
+    void* p = dlsym(g_lib, name);
+    if (!p) { fprintf(stderr, "launch_log: %s not found\n", name); exit(2); }
+    return (F)p;
+}
+
+// weight / bias element counts of the Bottleneck (expansion 4) and BasicBlock (expansion 1) layers, in the order ec_amd.h documents
+static void resnet_counts(const int* layers, bool basic, size_t& nw, size_t& nb) {
+    size_t in = 64;
+    for (int l = 0; l < 4; ++l) {
+        const size_t p = (size_t)64 << l, out = basic ? p : 4 * p;
+        for (int b = 0; b < layers[l]; ++b) {
+            nw += basic ? p * 9 * in + p * 9 * p : p * in + p * 9 * p + out * p;
+            nb += basic ? 2 * p : 2 * p + out;
+            if (b == 0 && (in != out || (l > 0))) { nw += out * in; nb += out; }
+            in = out;
+        }
+    }
+}
+
+static int run_trunk(const std::string& kind, int frames, int min_tiles) {
+    typedef void* P;
+    void* h = nullptr;
+    int rc;
+    const P w = fake(1u << 30), f = fake(1u << 28), stem = fake(1u << 20), rgb = fake(1u << 30), out = fake(1u << 30);
+    if (kind == "vitb32") {
+        const size_t D = 768, Kp = 32 * 32 * 3, L = 50, layers = 11;
+        rc = sym<int (*)(P*, int, int, int, int, int, P, size_t, P, size_t)>("ec_vit_create")(
+            &h, (int)D, (int)layers, 12, 32, 224, w, D * Kp + layers * 12 * D * D, f, D + L * D + 2 * D + layers * 13 * D);
+        if (rc) return rc;
+        sym<int (*)(P, int)>("ec_vit_set_conv8_min_tiles")(h, min_tiles);
+        const size_t ws = sym<size_t (*)(P, int)>("ec_vit_workspace_bytes")(h, frames);
+        rc = sym<int (*)(P, P, int, P, size_t, P, P)>("ec_vit_forward")(h, rgb, frames, fake(ws), ws, out, nullptr);
+        sym<void (*)(P)>("ec_vit_destroy")(h);
+        return rc;
+    }
+    const bool basic = kind == "tv18";
+    const int l50[4] = {3, 4, 6, 3}, l18[4] = {2, 2, 2, 2};
+    const int* layers = basic ? l18 : l50;
+    size_t nw = 0, nb = 0;
+    resnet_counts(layers, basic, nw, nb);
+    if (kind == "clip50")   // + stem conv2 [32][9*32], conv3 [64][9*32]; biases of stem conv1..3
+        rc = sym<int (*)(P*, int, const int*, int, P, P, size_t, P, size_t)>("ec_rn50_create")(
+            &h, 64, layers, 224, stem, w, nw + 32 * 288 + 64 * 288, f, nb + 32 + 32 + 64);
+    else
+        rc = sym<int (*)(P*, const int*, int, P, P, size_t, P, size_t)>(basic ? "ec_tvresnet_basic_create" : "ec_rn50tv_create")(
+            &h, layers, 224, stem, w, nw, f, nb + 64);
+    if (rc) return rc;
+    sym<int (*)(P, int)>("ec_rn50_set_conv8_min_tiles")(h, min_tiles);
+    const size_t ws = sym<size_t (*)(P, int)>("ec_rn50_workspace_bytes")(h, frames);
+    rc = sym<int (*)(P, P, int, P, size_t, P, int, P)>("ec_rn50_forward")(h, rgb, frames, fake(ws), ws, out, 0, nullptr);
+    sym<void (*)(P)>("ec_rn50_destroy")(h);
+    return rc;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 2) { fprintf(stderr, "usage: launch_log LIB [--args N] < commands\n"); return 2; }
+    if (argc >= 4 && !strcmp(argv[2], "--args")) g_dump_args = atoi(argv[3]);
+    g_lib = dlopen(argv[1], RTLD_NOW | RTLD_LOCAL);
+    if (!g_lib) { fprintf(stderr, "launch_log: %s\n", dlerror()); return 2; }
+    {
+        std::vector<std::string> names;
+        for (auto& k : g_kernels) names.push_back(k.second);
+        for (auto& n : names) printf("K %s\n", n.c_str());
+    }
+    typedef void* P;
+    const P in = fake(1), w = fake(1), bias = fake(1), resb = fake(1), out = fake(1);
+    char line[256];
+    while (fgets(line, sizeof line, stdin)) {
+        std::istringstream ss(line);
+        std::string cmd;
+        if (!(ss >> cmd)) continue;
+        line[strcspn(line, "\n")] = 0;
+        printf("C %s\n", line);
+        int v[10] = {0}, n = 0, rc = -100;
+        std::string kind;
+        if (cmd == "trunk") ss >> kind;
+        while (n < 10 && ss >> v[n]) ++n;
+        if (cmd == "conv" && n == 10) {
+            const P r = v[8] ? resb : nullptr;
+            if (v[9] == 0)
+                rc = sym<int (*)(P, P, P, P, P, int, int, int, int, int, int, int, int, P)>("ec_conv_bf16")(
+                    in, w, bias, r, out, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], nullptr);
+            else
+                rc = sym<int (*)(P, P, P, P, P, int, int, int, int, int, int, int, int, int, P)>("ec_conv_bf16_ld")(
+                    in, w, bias, r, out, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[9], nullptr);
+        } else if (cmd == "s2" && n == 8) {
+            rc = sym<int (*)(P, P, P, P, P, int, int, int, int, int, int, int, P)>("ec_conv_bf16_s2")(
+                in, w, bias, v[7] ? resb : nullptr, out, v[0], v[1], v[2], v[3], v[4], v[5], v[6], nullptr);
+        } else if (cmd == "gemm" && n == 5) {
+            rc = sym<int (*)(P, P, P, P, P, int, int, int, int, P)>("ec_gemm_bf16")(in, w, bias, v[4] ? resb : nullptr, out, v[0], v[1],
+                                                                                   v[2], v[3], nullptr);
+        } else if (cmd == "x3" && n == 4) {
+            rc = sym<int (*)(P, P, P, P, long, int, int, int, P)>("ec_gemm_bf16a_x3")(in, w, bias, out, (long)v[0], v[1], v[2], v[3], nullptr);
+        } else if (cmd == "trunk" && n == 2) {
+            rc = run_trunk(kind, v[0], v[1]);
+        } else {
+            fprintf(stderr, "launch_log: bad command: %s\n", line);
+            return 2;
+        }
+        printf("R %d\n", rc);
+    }
+    return 0;
+}
