@@ -94,6 +94,10 @@ SIGNATURES = {
                                    c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
     "ec_policy_act": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
                       + [C.c_uint64, C.c_uint64, c_int, c_void_p]),
+    "ec_policy_forward_vec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                      c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
+    "ec_policy_act_vec": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
+                          + [C.c_uint64, C.c_uint64, c_int, c_void_p]),
     "ec_policy_backward2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "ec_policy_backward3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t,
@@ -125,7 +129,7 @@ SIGNATURES = {
 
 class PolicyCfg(C.Structure):
     _fields_ = [(n, c_int) for n in ("in_channels", "spatial", "hidden", "goal_dims", "num_goals", "num_actions",
-                                     "compress_hid", "compress_out", "comb_hid", "comb_out", "fusion", "dual")]
+                                     "compress_hid", "compress_out", "comb_hid", "comb_out", "fusion", "dual", "goal_in")]
 
 _lib = None
 

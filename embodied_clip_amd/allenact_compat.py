@@ -250,6 +250,8 @@ _PATCH_TARGETS = (
     ("allenact_plugins.clip_plugin.clip_preprocessors", ("ClipResNetPreprocessor", "ClipViTPreprocessor")),
     ("projects.objectnav_baselines.models.object_nav_models", ("ResnetTensorObjectNavActorCritic",)),
     ("allenact_plugins.robothor_plugin.robothor_models", ("ResnetTensorObjectNavActorCritic",)),
+    # Habitat PointNav (readme_files/baselines_habitat.md:64,85-86): [U] projects/pointnav_baselines/models/point_nav_models.py
+    ("projects.pointnav_baselines.models.point_nav_models", ("ResnetTensorPointNavActorCritic",)),
     ("allenact.algorithms.onpolicy_sync.losses.ppo", ("PPO",)),
     ("allenact.algorithms.onpolicy_sync.losses", ("PPO",)),
     # the ImageNet baselines (objectnav_robothor_rgb_resnet{18,50}gru_ddppo: readme_files/imagenet_vs_objectnav.md,
@@ -268,7 +270,8 @@ def install_into_allenact(verbose: bool = False) -> List[str]:
     from . import policy as pol
     from . import ppo
     ours = {"ClipResNetPreprocessor": cp.ClipResNetPreprocessor, "ClipViTPreprocessor": cp.ClipViTPreprocessor,
-            "ResnetTensorObjectNavActorCritic": pol.ResnetTensorObjectNavActorCritic, "PPO": ppo.PPO,
+            "ResnetTensorObjectNavActorCritic": pol.ResnetTensorObjectNavActorCritic,
+            "ResnetTensorPointNavActorCritic": pol.ResnetTensorPointNavActorCritic, "PPO": ppo.PPO,
             "ResNetPreprocessor": ip.ResNetPreprocessor}
     done = []
     for modname, attrs in _PATCH_TARGETS:
@@ -277,7 +280,7 @@ def install_into_allenact(verbose: bool = False) -> List[str]:
         except Exception:  # noqa: BLE001 - optional module
             continue
         for a in attrs:
-            if hasattr(mod, a) or modname.endswith(("clip_preprocessors", "object_nav_models")):
+            if hasattr(mod, a) or modname.endswith(("clip_preprocessors", "object_nav_models", "point_nav_models")):
                 setattr(mod, a, ours[a])
                 done.append(f"{modname}.{a}")
     if verbose:

@@ -649,6 +649,127 @@ __global__ void group_sum_scatter_kernel(const float* __restrict__ dm1, const in
     }
 }
 
+// ---- coordinate goals (ec_policy_cfg.goal_in > 0; [U] ResnetTensorPointNavActorCritic: embed_goal = nn.Linear(goal_in, goal_dims)) ----
+// A goal that is a vector per frame cannot be tabulated: the goal half of target_obs_combiner.0 becomes a PER-FRAME bias row
+//     Eg[b, :]  = goal_vec[b, :] Wc^T + bc                 [B, goal_dims]
+//     E1f[b, :] = Eg[b, :] W3[:, co:]^T + b3               [B, comb_hid]
+// that the combiner's first stage adds to the rows of frame b.  One launch per forward call, every mode: both products are
+// fmaf chains over a frame's own values in a fixed order, so a frame's row does not depend on the batch it arrives in, and
+// nothing goal-derived is ever cached.  FR frames per pass of a workgroup; W3[:, co:], Wc and the biases sit in LDS.
+constexpr int GV_FR = 8;
+__global__ __launch_bounds__(256) void goal_vec_fwd_kernel(const float* __restrict__ gv, const float* __restrict__ Wc,
+                                                          const float* __restrict__ bc, const float* __restrict__ W3b, int w3_ld,
+                                                          const float* __restrict__ b3, float* __restrict__ Eg,
+                                                          float* __restrict__ E1f, long B, int gin, int gd, int ch) {
+    extern __shared__ float gsm_[];
+    float* sW3 = gsm_;                       // [ch][gd + 1]
+    float* sWc = sW3 + ch * (gd + 1);        // [gd][gin]
+    float* sbc = sWc + gd * gin;             // [gd]
+    float* sb3 = sbc + gd;                   // [ch]
+    float* sEg = sb3 + ch;                   // [GV_FR][gd]
+    const int tid = threadIdx.x;
+    for (int i = tid; i < ch * gd; i += 256) sW3[(i / gd) * (gd + 1) + i % gd] = W3b[(long)(i / gd) * w3_ld + i % gd];
+    for (int i = tid; i < gd * gin; i += 256) sWc[i] = Wc[i];
+    for (int i = tid; i < gd; i += 256) sbc[i] = bc[i];
+    for (int i = tid; i < ch; i += 256) sb3[i] = b3[i];
+    for (long b0 = (long)blockIdx.x * GV_FR; b0 < B; b0 += (long)gridDim.x * GV_FR) {
+        const int nf = (int)min((long)GV_FR, B - b0);
+        __syncthreads();                     // the tables are staged / the previous pass has read sEg
+        for (int e = tid; e < nf * gd; e += 256) {
+            const int f = e / gd, j = e - f * gd;
+            const float* g = gv + (b0 + f) * gin;
+            float v = sbc[j];
+            for (int q = 0; q < gin; ++q) v = fmaf(g[q], sWc[j * gin + q], v);
+            sEg[e] = v;
+            Eg[(b0 + f) * gd + j] = v;
+        }
+        __syncthreads();
+        for (int e = tid; e < nf * ch; e += 256) {
+            const int f = e / ch, n = e - f * ch;
+            float v = sb3[n];
+            for (int j = 0; j < gd; ++j) v = fmaf(sEg[f * gd + j], sW3[n * (gd + 1) + j], v);
+            E1f[(b0 + f) * ch + n] = v;
+        }
+    }
+}
+// dEg[b, j] = sum_n dE1f[b, n] W3[n, co + j]   (n ascending: one thread per output, no atomics)
+__global__ __launch_bounds__(256) void goal_vec_bwd_kernel(const float* __restrict__ dE1f, const float* __restrict__ W3b, int w3_ld,
+                                                          float* __restrict__ dEg, long B, int gd, int ch) {
+    extern __shared__ float gsm_[];
+    float* sW3 = gsm_;                       // [ch][gd + 1]
+    float* sD = sW3 + ch * (gd + 1);         // [GV_FR][ch]
+    const int tid = threadIdx.x;
+    for (int i = tid; i < ch * gd; i += 256) sW3[(i / gd) * (gd + 1) + i % gd] = W3b[(long)(i / gd) * w3_ld + i % gd];
+    for (long b0 = (long)blockIdx.x * GV_FR; b0 < B; b0 += (long)gridDim.x * GV_FR) {
+        const int nf = (int)min((long)GV_FR, B - b0);
+        __syncthreads();
+        for (int e = tid; e < nf * ch; e += 256) sD[e] = dE1f[b0 * ch + e];
+        __syncthreads();
+        for (int e = tid; e < nf * gd; e += 256) {
+            const int f = e / gd, j = e - f * gd;
+            float v = 0.f;
+            for (int n = 0; n < ch; ++n) v = fmaf(sD[f * ch + n], sW3[n * (gd + 1) + j], v);
+            dEg[(b0 + f) * gd + j] = v;
+        }
+    }
+}
+// dE1f[b, n] = sum over the tiles that hold rows of frame b, in tile order, of the segment sums tail_bwd_kernel<true> left:
+// seg[t][0] = column sums of dm1 over the rows of tile t that belong to the frame its first row is in, seg[t][1] = over the
+// rest (the next frame: S >= 32, so a 32-row tile touches at most two frames)
+__global__ __launch_bounds__(128) void seg_fold_kernel(const float* __restrict__ seg, float* __restrict__ dE1f, int S, long B) {
+    const long b = blockIdx.x;
+    const int n = threadIdx.x;
+    const long t0 = b * S / 32, t1 = ((b + 1) * S - 1) / 32;
+    float s = 0.f;
+    for (long t = t0; t <= t1; ++t) s += seg[(t * 2 + ((t * 32) / S == b ? 0 : 1)) * 128 + n];
+    dE1f[b * 128 + n] = s;
+}
+// the same off a materialised dm1 (the unfused tail): dE1f[b, n] = sum_p dm1[(b*S + p)*N + n]
+__global__ void frame_sum_kernel(const float* __restrict__ dm1, float* __restrict__ dE1f, int S, int N) {
+    const long b = blockIdx.x;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const float* p = dm1 + b * S * N + n;
+        float s = 0.f;
+        for (int q = 0; q < S; ++q) s += p[(long)q * N];
+        dE1f[b * N + n] = s;
+    }
+}
+// part[y][m*No + n] = sum over row block y (rows ascending) of A[r*lda + m] X[r*ldx + n]: the small weight gradients of the
+// goal half (dW3[:, co:] = dE1f^T Eg, dWc = dEg^T goal_vec) over all T*N frames; splitk_fold_kernel adds the row blocks in
+// order onto the gradient.  32 rows at a time through LDS, 16 outputs per thread and sweep.
+__global__ __launch_bounds__(256) void tn_small_part_kernel(const float* __restrict__ A, int lda, const float* __restrict__ X, int ldx,
+                                                           float* __restrict__ part, int Mo, int No, long K, int rows_per_block) {
+    extern __shared__ float gsm_[];
+    float* sA = gsm_;                        // [32][Mo]
+    float* sX = sA + 32 * Mo;                // [32][No]
+    const int tid = threadIdx.x, ne = Mo * No;
+    const long r0 = (long)blockIdx.x * rows_per_block, r1 = min(K, r0 + rows_per_block);
+    for (int e0 = 0; e0 < ne; e0 += 4096) {
+        float acc[16];
+        int am[16], an[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int e = min(e0 + tid + 256 * q, ne - 1);
+            acc[q] = 0.f; am[q] = e / No; an[q] = e - am[q] * No;
+        }
+        for (long c0 = r0; c0 < r1; c0 += 32) {
+            const int nr = (int)min((long)32, r1 - c0);
+            __syncthreads();
+            for (int i = tid; i < nr * Mo; i += 256) sA[i] = A[(c0 + i / Mo) * lda + i % Mo];
+            for (int i = tid; i < nr * No; i += 256) sX[i] = X[(c0 + i / No) * ldx + i % No];
+            __syncthreads();
+            for (int r = 0; r < nr; ++r)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) acc[q] = fmaf(sA[r * Mo + am[q]], sX[r * No + an[q]], acc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int e = e0 + tid + 256 * q;
+            if (e < ne && e < e0 + 4096) part[(long)blockIdx.x * ne + e] = acc[q];
+        }
+    }
+}
+
 // zero-shot fusion: x[b, :] = feat[b, :] / |feat[b, :]| * table[goal[b], :]   (one wave per row; fp32 statistics)
 template <bool BF16>
 __global__ __launch_bounds__(256) void fuse_goal_kernel(const void* __restrict__ feat, const float* __restrict__ table,
@@ -832,6 +953,11 @@ __global__ __launch_bounds__(512) void c1_act_kernel(const uint16_t* __restrict_
 constexpr int ACT_PARTS = 4, ACT_MAX_ROWS = 16384;   // act step: split-K factor of the two long-K GEMMs / row limit of that path
 constexpr int TL_P128 = 132, TL_P32 = 36;     // LDS row pitches (floats): 16-byte slots of 16 consecutive rows differ
 
+// VEC (coordinate goals, goal_in > 0): E1 is the per-frame bias E1f [M / S][128] and stays in global memory (16.8 MB at
+// 32,768 frames: L2-resident next to the c1 stream); no table is staged (num_goals == 0) and `goal` is not read.  A 32-row
+// tile touches at most two frames (S >= 32 on this variant): their two bias rows are fetched with the next c1 tile, ahead of
+// the contractions, and the epilogue picks one by row.
+template <bool VEC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void tail_fwd_kernel(const float* __restrict__ c1, const float* __restrict__ W2,
                                                          const float* __restrict__ b2, const float* __restrict__ W3,
                                                          int w3_ld, const float* __restrict__ E1,
@@ -911,6 +1037,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const int idx = lane + 64 * q, r = idx >> 5, c4 = idx & 31;
             st[q] = *reinterpret_cast<const f32x4_t*>(c1 + min((tile + tstep) * 32 + r, M - 1) * 128 + c4 * 4);
         }
+        float ef0[4], ef1[4];                                      // VEC: this tile's two bias rows (columns jt * 32 + i)
+        (void)ef0; (void)ef1; (void)last_row;
+        if constexpr (VEC) {
+            const long nframes = M / S;
+            const float* e0 = E1 + min(grp_base, nframes - 1) * 128 + i;
+            const float* e1 = E1 + min(grp_base + 1, nframes - 1) * 128 + i;
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) { ef0[jt] = e0[jt * 32]; ef1[jt] = e1[jt * 32]; }
+        }
         if (fold) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
@@ -966,6 +1101,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * hh;
+            if constexpr (VEC) {
+                const bool first = grp_rem + row < S;                // rows of the frame the tile starts in
+#pragma unroll
+                for (int jt = 0; jt < 4; ++jt)
+                    T1[row * TL_P128 + jt * 32 + i] = fmaxf(am[jt][r] + (first ? ef0[jt] : ef1[jt]), 0.f);
+            } else {
             // row group (actor-step) of this row in 32-bit arithmetic: a 64-bit division per element would cost more than the MFMAs
             const unsigned trow = min((unsigned)(grp_rem + row), (unsigned)(grp_rem + last_row));
             int g = goal[(grp_base + (long)(trow / (unsigned)S)) * gstride];   // (gstride 2: the low words of the caller's int64 ids)
@@ -974,6 +1115,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
             for (int jt = 0; jt < 4; ++jt)
                 T1[row * TL_P128 + jt * 32 + i] = fmaxf(am[jt][r] + e[jt * 32], 0.f);   // (the c1 tile is dead by now)
+            }
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -1027,6 +1169,12 @@ constexpr int TB_MAXG = 16;                       // goal rows of the per-wave d
 constexpr int TB_W = 3 * 4096;                    // dW4 [32][128], dW3a [128][32], dW2 [32][128]
 constexpr int TB_PART = TB_W + 64 + 64 + 256;     // + db4, db2 (two lane halves each), db1 (two halves)
 
+// VEC (coordinate goals): there is no goal table to accumulate into -- the gradient of the per-frame bias is dE1f[b] = the sum of
+// dm1 over the 49 rows of frame b, which span up to three tiles owned by different waves.  The tile's two row-group sums (the
+// same two 128-float lines the table variant forms) leave as they are, partE[tile][2][128]; seg_fold_kernel adds a frame's
+// segments in tile order.  8 floats of extra traffic per row against the ~1,300 B the tile already moves, no atomics, and no
+// second pass over m1 / dx4 as a per-frame kernel would need.
+template <bool VEC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void tail_bwd_kernel(
     const float* __restrict__ dx4, const float* __restrict__ m1, const float* __restrict__ c2, const float* __restrict__ c1,
     const float* __restrict__ W2, const float* __restrict__ W3, int w3_ld, const float* __restrict__ W4,
@@ -1053,9 +1201,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // into PER-WAVE register tables regE[goal][2] (lane owns columns lane, lane + 64; the goal ids are wave-uniform, the
     // table update is 16 predicated adds) -- a wave folds its tiles in a fixed order, one table per wave leaves the kernel.
     float* sEw = sE + wave * 256;
-    float regE[TB_MAXG][2];
+    float regE[VEC ? 1 : TB_MAXG][2];
+    if constexpr (!VEC) {
 #pragma unroll
     for (int g = 0; g < TB_MAXG; ++g) { regE[g][0] = 0.f; regE[g][1] = 0.f; }
+    }
 
     const int i = lane & 31, hh = lane >> 5;
     const long ntiles = (M + 31) / 32;
@@ -1118,9 +1268,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         // ---- dm1 = (dx4 W4) * [m1 > 0] -> Tm;  dE1 row-group sums (one 32-column tile at a time: 16 live accumulators) ----
         {
-            int g0 = goal[min(grp_base, ngroups - 1)], g1 = goal[min(grp_base + 1, ngroups - 1)];
+            int g0 = 0, g1 = 0;
+            if constexpr (!VEC) {
+            g0 = goal[min(grp_base, ngroups - 1)]; g1 = goal[min(grp_base + 1, ngroups - 1)];
             g0 = g0 < 0 ? 0 : (g0 >= num_goals ? num_goals - 1 : g0);
             g1 = g1 < 0 ? 0 : (g1 >= num_goals ? num_goals - 1 : g1);
+            }
 #pragma unroll 1
             for (int jt = 0; jt < 4; ++jt) {
                 f32x16_t acc;
@@ -1146,8 +1299,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
                 e0 += __shfl_xor(e0, 32, 64);                        // the two lane halves hold the column's rows 4 hh .. : add them
                 e1 += __shfl_xor(e1, 32, 64);
+                if constexpr (VEC) {                                 // the two segment sums of this tile, straight to partE[tile][2][128]
+                    if (hh == 0) { partE[tile * 256 + jt * 32 + i] = e0; partE[tile * 256 + 128 + jt * 32 + i] = e1; }
+                } else {
                 if (hh == 0) { sEw[jt * 32 + i] = e0; sEw[128 + jt * 32 + i] = e1; }
+                }
             }
+            (void)g0; (void)g1; (void)ngroups; (void)sEw;
+            if constexpr (!VEC) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
             const float c0a = sEw[lane], c0b = sEw[64 + lane], c1a = sEw[128 + lane], c1b = sEw[192 + lane];
@@ -1159,6 +1318,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (the line is rewritten by the next tile)
             __builtin_amdgcn_wave_barrier();
+            }
         }
         // ---- stage c2 (dx4 is dead); fetch the next tile's dx4 ----
 #pragma unroll
@@ -1287,10 +1447,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     pp[TB_W + 64 + hh * 32 + i] = db2p;
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) pp[TB_W + 128 + hh * 128 + jt * 32 + i] = db1p[jt];
+    if constexpr (!VEC) {
     float* pe = partE + ((long)blockIdx.x * 4 + wave) * num_goals * 128;
 #pragma unroll
     for (int g = 0; g < TB_MAXG; ++g)
         if (g < num_goals) { pe[g * 128 + lane] = regE[g][0]; pe[g * 128 + 64 + lane] = regE[g][1]; }
+    }
 }
 
 // folds the per-wave partial sets of tail_bwd_kernel into the gradient tensors (grads +=, dE1 +=).  Two stages, no atomics:
@@ -1364,14 +1526,17 @@ inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
 
 enum { P_EMB, P_W1, P_B1, P_W2, P_B2, P_W3, P_B3, P_W4, P_B4, P_WIH, P_WHH, P_BIH, P_BHH, P_WA, P_BA, P_WC, P_BC,
        // dual (RGB + depth) encoder: the depth stream's compressor / combiner, same shapes as P_W1 .. P_B4
-       P_W1D, P_B1D, P_W2D, P_B2D, P_W3D, P_B3D, P_W4D, P_B4D, P_COUNT };
-constexpr int P_COUNT_SINGLE = P_BC + 1;
+       P_W1D, P_B1D, P_W2D, P_B2D, P_W3D, P_B3D, P_W4D, P_B4D,
+       // coordinate goals (goal_in > 0): P_EMB is embed_goal.weight [goal_dims, goal_in], P_GB is embed_goal.bias, second in the flat order
+       P_GB, P_COUNT };
+constexpr int P_COUNT_SINGLE = P_BC + 1, P_COUNT_DUAL = P_B4D + 1, P_COUNT_VEC = P_COUNT_SINGLE + 1;
 
 }  // namespace
 
 struct ec_policy {
     ec_policy_cfg c;
     size_t off[P_COUNT], num[P_COUNT], total;
+    int order[P_COUNT], ntensors;        // the flat buffer's tensor order (what ec_policy_param_offset's idx counts)
     const float* goal_table = nullptr;   // fusion == 1: borrowed f32 [num_goals, in_channels]
     // EC_POLICY_INFER_REUSE bookkeeping: the key of the launch plan (make_plan) that built the weight-derived tables in a given
     // act workspace.  Which tables exist and where (E1, W1's planes in fragment order, the re-ordered weight_ih and its
@@ -1507,7 +1672,12 @@ struct Ws {   // float offsets into the workspace
     // act step: weight_ih in pixel-major column order (valid while E1 is); the same / W1's planes in MFMA-FRAGMENT order (gi_act_kernel / c1_act_kernel)
     size_t wihA, wihF, w1pF;
     size_t dhs, dhc, dgi, dghb, dx, dx4, dm1, dc2, dc1, dE1, tpart, tpartE, whhT, wihP, gwihP, tA, tB, end;
+    // coordinate goals (all empty with goal_in == 0): the per-frame bias rows and the goal embeddings of this call; the learn
+    // pass's copy of the goal vectors; the backward's dE1f / dEg, the tail's per-tile segment sums, the row-block partials of
+    // the two small weight gradients
+    size_t E1f, Eg, gvec, dE1f, dEg, tseg, gpart;
 };
+constexpr int GP_MAXY = 64;                   // row blocks of tn_small_part_kernel
 
 enum class C1 { pingpong, act_kernel, split_parts, plain };      // compressor conv 1
 enum class Gi { act7, act8, split_parts, plain };                // GRU input projection (act7 / act8: gi_act_kernel<7 | 8>)
@@ -1516,6 +1686,7 @@ enum class Step { gemm_gates, fused32, fused16 };                // a recurrence
 
 struct Plan {
     Geo g;
+    bool vec;                     // coordinate goals (goal_in > 0): per-frame bias rows instead of the goal-id table
     bool infer, feat_bf16;        // infer: EC_POLICY_INFER or _REUSE (stated by the caller, never inferred from the workspace size)
     ec_policy::Built key;         // what a REUSE call must match
     int act_parts;                // partial matrices the c1 / gi areas hold: ACT_PARTS for the act step's few rows, else 1
@@ -1572,6 +1743,12 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
     w.wihP = take_if(bwd, wih); w.gwihP = take_if(bwd, wih);                              // weight_ih in pixel-major column order (EC_WIH_PERM) and its gradient
     w.tA = take_if(bwd, B * 3 * H);                                                       // transposed operands of the GRU's weight-gradient GEMMs
     w.tB = take_if(bwd, B * (flat > H ? flat : H));
+    const bool vec = c.goal_in > 0;
+    w.E1f = take_if(vec, B * c.comb_hid); w.Eg = take_if(vec, B * c.goal_dims);
+    w.gvec = take_if(vec && bwd, B * c.goal_in);
+    w.dE1f = take_if(vec && bwd, B * c.comb_hid); w.dEg = take_if(vec && bwd, B * c.goal_dims);
+    w.tseg = take_if(vec && bwd, (M49 + 31) / 32 * 256);
+    w.gpart = take_if(vec && bwd, (size_t)GP_MAXY * c.comb_hid * c.goal_dims);
     w.end = o;
     return w;
 }
@@ -1588,7 +1765,7 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     g.H = c.hidden; g.A = c.num_actions; g.A1 = g.A + 1; g.C = c.in_channels; g.cat = c.compress_out + c.goal_dims;
     g.nstream = (c.dual && !c.fusion) ? 2 : 1; g.flat1 = c.comb_out * g.S; g.flat = c.fusion ? c.in_channels : g.nstream * g.flat1;
     const int B = g.B, S = g.S, M49 = g.M49, H = g.H, C = g.C, flat = g.flat;
-    p.infer = mode != EC_POLICY_LEARN; p.feat_bf16 = feat_bf16;
+    p.infer = mode != EC_POLICY_LEARN; p.feat_bf16 = feat_bf16; p.vec = c.goal_in > 0;
     p.key = ec_policy::Built{T, N, feat_bf16 ? 1 : 0};
     // Act step: so few rows that the two long-K, small-M GEMMs (compressor conv 1, GRU input projection) run as ACT_PARTS K
     // slices whose partial matrices the consuming kernels fold in a fixed order (no float atomics: rollouts stay bit-reproducible)
@@ -1598,11 +1775,11 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     // EC_TAIL_FUSED (default 1): the fused tail kernels are written for the reference's widths
     const bool tail_widths = cfg.tail_fused && !c.fusion && c.compress_hid == 128 && c.compress_out == 32 && c.comb_hid == 128 && c.comb_out == 32;
     p.tail_fwd_lds = ((size_t)2 * 32 * TL_P128 + 128 * TL_P32 + (size_t)c.num_goals * 128 + 64 + 4 * (size_t)(32 * TL_P128 + 32 * TL_P32)) * sizeof(float);
-    p.tail_fwd = tail_widths && p.tail_fwd_lds <= LDS_LIMIT;
+    p.tail_fwd = tail_widths && p.tail_fwd_lds <= LDS_LIMIT && (!p.vec || S >= 32);   // (vec: a tile spans at most two frames; else the GEMM route)
     p.tail_bwd_lds = ((size_t)2 * 128 * TL_P32 + 32 * TL_P128 + std::max<size_t>((size_t)c.num_goals * 128, 4 * 256) +
                       4 * (size_t)(32 * TL_P128 + 32 * TL_P32)) * sizeof(float);   // (the sE area: four wave-private 256-float lines)
     p.tail_bwd = tail_widths && S >= 32 && p.tail_bwd_lds <= LDS_LIMIT && c.num_goals <= TB_MAXG;
-    p.goal_direct = p.infer && p.tail_fwd; p.hs_direct = p.infer && T == 1;
+    p.goal_direct = p.infer && p.tail_fwd && !p.vec; p.hs_direct = p.infer && T == 1;
     // EC_WIH_PERM: the GRU's input projection reads the combiner output where it lies (pixel-major rows) against a re-ordered weight_ih
     // (permute_row_kernel, one row in LDS), no activation transposes.  Learn pass: per call; act step: by the first call after a parameter
     // update, kept in the workspace like E1
@@ -1679,6 +1856,21 @@ struct Fwd : Ctx {
     const int* goal_ids = nullptr;   // int32 ids in the workspace, or (goal_direct) the caller's int64 ids
     bool reuse = false;              // EC_POLICY_INFER_REUSE, and this workspace holds the tables of this plan
 
+    // coordinate goals: this call's per-frame bias rows (and, for a backward, the goal vectors and embeddings it will need)
+    static size_t goal_vec_lds(const ec_policy_cfg& c, bool bwd) {
+        const size_t w3 = (size_t)c.comb_hid * (c.goal_dims + 1);
+        return (bwd ? w3 + (size_t)GV_FR * c.comb_hid
+                    : w3 + (size_t)c.goal_dims * c.goal_in + c.goal_dims + c.comb_hid + (size_t)GV_FR * c.goal_dims) * sizeof(float);
+    }
+    int goal_rows(const float* goal_vec) {
+        const long nwg = std::min<long>(1024, ((long)g.B + GV_FR - 1) / GV_FR);
+        hipLaunchKernelGGL(goal_vec_fwd_kernel, dim3((unsigned)nwg), dim3(256), goal_vec_lds(c, false), s, goal_vec, W(P_EMB), W(P_GB),
+                           W(P_W3) + c.compress_out, g.cat, W(P_B3), ws + w.Eg, ws + w.E1f, (long)g.B, c.goal_in, c.goal_dims, c.comb_hid);
+        if (!p.infer)
+            (void)hipMemcpyAsync(ws + w.gvec, goal_vec, (size_t)g.B * c.goal_in * 4, hipMemcpyDeviceToDevice, s);
+        return EC_OK;
+    }
+
     int goal_and_fusion(const void* feat, const int64_t* goal) {
         int* goal32 = (int*)(ws + w.goal32);
         goal_ids = p.goal_direct ? (const int*)goal : goal32;
@@ -1702,8 +1894,8 @@ struct Fwd : Ctx {
         const Ws::Stream& o = w.st[sidx];
         const int M49 = g.M49, C = g.C, cat = g.cat;
         auto WS = [&](int i) { return W(i, sidx); };
-        // E1 = embed_class @ W3[:, co:]^T + b3
-        if (!reuse)
+        // E1 = embed_class @ W3[:, co:]^T + b3   (coordinate goals: goal_rows() has built E1f, per call)
+        if (!reuse && !p.vec)
             RC(gemm(WS(P_EMB), WS(P_W3) + c.compress_out, ws + o.E1, c.num_goals, c.comb_hid, c.goal_dims, c.goal_dims, 1, 1, cat, c.comb_hid, 0, WS(P_B3)));
         if (p.c1 == C1::pingpong) {
             RC(ec_split3_bf16(WS(P_W1), ws + w.w1p, c.compress_hid, C, stream));
@@ -1730,16 +1922,24 @@ struct Fwd : Ctx {
             RC(gemm(featS, WS(P_W1), ws + o.c1, M49, c.compress_hid, C, C, 1, 1, C, c.compress_hid, EC_GEMM_RELU | (p.feat_bf16 ? EC_GEMM_A_BF16 : 0), WS(P_B1)));
         }
         if (p.tail_fwd) {
-            allow_big_lds<tail_fwd_kernel>();
             const long nwg = std::min<long>(512, (((long)M49 + 31) / 32 + 3) / 4);   // 4 tiles of 32 rows per workgroup
-            hipLaunchKernelGGL(tail_fwd_kernel, dim3((unsigned)nwg), dim3(256), p.tail_fwd_lds, s, ws + o.c1, WS(P_W2), WS(P_B2), WS(P_W3), cat,
+            if (p.vec) {
+                allow_big_lds<tail_fwd_kernel<true>>();
+                hipLaunchKernelGGL(tail_fwd_kernel<true>, dim3((unsigned)nwg), dim3(256), p.tail_fwd_lds, s, ws + o.c1, WS(P_W2), WS(P_B2), WS(P_W3), cat,
+                                   ws + w.E1f, (const int*)nullptr, g.S, 0, WS(P_W4), WS(P_B4), ws + o.c2, ws + o.m1, ws + o.x4, (long)M49,
+                                   p.c1_fold, (long)M49 * c.compress_hid, WS(P_B1), 1);
+            } else {
+            allow_big_lds<tail_fwd_kernel<false>>();
+            hipLaunchKernelGGL(tail_fwd_kernel<false>, dim3((unsigned)nwg), dim3(256), p.tail_fwd_lds, s, ws + o.c1, WS(P_W2), WS(P_B2), WS(P_W3), cat,
                                ws + o.E1, goal_ids, g.S, c.num_goals, WS(P_W4), WS(P_B4), ws + o.c2, ws + o.m1, ws + o.x4, (long)M49,
                                p.c1_fold, (long)M49 * c.compress_hid, WS(P_B1), p.goal_direct ? 2 : 1);
+            }
         } else {
             RC(gemm(ws + o.c1, WS(P_W2), ws + o.c2, M49, c.compress_out, c.compress_hid, c.compress_hid, 1, 1, c.compress_hid, c.compress_out, EC_GEMM_RELU, WS(P_B2)));
             // target_obs_combiner (goal half folded into the row-group bias E1[goal])
+            // (coordinate goals: the row group IS the frame -- gidx null selects bias row m / S)
             RC(ec_gemm_f32(ws + o.c2, WS(P_W3), ws + o.m1, M49, c.comb_hid, c.compress_out, c.compress_out, 1, 1, cat,
-                           c.comb_hid, EC_GEMM_RELU, nullptr, ws + o.E1, goal_ids, g.S, nullptr, nullptr, 1, stream));
+                           c.comb_hid, EC_GEMM_RELU, nullptr, p.vec ? ws + w.E1f : ws + o.E1, p.vec ? nullptr : goal_ids, g.S, nullptr, nullptr, 1, stream));
             RC(gemm(ws + o.m1, WS(P_W4), ws + o.x4, M49, c.comb_out, c.comb_hid, c.comb_hid, 1, 1, c.comb_hid, c.comb_out, 0, WS(P_B4)));
         }
         if (p.wih == Wih::plain) {
@@ -1831,9 +2031,10 @@ bool tables_reusable(const ec_policy* h, const void* workspace, const Plan& p, i
 }
 
 int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16, const int64_t* goal,
-                        const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int mode, float* hv,
+                        const float* goal_vec, const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int mode, float* hv,
                         float* h_final, const SampleArgs& smp, ec_stream_t stream) {
-    if (!h || !params || !feat || !goal || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
+    if (!h || !params || !feat || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
+    if (h->c.goal_in > 0 ? (!goal_vec || goal) : (!goal || goal_vec)) return EC_ERR_ARG;   // the entry point of the handle's goal type
     if (h->c.dual && !feat2) return EC_ERR_ARG;
     if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
     if (mode < 0 || mode > EC_POLICY_INFER_REUSE) return EC_ERR_ARG;
@@ -1841,7 +2042,8 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
     if (ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
     Fwd f(h, p, params, workspace, stream);
     f.reuse = tables_reusable(h, workspace, p, mode);
-    RC(f.goal_and_fusion(feat, goal));
+    if (p.vec) RC(f.goal_rows(goal_vec));
+    else RC(f.goal_and_fusion(feat, goal));
     if (!h->c.fusion)
         for (int sidx = 0; sidx < p.g.nstream; ++sidx)   // dual encoder: the RGB stream, then the depth stream (own weights, own activations)
             RC(f.encoder_stream(sidx, sidx ? feat2 : feat));
@@ -1896,7 +2098,8 @@ struct Bwd : Ctx {
     // dW += dY^T X over K rows: K slices into partial matrices folded in order while the dx area is free (`parts_ok`); the
     // tail's unfused fallback GEMMs (EC_TAIL_FUSED=0, the dual encoder) run after dx exists and keep the atomic split
     int tn(const float* dY, int ldy, const void* X, int ldx, int x_bf16, float* dW, int Mo, int No, long K, int ldc) {
-        const int sk = pick_splitk(Mo, No, K), flags = (x_bf16 ? EC_GEMM_B_BF16 : 0) | p.bwd3;
+        // (coordinate goals: no float atomics on any route -- without the partial-matrix area the GEMM walks K in one piece)
+        const int sk = (p.vec && !parts_ok) ? 1 : pick_splitk(Mo, No, K), flags = (x_bf16 ? EC_GEMM_B_BF16 : 0) | p.bwd3;
         if (parts_ok) return gemm_acc_split(dY, X, dW, Mo, No, K, 1, ldy, ldx, 1, ldc, flags, sk);
         return ec_gemm_f32(dY, X, dW, Mo, No, (int)K, 1, ldy, ldx, 1, ldc, EC_GEMM_ACCUMULATE | flags, nullptr, nullptr, nullptr, 0, nullptr,
                            nullptr, sk, stream);
@@ -1942,7 +2145,7 @@ struct Bwd : Ctx {
                 // dh_carry += m * (dghb @ W_hh)   (fused: step T-1's back-projection runs inside the next launch)
                 if (p.step_bwd == Step::gemm_gates)
                     RC(ec_gemm_f32(ws + w.dghb + o3, W(P_WHH), ws + w.dhc, N, H, 3 * H, 3 * H, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr,
-                                   nullptr, nullptr, 0, nullptr, m, step_splitk(N, H, 3 * H), stream));
+                                   nullptr, nullptr, 0, nullptr, m, p.vec ? 1 : step_splitk(N, H, 3 * H), stream));
             } else if (p.step_bwd == Step::fused16) {
                 hipLaunchKernelGGL(gru_step_bwd512_kernel, dim3(32u, (unsigned)((N + 15) / 16)), dim3(256), gb16_lds, s,
                                    ws + w.dghb + o3 + (size_t)N * 3 * H, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dhc,
@@ -1994,6 +2197,30 @@ struct Bwd : Ctx {
                     EC_GEMM_ACCUMULATE);
     }
 
+    // dW[m*ldc + n] += sum_b A[b][m] X[b][n] for the goal half's small weight gradients: row blocks, folded in order
+    void tn_small(const float* A_, int Mo, const float* X, int No, float* dW, int ldc) {
+        const long K = g.B;
+        const int rpb = (int)std::max<long>(32, ((K + GP_MAXY - 1) / GP_MAXY + 31) / 32 * 32);
+        const int ny = (int)((K + rpb - 1) / rpb);
+        hipLaunchKernelGGL(tn_small_part_kernel, dim3((unsigned)ny), dim3(256), (size_t)32 * (Mo + No) * sizeof(float), s, A_, Mo, X, No,
+                           ws + w.gpart, Mo, No, K, rpb);
+        const long nq = (long)Mo * No;
+        hipLaunchKernelGGL(splitk_fold_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, ws + w.gpart, ny, Mo, No, ldc, dW);
+    }
+    // goal half with coordinate goals, from dE1f [B, comb_hid] (the per-frame sums of dm1):
+    //   db3 += colsum dE1f;  dW3[:, co:] += dE1f^T Eg;  dEg = dE1f W3[:, co:];  dWc += dEg^T goal_vec;  dbc += colsum dEg
+    int goal_half_vec() {
+        const float* dE1f = ws + w.dE1f;
+        colsum(dE1f, G(P_B3), g.B, c.comb_hid, c.comb_hid);
+        tn_small(dE1f, c.comb_hid, ws + w.Eg, c.goal_dims, G(P_W3) + c.compress_out, g.cat);
+        const long nwg = std::min<long>(1024, ((long)g.B + GV_FR - 1) / GV_FR);
+        hipLaunchKernelGGL(goal_vec_bwd_kernel, dim3((unsigned)nwg), dim3(256), Fwd::goal_vec_lds(c, true), s, dE1f, W(P_W3) + c.compress_out,
+                           g.cat, ws + w.dEg, (long)g.B, c.goal_dims, c.comb_hid);
+        tn_small(ws + w.dEg, c.goal_dims, ws + w.gvec, c.goal_in, G(P_EMB), c.goal_in);
+        colsum(ws + w.dEg, G(P_GB), g.B, c.goal_dims, c.goal_dims);
+        return EC_OK;
+    }
+
     // combiner and compressor of one encoder stream (the depth stream re-uses the gradient temporaries: one HIP stream)
     int encoder_stream(int sidx, const void* featS) {
         const Ws::Stream& o = w.st[sidx];
@@ -2006,14 +2233,22 @@ struct Bwd : Ctx {
             hipLaunchKernelGGL(from_cmajor_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws + w.dx,
                                ws + w.dx4, S, c.comb_out, total, g.flat, sidx * g.flat1);
         }
-        (void)hipMemsetAsync(ws + w.dE1, 0, (size_t)c.num_goals * c.comb_hid * 4, s);
+        if (!p.vec) (void)hipMemsetAsync(ws + w.dE1, 0, (size_t)c.num_goals * c.comb_hid * 4, s);
         if (p.tail_bwd) {
             // dm1 / dc2 / dc1 and all small weight gradients of the tail in one pass
-            allow_big_lds<tail_bwd_kernel>();
             const long nwg = std::min<long>(TB_MAX_WG, (((long)M49 + 31) / 32 + 3) / 4);
-            hipLaunchKernelGGL(tail_bwd_kernel, dim3((unsigned)nwg), dim3(256), p.tail_bwd_lds, s, ws + w.dx4, ws + o.m1, ws + o.c2, ws + o.c1,
+            if (p.vec) {
+                allow_big_lds<tail_bwd_kernel<true>>();
+                hipLaunchKernelGGL(tail_bwd_kernel<true>, dim3((unsigned)nwg), dim3(256), p.tail_bwd_lds, s, ws + w.dx4, ws + o.m1, ws + o.c2, ws + o.c1,
+                                   WS(P_W2), WS(P_W3), cat, WS(P_W4), (const int*)nullptr, S, 0, ws + w.dc1,
+                                   p.dw1_planes ? (uint16_t*)(ws + w.dc1) : nullptr, ws + w.tpart, ws + w.tseg, (long)M49);
+                hipLaunchKernelGGL(seg_fold_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.tseg, ws + w.dE1f, S, (long)B);
+            } else {
+            allow_big_lds<tail_bwd_kernel<false>>();
+            hipLaunchKernelGGL(tail_bwd_kernel<false>, dim3((unsigned)nwg), dim3(256), p.tail_bwd_lds, s, ws + w.dx4, ws + o.m1, ws + o.c2, ws + o.c1,
                                WS(P_W2), WS(P_W3), cat, WS(P_W4), goal32, S, c.num_goals, ws + w.dc1,
                                p.dw1_planes ? (uint16_t*)(ws + w.dc1) : nullptr, ws + w.tpart, ws + w.tpartE, (long)M49);
+            }
             const int ne = TB_PART + c.num_goals * 128;
             // the y-slices' sums: behind the used partial sets when there is room (nwg < TB_MAX_WG), else in the dm1 area, which
             // the fused path never materialises (nwg == TB_MAX_WG means M49 >= 32,768 rows: 4 M floats)
@@ -2032,6 +2267,8 @@ struct Bwd : Ctx {
             RC(ec_gemm_f32(ws + w.dx4, WS(P_W4), ws + w.dm1, M49, c.comb_hid, c.comb_out, c.comb_out, 1, c.comb_hid, 1, c.comb_hid,
                            0, nullptr, nullptr, nullptr, 0, ws + o.m1, nullptr, 1, stream));
             RC(tn(ws + w.dm1, c.comb_hid, ws + o.c2, c.compress_out, 0, GS(P_W3), c.comb_hid, c.compress_out, M49, cat));
+            if (p.vec) hipLaunchKernelGGL(frame_sum_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.dm1, ws + w.dE1f, S, c.comb_hid);
+            else
             hipLaunchKernelGGL(group_sum_scatter_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.dm1, goal32, ws + w.dE1, S,
                                c.comb_hid, (long)B);
             // ---- resnet_compressor ----
@@ -2043,7 +2280,8 @@ struct Bwd : Ctx {
                            c.compress_hid, 1, c.compress_hid, 0, nullptr, nullptr, nullptr, 0, ws + o.c1, nullptr, 1, stream));
             colsum(ws + w.dc1, GS(P_B1), M49, c.compress_hid, c.compress_hid);
         }
-        RC(goal_half(sidx));
+        if (p.vec) RC(goal_half_vec());
+        else RC(goal_half(sidx));
         if (p.dw1_planes) return ec_dw_tn_xp(ws + w.dc1, featS, ws + w.tpart, GS(P_W1), M49, C, p.planes, stream);   // (tpart: free again after the reducer)
         return tn(ws + w.dc1, c.compress_hid, featS, C, p.feat_bf16, GS(P_W1), c.compress_hid, C, M49, C);
     }
@@ -2057,7 +2295,9 @@ extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) {
     if (c.fusion != 0 && c.fusion != 1) return EC_ERR_ARG;
     if (c.dual != 0 && c.dual != 1) return EC_ERR_ARG;
     if (c.dual && c.fusion) return EC_ERR_ARG;
-    if (c.in_channels <= 0 || c.spatial <= 0 || c.hidden <= 0 || c.num_goals <= 0 || c.num_actions <= 0) return EC_ERR_SHAPE;
+    if (c.goal_in < 0 || c.goal_in > 8 || (c.goal_in && c.fusion)) return EC_ERR_ARG;
+    if (c.goal_in && c.dual) return EC_ERR_UNSUPPORTED;
+    if (c.in_channels <= 0 || c.spatial <= 0 || c.hidden <= 0 || (c.num_goals <= 0 && !c.goal_in) || c.num_actions <= 0) return EC_ERR_SHAPE;
     if ((c.in_channels & 3) || (c.hidden & 3)) return EC_ERR_SHAPE;
     if (c.fusion) {
         if (c.spatial != 1) return EC_ERR_SHAPE;
@@ -2067,24 +2307,35 @@ extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) {
         if ((c.compress_hid & 3) || (c.compress_out & 3) || (c.comb_hid & 3) || (c.comb_out & 3) || (c.goal_dims & 3))
             return EC_ERR_SHAPE;
     }
+    // (coordinate goals: W3[:, co:] and one pass of frames sit in the LDS of the two goal_vec kernels)
+    if (c.goal_in && std::max(Fwd::goal_vec_lds(c, false), Fwd::goal_vec_lds(c, true)) > 64 * 1024) return EC_ERR_SHAPE;
     ec_policy* h = new (std::nothrow) ec_policy();
     if (!h) return EC_ERR_ALLOC;
     h->c = c;
+    if (c.goal_in) h->c.num_goals = 0;   // ignored: no goal table anywhere (the table areas of the workspace are empty)
     const size_t S = (size_t)c.spatial * c.spatial, H = c.hidden;
     const size_t flat = c.fusion ? (size_t)c.in_channels : (size_t)(c.dual ? 2 : 1) * c.comb_out * S;
-    size_t n[P_COUNT] = {(size_t)c.num_goals * c.goal_dims,
+    size_t n[P_COUNT] = {c.goal_in ? (size_t)c.goal_dims * c.goal_in : (size_t)c.num_goals * c.goal_dims,
                                (size_t)c.compress_hid * c.in_channels, (size_t)c.compress_hid,
                                (size_t)c.compress_out * c.compress_hid, (size_t)c.compress_out,
                                (size_t)c.comb_hid * (c.compress_out + c.goal_dims), (size_t)c.comb_hid,
                                (size_t)c.comb_out * c.comb_hid, (size_t)c.comb_out,
                                3 * H * flat, 3 * H * H, 3 * H, 3 * H,
-                               (size_t)c.num_actions * H, (size_t)c.num_actions, H, 1, 0, 0, 0, 0, 0, 0, 0, 0};
+                               (size_t)c.num_actions * H, (size_t)c.num_actions, H, 1, 0, 0, 0, 0, 0, 0, 0, 0,
+                               c.goal_in ? (size_t)c.goal_dims : 0};
     if (c.fusion)
         for (int i = P_EMB; i <= P_B4; ++i) n[i] = 0;      // no goal embedding / compressor / combiner: GRU + heads only
     if (c.dual)
         for (int i = P_W1; i <= P_B4; ++i) n[i + (P_W1D - P_W1)] = n[i];
+    // flat order: the enum's, except that embed_goal.bias follows embed_goal.weight
+    h->ntensors = 0;
+    for (int i = 0; i < P_COUNT_DUAL; ++i) {
+        h->order[h->ntensors++] = i;
+        if (i == P_EMB && c.goal_in) h->order[h->ntensors++] = P_GB;
+    }
+    if (!c.goal_in) h->order[h->ntensors++] = P_GB;          // (zero elements)
     size_t o = 0;
-    for (int i = 0; i < P_COUNT; ++i) { h->off[i] = o; h->num[i] = n[i]; o += (n[i] + 3) / 4 * 4; }   // 16-B aligned
+    for (int k = 0; k < P_COUNT; ++k) { const int i = h->order[k]; h->off[i] = o; h->num[i] = n[i]; o += (n[i] + 3) / 4 * 4; }   // 16-B aligned
     h->total = o;
     *out = h;
     return EC_OK;
@@ -2095,11 +2346,13 @@ extern "C" int ec_policy_set_goal_table(ec_policy_t* h, const float* table) {
     h->goal_table = table;
     return EC_OK;
 }
-extern "C" int ec_policy_num_param_tensors(const ec_policy_t* h) { return (h && h->c.dual) ? P_COUNT : P_COUNT_SINGLE; }
+extern "C" int ec_policy_num_param_tensors(const ec_policy_t* h) {
+    return (h && h->c.dual) ? P_COUNT_DUAL : ((h && h->c.goal_in) ? P_COUNT_VEC : P_COUNT_SINGLE);
+}
 extern "C" size_t ec_policy_flat_size(const ec_policy_t* h) { return h ? h->total : 0; }
 extern "C" int ec_policy_param_offset(const ec_policy_t* h, int idx, size_t* off, size_t* numel) {
-    if (!h || idx < 0 || idx >= P_COUNT || !off || !numel) return EC_ERR_ARG;
-    *off = h->off[idx]; *numel = h->num[idx];
+    if (!h || idx < 0 || idx >= P_COUNT_DUAL || !off || !numel) return EC_ERR_ARG;
+    *off = h->off[h->order[idx]]; *numel = h->num[h->order[idx]];
     return EC_OK;
 }
 extern "C" size_t ec_policy_workspace_bytes(const ec_policy_t* h, int T, int N, int for_backward) {
@@ -2116,8 +2369,14 @@ extern "C" int ec_policy_forward(const ec_policy_t* h, const float* params, cons
 extern "C" int ec_policy_forward2(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                   const int64_t* goal, const float* h0, const float* masks, int T, int N, void* workspace,
                                   size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream) {
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final,
+    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final,
                                SampleArgs{}, stream);
+}
+extern "C" int ec_policy_forward_vec(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                                     const float* goal_vec, const float* h0, const float* masks, int T, int N, void* workspace,
+                                     size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream) {
+    return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, T, N, workspace, ws_bytes, for_backward, hv,
+                               h_final, SampleArgs{}, stream);
 }
 
 // The act step in ONE call ([U] allenact OnPolicyRLEngine.act: actor_critic(...) then distributions.sample() / log_probs()):
@@ -2130,7 +2389,17 @@ extern "C" int ec_policy_act(const ec_policy_t* h, const float* params, const vo
     if (!actions || !logp) return EC_ERR_ARG;
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;       // (the one-wave-per-row heads launch)
     const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, h0, masks, 1, N, workspace, ws_bytes,
+    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, 1, N, workspace, ws_bytes,
+                               reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
+}
+extern "C" int ec_policy_act_vec(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                                 const float* goal_vec, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
+                                 int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
+                                 uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream) {
+    if (!actions || !logp) return EC_ERR_ARG;
+    if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
+    const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
+    return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
                                reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
 }
 

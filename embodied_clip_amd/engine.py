@@ -50,7 +50,7 @@ class SyntheticEnv:
     random goal ids, episode resets w.p. 1/100, RoboTHOR-style rewards."""
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
-                 frames_u8: bool = False, host: bool = False):
+                 frames_u8: bool = False, host: bool = False, goal_in: int = 0):
         self.N, self.T = n_actors, T
         self.host = host
         # frames_u8: raw uint8 frames (what the simulator renders); normalisation is then fused into the stem kernel.
@@ -70,7 +70,9 @@ class SyntheticEnv:
         self.pool_steps = pool_steps
         masks = torch.cat([torch.ones(1, n_actors, 1), syn.synthetic_masks(seed + 1, T, n_actors)], 0)
         self.masks = masks.reshape(T + 1, n_actors).to(device).contiguous()
-        self.goals = syn.synthetic_goals(seed + 2, (T + 1, n_actors)).to(device).contiguous()
+        # goal_in > 0 (PointNav): float [T+1, N, goal_in] coordinate goals (distance, bearing) instead of int64 ids [T+1, N]
+        self.goals = (syn.synthetic_goal_vectors(seed + 2, (T + 1, n_actors), goal_in) if goal_in
+                      else syn.synthetic_goals(seed + 2, (T + 1, n_actors))).to(device).contiguous()
         self.rewards = syn.synthetic_rewards(seed + 3, masks[1:]).reshape(T, n_actors).to(device).contiguous()
         self._k = 0
 
@@ -104,12 +106,17 @@ class Worker:
                  encoder_chunk: int = 0, encoder: str = "rn50", encoder_streams: int = 2, frames_u8: bool = False,
                  frames_host: bool = False, zeroshot: bool = False, text_sd=None, goal_tokens=None,
                  num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
-                 overlap_allreduce: bool = True):
-        """``zeroshot=True`` (BASELINE config 5, readme_files/zeroshot_objectnav.md): the observation is the CLIP image
+                 overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6):
+        """``goal_in > 0``: the PointNav agent ([U] ResnetTensorPointNavActorCritic) -- the goal of a frame is ``goal_in``
+        floats (GPS + compass: distance, bearing), ``num_actions`` is 4 there; ``goal_in=0`` is the ObjectNav agent.
+
+        ``zeroshot=True`` (BASELINE config 5, readme_files/zeroshot_objectnav.md): the observation is the CLIP image
         EMBEDDING (RN50 trunk + AttentionPool2d, 1024-d), the goal is the frozen CLIP text embedding of its prompt
         (text tower run once -> [12, 1024] table) and the policy is the fusion=1 variant (GRU + heads trainable)."""
         self.lib = _lib.load()
         self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
+        assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
+        self.goal_in, self._num_actions = goal_in, num_actions
         # sync_actions: the action-synchronous order of a real vectorised env ([U] VectorSampledTasks.step(actions)): every
         # env step the sampled actions of ALL actors are copied to the host and waited for before observe() serves the next
         # frames.  Default off: the synthetic env does not read the actions (SURVEY.md 8d) and the host issues ahead.
@@ -188,7 +195,9 @@ class Worker:
             self.S, self.C = 7, encs[0].D
         else:
             raise ValueError(encoder)
-        pkw = dict(in_channels=self.C, spatial=self.S)
+        pkw = dict(in_channels=self.C, spatial=self.S, num_actions=self._num_actions)
+        if self.goal_in:
+            pkw["goal_in"] = self.goal_in
         if self.zeroshot:
             assert encoder == "rn50", "the zero-shot variant uses the CLIP-RN50 image embedding"
             pkw["fusion"] = 1
@@ -219,7 +228,7 @@ class Worker:
         self.hv_act = torch.empty((N, self.A + 1), dtype=torch.float32, device=d)
         self.stats = torch.zeros(2, dtype=torch.float64, device=d)
         self.sums = torch.zeros(4, dtype=torch.float64, device=d)
-        self.env = SyntheticEnv(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host)
+        self.env = SyntheticEnv(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in)
         self.slices: List[_Slice] = []
         # Streams.  The HIP runtime has FOUR hardware queues and binds a stream to one of them at its first submission; two
         # streams on one queue run one after the other (a slice pair that shared a queue serialised the two encoder launches:
@@ -490,7 +499,9 @@ class Worker:
         for sl in self.slices:
             rs = slice(sl.o, sl.o + sl.n)
             c = lambda x: x[:T, rs].reshape(-1).contiguous()
-            sl.goal, sl.masks = c(self.env.goals), c(self.env.masks)
+            # (coordinate goals keep their last dimension: [T*n, goal_in] rows)
+            sl.goal = self.env.goals[:T, rs].reshape(T * sl.n, -1).contiguous() if self.goal_in else c(self.env.goals)
+            sl.masks = c(self.env.masks)
             sl.actions, sl.logp, sl.old_v = c(self.actions), c(self.logp), c(self.values)
             sl.ret, sl.nadv = c(self.returns), c(self.nadv)
 
@@ -527,7 +538,8 @@ class Worker:
         fm = sl.feat_mb.view(-1)[:T * m * self.S * self.S * self.C].view(T, m, self.S * self.S, self.C)
         fm.copy_(sl.feat[:T, a:b])
         c = lambda x: x.view(T, sl.n)[:, a:b].reshape(-1).contiguous()
-        return (fm.view(T * m, self.S * self.S, self.C), c(sl.goal), c(sl.masks), c(sl.actions), c(sl.logp), c(sl.old_v),
+        goal = sl.goal.view(T, sl.n, -1)[:, a:b].reshape(T * m, -1).contiguous() if self.goal_in else c(sl.goal)
+        return (fm.view(T * m, self.S * self.S, self.C), goal, c(sl.masks), c(sl.actions), c(sl.logp), c(sl.old_v),
                 c(sl.ret), c(sl.nadv))
 
     def _sum_parts(self, parts, sec: slice):

@@ -42,9 +42,10 @@ class PolicyHandle:
     def __init__(self, **cfg: int):
         self.lib = _lib.load()
         self.cfg = dict(in_channels=2048, spatial=7, hidden=512, goal_dims=32, num_goals=12, num_actions=6,
-                        compress_hid=128, compress_out=32, comb_hid=128, comb_out=32, fusion=0, dual=0)
+                        compress_hid=128, compress_out=32, comb_hid=128, comb_out=32, fusion=0, dual=0, goal_in=0)
         self.cfg.update(cfg)
-        self.param_order = policy_param_order(self.cfg["dual"])
+        self.goal_in = self.cfg["goal_in"]      # > 0: the goal of a frame is goal_in floats (PointNav), ec_policy_*_vec
+        self.param_order = policy_param_order(self.cfg["dual"], self.goal_in)
         c = _lib.PolicyCfg(**self.cfg)
         h = C.c_void_p()
         _lib.check(self.lib.ec_policy_create(C.byref(h), C.byref(c)), "ec_policy_create")
@@ -85,6 +86,15 @@ class PolicyHandle:
     def H(self):
         return self.cfg["hidden"]
 
+    def _goal_ptr(self, goal, rows: int) -> int:
+        """The goal argument of the handle's entry points: int64 ids [rows], or (``goal_in > 0``) float32 [rows, goal_in]."""
+        if self.goal_in:
+            assert goal.dtype == torch.float32 and goal.is_contiguous() and tuple(goal.shape) == (rows, self.goal_in), \
+                (goal.dtype, tuple(goal.shape), (rows, self.goal_in))
+        else:
+            assert goal.dtype == torch.int64 and goal.numel() == rows, (goal.dtype, tuple(goal.shape))
+        return goal.data_ptr()
+
     def workspace_bytes(self, T: int, N: int, backward: bool) -> int:
         return self.lib.ec_policy_workspace_bytes(self.h, T, N, int(backward))
 
@@ -117,11 +127,12 @@ class PolicyHandle:
         ``actions`` / ``logp`` (and copies ``values``) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions``."""
         assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
         with _lib.tensor_guard(flat_params):
-            _lib.check(self.lib.ec_policy_act(
-                self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), goal.data_ptr(),
+            fn = self.lib.ec_policy_act_vec if self.goal_in else self.lib.ec_policy_act
+            _lib.check(fn(
+                self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), self._goal_ptr(goal, N),
                 h0.data_ptr(), masks.data_ptr(), N, ws.data_ptr(), ws.numel() * ws.element_size(), int(reuse_tables),
                 hv.data_ptr(), h_final.data_ptr(), actions.data_ptr(), logp.data_ptr(), _lib.ptr(values), seed, step, first_actor,
-                _lib.stream_ptr()), "ec_policy_act")
+                _lib.stream_ptr()), "ec_policy_act_vec" if self.goal_in else "ec_policy_act")
         return hv, h_final
 
     def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None):
@@ -131,10 +142,11 @@ class PolicyHandle:
             h_final = torch.empty((N, self.H), dtype=torch.float32, device=dev)
         if self.cfg["dual"]:       # RGB + depth: feat = the RGB features, feat2 = the depth features (same shape / dtype)
             assert feat2 is not None and feat2.is_contiguous() and feat2.dtype == feat.dtype and feat2.shape == feat.shape
-        _lib.check(self.lib.ec_policy_forward2(
-            self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), goal.data_ptr(),
+        fn = self.lib.ec_policy_forward_vec if self.goal_in else self.lib.ec_policy_forward2
+        _lib.check(fn(
+            self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), self._goal_ptr(goal, T * N),
             h0.data_ptr(), masks.data_ptr(), T, N, ws.data_ptr(), ws.numel() * ws.element_size(), int(for_backward),
-            hv.data_ptr(), h_final.data_ptr(), _lib.stream_ptr()), "ec_policy_forward2")
+            hv.data_ptr(), h_final.data_ptr(), _lib.stream_ptr()), "ec_policy_forward_vec" if self.goal_in else "ec_policy_forward2")
         return hv, h_final
 
     def backward(self, flat_params, feat, masks, T, N, ws, dhv, dh_final, flat_grads, feat2=None, recurrent_ready=None):
@@ -219,19 +231,11 @@ def _set_nested(root: nn.Module, dotted: str, p: nn.Parameter):
     m.register_parameter(parts[-1], p)
 
 
-class ResnetTensorObjectNavActorCritic(ActorCriticModel):
-    """[U] ``ResnetTensorObjectNavActorCritic(action_space, observation_space, goal_sensor_uuid,
-    rgb_resnet_preprocessor_uuid=None, depth_resnet_preprocessor_uuid=None, hidden_size=512, goal_dims=32,
-    resnet_compressor_hidden_out_dims=(128, 32), combiner_hidden_out_dims=(128, 32))`` -- an
-    ``allenact...policy.ActorCriticModel`` (the real ABC when allenact is importable).
-
-    Exactly one of the two preprocessor uuids selects the single-tower ``ResnetTensorGoalEncoder`` (RGB for the CLIP
-    configs of the reference; a depth-only tower is the same arithmetic on the depth features).  Both at once is
-    upstream's ``ResnetDualTensorGoalEncoder`` (RGB-D: readme_files/baselines_habitat.md:75 "replace rgb with rgbd"):
-    each stream has its own compressor and combiner (parameter names ``goal_visual_encoder.{rgb,depth}_resnet_compressor.*``
-    / ``{rgb,depth}_target_obs_combiner.*``), the goal embedding is shared, and ``cat([rgb_x, depth_x], dim=1)`` is
-    flattened into the GRU (``ec_policy_cfg.dual``).
-    """
+class _ResnetTensorGoalActorCritic(ActorCriticModel):
+    """What the ObjectNav and the PointNav model share: everything but the goal's type.  ``_coordinate_goal`` False: the goal
+    observation is an integer id per frame (``embed_class``); True: a float vector per frame (``embed_goal``), its width
+    read off the goal sensor's observation space."""
+    _coordinate_goal = False
 
     def __init__(self, action_space, observation_space, goal_sensor_uuid: str,
                  rgb_resnet_preprocessor_uuid: Optional[str] = None, depth_resnet_preprocessor_uuid: Optional[str] = None,
@@ -255,13 +259,18 @@ class ResnetTensorObjectNavActorCritic(ActorCriticModel):
         rs = observation_space.spaces[self.resnet_uuid].shape        # (C, S, S)
         if self.dual and tuple(observation_space.spaces[self.depth_uuid].shape) != tuple(rs):
             raise ValueError("the RGB and depth feature tensors must have the same shape")
-        num_goals = getattr(observation_space.spaces[self.goal_uuid], "n", 12)
+        if self._coordinate_goal:
+            if self.dual:
+                raise NotImplementedError("the RGB-D PointNav encoder is not built")
+            goal_kw = dict(goal_in=int(observation_space.spaces[self.goal_uuid].shape[-1]))
+        else:
+            goal_kw = dict(num_goals=getattr(observation_space.spaces[self.goal_uuid], "n", 12))
         self.handle = PolicyHandle(in_channels=rs[0], spatial=rs[1], hidden=hidden_size, goal_dims=goal_dims,
-                                   num_goals=num_goals, num_actions=action_space.n,
+                                   num_actions=action_space.n,
                                    compress_hid=resnet_compressor_hidden_out_dims[0],
                                    compress_out=resnet_compressor_hidden_out_dims[1],
                                    comb_hid=combiner_hidden_out_dims[0], comb_out=combiner_hidden_out_dims[1],
-                                   dual=int(self.dual))
+                                   dual=int(self.dual), **goal_kw)
         dev = torch.device(device)
         if state_dict is None:
             from .synthetic import policy_state_dict
@@ -391,7 +400,7 @@ class ResnetTensorObjectNavActorCritic(ActorCriticModel):
     def forward(self, observations: Dict[str, torch.Tensor], memory: Memory, prev_actions: torch.Tensor,
                 masks: torch.Tensor):
         """observations[resnet_uuid]: [T,N,C,S,S] fp32 (or bf16/fp32 channels-last [T,N,S,S,C] from
-        ``ClipResNetPreprocessor.process_bf16_nhwc``); observations[goal_uuid]: [T,N] int;
+        ``ClipResNetPreprocessor.process_bf16_nhwc``); observations[goal_uuid]: [T,N] int (PointNav: [T,N,goal_in] float);
         memory 'rnn': [1,N,H]; masks: [T,N,1].  -> (ActorCriticOutput, Memory)."""
         self.ensure_flat()
         goal = observations[self.goal_uuid]
@@ -414,7 +423,10 @@ class ResnetTensorObjectNavActorCritic(ActorCriticModel):
             rows2 = to_rows(observations[self.depth_uuid], 1)
             if rows2.dtype != rows.dtype:
                 rows, rows2 = rows.float(), rows2.float()
-        goal = goal.reshape(T * N).to(torch.int64).contiguous()
+        if self._coordinate_goal:
+            goal = goal.reshape(T * N, self.handle.goal_in).to(torch.float32).contiguous()
+        else:
+            goal = goal.reshape(T * N).to(torch.int64).contiguous()
         h0 = memory.tensor("rnn").reshape(N, self._hidden_size).to(torch.float32).contiguous()
         m = masks.reshape(T * N).to(torch.float32).contiguous()
         if torch.is_grad_enabled():
@@ -427,3 +439,34 @@ class ResnetTensorObjectNavActorCritic(ActorCriticModel):
         hv = hv.view(T, N, A + 1)
         out = ActorCriticOutput(distributions=CategoricalDistr(logits=hv[..., :A]), values=hv[..., A:], extras={})
         return out, memory.set_tensor("rnn", h_final.view(1, N, self._hidden_size))
+
+
+class ResnetTensorObjectNavActorCritic(_ResnetTensorGoalActorCritic):
+    """[U] ``ResnetTensorObjectNavActorCritic(action_space, observation_space, goal_sensor_uuid,
+    rgb_resnet_preprocessor_uuid=None, depth_resnet_preprocessor_uuid=None, hidden_size=512, goal_dims=32,
+    resnet_compressor_hidden_out_dims=(128, 32), combiner_hidden_out_dims=(128, 32))`` -- an
+    ``allenact...policy.ActorCriticModel`` (the real ABC when allenact is importable).
+
+    Exactly one of the two preprocessor uuids selects the single-tower ``ResnetTensorGoalEncoder`` (RGB for the CLIP
+    configs of the reference; a depth-only tower is the same arithmetic on the depth features).  Both at once is
+    upstream's ``ResnetDualTensorGoalEncoder`` (RGB-D: readme_files/baselines_habitat.md:75 "replace rgb with rgbd"):
+    each stream has its own compressor and combiner (parameter names ``goal_visual_encoder.{rgb,depth}_resnet_compressor.*``
+    / ``{rgb,depth}_target_obs_combiner.*``), the goal embedding is shared, and ``cat([rgb_x, depth_x], dim=1)`` is
+    flattened into the GRU (``ec_policy_cfg.dual``).
+    """
+
+
+class ResnetTensorPointNavActorCritic(_ResnetTensorGoalActorCritic):
+    """[U] allenact ~v0.5.0 ``projects/pointnav_baselines/models/point_nav_models.py``
+    ``ResnetTensorPointNavActorCritic(action_space, observation_space, goal_sensor_uuid, rgb_resnet_preprocessor_uuid=None,
+    depth_resnet_preprocessor_uuid=None, hidden_size=512, goal_dims=32, resnet_compressor_hidden_out_dims=(128, 32),
+    combiner_hidden_out_dims=(128, 32))`` -- the Habitat PointNav model the reference's readme names
+    (readme_files/baselines_habitat.md:64,85-86).  Restated from the published source, parity unpinned.
+
+    The ObjectNav model with one change: the goal is the GPS + compass sensor's float vector (polar ``(rho, phi)``, uuid
+    ``target_coordinates_ind``; ``observations[goal_uuid]``: ``[T, N, goal_in]``) through ``embed_goal = nn.Linear(goal_in,
+    goal_dims)`` instead of an id through ``embed_class``.  ``goal_in`` is the last dimension of the goal sensor's
+    observation space (2 upstream; 3 for Habitat's ``(rho, cos -phi, sin -phi)``).  18 parameters,
+    ``goal_visual_encoder.embed_goal.{weight,bias}`` first; single-tower only.
+    """
+    _coordinate_goal = True

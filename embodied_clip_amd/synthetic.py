@@ -339,16 +339,33 @@ POLICY_PARAM_ORDER_DUAL: Tuple[str, ...] = tuple(_DUAL_RGB.get(k, k) for k in PO
     for k in POLICY_PARAM_ORDER[1:9])
 
 
-def policy_param_order(dual: int = 0) -> Tuple[str, ...]:
+# [U] ResnetTensorPointNavActorCritic (``goal_in > 0``): ``embed_class = nn.Embedding(n, 32)`` is replaced by
+# ``embed_goal = nn.Linear(goal_in, 32)`` on the goal sensor's float vector; every other tensor keeps its name and place
+POLICY_PARAM_ORDER_POINTNAV: Tuple[str, ...] = (
+    "goal_visual_encoder.embed_goal.weight", "goal_visual_encoder.embed_goal.bias") + POLICY_PARAM_ORDER[1:]
+
+
+def policy_param_order(dual: int = 0, goal_in: int = 0) -> Tuple[str, ...]:
+    if goal_in:
+        assert not dual, "the RGB-D PointNav encoder is not built"
+        return POLICY_PARAM_ORDER_POINTNAV
     return POLICY_PARAM_ORDER_DUAL if dual else POLICY_PARAM_ORDER
 
 
 def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int = 512, goal_dims: int = 32,
                         num_goals: int = 12, num_actions: int = 6, compress_hid: int = 128,
-                        compress_out: int = 32, comb_hid: int = 128, comb_out: int = 32, fusion: int = 0, dual: int = 0):
+                        compress_out: int = 32, comb_hid: int = 128, comb_out: int = 32, fusion: int = 0, dual: int = 0,
+                        goal_in: int = 0):
     """``fusion=1`` (zero-shot dual-encoder policy): the goal-embedding / compressor / combiner tensors have zero
     elements and the GRU reads the ``in_channels``-wide fused embedding.  ``dual=1``: RGB + depth streams (25 tensors,
-    GRU input 2 * comb_out * spatial^2)."""
+    GRU input 2 * comb_out * spatial^2).  ``goal_in > 0`` (PointNav): 18 tensors, ``embed_goal.{weight,bias}`` in place
+    of ``embed_class.weight``; ``num_goals`` is ignored."""
+    if goal_in:
+        assert not fusion and not dual
+        one = policy_param_shapes(in_channels, spatial, hidden, goal_dims, num_goals, num_actions, compress_hid, compress_out,
+                                  comb_hid, comb_out)
+        return OrderedDict([("goal_visual_encoder.embed_goal.weight", (goal_dims, goal_in)),
+                            ("goal_visual_encoder.embed_goal.bias", (goal_dims,))] + list(one.items())[1:])
     if dual:
         assert not fusion
         one = policy_param_shapes(in_channels, spatial, hidden, goal_dims, num_goals, num_actions, compress_hid, compress_out,
@@ -394,7 +411,8 @@ def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int =
 
 
 def policy_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, torch.Tensor]":
-    """Synthetic policy parameters; RoboTHOR default = 3,480,775 params."""
+    """Synthetic policy parameters; RoboTHOR default = 3,480,775 params (PointNav, ``goal_in=2, num_actions=4``:
+    3,479,461; ``embed_goal.weight`` ~ N(0, 1/goal_in), the generic fan-in rule below)."""
     shapes = policy_param_shapes(**kw)
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     for k, shp in shapes.items():
@@ -437,6 +455,16 @@ def synthetic_rgb(seed: int, n: int, res: int = 224) -> torch.Tensor:
 def synthetic_goals(seed: int, shape, num_goals: int = 12) -> torch.Tensor:
     n = int(np.prod(shape))
     return torch.from_numpy((hash_u64(seed, n, stream=11) % np.uint64(num_goals)).astype(np.int64)).reshape(shape)
+
+
+def synthetic_goal_vectors(seed: int, shape, goal_in: int = 2, rho_max: float = 10.0) -> torch.Tensor:
+    """Coordinate goals fp32 ``shape + (goal_in,)``: component 0 (the distance rho) ~ U[0, rho_max), the others (bearings)
+    ~ U[-pi, pi), on the portable hash."""
+    n = int(np.prod(shape))
+    u = hash_uniform(seed, n * goal_in, stream=19).astype(np.float64).reshape(n, goal_in)
+    v = (u * 2.0 - 1.0) * np.pi
+    v[:, 0] = u[:, 0] * rho_max
+    return torch.from_numpy(v.astype(np.float32)).reshape(tuple(shape) + (goal_in,))
 
 
 def synthetic_masks(seed: int, T: int, N: int, p_reset: float = 0.01) -> torch.Tensor:

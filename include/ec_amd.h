@@ -359,6 +359,16 @@ typedef struct {
                         *    shared), rgb_x and depth_x concatenated along channels before nn.Flatten -> GRU input
                         *    2 * comb_out * spatial^2.  Eight more parameter tensors (the depth stream's, after the 17 of
                         *    the single encoder); use ec_policy_forward2 / ec_policy_backward2.  Not combinable with fusion */
+    int goal_in;       /* 0: the goal of a frame is an integer id (embed_class, the ObjectNav models above).
+                        * k in 1..8: the goal of a frame is k floats (PointNav: polar (rho, phi) from the GPS + compass sensor,
+                        *    k = 2; Habitat's own policy feeds (rho, cos -phi, sin -phi), k = 3) through
+                        *    embed_goal = nn.Linear(k, goal_dims) -- [U] allenact ~v0.5.0 projects/pointnav_baselines/models/
+                        *    point_nav_models.py ResnetTensorPointNavActorCritic, restated from the published source (parity
+                        *    unpinned, like the rest of the policy).  num_goals is ignored.  18 parameter tensors:
+                        *    embed_goal.weight [goal_dims, k] and embed_goal.bias [goal_dims] first, then the 16 others of the
+                        *    single encoder in the order above.  Use ec_policy_forward_vec / ec_policy_act_vec; the backward
+                        *    entry points are the same.  EC_ERR_ARG with fusion = 1; EC_ERR_UNSUPPORTED with dual = 1 (the
+                        *    RGB-D PointNav encoder is not built) */
 } ec_policy_cfg;
 typedef struct ec_policy ec_policy_t;
 
@@ -397,6 +407,20 @@ int ec_policy_act(const ec_policy_t* h, const float* params, const void* feat, c
                   const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                   int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                   uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream);
+/* goal_in > 0 handles: ec_policy_forward2 / ec_policy_act with the goal of every frame as goal_in floats, goal_vec f32
+ * [T*N, goal_in].  The goal half of target_obs_combiner.0 is a PER-FRAME bias row E1f[b] = (goal_vec[b] Wc^T + bc) W3[:, co:]^T + b3
+ * that every call rebuilds from ITS goal vectors: EC_POLICY_INFER_REUSE keeps weight-derived tables only (the re-ordered
+ * weight_ih, W1's planes), never a goal.  A learn pass leaves the goal vectors and their embeddings in the workspace for
+ * ec_policy_backward*.  No float atomics anywhere on these handles: two runs give the same bits, and an actor's result does
+ * not depend on how the actors are sliced.  The integer-goal entry points return EC_ERR_ARG on a goal_in > 0 handle, these
+ * on a goal_in == 0 handle. */
+int ec_policy_forward_vec(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                          const float* goal_vec, const float* h0, const float* masks, int T, int N,
+                          void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream);
+int ec_policy_act_vec(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                      const float* goal_vec, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
+                      int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
+                      uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream);
 /* dhv f32 [T*N, A+1] = dLoss/dhv; dh_final [N,H] or NULL; grads += dLoss/dparams.
  * `workspace` must be the one the matching ec_policy_forward filled (for_backward size). */
 int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,
