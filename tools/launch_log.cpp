@@ -12,6 +12,13 @@
 //   gemm  M N K act res                             ec_gemm_bf16
 //   x3    M N K act                                 ec_gemm_bf16a_x3
 //   trunk clip50|tv50|tv18|vitb32 frames min_tiles  create + ec_*_set_conv8_min_tiles + one forward + destroy
+//   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse
+//                                                   create + ec_policy_workspace_bytes + ec_policy_forward2 (goal_in > 0:
+//                                                   ec_policy_forward_vec) + destroy; mode 0 = EC_POLICY_INFER, 1 = _LEARN;
+//                                                   reuse 1: an EC_POLICY_INFER call builds the tables first (`B <rc>` ends
+//                                                   its launches), then the recorded call is EC_POLICY_INFER_REUSE in the
+//                                                   same workspace.  `W <bytes>` is the workspace size, `D <bytes>` a
+//                                                   device-to-device hipMemcpyAsync (policy commands only)
 // Output: `K <kernel>` per registered kernel, then per command `C <command>`, one `L <kernel>|<grid>|<block>|<lds>` per
 // launch (with --args N: `|` + the first N bytes of the first kernel argument in hex, for the conv_igemm kernels) and `R <rc>`.
 #include <cxxabi.h>
@@ -31,6 +38,7 @@ struct dim3 { unsigned x, y, z; };
 static std::map<const void*, std::string> g_kernels;
 static struct { dim3 grid, block; size_t lds; void* stream; } g_cfg;
 static int g_dump_args = 0;
+static int g_log_copies = 0;                   // policy commands: hipMemcpyAsync is part of the recorded sequence
 static uintptr_t g_next = 0x100000000000ull;   // fake device addresses; never dereferenced
 static void* fake(size_t bytes) { void* p = (void*)g_next; g_next += (bytes + 0xfffff) & ~(size_t)0xfffff; return p; }
 
@@ -67,7 +75,10 @@ int hipMalloc(void** p, size_t n) { *p = fake(n); return 0; }
 int hipFree(void*) { return 0; }
 int hipMemcpy(void*, const void*, size_t, int) { return 0; }
 int hipMemcpy2D(void*, size_t, const void*, size_t, size_t, size_t, int) { return 0; }
-int hipMemcpyAsync(void*, const void*, size_t, int, void*) { return 0; }
+int hipMemcpyAsync(void*, const void*, size_t n, int, void*) {
+    if (g_log_copies) printf("D %zu\n", n);
+    return 0;
+}
 int hipMemsetAsync(void*, int, size_t, void*) { return 0; }
 int hipDeviceSynchronize() { return 0; }
 int hipStreamSynchronize(void*) { return 0; }
@@ -135,6 +146,30 @@ static int run_trunk(const std::string& kind, int frames, int min_tiles) {
     return rc;
 }
 
+// v: the 13 ec_policy_cfg fields, then T, N, mode, bf16, reuse
+static int run_policy(const int* v) {
+    typedef void* P;
+    const int T = v[13], N = v[14], mode = v[15], bf16 = v[16], reuse = v[17], goal_in = v[12], dual = v[11];
+    if (mode < 0 || mode > 1 || (reuse && mode != 0)) return -100;
+    void* h = nullptr;
+    int rc = sym<int (*)(P*, const int*)>("ec_policy_create")(&h, v);
+    if (rc) return rc;
+    const size_t ws = sym<size_t (*)(P, int, int, int)>("ec_policy_workspace_bytes")(h, T, N, mode);
+    printf("W %zu\n", ws);
+    const P params = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4), feat = fake(1u << 30), feat2 = dual ? fake(1u << 30) : nullptr;
+    const P goal = fake(1u << 20), h0 = fake(1u << 24), masks = fake(1u << 20), wsp = fake(ws), hv = fake(1u << 20), hf = fake(1u << 24);
+    auto fwd = sym<int (*)(P, P, P, P, int, P, P, P, int, int, P, size_t, int, P, P, P)>(goal_in > 0 ? "ec_policy_forward_vec" : "ec_policy_forward2");
+    g_log_copies = 1;
+    if (reuse) {
+        rc = fwd(h, params, feat, feat2, bf16, goal, h0, masks, T, N, wsp, ws, 0 /* EC_POLICY_INFER */, hv, hf, nullptr);
+        printf("B %d\n", rc);
+    }
+    if (!rc) rc = fwd(h, params, feat, feat2, bf16, goal, h0, masks, T, N, wsp, ws, reuse ? 2 /* EC_POLICY_INFER_REUSE */ : mode, hv, hf, nullptr);
+    g_log_copies = 0;
+    sym<void (*)(P)>("ec_policy_destroy")(h);
+    return rc;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) { fprintf(stderr, "usage: launch_log LIB [--args N] < commands\n"); return 2; }
     if (argc >= 4 && !strcmp(argv[2], "--args")) g_dump_args = atoi(argv[3]);
@@ -154,11 +189,14 @@ int main(int argc, char** argv) {
         if (!(ss >> cmd)) continue;
         line[strcspn(line, "\n")] = 0;
         printf("C %s\n", line);
-        int v[10] = {0}, n = 0, rc = -100;
+        int v[18] = {0}, n = 0, rc = -100;
         std::string kind;
         if (cmd == "trunk") ss >> kind;
-        while (n < 10 && ss >> v[n]) ++n;
-        if (cmd == "conv" && n == 10) {
+        const int nmax = cmd == "policy" ? 18 : 10;
+        while (n < nmax && ss >> v[n]) ++n;
+        if (cmd == "policy" && n == 18) {
+            rc = run_policy(v);
+        } else if (cmd == "conv" && n == 10) {
             const P r = v[8] ? resb : nullptr;
             if (v[9] == 0)
                 rc = sym<int (*)(P, P, P, P, P, int, int, int, int, int, int, int, int, P)>("ec_conv_bf16")(
