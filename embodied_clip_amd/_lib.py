@@ -98,6 +98,12 @@ SIGNATURES = {
                                       c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
     "ec_policy_act_vec": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
                           + [C.c_uint64, C.c_uint64, c_int, c_void_p]),
+    # evaluation (readme_files/baselines_robothor_objectnav.md:66-68 `--eval`, baselines_habitat.md:89-97 `--run-type eval`,
+    # zeroshot_objectnav.md:20-27): the act entry points without seed / step / first_actor -- CategoricalDistr.mode()
+    "ec_policy_act_greedy": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
+                             + [c_void_p]),
+    "ec_policy_act_vec_greedy": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
+                                 + [c_void_p]),
     "ec_policy_backward2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "ec_policy_backward3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t,
@@ -109,6 +115,9 @@ SIGNATURES = {
     "ec_ppo_loss": (c_int, [c_void_p] * 8 + [C.c_long, c_int, c_float, c_float, c_float, c_float, c_void_p]),
     "ec_ppo_loss_ex": (c_int, [c_void_p] * 8 + [C.c_long, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p]),
     "ec_sample_actions": (c_int, [c_void_p] * 4 + [c_int, c_int, C.c_uint64, C.c_uint64, c_int, c_void_p]),
+    # ... its stand-alone selection (any number of actions) and the episode metrics an evaluation run reports (same reference lines)
+    "ec_mode_actions": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
+    "ec_episode_stats": (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_void_p]),
     "ec_vit_create": (c_int, [C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                               c_size_t]),
     "ec_vit_destroy": (None, [c_void_p]),

@@ -49,14 +49,34 @@ __device__ __forceinline__ uint64_t ec_mix64(uint64_t z) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+// log-sum-exp of one row of logits: the normaliser of log_prob(), shared by the sampling and the greedy selection below
 template <class RowFn>
-__device__ __forceinline__ void ec_sample_row(RowFn row, int A, uint64_t seed, uint64_t step, uint64_t global_actor, int& a_out,
-                                              float& logp_out) {
+__device__ __forceinline__ float ec_lse_row(RowFn row, int A) {
     float mx = -INFINITY;
     for (int k = 0; k < A; ++k) mx = fmaxf(mx, row(k));
     float se = 0.f;
     for (int k = 0; k < A; ++k) se += expf(row(k) - mx);
-    const float lse = mx + logf(se);
+    return mx + logf(se);
+}
+// CategoricalDistr.mode() + log_prob() of one row ([U] the same distributions.py: `self._param.argmax(dim=-1)`): the FIRST index
+// of the maximal logit (the tie rule numpy.argmax documents), evaluation's deterministic action.  Shared by mode_kernel (ppo.hip)
+// and the act step's heads launch (ec_policy_act_greedy).
+template <class RowFn>
+__device__ __forceinline__ void ec_mode_row(RowFn row, int A, int& a_out, float& logp_out) {
+    const float lse = ec_lse_row(row, A);
+    int a = 0;
+    float best = row(0);
+    for (int k = 1; k < A; ++k) {
+        const float v = row(k);
+        if (v > best) { best = v; a = k; }
+    }
+    a_out = a;
+    logp_out = best - lse;
+}
+template <class RowFn>
+__device__ __forceinline__ void ec_sample_row(RowFn row, int A, uint64_t seed, uint64_t step, uint64_t global_actor, int& a_out,
+                                              float& logp_out) {
+    const float lse = ec_lse_row(row, A);
     const uint64_t h = ec_mix64(ec_mix64(seed) ^ (step * 0x100000001B3ull + global_actor));
     const float u = (float)((h >> 40) * (1.0 / 16777216.0));   // [0,1) with 24 bits
     float cdf = 0.f;
@@ -67,6 +87,34 @@ __device__ __forceinline__ void ec_sample_row(RowFn row, int A, uint64_t seed, u
     }
     a_out = a;
     logp_out = row(a) - lse;
+}
+
+// Block reduction of up to NV doubles in a FIXED order (wave butterflies, then the waves' sums in wave order): thread 0 returns
+// the totals.  No atomics in the reductions that use it (round 6): a floating-point atomicAdd per block made the advantage
+// statistics, the loss sums and the gradient norm depend on the order the blocks happened to retire in -- two runs from one
+// seed differed in the last bits, and Adam's sign-like steps amplify that.  Shared by ppo.hip and episode.hip.
+__device__ __forceinline__ double ec_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+template <int NV, int NWAVES>
+__device__ __forceinline__ void ec_block_sum(double (&v)[NV], double (*red)[NV]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const double s = ec_wave_sum(v[i]);
+        if (lane == 0) red[wave][i] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            double t = 0.0;
+            for (int w = 0; w < NWAVES; ++w) t += red[w][i];
+            v[i] = t;
+        }
+    }
 }
 
 // Bijective XCD-aware remap of a linear block id (cdna guide T1): the

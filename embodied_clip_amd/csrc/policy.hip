@@ -1571,6 +1571,7 @@ struct SampleArgs {
     float* values = nullptr;
     uint64_t seed = 0, step = 0;
     int first_actor = 0;
+    int greedy = 0;               // 1: CategoricalDistr.mode() (ec_mode_row: first maximal logit) instead of a draw; seed / step / first_actor unused
 };
 template <int MAXO>
 __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict__ hs, const float* __restrict__ Wa,
@@ -1625,11 +1626,12 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict_
         if (lane == 0) {
             int a;
             float lp;
-            ec_sample_row([&](int k) { float v = 0.f;
+            const auto logit = [&](int k) { float v = 0.f;
 #pragma unroll
-                              for (int o = 0; o < MAXO; ++o) if (o == k) v = lg[o];
-                              return v; },
-                          A, smp.seed, smp.step, (uint64_t)(row + smp.first_actor), a, lp);
+                                            for (int o = 0; o < MAXO; ++o) if (o == k) v = lg[o];
+                                            return v; };
+            if (smp.greedy) ec_mode_row(logit, A, a, lp);          // (a runtime field: the same kernel instance serves evaluation)
+            else ec_sample_row(logit, A, smp.seed, smp.step, (uint64_t)(row + smp.first_actor), a, lp);
             smp.actions[row] = a;
             smp.logp[row] = lp;
             float vv = 0.f;
@@ -2399,6 +2401,30 @@ extern "C" int ec_policy_act_vec(const ec_policy_t* h, const float* params, cons
     if (!actions || !logp) return EC_ERR_ARG;
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
     const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
+    return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
+                               reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
+}
+
+// The evaluation act step (readme_files/baselines_robothor_objectnav.md:66-68 `--eval`, baselines_habitat.md:89-97
+// `--run-type eval`, zeroshot_objectnav.md:20-27): ec_policy_act / ec_policy_act_vec whose heads launch takes
+// CategoricalDistr.mode() instead of a draw (SampleArgs::greedy; the same kernel instances and launch geometry).
+extern "C" int ec_policy_act_greedy(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                                    const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
+                                    int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
+                                    ec_stream_t stream) {
+    if (!actions || !logp) return EC_ERR_ARG;
+    if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
+    const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
+    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, 1, N, workspace, ws_bytes,
+                               reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
+}
+extern "C" int ec_policy_act_vec_greedy(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                                        const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
+                                        size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
+                                        float* values, ec_stream_t stream) {
+    if (!actions || !logp) return EC_ERR_ARG;
+    if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
+    const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
                                reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
 }

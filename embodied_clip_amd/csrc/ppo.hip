@@ -14,33 +14,7 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-// Block reduction of up to NV doubles in a FIXED order (wave butterflies, then the waves' sums in wave order): thread 0 returns
-// the totals.  No atomics anywhere in this file's reductions (round 6): a floating-point atomicAdd per block made the advantage
-// statistics, the loss sums and the gradient norm depend on the order the blocks happened to retire in -- two runs from one
-// seed differed in the last bits, and Adam's sign-like steps amplify that.
-template <int NV, int NWAVES>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[NV]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const double s = wave_sum(v[i]);
-        if (lane == 0) red[wave][i] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            double t = 0.0;
-            for (int w = 0; w < NWAVES; ++w) t += red[w][i];
-            v[i] = t;
-        }
-    }
-}
+// (every reduction of this file: ec_block_sum, common.h -- a fixed order, no atomics)
 
 // One lane per sampler: reverse scan over T.
 //   delta = r[t] + g*V[t+1]*m[t+1] - V[t];  gae = delta + g*tau*m[t+1]*gae;  R[t] = gae + V[t]
@@ -65,7 +39,7 @@ __global__ __launch_bounds__(1024) void gae_kernel(const float* __restrict__ rew
         }
     }
     __shared__ double red[16][2];
-    block_sum<2, 16>(acc, red);
+    ec_block_sum<2, 16>(acc, red);
     if (threadIdx.x == 0) { stats[0] = acc[0]; stats[1] = acc[1]; }
 }
 
@@ -151,7 +125,7 @@ __global__ __launch_bounds__(1024) void ppo_loss_kernel(const float* __restrict_
         if (a < 0 || a >= A) acc[0] = (double)NAN;   // an out-of-range action id poisons the loss instead of passing silently
     }
     __shared__ double red[16][4];
-    block_sum<4, 16>(acc, red);
+    ec_block_sum<4, 16>(acc, red);
     if (threadIdx.x == 0) { sums[0] = acc[0]; sums[1] = acc[1]; sums[2] = acc[2]; sums[3] = acc[3]; }
 }
 
@@ -170,6 +144,21 @@ __global__ void sample_kernel(const float* __restrict__ hv, long long* __restric
     if (values) values[n] = row[A];
 }
 
+// CategoricalDistr.mode() + log_prob(): the first maximal logit (ec_mode_row, common.h) -- the two-call route of the
+// evaluation act step (more than 7 actions), beside sample_kernel.
+__global__ void mode_kernel(const float* __restrict__ hv, long long* __restrict__ actions, float* __restrict__ logp,
+                            float* __restrict__ values, int N, int A) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const float* row = hv + (long)n * (A + 1);
+    int a;
+    float lp;
+    ec_mode_row([&](int k) { return row[k]; }, A, a, lp);
+    actions[n] = a;
+    logp[n] = lp;
+    if (values) values[n] = row[A];
+}
+
 // sum of squares of the flat gradient bucket: every block folds its stride of the bucket in a fixed order and stores its partial
 // in scratch[1 + block]; the block that draws the last ticket (an INTEGER atomic: order-free) adds the partials in block order
 // into scratch[0].  scratch = EC_CLIP_ADAM_SCRATCH_DOUBLES doubles: [0] total, [1 .. 1024] partials, [1025] the ticket counter.
@@ -179,7 +168,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) acc[0] += (double)g[i] * (double)g[i];
     __shared__ double red[4][1];
     __shared__ unsigned last;
-    block_sum<1, 4>(acc, red);
+    ec_block_sum<1, 4>(acc, red);
     if (threadIdx.x == 0) {
         scratch[1 + blockIdx.x] = acc[0];
         __threadfence();                                             // the partial is visible device-wide before the ticket is
@@ -194,7 +183,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     double f[1] = {0.0};
     for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) f[0] += __hip_atomic_load(scratch + 1 + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();                                                 // (red is reused)
-    block_sum<1, 4>(f, red);
+    ec_block_sum<1, 4>(f, red);
     if (threadIdx.x == 0) {
         scratch[0] = f[0];
         *reinterpret_cast<unsigned*>(scratch + 1 + SUMSQ_MAX_BLOCKS) = 0u;
@@ -268,6 +257,15 @@ extern "C" int ec_sample_actions(const float* hv, int64_t* actions, float* logp,
     if (N <= 0 || A <= 0) return EC_ERR_SHAPE;
     hipLaunchKernelGGL(sample_kernel<16>, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, hv,
                        (long long*)actions, logp, values, N, A, seed, step, first_actor);
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
+
+extern "C" int ec_mode_actions(const float* hv, int64_t* actions, float* logp, float* values, int N, int A, ec_stream_t stream) {
+    if (!hv || !actions || !logp) return EC_ERR_ARG;
+    if (N <= 0 || A <= 0) return EC_ERR_SHAPE;
+    hipLaunchKernelGGL(mode_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, hv, (long long*)actions, logp,
+                       values, N, A);
     EC_CHECK_LAUNCH();
     return EC_OK;
 }

@@ -22,6 +22,7 @@ Rollout storage layout (the encoder writes straight into it):
 """
 from __future__ import annotations
 
+from collections import OrderedDict
 from typing import Dict, List, Optional
 
 import os
@@ -33,6 +34,7 @@ from . import _lib
 from . import synthetic as syn
 from .dist import (allreduce_flat, check_job_seed, collective_active, gather_actor_counts, global_minibatch_sizes,
                    minibatch_bounds)
+from .episodes import EpisodeTracker
 from .encoder import AttentionPool, ClipTextEncoder, ImageNetBasicTrunk, ImageNetRN50Trunk, RN50Trunk, ViTEmbedder
 from .policy import PolicyHandle
 from .ppo import FlatAdam, linear_decay_lr, ppo_loss_raw
@@ -74,6 +76,8 @@ class SyntheticEnv:
         self.goals = (syn.synthetic_goal_vectors(seed + 2, (T + 1, n_actors), goal_in) if goal_in
                       else syn.synthetic_goals(seed + 2, (T + 1, n_actors))).to(device).contiguous()
         self.rewards = syn.synthetic_rewards(seed + 3, masks[1:]).reshape(T, n_actors).to(device).contiguous()
+        # success flag of the step that ends an episode: the +10 reward of synthetic_rewards (episode metrics / evaluation)
+        self.success = ((self.rewards > 1) & (self.masks[1:] == 0)).to(torch.float32).contiguous()
         self._k = 0
 
     def observe(self, actions_host: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -93,72 +97,20 @@ class _Slice:
     pass
 
 
-class Worker:
-    """One DD-PPO worker.  The actor batch is processed as ``n_slices`` independent slices (default 2), each with its
-    own HIP stream, encoder handle, rollout feature buffer ``[T+1, n, S*S, C]``, policy workspaces and gradient
-    bucket.  Slices only meet at the GAE/advantage normalisation and at the gradient sum, so the HBM-bound and
-    MFMA-bound launches of one slice overlap the small / latency-bound launches (policy act step, GRU recurrence)
-    of the other.  Per-actor arithmetic does not depend on the slicing (tests assert identical features/actions)."""
+class _SlicedActor:
+    """What a training ``Worker`` and an ``evaluate.Evaluator`` share: the frozen encoder handles and the policy handle, the
+    actor slices with their streams, act workspaces and feature buffers, and hot loop A's encode step.  The users set
+    ``self.lib``, ``self.dev`` / ``self.device``, ``self.zeroshot``, ``self._text_sd``, ``self._goal_tokens``, ``self.goal_in``
+    and ``self._num_actions`` first, and ``self.env`` between ``_build_model`` and ``_build_slices``."""
 
-    def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, world: int = 1,
-                 update_repeats: int = 4, lr: float = 3e-4, max_grad_norm: float = 0.5, gamma: float = 0.99,
-                 tau: float = 0.95, encoder_sd=None, policy_sd=None, lr_total_steps: int = 300_000_000,
-                 encoder_chunk: int = 0, encoder: str = "rn50", encoder_streams: int = 2, frames_u8: bool = False,
-                 frames_host: bool = False, zeroshot: bool = False, text_sd=None, goal_tokens=None,
-                 num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
-                 overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6):
-        """``goal_in > 0``: the PointNav agent ([U] ResnetTensorPointNavActorCritic) -- the goal of a frame is ``goal_in``
-        floats (GPS + compass: distance, bearing), ``num_actions`` is 4 there; ``goal_in=0`` is the ObjectNav agent.
-
-        ``zeroshot=True`` (BASELINE config 5, readme_files/zeroshot_objectnav.md): the observation is the CLIP image
-        EMBEDDING (RN50 trunk + AttentionPool2d, 1024-d), the goal is the frozen CLIP text embedding of its prompt
-        (text tower run once -> [12, 1024] table) and the policy is the fusion=1 variant (GRU + heads trainable)."""
-        self.lib = _lib.load()
-        self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
-        assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
-        self.goal_in, self._num_actions = goal_in, num_actions
-        # sync_actions: the action-synchronous order of a real vectorised env ([U] VectorSampledTasks.step(actions)): every
-        # env step the sampled actions of ALL actors are copied to the host and waited for before observe() serves the next
-        # frames.  Default off: the synthetic env does not read the actions (SURVEY.md 8d) and the host issues ahead.
-        self.sync_actions = sync_actions
-        # force_allreduce: run the flat-bucket collective also at world size 1 (RCCL first-contact check on a 1-GPU box)
-        self.force_allreduce = force_allreduce
-        # overlap_allreduce (when there is a collective at all): the GRU + heads section of the flat bucket (92 % of its bytes,
-        # final first: ec_policy_backward3) is summed over ranks on a communication stream UNDER the rest of the backward;
-        # only the goal encoder's 1.1 MB is reduced after it (SURVEY.md 8e).  False: one 13.9-MB all-reduce after the backward
-        self.overlap_allreduce = overlap_allreduce
-        # [U] allenact RolloutStorage.recurrent_generator(num_mini_batch): contiguous sampler ranges, shuffled order
-        assert 1 <= num_mini_batch <= n_actors, "num_mini_batch must not exceed the number of samplers"
-        self.num_mini_batch = num_mini_batch
-        # ONE shuffle stream for all ranks: every rank visits the same minibatch range at the same optimiser step, so the
-        # SUM all-reduce with the fixed 1/world scale is the global minibatch mean also when N % num_mini_batch != 0
-        # (ranges of different sizes) -- with per-rank streams it would be a mean of differently-sized means
-        self._mb_rng = random.Random(seed)                  # (`seed` is the job's seed: identical on every rank)
-        self.dev = self.device = torch.device(device)
-        if self.dev.index is None:
-            self.dev = self.device = torch.device("cuda", torch.cuda.current_device())
-        check_job_seed(seed, world, device=self.dev)        # ... which is ENFORCED when a process group is up (on THIS worker's GPU)
-        # every rank's actor count: the gradient scale is local / GLOBAL minibatch size ([U] backprop_step), and the global size
-        # is the sum over the ranks -- shards need not be equal (dist.shard_actors(10, r, 3) = 4, 3, 3)
-        self.shard_counts = gather_actor_counts(n_actors, world, device=self.dev)
-        assert all(num_mini_batch <= c for c in self.shard_counts), "num_mini_batch must not exceed the smallest shard"
-        self._mb_global = global_minibatch_sizes(self.shard_counts, num_mini_batch)
-        self._init(n_actors, T, seed, rank, world, update_repeats, lr, max_grad_norm, gamma, tau, encoder_sd, policy_sd,
-                   lr_total_steps, encoder_chunk, encoder, encoder_streams, frames_u8, frames_host)
-
-    @_lib.on_device
-    def _init(self, n_actors, T, seed, rank, world, update_repeats, lr, max_grad_norm, gamma, tau, encoder_sd, policy_sd,
-              lr_total_steps, encoder_chunk, encoder, encoder_streams, frames_u8, frames_host=False):
-        self.N, self.T, self.rank, self.world = n_actors, T, rank, world
-        self.update_repeats, self.gamma, self.tau = update_repeats, gamma, tau
-        self.base_lr, self.lr_total_steps = lr, lr_total_steps
+    def _build_model(self, n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams):
+        """Encoder handles (one per slice, weights shared), the policy handle and its flat parameters.  -> (encs, pools)"""
         self.encoder = encoder
         # two slices (each with its own act -> encode chain on its own stream) from 48 actors on: measured round 3 at
         # 32 / 48 / 64 actors, one vs two slices: 26.8 / 29.0 / 35.0 k vs 26.1 / 31.8 / 36.8 k env-frames/s
         two_min = int(os.environ.get("EC_TWO_SLICE_MIN", "48"))          # (experiment switch for the rule above)
         ns = encoder_streams if (encoder_streams > 1 and n_actors >= two_min and n_actors % encoder_streams == 0) else 1
         self.ns = ns
-        n = n_actors // ns
         d = self.dev
         pools = [None] * ns
         if encoder in ("rn50", "rn50x16"):
@@ -211,24 +163,14 @@ class Worker:
             self.policy.set_goal_table(self.goal_table)
         self.H, self.A = self.policy.H, self.policy.A
         self.params = self.policy.flatten(policy_sd if policy_sd is not None else syn.policy_state_dict(0, **pkw), d)
-        self.grads = torch.zeros_like(self.params)
-        self.rec = self.policy.recurrent_section()          # GRU + heads: the part of the bucket whose gradients are final first
-        self.opt = FlatAdam(self.params, lr=lr, max_grad_norm=max_grad_norm)
-        N, S2 = n_actors, self.S * self.S
-        # [T, N] rollout scalars (global; tiny)
-        self.actions = torch.zeros((T, N), dtype=torch.int64, device=d)
-        self.logp = torch.zeros((T, N), dtype=torch.float32, device=d)
-        self.values = torch.zeros((T + 1, N), dtype=torch.float32, device=d)
-        self.returns = torch.zeros((T + 1, N), dtype=torch.float32, device=d)
-        self.adv = torch.zeros((T, N), dtype=torch.float32, device=d)
-        self.nadv = torch.zeros((T, N), dtype=torch.float32, device=d)
-        self.h_start = torch.zeros((N, self.H), dtype=torch.float32, device=d)
-        self.h = torch.zeros((N, self.H), dtype=torch.float32, device=d)
-        self.h_next = torch.zeros((N, self.H), dtype=torch.float32, device=d)
-        self.hv_act = torch.empty((N, self.A + 1), dtype=torch.float32, device=d)
-        self.stats = torch.zeros(2, dtype=torch.float64, device=d)
-        self.sums = torch.zeros(4, dtype=torch.float64, device=d)
-        self.env = SyntheticEnv(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in)
+        return encs, pools
+
+    def _build_slices(self, n_actors, encs, pools, feat_steps, n_comm, frames_host):
+        """Streams and the per-slice state hot loop A needs; ``feat_steps`` entries of feature storage per slice (T + 1: a
+        training rollout; 2: the ring of an evaluation run)."""
+        ns, d, encoder = self.ns, self.dev, self.encoder
+        n = n_actors // ns
+        S2 = self.S * self.S
         self.slices: List[_Slice] = []
         # Streams.  The HIP runtime has FOUR hardware queues and binds a stream to one of them at its first submission; two
         # streams on one queue run one after the other (a slice pair that shared a queue serialised the two encoder launches:
@@ -237,7 +179,6 @@ class Worker:
         # the slices' copy streams (frames in host memory) come from ONE pool that _lib.concurrent_streams has verified pairwise
         # concurrent; when that is more than the queues allow, the copy streams, then the communication stream, go unverified.
         n_own = ns if ns > 1 else 0
-        n_comm = 1 if (world > 1 or self.force_allreduce) else 0
         n_copy = ns if frames_host else 0
         plain = lambda k: [torch.cuda.Stream(device=d) for _ in range(k)]   # noqa: E731
         pool = None
@@ -258,26 +199,18 @@ class Worker:
         by = lambda kind: [s_ for s_, k_ in zip(pool, order) if k_ == kind]   # noqa: E731
         slice_streams = by("own") if n_own else [None]
         copy_streams = by("copy")
-        self.comm_stream = by("comm")[0] if n_comm else torch.cuda.Stream(device=d)
+        self.comm_stream = by("comm")[0] if n_comm else None      # (a Worker without a collective makes itself a plain one)
         for i in range(ns):
             sl = _Slice()
             sl.o, sl.n, sl.enc, sl.pool = i * n, n, encs[i], pools[i]
             sl.stream = slice_streams[i]
             # zero-shot: the rollout buffer holds fp32 image embeddings [T+1, n, 1, 1024]; else bf16 feature maps
-            sl.feat = torch.empty((T + 1, n, S2, self.C), dtype=torch.float32 if self.zeroshot else torch.bfloat16, device=d)
+            sl.feat = torch.empty((feat_steps, n, S2, self.C), dtype=torch.float32 if self.zeroshot else torch.bfloat16, device=d)
             sl.trunk_out = (torch.empty((n, self.trunk_S, self.trunk_S, self.trunk_C), dtype=torch.bfloat16, device=d)
                             if self.zeroshot else None)
             sl.tok = (torch.empty((n, encs[i].L, encs[i].D), dtype=torch.bfloat16, device=d) if encoder == "vit" else None)
             sl.ws_act = torch.empty(self.policy.workspace_bytes(1, n, False), dtype=torch.uint8, device=d)
             sl.act_tables_valid = False     # weight-derived tables in ws_act (rebuilt by the first act step after an update)
-            sl.ws_learn = torch.empty(self.policy.workspace_bytes(T, n, True), dtype=torch.uint8, device=d)
-            sl.hv = torch.empty((T * n, self.A + 1), dtype=torch.float32, device=d)
-            sl.dhv = torch.empty_like(sl.hv)
-            sl.grads = self.grads if ns == 1 else torch.zeros_like(self.params)
-            sl.rec_ready = torch.cuda.Event()
-            sl.rec_ready.record()          # (torch creates the hipEvent_t at the first record: the library needs the handle)
-            sl.sums = torch.zeros(4, dtype=torch.float64, device=d)
-            sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = None
             if frames_host:   # double-buffered device staging of the slice's frames + its own copy stream (SDMA)
                 fshape = (n,) + tuple(self.env.frames.shape[2:])
                 sl.stage = [torch.empty(fshape, dtype=self.env.frames.dtype, device=d) for _ in range(2)]
@@ -295,17 +228,8 @@ class Worker:
         for e in encs:
             e.set_conv8_min_tiles(self._conv8_min_tiles)
         self._act_fused = os.environ.get("EC_ACT_FUSED_SAMPLE", "1") != "0" and self.A + 1 <= 8   # (A/B switch; > 7 actions: two calls)
-        self.seed = seed + 7919 * rank
-        self.total_steps = 0
-        self.iter = 0
         self.trunk_events: List = []             # (start, end) HIP event pairs around the encoder launches
-        self.update_events: List = []            # ... and around the update phase (GAE excluded), one pair per timed iteration
         self.time_trunk = False
-        # first observation of the first rollout
-        rgb = self.env.observe()
-        for sl in self.slices:
-            self._encode_slice(sl, rgb, 0)
-        torch.cuda.synchronize(d)
 
     # ---- helpers ------------------------------------------------------------------------------
     @property
@@ -369,6 +293,128 @@ class Worker:
             ev.record(torch.cuda.current_stream())
             sl.consumed[i] = ev
 
+    # ---- parameters ---------------------------------------------------------------------------
+    def invalidate_act_tables(self):
+        """The act workspaces cache weight-derived tables (the goal-embedding table E1, the re-ordered weight_ih).  Call
+        this after ANY write to ``self.params`` that does not go through ``update()`` (checkpoint restore, parameter
+        broadcast, an external optimiser)."""
+        for sl in self.slices:
+            sl.act_tables_valid = False
+
+    def set_params(self, flat: torch.Tensor):
+        """Replace the flat parameter vector (e.g. a restored checkpoint) and drop everything derived from it."""
+        self.params.copy_(flat.to(self.params.device, self.params.dtype).view_as(self.params))
+        self.invalidate_act_tables()
+
+
+class Worker(_SlicedActor):
+    """One DD-PPO worker.  The actor batch is processed as ``n_slices`` independent slices (default 2), each with its
+    own HIP stream, encoder handle, rollout feature buffer ``[T+1, n, S*S, C]``, policy workspaces and gradient
+    bucket.  Slices only meet at the GAE/advantage normalisation and at the gradient sum, so the HBM-bound and
+    MFMA-bound launches of one slice overlap the small / latency-bound launches (policy act step, GRU recurrence)
+    of the other.  Per-actor arithmetic does not depend on the slicing (tests assert identical features/actions)."""
+
+    def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, world: int = 1,
+                 update_repeats: int = 4, lr: float = 3e-4, max_grad_norm: float = 0.5, gamma: float = 0.99,
+                 tau: float = 0.95, encoder_sd=None, policy_sd=None, lr_total_steps: int = 300_000_000,
+                 encoder_chunk: int = 0, encoder: str = "rn50", encoder_streams: int = 2, frames_u8: bool = False,
+                 frames_host: bool = False, zeroshot: bool = False, text_sd=None, goal_tokens=None,
+                 num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
+                 overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False):
+        """``track_episodes=True``: ``compute_returns()`` also folds the rollout's completed episodes into an ``EpisodeTracker``
+        (one more launch per iteration; ``episode_info()`` reads the means AllenAct logs every rollout).  Default off.
+
+        ``goal_in > 0``: the PointNav agent ([U] ResnetTensorPointNavActorCritic) -- the goal of a frame is ``goal_in``
+        floats (GPS + compass: distance, bearing), ``num_actions`` is 4 there; ``goal_in=0`` is the ObjectNav agent.
+
+        ``zeroshot=True`` (BASELINE config 5, readme_files/zeroshot_objectnav.md): the observation is the CLIP image
+        EMBEDDING (RN50 trunk + AttentionPool2d, 1024-d), the goal is the frozen CLIP text embedding of its prompt
+        (text tower run once -> [12, 1024] table) and the policy is the fusion=1 variant (GRU + heads trainable)."""
+        self.lib = _lib.load()
+        self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
+        assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
+        self.goal_in, self._num_actions = goal_in, num_actions
+        self.track_episodes = track_episodes
+        # sync_actions: the action-synchronous order of a real vectorised env ([U] VectorSampledTasks.step(actions)): every
+        # env step the sampled actions of ALL actors are copied to the host and waited for before observe() serves the next
+        # frames.  Default off: the synthetic env does not read the actions (SURVEY.md 8d) and the host issues ahead.
+        self.sync_actions = sync_actions
+        # force_allreduce: run the flat-bucket collective also at world size 1 (RCCL first-contact check on a 1-GPU box)
+        self.force_allreduce = force_allreduce
+        # overlap_allreduce (when there is a collective at all): the GRU + heads section of the flat bucket (92 % of its bytes,
+        # final first: ec_policy_backward3) is summed over ranks on a communication stream UNDER the rest of the backward;
+        # only the goal encoder's 1.1 MB is reduced after it (SURVEY.md 8e).  False: one 13.9-MB all-reduce after the backward
+        self.overlap_allreduce = overlap_allreduce
+        # [U] allenact RolloutStorage.recurrent_generator(num_mini_batch): contiguous sampler ranges, shuffled order
+        assert 1 <= num_mini_batch <= n_actors, "num_mini_batch must not exceed the number of samplers"
+        self.num_mini_batch = num_mini_batch
+        # ONE shuffle stream for all ranks: every rank visits the same minibatch range at the same optimiser step, so the
+        # SUM all-reduce with the fixed 1/world scale is the global minibatch mean also when N % num_mini_batch != 0
+        # (ranges of different sizes) -- with per-rank streams it would be a mean of differently-sized means
+        self._mb_rng = random.Random(seed)                  # (`seed` is the job's seed: identical on every rank)
+        self.dev = self.device = torch.device(device)
+        if self.dev.index is None:
+            self.dev = self.device = torch.device("cuda", torch.cuda.current_device())
+        check_job_seed(seed, world, device=self.dev)        # ... which is ENFORCED when a process group is up (on THIS worker's GPU)
+        # every rank's actor count: the gradient scale is local / GLOBAL minibatch size ([U] backprop_step), and the global size
+        # is the sum over the ranks -- shards need not be equal (dist.shard_actors(10, r, 3) = 4, 3, 3)
+        self.shard_counts = gather_actor_counts(n_actors, world, device=self.dev)
+        assert all(num_mini_batch <= c for c in self.shard_counts), "num_mini_batch must not exceed the smallest shard"
+        self._mb_global = global_minibatch_sizes(self.shard_counts, num_mini_batch)
+        self._init(n_actors, T, seed, rank, world, update_repeats, lr, max_grad_norm, gamma, tau, encoder_sd, policy_sd,
+                   lr_total_steps, encoder_chunk, encoder, encoder_streams, frames_u8, frames_host)
+
+    @_lib.on_device
+    def _init(self, n_actors, T, seed, rank, world, update_repeats, lr, max_grad_norm, gamma, tau, encoder_sd, policy_sd,
+              lr_total_steps, encoder_chunk, encoder, encoder_streams, frames_u8, frames_host=False):
+        self.N, self.T, self.rank, self.world = n_actors, T, rank, world
+        self.update_repeats, self.gamma, self.tau = update_repeats, gamma, tau
+        self.base_lr, self.lr_total_steps = lr, lr_total_steps
+        d = self.dev
+        encs, pools = self._build_model(n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams)
+        ns = self.ns
+        self.grads = torch.zeros_like(self.params)
+        self.rec = self.policy.recurrent_section()          # GRU + heads: the part of the bucket whose gradients are final first
+        self.opt = FlatAdam(self.params, lr=lr, max_grad_norm=max_grad_norm)
+        N = n_actors
+        # [T, N] rollout scalars (global; tiny)
+        self.actions = torch.zeros((T, N), dtype=torch.int64, device=d)
+        self.logp = torch.zeros((T, N), dtype=torch.float32, device=d)
+        self.values = torch.zeros((T + 1, N), dtype=torch.float32, device=d)
+        self.returns = torch.zeros((T + 1, N), dtype=torch.float32, device=d)
+        self.adv = torch.zeros((T, N), dtype=torch.float32, device=d)
+        self.nadv = torch.zeros((T, N), dtype=torch.float32, device=d)
+        self.h_start = torch.zeros((N, self.H), dtype=torch.float32, device=d)
+        self.h = torch.zeros((N, self.H), dtype=torch.float32, device=d)
+        self.h_next = torch.zeros((N, self.H), dtype=torch.float32, device=d)
+        self.hv_act = torch.empty((N, self.A + 1), dtype=torch.float32, device=d)
+        self.stats = torch.zeros(2, dtype=torch.float64, device=d)
+        self.sums = torch.zeros(4, dtype=torch.float64, device=d)
+        self.env = SyntheticEnv(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in)
+        self.episodes = EpisodeTracker(N, d) if self.track_episodes else None
+        self._build_slices(n_actors, encs, pools, T + 1, 1 if (world > 1 or self.force_allreduce) else 0, frames_host)
+        if self.comm_stream is None:
+            self.comm_stream = torch.cuda.Stream(device=d)
+        for sl in self.slices:      # the learn pass's share of a slice
+            sl.ws_learn = torch.empty(self.policy.workspace_bytes(T, sl.n, True), dtype=torch.uint8, device=d)
+            sl.hv = torch.empty((T * sl.n, self.A + 1), dtype=torch.float32, device=d)
+            sl.dhv = torch.empty_like(sl.hv)
+            sl.grads = self.grads if ns == 1 else torch.zeros_like(self.params)
+            sl.rec_ready = torch.cuda.Event()
+            sl.rec_ready.record()          # (torch creates the hipEvent_t at the first record: the library needs the handle)
+            sl.sums = torch.zeros(4, dtype=torch.float64, device=d)
+            sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = None
+        self.seed = seed + 7919 * rank
+        self.total_steps = 0
+        self.iter = 0
+        self.update_events: List = []            # (start, end) HIP event pairs around the update phase (GAE excluded), one pair per timed iteration
+        # first observation of the first rollout
+        rgb = self.env.observe()
+        for sl in self.slices:
+            self._encode_slice(sl, rgb, 0)
+        torch.cuda.synchronize(d)
+
+    # ---- HOT LOOP A ---------------------------------------------------------------------------
     def _act_slice(self, sl, t: int, sample: bool = True):
         """Policy act step (T=1, no grad) for the slice's actors on the current stream."""
         o, n, sp = sl.o, sl.n, _lib.stream_ptr()
@@ -472,25 +518,14 @@ class Worker:
         if (T & 1) == 1:
             self.h, self.h_next = self.h_next, self.h
 
-    # ---- parameters ---------------------------------------------------------------------------
-    def invalidate_act_tables(self):
-        """The act workspaces cache weight-derived tables (the goal-embedding table E1, the re-ordered weight_ih).  Call
-        this after ANY write to ``self.params`` that does not go through ``update()`` (checkpoint restore, parameter
-        broadcast, an external optimiser)."""
-        for sl in self.slices:
-            sl.act_tables_valid = False
-
-    def set_params(self, flat: torch.Tensor):
-        """Replace the flat parameter vector (e.g. a restored checkpoint) and drop everything derived from it."""
-        self.params.copy_(flat.to(self.params.device, self.params.dtype).view_as(self.params))
-        self.invalidate_act_tables()
-
     @_lib.on_device
     def compute_returns(self):
         _lib.check(self.lib.ec_gae(self.env.rewards.data_ptr(), self.values.data_ptr(), self.env.masks.data_ptr(),
                                    self.returns.data_ptr(), self.adv.data_ptr(), self.nadv.data_ptr(),
                                    self.stats.data_ptr(), self.T, self.N, self.gamma, self.tau, 1e-5,
                                    _lib.stream_ptr()), "ec_gae")
+        if self.episodes is not None:
+            self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None))
 
     # ---- HOT LOOP B ---------------------------------------------------------------------------
     def _gather_slice_batches(self):
@@ -638,6 +673,40 @@ class Worker:
                 e1.record(torch.cuda.current_stream())
             self.update_events.append((e0, e1))
         self.after_update()
+
+    def episode_info(self) -> Dict[str, float]:
+        """``{"episodes", "reward", "reward_std", "ep_length", "success"}`` over the episodes completed so far: the scalars
+        [U] AllenAct logs every rollout (``track_episodes=True`` only)."""
+        if self.episodes is None:
+            raise RuntimeError("Worker(track_episodes=True) keeps the episode metrics")
+        return self.episodes.info()
+
+    # ---- checkpoints --------------------------------------------------------------------------
+    def save_checkpoint(self, path: str) -> None:
+        """``torch.save`` of ``{"model_state_dict", "optimizer_state_dict", "total_steps"}``: the key layout of [U] AllenAct's
+        ``exp_...__stage_00__steps_N.pt`` files RESTATED, not pinned against one -- the model's tensors under
+        AllenAct's parameter names (``ResnetTensorObjectNavActorCritic.load_state_dict`` takes them), the optimiser as the
+        flat Adam moments (``exp_avg``, ``exp_avg_sq``, ``step``) of the flat bucket, not torch's per-parameter state."""
+        model = OrderedDict((k, v.detach().cpu().clone()) for k, v in self.policy.views(self.params).items())
+        torch.save({"model_state_dict": model,
+                    "optimizer_state_dict": {"exp_avg": self.opt.m.cpu(), "exp_avg_sq": self.opt.v.cpu(), "step": self.opt.step_count},
+                    "total_steps": self.total_steps}, path)
+
+    def load_checkpoint(self, path: str) -> None:
+        """Restore what ``save_checkpoint`` wrote: the parameters (through ``set_params``: the act tables are dropped), the
+        Adam moments and step count, and ``total_steps`` (the learning-rate schedule's position).  ``iter`` -- the iteration
+        index in the sampling keys ``iter * (T + 1) + t`` -- is set to the number of rollouts ``total_steps`` stands for with
+        THIS worker's rollout size, so a resumed worker does not redraw the keys of iteration 0.  Not restored: the
+        minibatch shuffle stream (``_mb_rng`` restarts from the seed), the recurrent memory and the env's position -- a
+        resumed run continues the optimisation, it is not a bit-for-bit continuation of the uninterrupted one."""
+        ck = torch.load(path, map_location="cpu")
+        self.set_params(self.policy.flatten(ck["model_state_dict"], self.dev))
+        o = ck["optimizer_state_dict"]
+        self.opt.m.copy_(o["exp_avg"].to(self.dev).view_as(self.opt.m))
+        self.opt.v.copy_(o["exp_avg_sq"].to(self.dev).view_as(self.opt.v))
+        self.opt.step_count = int(o["step"])
+        self.total_steps = int(ck["total_steps"])
+        self.iter = self.total_steps // (self.T * sum(self.shard_counts))
 
     def loss_info(self) -> Dict[str, float]:
         parts = getattr(self, "_loss_parts", None) or [(sl, sl.n) for sl in self.slices]   # the last minibatch

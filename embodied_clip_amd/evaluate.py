@@ -1,0 +1,192 @@
+"""Evaluation: run a trained agent and read out how well it does.
+
+The reference ends its experiment pages with this step -- ``--eval`` appended to the training command
+(readme_files/baselines_robothor_objectnav.md:66-68), ``--run-type eval`` (baselines_habitat.md:89-97), the same config with
+``--eval -c $CKPT_PATH`` (zeroshot_objectnav.md:20-27) -- which [U] AllenAct serves with ``OnPolicyInference``: the act loop of
+training without storage, loss or optimiser, ``CategoricalDistr.mode()`` or ``sample()`` for the actions, and the finished
+tasks' metrics averaged at the end.
+
+``Evaluator`` is hot loop A of ``engine.Worker`` alone, built from the same parts (``engine._SlicedActor``): per slice stream
+``act(t)`` then ``encode(t + 1)``.  It allocates no learn workspace, no ``hv`` / ``dhv``, no gradient buckets and no ``[T+1]``
+feature storage: each slice keeps a two-entry feature ring.  The episode metrics come from ``episodes.EpisodeTracker``.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib
+from .engine import SyntheticEnv, _SlicedActor
+from .episodes import EpisodeTracker
+
+
+class Evaluator(_SlicedActor):
+    """``run(chunks)`` plays ``chunks * T`` env steps of ``n_actors`` actors; ``info()`` returns the episode metrics.
+
+    Chunk ``c``, step ``t`` reads ``env.masks[t]`` / ``env.goals[t]`` and (when sampling) draws with the seed ``seed + 7919 *
+    rank`` and the key ``c * (T + 1) + t`` -- what a ``Worker`` with the same arguments uses in iteration ``c``, so with equal
+    weights the two take the same actions.  ``deterministic=True`` takes ``CategoricalDistr.mode()`` instead
+    (``ec_policy_act_greedy``).  The memory ``h`` carries across chunks.  ``checkpoint=`` is a file of
+    ``Worker.save_checkpoint`` (its ``model_state_dict``); otherwise ``policy_sd`` or the seeded stand-in weights.
+    ``record=True`` keeps ``actions``, ``logp``, ``values`` ``[chunks*T, N]`` and ``hv`` ``[chunks*T, N, A+1]`` of the last
+    ``run`` (tests).  ``env=``: any object with ``SyntheticEnv``'s attributes (``N``, ``T``, ``frames``, ``masks``, ``goals``,
+    ``rewards``, ``success``, ``host``, ``observe``); its ``N`` and ``T`` must be the evaluator's.  ``sync_actions=True``: every step's actions are copied to the host and waited for
+    before the env serves the next frames (one vectorised env for all actors)."""
+
+    def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, encoder: str = "rn50",
+                 encoder_sd=None, policy_sd=None, checkpoint: Optional[str] = None, deterministic: bool = False,
+                 encoder_streams: int = 2, frames_u8: bool = False, goal_in: int = 0, num_actions: int = 6,
+                 zeroshot: bool = False, sync_actions: bool = False, record: bool = False, env=None, text_sd=None,
+                 goal_tokens=None, encoder_chunk: int = 0, record_capacity: int = 0):
+        self.lib = _lib.load()
+        self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
+        assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
+        assert policy_sd is None or checkpoint is None, "policy_sd and checkpoint both name the weights"
+        if sync_actions not in (False, True):
+            raise ValueError("Evaluator: sync_actions is False or True (one vectorised env for all actors)")
+        self.goal_in, self._num_actions = goal_in, num_actions
+        self.deterministic, self.sync_actions, self.record = deterministic, sync_actions, record
+        self.dev = self.device = torch.device(device)
+        if self.dev.index is None:
+            self.dev = self.device = torch.device("cuda", torch.cuda.current_device())
+        self.checkpoint_steps = None
+        if checkpoint is not None:
+            ck = torch.load(checkpoint, map_location="cpu")
+            policy_sd, self.checkpoint_steps = ck["model_state_dict"], int(ck.get("total_steps", 0))
+        self._init(n_actors, T, seed, rank, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams, frames_u8, env,
+                   record_capacity)
+
+    @_lib.on_device
+    def _init(self, n_actors, T, seed, rank, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams, frames_u8, env,
+              record_capacity):
+        self.N, self.T, self.rank = n_actors, T, rank
+        N = n_actors
+        d = self.dev
+        encs, pools = self._build_model(n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams)
+        self.h = torch.zeros((N, self.H), dtype=torch.float32, device=d)
+        self.h_next = torch.zeros((N, self.H), dtype=torch.float32, device=d)
+        # one step's results (record=True: run() points these at the rows of the [chunks*T, ...] recordings instead)
+        self._hv = torch.empty((1, N, self.A + 1), dtype=torch.float32, device=d)
+        self._actions = torch.zeros((1, N), dtype=torch.int64, device=d)
+        self._logp = torch.zeros((1, N), dtype=torch.float32, device=d)
+        self._values = torch.zeros((1, N), dtype=torch.float32, device=d)
+        self.actions = self.logp = self.values = self.hv = None
+        self.env = env if env is not None else SyntheticEnv(N, T, d, seed=1000 + rank, frames_u8=frames_u8, goal_in=self.goal_in)
+        assert (self.env.N, self.env.T) == (N, T), "the env's actor count and rollout length are the evaluator's"
+        self.episodes = EpisodeTracker(N, d, capacity=record_capacity)
+        self._build_slices(n_actors, encs, pools, 2, 0, bool(self.env.host))
+        self.seed = seed + 7919 * rank
+        self.chunk = 0                  # chunks played so far (the sampling key's iteration; carries across run() calls)
+        self.k = 0                      # env steps played so far: the feature ring's and the memory ping-pong's parity
+        rgb = self.env.observe()        # first observation
+        for sl in self.slices:
+            self._encode_slice(sl, rgb, 0)
+        torch.cuda.synchronize(d)
+
+    # ---- one act step of a slice ----------------------------------------------------------------
+    def _act_slice(self, sl, t: int, row: int):
+        """Chunk step ``t`` of the slice's actors on the current stream; results go to row ``row`` of the step buffers."""
+        o, n = sl.o, sl.n
+        rs = slice(o, o + n)
+        h_in, h_out = (self.h, self.h_next) if (self.k & 1) == 0 else (self.h_next, self.h)
+        feat = sl.feat[self.k & 1]
+        hv, actions, logp, values = self._hv[row][rs], self._actions[row][rs], self._logp[row][rs], self._values[row][rs]
+        key = self.chunk * (self.T + 1) + t
+        if self._act_fused:
+            self.policy.act(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
+                            actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
+                            deterministic=self.deterministic)
+        else:   # more than 7 actions: the forward, then the stand-alone selection kernel
+            self.policy.forward(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n, sl.ws_act,
+                                hv=hv, h_final=h_out[rs], for_backward=False, reuse_tables=sl.act_tables_valid)
+            if self.deterministic:
+                _lib.check(self.lib.ec_mode_actions(hv.data_ptr(), actions.data_ptr(), logp.data_ptr(), values.data_ptr(), n,
+                                                    self.A, _lib.stream_ptr()), "ec_mode_actions")
+            else:
+                _lib.check(self.lib.ec_sample_actions(hv.data_ptr(), actions.data_ptr(), logp.data_ptr(), values.data_ptr(), n,
+                                                      self.A, self.seed, key, o, _lib.stream_ptr()), "ec_sample_actions")
+        sl.act_tables_valid = True
+
+    @_lib.on_device
+    def run(self, chunks: int = 1) -> Dict[str, float]:
+        """Play ``chunks * T`` env steps; after each chunk the tracker takes the env's ``rewards`` / ``masks`` / ``success``."""
+        T, N, d = self.T, self.N, self.dev
+        if self.record:
+            self.hv = self._hv = torch.empty((chunks * T, N, self.A + 1), dtype=torch.float32, device=d)
+            self.actions = self._actions = torch.zeros((chunks * T, N), dtype=torch.int64, device=d)
+            self.logp = self._logp = torch.zeros((chunks * T, N), dtype=torch.float32, device=d)
+            self.values = self._values = torch.zeros((chunks * T, N), dtype=torch.float32, device=d)
+        if self.sync_actions and getattr(self, "_actions_host", None) is None:
+            self._actions_host = torch.empty((N,), dtype=torch.int64).pin_memory()
+        for c in range(chunks):
+            self._fork()
+            for t in range(T):
+                row = c * T + t if self.record else 0
+                if self.sync_actions:
+                    for sl in self.slices:
+                        with self._on(sl):
+                            self._act_slice(sl, t, row)
+                            self._actions_host[sl.o:sl.o + sl.n].copy_(self._actions[row][sl.o:sl.o + sl.n], non_blocking=True)
+                    for sl in self.slices:
+                        (sl.stream if sl.stream is not None else torch.cuda.current_stream()).synchronize()
+                    rgb = self.env.observe(self._actions_host)          # env.step(actions[t])
+                    for sl in self.slices:
+                        with self._on(sl):
+                            self._encode_slice(sl, rgb, (self.k + 1) & 1)
+                else:
+                    rgb = self.env.observe()      # env.step(actions[t]) happens here in the real system
+                    for sl in self.slices:
+                        with self._on(sl):
+                            self._act_slice(sl, t, row)
+                            self._encode_slice(sl, rgb, (self.k + 1) & 1)
+                self.k += 1
+            self._join()
+            self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None))
+            self.chunk += 1
+        return self.info()
+
+    def info(self) -> Dict[str, float]:
+        """``{"episodes", "reward", "reward_std", "ep_length", "success"}`` over the episodes completed so far."""
+        return self.episodes.info()
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m embodied_clip_amd.evaluate",
+                                 description="Run an agent for chunks x steps env steps on the synthetic env and print its episode metrics.")
+    ap.add_argument("--checkpoint", default=None, help="a file written by Worker.save_checkpoint (policy weights; the encoder stays the seeded stand-in)")
+    ap.add_argument("--encoder", default="rn50")
+    ap.add_argument("--actors", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=128, help="env steps per chunk (the rollout length T)")
+    ap.add_argument("--chunks", type=int, default=4)
+    ap.add_argument("--deterministic", action="store_true", help="CategoricalDistr.mode() instead of sample()")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--goal-in", type=int, default=0)
+    ap.add_argument("--num-actions", type=int, default=6)
+    ap.add_argument("--zeroshot", action="store_true")
+    ap.add_argument("--frames-u8", action="store_true")
+    ap.add_argument("--sync-actions", action="store_true")
+    ap.add_argument("--json", default=None, metavar="OUT", help="also write the info dict to this file")
+    a = ap.parse_args(argv)
+    print("evaluate: the frozen encoder holds the seeded stand-in weights (a checkpoint carries the policy only)", file=sys.stderr)
+    if a.checkpoint is None:
+        print("evaluate: no --checkpoint given: using the seeded stand-in weights (an untrained agent)", file=sys.stderr)
+    ev = Evaluator(a.actors, T=a.steps, seed=a.seed, encoder=a.encoder, checkpoint=a.checkpoint, deterministic=a.deterministic,
+                   goal_in=a.goal_in, num_actions=a.num_actions, zeroshot=a.zeroshot, frames_u8=a.frames_u8,
+                   sync_actions=a.sync_actions)
+    info = ev.run(a.chunks)
+    torch.cuda.synchronize()
+    info = dict(info, env_steps=a.chunks * a.steps * a.actors, deterministic=bool(a.deterministic),
+                policy_weights=a.checkpoint or "seeded stand-in", encoder_weights="seeded stand-in", checkpoint_steps=ev.checkpoint_steps)
+    print(json.dumps(info))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(info, f)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -121,18 +121,21 @@ class PolicyHandle:
             mode = 1 if for_backward else (2 if reuse_tables else 0)
             return self._forward(flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, mode, feat2)
 
-    def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int, step: int,
-            first_actor: int, reuse_tables: bool = False, feat2=None):
+    def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
+            first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False):
         """The act step in one call (``ec_policy_act``): the T = 1 inference forward whose heads launch also samples
-        ``actions`` / ``logp`` (and copies ``values``) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions``."""
+        ``actions`` / ``logp`` (and copies ``values``) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions``.
+        ``deterministic=True`` (evaluation): the heads launch takes ``CategoricalDistr.mode()`` instead, the first maximal logit
+        (``ec_policy_act_greedy``; ``seed`` / ``step`` / ``first_actor`` are not used) -- ``forward`` + ``ec_mode_actions``."""
         assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
+        name = ("ec_policy_act_vec" if self.goal_in else "ec_policy_act") + ("_greedy" if deterministic else "")
+        key = () if deterministic else (seed, step, first_actor)
         with _lib.tensor_guard(flat_params):
-            fn = self.lib.ec_policy_act_vec if self.goal_in else self.lib.ec_policy_act
-            _lib.check(fn(
+            _lib.check(getattr(self.lib, name)(
                 self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), self._goal_ptr(goal, N),
                 h0.data_ptr(), masks.data_ptr(), N, ws.data_ptr(), ws.numel() * ws.element_size(), int(reuse_tables),
-                hv.data_ptr(), h_final.data_ptr(), actions.data_ptr(), logp.data_ptr(), _lib.ptr(values), seed, step, first_actor,
-                _lib.stream_ptr()), "ec_policy_act_vec" if self.goal_in else "ec_policy_act")
+                hv.data_ptr(), h_final.data_ptr(), actions.data_ptr(), logp.data_ptr(), _lib.ptr(values), *key,
+                _lib.stream_ptr()), name)
         return hv, h_final
 
     def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None):

@@ -421,6 +421,20 @@ int ec_policy_act_vec(const ec_policy_t* h, const float* params, const void* fea
                       const float* goal_vec, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                       int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                       uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream);
+/* The EVALUATION act step (the reference's readme_files/baselines_robothor_objectnav.md:66-68 `--eval`,
+ * baselines_habitat.md:89-97 `--run-type eval`, zeroshot_objectnav.md:20-27 `--eval -c $CKPT_PATH`): ec_policy_act /
+ * ec_policy_act_vec whose heads launch takes [U] CategoricalDistr.mode() -- the FIRST index of the maximal logit -- instead of
+ * a draw; logp = log_prob(actions) with the normaliser of the sampling route.  No seed, step or actor key: nothing is drawn.
+ * hv and h_final are those of ec_policy_forward2 / _vec; actions, logp, values are those of ec_mode_actions on that hv, bit
+ * for bit.  Same error codes as ec_policy_act (EC_ERR_UNSUPPORTED for more than 7 actions: use the two calls). */
+int ec_policy_act_greedy(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                         const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
+                         int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
+                         ec_stream_t stream);
+int ec_policy_act_vec_greedy(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                             const float* goal_vec, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
+                             int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
+                             ec_stream_t stream);
 /* dhv f32 [T*N, A+1] = dLoss/dhv; dh_final [N,H] or NULL; grads += dLoss/dparams.
  * `workspace` must be the one the matching ec_policy_forward filled (for_backward size). */
 int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,
@@ -465,6 +479,25 @@ int ec_ppo_loss_ex(const float* hv, const int64_t* actions, const float* old_log
  * slices (e.g. one per HIP stream) with identical results. */
 int ec_sample_actions(const float* hv, int64_t* actions, float* logp, float* values, int N, int A,
                       uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream);
+/* actions = [U] CategoricalDistr.mode() of Categorical(logits = hv[:, :A]) -- the first index of the maximal logit;
+ * logp = log_prob(actions); values = hv[:, A] (or NULL).  The deterministic action selection of an evaluation run (the
+ * reference's `--eval` / `--run-type eval`: readme_files/baselines_robothor_objectnav.md:66-68, baselines_habitat.md:89-97,
+ * zeroshot_objectnav.md:20-27); the stand-alone half of the two-call act step (any A). */
+int ec_mode_actions(const float* hv, int64_t* actions, float* logp, float* values, int N, int A, ec_stream_t stream);
+/* Episode bookkeeping of a rollout on the device: what [U] allenact's tasks and ScalarMeanTracker keep on the host and log
+ * as `reward`, `ep_length`, `success` (restated; the metrics an evaluation run reports: readme_files/
+ * baselines_robothor_objectnav.md:66-68, baselines_habitat.md:89-97, zeroshot_objectnav.md:20-27).  Conventions of ec_gae.
+ * rewards f32 [T,N]; masks f32 [T+1,N] (masks[0] is not read); success f32 [T,N] or NULL (read at terminal steps only, NULL = 0).
+ * For t = 0..T-1: carry_ret[n] += rewards[t,n] (fp32, step order), carry_len[n] += 1; masks[t+1,n] == 0 completes the
+ * episode: it is added to totals5 (doubles: episodes, sum return, sum return^2, sum length, sum success), recorded, and both
+ * carries restart at 0.  A running episode stays in the carries (f32 / int32 [N], in/out) for the next call.
+ * Records (rec_f f32 [cap,2] = return, success; rec_i int32 [cap,3] = actor, t, length; both or neither may be NULL) are
+ * appended at *n_records in a fixed order -- actor ascending, then t -- and dropped past cap, while *n_records (device
+ * int32, in/out) and totals5 still count them: *n_records > cap tells the caller.  One workgroup, no floating-point
+ * atomics: two runs give the same bits. */
+int ec_episode_stats(const float* rewards, const float* masks, const float* success, float* carry_ret, int32_t* carry_len,
+                     double* totals5, float* rec_f, int32_t* rec_i, int cap, int32_t* n_records, int T, int N,
+                     ec_stream_t stream);
 /* clip_grad_norm_(max_grad_norm) (<=0 disables) then Adam (1-based `step`) over n floats;
  * sumsq1: device scratch of ec_clip_adam_scratch_doubles() doubles; sumsq1[0] receives ||grads||^2 (the blocks' partial sums
  * and a ticket counter live behind it: the norm is folded in a fixed order, bit-identical run to run). */
