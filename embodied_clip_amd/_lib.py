@@ -126,6 +126,13 @@ SIGNATURES = {
     "ec_vit_plan_hash": (C.c_uint64, [c_void_p]),
     "ec_vit_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "ec_vit_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # the transformer tower stages, one at a time (tests/test_gpu_vit_stages.py)
+    "ec_mha_bf16": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
+    "ec_layernorm_bf16": (c_int, [c_void_p] * 4 + [C.c_long, c_int, c_void_p]),
+    "ec_vit_assemble_bf16": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
+    "ec_row_stats_bf16": (c_int, [c_void_p] * 2 + [C.c_long, c_int, c_void_p]),
+    "ec_ln_fold_bf16": (c_int, [c_void_p] * 7 + [c_int] * 2 + [c_void_p]),
+    "ec_gemm_bf16_ln": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 2 + [c_int, c_void_p, C.POINTER(c_int), c_void_p]),
     "ec_bf16_to_f32": (c_int, [c_void_p, c_void_p, C.c_long, C.c_long, C.c_long, c_void_p]),
     "ec_attnpool_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ec_attnpool_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 8 + [c_size_t, c_void_p,

@@ -557,8 +557,52 @@ namespace {
 constexpr int MHA_GENERAL_MAX_TOKENS = 512;
 size_t mha_general_lds(int L) { return (size_t)L * 72 * 2 * 2 + 4 * 64 * 4 + 4 * (size_t)((L + 63) / 64 * 64) * 4; }
 
-// `layers` ResidualAttentionBlocks ([U] clip/model.py) on the bf16 residual stream x [B*L, D]; w / f point at the
-// first block's weights (wqkv, wo, wfc, wpr) / params (ln1 w,b, bqkv, bo, ln2 w,b, bfc, bpr) and are advanced.
+// ---- the launches of the tower stages: the towers below and the stage entry points (ec_mha_bf16, ec_layernorm_bf16, ...) at the
+//      end of this file issue every stage through these, so a test of an entry point is a test of the towers' launch ----
+constexpr float LN_EPS = 1e-5f;
+// the attention core a (tokens, mask) pair takes: mha_kernel (MFMA; L <= 64, no mask) or mha_general_kernel
+inline bool mha_is_general(int L, bool causal) { return causal || L > 64; }
+// once per run of launches: refuses what no core handles and raises the general core's dynamic-LDS limit
+int mha_prepare(int L, bool causal) {
+    if (!mha_is_general(L, causal)) return EC_OK;
+    if (L > MHA_GENERAL_MAX_TOKENS) return EC_ERR_SHAPE;
+    static std::atomic<uint64_t> attr_done{0};
+    if (auto attr_g_ = ec_attr_needed(attr_done)) {
+        const int mx = (int)mha_general_lds(MHA_GENERAL_MAX_TOKENS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_general_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_general_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+    }
+    return EC_OK;
+}
+void mha_launch(const uint16_t* qkv, uint16_t* att, int B, int L, int D, int heads, bool causal, hipStream_t s) {
+    if (!mha_is_general(L, causal))
+        hipLaunchKernelGGL(mha_kernel, dim3((unsigned)(B * heads)), dim3(64), 0, s, qkv, att, L, D, heads, 0.125f);
+    else if (causal)
+        hipLaunchKernelGGL(mha_general_kernel<true>, dim3((unsigned)(B * heads)), dim3(256), mha_general_lds(L), s, qkv, att,
+                           L, D, heads, 0.125f);
+    else
+        hipLaunchKernelGGL(mha_general_kernel<false>, dim3((unsigned)(B * heads)), dim3(256), mha_general_lds(L), s, qkv, att,
+                           L, D, heads, 0.125f);
+}
+void layernorm_launch(const uint16_t* x, const float* gamma, const float* beta, uint16_t* out, long rows, int D, hipStream_t s) {
+    hipLaunchKernelGGL(layernorm_kernel<0>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, nullptr, nullptr, gamma, beta, out,
+                       rows, D, 1, LN_EPS, nullptr);
+}
+// token assembly + ln_pre (+ the record of every output row when stats != nullptr: block 0's folded ln_1)
+void assemble_launch(const uint16_t* pemb, const float* cls, const float* pos, const float* gamma, const float* beta, uint16_t* out,
+                     float* stats, int B, int L, int D, hipStream_t s) {
+    const long rows = (long)B * L;
+    hipLaunchKernelGGL(layernorm_kernel<1>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, pemb, cls, pos, gamma, beta, out, rows,
+                       D, L, LN_EPS, (float4*)stats);
+}
+void row_stats_launch(const uint16_t* x, float* stats, long rows, int D, hipStream_t s) {
+    hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, (float4*)stats, rows, D);
+}
+void ln_fold_launch(const uint16_t* W, const float* gamma, const float* beta, const float* b, uint16_t* Wg, float* s_out, float* c_out,
+                    int N, int K, hipStream_t s) {
+    hipLaunchKernelGGL(ln_fold_kernel, dim3((unsigned)N), dim3(256), 0, s, W, gamma, beta, b, Wg, s_out, c_out, K);
+}
+
 // Builds the folded copies for `layers` blocks whose weights / params start at (w, f): EC_OK, or leaves fold.ok = false when the
 // geometry does not suit the folded GEMMs (D % 128 != 0, more than 8 records per row) -- run_blocks then keeps the LayerNorm launches.
 int build_lnfold(ec_lnfold& fold, const uint16_t* w, const float* f, int layers, int D) {
@@ -573,9 +617,8 @@ int build_lnfold(ec_lnfold& fold, const uint16_t* w, const float* f, int layers,
         const uint16_t *wqkv = w, *wfc = w + (size_t)4 * D * D;
         uint16_t* wg = fold.w + l * wl;
         float* fg = fold.f + l * fl;
-        hipLaunchKernelGGL(ln_fold_kernel, dim3((unsigned)(3 * D)), dim3(256), 0, nullptr, wqkv, ln1w, ln1b, bqkv, wg, fg, fg + 3 * Dz, D);
-        hipLaunchKernelGGL(ln_fold_kernel, dim3((unsigned)(4 * D)), dim3(256), 0, nullptr, wfc, ln2w, ln2b, bfc, wg + 3 * Dz * Dz,
-                           fg + 6 * Dz, fg + 10 * Dz, D);
+        ln_fold_launch(wqkv, ln1w, ln1b, bqkv, wg, fg, fg + 3 * Dz, 3 * D, D, nullptr);
+        ln_fold_launch(wfc, ln2w, ln2b, bfc, wg + 3 * Dz * Dz, fg + 6 * Dz, fg + 10 * Dz, 4 * D, D, nullptr);
         f += 13 * Dz;
         w += 12 * Dz * Dz;
     }
@@ -595,18 +638,8 @@ int run_blocks(const uint16_t*& w, const float*& f, int layers, int heads, uint1
                ec_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const long rows = (long)B * L;
-    const unsigned lnb = (unsigned)((rows + 3) / 4);
-    const bool general = causal || L > 64;
     const bool folded = fold && fold->ok && stats;
-    if (general) {
-        if (L > MHA_GENERAL_MAX_TOKENS) return EC_ERR_SHAPE;
-        static std::atomic<uint64_t> attr_done{0};
-        if (auto attr_g_ = ec_attr_needed(attr_done)) {
-            const int mx = (int)mha_general_lds(MHA_GENERAL_MAX_TOKENS);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_general_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_general_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        }
-    }
+    RC(mha_prepare(L, causal));
     for (int l = 0; l < layers; ++l) {
         const float *ln1w = f, *ln1b = f + D, *bqkv = f + 2 * D, *bo = bqkv + 3 * D, *ln2w = bo + D, *ln2b = ln2w + D;
         const float *bfc = ln2b + D, *bpr = bfc + 4 * D;
@@ -619,18 +652,10 @@ int run_blocks(const uint16_t*& w, const float*& f, int layers, int heads, uint1
         if (folded)
             RC(ec_gemm_bf16_ln8(x, wg, fg + 3 * Dz, nullptr, qkv, (int)rows, 3 * D, D, EC_ACT_NONE, fg, stats, np, nullptr, nullptr, stream));
         else {
-        hipLaunchKernelGGL(layernorm_kernel<0>, dim3(lnb), dim3(256), 0, s, x, nullptr, nullptr, ln1w, ln1b, hbuf, rows, D,
-                           L, 1e-5f, nullptr);
+        layernorm_launch(x, ln1w, ln1b, hbuf, rows, D, s);
         RC(ec_gemm_bf16(hbuf, wqkv, bqkv, nullptr, qkv, (int)rows, 3 * D, D, EC_ACT_NONE, stream));
         }
-        if (!general)
-            hipLaunchKernelGGL(mha_kernel, dim3((unsigned)(B * heads)), dim3(64), 0, s, qkv, att, L, D, heads, 0.125f);
-        else if (causal)
-            hipLaunchKernelGGL(mha_general_kernel<true>, dim3((unsigned)(B * heads)), dim3(256), mha_general_lds(L), s, qkv, att,
-                               L, D, heads, 0.125f);
-        else
-            hipLaunchKernelGGL(mha_general_kernel<false>, dim3((unsigned)(B * heads)), dim3(256), mha_general_lds(L), s, qkv, att,
-                               L, D, heads, 0.125f);
+        mha_launch(qkv, att, B, L, D, heads, causal, s);
         if (folded) {
             RC(ec_gemm_bf16_ln8(att, wo, bo, x, x, (int)rows, D, D, EC_ACT_NONE, nullptr, nullptr, 0, stats, &np, stream));   // x += out_proj(...); + ln_2's records
             RC(ec_gemm_bf16_ln8(x, wg + 3 * Dz * Dz, fg + 10 * Dz, nullptr, mlp, (int)rows, 4 * D, D, EC_ACT_QUICKGELU, fg + 6 * Dz, stats, np,
@@ -639,8 +664,7 @@ int run_blocks(const uint16_t*& w, const float*& f, int layers, int heads, uint1
             continue;
         }
         RC(ec_gemm_bf16(att, wo, bo, x, x, (int)rows, D, D, EC_ACT_NONE, stream));          // x += out_proj(...)
-        hipLaunchKernelGGL(layernorm_kernel<0>, dim3(lnb), dim3(256), 0, s, x, nullptr, nullptr, ln2w, ln2b, hbuf, rows, D,
-                           L, 1e-5f, nullptr);
+        layernorm_launch(x, ln2w, ln2b, hbuf, rows, D, s);
         RC(ec_gemm_bf16(hbuf, wfc, bfc, nullptr, mlp, (int)rows, 4 * D, D, EC_ACT_QUICKGELU, stream));
         RC(ec_gemm_bf16(mlp, wpr, bpr, x, x, (int)rows, D, 4 * D, EC_ACT_NONE, stream));     // x += c_proj(...)
     }
@@ -732,10 +756,7 @@ extern "C" int ec_vit_forward(const ec_vit_t* h, const float* rgb, int batch, vo
     else
     RC(ec_gemm_bf16(patches, w, nullptr, nullptr, pemb, B * G2, D, Kp, EC_ACT_NONE, stream));
     w += (size_t)D * Kp;
-    const long rows = (long)B * L;
-    const unsigned lnb = (unsigned)((rows + 3) / 4);
-    hipLaunchKernelGGL(layernorm_kernel<1>, dim3(lnb), dim3(256), 0, s, pemb, cls, pos, lnpre_w, lnpre_b, x, rows, D, L,
-                       1e-5f, h->fold.ok ? (float4*)stats : nullptr);   // (+ the record of every output row: block 0's folded ln_1)
+    assemble_launch(pemb, cls, pos, lnpre_w, lnpre_b, x, h->fold.ok ? stats : nullptr, B, L, D, s);
     RC(run_blocks(w, f, h->layers, h->heads, x, hbuf, qkv, att, mlp, B, L, D, false, &h->fold, stats, 1, stream));
     EC_CHECK_LAUNCH();
     return EC_OK;
@@ -809,7 +830,7 @@ extern "C" int ec_text_forward(const ec_text_t* h, const int32_t* tokens, int ba
     hipLaunchKernelGGL(embed_tokens_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, tokens, tok_emb, pos, x, rows, L,
                        D, h->vocab);
     if (h->fold.ok)   // the embedding rows' LayerNorm records for block 0's folded ln_1
-        hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, (float4*)stats, rows, D);
+        row_stats_launch(x, stats, rows, D, s);
     RC(run_blocks(w, f, h->layers, h->heads, x, hbuf, qkv, att, mlp, B, L, D, true, &h->fold, stats, 1, stream));
     hipLaunchKernelGGL(eot_layernorm_kernel, dim3((unsigned)B), dim3(64), 0, s, tokens, x, f, f + D, eot, L, D, 1e-5f);
     RC(ec_gemm_bf16(eot, w, nullptr, nullptr, emb, B, E, D, EC_ACT_NONE, stream));          // @ text_projection
@@ -857,4 +878,63 @@ extern "C" int ec_attnpool_forward(const void* feat, int batch, int HW, int C, i
                        0.125f);
     RC(ec_gemm_bf16(att, wc, bc, nullptr, ob, (int)B, out_dim, C, EC_ACT_NONE, stream));
     return ec_bf16_to_f32(ob, out, (long)B, out_dim, out_dim, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Stage entry points: each tower stage alone, through the launch functions the towers use (exposed for tests, as
+// ec_gemm_f32 / ec_split3_bf16 / ec_dw_tn_x3 expose the policy's inner GEMMs).  Arguments are checked before any HIP call.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+inline bool ln_width_ok(int D) { return D >= 64 && D % 64 == 0 && D <= 1024; }
+}  // namespace
+
+extern "C" int ec_mha_bf16(const void* qkv, void* out, int B, int L, int D, int heads, int causal, ec_stream_t stream) {
+    if (!qkv || !out) return EC_ERR_ARG;
+    if (B <= 0 || heads <= 0 || D <= 0 || D % heads != 0 || D / heads != 64 || L < 1 || L > MHA_GENERAL_MAX_TOKENS) return EC_ERR_SHAPE;
+    if ((long)B * heads >= (1L << 31) || (long)B * L * 3 * D * 2 >= (1L << 31)) return EC_ERR_SHAPE;
+    RC(mha_prepare(L, causal != 0));
+    mha_launch((const uint16_t*)qkv, (uint16_t*)out, B, L, D, heads, causal != 0, (hipStream_t)stream);
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
+
+extern "C" int ec_layernorm_bf16(const void* x, const float* gamma, const float* beta, void* out, long rows, int D,
+                                 ec_stream_t stream) {
+    if (!x || !gamma || !beta || !out) return EC_ERR_ARG;
+    if (rows <= 0 || rows >= (1L << 31) || !ln_width_ok(D)) return EC_ERR_SHAPE;
+    layernorm_launch((const uint16_t*)x, gamma, beta, (uint16_t*)out, rows, D, (hipStream_t)stream);
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
+
+extern "C" int ec_vit_assemble_bf16(const void* pemb, const float* cls, const float* pos, const float* gamma, const float* beta,
+                                    void* out, float* stats_or_null, int B, int L, int D, ec_stream_t stream) {
+    if (!pemb || !cls || !pos || !gamma || !beta || !out) return EC_ERR_ARG;
+    if (B <= 0 || L < 2 || (long)B * L >= (1L << 31) || !ln_width_ok(D)) return EC_ERR_SHAPE;
+    assemble_launch((const uint16_t*)pemb, cls, pos, gamma, beta, (uint16_t*)out, stats_or_null, B, L, D, (hipStream_t)stream);
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
+
+extern "C" int ec_row_stats_bf16(const void* x, float* stats, long rows, int D, ec_stream_t stream) {
+    if (!x || !stats) return EC_ERR_ARG;
+    if (rows <= 0 || rows >= (1L << 31) || !ln_width_ok(D)) return EC_ERR_SHAPE;
+    row_stats_launch((const uint16_t*)x, stats, rows, D, (hipStream_t)stream);
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
+
+extern "C" int ec_ln_fold_bf16(const void* W, const float* gamma, const float* beta, const float* b, void* Wg, float* s, float* c,
+                               int N, int K, ec_stream_t stream) {
+    if (!W || !gamma || !beta || !b || !Wg || !s || !c) return EC_ERR_ARG;
+    if (N <= 0 || K <= 0) return EC_ERR_SHAPE;
+    ln_fold_launch((const uint16_t*)W, gamma, beta, b, (uint16_t*)Wg, s, c, N, K, (hipStream_t)stream);
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
+
+extern "C" int ec_gemm_bf16_ln(const void* A, const void* Wt, const float* bias, const void* res, void* out, int M, int N, int K,
+                               int act, const float* ln_s, const float* ln_stats, int ln_np, float* stats_out, int* np_out,
+                               ec_stream_t stream) {
+    return ec_gemm_bf16_ln8(A, Wt, bias, res, out, M, N, K, act, ln_s, ln_stats, ln_np, stats_out, np_out, stream);
 }

@@ -88,6 +88,37 @@ int ec_gemm_bf16(const void* A, const void* W, const float* bias, const void* re
                  int M, int N, int K, int act, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Transformer tower stages, one at a time (vit.hip).  ec_vit_forward / ec_text_forward issue every stage through the
+ * same launch code; these entries exist so that each kernel can be tested alone against a float64 reference
+ * (tests/test_gpu_vit_stages.py), as ec_gemm_f32 / ec_split3_bf16 / ec_dw_tn_x3 expose the policy's inner GEMMs.
+ * Arguments are checked before any HIP call: NULL -> EC_ERR_ARG, a refused geometry -> EC_ERR_SHAPE.
+ *   ec_mha_bf16: softmax(q k^T / 8 [+ causal mask]) v per (sequence, head) of [U] clip/model.py
+ *     ResidualAttentionBlock.attention; qkv bf16 [B*L, 3D] (q | k | v, head h at columns 64 h..), out bf16 [B*L, D].
+ *     Non-causal L <= 64 runs the MFMA core, everything else the general LDS core.  D / heads == 64, 1 <= L <= 512.
+ *   ec_layernorm_bf16: nn.LayerNorm(D), eps 1e-5, bf16 rows in and out, fp32 gamma / beta.  D % 64 == 0, D <= 1024.
+ *   ec_vit_assemble_bf16: row t of frame b = ln_pre((t == 0 ? cls : pemb[b, t - 1]) + pos[t]); pemb bf16 [B*(L-1), D],
+ *     cls f32 [D], pos f32 [L, D].  stats_or_null: f32 [B*L][4], the record {sum, M2, D, 0} of every ROUNDED output
+ *     row.  Same widths, L >= 2.
+ *   ec_row_stats_bf16: the record {sum, M2, D, 0} of every bf16 row of x [rows, D].  Same widths.
+ *   ec_ln_fold_bf16: a LayerNorm folded into the Linear that consumes it: W bf16 [N, K], b f32 [N] ->
+ *     Wg = bf16(W diag(gamma)) [N, K], s[n] = sum_k Wg[n, k], c[n] = sum_k beta[k] W[n, k] + b[n].
+ *   ec_gemm_bf16_ln: the 8-wave GEMM with LayerNorm folded in.  Consumer (ln_s != NULL, no res): out = act(rstd (A Wt^T -
+ *     mean ln_s) + bias) with Wt / ln_s / bias = Wg / s / c of ec_ln_fold_bf16 and the rows' mean / rstd (eps 1e-5)
+ *     combined from the ln_np (1..8) records per row in ln_stats [M][ln_np][4].  Producer (stats_out != NULL):
+ *     out = act(A Wt^T + bias (+ res)) and one record per row and column tile into stats_out [M][*np_out][4]
+ *     (*np_out = N / 128 or N / 256, at most 8).  N % 128 == 0, K % 64 == 0.
+ * ---------------------------------------------------------------------- */
+int ec_mha_bf16(const void* qkv, void* out, int B, int L, int D, int heads, int causal, ec_stream_t stream);
+int ec_layernorm_bf16(const void* x, const float* gamma, const float* beta, void* out, long rows, int D, ec_stream_t stream);
+int ec_vit_assemble_bf16(const void* pemb, const float* cls, const float* pos, const float* gamma, const float* beta, void* out,
+                         float* stats_or_null, int B, int L, int D, ec_stream_t stream);
+int ec_row_stats_bf16(const void* x, float* stats, long rows, int D, ec_stream_t stream);
+int ec_ln_fold_bf16(const void* W, const float* gamma, const float* beta, const float* b, void* Wg, float* s, float* c, int N,
+                    int K, ec_stream_t stream);
+int ec_gemm_bf16_ln(const void* A, const void* Wt, const float* bias, const void* res, void* out, int M, int N, int K, int act,
+                    const float* ln_s, const float* ln_stats, int ln_np, float* stats_out, int* np_out, ec_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * CLIP image preprocessing on raw uint8 frames: Resize(n_px, BICUBIC) + CenterCrop(n_px), bit-exact with Pillow.
  * Replaces the PIL/torchvision half of `clip_preprocess(frame)` (primitive_probing/generate_data/
  * thor_image_features.py:108, :36-44; frames are 300x300: thor_frames.py:33-34).  ToTensor + Normalize are fused into
