@@ -118,6 +118,8 @@ SIGNATURES = {
     # ... its stand-alone selection (any number of actions) and the episode metrics an evaluation run reports (same reference lines)
     "ec_mode_actions": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
     "ec_episode_stats": (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_void_p]),
+    # ... and with the navigation metrics (SPL, SoftSPL, distance to goal, per-category rows)
+    "ec_nav_episode_stats": (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int, c_void_p]),
     "ec_vit_create": (c_int, [C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                               c_size_t]),
     "ec_vit_destroy": (None, [c_void_p]),

@@ -99,3 +99,16 @@ def check_job_seed(seed: int, world: int, group=None, device=None) -> None:
     if float(lo.item()) != float(hi.item()):
         raise ValueError(f"Worker(seed=...) must be the JOB seed, identical on every rank (got {int(lo.item())}..{int(hi.item())}); "
                          "per-rank randomness is derived from it internally (seed + 7919 * rank)")
+
+
+def allreduce_totals(totals: torch.Tensor, group=None, device=None) -> torch.Tensor:
+    """SUM over the ranks of a float64 totals table (``episodes.NavEpisodeTracker.totals``: counts and sums of the completed
+    episodes), so that every rank reports the job's metrics and not its shard's.  Returns a NEW tensor -- the local table keeps
+    accumulating this rank's episodes -- on the table's device; the collective itself runs where ``_coll_device`` says (this
+    rank's GPU under RCCL, the host under gloo).  Without a process group: a copy of the table."""
+    assert totals.dtype == torch.float64, totals.dtype
+    if not (dist.is_available() and dist.is_initialized()):
+        return totals.detach().clone()
+    t = totals.detach().to(_coll_device(group, device), copy=True).contiguous()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.to(totals.device)

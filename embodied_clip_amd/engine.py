@@ -34,7 +34,7 @@ from . import _lib
 from . import synthetic as syn
 from .dist import (allreduce_flat, check_job_seed, collective_active, gather_actor_counts, global_minibatch_sizes,
                    minibatch_bounds)
-from .episodes import EpisodeTracker
+from .episodes import EpisodeTracker, NavEpisodeTracker, nav_env_tensors
 from .encoder import AttentionPool, ClipTextEncoder, ImageNetBasicTrunk, ImageNetRN50Trunk, RN50Trunk, ViTEmbedder
 from .policy import PolicyHandle
 from .ppo import FlatAdam, linear_decay_lr, ppo_loss_raw
@@ -90,6 +90,21 @@ class SyntheticEnv:
     def observe_at(self, k: int, actions_host: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The batch ``observe()`` serves as its k-th call (per-slice env stepping: every slice asks for step k itself)."""
         return self.frames[k % self.pool_steps]
+
+
+class NavSyntheticEnv(SyntheticEnv):
+    """``SyntheticEnv`` (the same frames, masks, goals, rewards, success) plus the geometry the navigation metrics read:
+    ``step_dist`` / ``start_dist`` / ``goal_dist`` f32 [T, N] (``synthetic.synthetic_navigation``, hash streams of its own) and
+    ``num_goals``, the number of goal ids (0 with coordinate goals)."""
+
+    def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
+                 frames_u8: bool = False, host: bool = False, goal_in: int = 0):
+        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in)
+        self.num_goals = 0 if goal_in else 12
+        step_dist, start_dist, goal_dist = syn.synthetic_navigation(seed + 4, self.masks[1:], self.success)
+        self.step_dist = step_dist.to(device).contiguous()
+        self.start_dist = start_dist.to(device).contiguous()
+        self.goal_dist = goal_dist.to(device).contiguous()
 
 
 class _Slice:
@@ -320,9 +335,12 @@ class Worker(_SlicedActor):
                  encoder_chunk: int = 0, encoder: str = "rn50", encoder_streams: int = 2, frames_u8: bool = False,
                  frames_host: bool = False, zeroshot: bool = False, text_sd=None, goal_tokens=None,
                  num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
-                 overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False):
+                 overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False,
+                 nav_metrics: bool = False):
         """``track_episodes=True``: ``compute_returns()`` also folds the rollout's completed episodes into an ``EpisodeTracker``
         (one more launch per iteration; ``episode_info()`` reads the means AllenAct logs every rollout).  Default off.
+        ``nav_metrics=True`` (with ``track_episodes``): the tracker is a ``NavEpisodeTracker`` on a ``NavSyntheticEnv`` and
+        ``episode_info()`` also carries ``spl``, ``soft_spl``, ``dist_to_goal``, ``path_length``, ``no_path``.
 
         ``goal_in > 0``: the PointNav agent ([U] ResnetTensorPointNavActorCritic) -- the goal of a frame is ``goal_in``
         floats (GPS + compass: distance, bearing), ``num_actions`` is 4 there; ``goal_in=0`` is the ObjectNav agent.
@@ -335,6 +353,9 @@ class Worker(_SlicedActor):
         assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
         self.goal_in, self._num_actions = goal_in, num_actions
         self.track_episodes = track_episodes
+        if nav_metrics and not track_episodes:
+            raise ValueError("Worker(nav_metrics=True) needs track_episodes=True")
+        self.nav_metrics = nav_metrics
         # sync_actions: the action-synchronous order of a real vectorised env ([U] VectorSampledTasks.step(actions)): every
         # env step the sampled actions of ALL actors are copied to the host and waited for before observe() serves the next
         # frames.  Default off: the synthetic env does not read the actions and the host issues ahead.
@@ -390,8 +411,12 @@ class Worker(_SlicedActor):
         self.hv_act = torch.empty((N, self.A + 1), dtype=torch.float32, device=d)
         self.stats = torch.zeros(2, dtype=torch.float64, device=d)
         self.sums = torch.zeros(4, dtype=torch.float64, device=d)
-        self.env = SyntheticEnv(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in)
-        self.episodes = EpisodeTracker(N, d) if self.track_episodes else None
+        env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
+        self.env = env_cls(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in)
+        if self.nav_metrics:      # per-category rows for goal ids; coordinate goals have no categories
+            self.episodes = NavEpisodeTracker(N, d, num_categories=0 if self.goal_in else self.env.num_goals)
+        else:
+            self.episodes = EpisodeTracker(N, d) if self.track_episodes else None
         self._build_slices(n_actors, encs, pools, T + 1, 1 if (world > 1 or self.force_allreduce) else 0, frames_host)
         if self.comm_stream is None:
             self.comm_stream = torch.cuda.Stream(device=d)
@@ -524,7 +549,10 @@ class Worker(_SlicedActor):
                                    self.returns.data_ptr(), self.adv.data_ptr(), self.nadv.data_ptr(),
                                    self.stats.data_ptr(), self.T, self.N, self.gamma, self.tau, 1e-5,
                                    _lib.stream_ptr()), "ec_gae")
-        if self.episodes is not None:
+        if self.nav_metrics:
+            self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None),
+                                 *nav_env_tensors(self.env, self.episodes.C > 0))
+        elif self.episodes is not None:
             self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None))
 
     # ---- HOT LOOP B ---------------------------------------------------------------------------

@@ -8,20 +8,23 @@ tasks' metrics averaged at the end.
 
 ``Evaluator`` is hot loop A of ``engine.Worker`` alone, built from the same parts (``engine._SlicedActor``): per slice stream
 ``act(t)`` then ``encode(t + 1)``.  It allocates no learn workspace, no ``hv`` / ``dhv``, no gradient buckets and no ``[T+1]``
-feature storage: each slice keeps a two-entry feature ring.  The episode metrics come from ``episodes.EpisodeTracker``.
+feature storage: each slice keeps a two-entry feature ring.  The episode metrics come from ``episodes.EpisodeTracker``, or with
+``nav_metrics=True`` from ``episodes.NavEpisodeTracker``: SPL, SoftSPL, distance to goal, and all of them per goal category --
+the success / SPL per object type that readme_files/zeroshot_objectnav.md:20-48 reads from the metrics file of an ``--eval``
+run (``write_metrics_json`` / ``scores_by_object_type``).
 """
 from __future__ import annotations
 
 import argparse
 import json
 import sys
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
-from .engine import SyntheticEnv, _SlicedActor
-from .episodes import EpisodeTracker
+from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor
+from .episodes import EpisodeTracker, NavEpisodeTracker, category_names, nav_env_tensors
 
 
 class Evaluator(_SlicedActor):
@@ -35,13 +38,19 @@ class Evaluator(_SlicedActor):
     ``record=True`` keeps ``actions``, ``logp``, ``values`` ``[chunks*T, N]`` and ``hv`` ``[chunks*T, N, A+1]`` of the last
     ``run`` (tests).  ``env=``: any object with ``SyntheticEnv``'s attributes (``N``, ``T``, ``frames``, ``masks``, ``goals``,
     ``rewards``, ``success``, ``host``, ``observe``); its ``N`` and ``T`` must be the evaluator's.  ``sync_actions=True``: every step's actions are copied to the host and waited for
-    before the env serves the next frames (one vectorised env for all actors)."""
+    before the env serves the next frames (one vectorised env for all actors).  ``nav_metrics=True``: the tracker is a
+    ``NavEpisodeTracker`` fed the env's ``step_dist`` / ``start_dist`` / ``goal_dist`` (the last is optional) and, for id goals,
+    ``env.goals`` as the categories (``num_categories``, default the env's ``num_goals``; 0 with coordinate goals); the default
+    env is then a ``NavSyntheticEnv`` and ``info()`` carries ``spl``, ``soft_spl``, ``dist_to_goal``, ``path_length``,
+    ``no_path``.  The act loop does not change.  ``env_seed``: the seed of the env the evaluator builds itself (default
+    ``1000 + rank``, the ``Worker``'s)."""
 
     def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, encoder: str = "rn50",
                  encoder_sd=None, policy_sd=None, checkpoint: Optional[str] = None, deterministic: bool = False,
                  encoder_streams: int = 2, frames_u8: bool = False, goal_in: int = 0, num_actions: int = 6,
                  zeroshot: bool = False, sync_actions: bool = False, record: bool = False, env=None, text_sd=None,
-                 goal_tokens=None, encoder_chunk: int = 0, record_capacity: int = 0):
+                 goal_tokens=None, encoder_chunk: int = 0, record_capacity: int = 0, nav_metrics: bool = False,
+                 num_categories: Optional[int] = None, env_seed: Optional[int] = None):
         self.lib = _lib.load()
         self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
         assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
@@ -49,6 +58,9 @@ class Evaluator(_SlicedActor):
         if sync_actions not in (False, True):
             raise ValueError("Evaluator: sync_actions is False or True (one vectorised env for all actors)")
         self.goal_in, self._num_actions = goal_in, num_actions
+        self.nav_metrics, self._num_categories, self._env_seed = nav_metrics, num_categories, env_seed
+        if nav_metrics and env is not None:
+            nav_env_tensors(env, False)     # an env that cannot be scored fails here, before anything is built
         self.deterministic, self.sync_actions, self.record = deterministic, sync_actions, record
         self.dev = self.device = torch.device(device)
         if self.dev.index is None:
@@ -75,9 +87,16 @@ class Evaluator(_SlicedActor):
         self._logp = torch.zeros((1, N), dtype=torch.float32, device=d)
         self._values = torch.zeros((1, N), dtype=torch.float32, device=d)
         self.actions = self.logp = self.values = self.hv = None
-        self.env = env if env is not None else SyntheticEnv(N, T, d, seed=1000 + rank, frames_u8=frames_u8, goal_in=self.goal_in)
+        env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
+        env_seed = self._env_seed if self._env_seed is not None else 1000 + rank
+        self.env = env if env is not None else env_cls(N, T, d, seed=env_seed, frames_u8=frames_u8, goal_in=self.goal_in)
         assert (self.env.N, self.env.T) == (N, T), "the env's actor count and rollout length are the evaluator's"
-        self.episodes = EpisodeTracker(N, d, capacity=record_capacity)
+        if self.nav_metrics:
+            C = 0 if self.goal_in else (self._num_categories if self._num_categories is not None
+                                        else getattr(self.env, "num_goals", 12))
+            self.episodes = NavEpisodeTracker(N, d, num_categories=C, capacity=record_capacity)
+        else:
+            self.episodes = EpisodeTracker(N, d, capacity=record_capacity)
         self._build_slices(n_actors, encs, pools, 2, 0, bool(self.env.host))
         self.seed = seed + 7919 * rank
         self.chunk = 0                  # chunks played so far (the sampling key's iteration; carries across run() calls)
@@ -145,13 +164,72 @@ class Evaluator(_SlicedActor):
                             self._encode_slice(sl, rgb, (self.k + 1) & 1)
                 self.k += 1
             self._join()
-            self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None))
+            if self.nav_metrics:
+                self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None),
+                                     *nav_env_tensors(self.env, self.episodes.C > 0))
+            else:
+                self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None))
             self.chunk += 1
         return self.info()
 
     def info(self) -> Dict[str, float]:
-        """``{"episodes", "reward", "reward_std", "ep_length", "success"}`` over the episodes completed so far."""
+        """``{"episodes", "reward", "reward_std", "ep_length", "success"}`` over the episodes completed so far (with
+        ``nav_metrics`` also ``spl``, ``soft_spl``, ``dist_to_goal``, ``path_length``, ``no_path``)."""
         return self.episodes.info()
+
+
+# ---- the metrics file of an evaluation run ------------------------------------------------------------------------------------
+# One entry per recorded episode.  readme_files/zeroshot_objectnav.md:29-48 reads three things from the file [U] AllenAct's
+# ``--eval`` writes -- ``[0]["tasks"][i]["task_info"]["object_type"]``, ``["success"]`` and ``["spl"]`` -- and only those three
+# are promised in AllenAct's shape; the other keys are this project's.
+
+def metrics_from_records(records: Dict, names: Optional[Sequence[str]] = None) -> List[Dict]:
+    """``NavEpisodeTracker.records()`` -> the metrics file's content: a list holding one object whose ``"tasks"`` has one entry
+    per stored episode; ``"dropped": k`` joins it when ``k`` more episodes completed than the record buffers hold.
+    ``names[c]`` names goal id ``c`` (default ``str(c)``); an id without a name is written as ``str(id)``."""
+    cols = {k: (v.tolist() if hasattr(v, "tolist") else list(v)) for k, v in records.items() if k != "dropped"}
+    names = list(names) if names is not None else None
+    tasks = []
+    for i in range(len(cols["actor"])):
+        c = int(cols["category"][i])
+        name = names[c] if names is not None and 0 <= c < len(names) else str(c)
+        tasks.append({"task_info": {"object_type": name, "actor": int(cols["actor"][i])},
+                      "success": float(cols["success"][i]), "spl": float(cols["spl"][i]),
+                      "soft_spl": float(cols["soft_spl"][i]), "ep_length": int(cols["length"][i]),
+                      "reward": float(cols["return"][i]), "dist_to_target": float(cols["goal_dist"][i]),
+                      "path_length": float(cols["path"][i])})
+    top = {"tasks": tasks}
+    dropped = int(records.get("dropped", 0))
+    if dropped > 0:
+        top["dropped"] = dropped
+    return [top]
+
+
+def write_metrics_json(path: str, records: Dict, names: Optional[Sequence[str]] = None) -> List[Dict]:
+    metrics = metrics_from_records(records, names)
+    if "dropped" in metrics[0]:
+        print(f"evaluate: {metrics[0]['dropped']} episodes completed beyond the record capacity and are missing from {path}",
+              file=sys.stderr)
+    with open(path, "w") as f:
+        json.dump(metrics, f)
+    return metrics
+
+
+def scores_by_object_type(metrics, names: Sequence[str]) -> Dict[str, Tuple[float, float]]:
+    """``{name: (success rate, mean SPL)}`` over the episodes of each object type in a metrics file's content (the parsed JSON,
+    or its path); a type without episodes scores ``(nan, nan)``."""
+    if isinstance(metrics, str):
+        with open(metrics) as f:
+            metrics = json.load(f)
+    sums = {name: [0, 0.0, 0.0] for name in names}
+    for task in metrics[0]["tasks"]:
+        s = sums.get(task["task_info"]["object_type"])
+        if s is not None:
+            s[0] += 1
+            s[1] += task["success"]
+            s[2] += task["spl"]
+    nan = float("nan")
+    return {name: (s[1] / s[0], s[2] / s[0]) if s[0] else (nan, nan) for name, s in sums.items()}
 
 
 def main(argv=None) -> int:
@@ -170,15 +248,46 @@ def main(argv=None) -> int:
     ap.add_argument("--frames-u8", action="store_true")
     ap.add_argument("--sync-actions", action="store_true")
     ap.add_argument("--json", default=None, metavar="OUT", help="also write the info dict to this file")
+    ap.add_argument("--env-seed", type=int, default=None, help="seed of the synthetic env (default 1000, what Evaluator builds itself)")
+    ap.add_argument("--nav-metrics", action="store_true", help="also SPL, SoftSPL, distance to goal, and the scores per object type")
+    ap.add_argument("--object-types", default=None, metavar="FILE", help="a JSON list of names, one per goal id (default \"0\", \"1\", ...)")
+    ap.add_argument("--groups", default=None, metavar="FILE", help="a JSON object {group: [names]}: the scores over each group's episodes")
+    ap.add_argument("--metrics-json", default=None, metavar="OUT", help="one entry per episode, in the shape the per-object-type readers expect")
     a = ap.parse_args(argv)
+    if (a.object_types or a.groups or a.metrics_json) and not a.nav_metrics:
+        ap.error("--object-types, --groups and --metrics-json go with --nav-metrics")
+    if (a.object_types or a.groups) and a.goal_in:
+        ap.error("--object-types and --groups name goal ids; --goal-in > 0 gives coordinate goals, which have no categories")
+    names = groups = None
+    if a.object_types:
+        with open(a.object_types) as f:
+            names = json.load(f)
+        if isinstance(names, dict):         # (the fixture's shape: {"object_types": [...], ...})
+            names = names["object_types"]
+    if a.groups:
+        with open(a.groups) as f:
+            groups = json.load(f)
+        groups = {k: v for k, v in groups.items() if k != "object_types"}
     print("evaluate: the frozen encoder holds the seeded stand-in weights (a checkpoint carries the policy only)", file=sys.stderr)
     if a.checkpoint is None:
         print("evaluate: no --checkpoint given: using the seeded stand-in weights (an untrained agent)", file=sys.stderr)
-    ev = Evaluator(a.actors, T=a.steps, seed=a.seed, encoder=a.encoder, checkpoint=a.checkpoint, deterministic=a.deterministic,
+    ev = Evaluator(a.actors, T=a.steps, seed=a.seed, env_seed=a.env_seed, encoder=a.encoder, checkpoint=a.checkpoint, deterministic=a.deterministic,
                    goal_in=a.goal_in, num_actions=a.num_actions, zeroshot=a.zeroshot, frames_u8=a.frames_u8,
-                   sync_actions=a.sync_actions)
+                   sync_actions=a.sync_actions, nav_metrics=a.nav_metrics,
+                   num_categories=len(names) if (names is not None and not a.goal_in) else None,
+                   # every actor can end an episode at every step: the metrics file then misses none
+                   record_capacity=a.chunks * a.steps * a.actors if a.metrics_json else 0)
     info = ev.run(a.chunks)
     torch.cuda.synchronize()
+    if a.nav_metrics:
+        tr = ev.episodes
+        names = category_names(tr.C, names) if tr.C else []
+        info = dict(info, by_object_type=tr.info_by_category(names) if tr.C else {},
+                    groups=tr.info_groups(groups, names) if (groups and tr.C) else {})
+        if a.metrics_json:
+            if not tr.C:
+                print("evaluate: coordinate goals have no object types: every task's object_type is written as \"-1\"", file=sys.stderr)
+            write_metrics_json(a.metrics_json, tr.records(), names)
     info = dict(info, env_steps=a.chunks * a.steps * a.actors, deterministic=bool(a.deterministic),
                 policy_weights=a.checkpoint or "seeded stand-in", encoder_weights="seeded stand-in", checkpoint_steps=ev.checkpoint_steps)
     print(json.dumps(info))

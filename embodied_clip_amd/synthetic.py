@@ -480,3 +480,27 @@ def synthetic_rewards(seed: int, masks_next: torch.Tensor) -> torch.Tensor:
     r = torch.full((T, N, 1), -0.01, dtype=torch.float32)
     r = r + 10.0 * ((masks_next == 0) & (u < 0.3)).to(torch.float32)
     return r
+
+
+def synthetic_navigation(seed: int, masks_next, success=None, step: float = 0.25, p_move: float = 0.6, d_max: float = 8.0,
+                         p_zero: float = 0.02, p_unreach: float = 0.02):
+    """Geometry of a synthetic rollout for the navigation metrics: ``(step_dist, start_dist, goal_dist)``, fp32 [T, N] each.
+    ``masks_next`` ([T, N] or [T, N, 1], tensor or array) gives the shape; ``success`` ([T, N], optional) pulls the final
+    distance of a successful step under 1 m.  Hash streams 21-24, which no other generator of this module draws from.
+      step_dist  = ``step`` w.p. ``p_move``, else 0 (a move, or a turn in place);
+      start_dist = the shortest-path length, a multiple of ``step`` in (0, d_max]; 0 w.p. ``p_zero`` (the agent starts on its
+                   goal), -1 w.p. ``p_unreach`` (no path);
+      goal_dist  ~ U[0, 10), U[0, 1) where ``success > 0``."""
+    shape = tuple(masks_next.shape)
+    T, N = shape[0], shape[1]
+    assert shape in ((T, N), (T, N, 1)), shape
+    u_move, u_len, u_kind, u_goal = (hash_uniform(seed, T * N, stream=k).reshape(T, N) for k in (21, 22, 23, 24))
+    step_dist = np.where(u_move < p_move, step, 0.0).astype(np.float32)
+    start = step * np.ceil(u_len * d_max / step)
+    start = np.where(u_kind < p_zero, 0.0, start)
+    start = np.where((u_kind >= p_zero) & (u_kind < p_zero + p_unreach), -1.0, start)
+    goal = (u_goal * 10.0).astype(np.float32)
+    if success is not None:
+        won = np.asarray(success.cpu() if isinstance(success, torch.Tensor) else success).reshape(T, N) > 0
+        goal = np.where(won, u_goal.astype(np.float32), goal)
+    return torch.from_numpy(step_dist), torch.from_numpy(start.astype(np.float32)), torch.from_numpy(goal)

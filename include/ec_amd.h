@@ -529,6 +529,29 @@ int ec_mode_actions(const float* hv, int64_t* actions, float* logp, float* value
 int ec_episode_stats(const float* rewards, const float* masks, const float* success, float* carry_ret, int32_t* carry_len,
                      double* totals5, float* rec_f, int32_t* rec_i, int cap, int32_t* n_records, int T, int N,
                      ec_stream_t stream);
+/* Navigation metrics of a rollout on the device: ec_episode_stats plus the path-efficiency scores the reference's result
+ * tables give beside the success rate (SPL on RoboTHOR ObjectNav; SPL, SoftSPL and the distance to the goal on Habitat;
+ * success and SPL per object type on readme_files/zeroshot_objectnav.md:20-48).  Restates [U] allenact's `spl_metric`
+ * (RoboTHOR ObjectNav task) and [U] habitat-lab's `SPL` / `SoftSPL` measures from their published descriptions; neither
+ * source is pinned.  Conventions of ec_episode_stats (masks [T+1,N], carries in/out, record order, records past cap).
+ * step_dist f32 [T,N]: metres moved by step t, summed per episode in fp32, step order, in carry_path f32 [N] (in/out).
+ * Read at the step that ends an episode only: start_dist f32 [T,N] (shortest-path length d0; < 0: no path), goal_dist f32
+ * [T,N] or NULL (distance to the goal d1), category int64 with row stride N, rows 0..T-1 (or NULL; then C must be 0).
+ * With p the path sum including step t and s the success flag, all in fp32:
+ *   d0 <  0: spl = soft_spl = 0, the episode counts in no_path;
+ *   d0 == 0: spl = soft_spl = (s > 0 && p == 0) ? 1 : 0;
+ *   d0 >  0: ratio = d0 / max(d0, p); spl = s > 0 ? ratio : 0; soft_spl = max(0, 1 - d1 / d0) * ratio.
+ * goal_dist NULL: soft_spl and the goal distance are not accumulated; their record fields are 0.
+ * totals: double [(1 + C), 10], in/out -- row 0 all episodes, row 1 + c those of category c (an id outside [0, C) counts in
+ * row 0 only); columns episodes, sum return, sum return^2, sum length, sum success, sum spl, sum soft_spl, sum goal_dist,
+ * sum path, no_path.  0 <= C <= 64.
+ * rec_f f32 [cap,7] = return, success, spl, soft_spl, path, goal_dist, start_dist; rec_i int32 [cap,4] = actor, t, length,
+ * category (-1 without categories; an id outside [0, C) as given).  One workgroup, one launch, no floating-point atomics:
+ * two runs give the same bits. */
+int ec_nav_episode_stats(const float* rewards, const float* masks, const float* success, const float* step_dist,
+                         const float* start_dist, const float* goal_dist, const int64_t* category, int C, float* carry_ret,
+                         int32_t* carry_len, float* carry_path, double* totals, float* rec_f, int32_t* rec_i, int cap,
+                         int32_t* n_records, int T, int N, ec_stream_t stream);
 /* clip_grad_norm_(max_grad_norm) (<=0 disables) then Adam (1-based `step`) over n floats;
  * sumsq1: device scratch of ec_clip_adam_scratch_doubles() doubles; sumsq1[0] receives ||grads||^2 (the blocks' partial sums
  * and a ticket counter live behind it: the norm is folded in a fixed order, bit-identical run to run). */

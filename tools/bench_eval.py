@@ -3,7 +3,9 @@
 Prints env-frames/s of ``Evaluator.run`` (sampled and greedy actions) and of ``Worker.collect_rollout`` -- the same launches per
 env step -- at 256 actors, ``--repeats`` timings each (their spread is the run-to-run noise the comparison has to clear), and
 the time of ``ec_episode_stats`` beside ``ec_gae`` at T = 128, N = 256.  On a checkout without ``embodied_clip_amd.evaluate``
-(the parent commit) it prints the rollout rate and the ``ec_gae`` time only."""
+(the parent commit) it prints the rollout rate and the ``ec_gae`` time only.  Where the tree has the navigation metrics it also
+times ``ec_nav_episode_stats`` (12 categories) at the same shape, with and without records, and ``Evaluator.run`` with
+``nav_metrics`` on beside the runs with it off."""
 import argparse
 import os
 import sys
@@ -73,10 +75,32 @@ tr = EpisodeTracker(N, "cuda:0")
 print(f"ec_episode_stats                     T={T} N={N}: {kernel_us(lambda: tr.update(env.rewards, env.masks, env.success)):6.1f} us per call")
 tr = EpisodeTracker(N, "cuda:0", capacity=4096)
 print(f"ec_episode_stats, records kept       T={T} N={N}: {kernel_us(lambda: (tr.reset(), tr.update(env.rewards, env.masks, env.success))):6.1f} us per call (with the reset)")
+try:
+    from embodied_clip_amd.engine import NavSyntheticEnv
+    from embodied_clip_amd.episodes import NavEpisodeTracker
+except ImportError:
+    NavSyntheticEnv = None
+if NavSyntheticEnv is not None:
+    nav = NavSyntheticEnv(N, T, "cuda:0", seed=1000)
+    nav_args = (nav.rewards, nav.masks, nav.success, nav.step_dist, nav.start_dist, nav.goal_dist, nav.goals)
+    assert torch.equal(nav.rewards, env.rewards) and torch.equal(nav.masks, env.masks)      # the same episodes as the legs above
+    ntr = NavEpisodeTracker(N, "cuda:0", num_categories=12)
+    print(f"ec_nav_episode_stats, C=12           T={T} N={N}: {kernel_us(lambda: ntr.update(*nav_args)):6.1f} us per call")
+    ntr = NavEpisodeTracker(N, "cuda:0", num_categories=12, capacity=4096)
+    print(f"ec_nav_episode_stats, records kept   T={T} N={N}: {kernel_us(lambda: (ntr.reset(), ntr.update(*nav_args))):6.1f} us per call (with the reset)")
+    ntr = NavEpisodeTracker(N, "cuda:0", num_categories=0)
+    print(f"ec_nav_episode_stats, C=0            T={T} N={N}: {kernel_us(lambda: ntr.update(*nav_args[:6])):6.1f} us per call")
+    del nav, nav_args, ntr
 del env
 for det in (False, True):
     ev = Evaluator(N, T=T, device="cuda:0", deterministic=det)
     show(f"Evaluator.run, {'greedy' if det else 'sampled'} actions", rates(lambda: ev.run(1)))
+    print("    ", ev.info())
+    del ev
+    torch.cuda.empty_cache()
+if NavSyntheticEnv is not None:
+    ev = Evaluator(N, T=T, device="cuda:0", nav_metrics=True)
+    show("Evaluator.run, sampled, nav_metrics", rates(lambda: ev.run(1)))
     print("    ", ev.info())
     del ev
     torch.cuda.empty_cache()
