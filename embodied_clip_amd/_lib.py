@@ -63,6 +63,10 @@ SIGNATURES = {
     "ec_rn50_out_channels": (c_int, [c_void_p]),
     "ec_rn50_out_spatial": (c_int, [c_void_p]),
     "ec_rn50_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    # the depth tower of the RGB-D agent: one-channel stem kernel and the trunk entry point that uses it
+    "ec_stem_conv1_depth": (c_int, [c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "ec_rn50_forward_depth": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int,
+                                      c_void_p]),
     "ec_rn50_num_ops": (c_int, [c_void_p]),
     "ec_rn50_plan_hash": (C.c_uint64, [c_void_p]),
     "ec_rn50_set_conv8_min_tiles": (c_int, [c_void_p, c_int]),

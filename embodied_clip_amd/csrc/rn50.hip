@@ -469,27 +469,47 @@ extern "C" size_t ec_rn50_workspace_bytes(const ec_rn50_t* h, int batch) {
 }
 
 namespace {
-int rn50_run(const ec_rn50_t* h, const void* rgb, bool u8, const float* mean3, const float* std3, int batch,
-             void* workspace, size_t ws_bytes, void* feat, int chunk, ec_stream_t stream);
+// What the frames are: the stem op is the only one that looks at them.
+struct FrameIn {
+    enum Kind { F32, U8, DEPTH } kind;
+    const void* p;                 // F32: fp32 [B,R,R,3]; U8: uint8 [B,R,R,3]; DEPTH: fp32 [B,R,R] (one channel)
+    const float *mean3, *std3;     // U8: host pointers
+    float scale, shift;            // DEPTH: value = depth * scale + shift
+    const float* stem_w9;          // DEPTH: the stem weights summed over the input channels, f32 [9][stem channels]
+};
+int rn50_run(const ec_rn50_t* h, const FrameIn& in, int batch, void* workspace, size_t ws_bytes, void* feat, int chunk,
+             ec_stream_t stream);
 }
 
 extern "C" int ec_rn50_forward(const ec_rn50_t* h, const float* rgb, int batch, void* workspace, size_t ws_bytes,
                                void* feat, int chunk, ec_stream_t stream) {
-    return rn50_run(h, rgb, false, nullptr, nullptr, batch, workspace, ws_bytes, feat, chunk, stream);
+    return rn50_run(h, FrameIn{FrameIn::F32, rgb, nullptr, nullptr, 1.f, 0.f, nullptr}, batch, workspace, ws_bytes, feat, chunk, stream);
 }
 
 extern "C" int ec_rn50_forward_u8(const ec_rn50_t* h, const uint8_t* rgb_u8, const float* h_mean3, const float* h_std3,
                                   int batch, void* workspace, size_t ws_bytes, void* feat, int chunk,
                                   ec_stream_t stream) {
     if (!h_mean3 || !h_std3) return EC_ERR_ARG;
-    return rn50_run(h, rgb_u8, true, h_mean3, h_std3, batch, workspace, ws_bytes, feat, chunk, stream);
+    return rn50_run(h, FrameIn{FrameIn::U8, rgb_u8, h_mean3, h_std3, 1.f, 0.f, nullptr}, batch, workspace, ws_bytes, feat, chunk, stream);
+}
+
+// The depth tower of the RGB-D agent: the same plan, OP_STEM1 on the one-channel kernel (stem_depth.hip).  The handle stays
+// pointer-only: the folded stem weights come with the call.
+extern "C" int ec_rn50_forward_depth(const ec_rn50_t* h, const float* depth, float scale, float shift, const float* stem_w9,
+                                     int batch, void* workspace, size_t ws_bytes, void* feat, int chunk, ec_stream_t stream) {
+    if (!stem_w9) return EC_ERR_ARG;
+    return rn50_run(h, FrameIn{FrameIn::DEPTH, depth, nullptr, nullptr, scale, shift, stem_w9}, batch, workspace, ws_bytes, feat,
+                    chunk, stream);
 }
 
 namespace {
-int rn50_run(const ec_rn50_t* h, const void* rgb, bool u8, const float* mean3, const float* std3, int batch,
-             void* workspace, size_t ws_bytes, void* feat, int chunk, ec_stream_t stream_main) {
-    if (!h || !rgb || !workspace || !feat) return EC_ERR_ARG;
+int rn50_run(const ec_rn50_t* h, const FrameIn& in, int batch, void* workspace, size_t ws_bytes, void* feat, int chunk,
+             ec_stream_t stream_main) {
+    if (!h || !in.p || !workspace || !feat) return EC_ERR_ARG;
     if (batch <= 0) return EC_ERR_SHAPE;
+    const bool u8 = in.kind == FrameIn::U8;
+    if (in.kind == FrameIn::DEPTH && (h->ops.empty() || h->ops.front().kind != OP_STEM1))
+        return EC_ERR_UNSUPPORTED;   // the 7x7 stem of the torchvision towers has no one-channel kernel
     if (chunk <= 0 || chunk > batch) chunk = batch;
     {   // the conv kernels address activations through 32-bit buffer descriptors (< 2 GiB per tensor)
         const long maxc = ((1L << 31) - 1) / (long)(h->max_elems_per_frame * 2);
@@ -499,7 +519,10 @@ int rn50_run(const ec_rn50_t* h, const void* rgb, bool u8, const float* mean3, c
     const ec_min_tiles_scope mint_scope(h->conv8_min_tiles);   // this handle's dispatch threshold, for this call only
     const size_t bufsz = align_up(h->max_elems_per_frame * 2 * (size_t)chunk, 256);
     unsigned char* base = (unsigned char*)workspace;
-    const size_t rgb_stride = (size_t)h->res * h->res * 3;
+    // elements per frame: a depth frame has ONE channel
+    const size_t rgb_stride = (size_t)h->res * h->res * (in.kind == FrameIn::DEPTH ? 1 : 3);
+    const void* rgb = in.p;
+    const float *mean3 = in.mean3, *std3 = in.std3;
     const size_t out_stride = (size_t)h->out_sp * h->out_sp * h->out_c;
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
@@ -513,7 +536,10 @@ int rn50_run(const ec_rn50_t* h, const void* rgb, bool u8, const float* mean3, c
             const hipStream_t stream = (hipStream_t)stream_main;
             switch (o.kind) {
                 case OP_STEM1:
-                    if (u8)
+                    if (in.kind == FrameIn::DEPTH)
+                        rc = ec_stem_conv1_depth((const float*)rgb + (size_t)b0 * rgb_stride, in.scale, in.shift, in.stem_w9,
+                                                 h->bias + o.b_off, buf(o.dst), nb, o.H, o.W, o.Cout, stream);
+                    else if (u8)
                         rc = ec_stem_conv1_u8((const uint8_t*)rgb + (size_t)b0 * rgb_stride, mean3, std3, h->stem_w,
                                               h->bias + o.b_off, buf(o.dst), nb, o.H, o.W, o.Cout, stream);
                     else

@@ -90,6 +90,16 @@ def pack_rn50(sd: Dict[str, torch.Tensor]):
     return (width, layers), stem_w, torch.cat(ws), torch.cat(bs)
 
 
+def fold_stem_depth(stem_w: torch.Tensor) -> torch.Tensor:
+    """``stem_w`` f32 [27, sc] ((ky, kx, ci)-major, ``pack_rn50``) -> f32 [9, sc]: the stem's first conv summed over its three
+    input channels.  [U] ``ClipResNetPreprocessor.process`` repeats a one-channel frame three times; a conv over three equal
+    channels is the conv of the one channel with the summed weights, so the depth stem (``ec_stem_conv1_depth``) reads the
+    one-channel frame itself.  fp32 on the host."""
+    w = stem_w.detach().to("cpu", torch.float32)
+    assert w.dim() == 2 and w.shape[0] == 27, tuple(w.shape)
+    return w.view(9, 3, w.shape[1]).sum(dim=1).contiguous()
+
+
 class ClipResizeCrop:
     """``Resize(n_px, BICUBIC)`` + ``CenterCrop(n_px)`` of CLIP's ``_transform`` on raw uint8 frames, bit-exact with
     Pillow (``clip_preprocess``: primitive_probing/generate_data/thor_image_features.py:108).  The coefficient tables
@@ -144,9 +154,12 @@ class RN50Trunk:
             assert weights_from.device == self.device and weights_from.input_resolution == input_resolution
             width, layers = weights_from._arch
             self.stem_w, self.w, self.bias = weights_from.stem_w, weights_from.w, weights_from.bias
+            self.stem_w9 = weights_from.stem_w9
         else:
             (width, layers), stem_w, w, bias = self._pack(state_dict)
             self.stem_w = stem_w.to(self.device)
+            # the depth tower's first conv (forward_depth); the torchvision towers' 7x7 stem has no one-channel form
+            self.stem_w9 = fold_stem_depth(stem_w).to(self.device) if stem_w.dtype == torch.float32 and stem_w.shape[0] == 27 else None
             self.w = w.to(self.device)
             self.bias = bias.to(self.device)
         self._arch = (width, layers)
@@ -226,6 +239,29 @@ class RN50Trunk:
         m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
         _lib.check(self.lib.ec_rn50_forward_u8(self.h, rgb_u8.data_ptr(), m3, s3, B, ws.data_ptr(), ws.numel(),
                                                out.data_ptr(), chunk, _lib.stream_ptr()), "ec_rn50_forward_u8")
+        return out
+
+    @_lib.on_device
+    def forward_depth(self, depth: torch.Tensor, out: Optional[torch.Tensor] = None, scale: float = 1.0,
+                      shift: float = 0.0) -> torch.Tensor:
+        """depth: device fp32 [B, R, R, 1] or [B, R, R] contiguous (the depth sensor's frame); the stem reads
+        ``depth * scale + shift`` (padding zero after the affine).  Same frozen weights as ``forward`` -- the depth tower of
+        the RGB-D agent ([U] a second ClipResNetPreprocessor on the depth sensor) without the three-channel copy."""
+        assert depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
+        assert depth.dim() in (3, 4) and (depth.dim() == 3 or depth.shape[3] == 1), depth.shape
+        B, R, R2 = depth.shape[:3]
+        assert R == self.input_resolution and R2 == R, depth.shape
+        if self.stem_w9 is None:
+            raise _lib.EcError("forward_depth: this tower has no one-channel stem (CLIP ModifiedResNet towers only)")
+        S, Cc = self.out_spatial, self.out_channels
+        if out is None:
+            out = torch.empty((B, S, S, Cc), dtype=torch.bfloat16, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.numel() == B * S * S * Cc
+        chunk = self.chunk if self.chunk > 0 else B
+        ws = self._workspace(min(chunk, B))
+        _lib.check(self.lib.ec_rn50_forward_depth(self.h, depth.data_ptr(), float(scale), float(shift), self.stem_w9.data_ptr(),
+                                                  B, ws.data_ptr(), ws.numel(), out.data_ptr(), chunk, _lib.stream_ptr()),
+                   "ec_rn50_forward_depth")
         return out
 
     @_lib.on_device

@@ -52,7 +52,7 @@ class SyntheticEnv:
     random goal ids, episode resets w.p. 1/100, RoboTHOR-style rewards."""
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
-                 frames_u8: bool = False, host: bool = False, goal_in: int = 0):
+                 frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False):
         self.N, self.T = n_actors, T
         self.host = host
         # frames_u8: raw uint8 frames (what the simulator renders); normalisation is then fused into the stem kernel.
@@ -78,6 +78,12 @@ class SyntheticEnv:
         self.rewards = syn.synthetic_rewards(seed + 3, masks[1:]).reshape(T, n_actors).to(device).contiguous()
         # success flag of the step that ends an episode: the +10 reward of synthetic_rewards (episode metrics / evaluation)
         self.success = ((self.rewards > 1) & (self.masks[1:] == 0)).to(torch.float32).contiguous()
+        if depth:
+            # RGB-D: one-channel depth frames from a hash stream of their own, normalised (synthetic.normalize_depth), with
+            # the frames' construction: pool entry s is the base batch shifted by s + 1 actors and 7 (s + 1) columns
+            dbase = syn.normalize_depth(syn.synthetic_depth(seed + 5, n_actors, res).to(device))
+            self.depth = torch.stack([dbase.roll(shifts=s + 1, dims=0).roll(shifts=7 * (s + 1), dims=2)
+                                      for s in range(pool_steps)]).contiguous()   # [P, N, R, R, 1] fp32
         self._k = 0
 
     def observe(self, actions_host: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -91,6 +97,14 @@ class SyntheticEnv:
         """The batch ``observe()`` serves as its k-th call (per-slice env stepping: every slice asks for step k itself)."""
         return self.frames[k % self.pool_steps]
 
+    def observe_depth(self) -> torch.Tensor:
+        """The depth batch that goes with the frames ``observe()`` served last (``depth=True`` envs)."""
+        return self.depth[(self._k - 1) % self.pool_steps]
+
+    def observe_depth_at(self, k: int) -> torch.Tensor:
+        """The depth batch that goes with ``observe_at(k)``."""
+        return self.depth[k % self.pool_steps]
+
 
 class NavSyntheticEnv(SyntheticEnv):
     """``SyntheticEnv`` (the same frames, masks, goals, rewards, success) plus the geometry the navigation metrics read:
@@ -98,8 +112,8 @@ class NavSyntheticEnv(SyntheticEnv):
     ``num_goals``, the number of goal ids (0 with coordinate goals)."""
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
-                 frames_u8: bool = False, host: bool = False, goal_in: int = 0):
-        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in)
+                 frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False):
+        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in, depth)
         self.num_goals = 0 if goal_in else 12
         step_dist, start_dist, goal_dist = syn.synthetic_navigation(seed + 4, self.masks[1:], self.success)
         self.step_dist = step_dist.to(device).contiguous()
@@ -112,11 +126,28 @@ class _Slice:
     pass
 
 
+def check_rgbd(encoder: str, zeroshot: bool, goal_in: int, frames_host: bool) -> None:
+    """What ``depth=True`` (the RGB-D agent) cannot be combined with; raised before anything is allocated."""
+    if encoder not in ("rn50", "rn50x16"):
+        raise ValueError(f"depth=True: the one-channel depth stem exists for the CLIP ResNet towers (encoder 'rn50' / 'rn50x16'), not {encoder!r}")
+    if zeroshot:
+        raise ValueError("depth=True: the zero-shot agent fuses ONE image embedding with the text embedding; it has no depth stream")
+    if goal_in:
+        raise ValueError("depth=True: the dual (RGB + depth) goal encoder takes goal ids; coordinate goals (goal_in > 0) are unsupported by the policy library")
+    if frames_host:
+        raise ValueError("depth=True: host-resident frames (frames_host=True) have no depth staging path")
+
+
 class _SlicedActor:
     """What a training ``Worker`` and an ``evaluate.Evaluator`` share: the frozen encoder handles and the policy handle, the
     actor slices with their streams, act workspaces and feature buffers, and hot loop A's encode step.  The users set
-    ``self.lib``, ``self.dev`` / ``self.device``, ``self.zeroshot``, ``self._text_sd``, ``self._goal_tokens``, ``self.goal_in``
-    and ``self._num_actions`` first, and ``self.env`` between ``_build_model`` and ``_build_slices``."""
+    ``self.lib``, ``self.dev`` / ``self.device``, ``self.zeroshot``, ``self._text_sd``, ``self._goal_tokens``, ``self.goal_in``,
+    ``self._num_actions`` and ``self.depth`` first, and ``self.env`` between ``_build_model`` and ``_build_slices``.
+
+    ``self.depth`` (the RGB-D agent, readme_files/baselines_habitat.md:75): every slice's trunk handle also encodes the
+    env's depth batch (``RN50Trunk.forward_depth``: same frozen weights, one-channel stem) into a second feature buffer
+    ``sl.feat2``, and the policy is the dual-encoder variant."""
+    depth = False
 
     def _build_model(self, n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams):
         """Encoder handles (one per slice, weights shared), the policy handle and its flat parameters.  -> (encs, pools)"""
@@ -165,6 +196,8 @@ class _SlicedActor:
         pkw = dict(in_channels=self.C, spatial=self.S, num_actions=self._num_actions)
         if self.goal_in:
             pkw["goal_in"] = self.goal_in
+        if self.depth:      # [U] ResnetDualTensorGoalEncoder: 25 tensors, rgb_* / depth_* compressors and combiners
+            pkw["dual"] = 1
         if self.zeroshot:
             assert encoder == "rn50", "the zero-shot variant uses the CLIP-RN50 image embedding"
             pkw["fusion"] = 1
@@ -221,6 +254,7 @@ class _SlicedActor:
             sl.stream = slice_streams[i]
             # zero-shot: the rollout buffer holds fp32 image embeddings [T+1, n, 1, 1024]; else bf16 feature maps
             sl.feat = torch.empty((feat_steps, n, S2, self.C), dtype=torch.float32 if self.zeroshot else torch.bfloat16, device=d)
+            sl.feat2 = torch.empty_like(sl.feat) if self.depth else None      # the depth tower's features
             sl.trunk_out = (torch.empty((n, self.trunk_S, self.trunk_S, self.trunk_C), dtype=torch.bfloat16, device=d)
                             if self.zeroshot else None)
             sl.tok = (torch.empty((n, encs[i].L, encs[i].D), dtype=torch.bfloat16, device=d) if encoder == "vit" else None)
@@ -253,6 +287,21 @@ class _SlicedActor:
         return self.slices[0].feat if self.ns == 1 else torch.cat([sl.feat for sl in self.slices], dim=1)
 
     @property
+    def feat2(self) -> Optional[torch.Tensor]:
+        """The depth tower's features, laid out as ``feat`` (``depth=True``; else None)."""
+        if not self.depth:
+            return None
+        return self.slices[0].feat2 if self.ns == 1 else torch.cat([sl.feat2 for sl in self.slices], dim=1)
+
+    def _f2(self, sl, t: int):
+        return sl.feat2[t] if self.depth else None
+
+    def _observe(self, actions_host=None):
+        """env.step: the next RGB batch and (``depth=True``) the depth batch that goes with it."""
+        rgb = self.env.observe(actions_host) if actions_host is not None else self.env.observe()
+        return rgb, (self.env.observe_depth() if self.depth else None)
+
+    @property
     def enc_streams(self):
         return [sl.stream for sl in self.slices if sl.stream is not None]
 
@@ -272,7 +321,7 @@ class _SlicedActor:
                 cur.wait_stream(sl.stream)
 
     # ---- HOT LOOP A ---------------------------------------------------------------------------
-    def _encode_slice(self, sl, rgb: torch.Tensor, t: int):
+    def _encode_slice(self, sl, rgb: torch.Tensor, t: int, dep: Optional[torch.Tensor] = None):
         src = rgb[sl.o:sl.o + sl.n]
         if self.env.host:
             # H2D of this slice's frames on its copy stream, overlapping whatever the other slice is computing; the
@@ -297,6 +346,8 @@ class _SlicedActor:
         elif self.encoder in ("rn50", "rn50x16") or self.encoder in IMAGENET_ENCODERS:
             # the last conv writes straight into the rollout slice
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.feat[t])
+            if self.depth:      # the depth tower: the same handle on the one-channel batch, behind the RGB tower on this stream
+                sl.enc.forward_depth(dep[sl.o:sl.o + sl.n], sl.feat2[t])
         else:
             sl.enc.forward(src, sl.tok)
             sl.feat[t].copy_(sl.tok[:, 1:, :])        # drop CLS: [n,49,768] channels-last rows
@@ -336,8 +387,14 @@ class Worker(_SlicedActor):
                  frames_host: bool = False, zeroshot: bool = False, text_sd=None, goal_tokens=None,
                  num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
                  overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False,
-                 nav_metrics: bool = False):
-        """``track_episodes=True``: ``compute_returns()`` also folds the rollout's completed episodes into an ``EpisodeTracker``
+                 nav_metrics: bool = False, depth: bool = False):
+        """``depth=True``: the RGB-D agent (readme_files/baselines_habitat.md:75; [U] a second ClipResNetPreprocessor on the
+        depth sensor feeding ResnetDualTensorGoalEncoder): the env also serves one-channel depth frames, every slice's trunk
+        runs twice per env step (RGB, then depth through the one-channel stem) into ``feat`` / ``feat2``, and the policy is
+        ``PolicyHandle(dual=1)``.  Rollout feature storage doubles.  Only with ``encoder`` "rn50" / "rn50x16", goal ids and
+        device-resident frames.
+
+        ``track_episodes=True``: ``compute_returns()`` also folds the rollout's completed episodes into an ``EpisodeTracker``
         (one more launch per iteration; ``episode_info()`` reads the means AllenAct logs every rollout).  Default off.
         ``nav_metrics=True`` (with ``track_episodes``): the tracker is a ``NavEpisodeTracker`` on a ``NavSyntheticEnv`` and
         ``episode_info()`` also carries ``spl``, ``soft_spl``, ``dist_to_goal``, ``path_length``, ``no_path``.
@@ -348,6 +405,9 @@ class Worker(_SlicedActor):
         ``zeroshot=True`` (BASELINE config 5, readme_files/zeroshot_objectnav.md): the observation is the CLIP image
         EMBEDDING (RN50 trunk + AttentionPool2d, 1024-d), the goal is the frozen CLIP text embedding of its prompt
         (text tower run once -> [12, 1024] table) and the policy is the fusion=1 variant (GRU + heads trainable)."""
+        if depth:
+            check_rgbd(encoder, zeroshot, goal_in, frames_host)
+        self.depth = bool(depth)
         self.lib = _lib.load()
         self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
         assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
@@ -412,7 +472,8 @@ class Worker(_SlicedActor):
         self.stats = torch.zeros(2, dtype=torch.float64, device=d)
         self.sums = torch.zeros(4, dtype=torch.float64, device=d)
         env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
-        self.env = env_cls(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in)
+        dkw = dict(depth=True) if self.depth else {}
+        self.env = env_cls(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in, **dkw)
         if self.nav_metrics:      # per-category rows for goal ids; coordinate goals have no categories
             self.episodes = NavEpisodeTracker(N, d, num_categories=0 if self.goal_in else self.env.num_goals)
         else:
@@ -434,9 +495,9 @@ class Worker(_SlicedActor):
         self.iter = 0
         self.update_events: List = []            # (start, end) HIP event pairs around the update phase (GAE excluded), one pair per timed iteration
         # first observation of the first rollout
-        rgb = self.env.observe()
+        rgb, dep = self._observe()
         for sl in self.slices:
-            self._encode_slice(sl, rgb, 0)
+            self._encode_slice(sl, rgb, 0, dep)
         torch.cuda.synchronize(d)
 
     # ---- HOT LOOP A ---------------------------------------------------------------------------
@@ -449,12 +510,12 @@ class Worker(_SlicedActor):
             # forward + CategoricalDistr.sample / log_prob in one call: the heads launch samples (ec_policy_act, one launch less)
             self.policy.act(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act,
                             self.hv_act[rs], h_out[rs], self.actions[t][rs], self.logp[t][rs], self.values[t][rs], self.seed,
-                            self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid)
+                            self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t))
             sl.act_tables_valid = True
             return
         self.policy.forward(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n,
                             sl.ws_act, hv=self.hv_act[rs], h_final=h_out[rs], for_backward=False,
-                            reuse_tables=sl.act_tables_valid)      # (E1 depends on the parameters only)
+                            reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t))      # (E1 depends on the parameters only)
         sl.act_tables_valid = True
         if sample:
             _lib.check(self.lib.ec_sample_actions(self.hv_act[rs].data_ptr(), self.actions[t][rs].data_ptr(),
@@ -471,11 +532,11 @@ class Worker(_SlicedActor):
         if self.sync_actions:
             return self._collect_rollout_sync()
         for t in range(T):
-            rgb = self.env.observe()      # env.step(actions[t]) happens here in the real system (fp32 NHWC frames)
+            rgb, dep = self._observe()    # env.step(actions[t]) happens here in the real system (fp32 NHWC frames)
             for sl in self.slices:
                 with self._on(sl):
                     self._act_slice(sl, t)
-                    self._encode_slice(sl, rgb, t + 1)
+                    self._encode_slice(sl, rgb, t + 1, dep)
         for sl in self.slices:
             with self._on(sl):
                 self._act_slice(sl, T, sample=False)
@@ -516,8 +577,9 @@ class Worker(_SlicedActor):
                 for sl in self.slices:
                     wait(sl)                                                 # this slice's actions[t] are on the host
                     rgb = self.env.observe_at(k0 + t, self._actions_host)   # env.step of this slice's samplers
+                    dep = self.env.observe_depth_at(k0 + t) if self.depth else None
                     with self._on(sl):
-                        self._encode_slice(sl, rgb, t + 1)
+                        self._encode_slice(sl, rgb, t + 1, dep)
                         if t + 1 < T:
                             self._act_slice(sl, t + 1)
                             d2h(sl, t + 1)
@@ -532,10 +594,10 @@ class Worker(_SlicedActor):
                         d2h(sl, t)
                 for sl in self.slices:
                     wait(sl)
-                rgb = self.env.observe(self._actions_host)          # env.step(actions[t])
+                rgb, dep = self._observe(self._actions_host)        # env.step(actions[t])
                 for sl in self.slices:
                     with self._on(sl):
-                        self._encode_slice(sl, rgb, t + 1)
+                        self._encode_slice(sl, rgb, t + 1, dep)
             for sl in self.slices:
                 with self._on(sl):
                     self._act_slice(sl, T, sample=False)
@@ -605,6 +667,21 @@ class Worker(_SlicedActor):
         return (fm.view(T * m, self.S * self.S, self.C), goal, c(sl.masks), c(sl.actions), c(sl.logp), c(sl.old_v),
                 c(sl.ret), c(sl.nadv))
 
+    def _gather_feat2(self, sl, a: int, b: int):
+        """The depth features of the batch ``_gather_part(sl, a, b)`` returns (``depth=True``; else None): the whole slice in
+        place, a partial range through a staging buffer of its own, sized as ``feat_mb``."""
+        if not self.depth:
+            return None
+        T, S2 = self.T, self.S * self.S
+        if a == 0 and b == sl.n:
+            return sl.feat2[:T].view(T * sl.n, S2, self.C)
+        m = b - a
+        if getattr(sl, "feat2_mb", None) is None:
+            sl.feat2_mb = torch.empty((T, self._max_partial_range(sl), S2, self.C), dtype=sl.feat2.dtype, device=self.dev)
+        fm = sl.feat2_mb.view(-1)[:T * m * S2 * self.C].view(T, m, S2, self.C)
+        fm.copy_(sl.feat2[:T, a:b])
+        return fm.view(T * m, S2, self.C)
+
     def _sum_parts(self, parts, sec: slice):
         """self.grads[sec] = sum of the slices' gradient buckets over ``sec`` (one slice: its bucket IS self.grads)."""
         if self.ns == 1:
@@ -642,6 +719,7 @@ class Worker(_SlicedActor):
                     with self._on(sl):
                         m = b - a
                         feat, goal, masks, actions, logp, old_v, ret, nadv = self._gather_part(sl, a, b)
+                        feat2 = self._gather_feat2(sl, a, b)
                         hv, dhv = sl.hv[:T * m], sl.dhv[:T * m]
                         # d(total)/d(hv) carries 1/B_part inside the loss kernel: rescale to the mean over the WHOLE
                         # local minibatch (m / nmb), then local_bsize / global_bsize (nmb / nmb_global: the sum of the
@@ -651,11 +729,11 @@ class Worker(_SlicedActor):
                         #  run beside the other slice's GRU recurrence -- was measured in round 3: 53 -> 58 ms per update;
                         #  the step kernels wait for CUs the GEMM workgroups hold)
                         self.policy.forward(self.params, feat, goal, self.h_start[sl.o + a:sl.o + b], masks, T, m,
-                                            sl.ws_learn, hv=hv)
+                                            sl.ws_learn, hv=hv, feat2=feat2)
                         ppo_loss_raw(hv, actions, logp, old_v, ret, nadv, self.A, grad_scale=grad_scale, dhv=dhv,
                                      sums=sl.sums)
                         sl.grads.zero_()
-                        self.policy.backward(self.params, feat, masks, T, m, sl.ws_learn, dhv, None, sl.grads,
+                        self.policy.backward(self.params, feat, masks, T, m, sl.ws_learn, dhv, None, sl.grads, feat2=feat2,
                                              recurrent_ready=sl.rec_ready if early else None)
                 if early:
                     # GRU + heads section: summed over the slices and over the ranks on the communication stream, behind the
@@ -684,6 +762,8 @@ class Worker(_SlicedActor):
     def after_update(self):
         for sl in self.slices:
             sl.feat[0].copy_(sl.feat[self.T])
+            if self.depth:
+                sl.feat2[0].copy_(sl.feat2[self.T])
         self.total_steps += self.T * sum(self.shard_counts)
         self.iter += 1
 

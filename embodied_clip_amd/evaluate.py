@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor
+from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_rgbd
 from .episodes import EpisodeTracker, NavEpisodeTracker, category_names, nav_env_tensors
 
 
@@ -43,14 +43,21 @@ class Evaluator(_SlicedActor):
     ``env.goals`` as the categories (``num_categories``, default the env's ``num_goals``; 0 with coordinate goals); the default
     env is then a ``NavSyntheticEnv`` and ``info()`` carries ``spl``, ``soft_spl``, ``dist_to_goal``, ``path_length``,
     ``no_path``.  The act loop does not change.  ``env_seed``: the seed of the env the evaluator builds itself (default
-    ``1000 + rank``, the ``Worker``'s)."""
+    ``1000 + rank``, the ``Worker``'s).  ``depth=True``: the RGB-D agent of ``Worker(depth=True)`` -- a second feature ring per slice
+    for the depth tower, the dual-encoder policy (a checkpoint then carries 25 tensors); an ``env=`` must also have ``depth`` and
+    ``observe_depth()``; refused with the combinations ``engine.check_rgbd`` names."""
 
     def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, encoder: str = "rn50",
                  encoder_sd=None, policy_sd=None, checkpoint: Optional[str] = None, deterministic: bool = False,
                  encoder_streams: int = 2, frames_u8: bool = False, goal_in: int = 0, num_actions: int = 6,
                  zeroshot: bool = False, sync_actions: bool = False, record: bool = False, env=None, text_sd=None,
                  goal_tokens=None, encoder_chunk: int = 0, record_capacity: int = 0, nav_metrics: bool = False,
-                 num_categories: Optional[int] = None, env_seed: Optional[int] = None):
+                 num_categories: Optional[int] = None, env_seed: Optional[int] = None, depth: bool = False):
+        if depth:       # the RGB-D agent (engine.Worker(depth=True)): the same refusals, before anything is built
+            check_rgbd(encoder, zeroshot, goal_in, bool(env is not None and getattr(env, "host", False)))
+            if env is not None and getattr(env, "depth", None) is None:
+                raise ValueError("depth=True: the env serves no depth frames (SyntheticEnv(..., depth=True) holds env.depth)")
+        self.depth = bool(depth)
         self.lib = _lib.load()
         self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
         assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
@@ -89,7 +96,8 @@ class Evaluator(_SlicedActor):
         self.actions = self.logp = self.values = self.hv = None
         env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
         env_seed = self._env_seed if self._env_seed is not None else 1000 + rank
-        self.env = env if env is not None else env_cls(N, T, d, seed=env_seed, frames_u8=frames_u8, goal_in=self.goal_in)
+        dkw = dict(depth=True) if self.depth else {}
+        self.env = env if env is not None else env_cls(N, T, d, seed=env_seed, frames_u8=frames_u8, goal_in=self.goal_in, **dkw)
         assert (self.env.N, self.env.T) == (N, T), "the env's actor count and rollout length are the evaluator's"
         if self.nav_metrics:
             C = 0 if self.goal_in else (self._num_categories if self._num_categories is not None
@@ -101,9 +109,9 @@ class Evaluator(_SlicedActor):
         self.seed = seed + 7919 * rank
         self.chunk = 0                  # chunks played so far (the sampling key's iteration; carries across run() calls)
         self.k = 0                      # env steps played so far: the feature ring's and the memory ping-pong's parity
-        rgb = self.env.observe()        # first observation
+        rgb, dep = self._observe()      # first observation
         for sl in self.slices:
-            self._encode_slice(sl, rgb, 0)
+            self._encode_slice(sl, rgb, 0, dep)
         torch.cuda.synchronize(d)
 
     # ---- one act step of a slice ----------------------------------------------------------------
@@ -112,16 +120,16 @@ class Evaluator(_SlicedActor):
         o, n = sl.o, sl.n
         rs = slice(o, o + n)
         h_in, h_out = (self.h, self.h_next) if (self.k & 1) == 0 else (self.h_next, self.h)
-        feat = sl.feat[self.k & 1]
+        feat, feat2 = sl.feat[self.k & 1], self._f2(sl, self.k & 1)
         hv, actions, logp, values = self._hv[row][rs], self._actions[row][rs], self._logp[row][rs], self._values[row][rs]
         key = self.chunk * (self.T + 1) + t
         if self._act_fused:
             self.policy.act(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
                             actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
-                            deterministic=self.deterministic)
+                            deterministic=self.deterministic, feat2=feat2)
         else:   # more than 7 actions: the forward, then the stand-alone selection kernel
             self.policy.forward(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n, sl.ws_act,
-                                hv=hv, h_final=h_out[rs], for_backward=False, reuse_tables=sl.act_tables_valid)
+                                hv=hv, h_final=h_out[rs], for_backward=False, reuse_tables=sl.act_tables_valid, feat2=feat2)
             if self.deterministic:
                 _lib.check(self.lib.ec_mode_actions(hv.data_ptr(), actions.data_ptr(), logp.data_ptr(), values.data_ptr(), n,
                                                     self.A, _lib.stream_ptr()), "ec_mode_actions")
@@ -152,16 +160,16 @@ class Evaluator(_SlicedActor):
                             self._actions_host[sl.o:sl.o + sl.n].copy_(self._actions[row][sl.o:sl.o + sl.n], non_blocking=True)
                     for sl in self.slices:
                         (sl.stream if sl.stream is not None else torch.cuda.current_stream()).synchronize()
-                    rgb = self.env.observe(self._actions_host)          # env.step(actions[t])
+                    rgb, dep = self._observe(self._actions_host)        # env.step(actions[t])
                     for sl in self.slices:
                         with self._on(sl):
-                            self._encode_slice(sl, rgb, (self.k + 1) & 1)
+                            self._encode_slice(sl, rgb, (self.k + 1) & 1, dep)
                 else:
-                    rgb = self.env.observe()      # env.step(actions[t]) happens here in the real system
+                    rgb, dep = self._observe()    # env.step(actions[t]) happens here in the real system
                     for sl in self.slices:
                         with self._on(sl):
                             self._act_slice(sl, t, row)
-                            self._encode_slice(sl, rgb, (self.k + 1) & 1)
+                            self._encode_slice(sl, rgb, (self.k + 1) & 1, dep)
                 self.k += 1
             self._join()
             if self.nav_metrics:
@@ -246,6 +254,7 @@ def main(argv=None) -> int:
     ap.add_argument("--num-actions", type=int, default=6)
     ap.add_argument("--zeroshot", action="store_true")
     ap.add_argument("--frames-u8", action="store_true")
+    ap.add_argument("--depth", action="store_true", help="the RGB-D agent: a depth tower beside the RGB tower, dual goal encoder (encoder rn50 / rn50x16)")
     ap.add_argument("--sync-actions", action="store_true")
     ap.add_argument("--json", default=None, metavar="OUT", help="also write the info dict to this file")
     ap.add_argument("--env-seed", type=int, default=None, help="seed of the synthetic env (default 1000, what Evaluator builds itself)")
@@ -273,7 +282,7 @@ def main(argv=None) -> int:
         print("evaluate: no --checkpoint given: using the seeded stand-in weights (an untrained agent)", file=sys.stderr)
     ev = Evaluator(a.actors, T=a.steps, seed=a.seed, env_seed=a.env_seed, encoder=a.encoder, checkpoint=a.checkpoint, deterministic=a.deterministic,
                    goal_in=a.goal_in, num_actions=a.num_actions, zeroshot=a.zeroshot, frames_u8=a.frames_u8,
-                   sync_actions=a.sync_actions, nav_metrics=a.nav_metrics,
+                   sync_actions=a.sync_actions, nav_metrics=a.nav_metrics, depth=a.depth,
                    num_categories=len(names) if (names is not None and not a.goal_in) else None,
                    # every actor can end an episode at every step: the metrics file then misses none
                    record_capacity=a.chunks * a.steps * a.actors if a.metrics_json else 0)

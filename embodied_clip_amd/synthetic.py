@@ -452,6 +452,21 @@ def synthetic_rgb(seed: int, n: int, res: int = 224) -> torch.Tensor:
     return normalize_rgb(synthetic_rgb_u8(seed, n, res))
 
 
+def synthetic_depth(seed: int, n: int, res: int = 224) -> torch.Tensor:
+    """Depth frames fp32 ~ U[0, 1), [n, res, res, 1] (what a depth sensor clipped to its range and scaled hands over)."""
+    u = hash_uniform(seed, n * res * res, stream=23)
+    return torch.from_numpy(u.astype(np.float32)).clamp_(0.0, 1.0).reshape(n, res, res, 1)
+
+
+DEPTH_MEAN, DEPTH_STD = 0.5, 0.25
+
+
+def normalize_depth(d: torch.Tensor) -> torch.Tensor:
+    """The depth sensor's wire form: ``(d - 0.5) / 0.25`` ([U] AllenAct ``DepthSensor`` with the Habitat / RoboTHOR
+    configs' mean 0.5, std 0.25; restated, not pinned)."""
+    return (d.to(torch.float32) - DEPTH_MEAN) / DEPTH_STD
+
+
 def synthetic_goals(seed: int, shape, num_goals: int = 12) -> torch.Tensor:
     n = int(np.prod(shape))
     return torch.from_numpy((hash_u64(seed, n, stream=11) % np.uint64(num_goals)).astype(np.int64)).reshape(shape)

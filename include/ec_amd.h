@@ -172,6 +172,18 @@ int ec_dw_tn_x3(const void* dY_planes, const void* X_bf16, float* part, float* d
 int ec_stem_conv1(const float* rgb_nhwc, const float* w, const float* bias, void* out,
                   int B, int H, int W, int Cout, ec_stream_t stream);
 
+/* Stem conv1 on a ONE-channel frame: the depth tower of the RGB-D agent (readme_files/baselines_habitat.md:75 "replace `rgb`
+ * with `rgbd`"; [U] a second ClipResNetPreprocessor on the depth sensor, which repeats the frame to three channels).
+ * depth f32 [B,H,W] (== [B,H,W,1]); the value fed to the conv is depth*scale + shift for pixels inside the frame and exactly 0
+ * in the padding (zero in the NORMALISED domain, as ec_stem_conv1_u8 does); w9 f32 [9][Cout], tap-major (ky*3+kx),
+ * w9[k][co] = sum_ci w[(k*3+ci)][co] of ec_stem_conv1's weights (the channel repeat folded in); bias f32 [Cout];
+ * out bf16 NHWC [B,Ho,Wo,Cout], Ho = (H-1)/2+1.  3x3, stride 2, pad 1, folded BN + ReLU.  Cout in {32, 48, 64}: the two
+ * arithmetic routes of ec_stem_conv1 (bf16 MFMA for 32 / 64 with the window K = 9 padded to 16, packed fp32 FMAs for 48).
+ * Reads 4 B and writes Cout/2 B per input pixel: 200,704 B in, 802,816 B out per 224 x 224 frame at Cout = 64.
+ * Checked before any HIP call: NULL -> EC_ERR_ARG; B <= 0, H < 2, W < 2 or another Cout -> EC_ERR_SHAPE. */
+int ec_stem_conv1_depth(const float* depth, float scale, float shift, const float* w9, const float* bias, void* out,
+                        int B, int H, int W, int Cout, ec_stream_t stream);
+
 /* Fused pair of 1x1 convolutions across a Bottleneck boundary of layer1 (bandwidth-bound at 56x56):
  *   y = relu(a0 . w0^T + b0 [+ a1 . w1^T + b1] [+ res])   [M,256]  == relu(bn3(conv3(out)) + identity), the identity
  *                                                                    being `res` or the fused downsample conv (a1,w1,b1)
@@ -322,6 +334,13 @@ int ec_rn50_forward(const ec_rn50_t* h, const float* rgb_nhwc, int batch, void* 
 int ec_rn50_forward_u8(const ec_rn50_t* h, const uint8_t* rgb_u8_nhwc, const float* h_mean3, const float* h_std3,
                        int batch, void* workspace, size_t ws_bytes, void* feat_bf16_nhwc, int chunk,
                        ec_stream_t stream);
+/* The depth tower of the RGB-D agent: ec_rn50_forward's plan with the stem's first conv served by ec_stem_conv1_depth.
+ * depth f32 [B,R,R] (== [B,R,R,1]), normalised as depth*scale + shift inside the kernel; stem_w9 f32 [9][stem channels]
+ * (device; see ec_stem_conv1_depth) is passed per call -- the handle stays pointer-only and both towers of the agent read
+ * the same frozen weights, as [U] AllenAct's two preprocessors do.  `chunk` as above.  A handle of the torchvision towers
+ * (7x7 stem) returns EC_ERR_UNSUPPORTED; NULL pointers EC_ERR_ARG. */
+int ec_rn50_forward_depth(const ec_rn50_t* h, const float* depth, float scale, float shift, const float* stem_w9, int batch,
+                          void* workspace, size_t ws_bytes, void* feat_bf16_nhwc, int chunk, ec_stream_t stream);
 /* Number of ops in the handle's launch plan (from 128 frames on one kernel launch each: 38 for CLIP RN50 at 224 x 224;
  * smaller launches run the five fused layer-3 blocks as three launches each).  Tests and tools/ key on it. */
 int ec_rn50_num_ops(const ec_rn50_t* h);
