@@ -1,16 +1,19 @@
-// CLIP ModifiedResNet trunk executor (stem + layer1..4, attnpool detached).
+// ResNet trunk executor: CLIP ModifiedResNet (stem + layer1..4, attnpool detached), torchvision ResNet-50, ResNet-18 / 34.
 //
-// Replaces `clip_features = clip_model(clip_input)` with
-// `clip_model.attnpool = nn.Identity()`
-// (primitive_probing/generate_data/thor_image_features.py:59-67,109) ==
-// [U] allenact_plugins/clip_plugin ClipResNetEmbedder.forward.
+// Replaces `clip_features = clip_model(clip_input)` with `clip_model.attnpool = nn.Identity()`
+// (primitive_probing/generate_data/thor_image_features.py:59-67,109) == [U] allenact_plugins/clip_plugin ClipResNetEmbedder.forward.
 //
-// The op list is derived from the architecture ([U] openai/CLIP clip/model.py
-// ModifiedResNet.__init__/_make_layer, Bottleneck): it is a straight line of
-// fused conv launches over five ping-pong NHWC bf16 buffers in the caller's
-// workspace.  CLIP's anti-aliased stride (3x3 conv at full resolution, then
-// AvgPool2d(2)) is fused into the 3x3 conv's epilogue; the residual add + ReLU
-// is fused into conv3's epilogue.
+// The plan is derived from the architecture ([U] openai/CLIP clip/model.py ModifiedResNet.__init__/_make_layer, Bottleneck)
+// before the first launch, in three steps:
+//   slots  walk_arch(): geometry, buffers and the weight / bias offsets of every conv, in the order ec_amd.h documents
+//   forms  block_form(): what a block runs as (plain convs, a boundary pair, a K-concatenated tail, a fused bottleneck, ...): a
+//          function of the architecture, the block's position and ec_config() -- and of the NEXT block's form, equally static
+//   ops    plan_bottleneck() / plan_basic() append the block's ops in that form.  A fused op carries as its PARTS the plain convs
+//          it stands for, made by mk_conv() like every other conv, with their buffers and slots
+// rn50_run() is a straight line of launches over five ping-pong NHWC bf16 buffers in the caller's workspace: one runner per op
+// kind, whose route function picks the launch for this chunk's frame count; every fallback runs the op's parts through run_conv().
+// CLIP's anti-aliased stride (3x3 conv at full resolution, then AvgPool2d(2)) is fused into the 3x3 conv's epilogue; the
+// residual add + ReLU is fused into conv3's epilogue.
 #include <stdlib.h>
 
 #include <new>
@@ -22,28 +25,47 @@
 
 namespace {
 
-enum OpKind { OP_STEM1, OP_CONV, OP_POOL, OP_PAIR, OP_BNECK, OP_STEM7, OP_BTAIL };
+enum OpKind { OP_STEM1, OP_CONV, OP_POOL, OP_PAIR, OP_BNECK, OP_STEM7, OP_BTAIL, OP_CAT, OP_CONV_POOLOUT };   // (values: ec_rn50_plan_hash)
+
+// buffers: 0 = X (block input / output), 1,2 = temporaries, 3 = identity path, 4 = Y; and
+constexpr int BUF_NONE = -1, BUF_IN = -2, BUF_OUT = -3;   // no operand; the caller's frames; the caller's feature tensor
+
+struct Slot { size_t w = 0, b = 0; };   // one conv's element offsets into w_bf16 / bias
+
+// One plain convolution: an op of its own (OP_CONV) or a part of a fused op.  run_conv() is the only code that launches one.
+struct Conv {
+    int src, dst, res;        // buffer ids
+    int H, W, Cin, Cout, ks, pool, act;
+    int stride;               // 2 = torchvision's strided conv (ec_conv_bf16_s2); H, W are the INPUT dims
+    Slot at;
+    int ldo = 0, ocol = 0;    // writing a column block of a wider tensor: row stride (0 = dense) and first column (elements)
+    int img_max = 0;          // > 0: a 3x3 conv that launches of up to this many frames run on the image-resident kernel (img3_max_frames)
+    size_t wimg_off = 0;      // ... from its streaming-order weights at this offset (elements) into wbneck
+};
+
+// [a | b] . [Wa | Wb]^T + (ba + bb): two convs as ONE GEMM over the concatenated K axis, from weights laid side by side in wbneck
+// and the summed bias in bias_cat (pack_plan_weights)
+struct Cat { Slot a, b; int Ka, Kb; size_t w_off = 0, b_off = 0; };   // (offsets: elements into wbneck / bias_cat)
 
 struct Op {
     OpKind kind;
-    int src, dst, res;       // buffer ids; -1 = none; src -2 = rgb input; dst -3 = final output
-    int H, W, Cin, Cout, ks, pool, act;
-    size_t w_off, b_off;     // element offsets into w_bf16 / bias
-    // OP_PAIR (fused layer-1 block boundary, conv_pair.hip): y = relu(src.w + [src1.w1] + [res]) -> dst;
-    // z = relu(y.w2) -> dst2 (the next block's conv1 output, N2 channels)
-    int src1 = -1, dst2 = -1, N2 = 0;
-    int dst3 = -1;           // OP_PAIR at the layer-1 -> layer-2 boundary: AvgPool2d(2)(y) for the downsample path
-    size_t w1_off = 0, b1_off = 0, w2_off = 0, b2_off = 0;
-    long wc1_off = -1, bc1_off = -1;   // OP_BNECK with conv1 folded in (whole block in one launch): conv1's weight / bias offsets; its input is `res`
-    int stride = 1;          // OP_CONV: 2 = torchvision's strided conv (ec_conv_bf16_s2); H, W are the INPUT dims
-    long wimg_off = -1;      // offset (elements, into wbneck) of this 3x3 conv's streaming-order weights for the small-launch kernel
-    int ldo = 0, ocol = 0;   // OP_CONV / OP_POOL writing a column block of a wider tensor: row stride (0 = dense) and first column (elements)
-    long wcat_off = -1;      // OP_CONV over a concatenated K axis (conv3 | downsample conv of a stride-2 block): its [Cout][K1 + K2] weights in wbneck,
-    long bcat_off = -1;      // ... its summed bias in bias_cat; w_off / b_off = conv3's, w1_off / b1_off = the downsample conv's, Cin = K1 + K2, N2 = K1    // OP_CONV (a block's conv3) that may also emit AvgPool2d(2) of its output for the NEXT block's K-concatenated GEMM (buffer pdst, row stride
-    // pld, first column pcol): taken when the launch runs on conv1x1_regw_kernel<.., PL>; the OP_POOL that follows the next block's conv2 carries
-    // pool_of = 1 and is skipped then
-    int pdst = -1, pld = 0, pcol = 0;
-    int pool_of = 0;
+    // OP_STEM1 / OP_STEM7: the stem conv on the caller's frames.  OP_CONV: the conv.  OP_CONV_POOLOUT: a block's conv3.
+    // OP_CAT: the GEMM over the concatenated K axis (geometry and buffers; its weights are `cat`'s)
+    Conv c;
+    // OP_POOL: AvgPool2d(2) of src [H, W, C] into a column block of dst (ldo 0: dense).  pool_of: skipped when the previous
+    // block's OP_CONV_POOLOUT wrote it already.  pd: where that op's pooled copy goes (buffer, row stride, column)
+    struct { int src, dst, H, W, C, ldo, ocol, pool_of; } pl;
+    struct { int dst, ld, col; } pd;
+    // The parts of a fused op --
+    // OP_PAIR (conv_pair.hip): y = relu(c3 [+ ds] [+ c3.res]) -> c3.dst, z = relu(next_c1(y)) -> next_c1.dst, the NEXT block's conv1
+    // OP_BNECK (conv_bneck.hip): conv2 + conv3 + identity + ReLU of one Bottleneck; with fold_c1 its conv1 too
+    // OP_BTAIL (conv_basic.hip): a BasicBlock's stride-2 tail, relu(c2(conv1's output) + ds(block input)), as one `cat` GEMM
+    Conv c1, c2, c3, ds, next_c1;
+    bool fold_ds;        // OP_PAIR: the block's downsample conv is folded in as a second K operand (its output is never materialised)
+    int pooled_dst;      // OP_PAIR at the layer-1 -> layer-2 boundary: buffer for AvgPool2d(2)(y), the next block's downsample input; or BUF_NONE
+    bool fold_c1;        // OP_BNECK: the whole block in one launch
+    size_t wpack_off;    // OP_BNECK: its streaming-order weights in wbneck (ec_bneck_pack_weights / ec_bneck3_pack_weights)
+    Cat cat;             // OP_CAT, OP_BTAIL
 };
 
 }  // namespace
@@ -59,8 +81,8 @@ struct ec_rn50 {
     const float* bias;
     size_t n_w, n_b;
     int conv8_min_tiles = 0;      // 0 = library default (ec_rn50_set_conv8_min_tiles)
-    uint16_t* wbneck = nullptr;   // streaming-order weights of the fused bottleneck launches (ec_bneck_pack_weights), one block per OP_BNECK
-    float* bias_cat = nullptr;    // summed biases of the K-concatenated convs (Op::bcat_off)
+    uint16_t* wbneck = nullptr;   // weights the plan's launches read in their own layout: Cat::w_off, Op::wpack_off, Conv::wimg_off
+    float* bias_cat = nullptr;    // summed biases of the K-concatenated GEMMs (Cat::b_off)
     ~ec_rn50() {
         if (wbneck) (void)hipFree(wbneck);
         if (bias_cat) (void)hipFree(bias_cat);
@@ -70,18 +92,317 @@ struct ec_rn50 {
 namespace {
 constexpr int NBUF = 5;
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-}  // namespace
 
-namespace {
-int pack_plan_weights(ec_rn50* h);
-int rn50_build(ec_rn50_t** out, bool tv, int width, const int* layers4, int input_resolution, const void* stem_w,
-               const void* w_bf16, size_t n_w, const float* bias, size_t n_bias);
+enum TowerKind { CLIP = 0, TV_BOTTLENECK = 1, TV_BASIC = 2 };   // (== ec_rn50::tv)
+
+struct Blk {
+    int li, planes, inplanes, stride;
+    int R, Ro;                // resolution of the block's input / output
+    int x, out;               // buffers of the block's input / output (ping-pong between 0 and 4; the last block writes BUF_OUT)
+    int y;                    // the ping-pong buffer opposite x (== out but for the last block): free until the block's last launch
+    bool ds, last_of_layer;
+    Slot c1, c2, c3, dsc;     // (a BasicBlock has no c3; dsc only where the block downsamples)
+};
+struct Arch { TowerKind kind; int width, R1; Slot stem[3], total; std::vector<Blk> B; };   // R1: resolution behind the stem
+
+// The architecture before any op is planned, in the order ec_amd.h documents: stem convs (CLIP: conv1's weights are passed apart,
+// fp32; the 7x7 stem: all of them), then per block conv1, conv2, conv3, [downsample] (BasicBlock: conv1, conv2, [downsample])
+Arch walk_arch(TowerKind kind, int width, int sc, const int* layers4, int R) {
+    Arch a{kind, width, R};
+    Slot& at = a.total;
+    auto take = [&](size_t Cout, size_t K) { const Slot s = at; at.w += Cout * K; at.b += Cout; return s; };
+    a.stem[0] = take(kind == CLIP ? sc : width, 0);
+    if (kind == CLIP) { a.stem[1] = take(sc, (size_t)9 * sc); a.stem[2] = take(width, (size_t)9 * sc); }
+    const int expansion = kind == TV_BASIC ? 1 : 4;
+    int inplanes = width, x = 0;
+    for (int li = 0; li < 4; ++li)
+        for (int b = 0; b < layers4[li]; ++b) {
+            Blk k{li, width << li, inplanes, (b == 0 && li > 0) ? 2 : 1};
+            const size_t p = k.planes, in = inplanes;
+            k.ds = k.stride > 1 || inplanes != k.planes * expansion;
+            k.last_of_layer = b + 1 == layers4[li];
+            k.R = R; k.Ro = R / k.stride;
+            k.x = x; k.y = k.out = (x == 0) ? 4 : 0;
+            k.c1 = take(p, kind == TV_BASIC ? 9 * in : in);
+            k.c2 = take(p, 9 * p);
+            if (kind != TV_BASIC) k.c3 = take(4 * p, p);
+            if (k.ds) k.dsc = take(expansion * p, in);
+            a.B.push_back(k);
+            x = k.y; inplanes = k.planes * expansion; R = k.Ro;
+        }
+    if (!a.B.empty()) a.B.back().out = BUF_OUT;
+    return a;
 }
 
-extern "C" int ec_rn50_create(ec_rn50_t** out, int width, const int* layers4, int input_resolution,
-                              const float* stem_w_f32, const void* w_bf16, size_t n_w, const float* bias,
-                              size_t n_bias) {
-    return rn50_build(out, false, width, layers4, input_resolution, stem_w_f32, w_bf16, n_w, bias, n_bias);
+// The image-resident K-split 3x3 kernel (conv3x3_img_kernel) instead of conv_igemm: up to how many frames per launch (0: not this conv).
+// The three limits: a fused bottleneck's conv2 run alone (14x14x256) while its (image, slice) workgroups fit one round, 8 * frames <= 256;
+// the un-pooled 7x7x512 convs, two rounds of workgroups at most; layer4.0's pooled 14x14x512 conv2 (two channel chunks, 16 slices per
+// image: one round of workgroups) -- at 32 frames it ties with conv_igemm (47.6 vs 46.6 us).  (The kernel has no residual input: a
+// BasicBlock's conv2 stays on conv_igemm.)
+int img3_max_frames(const Conv& c, bool bneck_conv2 = false) {
+    if (!ec_config().rn50_img3 || c.ks != 3) return 0;
+    if (bneck_conv2) return 32;
+    if (c.Cin != 512 || c.Cout != 512 || c.res >= 0) return 0;
+    return !c.pool && c.H == 7 && c.W == 7 ? 64 : c.pool && c.H == 14 && c.W == 14 ? 16 : 0;
+}
+
+Conv mk_conv(int src, int dst, int res, int H, int W, int Cin, int Cout, int ks, int pool, int act, Slot at, int stride = 1) {
+    Conv c{src, dst, res, H, W, Cin, Cout, ks, pool, act, stride, at};
+    c.img_max = img3_max_frames(c);
+    return c;
+}
+
+struct Plan {   // what the planners append to
+    std::vector<Op>& ops;
+    size_t mx = 0;   // largest activation per frame so far
+    void track(int H, int W, int C) { mx = std::max(mx, (size_t)H * W * C); }
+    void push(const Op& o, int H, int W, int C) { ops.push_back(o); track(H, W, C); }
+    void conv(const Conv& c) {
+        Op o{OP_CONV, c};
+        const int half = (c.pool || c.stride == 2) ? 2 : 1;
+        push(o, c.H / half, c.W / half, c.Cout);
+    }
+    void pool(int src, int dst, int R, int C, int ldo, int ocol, bool pool_of) {
+        Op o{OP_POOL};
+        o.pl = {src, dst, R, R, C, ldo, ocol, pool_of};
+        push(o, R / 2, R / 2, ldo ? ldo : C);
+    }
+};
+
+// What the previous block's boundary launch (OP_PAIR) already produced for this block: the buffer of its conv1 output and
+// (layer-1 -> layer-2) of the pooled block input for the downsample path
+struct Given { int c1_buf = BUF_NONE, pooled_in = BUF_NONE; };
+
+enum Form {
+    F_PLAIN,        // conv1, conv2, [pool,] [downsample conv,] conv3
+    F_POOLOUT,      // ... whose conv3 may also emit the pooled copy of its output for the next block's F_CAT
+    F_PAIR1,        // layer 1: conv3 (+ the block-0 downsample conv) + identity + ReLU chained into the next block's conv1, one launch
+    F_PAIR1_POOL,   // ... that also emits the pooled block output (the next block pools its input)
+    F_PAIR2,        // layer 2: conv3 + identity + ReLU and the next block's conv1 in one launch
+    F_CAT,          // stride-2 block of layers 3-4: conv3 | downsample conv as one GEMM over the concatenated K axis
+    F_BNECK         // conv2 + conv3 (+ conv1) + identity + ReLU in one launch per image
+};
+
+Form block_form(const Arch& a, size_t i) {
+    const Blk& k = a.B[i];
+    const Blk* nx = i + 1 < a.B.size() ? &a.B[i + 1] : nullptr;
+    const auto& cfg = ec_config();
+    // Layer-1 block boundaries (56x56, bandwidth-bound 1x1 convs) run as ONE fused launch per boundary:
+    // conv3 (+ the block-0 downsample conv) + identity + ReLU, chained in registers into the next block's conv1.
+    const bool fuse = cfg.rn50_fuse != 0 && a.width == 64 && (a.R1 % 8) == 0;   // K = 64, N = 256; 32-pixel tiles divide R*R
+    // boundary fusion applies to every block of layer 1 that is followed by a 1x1 conv1 on its output
+    // (downsample + a 128-wide conv1 exceeds the LDS)
+    if (fuse && k.li == 0 && nx && nx->li <= 1 && (!k.ds || (k.inplanes == k.planes && !k.last_of_layer)))
+        return (a.kind == CLIP && k.last_of_layer && !k.ds) ? F_PAIR1_POOL : F_PAIR1;
+    // Stride-2 blocks of layers 3-4 (CLIP: AvgPool2d(2) after conv2 and in front of the downsample conv): the pooled conv2
+    // output [M, planes] and the pooled block input [M, inplanes] are laid side by side, and
+    //   relu(conv3(c2) + b3 + downsample(xp) + bd) == relu([c2 | xp] . [W3 | Wd]^T + (b3 + bd))
+    // is ONE GEMM with K = planes + inplanes: the downsample output (M x 4 planes) is never written or re-read, one
+    // launch less, and the sum is rounded to bf16 once instead of twice.  (layer 2's first block gets its pooled
+    // input from the layer-1 boundary launch and chains conv3 into the next conv1: left as is.)
+    if (k.ds && a.kind == CLIP && k.stride > 1 && k.li >= 2 && cfg.rn50_dscat && (k.planes % 8) == 0) return F_CAT;
+    // Layer-2 block boundaries (28x28, 128 -> 512 -> 128): conv3 + identity + ReLU and the next block's conv1 in
+    // one launch with the weights in registers (conv_pair.hip, layer-2 geometry).
+    if (fuse && k.li == 1 && k.planes == 128 && !k.last_of_layer) return F_PAIR2;
+    // Bottleneck-level fusion (conv_bneck.hip): conv2 + conv3 + identity + ReLU of layer3.1 .. layer3.5 in one launch, one
+    // workgroup per image with the 14 x 14 x 256 map resident in LDS
+    if (cfg.rn50_bneck > 0 && !k.ds && k.stride == 1 && k.planes == 256 && k.Ro == 14) return F_BNECK;
+    // layer 2's last conv3 (128 -> 512 + identity @28x28) can emit the pooled copy the next block's concatenated operand needs
+    // (conv1x1_regw_kernel<.., PL>); whether it did is known per launch (run_conv_poolout)
+    if (cfg.rn50_poolout && k.planes == 128 && nx && block_form(a, i + 1) == F_CAT) return F_POOLOUT;
+    return F_PLAIN;
+}
+
+Given plan_bottleneck(Plan& p, const Arch& a, size_t i, Given g) {
+    const Blk& k = a.B[i];
+    const Blk* nx = i + 1 < a.B.size() ? &a.B[i + 1] : nullptr;
+    const Form f = block_form(a, i);
+    const bool tv = a.kind != CLIP, c1_given = g.c1_buf != BUF_NONE;
+    const int planes = k.planes, inplanes = k.inplanes, R = k.R, Ro = k.Ro, x = k.x, c1_buf = c1_given ? g.c1_buf : 1;
+    // EC_RN50_BNECK3 (default 1): conv1 too -- the whole Bottleneck is ONE launch (bneck23_kernel<.., F1>), conv1's output never leaves the LDS
+    const bool fold_c1 = f == F_BNECK && ec_config().rn50_bneck3 && !c1_given;
+    const Conv c1 = mk_conv(x, 1, BUF_NONE, R, R, inplanes, planes, 1, 0, EC_ACT_RELU, k.c1);
+    // conv2: torchvision strides inside the 3x3 conv itself, CLIP pools behind it
+    Conv c2 = tv && k.stride > 1 ? mk_conv(c1_buf, 2, BUF_NONE, R, R, planes, planes, 3, 0, EC_ACT_RELU, k.c2, 2)
+                                 : mk_conv(c1_buf, 2, BUF_NONE, R, R, planes, planes, 3, k.stride > 1 ? 1 : 0, EC_ACT_RELU, k.c2);
+    if (!c1_given && !fold_c1) p.conv(c1);
+    Op o{};
+    if (f == F_BNECK) {   // launches below EC_RN50_BNECK frames run the parts (bneck_route)
+        o.kind = OP_BNECK; o.fold_c1 = fold_c1;
+        o.c1 = c1; o.c2 = c2; o.c2.img_max = img3_max_frames(c2, true);
+        o.c3 = mk_conv(2, k.out, x, Ro, Ro, planes, planes * 4, 1, 0, EC_ACT_RELU, k.c3);
+        p.push(o, Ro, Ro, planes * 4);
+        return Given{};
+    }
+    if (f == F_PAIR1 || f == F_PAIR1_POOL) {
+        p.conv(c2);
+        o.kind = OP_PAIR;
+        o.c3 = mk_conv(2, k.out, k.ds ? BUF_NONE : x, R, R, planes, planes * 4, 1, 0, EC_ACT_RELU, k.c3);
+        o.fold_ds = k.ds;   // block 0: the downsample conv (x -> 256) is folded in as a second K = 64 operand
+        if (k.ds) o.ds = mk_conv(x, BUF_NONE, BUF_NONE, R, R, inplanes, planes * 4, 1, 0, EC_ACT_NONE, k.dsc);
+        o.next_c1 = mk_conv(k.out, 1, BUF_NONE, R, R, planes * 4, nx->planes, 1, 0, EC_ACT_RELU, nx->c1);
+        o.pooled_dst = f == F_PAIR1_POOL ? 3 : BUF_NONE;
+        if (f == F_PAIR1_POOL) p.track(R / 2, R / 2, planes * 4);
+        p.push(o, R, R, planes * 4);
+        return Given{1, o.pooled_dst};
+    }
+    if (f == F_CAT) {
+        const int Kc = planes + inplanes;
+        // The concatenated operand lives in buffer 3 (free in layers 3-4), not in buffer 2: the conv3 that PRODUCES this block's
+        // input reads its own conv2 output from buffer 2 and may write the pooled columns in the same launch (F_POOLOUT).
+        const int cat = 3;
+        c2.dst = cat; c2.ldo = Kc;   // conv2 (+ pool) -> columns [0, planes)
+        p.conv(c2);
+        p.pool(x, cat, R, inplanes, Kc, planes, i > 0 && block_form(a, i - 1) == F_POOLOUT);   // pooled block input -> columns [planes, Kc)
+        o.kind = OP_CAT;
+        o.c = mk_conv(cat, k.out, BUF_NONE, Ro, Ro, Kc, planes * 4, 1, 0, EC_ACT_RELU, Slot{});
+        o.cat = Cat{k.c3, k.dsc, planes, inplanes};
+        p.push(o, Ro, Ro, planes * 4);
+        return Given{};
+    }
+    // F_PLAIN, F_POOLOUT, F_PAIR2: conv2, the downsample path, conv3.  (The weights are laid out conv1, conv2, conv3, downsample;
+    // the downsample conv has to run BEFORE conv3, which consumes its output as the residual.)
+    p.conv(c2);
+    int idt = x;
+    if (k.ds) {
+        int dsrc = x, ddst = 3;
+        if (tv) {
+            // torchvision: downsample = Conv2d(1x1, stride) + BatchNorm2d straight on the block input
+        } else if (k.stride > 1 && g.pooled_in != BUF_NONE) {   // pooled input came with the previous boundary launch;
+            dsrc = g.pooled_in;                                  // buffer 1 (this block's conv1 output) is free after conv2
+            ddst = 1;
+        } else if (k.stride > 1) {
+            // the pooled block input goes to the block's OUTPUT buffer y (free until conv3 writes it), not to the
+            // conv1 / conv2 temporaries
+            p.pool(x, k.y, R, inplanes, 0, 0, false);
+            dsrc = k.y;
+        }
+        p.conv(tv && k.stride > 1 ? mk_conv(dsrc, ddst, BUF_NONE, R, R, inplanes, planes * 4, 1, 0, EC_ACT_NONE, k.dsc, 2)
+                                  : mk_conv(dsrc, ddst, BUF_NONE, Ro, Ro, inplanes, planes * 4, 1, 0, EC_ACT_NONE, k.dsc));
+        idt = ddst;
+    }
+    const Conv c3 = mk_conv(2, k.out, idt, Ro, Ro, planes, planes * 4, 1, 0, EC_ACT_RELU, k.c3);
+    if (f == F_PLAIN) { p.conv(c3); return Given{}; }
+    if (f == F_PAIR2) {   // frame counts whose row count is not a multiple of 32 run the two convs separately (run_pair)
+        o.kind = OP_PAIR;
+        o.c3 = c3;
+        o.next_c1 = mk_conv(k.out, idt == 1 ? 3 : 1, BUF_NONE, Ro, Ro, planes * 4, planes, 1, 0, EC_ACT_RELU, nx->c1);   // (block 0 with a pooled input keeps its identity in buffer 1)
+        o.pooled_dst = BUF_NONE;
+    } else {   // F_POOLOUT
+        o.kind = OP_CONV_POOLOUT;
+        o.c = c3;
+        o.pd = {3, nx->planes + nx->inplanes, nx->planes};   // the next block's concatenated operand, behind its conv2 columns
+    }
+    p.push(o, Ro, Ro, planes * 4);
+    return f == F_PAIR2 ? Given{o.next_c1.dst, BUF_NONE} : Given{};
+}
+
+// torchvision BasicBlock: conv1: 3x3 + ReLU (stride 2 in the first block of layers 2-4: ec_conv_bf16_s2)
+//   conv2: stride-1 blocks  3x3 + identity + ReLU (ec_conv_bf16 with a residual)
+//          transition blocks 3x3 over conv1's output + the 1x1 stride-2 downsample conv of the block input + ReLU as ONE
+//                            K-concatenated GEMM (OP_BTAIL, conv_basic.hip)
+// Buffers: the block input / output ping-pong between 0 and 4, conv1's output goes to 1; buffer 3 holds the downsample
+// output of a transition tail that runs as two launches (btail_fused).
+void plan_basic(Plan& p, const Blk& k) {
+    const int planes = k.planes, Ro = k.Ro;
+    p.conv(mk_conv(k.x, 1, BUF_NONE, k.R, k.R, k.inplanes, planes, 3, 0, EC_ACT_RELU, k.c1, k.stride));
+    if (!k.ds) {   // conv2 + identity + ReLU
+        p.conv(mk_conv(1, k.out, k.x, Ro, Ro, planes, planes, 3, 0, EC_ACT_RELU, k.c2));
+        return;
+    }
+    Op o{};   // (torchvision downsamples exactly where it strides)
+    o.kind = OP_BTAIL;
+    o.ds = mk_conv(k.x, 3, BUF_NONE, k.R, k.R, k.inplanes, planes, 1, 0, EC_ACT_NONE, k.dsc, 2);
+    o.c2 = mk_conv(1, k.out, 3, Ro, Ro, planes, planes, 3, 0, EC_ACT_RELU, k.c2);
+    o.cat = Cat{k.c2, k.dsc, 9 * planes, k.inplanes};
+    p.push(o, Ro, Ro, planes);
+}
+
+// Weights the plan's fused / K-concatenated / image-resident launches read in their own layout (device copies owned by the handle)
+int pack_plan_weights(ec_rn50* h) {
+    size_t tot = 0, btot = 0;
+    // offsets: the concatenated GEMMs ([Cout][Ka + Kb] weights, summed bias), then per fused bottleneck one packed block (its conv2
+    // comes first in it: what the image-resident kernel reads when conv2 runs alone) and the image-resident 3x3 convs
+    auto cat_n = [](const Op& o) { return (size_t)(o.kind == OP_CAT ? o.c.Cout : o.c2.Cout); };
+    for (Op& o : h->ops)
+        if (o.kind == OP_CAT || o.kind == OP_BTAIL) {
+            o.cat.w_off = tot; tot += cat_n(o) * (size_t)(o.cat.Ka + o.cat.Kb);
+            o.cat.b_off = btot; btot += cat_n(o);
+        }
+    for (Op& o : h->ops) {
+        if (o.kind == OP_BNECK) { o.wpack_off = o.c2.wimg_off = tot; tot += ec_bneck3_packed_elems(o.c2.Cin); }   // (room for conv1 too)
+        if (o.kind == OP_CONV && o.c.img_max) { o.c.wimg_off = tot; tot += (size_t)o.c.Cout * 9 * o.c.Cin; }
+    }
+    if (btot && hipMalloc(&h->bias_cat, btot * sizeof(float)) != hipSuccess) { h->bias_cat = nullptr; return EC_ERR_LAUNCH; }
+    if (!tot) return EC_OK;
+    if (hipMalloc(&h->wbneck, tot * sizeof(uint16_t)) != hipSuccess) { h->wbneck = nullptr; return EC_ERR_LAUNCH; }
+    auto pack_cat = [&](const Cat& c, size_t N) -> int {
+        const size_t K = (size_t)c.Ka + c.Kb;
+        uint16_t* wc = h->wbneck + c.w_off;
+        if (hipMemcpy2D(wc, K * 2, h->w + c.a.w, (size_t)c.Ka * 2, (size_t)c.Ka * 2, N, hipMemcpyDeviceToDevice) != hipSuccess ||
+            hipMemcpy2D(wc + c.Ka, K * 2, h->w + c.b.w, (size_t)c.Kb * 2, (size_t)c.Kb * 2, N, hipMemcpyDeviceToDevice) != hipSuccess) return EC_ERR_LAUNCH;
+        std::vector<float> ba(N), bb(N);
+        if (hipMemcpy(ba.data(), h->bias + c.a.b, N * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(bb.data(), h->bias + c.b.b, N * 4, hipMemcpyDeviceToHost) != hipSuccess) return EC_ERR_LAUNCH;
+        for (size_t i = 0; i < N; ++i) ba[i] += bb[i];
+        return hipMemcpy(h->bias_cat + c.b_off, ba.data(), N * 4, hipMemcpyHostToDevice) != hipSuccess ? EC_ERR_LAUNCH : EC_OK;
+    };
+    for (const Op& o : h->ops) {
+        int rc = EC_OK;
+        if (o.kind == OP_CAT || o.kind == OP_BTAIL) rc = pack_cat(o.cat, cat_n(o));
+        else if (o.kind == OP_BNECK)
+            rc = o.fold_c1 ? ec_bneck3_pack_weights(h->w + o.c1.at.w, h->w + o.c2.at.w, h->w + o.c3.at.w, h->wbneck + o.wpack_off, o.c2.Cin, nullptr)
+                           : ec_bneck_pack_weights(h->w + o.c2.at.w, h->w + o.c3.at.w, h->wbneck + o.wpack_off, o.c2.Cin, nullptr);
+        else if (o.kind == OP_CONV && o.c.img_max) rc = ec_conv3x3_img_pack(h->w + o.c.at.w, h->wbneck + o.c.wimg_off, o.c.Cin, nullptr);
+        if (rc != EC_OK) return EC_ERR_LAUNCH;
+    }
+    (void)hipStreamSynchronize(nullptr);
+    return EC_OK;
+}
+
+// The one builder: the towers differ in their stem and in their block planner
+int rn50_build(ec_rn50_t** out, TowerKind kind, int width, const int* layers4, int input_resolution, const void* stem_w,
+               const void* w_bf16, size_t n_w, const float* bias, size_t n_bias) {
+    if (!out || !layers4 || !stem_w || !w_bf16 || !bias) return EC_ERR_ARG;
+    if (width % 32 != 0 || width < 32 || input_resolution % 32 != 0) return EC_ERR_SHAPE;
+    if (kind == TV_BASIC && (input_resolution < 32 || layers4[0] < 1 || layers4[1] < 1 || layers4[2] < 1 || layers4[3] < 1)) return EC_ERR_SHAPE;
+    // stem channels: width/2, rounded up to the 32-channel granule of the conv kernels (RN50x16: 48 -> 64; the
+    // packer zero-pads the weights, so the padded channels are exactly 0 after ReLU and contribute nothing)
+    const int sc = (width / 2 + 31) / 32 * 32, res = input_resolution;
+    const Arch a = walk_arch(kind, width, sc, layers4, res / 4);
+    if (n_w != a.total.w || n_bias != a.total.b) return EC_ERR_SHAPE;
+    ec_rn50* h = new (std::nothrow) ec_rn50();
+    if (!h) return EC_ERR_ALLOC;
+    h->width = width; h->res = res; h->tv = kind;
+    h->stem_w = (const float*)stem_w; h->w = (const uint16_t*)w_bf16; h->bias = bias;
+    h->n_w = a.total.w; h->n_b = a.total.b;
+    Plan p{h->ops};
+    const int x0 = a.B.empty() ? BUF_OUT : 0;   // the stem's output is the first block's input
+    if (kind == CLIP) {   // conv1 strides by 2 itself: frame -> buffer 1 at R x R x sc
+        const int R = res / 2;
+        p.push(Op{OP_STEM1, mk_conv(BUF_IN, 1, BUF_NONE, res, res, 3, sc, 3, 0, EC_ACT_RELU, a.stem[0])}, R, R, sc);
+        p.conv(mk_conv(1, 2, BUF_NONE, R, R, sc, sc, 3, 0, EC_ACT_RELU, a.stem[1]));
+        p.conv(mk_conv(2, x0, BUF_NONE, R, R, sc, width, 3, 1, EC_ACT_RELU, a.stem[2]));   // + fused AvgPool2d(2)
+    } else {   // conv1 7x7 s2 + bn1 + relu + maxpool 3x3 s2 in one launch: frame -> buffer 0 at R1 x R1 x 64
+        p.push(Op{OP_STEM7, mk_conv(BUF_IN, x0, BUF_NONE, res, res, 3, width, 7, 0, EC_ACT_RELU, a.stem[0])}, a.R1, a.R1, width);
+    }
+    Given g;
+    for (size_t i = 0; i < a.B.size(); ++i)
+        if (kind == TV_BASIC) plan_basic(p, a.B[i]);
+        else g = plan_bottleneck(p, a, i, g);
+    h->out_c = a.B.empty() ? width : a.B.back().planes * (kind == TV_BASIC ? 1 : 4);
+    h->out_sp = a.B.empty() ? a.R1 : a.B.back().Ro;
+    h->max_elems_per_frame = p.mx;
+    const int rc = pack_plan_weights(h);
+    if (rc != EC_OK) { delete h; return rc; }
+    *out = h;
+    return EC_OK;
+}
+}  // namespace
+
+extern "C" int ec_rn50_create(ec_rn50_t** out, int width, const int* layers4, int input_resolution, const float* stem_w_f32,
+                              const void* w_bf16, size_t n_w, const float* bias, size_t n_bias) {
+    return rn50_build(out, CLIP, width, layers4, input_resolution, stem_w_f32, w_bf16, n_w, bias, n_bias);
 }
 
 // torchvision ResNet (v1.5) trunk == Sequential(*list(resnet50.children())[:-2])
@@ -90,349 +411,14 @@ extern "C" int ec_rn50_create(ec_rn50_t** out, int width, const int* layers4, in
 // block of layers 2-4 strides inside its 3x3 conv and its 1x1 downsample conv (ec_conv_bf16_s2) instead of pooling.
 extern "C" int ec_rn50tv_create(ec_rn50_t** out, const int* layers4, int input_resolution, const void* stem_w_bf16,
                                 const void* w_bf16, size_t n_w, const float* bias, size_t n_bias) {
-    return rn50_build(out, true, 64, layers4, input_resolution, stem_w_bf16, w_bf16, n_w, bias, n_bias);
+    return rn50_build(out, TV_BOTTLENECK, 64, layers4, input_resolution, stem_w_bf16, w_bf16, n_w, bias, n_bias);
 }
-
-namespace {
-int rn50_build(ec_rn50_t** out, bool tv, int width, const int* layers4, int input_resolution, const void* stem_w_f32,
-               const void* w_bf16, size_t n_w, const float* bias, size_t n_bias) {
-    if (!out || !layers4 || !stem_w_f32 || !w_bf16 || !bias) return EC_ERR_ARG;
-    if (width % 32 != 0 || width < 32 || input_resolution % 32 != 0) return EC_ERR_SHAPE;
-    // stem channels: width/2, rounded up to the 32-channel granule of the conv kernels (RN50x16: 48 -> 64; the
-    // packer zero-pads the weights, so the padded channels are exactly 0 after ReLU and contribute nothing)
-    const int sc = (width / 2 + 31) / 32 * 32;
-    ec_rn50* h = new (std::nothrow) ec_rn50();
-    if (!h) return EC_ERR_ALLOC;
-    h->width = width; h->res = input_resolution; h->tv = tv ? 1 : 0;
-    h->stem_w = (const float*)stem_w_f32; h->w = (const uint16_t*)w_bf16; h->bias = bias;
-    size_t wo = 0, bo = 0, mx = 0;
-    auto track = [&](int H, int W, int C) { mx = std::max(mx, (size_t)H * W * C); };
-    auto conv = [&](int src, int dst, int res, int H, int W, int Cin, int Cout, int ks, int pool, int act, int stride = 1) {
-        Op o{OP_CONV, src, dst, res, H, W, Cin, Cout, ks, pool, act, wo, bo};
-        o.stride = stride;
-        wo += (size_t)Cout * ks * ks * Cin;
-        bo += Cout;
-        h->ops.push_back(o);
-        track((pool || stride == 2) ? H / 2 : H, (pool || stride == 2) ? W / 2 : W, Cout);
-    };
-    int R = input_resolution / 2;
-    // buffers: 0 = X (block input / output), 1,2 = temporaries, 3 = identity path, 4 = Y
-    if (tv) {   // conv1 7x7 s2 + bn1 + relu + maxpool 3x3 s2 in one launch: frame -> buffer 0 at R/2 x R/2 x 64
-        Op o{OP_STEM7, -2, 0, -1, input_resolution, input_resolution, 3, width, 7, 0, EC_ACT_RELU, 0, bo};
-        bo += width;
-        h->ops.push_back(o);
-        R /= 2;
-        track(R, R, width);
-    } else {   // stem
-        Op o{OP_STEM1, -2, 1, -1, input_resolution, input_resolution, 3, sc, 3, 0, EC_ACT_RELU, 0, bo};
-        bo += sc;
-        h->ops.push_back(o);
-        track(R, R, sc);
-        conv(1, 2, -1, R, R, sc, sc, 3, 0, EC_ACT_RELU);
-        conv(2, 0, -1, R, R, sc, width, 3, 1, EC_ACT_RELU);   // + fused AvgPool2d(2)
-        R /= 2;
-    }
-    // Layer-1 block boundaries (56x56, bandwidth-bound 1x1 convs) run as ONE fused launch per boundary:
-    // conv3 (+ the block-0 downsample conv) + identity + ReLU, chained in registers into the next block's conv1.
-    const bool fuse_env = ec_config().rn50_fuse != 0;
-    const bool fuse_l1 = fuse_env && width == 64 && (R % 8) == 0;   // K = 64, N = 256; 32-pixel tiles divide R*R
-    bool conv1_done = false;   // the previous boundary launch already produced this block's conv1 output in buffer 1
-    int pooled_in = -1;        // ... and (layer-1 -> layer-2) the pooled block input for the downsample path, in this buffer
-    int c1_buf = 1;            // buffer holding that conv1 output
-    int inplanes = width, x = 0;
-    for (int li = 0; li < 4; ++li) {
-        const int planes = width << li;
-        for (int b = 0; b < layers4[li]; ++b) {
-            const int stride = (b == 0 && li > 0) ? 2 : 1;
-            const bool ds = stride > 1 || inplanes != planes * 4;
-            const int y = (x == 0) ? 4 : 0;
-            const int Ro = R / stride;
-            int c1 = 1;
-            if (conv1_done) {   // weights are still laid out conv1, conv2, conv3, downsample: skip the slot
-                wo += (size_t)planes * inplanes;
-                bo += planes;
-                conv1_done = false;
-                c1 = c1_buf;
-            } else {
-                conv(x, 1, -1, R, R, inplanes, planes, 1, 0, EC_ACT_RELU);
-            }
-            if (tv && stride > 1) {   // torchvision: the 3x3 conv itself strides (no pool)
-                conv(c1, 2, -1, R, R, planes, planes, 3, 0, EC_ACT_RELU, 2);
-            } else
-            conv(c1, 2, -1, R, R, planes, planes, 3, stride > 1 ? 1 : 0, EC_ACT_RELU);
-            int idt = x;
-            // weights are laid out conv1, conv2, conv3, downsample; the downsample conv
-            // has to run BEFORE conv3 (conv3 consumes its output as the residual), so
-            // reserve conv3's weight slot first.
-            const size_t w_c3 = wo, b_c3 = bo;
-            wo += (size_t)planes * 4 * planes; bo += planes * 4;
-            // boundary fusion applies to every block of layer 1 that is followed by a 1x1 conv1 on its output
-            const bool last_of_layer = (b + 1 == layers4[li]);
-            const bool pair = fuse_l1 && li == 0 && stride == 1 && (!ds || (inplanes == planes && !last_of_layer)) &&
-                              (!last_of_layer || li + 1 < 4);   // (downsample + a 128-wide conv1 exceeds the LDS)
-            if (pair) {
-                Op o{OP_PAIR, 2, y, ds ? -1 : x, R, R, planes, planes * 4, 1, 0, EC_ACT_RELU, w_c3, b_c3};
-                if (ds) {   // block 0: the downsample conv (x -> 256) is folded in as a second K = 64 operand
-                    o.src1 = x; o.w1_off = wo; o.b1_off = bo;
-                    wo += (size_t)planes * 4 * inplanes; bo += planes * 4;
-                }
-                o.dst2 = 1;
-                o.N2 = last_of_layer ? planes * 2 : planes;          // next conv1: 256 -> planes (same layer) | 2*planes
-                if (!tv && last_of_layer && !ds && (R % 8) == 0) {   // the next block pools its input: emit it here
-                    o.dst3 = 3;
-                    pooled_in = 3;
-                    track(R / 2, R / 2, planes * 4);
-                }
-                o.w2_off = wo; o.b2_off = bo;                        // == the next block's conv1 slot
-                h->ops.push_back(o);
-                track(R, R, planes * 4);
-                conv1_done = true;
-                c1_buf = 1;
-                x = y;
-                inplanes = planes * 4;
-                continue;
-            }
-            // Stride-2 blocks of layers 3-4 (CLIP: AvgPool2d(2) after conv2 and in front of the downsample conv): the pooled conv2
-            // output [M, planes] and the pooled block input [M, inplanes] are laid side by side in buffer 2, and
-            //   relu(conv3(c2) + b3 + downsample(xp) + bd) == relu([c2 | xp] . [W3 | Wd]^T + (b3 + bd))
-            // is ONE GEMM with K = planes + inplanes: the downsample output (M x 4 planes) is never written or re-read, one
-            // launch less, and the sum is rounded to bf16 once instead of twice.  (layer 2's first block gets its pooled
-            // input from the layer-1 boundary launch and chains conv3 into the next conv1: left as is.)
-            if (ds && !tv && stride > 1 && li >= 2 && pooled_in < 0 && ec_config().rn50_dscat && (planes % 8) == 0) {
-                const int Kc = planes + inplanes;
-                // The concatenated operand lives in buffer 3 (free in layers 3-4), not in buffer 2: the conv3 that PRODUCES this block's
-                // input reads its own conv2 output from buffer 2 and may write the pooled columns in the same launch (below).
-                const int cat = 3;
-                Op& c2op = h->ops.back();                       // conv2 (+ pool) -> buffer `cat`, columns [0, planes)
-                c2op.ldo = Kc;
-                c2op.dst = cat;
-                Op pl{OP_POOL, x, cat, -1, R, R, inplanes, inplanes, 0, 0, 0, 0, 0};
-                pl.ldo = Kc; pl.ocol = planes;                 // pooled block input -> buffer `cat`, columns [planes, Kc)
-                // layer 2's last conv3 (128 -> 512 + identity @28x28; three ops back: behind it came this block's conv1 and conv2) can emit
-                // the pooled copy itself (conv1x1_regw_kernel<.., PL>); whether it did is known per launch (rn50_run)
-                if (ec_config().rn50_poolout && h->ops.size() >= 3) {
-                    Op& pr = h->ops[h->ops.size() - 3];
-                    if (pr.kind == OP_CONV && pr.ks == 1 && pr.dst == x && pr.res >= 0 && pr.Cin == 128 && pr.Cout == inplanes && inplanes == 512 &&
-                        pr.H == R && pr.W == R && pr.act == EC_ACT_RELU && !pr.pool && !pr.ldo && pr.wcat_off < 0) {
-                        pr.pdst = cat; pr.pld = Kc; pr.pcol = planes;
-                        pl.pool_of = 1;
-                    }
-                }
-                h->ops.push_back(pl);
-                track(Ro, Ro, Kc);
-                Op o{OP_CONV, cat, y, -1, Ro, Ro, Kc, planes * 4, 1, 0, EC_ACT_RELU, w_c3, b_c3};
-                o.w1_off = wo; o.b1_off = bo;                   // the downsample conv's slot
-                o.N2 = planes;
-                o.wcat_off = 0;                                 // (assigned below, with the other packed weights)
-                wo += (size_t)planes * 4 * inplanes; bo += planes * 4;
-                h->ops.push_back(o);
-                track(Ro, Ro, planes * 4);
-                x = y;
-                inplanes = planes * 4;
-                R = Ro;
-                continue;
-            }
-            if (ds) {
-                int dsrc = x, ddst = 3;
-                if (tv) {
-                    // torchvision: downsample = Conv2d(1x1, stride) + BatchNorm2d straight on the block input
-                } else
-                if (stride > 1 && pooled_in >= 0) {   // pooled input came with the previous boundary launch (buffer 3);
-                    dsrc = pooled_in;                 // buffer 1 (this block's conv1 output) is free after conv2
-                    ddst = 1;
-                    pooled_in = -1;
-                } else if (stride > 1) {
-                    // the pooled block input goes to the block's OUTPUT buffer y (free until conv3 writes it), not to the
-                    // conv1 / conv2 temporaries
-                    Op o{OP_POOL, x, y, -1, R, R, inplanes, inplanes, 0, 0, 0, 0, 0};
-                    h->ops.push_back(o);
-                    track(Ro, Ro, inplanes);
-                    dsrc = y;
-                }
-                if (tv && stride > 1) {
-                    conv(dsrc, ddst, -1, R, R, inplanes, planes * 4, 1, 0, EC_ACT_NONE, 2);
-                } else
-                conv(dsrc, ddst, -1, Ro, Ro, inplanes, planes * 4, 1, 0, EC_ACT_NONE);
-                idt = ddst;
-            }
-            // Layer-2 block boundaries (28x28, 128 -> 512 -> 128): conv3 + identity + ReLU and the next block's conv1 in
-            // one launch with the weights in registers (conv_pair.hip, layer-2 geometry).  Frame counts whose row count
-            // is not a multiple of 32 run the two convs separately (see rn50_run).
-            if (fuse_l1 && li == 1 && planes == 128 && !last_of_layer) {
-                Op o{OP_PAIR, 2, y, idt, Ro, Ro, planes, planes * 4, 1, 0, EC_ACT_RELU, w_c3, b_c3};
-                o.dst2 = (idt == 1) ? 3 : 1;      // block 0 with a pooled input keeps its identity in buffer 1
-                o.N2 = planes;
-                o.w2_off = wo; o.b2_off = bo;     // == the next block's conv1 slot
-                h->ops.push_back(o);
-                track(Ro, Ro, planes * 4);
-                conv1_done = true;
-                c1_buf = o.dst2;
-            } else if (ec_config().rn50_bneck > 0 && !ds && stride == 1 && planes == 256 && Ro == 14 && !h->ops.empty() &&
-                       h->ops.back().kind == OP_CONV && h->ops.back().ks == 3 && h->ops.back().dst == 2) {
-                // Bottleneck-level fusion (conv_bneck.hip): conv2 + conv3 + identity + ReLU of layer3.1 .. layer3.5 in one
-                // launch, one workgroup per image with the 14 x 14 x 256 map resident in LDS.  The conv2 op just planned
-                // is folded in: src = conv1's output, res = the block input, w / b = conv2's, w1 / b1 = conv3's.
-                // Launches below EC_RN50_BNECK frames run the two convs separately (rn50_run): a workgroup per image
-                // only fills the chip from ~128 images on.
-                const Op c2 = h->ops.back();
-                h->ops.pop_back();
-                Op o{OP_BNECK, c2.src, y, idt, Ro, Ro, planes, planes * 4, 3, 0, EC_ACT_RELU, c2.w_off, c2.b_off};
-                o.w1_off = w_c3; o.b1_off = b_c3;
-                // EC_RN50_BNECK3 (default 1): conv1 too -- the whole Bottleneck is ONE launch (bneck23_kernel<.., F1>): the op
-                // just before conv2 is this block's conv1 (x -> buffer 1); it is folded in and its output never leaves the LDS
-                if (ec_config().rn50_bneck3 && !h->ops.empty() && h->ops.back().kind == OP_CONV && h->ops.back().ks == 1 &&
-                    h->ops.back().src == idt && h->ops.back().dst == c2.src && h->ops.back().Cin == planes * 4 && h->ops.back().Cout == planes) {
-                    o.wc1_off = (long)h->ops.back().w_off; o.bc1_off = (long)h->ops.back().b_off;
-                    h->ops.pop_back();
-                }
-                h->ops.push_back(o);
-                track(Ro, Ro, planes * 4);
-            } else {
-                Op o{OP_CONV, 2, y, idt, Ro, Ro, planes, planes * 4, 1, 0, EC_ACT_RELU, w_c3, b_c3};
-                h->ops.push_back(o);
-                track(Ro, Ro, planes * 4);
-            }
-            x = y;
-            inplanes = planes * 4;
-            R = Ro;
-        }
-    }
-    h->ops.back().dst = -3;
-    h->out_c = inplanes; h->out_sp = R;
-    h->max_elems_per_frame = mx;
-    h->n_w = wo; h->n_b = bo;
-    if (n_w != wo || n_bias != bo) { delete h; return EC_ERR_SHAPE; }
-    const int rc = pack_plan_weights(h);
-    if (rc != EC_OK) { delete h; return rc; }
-    *out = h;
-    return EC_OK;
-}
-
-// Weights the plan's fused / K-concatenated launches read in their own layout (device copies owned by the handle)
-int pack_plan_weights(ec_rn50* h) {
-    {   // fused bottleneck launches: their conv2 + conv3 weights in streaming order, one packed block per op (w2_off = its offset)
-        size_t tot = 0, btot = 0;
-        for (Op& o : h->ops)
-            if (o.wcat_off >= 0) {   // K-concatenated conv3 | downsample conv: [Cout][K1 + K2] weights, summed bias
-                o.wcat_off = (long)tot; tot += (size_t)o.Cout * o.Cin;
-                o.bcat_off = (long)btot; btot += (size_t)o.Cout;
-            }
-        if (btot && hipMalloc(&h->bias_cat, btot * sizeof(float)) != hipSuccess) { h->bias_cat = nullptr; return EC_ERR_LAUNCH; }
-        for (Op& o : h->ops) {
-            if (o.kind == OP_BNECK) { o.w2_off = tot; o.wimg_off = (long)tot; tot += ec_bneck3_packed_elems(o.Cin); }   // (packed conv2 comes first; room for conv1 too)
-            // the un-pooled 3x3 convs of the 7x7 stage: streaming-order weights for the small-launch kernel (conv3x3_img_kernel)
-            // (that kernel has no residual input: a BasicBlock's conv2 stays on conv_igemm)
-            if (o.kind == OP_CONV && o.ks == 3 && o.Cin == 512 && o.Cout == 512 && o.res < 0 && ec_config().rn50_img3 &&
-                ((!o.pool && o.H == 7 && o.W == 7) || (o.pool && o.H == 14 && o.W == 14))) {   // (layer4.0's conv2 + AvgPool2d: the chunked variant)
-                o.wimg_off = (long)tot;
-                tot += (size_t)o.Cout * 9 * o.Cin;
-            }
-        }
-        if (tot) {
-            if (hipMalloc(&h->wbneck, tot * sizeof(uint16_t)) != hipSuccess) { h->wbneck = nullptr; return EC_ERR_LAUNCH; }
-            for (const Op& o : h->ops) {
-                int rc = EC_OK;
-                if (o.wcat_off >= 0) {
-                    const int K1 = o.N2, K2 = o.Cin - o.N2;
-                    uint16_t* wc = h->wbneck + o.wcat_off;
-                    if (hipMemcpy2D(wc, (size_t)o.Cin * 2, h->w + o.w_off, (size_t)K1 * 2, (size_t)K1 * 2, (size_t)o.Cout,
-                                    hipMemcpyDeviceToDevice) != hipSuccess ||
-                        hipMemcpy2D(wc + K1, (size_t)o.Cin * 2, h->w + o.w1_off, (size_t)K2 * 2, (size_t)K2 * 2, (size_t)o.Cout,
-                                    hipMemcpyDeviceToDevice) != hipSuccess) return EC_ERR_LAUNCH;
-                    std::vector<float> b3((size_t)o.Cout), bd((size_t)o.Cout);
-                    if (hipMemcpy(b3.data(), h->bias + o.b_off, (size_t)o.Cout * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(bd.data(), h->bias + o.b1_off, (size_t)o.Cout * 4, hipMemcpyDeviceToHost) != hipSuccess) return EC_ERR_LAUNCH;
-                    for (int i = 0; i < o.Cout; ++i) b3[(size_t)i] += bd[(size_t)i];
-                    if (hipMemcpy(h->bias_cat + o.bcat_off, b3.data(), (size_t)o.Cout * 4, hipMemcpyHostToDevice) != hipSuccess) return EC_ERR_LAUNCH;
-                    continue;
-                }
-                if (o.kind == OP_BNECK)
-                    rc = o.wc1_off >= 0 ? ec_bneck3_pack_weights(h->w + o.wc1_off, h->w + o.w_off, h->w + o.w1_off, h->wbneck + o.w2_off, o.Cin, nullptr)
-                                        : ec_bneck_pack_weights(h->w + o.w_off, h->w + o.w1_off, h->wbneck + o.w2_off, o.Cin, nullptr);
-                else if (o.wimg_off >= 0) rc = ec_conv3x3_img_pack(h->w + o.w_off, h->wbneck + o.wimg_off, o.Cin, nullptr);
-                if (rc != EC_OK) return EC_ERR_LAUNCH;
-            }
-            (void)hipStreamSynchronize(nullptr);
-        }
-    }
-    return EC_OK;
-}
-}  // namespace
 
 // torchvision BasicBlock ResNet (ResNet-18: 2,2,2,2 / ResNet-34: 3,4,6,3) without avgpool / fc, behind the same handle:
-// the 7x7 stem launch of ec_rn50tv_create, then per block
-//   conv1: 3x3 + ReLU (stride 2 in the first block of layers 2-4: ec_conv_bf16_s2)
-//   conv2: stride-1 blocks  3x3 + identity + ReLU (ec_conv_bf16 with a residual)
-//          transition blocks 3x3 over conv1's output + the 1x1 stride-2 downsample conv of the block input + ReLU as ONE
-//                            K-concatenated GEMM (OP_BTAIL, conv_basic.hip)
-// Buffers: the block input / output ping-pong between 0 and 4, conv1's output goes to 1; buffer 3 holds the downsample
-// output of a transition tail that runs as two launches (rn50_run).
+// the 7x7 stem launch of ec_rn50tv_create, then plan_basic() per block
 extern "C" int ec_tvresnet_basic_create(ec_rn50_t** out, const int* layers4, int input_resolution, const void* stem_w_bf16,
                                         const void* w_bf16, size_t n_w, const float* bias, size_t n_bias) {
-    if (!out || !layers4 || !stem_w_bf16 || !w_bf16 || !bias) return EC_ERR_ARG;
-    if (input_resolution % 32 != 0 || input_resolution < 32) return EC_ERR_SHAPE;
-    for (int li = 0; li < 4; ++li)
-        if (layers4[li] < 1) return EC_ERR_SHAPE;
-    const int width = 64;
-    ec_rn50* h = new (std::nothrow) ec_rn50();
-    if (!h) return EC_ERR_ALLOC;
-    h->width = width; h->res = input_resolution; h->tv = 2;
-    h->stem_w = (const float*)stem_w_bf16; h->w = (const uint16_t*)w_bf16; h->bias = bias;
-    size_t wo = 0, bo = 0, mx = 0;
-    auto track = [&](int H, int W, int C) { mx = std::max(mx, (size_t)H * W * C); };
-    int R = input_resolution / 4;
-    {   // conv1 7x7 s2 + bn1 + relu + maxpool 3x3 s2 in one launch: frame -> buffer 0 at R x R x 64
-        Op o{OP_STEM7, -2, 0, -1, input_resolution, input_resolution, 3, width, 7, 0, EC_ACT_RELU, 0, bo};
-        bo += width;
-        h->ops.push_back(o);
-        track(R, R, width);
-    }
-    int inplanes = width, x = 0;
-    for (int li = 0; li < 4; ++li) {
-        const int planes = width << li;
-        for (int b = 0; b < layers4[li]; ++b) {
-            const int stride = (b == 0 && li > 0) ? 2 : 1;
-            const int y = (x == 0) ? 4 : 0;
-            const int Ro = R / stride;
-            {   // conv1 (H, W of a stride-2 op are its INPUT dims)
-                Op o{OP_CONV, x, 1, -1, R, R, inplanes, planes, 3, 0, EC_ACT_RELU, wo, bo};
-                o.stride = stride;
-                wo += (size_t)planes * 9 * inplanes; bo += planes;
-                h->ops.push_back(o);
-                track(Ro, Ro, planes);
-            }
-            if (stride == 1 && inplanes == planes) {   // conv2 + identity + ReLU
-                Op o{OP_CONV, 1, y, x, R, R, planes, planes, 3, 0, EC_ACT_RELU, wo, bo};
-                wo += (size_t)planes * 9 * planes; bo += planes;
-                h->ops.push_back(o);
-            } else {
-                if (stride != 2) { delete h; return EC_ERR_SHAPE; }   // (torchvision downsamples exactly where it strides)
-                // conv2 | downsample over K = 9 planes + inplanes: Cin = the concatenated K, N2 = conv2's share (the layout the
-                // K-concatenated convs of the CLIP plan use, so pack_plan_weights builds W_cat and the summed bias)
-                Op o{OP_BTAIL, 1, y, -1, Ro, Ro, 9 * planes + inplanes, planes, 3, 0, EC_ACT_RELU, wo, bo};
-                o.src1 = x;
-                o.N2 = 9 * planes;
-                wo += (size_t)planes * 9 * planes; bo += planes;
-                o.w1_off = wo; o.b1_off = bo;
-                wo += (size_t)planes * inplanes; bo += planes;
-                o.wcat_off = 0;                          // (assigned by pack_plan_weights)
-                h->ops.push_back(o);
-            }
-            track(Ro, Ro, planes);
-            x = y;
-            inplanes = planes;
-            R = Ro;
-        }
-    }
-    h->ops.back().dst = -3;
-    h->out_c = inplanes; h->out_sp = R;
-    h->max_elems_per_frame = mx;
-    h->n_w = wo; h->n_b = bo;
-    if (n_w != wo || n_bias != bo) { delete h; return EC_ERR_SHAPE; }
-    const int rc = pack_plan_weights(h);
-    if (rc != EC_OK) { delete h; return rc; }
-    *out = h;
-    return EC_OK;
+    return rn50_build(out, TV_BASIC, 64, layers4, input_resolution, stem_w_bf16, w_bf16, n_w, bias, n_bias);
 }
 
 extern "C" void ec_rn50_destroy(ec_rn50_t* h) { delete h; }
@@ -451,8 +437,23 @@ extern "C" uint64_t ec_rn50_plan_hash(const ec_rn50_t* h) {
     mix(ec_version()); mix((long)ec_config_hash());
     mix(h->width); mix(h->res); mix(h->conv8_min_tiles); mix(h->tv);
     for (const Op& o : h->ops) {
-        mix(o.kind); mix(o.src); mix(o.dst); mix(o.res); mix(o.H); mix(o.W); mix(o.Cin); mix(o.Cout); mix(o.ks);
-        mix(o.pool); mix(o.act); mix(o.stride); mix(o.src1); mix(o.dst2); mix(o.N2); mix(o.dst3); mix(o.wc1_off >= 0); mix(o.ldo); mix(o.ocol); mix(o.wcat_off >= 0); mix(o.pdst); mix(o.pld); mix(o.pcol); mix(o.pool_of);
+        // The 24 values per op and their order are FROZEN (the flat op record of the versions the summaries under profiles/ were
+        // measured on): a plan that launches the same kernels must keep its key.  0 kind, 1 src, 2 dst, 3 res, 4 H, 5 W, 6 Cin, 7 Cout,
+        // 8 ks, 9 pool, 10 act, 11 stride, 12 second source, 13 second dst, 14 second width / first K share, 15 pooled dst, 16 conv1
+        // folded, 17 ldo, 18 ocol, 19 concatenated K, 20-22 pooled-output buffer, row stride, column, 23 pool_of
+        const Conv& c = o.kind == OP_PAIR || o.kind == OP_BNECK ? o.c3 : o.kind == OP_BTAIL ? o.c2 : o.c;
+        long f[24] = {o.kind, c.src, c.dst, c.res, c.H, c.W, c.Cin, c.Cout, c.ks, c.pool, c.act, c.stride, -1, -1, 0, -1, 0, c.ldo, c.ocol, 0, -1, 0, 0, 0};
+        if (o.kind == OP_POOL) {
+            const long p[12] = {OP_POOL, o.pl.src, o.pl.dst, -1, o.pl.H, o.pl.W, o.pl.C, o.pl.C, 0, 0, 0, 1};
+            std::copy(p, p + 12, f);
+            f[17] = o.pl.ldo; f[18] = o.pl.ocol; f[23] = o.pl.pool_of;
+        }
+        if (o.kind == OP_PAIR) { f[12] = o.fold_ds ? o.ds.src : -1; f[13] = o.next_c1.dst; f[14] = o.next_c1.Cout; f[15] = o.pooled_dst; }
+        if (o.kind == OP_BNECK) { f[1] = o.c2.src; f[8] = 3; f[16] = o.fold_c1; }
+        if (o.kind == OP_BTAIL) { f[3] = -1; f[6] = o.cat.Ka + o.cat.Kb; f[12] = o.ds.src; f[14] = o.cat.Ka; f[19] = 1; }
+        if (o.kind == OP_CAT) { f[0] = OP_CONV; f[14] = o.cat.Ka; f[19] = 1; }
+        if (o.kind == OP_CONV_POOLOUT) { f[0] = OP_CONV; f[20] = o.pd.dst; f[21] = o.pd.ld; f[22] = o.pd.col; }
+        for (long v : f) mix(v);
     }
     return x;
 }
@@ -477,37 +478,125 @@ struct FrameIn {
     float scale, shift;            // DEPTH: value = depth * scale + shift
     const float* stem_w9;          // DEPTH: the stem weights summed over the input channels, f32 [9][stem channels]
 };
-int rn50_run(const ec_rn50_t* h, const FrameIn& in, int batch, void* workspace, size_t ws_bytes, void* feat, int chunk,
-             ec_stream_t stream);
+struct Run {   // one chunk of frames on its way through the plan
+    const ec_rn50* h;
+    const FrameIn& in;
+    const void* frames; int nb;   // this chunk's frames
+    unsigned char* base;   // the workspace: NBUF buffers of bufsz bytes
+    size_t bufsz;
+    void* out;             // this chunk's rows of the caller's feature tensor
+    hipStream_t stream;
+    bool pooled_emitted;   // the last OP_CONV_POOLOUT wrote the pooled copy of its output: the OP_POOL marked pool_of is skipped
+    void* buf(int id) const { return id == BUF_OUT ? out : base + (size_t)id * bufsz; }
+    const void* opt(int id) const { return id == BUF_NONE ? nullptr : buf(id); }
+};
+
+// Every plain conv, op or part: the strided kernel, the image-resident 3x3 kernel for small launches (img3_max_frames), conv_igemm
+int run_conv(const Run& r, const Conv& c) {
+    const ec_rn50* h = r.h;
+    if (c.stride == 2)
+        return ec_conv_bf16_s2(r.buf(c.src), h->w + c.at.w, h->bias + c.at.b, r.opt(c.res), r.buf(c.dst), r.nb, c.H, c.W, c.Cin, c.Cout, c.ks,
+                               c.act, r.stream);
+    uint16_t* dst = (uint16_t*)r.buf(c.dst) + c.ocol;
+    if (r.nb <= c.img_max)
+        return ec_conv3x3_img_bf16_ld(r.buf(c.src), h->wbneck + c.wimg_off, h->bias + c.at.b, dst, r.nb, c.H, c.W, c.Cin, c.pool,
+                                      c.ldo ? c.ldo : c.Cin, r.stream);
+    return ec_conv_bf16_ld(r.buf(c.src), h->w + c.at.w, h->bias + c.at.b, r.opt(c.res), dst, r.nb, c.H, c.W, c.Cin, c.Cout, c.ks, c.pool, c.act,
+                           c.ldo ? c.ldo : c.Cout, r.stream);
 }
 
-extern "C" int ec_rn50_forward(const ec_rn50_t* h, const float* rgb, int batch, void* workspace, size_t ws_bytes,
-                               void* feat, int chunk, ec_stream_t stream) {
-    return rn50_run(h, FrameIn{FrameIn::F32, rgb, nullptr, nullptr, 1.f, 0.f, nullptr}, batch, workspace, ws_bytes, feat, chunk, stream);
+int run_stem(const Run& r, const Op& o) {
+    const FrameIn& in = r.in;
+    const Conv& c = o.c;
+    const float* bias = r.h->bias + c.at.b;
+    if (o.kind == OP_STEM7)
+        return ec_stem7_pool(r.frames, in.kind == FrameIn::U8 ? 1 : 0, in.mean3, in.std3, r.h->stem_w, bias, r.buf(c.dst), r.nb, c.H, c.W, r.stream);
+    if (in.kind == FrameIn::DEPTH)
+        return ec_stem_conv1_depth((const float*)r.frames, in.scale, in.shift, in.stem_w9, bias, r.buf(c.dst), r.nb, c.H, c.W, c.Cout, r.stream);
+    if (in.kind == FrameIn::U8)
+        return ec_stem_conv1_u8((const uint8_t*)r.frames, in.mean3, in.std3, r.h->stem_w, bias, r.buf(c.dst), r.nb, c.H, c.W, c.Cout, r.stream);
+    return ec_stem_conv1((const float*)r.frames, r.h->stem_w, bias, r.buf(c.dst), r.nb, c.H, c.W, c.Cout, r.stream);
 }
 
-extern "C" int ec_rn50_forward_u8(const ec_rn50_t* h, const uint8_t* rgb_u8, const float* h_mean3, const float* h_std3,
-                                  int batch, void* workspace, size_t ws_bytes, void* feat, int chunk,
-                                  ec_stream_t stream) {
-    if (!h_mean3 || !h_std3) return EC_ERR_ARG;
-    return rn50_run(h, FrameIn{FrameIn::U8, rgb_u8, h_mean3, h_std3, 1.f, 0.f, nullptr}, batch, workspace, ws_bytes, feat, chunk, stream);
+int run_pool(Run& r, const Op& o) {
+    const auto& p = o.pl;
+    if (p.pool_of && r.pooled_emitted) { r.pooled_emitted = false; return EC_OK; }
+    if (p.ldo) return ec_avgpool2_bf16_ld(r.buf(p.src), (uint16_t*)r.buf(p.dst) + p.ocol, r.nb, p.H, p.W, p.C, p.ldo, r.stream);
+    return ec_avgpool2_bf16(r.buf(p.src), r.buf(p.dst), r.nb, p.H, p.W, p.C, r.stream);
 }
 
-// The depth tower of the RGB-D agent: the same plan, OP_STEM1 on the one-channel kernel (stem_depth.hip).  The handle stays
-// pointer-only: the folded stem weights come with the call.
-extern "C" int ec_rn50_forward_depth(const ec_rn50_t* h, const float* depth, float scale, float shift, const float* stem_w9,
-                                     int batch, void* workspace, size_t ws_bytes, void* feat, int chunk, ec_stream_t stream) {
-    if (!stem_w9) return EC_ERR_ARG;
-    return rn50_run(h, FrameIn{FrameIn::DEPTH, depth, nullptr, nullptr, scale, shift, stem_w9}, batch, workspace, ws_bytes, feat,
-                    chunk, stream);
+// conv3 that may also emit AvgPool2d(2) of its output.  The launch itself is the route function: conv1x1_regw_kernel<.., PL> takes an
+// even frame count of at least 42 and returns EC_ERR_SHAPE otherwise; the plain conv3 runs then, and the OP_POOL marked pool_of pools
+int run_conv_poolout(Run& r, const Op& o) {
+    const Conv& c = o.c;
+    const int rc = ec_conv1x1_regw_pool(r.buf(c.src), r.h->w + c.at.w, r.h->bias + c.at.b, r.buf(c.res), r.buf(c.dst),
+                                        (uint16_t*)r.buf(o.pd.dst) + o.pd.col, r.nb, c.H, c.W, c.Cin, c.Cout, c.act, o.pd.ld, r.stream);
+    if (rc == EC_OK) r.pooled_emitted = true;
+    return rc == EC_ERR_SHAPE ? run_conv(r, c) : rc;
 }
 
-namespace {
+int run_cat(const Run& r, const Op& o) {   // conv3 | downsample conv over the concatenated K axis
+    const Conv& c = o.c;
+    return ec_conv_bf16_ld(r.buf(c.src), r.h->wbneck + o.cat.w_off, r.h->bias_cat + o.cat.b_off, nullptr, r.buf(c.dst), r.nb, c.H, c.W, c.Cin,
+                           c.Cout, 1, 0, c.act, c.Cout, r.stream);
+}
+
+// The boundary launch is its own route function too: EC_ERR_SHAPE for a row count that is no multiple of its tile (e.g. an odd number
+// of 28x28 frames), and the two convs run separately.  (With the downsample conv folded in, or the pooled copy, there is no such route.)
+int run_pair(const Run& r, const Op& o) {
+    const ec_rn50* h = r.h;
+    const Conv &c3 = o.c3, &c1 = o.next_c1;
+    if (o.pooled_dst != BUF_NONE)
+        // (the full-resolution block output is dead here: the next block reads c1.dst and pooled_dst only)
+        return ec_conv1x1_pair_pool_bf16(r.buf(c3.src), h->w + c3.at.w, h->bias + c3.at.b, r.buf(c3.res), nullptr, r.buf(o.pooled_dst),
+                                         h->w + c1.at.w, h->bias + c1.at.b, r.buf(c1.dst), r.nb, c3.H, c3.W, c3.Cin, c3.Cout, c1.Cout, r.stream);
+    int rc = ec_conv1x1_pair_bf16(r.buf(c3.src), h->w + c3.at.w, h->bias + c3.at.b, o.fold_ds ? r.buf(o.ds.src) : nullptr,
+                                  o.fold_ds ? h->w + o.ds.at.w : nullptr, o.fold_ds ? h->bias + o.ds.at.b : nullptr, r.opt(c3.res),
+                                  r.buf(c3.dst), h->w + c1.at.w, h->bias + c1.at.b, r.buf(c1.dst), (long)r.nb * c3.H * c3.W, c3.Cin, c3.Cout,
+                                  c1.Cout, r.stream);
+    if (rc == EC_ERR_SHAPE && !o.fold_ds) {
+        rc = run_conv(r, c3);
+        if (rc == EC_OK) rc = run_conv(r, c1);
+    }
+    return rc;
+}
+
+// Launches below EC_RN50_BNECK frames run the convs separately: a workgroup per image only fills the chip from ~128 images on.
+bool bneck_fused(int nb) { return nb >= ec_config().rn50_bneck; }
+
+int run_bneck(const Run& r, const Op& o) {
+    const ec_rn50* h = r.h;
+    const Conv &c1 = o.c1, &c2 = o.c2, &c3 = o.c3;
+    if (bneck_fused(r.nb) && o.fold_c1)
+        return ec_bneck_conv123_bf16(r.buf(c3.res), h->wbneck + o.wpack_off, h->bias + c1.at.b, h->bias + c2.at.b, h->bias + c3.at.b,
+                                     r.buf(c3.dst), r.nb, c3.H, c3.W, c2.Cin, r.stream);
+    if (bneck_fused(r.nb))
+        return ec_bneck_conv23_bf16(r.buf(c2.src), h->wbneck + o.wpack_off, h->bias + c2.at.b, h->bias + c3.at.b, r.buf(c3.res),
+                                    r.buf(c3.dst), r.nb, c3.H, c3.W, c2.Cin, r.stream);
+    // (buffer 1 = conv1's, buffer 2 = conv2's output, as in the unfused plan; conv2 on the image-resident kernel while it fits one round)
+    int rc = o.fold_c1 ? run_conv(r, c1) : EC_OK;
+    if (rc == EC_OK) rc = run_conv(r, c2);
+    return rc == EC_OK ? run_conv(r, c3) : rc;
+}
+
+// The one-launch tail where it measured faster than the two launches (profiles/basic_tail_ab.txt): layer2.0 at every frame count,
+// layer3.0 up to 32 frames.  Deeper-K / larger launches: the downsample conv into buffer 3, then conv2 with it as the residual
+// (the 8-wave and ring instances of conv_igemm win there).
+bool btail_fused(const Op& o, int nb) { return o.c2.Cout <= 128 || (o.c2.Cout <= 256 && nb <= 32); }
+
+int run_btail(const Run& r, const Op& o) {
+    const Conv &c2 = o.c2, &ds = o.ds;
+    if (btail_fused(o, r.nb))
+        return ec_basic_tail_s2_bf16(r.buf(c2.src), r.buf(ds.src), r.h->wbneck + o.cat.w_off, r.h->bias_cat + o.cat.b_off, r.buf(c2.dst), r.nb,
+                                     c2.H, c2.W, c2.Cin, ds.Cin, c2.Cout, r.stream);
+    const int rc = run_conv(r, ds);
+    return rc == EC_OK ? run_conv(r, c2) : rc;
+}
+
 int rn50_run(const ec_rn50_t* h, const FrameIn& in, int batch, void* workspace, size_t ws_bytes, void* feat, int chunk,
              ec_stream_t stream_main) {
     if (!h || !in.p || !workspace || !feat) return EC_ERR_ARG;
     if (batch <= 0) return EC_ERR_SHAPE;
-    const bool u8 = in.kind == FrameIn::U8;
     if (in.kind == FrameIn::DEPTH && (h->ops.empty() || h->ops.front().kind != OP_STEM1))
         return EC_ERR_UNSUPPORTED;   // the 7x7 stem of the torchvision towers has no one-channel kernel
     if (chunk <= 0 || chunk > batch) chunk = batch;
@@ -518,133 +607,24 @@ int rn50_run(const ec_rn50_t* h, const FrameIn& in, int batch, void* workspace, 
     if (ws_bytes < ec_rn50_workspace_bytes(h, chunk)) return EC_ERR_WORKSPACE;
     const ec_min_tiles_scope mint_scope(h->conv8_min_tiles);   // this handle's dispatch threshold, for this call only
     const size_t bufsz = align_up(h->max_elems_per_frame * 2 * (size_t)chunk, 256);
-    unsigned char* base = (unsigned char*)workspace;
-    // elements per frame: a depth frame has ONE channel
-    const size_t rgb_stride = (size_t)h->res * h->res * (in.kind == FrameIn::DEPTH ? 1 : 3);
-    const void* rgb = in.p;
-    const float *mean3 = in.mean3, *std3 = in.std3;
+    // bytes per frame: a depth frame has ONE channel
+    const size_t frame_bytes = (size_t)h->res * h->res * (in.kind == FrameIn::DEPTH ? 1 : 3) * (in.kind == FrameIn::U8 ? 1 : 4);
     const size_t out_stride = (size_t)h->out_sp * h->out_sp * h->out_c;
     for (int b0 = 0; b0 < batch; b0 += chunk) {
-        const int nb = std::min(chunk, batch - b0);
-        auto buf = [&](int id) -> void* {
-            if (id == -3) return (uint16_t*)feat + (size_t)b0 * out_stride;
-            return base + (size_t)id * bufsz;
-        };
-        bool pooled_emitted = false;   // the last conv3 wrote the pooled copy of its output: the OP_POOL marked pool_of is skipped
+        Run r{h, in, (const unsigned char*)in.p + (size_t)b0 * frame_bytes, std::min(chunk, batch - b0), (unsigned char*)workspace, bufsz,
+              (uint16_t*)feat + (size_t)b0 * out_stride, (hipStream_t)stream_main, false};
         for (const Op& o : h->ops) {
             int rc;
-            const hipStream_t stream = (hipStream_t)stream_main;
             switch (o.kind) {
                 case OP_STEM1:
-                    if (in.kind == FrameIn::DEPTH)
-                        rc = ec_stem_conv1_depth((const float*)rgb + (size_t)b0 * rgb_stride, in.scale, in.shift, in.stem_w9,
-                                                 h->bias + o.b_off, buf(o.dst), nb, o.H, o.W, o.Cout, stream);
-                    else if (u8)
-                        rc = ec_stem_conv1_u8((const uint8_t*)rgb + (size_t)b0 * rgb_stride, mean3, std3, h->stem_w,
-                                              h->bias + o.b_off, buf(o.dst), nb, o.H, o.W, o.Cout, stream);
-                    else
-                        rc = ec_stem_conv1((const float*)rgb + (size_t)b0 * rgb_stride, h->stem_w, h->bias + o.b_off,
-                                           buf(o.dst), nb, o.H, o.W, o.Cout, stream);
-                    break;
-                case OP_STEM7:
-                    rc = ec_stem7_pool(u8 ? (const void*)((const uint8_t*)rgb + (size_t)b0 * rgb_stride)
-                                          : (const void*)((const float*)rgb + (size_t)b0 * rgb_stride),
-                                       u8 ? 1 : 0, mean3, std3, h->stem_w, h->bias + o.b_off, buf(o.dst), nb, o.H, o.W, stream);
-                    break;
-                case OP_POOL:
-                    if (o.pool_of && pooled_emitted) { pooled_emitted = false; rc = EC_OK; break; }
-                    if (o.ldo) rc = ec_avgpool2_bf16_ld(buf(o.src), (uint16_t*)buf(o.dst) + o.ocol, nb, o.H, o.W, o.Cin, o.ldo, stream);
-                    else
-                    rc = ec_avgpool2_bf16(buf(o.src), buf(o.dst), nb, o.H, o.W, o.Cin, stream);
-                    break;
-                case OP_PAIR:
-                    if (o.dst3 >= 0) {
-                        // (the full-resolution block output is dead here: the next block reads dst2 and dst3 only)
-                        rc = ec_conv1x1_pair_pool_bf16(buf(o.src), h->w + o.w_off, h->bias + o.b_off, buf(o.res), nullptr,
-                                                       buf(o.dst3), h->w + o.w2_off, h->bias + o.b2_off, buf(o.dst2), nb, o.H,
-                                                       o.W, o.Cin, o.Cout, o.N2, stream);
-                        break;
-                    }
-                    rc = ec_conv1x1_pair_bf16(buf(o.src), h->w + o.w_off, h->bias + o.b_off,
-                                              o.src1 >= 0 ? buf(o.src1) : nullptr, o.src1 >= 0 ? h->w + o.w1_off : nullptr,
-                                              o.src1 >= 0 ? h->bias + o.b1_off : nullptr, o.res >= 0 ? buf(o.res) : nullptr,
-                                              buf(o.dst), h->w + o.w2_off, h->bias + o.b2_off, buf(o.dst2),
-                                              (long)nb * o.H * o.W, o.Cin, o.Cout, o.N2, stream);
-                    if (rc == EC_ERR_SHAPE && o.src1 < 0) {   // e.g. an odd number of 28x28 frames: the two convs separately
-                        rc = ec_conv_bf16(buf(o.src), h->w + o.w_off, h->bias + o.b_off, o.res >= 0 ? buf(o.res) : nullptr,
-                                          buf(o.dst), nb, o.H, o.W, o.Cin, o.Cout, 1, 0, EC_ACT_RELU, stream);
-                        if (rc == EC_OK)
-                            rc = ec_conv_bf16(buf(o.dst), h->w + o.w2_off, h->bias + o.b2_off, nullptr, buf(o.dst2), nb, o.H,
-                                              o.W, o.Cout, o.N2, 1, 0, EC_ACT_RELU, stream);
-                    }
-                    break;
-                case OP_BNECK:
-                    if (nb >= ec_config().rn50_bneck && o.wc1_off >= 0)
-                        rc = ec_bneck_conv123_bf16(buf(o.res), h->wbneck + o.w2_off, h->bias + o.bc1_off, h->bias + o.b_off, h->bias + o.b1_off,
-                                                   buf(o.dst), nb, o.H, o.W, o.Cin, stream);
-                    else if (nb >= ec_config().rn50_bneck)
-                        rc = ec_bneck_conv23_bf16(buf(o.src), h->wbneck + o.w2_off, h->bias + o.b_off, h->bias + o.b1_off,
-                                                  buf(o.res), buf(o.dst), nb, o.H, o.W, o.Cin, stream);
-                    else {   // small launches: the convs separately (buffer 1 = conv1's, buffer 2 = conv2's output, as in the unfused plan)
-                        if (o.wc1_off >= 0) {
-                            rc = ec_conv_bf16(buf(o.res), h->w + o.wc1_off, h->bias + o.bc1_off, nullptr, buf(o.src), nb, o.H, o.W,
-                                                 o.Cout, o.Cin, 1, 0, EC_ACT_RELU, stream);
-                            if (rc != EC_OK) return rc;
-                        }
-                        // ... conv2 on the image-resident K-split kernel while its (image, slice) workgroups fit one round
-                        if (ec_config().rn50_img3 && nb * 8 <= 256)
-                            rc = ec_conv3x3_img_bf16(buf(o.src), h->wbneck + o.wimg_off, h->bias + o.b_off, buf(2), nb, o.H, o.W, o.Cin, 0, stream);
-                        else
-                        rc = ec_conv_bf16(buf(o.src), h->w + o.w_off, h->bias + o.b_off, nullptr, buf(2), nb, o.H, o.W,
-                                             o.Cin, o.Cin, 3, 0, EC_ACT_RELU, stream);
-                        if (rc == EC_OK)
-                            rc = ec_conv_bf16(buf(2), h->w + o.w1_off, h->bias + o.b1_off, buf(o.res), buf(o.dst), nb, o.H,
-                                                 o.W, o.Cin, o.Cout, 1, 0, EC_ACT_RELU, stream);
-                    }
-                    break;
-                case OP_BTAIL: {
-                    // the one-launch tail where it measured faster than the two launches (profiles/basic_tail_ab.txt): layer2.0
-                    // at every frame count, layer3.0 up to 32 frames.  Deeper-K / larger launches: the downsample conv into
-                    // buffer 3, then conv2 with it as the residual (the 8-wave and ring instances of conv_igemm win there).
-                    const int planes = o.N2 / 9, inplanes = o.Cin - o.N2;
-                    if (planes <= 128 || (planes <= 256 && nb <= 32)) {
-                        rc = ec_basic_tail_s2_bf16(buf(o.src), buf(o.src1), h->wbneck + o.wcat_off, h->bias_cat + o.bcat_off, buf(o.dst), nb,
-                                                   o.H, o.W, planes, inplanes, o.Cout, stream);
-                        break;
-                    }
-                    rc = ec_conv_bf16_s2(buf(o.src1), h->w + o.w1_off, h->bias + o.b1_off, nullptr, buf(3), nb, 2 * o.H, 2 * o.W, inplanes,
-                                         o.Cout, 1, EC_ACT_NONE, stream);
-                    if (rc == EC_OK)
-                        rc = ec_conv_bf16(buf(o.src), h->w + o.w_off, h->bias + o.b_off, buf(3), buf(o.dst), nb, o.H, o.W, planes, o.Cout,
-                                          3, 0, EC_ACT_RELU, stream);
-                    break;
-                }
-                default:
-                    if (o.stride == 2) {
-                        rc = ec_conv_bf16_s2(buf(o.src), h->w + o.w_off, h->bias + o.b_off, o.res >= 0 ? buf(o.res) : nullptr, buf(o.dst),
-                                             nb, o.H, o.W, o.Cin, o.Cout, o.ks, o.act, stream);
-                        break;
-                    }
-                    if (o.wimg_off >= 0 && o.kind == OP_CONV && nb <= (o.pool ? 16 : 64)) {   // 7x7x512 3x3 convs of small launches (two rounds of
-                        // workgroups at most); layer4.0's pooled 14x14x512 conv2 (two channel chunks, 16 slices per image: one round of workgroups) up to 16 frames -- at 32 it ties with conv_igemm (47.6 vs 46.6 us)
-                        rc = ec_conv3x3_img_bf16_ld(buf(o.src), h->wbneck + o.wimg_off, h->bias + o.b_off, (uint16_t*)buf(o.dst) + o.ocol, nb, o.H, o.W,
-                                                    o.Cin, o.pool, o.ldo ? o.ldo : o.Cin, stream);
-                        break;
-                    }
-                    if (o.wcat_off >= 0) {   // conv3 | downsample conv over the concatenated K axis
-                        rc = ec_conv_bf16(buf(o.src), h->wbneck + o.wcat_off, h->bias_cat + o.bcat_off, nullptr, buf(o.dst), nb, o.H, o.W,
-                                          o.Cin, o.Cout, 1, 0, o.act, stream);
-                        break;
-                    }
-                    if (o.pdst >= 0) {
-                        rc = ec_conv1x1_regw_pool(buf(o.src), h->w + o.w_off, h->bias + o.b_off, buf(o.res), buf(o.dst),
-                                                  (uint16_t*)buf(o.pdst) + o.pcol, nb, o.H, o.W, o.Cin, o.Cout, o.act, o.pld, stream);
-                        if (rc == EC_OK) { pooled_emitted = true; break; }
-                        if (rc != EC_ERR_SHAPE) return rc;
-                    }
-                    rc = ec_conv_bf16_ld(buf(o.src), h->w + o.w_off, h->bias + o.b_off, o.res >= 0 ? buf(o.res) : nullptr,
-                                         (uint16_t*)buf(o.dst) + o.ocol, nb, o.H, o.W, o.Cin, o.Cout, o.ks, o.pool, o.act,
-                                         o.ldo ? o.ldo : o.Cout, stream);
+                case OP_STEM7: rc = run_stem(r, o); break;
+                case OP_POOL: rc = run_pool(r, o); break;
+                case OP_PAIR: rc = run_pair(r, o); break;
+                case OP_BNECK: rc = run_bneck(r, o); break;
+                case OP_BTAIL: rc = run_btail(r, o); break;
+                case OP_CAT: rc = run_cat(r, o); break;
+                case OP_CONV_POOLOUT: rc = run_conv_poolout(r, o); break;
+                default: rc = run_conv(r, o.c);
             }
             if (rc != EC_OK) return rc;
         }
@@ -652,3 +632,22 @@ int rn50_run(const ec_rn50_t* h, const FrameIn& in, int batch, void* workspace, 
     return EC_OK;
 }
 }  // namespace
+
+extern "C" int ec_rn50_forward(const ec_rn50_t* h, const float* rgb, int batch, void* workspace, size_t ws_bytes,
+                               void* feat, int chunk, ec_stream_t stream) {
+    return rn50_run(h, FrameIn{FrameIn::F32, rgb, nullptr, nullptr, 1.f, 0.f, nullptr}, batch, workspace, ws_bytes, feat, chunk, stream);
+}
+
+extern "C" int ec_rn50_forward_u8(const ec_rn50_t* h, const uint8_t* rgb_u8, const float* h_mean3, const float* h_std3, int batch,
+                                  void* workspace, size_t ws_bytes, void* feat, int chunk, ec_stream_t stream) {
+    if (!h_mean3 || !h_std3) return EC_ERR_ARG;
+    return rn50_run(h, FrameIn{FrameIn::U8, rgb_u8, h_mean3, h_std3, 1.f, 0.f, nullptr}, batch, workspace, ws_bytes, feat, chunk, stream);
+}
+
+// The depth tower of the RGB-D agent: the same plan, OP_STEM1 on the one-channel kernel (stem_depth.hip).  The handle stays
+// pointer-only: the folded stem weights come with the call.
+extern "C" int ec_rn50_forward_depth(const ec_rn50_t* h, const float* depth, float scale, float shift, const float* stem_w9,
+                                     int batch, void* workspace, size_t ws_bytes, void* feat, int chunk, ec_stream_t stream) {
+    if (!stem_w9) return EC_ERR_ARG;
+    return rn50_run(h, FrameIn{FrameIn::DEPTH, depth, nullptr, nullptr, scale, shift, stem_w9}, batch, workspace, ws_bytes, feat, chunk, stream);
+}

@@ -10,9 +10,11 @@ whole trunk forwards, under every dispatch switch setting (CPU only: tools/launc
                                          sequence `base` with the launches at the positions in `set` replaced); per setting the
                                          sequence index of each case -- in full for `default`, only where it differs for the others
 
-The committed table was written by the library of commit 6f7d5da, the commit BEFORE the host side of csrc/conv_igemm.hip was
-rebuilt around one ConvArgs builder, one route function and one launcher; tests/test_conv_routes.py holds every later build to
-it, launch for launch.  The library reads its switches once per process: one recorder process per setting."""
+The committed table was written by the library of commit d571d96, the commit BEFORE the host side of csrc/rn50.hip (the trunk
+executor's plan builder and runner) was rebuilt around block forms, op parts and one route function per op kind; every
+(setting, case) pair of the table before it (written by commit 6f7d5da, the commit before the host side of csrc/conv_igemm.hip
+was rebuilt) decodes to the same launches in this one.  tests/test_conv_routes.py holds every later build to it, launch for
+launch.  The library reads its switches once per process: one recorder process per setting."""
 import json
 import os
 import subprocess
@@ -21,7 +23,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 GOLDEN = os.path.join(HERE, "conv_routes_golden.json")
-PARENT_COMMIT = "6f7d5da"
+PARENT_COMMIT = "d571d96"
 ENGINE_MIN_TILES = 50          # what clip_preprocessors.py sets on a worker's two encoder handles
 
 SETTINGS = {
@@ -36,6 +38,12 @@ SETTINGS = {
     "min_tiles50": {"EC_CONV8_MIN_TILES": "50"},
     "vit_wide0": {"EC_VIT_WIDE": "0"}, "vit_wide2": {"EC_VIT_WIDE": "2"},
     "vit_bm192_0": {"EC_VIT_BM192": "0"},
+    # the trunk plan's switches (csrc/rn50.hip): each alone, the fully plain plan, the bottleneck fusion without both of its parts
+    "fuse0": {"EC_RN50_FUSE": "0"}, "bneck0": {"EC_RN50_BNECK": "0"}, "bneck2": {"EC_RN50_BNECK": "2"},
+    "bneck3_0": {"EC_RN50_BNECK3": "0"}, "img3_0": {"EC_RN50_IMG3": "0"}, "dscat0": {"EC_RN50_DSCAT": "0"},
+    "poolout0": {"EC_RN50_POOLOUT": "0"},
+    "plain": {"EC_RN50_FUSE": "0", "EC_RN50_DSCAT": "0", "EC_RN50_BNECK": "0"},
+    "bneck3_0_img3_0": {"EC_RN50_BNECK3": "0", "EC_RN50_IMG3": "0"},
 }
 
 # Instance names as the test writes them: 8-wave kernel c8<BN, KS, POOL, ABL, X3, S2, BM, XP>, 4-wave kernel
@@ -149,7 +157,25 @@ EXTRA = ["conv 64 28 28 128 512 1 0 1 1 0", "conv 64 28 28 512 256 1 0 1 0 0", "
          "s2 8 14 14 64 64 1 2 0", "gemm 100 64 4 0 0", "x3 100 64 64 0"]
 FRAMES = [1, 32, 64, 128, 256]
 TRUNKS = ["trunk %s %d %d" % (k, f, m) for k in ("clip50", "tv50", "tv18", "vitb32") for f in FRAMES for m in (0, ENGINE_MIN_TILES)]
-CASES = list(dict.fromkeys([c for _s, _r, c, _k in EXPECT] + EXTRA + TRUNKS))
+
+
+def tower(kind, layers, frames, width=64, res=224, min_tiles=0, chunk=0, inp="f32"):
+    return "tower %s %d %d %d %d %d %d %d %d %d %s" % (kind, width, *layers, res, frames, min_tiles, chunk, inp)
+
+
+# Both sides of every route decision of the trunk executor (csrc/rn50.hip): an odd frame count (the layer-2 pair launch refuses
+# it: two convs), the image-resident 3x3 limits (16 pooled, 32 at 14x14x256, 64 at 7x7x512), the pooled-output conv3 (an even
+# count from 42 on), the fused bottleneck's 128 frames, the BasicBlock tail's 32; the engine's min-tiles, a ragged last chunk,
+# the u8 and depth stems (a 7x7-stem tower refuses depth frames: the return code is the record), RN50x16, the test-sized towers.
+L50, L18, L34, LX16, L1 = (3, 4, 6, 3), (2, 2, 2, 2), (3, 4, 6, 3), (6, 8, 18, 8), (1, 1, 1, 1)
+TOWERS = ([tower("clip", L50, f) for f in (3, 16, 17, 32, 33, 40, 42, 64, 65, 127, 128)] +
+          [tower("clip", L50, 128, min_tiles=ENGINE_MIN_TILES), tower("clip", L50, 5, chunk=2),
+           tower("clip", L50, 3, inp="u8"), tower("clip", L50, 3, inp="depth")] +
+          [tower("clip", LX16, f, width=96, res=384) for f in (2, 32)] +
+          [tower(k, L1, 2, res=64) for k in ("clip", "tvb", "tvbasic")] +
+          [tower("tvb", L50, 3), tower("tvb", L50, 33), tower("tvb", L50, 3, inp="depth")] +
+          [tower("tvbasic", l, f) for l in (L18, L34) for f in (3, 32, 33, 128)])
+CASES = list(dict.fromkeys([c for _s, _r, c, _k in EXPECT] + EXTRA + TRUNKS + TOWERS))
 
 # conv_igemm instances that only a call the recorder cannot make reaches (library-internal C++ entry points): instance -> that call
 UNRECORDED = {

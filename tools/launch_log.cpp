@@ -12,6 +12,11 @@
 //   gemm  M N K act res                             ec_gemm_bf16
 //   x3    M N K act                                 ec_gemm_bf16a_x3
 //   trunk clip50|tv50|tv18|vitb32 frames min_tiles  create + ec_*_set_conv8_min_tiles + one forward + destroy
+//   tower clip|tvb|tvbasic width l1 l2 l3 l4 res frames min_tiles chunk f32|u8|depth
+//                                                   the same for an explicit ResNet architecture (CLIP tower, torchvision
+//                                                   Bottleneck / BasicBlock tower; the torchvision towers have width 64) through
+//                                                   ec_rn50_forward / _u8 / _depth; `P <ec_rn50_num_ops> <ec_rn50_plan_hash>`
+//                                                   comes before its launches
 //   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse
 //                                                   create + ec_policy_workspace_bytes + ec_policy_forward2 (goal_in > 0:
 //                                                   ec_policy_forward_vec) + destroy; mode 0 = EC_POLICY_INFER, 1 = _LEARN;
@@ -98,10 +103,10 @@ static F sym(const char* name) {
 }
 
 // weight / bias element counts of the Bottleneck (expansion 4) and BasicBlock (expansion 1) layers, in the order ec_amd.h documents
-static void resnet_counts(const int* layers, bool basic, size_t& nw, size_t& nb) {
-    size_t in = 64;
+static void resnet_counts(const int* layers, bool basic, size_t& nw, size_t& nb, size_t width = 64) {
+    size_t in = width;
     for (int l = 0; l < 4; ++l) {
-        const size_t p = (size_t)64 << l, out = basic ? p : 4 * p;
+        const size_t p = width << l, out = basic ? p : 4 * p;
         for (int b = 0; b < layers[l]; ++b) {
             nw += basic ? p * 9 * in + p * 9 * p : p * in + p * 9 * p + out * p;
             nb += basic ? 2 * p : 2 * p + out;
@@ -142,6 +147,45 @@ static int run_trunk(const std::string& kind, int frames, int min_tiles) {
     sym<int (*)(P, int)>("ec_rn50_set_conv8_min_tiles")(h, min_tiles);
     const size_t ws = sym<size_t (*)(P, int)>("ec_rn50_workspace_bytes")(h, frames);
     rc = sym<int (*)(P, P, int, P, size_t, P, int, P)>("ec_rn50_forward")(h, rgb, frames, fake(ws), ws, out, 0, nullptr);
+    sym<void (*)(P)>("ec_rn50_destroy")(h);
+    return rc;
+}
+
+// v: width, the four layer counts, resolution, frames, min_tiles, chunk
+static int run_tower(const std::string& kind, const int* v, const std::string& input) {
+    typedef void* P;
+    const int width = v[0], *layers = v + 1, res = v[5], frames = v[6], min_tiles = v[7], chunk = v[8];
+    const bool clip = kind == "clip", basic = kind == "tvbasic";
+    if ((!clip && kind != "tvb" && !basic) || (!clip && width != 64) || width <= 0) return -100;
+    void* h = nullptr;
+    int rc;
+    const P w = fake(1u << 30), f = fake(1u << 28), stem = fake(1u << 20), rgb = fake(1u << 30), out = fake(1u << 30), w9 = fake(1u << 20);
+    size_t nw = 0, nb = 0;
+    resnet_counts(layers, basic, nw, nb, (size_t)width);
+    if (clip) {   // + stem conv2 [sc][9*sc], conv3 [width][9*sc] at the padded stem width sc; biases of stem conv1..3
+        const size_t sc = ((size_t)width / 2 + 31) / 32 * 32;
+        rc = sym<int (*)(P*, int, const int*, int, P, P, size_t, P, size_t)>("ec_rn50_create")(
+            &h, width, layers, res, stem, w, nw + sc * 9 * sc + (size_t)width * 9 * sc, f, nb + 2 * sc + (size_t)width);
+    } else {
+        rc = sym<int (*)(P*, const int*, int, P, P, size_t, P, size_t)>(basic ? "ec_tvresnet_basic_create" : "ec_rn50tv_create")(
+            &h, layers, res, stem, w, nw, f, nb + 64);
+    }
+    if (rc) return rc;
+    sym<int (*)(P, int)>("ec_rn50_set_conv8_min_tiles")(h, min_tiles);
+    printf("P %d %016llx\n", sym<int (*)(P)>("ec_rn50_num_ops")(h), (unsigned long long)sym<uint64_t (*)(P)>("ec_rn50_plan_hash")(h));
+    const size_t ws = sym<size_t (*)(P, int)>("ec_rn50_workspace_bytes")(h, frames);
+    const P wsp = fake(ws);
+    static const float mean3[3] = {0.485f, 0.456f, 0.406f}, std3[3] = {0.229f, 0.224f, 0.225f};   // read on the host by the u8 entry point
+    if (input == "f32")
+        rc = sym<int (*)(P, P, int, P, size_t, P, int, P)>("ec_rn50_forward")(h, rgb, frames, wsp, ws, out, chunk, nullptr);
+    else if (input == "u8")
+        rc = sym<int (*)(P, P, const float*, const float*, int, P, size_t, P, int, P)>("ec_rn50_forward_u8")(h, rgb, mean3, std3, frames, wsp, ws,
+                                                                                                            out, chunk, nullptr);
+    else if (input == "depth")
+        rc = sym<int (*)(P, P, float, float, P, int, P, size_t, P, int, P)>("ec_rn50_forward_depth")(h, rgb, 0.2f, -0.5f, w9, frames, wsp, ws, out,
+                                                                                                    chunk, nullptr);
+    else
+        rc = -100;
     sym<void (*)(P)>("ec_rn50_destroy")(h);
     return rc;
 }
@@ -191,10 +235,13 @@ int main(int argc, char** argv) {
         printf("C %s\n", line);
         int v[18] = {0}, n = 0, rc = -100;
         std::string kind;
-        if (cmd == "trunk") ss >> kind;
-        const int nmax = cmd == "policy" ? 18 : 10;
+        if (cmd == "trunk" || cmd == "tower") ss >> kind;
+        const int nmax = cmd == "policy" ? 18 : cmd == "tower" ? 9 : 10;
         while (n < nmax && ss >> v[n]) ++n;
-        if (cmd == "policy" && n == 18) {
+        std::string input;
+        if (cmd == "tower" && n == 9 && ss >> input) {
+            rc = run_tower(kind, v, input);
+        } else if (cmd == "policy" && n == 18) {
             rc = run_policy(v);
         } else if (cmd == "conv" && n == 10) {
             const P r = v[8] ? resb : nullptr;
