@@ -146,6 +146,12 @@ SIGNATURES = {
     "ec_clip_adam_scratch_doubles": (c_int, []),
     "ec_clip_adam_step": (c_int, [c_void_p] * 5 + [C.c_long, c_float, c_float, c_float, c_float, c_float, c_int,
                                   c_void_p]),
+    # imitation learning ([U] allenact losses/imitation.py, TeacherForcingDistr): expert cross-entropy, its normaliser, forcing
+    "ec_imitation_scratch_doubles": (c_int, []),
+    "ec_imitation_loss": (c_int, [c_void_p] * 7 + [C.c_long, c_int, c_float, c_float, c_int, c_void_p]),
+    "ec_expert_count": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ec_teacher_force": (c_int, [c_void_p] * 3 + [c_float] + [c_void_p] * 2 + [c_int, c_int, C.c_uint64, C.c_uint64, c_int,
+                                                                            c_void_p]),
 }
 
 

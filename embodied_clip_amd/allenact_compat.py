@@ -254,6 +254,9 @@ _PATCH_TARGETS = (
     ("projects.pointnav_baselines.models.point_nav_models", ("ResnetTensorPointNavActorCritic",)),
     ("allenact.algorithms.onpolicy_sync.losses.ppo", ("PPO",)),
     ("allenact.algorithms.onpolicy_sync.losses", ("PPO",)),
+    # imitation learning (the DAgger stages of readme_files/baselines_ithor_rearrangement.md; AllenAct's BC / DAgger configs)
+    ("allenact.algorithms.onpolicy_sync.losses.imitation", ("Imitation",)),
+    ("allenact.algorithms.onpolicy_sync.losses", ("Imitation",)),
     # the ImageNet baselines (objectnav_robothor_rgb_resnet{18,50}gru_ddppo: readme_files/imagenet_vs_objectnav.md,
     # baselines_robothor_objectnav.md:47)
     ("allenact.embodiedai.preprocessors.resnet", ("ResNetPreprocessor",)),
@@ -268,11 +271,12 @@ def install_into_allenact(verbose: bool = False) -> List[str]:
     from . import clip_preprocessors as cp
     from . import imagenet_preprocessors as ip
     from . import policy as pol
+    from . import imitation as il
     from . import ppo
     ours = {"ClipResNetPreprocessor": cp.ClipResNetPreprocessor, "ClipViTPreprocessor": cp.ClipViTPreprocessor,
             "ResnetTensorObjectNavActorCritic": pol.ResnetTensorObjectNavActorCritic,
             "ResnetTensorPointNavActorCritic": pol.ResnetTensorPointNavActorCritic, "PPO": ppo.PPO,
-            "ResNetPreprocessor": ip.ResNetPreprocessor}
+            "ResNetPreprocessor": ip.ResNetPreprocessor, "Imitation": il.Imitation}
     done = []
     for modname, attrs in _PATCH_TARGETS:
         try:

@@ -37,6 +37,7 @@ from .dist import (allreduce_flat, check_job_seed, collective_active, gather_act
 from .episodes import EpisodeTracker, NavEpisodeTracker, nav_env_tensors
 from .encoder import AttentionPool, ClipTextEncoder, ImageNetBasicTrunk, ImageNetRN50Trunk, RN50Trunk, ViTEmbedder
 from .policy import PolicyHandle
+from .imitation import imitation_loss_raw, imitation_scratch
 from .ppo import FlatAdam, linear_decay_lr, ppo_loss_raw
 
 # encoder name -> (blocks per layer, torchvision block type, trunk class) of the ImageNet-feature agents
@@ -52,7 +53,8 @@ class SyntheticEnv:
     random goal ids, episode resets w.p. 1/100, RoboTHOR-style rewards."""
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
-                 frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False):
+                 frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False, expert: bool = False,
+                 num_actions: int = 6):
         self.N, self.T = n_actors, T
         self.host = host
         # frames_u8: raw uint8 frames (what the simulator renders); normalisation is then fused into the stem kernel.
@@ -73,8 +75,14 @@ class SyntheticEnv:
         masks = torch.cat([torch.ones(1, n_actors, 1), syn.synthetic_masks(seed + 1, T, n_actors)], 0)
         self.masks = masks.reshape(T + 1, n_actors).to(device).contiguous()
         # goal_in > 0 (PointNav): float [T+1, N, goal_in] coordinate goals (distance, bearing) instead of int64 ids [T+1, N]
-        self.goals = (syn.synthetic_goal_vectors(seed + 2, (T + 1, n_actors), goal_in) if goal_in
-                      else syn.synthetic_goals(seed + 2, (T + 1, n_actors))).to(device).contiguous()
+        goals = (syn.synthetic_goal_vectors(seed + 2, (T + 1, n_actors), goal_in) if goal_in
+                 else syn.synthetic_goals(seed + 2, (T + 1, n_actors)))
+        self.goals = goals.to(device).contiguous()
+        if expert:
+            # imitation learning: the expert's action (a function of the goal) and whether it has one, [T+1, N] each, from a
+            # seed and a hash stream of their own (synthetic.synthetic_expert) -- nothing else the env builds changes
+            ea, em = syn.synthetic_expert(seed + 6, goals, num_actions)
+            self.expert_actions, self.expert_mask = ea.to(device).contiguous(), em.to(device).contiguous()
         self.rewards = syn.synthetic_rewards(seed + 3, masks[1:]).reshape(T, n_actors).to(device).contiguous()
         # success flag of the step that ends an episode: the +10 reward of synthetic_rewards (episode metrics / evaluation)
         self.success = ((self.rewards > 1) & (self.masks[1:] == 0)).to(torch.float32).contiguous()
@@ -112,8 +120,9 @@ class NavSyntheticEnv(SyntheticEnv):
     ``num_goals``, the number of goal ids (0 with coordinate goals)."""
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
-                 frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False):
-        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in, depth)
+                 frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False, expert: bool = False,
+                 num_actions: int = 6):
+        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in, depth, expert, num_actions)
         self.num_goals = 0 if goal_in else 12
         step_dist, start_dist, goal_dist = syn.synthetic_navigation(seed + 4, self.masks[1:], self.success)
         self.step_dist = step_dist.to(device).contiguous()
@@ -387,8 +396,19 @@ class Worker(_SlicedActor):
                  frames_host: bool = False, zeroshot: bool = False, text_sd=None, goal_tokens=None,
                  num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
                  overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False,
-                 nav_metrics: bool = False, depth: bool = False):
-        """``depth=True``: the RGB-D agent (readme_files/baselines_habitat.md:75; [U] a second ClipResNetPreprocessor on the
+                 nav_metrics: bool = False, depth: bool = False, loss: str = "ppo", il_weight: float = 1.0,
+                 teacher_forcing=None):
+        """``loss``: what a rollout is trained on -- "ppo" (GAE, then the PPO loss: the default), "imitation" (the expert
+        cross-entropy of [U] AllenAct's ``Imitation`` loss on the env's expert actions; no GAE launch) or "ppo+imitation"
+        (``ppo_total + il_weight * imitation``: the PPO call writes d(total)/d(hv), the imitation call adds its term).
+        ``il_weight`` is the imitation term's loss weight in both.  ``teacher_forcing``: None, or a callable of ``total_steps``
+        (``imitation.LinearDecay`` / ``StepwiseLinearDecay``) giving the probability p with which a step that has an expert
+        action TAKES it ([U] ``TeacherForcingDistr``; DAgger is a p that decays from 1): evaluated once per rollout, at the
+        rollout's first ``total_steps``; one small launch behind every sampling act step while p > 0, none otherwise.  With
+        the defaults nothing of this runs and the env builds no expert.  The imitation normaliser (the number of steps with an
+        expert action in a minibatch range) is rank-local, as the advantage normalisation is.
+
+        ``depth=True``: the RGB-D agent (readme_files/baselines_habitat.md:75; [U] a second ClipResNetPreprocessor on the
         depth sensor feeding ResnetDualTensorGoalEncoder): the env also serves one-channel depth frames, every slice's trunk
         runs twice per env step (RGB, then depth through the one-channel stem) into ``feat`` / ``feat2``, and the policy is
         ``PolicyHandle(dual=1)``.  Rollout feature storage doubles.  Only with ``encoder`` "rn50" / "rn50x16", goal ids and
@@ -416,6 +436,13 @@ class Worker(_SlicedActor):
         if nav_metrics and not track_episodes:
             raise ValueError("Worker(nav_metrics=True) needs track_episodes=True")
         self.nav_metrics = nav_metrics
+        if loss not in ("ppo", "imitation", "ppo+imitation"):
+            raise ValueError(f"Worker(loss={loss!r}): one of 'ppo', 'imitation', 'ppo+imitation'")
+        if teacher_forcing is not None and not callable(teacher_forcing):
+            raise ValueError("Worker(teacher_forcing=...): None or a callable of total_steps")
+        self.loss_mode, self.il_weight, self.teacher_forcing = loss, float(il_weight), teacher_forcing
+        self._ppo, self._il = loss != "imitation", loss != "ppo"
+        self._tf_p = 0.0                                    # this rollout's forcing probability (collect_rollout sets it)
         # sync_actions: the action-synchronous order of a real vectorised env ([U] VectorSampledTasks.step(actions)): every
         # env step the sampled actions of ALL actors are copied to the host and waited for before observe() serves the next
         # frames.  Default off: the synthetic env does not read the actions and the host issues ahead.
@@ -473,6 +500,8 @@ class Worker(_SlicedActor):
         self.sums = torch.zeros(4, dtype=torch.float64, device=d)
         env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
         dkw = dict(depth=True) if self.depth else {}
+        if self._il or self.teacher_forcing is not None:
+            dkw.update(expert=True, num_actions=self._num_actions)
         self.env = env_cls(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in, **dkw)
         if self.nav_metrics:      # per-category rows for goal ids; coordinate goals have no categories
             self.episodes = NavEpisodeTracker(N, d, num_categories=0 if self.goal_in else self.env.num_goals)
@@ -490,6 +519,12 @@ class Worker(_SlicedActor):
             sl.rec_ready.record()          # (torch creates the hipEvent_t at the first record: the library needs the handle)
             sl.sums = torch.zeros(4, dtype=torch.float64, device=d)
             sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = None
+            if self._il:      # the imitation loss's sums and partial-sum scratch: one per slice stream
+                sl.il_sums = torch.zeros(3, dtype=torch.float64, device=d)
+                sl.il_scratch = imitation_scratch(d)
+                sl.ex_a = sl.ex_m = None
+        if self._il:          # one normaliser per minibatch range (update() fills them once per rollout)
+            self._il_denoms = torch.zeros(self.num_mini_batch, dtype=torch.float64, device=d)
         self.seed = seed + 7919 * rank
         self.total_steps = 0
         self.iter = 0
@@ -512,6 +547,7 @@ class Worker(_SlicedActor):
                             self.hv_act[rs], h_out[rs], self.actions[t][rs], self.logp[t][rs], self.values[t][rs], self.seed,
                             self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t))
             sl.act_tables_valid = True
+            self._teacher_force_slice(sl, t)
             return
         self.policy.forward(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n,
                             sl.ws_act, hv=self.hv_act[rs], h_final=h_out[rs], for_backward=False,
@@ -521,13 +557,31 @@ class Worker(_SlicedActor):
             _lib.check(self.lib.ec_sample_actions(self.hv_act[rs].data_ptr(), self.actions[t][rs].data_ptr(),
                                                   self.logp[t][rs].data_ptr(), self.values[t][rs].data_ptr(), n, self.A,
                                                   self.seed, self.iter * (self.T + 1) + t, o, sp), "ec_sample_actions")
+            self._teacher_force_slice(sl, t)
         else:   # bootstrap value of the last observation; memory is NOT advanced
             self.values[t][rs].copy_(self.hv_act[rs, self.A])
+
+    def _teacher_force_slice(self, sl, t: int):
+        """[U] TeacherForcingDistr behind a sampling act step: with this rollout's probability p, a step that has an expert
+        action takes it (action and log-prob; ec_teacher_force) -- on the slice's stream, keyed like the sampler.  No launch
+        while p is 0."""
+        if self._tf_p <= 0.0:
+            return
+        rs = slice(sl.o, sl.o + sl.n)
+        _lib.check(self.lib.ec_teacher_force(self.hv_act[rs].data_ptr(), self.env.expert_actions[t][rs].data_ptr(),
+                                             self.env.expert_mask[t][rs].data_ptr(), self._tf_p,
+                                             self.actions[t][rs].data_ptr(), self.logp[t][rs].data_ptr(), sl.n, self.A,
+                                             self.seed, self.iter * (self.T + 1) + t, sl.o, _lib.stream_ptr()),
+                   "ec_teacher_force")
 
     @_lib.on_device
     def collect_rollout(self):
         T = self.T
         self.h_start.copy_(self.h)
+        if self.teacher_forcing is not None:      # p of this rollout: the schedule at the rollout's first total_steps
+            self._tf_p = float(self.teacher_forcing(self.total_steps))
+            if not 0.0 <= self._tf_p <= 1.0:
+                raise ValueError(f"teacher_forcing({self.total_steps}) = {self._tf_p}: a probability is expected")
         self._fork()
         if self.sync_actions:
             return self._collect_rollout_sync()
@@ -607,10 +661,11 @@ class Worker(_SlicedActor):
 
     @_lib.on_device
     def compute_returns(self):
-        _lib.check(self.lib.ec_gae(self.env.rewards.data_ptr(), self.values.data_ptr(), self.env.masks.data_ptr(),
-                                   self.returns.data_ptr(), self.adv.data_ptr(), self.nadv.data_ptr(),
-                                   self.stats.data_ptr(), self.T, self.N, self.gamma, self.tau, 1e-5,
-                                   _lib.stream_ptr()), "ec_gae")
+        if self._ppo:         # (pure imitation reads neither returns nor advantages: no GAE launch)
+            _lib.check(self.lib.ec_gae(self.env.rewards.data_ptr(), self.values.data_ptr(), self.env.masks.data_ptr(),
+                                       self.returns.data_ptr(), self.adv.data_ptr(), self.nadv.data_ptr(),
+                                       self.stats.data_ptr(), self.T, self.N, self.gamma, self.tau, 1e-5,
+                                       _lib.stream_ptr()), "ec_gae")
         if self.nav_metrics:
             self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None),
                                  *nav_env_tensors(self.env, self.episodes.C > 0))
@@ -629,6 +684,8 @@ class Worker(_SlicedActor):
             sl.masks = c(self.env.masks)
             sl.actions, sl.logp, sl.old_v = c(self.actions), c(self.logp), c(self.values)
             sl.ret, sl.nadv = c(self.returns), c(self.nadv)
+            if self._il:
+                sl.ex_a, sl.ex_m = c(self.env.expert_actions), c(self.env.expert_mask)
 
     def minibatch_ranges(self):
         """[U] allenact ``RolloutStorage.recurrent_generator``: the samplers (actors) are cut at
@@ -667,6 +724,24 @@ class Worker(_SlicedActor):
         return (fm.view(T * m, self.S * self.S, self.C), goal, c(sl.masks), c(sl.actions), c(sl.logp), c(sl.old_v),
                 c(sl.ret), c(sl.nadv))
 
+    def _gather_expert(self, sl, a: int, b: int):
+        """The expert actions and mask of the batch ``_gather_part(sl, a, b)`` returns, [T * (b - a)] each."""
+        if a == 0 and b == sl.n:
+            return sl.ex_a, sl.ex_m
+        c = lambda x: x.view(self.T, sl.n)[:, a:b].reshape(-1).contiguous()
+        return c(sl.ex_a), c(sl.ex_m)
+
+    def _expert_counts(self) -> Dict[tuple, torch.Tensor]:
+        """The imitation normaliser of every minibatch range -- the number of this rollout's steps that have an expert action
+        among the range's samplers (rank-local) -- once per rollout, on the current stream: {(s0, s1): float64 [1] view}."""
+        inds = minibatch_bounds(self.N, self.num_mini_batch)
+        out = {}
+        for j, (s0, s1) in enumerate(zip(inds[:-1], inds[1:])):
+            out[(s0, s1)] = self._il_denoms[j:j + 1]
+            _lib.check(self.lib.ec_expert_count(self.env.expert_mask.data_ptr(), self.T, self.N, s0, s1,
+                                                out[(s0, s1)].data_ptr(), _lib.stream_ptr()), "ec_expert_count")
+        return out
+
     def _gather_feat2(self, sl, a: int, b: int):
         """The depth features of the batch ``_gather_part(sl, a, b)`` returns (``depth=True``; else None): the whole slice in
         place, a partial range through a staging buffer of its own, sized as ``feat_mb``."""
@@ -703,6 +778,7 @@ class Worker(_SlicedActor):
         T = self.T
         collective = collective_active(self.world, self.force_allreduce)
         self._gather_slice_batches()
+        il_denoms = self._expert_counts() if self._il else None      # (the _fork() below orders the slice streams behind it)
         for _ in range(self.update_repeats):
             for (s0, s1, nmb_global) in self.minibatch_ranges():
                 # the minibatch's actors, slice by slice (each part on its slice's stream)
@@ -730,8 +806,16 @@ class Worker(_SlicedActor):
                         #  the step kernels wait for CUs the GEMM workgroups hold)
                         self.policy.forward(self.params, feat, goal, self.h_start[sl.o + a:sl.o + b], masks, T, m,
                                             sl.ws_learn, hv=hv, feat2=feat2)
-                        ppo_loss_raw(hv, actions, logp, old_v, ret, nadv, self.A, grad_scale=grad_scale, dhv=dhv,
-                                     sums=sl.sums)
+                        if self._ppo:
+                            ppo_loss_raw(hv, actions, logp, old_v, ret, nadv, self.A, grad_scale=grad_scale, dhv=dhv,
+                                         sums=sl.sums)
+                        if self._il:
+                            # the kernel divides by the RANGE's normaliser (shared by the parts), so only local / global
+                            # minibatch size is left to apply; after a PPO call the term is added to its dhv
+                            ex_a, ex_m = self._gather_expert(sl, a, b)
+                            imitation_loss_raw(hv, ex_a, ex_m, self.A, weight=self.il_weight,
+                                               grad_scale=(s1 - s0) / nmb_global, denom=il_denoms[(s0, s1)], dhv=dhv,
+                                               sums=sl.il_sums, scratch=sl.il_scratch, accumulate=self._ppo)
                         sl.grads.zero_()
                         self.policy.backward(self.params, feat, masks, T, m, sl.ws_learn, dhv, None, sl.grads, feat2=feat2,
                                              recurrent_ready=sl.rec_ready if early else None)
@@ -818,10 +902,18 @@ class Worker(_SlicedActor):
 
     def loss_info(self) -> Dict[str, float]:
         parts = getattr(self, "_loss_parts", None) or [(sl, sl.n) for sl in self.slices]   # the last minibatch
-        tot = sum(sl.sums for sl, _ in parts)
-        s = (tot / (self.T * sum(m for _, m in parts))).tolist()
-        return {"action": s[0], "value": s[1], "entropy": s[2], "ratio": s[3],
-                "ppo_total": s[0] + 0.5 * s[1] + 0.01 * s[2], "grad_norm": self.opt.grad_norm()}
+        info = {}
+        if self._ppo:
+            tot = sum(sl.sums for sl, _ in parts)
+            s = (tot / (self.T * sum(m for _, m in parts))).tolist()
+            info.update({"action": s[0], "value": s[1], "entropy": s[2], "ratio": s[3],
+                         "ppo_total": s[0] + 0.5 * s[1] + 0.01 * s[2]})
+        if self._il:          # the parts' sums over the steps that have an expert action; divided here, on the host
+            nll, cnt, agree = sum(sl.il_sums for sl, _ in parts).tolist()
+            info.update({"expert_cross_entropy": nll / max(cnt, 1.0), "expert_agreement": agree / max(cnt, 1.0),
+                         "expert_steps": cnt})
+        info["grad_norm"] = self.opt.grad_norm()
+        return info
 
 
 class _NullCtx:

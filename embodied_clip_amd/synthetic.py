@@ -482,6 +482,27 @@ def synthetic_goal_vectors(seed: int, shape, goal_in: int = 2, rho_max: float = 
     return torch.from_numpy(v.astype(np.float32)).reshape(tuple(shape) + (goal_in,))
 
 
+def synthetic_expert(seed: int, goals: torch.Tensor, num_actions: int, p_fail: float = 0.05):
+    """A synthetic expert for imitation learning: ``(expert_actions int64, expert_mask fp32)``, both with the goals' leading
+    shape (what [U] AllenAct's ``ExpertActionSensor`` hands over as ``expert_action[..., 0]`` and ``[..., 1]``).  The action is
+    a function of the goal ALONE, so a policy can learn it: ``goal % num_actions`` for goal ids (int64 ``shape``), the sector
+    of the bearing for coordinate goals (float ``shape + (goal_in,)``; component 1 -- component 0 when there is only one --
+    in [-pi, pi), ``num_actions`` equal sectors).  The mask is 0 w.p. ``p_fail`` (the expert has no action to offer), on hash
+    stream 29, which no other generator of this module draws from."""
+    g = goals.detach().cpu()
+    if g.dtype.is_floating_point:
+        shape = tuple(g.shape[:-1])
+        b = g[..., 1 if g.shape[-1] > 1 else 0].to(torch.float64).numpy()
+        act = np.clip(np.floor((b + np.pi) / (2.0 * np.pi) * num_actions), 0, num_actions - 1).astype(np.int64)
+    else:
+        shape = tuple(g.shape)
+        act = (g.to(torch.int64).numpy() % num_actions).astype(np.int64)
+    n = int(np.prod(shape))
+    u = hash_uniform(seed, n, stream=29)
+    mask = (u >= p_fail).astype(np.float32).reshape(shape)
+    return torch.from_numpy(np.ascontiguousarray(act.reshape(shape))), torch.from_numpy(mask)
+
+
 def synthetic_masks(seed: int, T: int, N: int, p_reset: float = 0.01) -> torch.Tensor:
     """masks[t,n,0] = 0 with prob p_reset (episode reset), else 1. fp32 [T,N,1]."""
     u = hash_uniform(seed, T * N, stream=13)

@@ -580,6 +580,42 @@ int ec_clip_adam_step(float* params, const float* grads, float* exp_avg, float* 
                       ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Imitation learning ([U] allenact onpolicy_sync/losses/imitation.py Imitation.loss, the `expert_action` branch for a
+ * CategoricalDistr; base_abstractions/distributions.py TeacherForcingDistr).  The training method of the reference's
+ * rearrangement baselines (readme_files/baselines_ithor_rearrangement.md: DAgger) and of AllenAct's behaviour-cloning /
+ * DAgger configurations of the ObjectNav and PointNav agents.  Restated from the published source; parity unpinned.
+ * ---------------------------------------------------------------------- */
+/* Expert cross-entropy, forward + analytic backward (restates Imitation.loss: -(mask * log_prob(expert)).sum() /
+ * mask.sum().clamp(min=1)).  hv [B,A+1] (logits, value); expert_actions int64 [B]; expert_mask f32 [B]; 1 <= A <= 256.
+ *   loss = -sum_b mask[b] * log_softmax(hv[b,:A])[e_b] / max(D, 1),  D = *denom (device memory) or, with denom NULL, this
+ *   call's own sum of the mask (every block sums the whole mask in one order: no grid-wide synchronisation).
+ *   sums3 (doubles, out) = {sum mask * (-logp_e), sum mask, sum mask * [first maximal logit of the row == e_b]} over this
+ *   call's rows; the caller divides.
+ *   dhv[b,k] = grad_scale * weight * mask[b] * (softmax_k - [k == e_b]) / max(D, 1).
+ * accumulate == 0: dhv is written -- rows with mask 0 and the value column as zeros.  accumulate != 0: the term is ADDED to
+ * dhv; rows with mask 0 and the value column are left alone ("PPO + imitation": ec_ppo_loss_ex first, then this call).
+ * A row with mask 0 never reads its expert id; a row with mask != 0 and an id outside [0, A) makes sums3[0] NaN
+ * (ec_ppo_loss_ex's rule).  A <= 16: one thread per row; above: one 64-lane wave per row.  Contiguous row chunks over several
+ * workgroups; the blocks' partial sums go to scratch (ec_imitation_scratch_doubles() doubles, owned by one stream at a
+ * time) and are folded in block order by the block that draws the last integer ticket -- no floating-point atomics: two
+ * runs give the same bits, and with a shared denom a row's dhv does not depend on how the rows are split over calls.
+ * Checked before any HIP call: NULL (but denom) -> EC_ERR_ARG; B <= 0 or A outside [1, 256] -> EC_ERR_SHAPE. */
+int ec_imitation_scratch_doubles(void);
+int ec_imitation_loss(const float* hv, const int64_t* expert_actions, const float* expert_mask, const double* denom,
+                      float* dhv, double* sums3, double* scratch, long B, int A, float weight, float grad_scale,
+                      int accumulate, ec_stream_t stream);
+/* out[0] = sum over t < T, n0 <= n < n1 of expert_mask[t,n] (f32 [T,N]) in a fixed order: the normaliser mask.sum() of
+ * Imitation.loss for the minibatch of samplers [n0, n1), computed once per rollout and shared by the calls that split it. */
+int ec_expert_count(const float* expert_mask, int T, int N, int n0, int n1, double* out, ec_stream_t stream);
+/* Teacher forcing after an act step (restates TeacherForcingDistr.sample / log_prob): actor n draws a uniform keyed by
+ * (seed, step, first_actor + n) -- ec_sample_actions' key on a stream constant of its own, so it is not the sampler's draw --
+ * and where expert_mask[n] != 0 and u < p: actions[n] = expert_actions[n], logp[n] = log_softmax(hv[n,:A])[expert].  Every
+ * other row keeps what the act step wrote.  Slice-invariant like ec_sample_actions.  p outside [0, 1] -> EC_ERR_ARG; p == 0
+ * launches nothing.  A forced id outside [0, A) gives logp NaN. */
+int ec_teacher_force(const float* hv, const int64_t* expert_actions, const float* expert_mask, float p, int64_t* actions,
+                     float* logp, int N, int A, uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * CLIP VisionTransformer embedder == [U] allenact ClipViTEmbedder.forward over
  * [U] openai/CLIP VisionTransformer: patch-embed, class +
  * positional embedding, ln_pre, then `layers_run` ResidualAttentionBlocks
