@@ -11,6 +11,12 @@
 //   s2    B H W Cin Cout ksize act res              ec_conv_bf16_s2
 //   gemm  M N K act res                             ec_gemm_bf16
 //   x3    M N K act                                 ec_gemm_bf16a_x3
+//   pair  M K0 N N2 two res                         ec_conv1x1_pair_bf16 (two: the second product a1 . w1^T + b1; res: the residual)
+//   pairpool B H W K0 N N2 y                        ec_conv1x1_pair_pool_bf16 (y = 0: y = NULL, not stored)
+//   img   B H C pool ldo                            ec_conv3x3_img_pack + ec_conv3x3_img_bf16_ld (ldo = 0: dense)
+//   bneck23  B H W C                                ec_bneck_pack_weights + ec_bneck_conv23_bf16
+//   bneck123 B H W C                                ec_bneck3_pack_weights + ec_bneck_conv123_bf16
+//   tail  B Ho Wo planes inplanes Cout              ec_basic_tail_s2_bf16
 //   trunk clip50|tv50|tv18|vitb32 frames min_tiles  create + ec_*_set_conv8_min_tiles + one forward + destroy
 //   tower clip|tvb|tvbasic width l1 l2 l3 l4 res frames min_tiles chunk f32|u8|depth
 //                                                   the same for an explicit ResNet architecture (CLIP tower, torchvision
@@ -259,6 +265,31 @@ int main(int argc, char** argv) {
                                                                                    v[2], v[3], nullptr);
         } else if (cmd == "x3" && n == 4) {
             rc = sym<int (*)(P, P, P, P, long, int, int, int, P)>("ec_gemm_bf16a_x3")(in, w, bias, out, (long)v[0], v[1], v[2], v[3], nullptr);
+        } else if (cmd == "pair" && n == 6) {
+            rc = sym<int (*)(P, P, P, P, P, P, P, P, P, P, P, long, int, int, int, P)>("ec_conv1x1_pair_bf16")(
+                in, w, bias, v[4] ? in : nullptr, v[4] ? w : nullptr, v[4] ? bias : nullptr, v[5] ? resb : nullptr, out, w, bias, out, (long)v[0],
+                v[1], v[2], v[3], nullptr);
+        } else if (cmd == "pairpool" && n == 7) {
+            rc = sym<int (*)(P, P, P, P, P, P, P, P, P, int, int, int, int, int, int, P)>("ec_conv1x1_pair_pool_bf16")(
+                in, w, bias, resb, v[6] ? out : nullptr, out, w, bias, out, v[0], v[1], v[2], v[3], v[4], v[5], nullptr);
+        } else if (cmd == "img" && n == 5) {
+            rc = sym<int (*)(P, P, int, P)>("ec_conv3x3_img_pack")(w, w, v[2], nullptr);
+            if (!rc)
+                rc = sym<int (*)(P, P, P, P, int, int, int, int, int, int, P)>("ec_conv3x3_img_bf16_ld")(in, w, bias, out, v[0], v[1], v[1], v[2], v[3],
+                                                                                                       v[4] ? v[4] : v[2], nullptr);
+        } else if (cmd == "bneck23" && n == 4) {
+            rc = sym<int (*)(P, P, P, int, P)>("ec_bneck_pack_weights")(w, w, w, v[3], nullptr);
+            if (!rc)
+                rc = sym<int (*)(P, P, P, P, P, P, int, int, int, int, P)>("ec_bneck_conv23_bf16")(in, w, bias, bias, resb, out, v[0], v[1], v[2], v[3],
+                                                                                                 nullptr);
+        } else if (cmd == "bneck123" && n == 4) {
+            rc = sym<int (*)(P, P, P, P, int, P)>("ec_bneck3_pack_weights")(w, w, w, w, v[3], nullptr);
+            if (!rc)
+                rc = sym<int (*)(P, P, P, P, P, P, int, int, int, int, P)>("ec_bneck_conv123_bf16")(in, w, bias, bias, bias, out, v[0], v[1], v[2], v[3],
+                                                                                                  nullptr);
+        } else if (cmd == "tail" && n == 6) {
+            rc = sym<int (*)(P, P, P, P, P, int, int, int, int, int, int, P)>("ec_basic_tail_s2_bf16")(in, resb, w, bias, out, v[0], v[1], v[2], v[3],
+                                                                                                     v[4], v[5], nullptr);
         } else if (cmd == "trunk" && n == 2) {
             rc = run_trunk(kind, v[0], v[1]);
         } else {
