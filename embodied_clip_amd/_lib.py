@@ -152,6 +152,13 @@ SIGNATURES = {
     "ec_expert_count": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ec_teacher_force": (c_int, [c_void_p] * 3 + [c_float] + [c_void_p] * 2 + [c_int, c_int, C.c_uint64, C.c_uint64, c_int,
                                                                             c_void_p]),
+    # wide action spaces (up to 256 actions): heads + selection in one launch, the act step for every handle, the PPO loss
+    "ec_heads_wide": (c_int, [c_void_p] * 6 + [C.c_long, c_int, c_int] + [c_void_p] * 3 + [c_int, C.c_uint64, C.c_uint64, c_int]
+                      + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_policy_act_ex": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
+                         + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_ppo_loss_wide_scratch_doubles": (c_int, []),
+    "ec_ppo_loss_wide": (c_int, [c_void_p] * 9 + [C.c_long, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p]),
 }
 
 

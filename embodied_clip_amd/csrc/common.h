@@ -89,6 +89,10 @@ __device__ __forceinline__ void ec_sample_row(RowFn row, int A, uint64_t seed, u
     logp_out = row(a) - lse;
 }
 
+// the stream constant of the teacher-forcing uniform ("teachFor"): another draw than ec_sample_row makes for the same key.
+// Shared by il_teacher_force_kernel (imitation.hip) and the wide heads launch (wide_actions.hip).
+constexpr uint64_t IL_TF_STREAM = 0x7465616368466f72ull;
+
 // Block reduction of up to NV doubles in a FIXED order (wave butterflies, then the waves' sums in wave order): thread 0 returns
 // the totals.  No atomics in the reductions that use it (round 6): a floating-point atomicAdd per block made the advantage
 // statistics, the loss sums and the gradient norm depend on the order the blocks happened to retire in -- two runs from one
@@ -250,6 +254,16 @@ int ec_gemm_bf16a_xp(const void* A, const void* Wplanes, const float* bias, floa
 int ec_gemm_bf16_ln8(const void* A, const void* Wt, const float* bias, const void* res, void* out, int M, int N, int K, int act,
                      const float* ln_s, const float* ln_stats, int ln_np, float* stats_out, int* np_out,
                      ec_stream_t stream);         // conv_igemm.hip: the 8-wave GEMM with LayerNorm folded in / emitting its row records
+
+int ec_heads_wide_launch(const float* hs, const float* Wa, const float* ba, const float* wc, const float* bc, float* hv, long B, int H,
+                         int A, long long* actions, float* logp, float* values, int greedy, uint64_t seed, uint64_t step,
+                         int first_actor, const long long* expert_actions, const float* expert_mask, float force_p,
+                         hipStream_t s);           // wide_actions.hip: the heads of a wide action space + selection, one launch
+// wide_actions.hip, the learn pass of a wide handle: [Wa; wc | ba; bc] as one table ((A + 1) * H + A + 1 floats), the table's
+// gradient added onto the four gradient tensors, and the goal-embedding scatter of the unfused tail in a fixed order
+void ec_heads_pack_launch(const float* Wa, const float* ba, const float* wc, const float* bc, float* tab, int A, int H, hipStream_t s);
+void ec_heads_unpack_add_launch(const float* gtab, float* gWa, float* gba, float* gwc, float* gbc, int A, int H, hipStream_t s);
+void ec_goal_group_sum_launch(const float* dm1, const int* goal, float* dE1, int S, int N, long B, int num_goals, hipStream_t s);
 
 #define EC_CHECK_LAUNCH()                                   \
     do {                                                    \

@@ -22,9 +22,6 @@ constexpr int IL_MAX_A = 256;             // the wave path keeps IL_MAX_A / 64 l
 // scratch: [3 * block + i] the blocks' partial sums, [3 * IL_MAX_BLOCKS] the ticket counter
 constexpr int IL_TICKET = 3 * IL_MAX_BLOCKS;
 
-// the stream constant of the teacher-forcing uniform ("teachFor"): another draw than ec_sample_row makes for the same key
-constexpr uint64_t IL_TF_STREAM = 0x7465616368466f72ull;
-
 __device__ __forceinline__ float il_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

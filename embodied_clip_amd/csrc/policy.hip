@@ -1573,6 +1573,12 @@ struct SampleArgs {
     int first_actor = 0;
     int greedy = 0;               // 1: CategoricalDistr.mode() (ec_mode_row: first maximal logit) instead of a draw; seed / step / first_actor unused
 };
+// ec_policy_act_ex: teacher forcing behind the selection (expert == nullptr: none)
+struct ForceArgs {
+    const long long* expert = nullptr;
+    const float* mask = nullptr;
+    float p = 0.f;
+};
 template <int MAXO>
 __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict__ hs, const float* __restrict__ Wa,
                                                        const float* __restrict__ ba, const float* __restrict__ Wc,
@@ -1678,8 +1684,12 @@ struct Ws {   // float offsets into the workspace
     // pass's copy of the goal vectors; the backward's dE1f / dEg, the tail's per-tile segment sums, the row-block partials of
     // the two small weight gradients
     size_t E1f, Eg, gvec, dE1f, dEg, tseg, gpart;
+    // learn pass of a wide handle (A + 1 > 8; all empty otherwise): both heads as one table [Wa; wc | ba; bc] ((A + 1) * H
+    // weights, then A + 1 biases), the table's gradient in the same layout, the row-block partials of its column sum
+    size_t hW, hG, hP;
 };
 constexpr int GP_MAXY = 64;                   // row blocks of tn_small_part_kernel
+constexpr int HP_MAXY = 128;                  // row blocks of the wide heads' column sum
 
 enum class C1 { pingpong, act_kernel, split_parts, plain };      // compressor conv 1
 enum class Gi { act7, act8, split_parts, plain };                // GRU input projection (act7 / act8: gi_act_kernel<7 | 8>)
@@ -1689,6 +1699,7 @@ enum class Step { gemm_gates, fused32, fused16 };                // a recurrence
 struct Plan {
     Geo g;
     bool vec;                     // coordinate goals (goal_in > 0): per-frame bias rows instead of the goal-id table
+    bool wide;                    // learn pass with A + 1 > 8: the heads through one packed table, and no float atomics on any route
     bool infer, feat_bf16;        // infer: EC_POLICY_INFER or _REUSE (stated by the caller, never inferred from the workspace size)
     ec_policy::Built key;         // what a REUSE call must match
     int act_parts;                // partial matrices the c1 / gi areas hold: ACT_PARTS for the act step's few rows, else 1
@@ -1751,6 +1762,9 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
     w.dE1f = take_if(vec && bwd, B * c.comb_hid); w.dEg = take_if(vec && bwd, B * c.goal_dims);
     w.tseg = take_if(vec && bwd, (M49 + 31) / 32 * 256);
     w.gpart = take_if(vec && bwd, (size_t)GP_MAXY * c.comb_hid * c.goal_dims);
+    const bool wide = bwd && g.A1 > 8;
+    w.hW = take_if(wide, (size_t)g.A1 * H + g.A1); w.hG = take_if(wide, (size_t)g.A1 * H + g.A1);
+    w.hP = take_if(wide, (size_t)HP_MAXY * g.A1);
     w.end = o;
     return w;
 }
@@ -1768,6 +1782,7 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     g.nstream = (c.dual && !c.fusion) ? 2 : 1; g.flat1 = c.comb_out * g.S; g.flat = c.fusion ? c.in_channels : g.nstream * g.flat1;
     const int B = g.B, S = g.S, M49 = g.M49, H = g.H, C = g.C, flat = g.flat;
     p.infer = mode != EC_POLICY_LEARN; p.feat_bf16 = feat_bf16; p.vec = c.goal_in > 0;
+    p.wide = !p.infer && g.A1 > 8;
     p.key = ec_policy::Built{T, N, feat_bf16 ? 1 : 0};
     // Act step: so few rows that the two long-K, small-M GEMMs (compressor conv 1, GRU input projection) run as ACT_PARTS K
     // slices whose partial matrices the consuming kernels fold in a fixed order (no float atomics: rollouts stay bit-reproducible)
@@ -2004,10 +2019,16 @@ struct Fwd : Ctx {
     }
 
     // heads: hv[:, :A] = actor logits, hv[:, A] = critic value; then the final state, unless the recurrence left it there
-    int heads(const float* hs, float* hv, float* h_final, const SampleArgs& smp) {
+    int heads(const float* hs, float* hv, float* h_final, const SampleArgs& smp, const ForceArgs* wide) {
         const int B = g.B, H = g.H, A = g.A, A1 = g.A1;
         if (A1 <= 8) {
             hipLaunchKernelGGL(heads_fwd_kernel<8>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, hs, W(P_WA), W(P_BA), W(P_WC), W(P_BC), hv, (long)B, H, A, smp);
+        } else if (p.wide) {    // learn pass: both heads as one [A + 1, H] table (kept for the backward), one GEMM with the bias fused
+            ec_heads_pack_launch(W(P_WA), W(P_BA), W(P_WC), W(P_BC), ws + w.hW, A, H, s);
+            RC(gemm(hs, ws + w.hW, hv, B, A1, H, H, 1, 1, H, A1, 0, ws + w.hW + (size_t)A1 * H));
+        } else if (wide) {      // ec_policy_act_ex: heads and selection in one launch (wide_actions.hip), no workspace of its own
+            RC(ec_heads_wide_launch(hs, W(P_WA), W(P_BA), W(P_WC), W(P_BC), hv, (long)B, H, A, smp.actions, smp.logp, smp.values, smp.greedy,
+                                    smp.seed, smp.step, smp.first_actor, wide->expert, wide->mask, wide->p, s));
         } else {
             RC(gemm(hs, W(P_WA), hv, B, A, H, H, 1, 1, H, A1, 0, W(P_BA)));
             RC(gemm(hs, W(P_WC), hv + A, B, 1, H, H, 1, 1, H, A1, 0, W(P_BC)));
@@ -2034,7 +2055,7 @@ bool tables_reusable(const ec_policy* h, const void* workspace, const Plan& p, i
 
 int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16, const int64_t* goal,
                         const float* goal_vec, const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int mode, float* hv,
-                        float* h_final, const SampleArgs& smp, ec_stream_t stream) {
+                        float* h_final, const SampleArgs& smp, ec_stream_t stream, const ForceArgs* wide = nullptr) {
     if (!h || !params || !feat || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
     if (h->c.goal_in > 0 ? (!goal_vec || goal) : (!goal || goal_vec)) return EC_ERR_ARG;   // the entry point of the handle's goal type
     if (h->c.dual && !feat2) return EC_ERR_ARG;
@@ -2052,7 +2073,7 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
     RC(f.input_projection());
     float* hs = (p.hs_direct && h_final && h_final != h0) ? h_final : f.ws + p.w.hs;
     RC(f.recurrence(h0, masks, hs));
-    RC(f.heads(hs, hv, h_final, smp));
+    RC(f.heads(hs, hv, h_final, smp, wide));
     EC_CHECK_LAUNCH();
     return EC_OK;
 }
@@ -2065,9 +2086,8 @@ struct Bwd : Ctx {
 
     // column sums (bias gradients) without atomics: row block y leaves its sums in cpart[y][Ncol] (the forward's per-step `gh`
     // scratch: N x 3H floats, idle in the backward), colsum_fold_kernel adds the row blocks in order onto the gradient
-    void colsum(const float* Y, float* out, long M, int Ncol, int ld) {
-        float* cpart = ws + w.gh;
-        const size_t cpart_cap = (size_t)g.N * 3 * g.H;
+    void colsum(const float* Y, float* out, long M, int Ncol, int ld, float* cpart = nullptr, size_t cpart_cap = 0) {
+        if (!cpart) { cpart = ws + w.gh; cpart_cap = (size_t)g.N * 3 * g.H; }
         const bool wide = (Ncol & 3) == 0 && (ld & 3) == 0 && Ncol >= 256 && M >= 1024;
         long nby = (M + (wide ? 255 : 2047)) / (wide ? 256 : 2048);
         const long fit = (long)(cpart_cap / (size_t)Ncol);
@@ -2100,8 +2120,8 @@ struct Bwd : Ctx {
     // dW += dY^T X over K rows: K slices into partial matrices folded in order while the dx area is free (`parts_ok`); the
     // tail's unfused fallback GEMMs (EC_TAIL_FUSED=0, the dual encoder) run after dx exists and keep the atomic split
     int tn(const float* dY, int ldy, const void* X, int ldx, int x_bf16, float* dW, int Mo, int No, long K, int ldc) {
-        // (coordinate goals: no float atomics on any route -- without the partial-matrix area the GEMM walks K in one piece)
-        const int sk = (p.vec && !parts_ok) ? 1 : pick_splitk(Mo, No, K), flags = (x_bf16 ? EC_GEMM_B_BF16 : 0) | p.bwd3;
+        // (coordinate goals, wide handles: no float atomics on any route -- without the partial-matrix area the GEMM walks K in one piece)
+        const int sk = ((p.vec || p.wide) && !parts_ok) ? 1 : pick_splitk(Mo, No, K), flags = (x_bf16 ? EC_GEMM_B_BF16 : 0) | p.bwd3;
         if (parts_ok) return gemm_acc_split(dY, X, dW, Mo, No, K, 1, ldy, ldx, 1, ldc, flags, sk);
         return ec_gemm_f32(dY, X, dW, Mo, No, (int)K, 1, ldy, ldx, 1, ldc, EC_GEMM_ACCUMULATE | flags, nullptr, nullptr, nullptr, 0, nullptr,
                            nullptr, sk, stream);
@@ -2118,6 +2138,17 @@ struct Bwd : Ctx {
 
     int heads(const float* dhv) {
         const int B = g.B, H = g.H, A = g.A, A1 = g.A1;
+        if (p.wide) {
+            // on the forward's packed table: dhs = dhv [B, A+1] x tab [A+1, H]; the table's gradient dhv^T hs by K slices folded
+            // in order and its bias row by ordered column sums, both onto a zeroed copy; one launch adds that to the four tensors
+            float* gt = ws + w.hG;
+            RC(gemm(dhv, ws + w.hW, ws + w.dhs, B, H, A1, A1, 1, H, 1, H));
+            (void)hipMemsetAsync(gt, 0, ((size_t)A1 * H + A1) * 4, s);
+            RC(gemm_acc_split(dhv, ws + w.hs, gt, A1, H, B, 1, A1, H, 1, H, 0, pick_splitk(A1, H, B)));
+            colsum(dhv, gt + (size_t)A1 * H, B, A1, A1, ws + w.hP, (size_t)HP_MAXY * A1);
+            ec_heads_unpack_add_launch(gt, G(P_WA), G(P_BA), G(P_WC), G(P_BC), A, H, s);
+            return EC_OK;
+        }
         RC(gemm(dhv, W(P_WA), ws + w.dhs, B, H, A, A1, 1, H, 1, H));
         RC(gemm(dhv + A, W(P_WC), ws + w.dhs, B, H, 1, A1, 1, H, 1, H, EC_GEMM_ACCUMULATE));
         RC(gemm_acc_split(dhv, ws + w.hs, G(P_WA), A, H, B, 1, A1, H, 1, H, 0, pick_splitk(A, H, B)));
@@ -2147,7 +2178,7 @@ struct Bwd : Ctx {
                 // dh_carry += m * (dghb @ W_hh)   (fused: step T-1's back-projection runs inside the next launch)
                 if (p.step_bwd == Step::gemm_gates)
                     RC(ec_gemm_f32(ws + w.dghb + o3, W(P_WHH), ws + w.dhc, N, H, 3 * H, 3 * H, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr,
-                                   nullptr, nullptr, 0, nullptr, m, p.vec ? 1 : step_splitk(N, H, 3 * H), stream));
+                                   nullptr, nullptr, 0, nullptr, m, (p.vec || p.wide) ? 1 : step_splitk(N, H, 3 * H), stream));
             } else if (p.step_bwd == Step::fused16) {
                 hipLaunchKernelGGL(gru_step_bwd512_kernel, dim3(32u, (unsigned)((N + 15) / 16)), dim3(256), gb16_lds, s,
                                    ws + w.dghb + o3 + (size_t)N * 3 * H, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dhc,
@@ -2270,6 +2301,7 @@ struct Bwd : Ctx {
                            0, nullptr, nullptr, nullptr, 0, ws + o.m1, nullptr, 1, stream));
             RC(tn(ws + w.dm1, c.comb_hid, ws + o.c2, c.compress_out, 0, GS(P_W3), c.comb_hid, c.compress_out, M49, cat));
             if (p.vec) hipLaunchKernelGGL(frame_sum_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.dm1, ws + w.dE1f, S, c.comb_hid);
+            else if (p.wide) ec_goal_group_sum_launch(ws + w.dm1, goal32, ws + w.dE1, S, c.comb_hid, (long)B, c.num_goals, s);
             else
             hipLaunchKernelGGL(group_sum_scatter_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.dm1, goal32, ws + w.dE1, S,
                                c.comb_hid, (long)B);
@@ -2427,6 +2459,32 @@ extern "C" int ec_policy_act_vec_greedy(const ec_policy_t* h, const float* param
     const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
                                reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
+}
+
+// The act step in one call for every handle (include/ec_amd.h).  More than 7 actions: the stages in front as they are, then the
+// wide heads launch with the selection (and the forcing) in it; up to 7: what ec_policy_act* launch, then ec_teacher_force's launch.
+extern "C" int ec_policy_act_ex(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                                const int64_t* goal, const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
+                                size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
+                                float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
+                                const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
+    if (!h || !actions || !logp) return EC_ERR_ARG;
+    if ((expert_actions != nullptr) != (expert_mask != nullptr)) return EC_ERR_ARG;
+    if (!(force_p >= 0.f && force_p <= 1.f)) return EC_ERR_ARG;       // (NaN included)
+    if (!expert_actions && force_p != 0.f) return EC_ERR_ARG;
+    if (expert_actions && greedy) return EC_ERR_ARG;                   // forcing belongs to the sampling act step
+    if (h->c.num_actions > 256) return EC_ERR_UNSUPPORTED;
+    if (first_actor < 0) return EC_ERR_SHAPE;
+    const SampleArgs smp{(long long*)actions, logp, values, greedy ? 0 : seed, greedy ? 0 : step, greedy ? 0 : first_actor, greedy ? 1 : 0};
+    const ForceArgs force{(const long long*)expert_actions, expert_mask, force_p};
+    const int mode = reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER;
+    if (h->c.num_actions + 1 > 8)
+        return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, 1, N, workspace, ws_bytes, mode, hv, h_final,
+                                   smp, stream, &force);
+    const int rc = policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, 1, N, workspace, ws_bytes, mode, hv,
+                                       h_final, smp, stream);
+    if (rc != EC_OK || !expert_actions) return rc;
+    return ec_teacher_force(hv, expert_actions, expert_mask, force_p, actions, logp, N, h->c.num_actions, seed, step, first_actor, stream);
 }
 
 extern "C" int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,

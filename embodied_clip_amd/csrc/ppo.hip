@@ -239,7 +239,7 @@ extern "C" int ec_ppo_loss_ex(const float* hv, const int64_t* actions, const flo
                               float clip, float value_clip, float vcoef, float ecoef, float grad_scale,
                               ec_stream_t stream) {
     if (!hv || !actions || !old_logp || !old_values || !returns || !norm_adv || !dhv || !sums4) return EC_ERR_ARG;
-    if (B <= 0 || A <= 0 || A > 16) return EC_ERR_SHAPE;
+    if (B <= 0 || A <= 0 || A > 16) return EC_ERR_SHAPE;              // (a row in one thread's registers; up to 256 actions: ec_ppo_loss_wide, wide_actions.hip)
     hipStream_t s = (hipStream_t)stream;
     if (A <= 8)
         hipLaunchKernelGGL(ppo_loss_kernel<8>, dim3(1), dim3(1024), 0, s, hv, (const long long*)actions, old_logp, old_values,

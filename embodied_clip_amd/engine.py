@@ -38,7 +38,7 @@ from .episodes import EpisodeTracker, NavEpisodeTracker, nav_env_tensors
 from .encoder import AttentionPool, ClipTextEncoder, ImageNetBasicTrunk, ImageNetRN50Trunk, RN50Trunk, ViTEmbedder
 from .policy import PolicyHandle
 from .imitation import imitation_loss_raw, imitation_scratch
-from .ppo import FlatAdam, linear_decay_lr, ppo_loss_raw
+from .ppo import PPO_NARROW_MAX_A, FlatAdam, linear_decay_lr, ppo_loss_raw, ppo_wide_scratch
 
 # encoder name -> (blocks per layer, torchvision block type, trunk class) of the ImageNet-feature agents
 IMAGENET_ENCODERS = {
@@ -285,7 +285,12 @@ class _SlicedActor:
         self._conv8_min_tiles = (50 if n >= 128 else (75 if n >= 64 else 0)) if ns == 2 else 0
         for e in encs:
             e.set_conv8_min_tiles(self._conv8_min_tiles)
-        self._act_fused = os.environ.get("EC_ACT_FUSED_SAMPLE", "1") != "0" and self.A + 1 <= 8   # (A/B switch; > 7 actions: two calls)
+        # A/B switch.  Up to 7 actions: the narrow heads launch samples (ec_policy_act).  8 to 256: the wide heads launch computes
+        # the logits, selects and forces (ec_policy_act_ex).  Off, above 256, or a hidden size whose rows do not fit the wide
+        # launch's LDS (ec_heads_wide: H <= 3576): the forward, then the stand-alone selection calls
+        fused = os.environ.get("EC_ACT_FUSED_SAMPLE", "1") != "0"
+        self._act_fused = fused and self.A + 1 <= 8
+        self._act_wide = fused and 8 < self.A + 1 <= 257 and self.H <= 3576
         self.trunk_events: List = []             # (start, end) HIP event pairs around the encoder launches
         self.time_trunk = False
 
@@ -519,6 +524,8 @@ class Worker(_SlicedActor):
             sl.rec_ready.record()          # (torch creates the hipEvent_t at the first record: the library needs the handle)
             sl.sums = torch.zeros(4, dtype=torch.float64, device=d)
             sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = None
+            # more than 16 actions: the wide loss kernel's partial-sum scratch, one per slice stream as for imitation
+            sl.ppo_scratch = ppo_wide_scratch(d) if (self._ppo and self.A > PPO_NARROW_MAX_A) else None
             if self._il:      # the imitation loss's sums and partial-sum scratch: one per slice stream
                 sl.il_sums = torch.zeros(3, dtype=torch.float64, device=d)
                 sl.il_scratch = imitation_scratch(d)
@@ -548,6 +555,16 @@ class Worker(_SlicedActor):
                             self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t))
             sl.act_tables_valid = True
             self._teacher_force_slice(sl, t)
+            return
+        if sample and self._act_wide:
+            # the same for 8 to 256 actions (ec_policy_act_ex): the wide heads launch samples and, while p > 0, forces
+            tf = self._tf_p > 0.0
+            self.policy.act_ex(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act,
+                               self.hv_act[rs], h_out[rs], self.actions[t][rs], self.logp[t][rs], self.values[t][rs], self.seed,
+                               self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t),
+                               expert_actions=self.env.expert_actions[t][rs] if tf else None,
+                               expert_mask=self.env.expert_mask[t][rs] if tf else None, force_p=self._tf_p if tf else 0.0)
+            sl.act_tables_valid = True
             return
         self.policy.forward(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n,
                             sl.ws_act, hv=self.hv_act[rs], h_final=h_out[rs], for_backward=False,
@@ -808,7 +825,7 @@ class Worker(_SlicedActor):
                                             sl.ws_learn, hv=hv, feat2=feat2)
                         if self._ppo:
                             ppo_loss_raw(hv, actions, logp, old_v, ret, nadv, self.A, grad_scale=grad_scale, dhv=dhv,
-                                         sums=sl.sums)
+                                         sums=sl.sums, scratch=sl.ppo_scratch)
                         if self._il:
                             # the kernel divides by the RANGE's normaliser (shared by the parts), so only local / global
                             # minibatch size is left to apply; after a PPO call the term is added to its dhv

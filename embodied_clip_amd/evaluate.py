@@ -127,7 +127,11 @@ class Evaluator(_SlicedActor):
             self.policy.act(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
                             actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
                             deterministic=self.deterministic, feat2=feat2)
-        else:   # more than 7 actions: the forward, then the stand-alone selection kernel
+        elif self._act_wide:   # 8 to 256 actions: the wide heads launch selects (ec_policy_act_ex)
+            self.policy.act_ex(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
+                               actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
+                               deterministic=self.deterministic, feat2=feat2)
+        else:   # the switch off: the forward, then the stand-alone selection kernel
             self.policy.forward(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n, sl.ws_act,
                                 hv=hv, h_final=h_out[rs], for_backward=False, reuse_tables=sl.act_tables_valid, feat2=feat2)
             if self.deterministic:

@@ -138,6 +138,27 @@ class PolicyHandle:
                 _lib.stream_ptr()), name)
         return hv, h_final
 
+    def act_ex(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
+               first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, expert_actions=None,
+               expert_mask=None, force_p: float = 0.0):
+        """The act step in one call for every handle, up to 256 actions (``ec_policy_act_ex``).  With more than 7 actions the
+        heads launch of the wide action space computes the logits and selects (sample, or ``deterministic=True`` the first
+        maximal logit) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions`` / ``ec_mode_actions`` on the
+        ``hv`` it writes, bit for bit; with up to 7 it is ``act``.  ``expert_actions`` / ``expert_mask`` / ``force_p``: teacher
+        forcing (``imitation.teacher_force``) in the same call -- inside the heads launch of a wide action space."""
+        assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
+        gp = self._goal_ptr(goal, N)
+        forcing = expert_actions is not None and force_p > 0.0
+        with _lib.tensor_guard(flat_params):
+            _lib.check(self.lib.ec_policy_act_ex(
+                self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16),
+                0 if self.goal_in else gp, gp if self.goal_in else 0, h0.data_ptr(), masks.data_ptr(), N, ws.data_ptr(),
+                ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), h_final.data_ptr(), actions.data_ptr(),
+                logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
+                expert_actions.data_ptr() if forcing else 0, expert_mask.data_ptr() if forcing else 0,
+                force_p if forcing else 0.0, _lib.stream_ptr()), "ec_policy_act_ex")
+        return hv, h_final
+
     def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None):
         if hv is None:
             hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)

@@ -24,18 +24,49 @@ from .allenact_compat import AbstractActorCriticLoss
 PPOConfig = dict(clip_param=0.1, value_loss_coef=0.5, entropy_coef=0.01)
 
 
+PPO_NARROW_MAX_A = 16          # ec_ppo_loss_ex's bound; above, ec_ppo_loss_wide (up to 256 actions)
+_wide_scratch: Dict[tuple, torch.Tensor] = {}
+
+
+def ppo_wide_scratch(device) -> torch.Tensor:
+    """A partial-sum scratch of the wide loss kernel (one per stream that calls it)."""
+    return torch.zeros(_lib.load().ec_ppo_loss_wide_scratch_doubles(), dtype=torch.float64, device=device)
+
+
+def _cached_wide_scratch(device) -> torch.Tensor:
+    """The scratch of (device, current stream): calls on one stream are ordered, so they may share one."""
+    key = (torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
+    s = _wide_scratch.get(key)
+    if s is None:
+        s = _wide_scratch[key] = ppo_wide_scratch(device)
+    return s
+
+
 def ppo_loss_raw(hv, actions, old_logp, old_values, returns, norm_adv, A: int, clip_param=0.1, value_loss_coef=0.5,
                  entropy_coef=0.01, grad_scale: float = 1.0, dhv: Optional[torch.Tensor] = None,
-                 sums: Optional[torch.Tensor] = None, use_clipped_value_loss: bool = True):
+                 sums: Optional[torch.Tensor] = None, use_clipped_value_loss: bool = True,
+                 scratch: Optional[torch.Tensor] = None):
     """Fused loss forward+backward.  hv [B, A+1] fp32 contiguous; everything else flat [B].
     Returns (dhv [B, A+1], sums4 float64 device tensor = sum over B of {action, value, -entropy, ratio}).
-    An action id outside [0, A) makes sums4[0] (and so the loss) NaN."""
+    An action id outside [0, A) makes sums4[0] (and so the loss) NaN.
+    More than 16 actions (up to 256) run ``ec_ppo_loss_wide``; ``scratch`` is its partial-sum scratch (``ppo_wide_scratch``),
+    by default one cached per device and stream."""
     lib = _lib.load()
     B = hv.shape[0]
     if dhv is None:
         dhv = torch.empty_like(hv)
     if sums is None:
         sums = torch.empty(4, dtype=torch.float64, device=hv.device)
+    if A > PPO_NARROW_MAX_A:
+        with _lib.tensor_guard(hv):
+            if scratch is None:
+                scratch = _cached_wide_scratch(hv.device)
+            _lib.check(lib.ec_ppo_loss_wide(hv.data_ptr(), actions.data_ptr(), old_logp.data_ptr(), old_values.data_ptr(),
+                                            returns.data_ptr(), norm_adv.data_ptr(), dhv.data_ptr(), sums.data_ptr(),
+                                            scratch.data_ptr(), B, A, clip_param,
+                                            clip_param if use_clipped_value_loss else -1.0, value_loss_coef, entropy_coef,
+                                            grad_scale, _lib.stream_ptr()), "ec_ppo_loss_wide")
+        return dhv, sums
     with _lib.tensor_guard(hv):
         _lib.check(lib.ec_ppo_loss_ex(hv.data_ptr(), actions.data_ptr(), old_logp.data_ptr(), old_values.data_ptr(),
                                       returns.data_ptr(), norm_adv.data_ptr(), dhv.data_ptr(), sums.data_ptr(), B, A,

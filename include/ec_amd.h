@@ -436,6 +436,8 @@ size_t ec_policy_workspace_bytes(const ec_policy_t* h, int T, int N, int for_bac
  * hv f32 [T*N, A+1] out: logits in cols 0..A-1, value in col A; h_final f32 [N,H] or NULL.
  * for_backward (the kernel plan depends on this flag alone, never on the size of the buffer handed in):
  *   EC_POLICY_LEARN (1)        the workspace (ec_policy_workspace_bytes(.., 1)) keeps every activation ec_policy_backward needs;
+ *                              with more than 7 actions also both heads as one packed [A + 1, H] table and its gradient (one GEMM
+ *                              each way; no float atomics on any route of such a handle: two learn passes give equal bits);
  *   EC_POLICY_INFER (0)        inference only (act step; a workspace of ec_policy_workspace_bytes(.., 0) suffices);
  *   EC_POLICY_INFER_REUSE (2)  inference, and the weight-derived tables an EC_POLICY_INFER call left in THIS workspace are
  *                              still valid (unchanged parameters: the later act steps of a rollout) -- they are not rebuilt. */
@@ -614,6 +616,48 @@ int ec_expert_count(const float* expert_mask, int T, int N, int n0, int n1, doub
  * launches nothing.  A forced id outside [0, A) gives logp NaN. */
 int ec_teacher_force(const float* hv, const int64_t* expert_actions, const float* expert_mask, float p, int64_t* actions,
                      float* logp, int N, int A, uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Wide action spaces: up to 256 actions, ec_imitation_loss's bound (the reference's rearrangement experiment has 84:
+ * readme_files/baselines_ithor_rearrangement.md).  The narrow entry points keep their limits -- ec_policy_act* 7 actions,
+ * ec_ppo_loss_ex 16 -- and their kernels; these run kernels of their own (csrc/wide_actions.hip).
+ * ---------------------------------------------------------------------- */
+/* The actor and critic heads with the action selection in the same launch:
+ *   hv[b,:A] = hs[b] . Wa^T + ba,  hv[b,A] = hs[b] . wc + bc      hs f32 [B,H], Wa [A,H], ba [A], wc [H], bc [1], hv [B,A+1].
+ * 1 <= A <= 256, H % 4 == 0 (and H <= 3576: a workgroup keeps its four rows of hs in LDS, above is EC_ERR_UNSUPPORTED).
+ * actions NULL: logits and values only.  Otherwise, once a row's A + 1 outputs exist, the same launch selects:
+ *   greedy == 0: ec_sample_actions' draw, keyed by (seed, step, first_actor + b);   greedy != 0: ec_mode_actions' first
+ *   maximal logit;   logp = log_prob(action), values = hv[:,A] (or NULL).
+ *   expert_actions / expert_mask / force_p (NULL, NULL, 0 = none; sampling only): ec_teacher_force's rule and uniform -- a row
+ *   with mask 0 never reads its expert id, a forced id outside [0, A) gives that action with logp NaN.
+ * actions / logp / values are bit-identical to ec_sample_actions / ec_mode_actions (then ec_teacher_force) run on the hv this
+ * launch wrote: the exp terms are computed across lanes, the sums of the log-sum-exp and of the CDF in their index order.
+ * A row's outputs do not depend on B or on the rows that share its workgroup.
+ * Checked before any HIP call: NULL, forcing with greedy or without actions, force_p outside [0, 1] or without expert
+ * arrays -> EC_ERR_ARG; B <= 0, A outside [1, 256], H % 4 -> EC_ERR_SHAPE. */
+int ec_heads_wide(const float* hs, const float* Wa, const float* ba, const float* wc, const float* bc, float* hv, long B, int H,
+                  int A, int64_t* actions, float* logp, float* values, int greedy, uint64_t seed, uint64_t step,
+                  int first_actor, const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream);
+/* The act step in one call for every handle: 1 <= num_actions <= 256, integer or coordinate goals (exactly one of goal /
+ * goal_vec, by the handle's type), dual, fusion.  Arguments of ec_policy_act plus goal_vec, greedy and the forcing triple of
+ * ec_heads_wide (forcing with greedy -> EC_ERR_ARG).
+ *   more than 7 actions: ec_policy_forward2's stages up to the recurrence (T = 1, EC_POLICY_INFER[_REUSE]; the same
+ *     workspace), then ec_heads_wide's launch on actor.linear.* / critic.fc.* where they lie in `params`;
+ *   up to 7 actions: exactly the launches of ec_policy_act / _vec / _greedy, then ec_teacher_force's when forcing is asked. */
+int ec_policy_act_ex(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                     const int64_t* goal, const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
+                     size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
+                     int greedy, uint64_t seed, uint64_t step, int first_actor, const int64_t* expert_actions,
+                     const float* expert_mask, float force_p, ec_stream_t stream);
+/* ec_ppo_loss_ex for 1 <= A <= 256: the same per-row arithmetic with one 64-lane wave per row (lane-strided logits, xor
+ * butterflies for the maximum and the sums) and contiguous row chunks over several workgroups.  The blocks' fp64 partials of
+ * the four sums go to scratch (ec_ppo_loss_wide_scratch_doubles() doubles, owned by one stream at a time) and are folded in
+ * block order by the block that draws the last integer ticket: two runs give the same bits, and a row's dhv depends on the
+ * row and on grad_scale / B alone. */
+int ec_ppo_loss_wide_scratch_doubles(void);
+int ec_ppo_loss_wide(const float* hv, const int64_t* actions, const float* old_logp, const float* old_values,
+                     const float* returns, const float* norm_adv, float* dhv, double* sums4, double* scratch, long B, int A,
+                     float clip, float value_clip, float vcoef, float ecoef, float grad_scale, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * CLIP VisionTransformer embedder == [U] allenact ClipViTEmbedder.forward over

@@ -1,0 +1,248 @@
+"""GPU: an 84-action agent through the engine -- ``Worker(num_actions=84, loss="ppo" / "ppo+imitation")``, the ``Evaluator`` and
+the A/B switch -- against the CPU oracle policy with the reference losses under torch autograd (the set-up and tolerances of
+tests/test_gpu_imitation_engine.py: the same tiny encoder, actor and step counts), and the learn pass of a wide handle against
+the float64 oracle (the shapes and tolerances of tests/test_gpu_policy.py: gradients 2e-4, the forward 2e-5), where its heads run
+through one packed [A + 1, H] table and two passes give equal bits."""
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import _imitation_ref as iref  # noqa: E402
+import _wide_actions_engine_check as chk  # noqa: E402
+import _wide_actions_ref as ref  # noqa: E402
+from embodied_clip_amd import synthetic as syn  # noqa: E402
+from oracle import policy as opol  # noqa: E402
+from oracle import ppo as oppo  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+A84 = 84
+DEV = "cuda:0"
+
+
+def _batch(w):
+    """The rollout of ``w`` in the oracle's layout (features are the GPU's own, bf16-exact)."""
+    T, N, S, C = w.T, w.N, w.S, w.C
+    feat = w.feat.float().cpu().view(T + 1, N, S, S, C).permute(0, 1, 4, 2, 3).contiguous()
+    masks = w.env.masks.cpu().unsqueeze(-1)
+    b = dict(feat=feat[:T], goal=w.env.goals.cpu()[:T], h0=torch.zeros(1, N, w.H), masks=masks[:T], actions=w.actions.cpu(),
+             old_log_probs=w.logp.cpu().unsqueeze(-1), old_values=w.values[:T].cpu().unsqueeze(-1),
+             returns=w.returns[:T].cpu().unsqueeze(-1), norm_adv=w.nadv.cpu().unsqueeze(-1))
+    if hasattr(w.env, "expert_actions"):
+        b["expert"], b["emask"] = w.env.expert_actions.cpu()[:T], w.env.expert_mask.cpu()[:T]
+    return b
+
+
+def _oracle_step(sd, batch, st, il_weight=None, lr=3e-4, max_grad_norm=0.5):
+    """oracle.ppo.ppo_update_step, plus ``il_weight`` x the reference imitation loss when given"""
+    names = list(sd)
+    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
+    logits, values, _ = opol.actor_critic_forward(batch["feat"], batch["goal"], batch["h0"], batch["masks"], leaves)
+    total, info = oppo.ppo_loss(logits, values, batch["actions"], batch["old_log_probs"], batch["old_values"], batch["returns"],
+                                batch["norm_adv"])
+    if il_weight is not None:
+        e, m = batch["expert"], batch["emask"]
+        lp = opol.categorical_log_prob(logits, torch.where(m != 0, e, torch.zeros_like(e)))
+        ce = -(m * lp).sum() / m.sum().clamp(min=1)
+        total = total + il_weight * ce
+        info["expert_cross_entropy"] = float(ce.detach())
+    grads = torch.autograd.grad(total, [leaves[k] for k in names], allow_unused=True)
+    grads = [torch.zeros_like(sd[k]) if g is None else g.clone() for k, g in zip(names, grads)]
+    raw = [g.clone() for g in grads]
+    info["grad_norm"] = oppo.clip_grad_norm_(grads, max_grad_norm)
+    if "step" not in st:
+        st.update(step=0, m=[torch.zeros_like(sd[k]) for k in names], v=[torch.zeros_like(sd[k]) for k in names])
+    st["step"] += 1
+    with torch.no_grad():
+        oppo.adam_step([sd[k] for k in names], grads, st["m"], st["v"], st["step"], lr=lr)
+    return info, dict(zip(names, raw))
+
+
+def _record_act_ex(w):
+    """wrap the handle's act_ex: after every call, the shared selection functions on the hv it wrote, on the same stream"""
+    from embodied_clip_amd import _lib as L
+    lib, orig, seen = L.load(), w.policy.act_ex, []
+
+    def act_ex(params, feat, goal, h0, masks, n, ws, hv, h_final, actions, logp, values, seed, step, first_actor, **kw):
+        orig(params, feat, goal, h0, masks, n, ws, hv, h_final, actions, logp, values, seed, step, first_actor, **kw)
+        a2, lp2, v2 = torch.empty_like(actions), torch.empty_like(logp), torch.empty_like(values)
+        L.check(lib.ec_sample_actions(hv.data_ptr(), a2.data_ptr(), lp2.data_ptr(), v2.data_ptr(), n, w.A, seed, step, first_actor,
+                                      L.stream_ptr()))
+        if kw.get("expert_actions") is not None:
+            L.check(lib.ec_teacher_force(hv.data_ptr(), kw["expert_actions"].data_ptr(), kw["expert_mask"].data_ptr(), kw["force_p"],
+                                         a2.data_ptr(), lp2.data_ptr(), n, w.A, seed, step, first_actor, L.stream_ptr()))
+        seen.append((actions.clone(), logp.clone(), values.clone(), a2, lp2, v2, kw.get("expert_actions") is not None))
+    w.policy.act_ex = act_ex
+    return seen
+
+
+@pytest.mark.parametrize("loss", ["ppo", "ppo+imitation"])
+def test_wide_worker_iteration_matches_oracle(loss):
+    T, N, R, wgt = 3, 2, 1, 0.5
+    pol_sd = syn.policy_state_dict(0, num_actions=A84)
+    w = chk.build_worker(A84, loss, N=N, T=T, seed=3, update_repeats=R, **({} if loss == "ppo" else dict(il_weight=wgt)))
+    assert w._act_wide and not w._act_fused and w.A == A84
+    seen = _record_act_ex(w)
+    w.collect_rollout()
+    w.compute_returns()
+    torch.cuda.synchronize()
+    assert len(seen) == T * w.ns                                   # every sampling step took the one-call route
+    bits = lambda x: x.view(torch.int32)
+    for (a, lp, v, a2, lp2, v2, forced) in seen:
+        assert forced == (loss != "ppo")
+        assert torch.equal(a, a2) and torch.equal(bits(lp), bits(lp2)) and torch.equal(bits(v), bits(v2))
+    assert int(w.actions.max()) > 6, "an 84-action rollout that never leaves the narrow agents' ids"
+    if loss != "ppo":      # forced steps took the expert's action
+        em = w.env.expert_mask.cpu().numpy()
+        for t in range(T):
+            forced = torch.from_numpy(iref.teacher_force_decisions(w.seed, t, 0, em[t], 0.5))
+            assert torch.equal(w.actions[t].cpu()[forced], w.env.expert_actions[t].cpu()[forced])
+    batch = _batch(w)
+    sd_ref = {k: v.clone() for k, v in pol_sd.items()}
+    info, g_ = _oracle_step(sd_ref, batch, {}, il_weight=None if loss == "ppo" else wgt)
+    w.update()
+    torch.cuda.synchronize()
+    got = w.loss_info()
+    print("worker", got, "oracle", info)
+    assert abs(got["ppo_total"] - info["ppo_total"]) < 2e-4 * max(1.0, abs(info["ppo_total"]))
+    assert abs(got["grad_norm"] - info["grad_norm"]) < 2e-3 * info["grad_norm"], (got, info)
+    if loss != "ppo":
+        r = info["expert_cross_entropy"]
+        assert abs(got["expert_cross_entropy"] - r) < 2e-4 * max(1.0, abs(r)), (got, info)
+    iref.check_updates(w.policy.views(w.params), pol_sd, sd_ref, [g_], R)
+
+
+def test_two_wide_workers_from_one_seed_end_bit_identical():
+    outs = []
+    for _ in range(2):
+        w = chk.build_worker(A84, "ppo+imitation")
+        for _it in range(2):
+            w.iteration()
+        outs.append(chk.snapshot(w))
+        outs[-1]["sums"] = torch.stack([sl.sums for sl in w.slices]).cpu().clone()
+        del w
+    for k in outs[0]:
+        assert torch.equal(outs[0][k], outs[1][k]), k
+
+
+def _child(num_actions, loss, path, switch):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("EC_") or k == "EC_AMD_LIB"}
+    if switch is not None:
+        env["EC_ACT_FUSED_SAMPLE"] = switch
+    r = subprocess.run([sys.executable, os.path.join(HERE, "_wide_actions_engine_check.py"), str(num_actions), loss, path],
+                       capture_output=True, text=True, env=env, timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return torch.load(path)
+
+
+def test_switch_off_takes_the_multi_call_route(tmp_path):
+    """EC_ACT_FUSED_SAMPLE=0, 84 actions: the forward's GEMM heads, then the stand-alone selection and forcing calls.  Its logits
+    differ from the wide launch's in summation order, so: the same actions wherever the two forwards agree to the bit, and the
+    forwards within the act-route bound of one another (2e-5 each against float64)."""
+    off = _child(A84, "ppo+imitation", str(tmp_path / "off.pt"), "0")
+    assert not off["act_wide"] and not off["act_fused"]
+    w = chk.build_worker(A84, "ppo+imitation")
+    chk.record_hv(w)
+    w.iteration()
+    on = chk.snapshot(w)
+    assert w._act_wide
+    T = w.T
+    same = float((on["actions"] == off["actions"]).float().mean())
+    rel_v, rel_hv = ref.rel_l2(on["values"], off["values"]), ref.rel_l2(on["hv_steps"], off["hv_steps"])
+    # step by step, row by row: where the two routes stored the same logits and value, they selected from the same numbers
+    bits = lambda x: x.view(torch.int32)
+    rows = (bits(on["hv_steps"][:T]) == bits(off["hv_steps"][:T])).all(dim=-1)                # [T, N]
+    print("switch off vs on: equal actions %.3f, rows with bit-equal hv %d of %d, values rel-L2 %.3e, hv rel-L2 %.3e"
+          % (same, int(rows.sum()), rows.numel(), rel_v, rel_hv))
+    assert torch.equal(on["actions"][rows], off["actions"][rows])
+    assert torch.equal(bits(on["logp"])[rows], bits(off["logp"])[rows])
+    assert torch.equal(bits(on["values"][:T])[rows], bits(off["values"][:T])[rows])
+    assert rel_v < 2 * 2e-5 and rel_hv < 2 * 2e-5
+
+
+def test_narrow_worker_is_untouched(tmp_path):
+    """6 actions: the worker as it is, against the same worker with the one-call routes switched off, in child processes --
+    rollout and parameters bit for bit (ec_policy_act is the forward + ec_sample_actions; nothing wide runs at this width)."""
+    on = _child(6, "ppo+imitation", str(tmp_path / "on.pt"), None)
+    off = _child(6, "ppo+imitation", str(tmp_path / "off.pt"), "0")
+    assert on["act_fused"] and not on["act_wide"] and not off["act_fused"] and not off["act_wide"]
+    for k in ("actions", "logp", "values", "hv_act", "params"):
+        assert torch.equal(on[k], off[k]), k
+
+
+def test_wide_evaluator_greedy_is_mode_actions():
+    from embodied_clip_amd import _lib as L
+    from embodied_clip_amd.evaluate import Evaluator
+    N, T = 6, 4
+    ev = Evaluator(N, T=T, device=DEV, seed=5, encoder_sd=syn.rn50_visual_state_dict(0), policy_sd=syn.policy_state_dict(0, num_actions=A84),
+                   num_actions=A84, record=True, deterministic=True)
+    assert ev._act_wide
+    ev.run(1)
+    torch.cuda.synchronize()
+    hv = ev.hv.reshape(T * N, A84 + 1).contiguous()
+    a2, lp2 = torch.empty(T * N, dtype=torch.int64, device=DEV), torch.empty(T * N, device=DEV)
+    L.check(L.load().ec_mode_actions(hv.data_ptr(), a2.data_ptr(), lp2.data_ptr(), None, T * N, A84, L.stream_ptr()))
+    torch.cuda.synchronize()
+    assert torch.equal(ev.actions.reshape(-1), a2) and torch.equal(ev.logp.reshape(-1), lp2)
+    assert torch.equal(ev.actions.reshape(-1).cpu(), hv[:, :A84].cpu().argmax(dim=-1))
+    assert torch.equal(ev.values.reshape(-1), hv[:, A84])
+
+
+# ---- the learn pass of a wide handle ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("A", [9, 84])
+@pytest.mark.parametrize("T,N,S,C,H", [(4, 19, 7, 64, 512), (6, 4, 3, 64, 32)])
+def test_wide_learn_pass_against_float64(T, N, S, C, H, A):
+    from embodied_clip_amd import ppo
+    from embodied_clip_amd.policy import PolicyHandle
+    cfg = dict(in_channels=C, spatial=S, hidden=H, num_actions=A)
+    sd = syn.policy_state_dict(7, **cfg)
+    g = torch.Generator().manual_seed(8 + A)
+    feat = torch.randn(T, N, C, S, S, generator=g).abs().to(torch.bfloat16).float()
+    goal = syn.synthetic_goals(9, (T, N))
+    h0 = torch.randn(1, N, H, generator=g) * 0.5
+    masks = syn.synthetic_masks(10, T, N, p_reset=0.2)
+    # float64 reference: the oracle's forward and the reference loss under autograd
+    leaves = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    lg, vv, _ = opol.actor_critic_forward(feat.double(), goal, h0.double(), masks.double(), leaves)
+    hv64 = torch.cat([lg, vv], -1).reshape(T * N, A + 1)
+    B = T * N
+    lp = torch.log_softmax(hv64[:, :A].detach(), -1)
+    actions = torch.multinomial(lp.exp().float(), 1, generator=g).squeeze(-1)
+    inp = dict(hv=hv64.detach().float(), actions=actions, old_logp=(lp.gather(-1, actions[:, None]).squeeze(-1) + 0.12 * torch.randn(B, generator=g).double()).float(),
+               old_v=hv64[:, A].detach().float() + 0.15 * torch.randn(B, generator=g), ret=torch.randn(B, generator=g),
+               nadv=torch.randn(B, generator=g), clip=0.1, vclip=0.1, vcoef=0.5, ecoef=0.01, grad_scale=1.0)
+    la, lv, ne, _, _ = ref.ppo_terms(hv64, actions, inp["old_logp"].double(), inp["old_v"].double(), inp["ret"].double(), inp["nadv"].double(), 0.1, 0.1)
+    total = la.mean() + 0.5 * lv.mean() + 0.01 * ne.mean()
+    names = list(sd)
+    ref_grads = dict(zip(names, torch.autograd.grad(total, [leaves[k] for k in names])))
+
+    h = PolicyHandle(**cfg)
+    flat = h.flatten(sd, DEV)
+    rows = feat.permute(0, 1, 3, 4, 2).reshape(B, S * S, C).contiguous().to(torch.bfloat16).to(DEV)
+    m = masks.reshape(-1).to(DEV)
+    f = lambda t: t.reshape(-1).contiguous().to(DEV)
+    runs = []
+    for fill in (0xFF, 0x00):
+        ws = torch.full((h.workspace_bytes(T, N, True),), fill, dtype=torch.uint8, device=DEV)
+        hv, _ = h.forward(flat, rows, goal.reshape(-1).to(DEV), h0[0].contiguous().to(DEV), m, T, N, ws)
+        dhv, sums = ppo.ppo_loss_raw(hv, f(actions), f(inp["old_logp"]), f(inp["old_v"]), f(inp["ret"]), f(inp["nadv"]), A)
+        grads = torch.zeros_like(flat)
+        h.backward(flat, rows, m, T, N, ws, dhv, None, grads)
+        torch.cuda.synchronize()
+        runs.append((hv.clone(), dhv.clone(), grads.clone()))
+    hv, dhv, grads = runs[0]
+    rel_f = ref.rel_l2(hv.cpu(), hv64.detach())
+    print("learn pass A %d: forward rel-L2 %.3e" % (A, rel_f))
+    assert rel_f < 2e-5
+    gv = h.views(grads)
+    worst = {k: ref.rel_l2(gv[k].cpu(), ref_grads[k]) for k in names}
+    print({k: "%.2e" % v for k, v in worst.items()})
+    for k, v in worst.items():
+        assert v < 2e-4, (k, v)
+    # every sum of a wide handle's learn pass has a fixed order: equal bits from a NaN-filled and a zero-filled workspace
+    for name, x, y in zip(("hv", "dhv", "grads"), runs[0], runs[1]):
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32)), "two learn passes differ in " + name
