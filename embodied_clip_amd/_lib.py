@@ -159,12 +159,22 @@ SIGNATURES = {
                          + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
     "ec_ppo_loss_wide_scratch_doubles": (c_int, []),
     "ec_ppo_loss_wide": (c_int, [c_void_p] * 9 + [C.c_long, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p]),
+    # previous-action embedding (the kernels alone): the weight-derived table, its gather-add onto gi, the binned ordered gradient
+    "ec_prev_action_table": (c_int, [c_void_p, c_void_p, C.c_long, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ec_prev_action_add": (c_int, [c_void_p] * 4 + [c_int, c_int, C.c_long, c_int, c_void_p]),
+    "ec_prev_action_grad_scratch_floats": (c_size_t, [C.c_long, c_int, c_int, c_int]),
+    "ec_policy_forward_pa": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 3),
+    "ec_policy_act_pa": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
+                         + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_prev_action_grad": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p, c_void_p, C.c_long, c_int] + [c_void_p] * 3
+                            + [C.c_long, c_int, c_int, c_void_p]),
 }
 
 
 class PolicyCfg(C.Structure):
     _fields_ = [(n, c_int) for n in ("in_channels", "spatial", "hidden", "goal_dims", "num_goals", "num_actions",
-                                     "compress_hid", "compress_out", "comb_hid", "comb_out", "fusion", "dual", "goal_in")]
+                                     "compress_hid", "compress_out", "comb_hid", "comb_out", "fusion", "dual", "goal_in",
+                                     "prev_action_dims", "prev_action_null")]
 
 _lib = None
 

@@ -265,6 +265,90 @@ void ec_heads_pack_launch(const float* Wa, const float* ba, const float* wc, con
 void ec_heads_unpack_add_launch(const float* gtab, float* gWa, float* gba, float* gwc, float* gbc, int A, int H, hipStream_t s);
 void ec_goal_group_sum_launch(const float* dm1, const int* goal, float* dE1, int S, int N, long B, int num_goals, hipStream_t s);
 
+// prev_action.hip: the previous-action embedding.  Row of the table that frame b selects, or -1.  null: row 0 is the null token
+// (an episode's first step, masks == 0) and action a
+// is row a + 1 -- ((prev + 1) * masks).long() for masks in {0, 1}; otherwise the action itself.  Compared as 64 bits: 1 << 32
+// is no action 0.
+__device__ __forceinline__ int ec_pa_index(const long long* __restrict__ prev, const float* __restrict__ masks, long b, int null_token,
+                                        int A) {
+    const long long a = prev[b];
+    if (null_token) {
+        if (masks[b] == 0.f) return 0;
+        return (a >= -1 && a < A) ? (int)a + 1 : -1;
+    }
+    return (a >= 0 && a < A) ? (int)a : -1;
+}
+
+// The act step's input projection (policy.hip gi_act_kernel<NW>: its header comment describes the tiling) as a body shared with
+// prev_action.hip's instance, which adds the previous action's row of the table PT in the fold, behind the bias (PA).  The PA = false
+// instantiation is gi_act_kernel's arithmetic as it was.
+struct ec_gi_act_pa { const float* pt; const long long* prev; const float* masks; int null_token, A; };
+template <int NW, bool PA>
+__device__ __forceinline__ void ec_gi_act_body(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
+                                               float* __restrict__ gi, int N, int K, int NO, const ec_gi_act_pa pax) {
+    __shared__ float part[NW][32][33];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 31, hh = lane >> 5;
+    const int j0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
+    const int kw = K / NW, k0 = wave * kw;
+    const float* pa = x + (long)min(n0 + i, N - 1) * K + k0 + 4 * hh;        // (rows past N are computed on a clamped row, never stored)
+    // W in fragment order (frag_pack_f32_kernel): group g of column block cb is the contiguous 1-KB unit (cb K/8 + g)
+    const f32x4_t* pbf = reinterpret_cast<const f32x4_t*>(W) + ((long)blockIdx.x * (K / 8) + k0 / 8) * 64 + lane;
+    f32x16_t acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    constexpr int U = 7;                                          // groups of 8 k in flight
+    for (int kb = 0; kb < kw; kb += 8 * U) {
+        f32x4_t a[U], b[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int kk = min(kb + 8 * u, kw - 8);                // (kw is a multiple of 8; a clamped group is skipped below)
+            a[u] = *reinterpret_cast<const f32x4_t*>(pa + kk);
+            b[u] = pbf[(kk >> 3) * 64];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (kb + 8 * u < kw) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][0], b[u][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][1], b[u][1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][2], b[u][2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][3], b[u][3], acc, 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * hh][i] = acc[r];     // C/D layout: row = actor, column = lane & 31
+    __syncthreads();
+    for (int e = tid; e < 32 * 32; e += NW * 64) {
+        const int row = e >> 5, col = e & 31;
+        float v = part[0][row][col];
+#pragma unroll
+        for (int w2 = 1; w2 < NW; ++w2) v += part[w2][row][col];
+        if (!PA) {
+            if (n0 + row < N) gi[(long)(n0 + row) * NO + j0 + col] = v + (bias ? bias[j0 + col] : 0.f);
+        } else if (n0 + row < N) {
+            float o = v + (bias ? bias[j0 + col] : 0.f);
+            const int r = ec_pa_index(pax.prev, pax.masks, n0 + row, pax.null_token, pax.A);
+            if (r >= 0) o += pax.pt[(long)r * NO + j0 + col];
+            gi[(long)(n0 + row) * NO + j0 + col] = o;
+        }
+    }
+}
+
+// ... and its launches for policy.hip: the table PT = Emb . Wa^T, gi[b] += PT[idx[b]], and the binned ordered gradient (scratch:
+// ec_pa_grad_scratch_floats floats; its first R * G hold dPT afterwards)
+void ec_pa_table_launch(const float* emb, const float* w, long ld, int col0, float* pt, int R, int G, int E, hipStream_t s);
+void ec_pa_add_launch(float* gi, const float* pt, const long long* prev, const float* masks, int null_token, int A, long B, int G,
+                      hipStream_t s);
+size_t ec_pa_grad_scratch_floats(long B, int G, int R);
+// gi_act_kernel<nw>'s launch (nw = 7 | 8) with the table row added in the fold; rows [rows, cols] copied between two row strides
+// (add == 0) or added (add == 1): weight_ih[:, :flat] as a dense copy, the dense gradient back onto the parameter's rows
+void ec_pa_gi_act_launch(int nw, const float* x, const float* W, const float* bias, float* gi, int N, int K, int NO, ec_gi_act_pa pa,
+                         hipStream_t s);
+void ec_pa_rows_copy_launch(const float* in, int ld_in, float* out, int ld_out, int rows, int cols, int add, hipStream_t s);
+void ec_pa_grad_launch(const float* dgi, const long long* prev, const float* masks, int null_token, int A, const float* emb,
+                       const float* w, long ld, int col0, float* demb, float* dw, float* scratch, long B, int G, int E, hipStream_t s);
+
 #define EC_CHECK_LAUNCH()                                   \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \

@@ -62,20 +62,21 @@ __global__ void from_cmajor_kernel(const float* __restrict__ dx, float* __restri
 // nn.Flatten's channel-major order (to_cmajor / from_cmajor: 2 x 206 MB of strided traffic per optimiser step, 0.5 ms),
 // the 9.6-MB weight_ih is re-ordered once per step: mode 0  out[r, p*Cc + c] = in[r, c*S + p];  mode 1 (its gradient,
 // back to the parameter's order)  out[r, c*S + p] += in[r, p*Cc + c].  One row per workgroup, staged through LDS.
+// ld: the row stride of the PARAMETER and of its gradient (mode 0's `in`, mode 1's `out`) -- flat, or flat + E on a handle with a
+// previous-action embedding, whose columns flat.. are not touched; the re-ordered copy is dense.
 __global__ __launch_bounds__(256) void permute_row_kernel(const float* __restrict__ in, float* __restrict__ out, int S, int Cc,
-                                                         int mode) {
+                                                         int mode, int ld) {
     extern __shared__ float prow[];
     const int flat = S * Cc;
-    const long base = (long)blockIdx.x * flat;
-    for (int i = threadIdx.x; i < flat; i += 256) prow[i] = in[base + i];
+    const long base = (long)blockIdx.x * flat, pbase = (long)blockIdx.x * ld;
+    for (int i = threadIdx.x; i < flat; i += 256) prow[i] = in[(mode == 0 ? pbase : base) + i];
     __syncthreads();
     if (mode == 0) {
         for (int i = threadIdx.x; i < flat; i += 256) out[base + i] = prow[(i % Cc) * S + i / Cc];
     } else {
-        for (int i = threadIdx.x; i < flat; i += 256) out[base + i] += prow[(i % S) * Cc + i / S];
+        for (int i = threadIdx.x; i < flat; i += 256) out[pbase + i] += prow[(i % S) * Cc + i / S];
     }
 }
-
 // torch.nn.GRU cell with the RNNStateEncoder episode mask:
 //   hp = m*h_prev;  r = s(gi_r + m*gh_r + b_hr);  z = s(gi_z + m*gh_z + b_hz)
 //   hn = m*gh_n + b_hn;  n = tanh(gi_n + r*hn);  h = (1-z)*n + z*hp
@@ -841,46 +842,7 @@ template <int NW>
 __global__ __launch_bounds__(NW * 64) void gi_act_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                          const float* __restrict__ bias, float* __restrict__ gi, int N, int K,
                                                          int NO) {
-    __shared__ float part[NW][32][33];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, hh = lane >> 5;
-    const int j0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-    const int kw = K / NW, k0 = wave * kw;
-    const float* pa = x + (long)min(n0 + i, N - 1) * K + k0 + 4 * hh;        // (rows past N are computed on a clamped row, never stored)
-    // W in fragment order (frag_pack_f32_kernel): group g of column block cb is the contiguous 1-KB unit (cb K/8 + g)
-    const f32x4_t* pbf = reinterpret_cast<const f32x4_t*>(W) + ((long)blockIdx.x * (K / 8) + k0 / 8) * 64 + lane;
-    f32x16_t acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    constexpr int U = 7;                                          // groups of 8 k in flight
-    for (int kb = 0; kb < kw; kb += 8 * U) {
-        f32x4_t a[U], b[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int kk = min(kb + 8 * u, kw - 8);                // (kw is a multiple of 8; a clamped group is skipped below)
-            a[u] = *reinterpret_cast<const f32x4_t*>(pa + kk);
-            b[u] = pbf[(kk >> 3) * 64];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (kb + 8 * u < kw) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][0], b[u][0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][1], b[u][1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][2], b[u][2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][3], b[u][3], acc, 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * hh][i] = acc[r];     // C/D layout: row = actor, column = lane & 31
-    __syncthreads();
-    for (int e = tid; e < 32 * 32; e += NW * 64) {
-        const int row = e >> 5, col = e & 31;
-        float v = part[0][row][col];
-#pragma unroll
-        for (int w2 = 1; w2 < NW; ++w2) v += part[w2][row][col];
-        if (n0 + row < N) gi[(long)(n0 + row) * NO + j0 + col] = v + (bias ? bias[j0 + col] : 0.f);
-    }
+    ec_gi_act_body<NW, false>(x, W, bias, gi, N, K, NO, ec_gi_act_pa{});      // (the body: common.h, shared with prev_action.hip's instance)
 }
 
 // Act step: the compressor's first 1x1 conv over the slice's bf16 feature rows, c1[M][NO] = relu(feat[M][K] W1[NO][K]^T + b1)
@@ -1528,7 +1490,9 @@ enum { P_EMB, P_W1, P_B1, P_W2, P_B2, P_W3, P_B3, P_W4, P_B4, P_WIH, P_WHH, P_BI
        // dual (RGB + depth) encoder: the depth stream's compressor / combiner, same shapes as P_W1 .. P_B4
        P_W1D, P_B1D, P_W2D, P_B2D, P_W3D, P_B3D, P_W4D, P_B4D,
        // coordinate goals (goal_in > 0): P_EMB is embed_goal.weight [goal_dims, goal_in], P_GB is embed_goal.bias, second in the flat order
-       P_GB, P_COUNT };
+       P_GB,
+       // previous-action embedding (prev_action_dims > 0): prev_action_embedder.fc.weight [num_actions + null, E], last in the flat order
+       P_PAE, P_COUNT };
 constexpr int P_COUNT_SINGLE = P_BC + 1, P_COUNT_DUAL = P_B4D + 1, P_COUNT_VEC = P_COUNT_SINGLE + 1;
 
 }  // namespace
@@ -1672,6 +1636,7 @@ struct Geo {
     int S, M49;                   // pixels per frame; B * S rows through compressor and combiner (0 in fusion mode)
     int H, A, A1, C, cat;         // hidden size; actions, actions + critic; feature channels; compress_out + goal_dims
     int nstream, flat1, flat;     // encoder streams (2: dual RGB + depth); one stream's / the whole GRU input width
+    int E, R, ldw;                // previous-action embedding: width (0: none), table rows, weight_ih's row stride flat + E
 };
 
 struct Ws {   // float offsets into the workspace
@@ -1687,6 +1652,9 @@ struct Ws {   // float offsets into the workspace
     // learn pass of a wide handle (A + 1 > 8; all empty otherwise): both heads as one table [Wa; wc | ba; bc] ((A + 1) * H
     // weights, then A + 1 biases), the table's gradient in the same layout, the row-block partials of its column sum
     size_t hW, hG, hP;
+    // previous-action embedding (all empty with prev_action_dims == 0): the table PT [R, 3H] (weight-derived: kept with E1 under
+    // EC_POLICY_INFER_REUSE); the learn pass's copy of the int64 indices; ec_pa_grad_launch's scratch
+    size_t pt, paidx, pas;
 };
 constexpr int GP_MAXY = 64;                   // row blocks of tn_small_part_kernel
 constexpr int HP_MAXY = 128;                  // row blocks of the wide heads' column sum
@@ -1765,6 +1733,10 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
     const bool wide = bwd && g.A1 > 8;
     w.hW = take_if(wide, (size_t)g.A1 * H + g.A1); w.hG = take_if(wide, (size_t)g.A1 * H + g.A1);
     w.hP = take_if(wide, (size_t)HP_MAXY * g.A1);
+    const bool pa = g.E > 0;
+    w.pt = take_if(pa, (size_t)g.R * 3 * H);
+    w.paidx = take_if(pa && bwd, 2 * B);
+    w.pas = take_if(pa && bwd, pa ? ec_pa_grad_scratch_floats((long)B, 3 * g.H, g.R) : 0);
     w.end = o;
     return w;
 }
@@ -1780,6 +1752,7 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     g.S = c.spatial * c.spatial; g.M49 = c.fusion ? 0 : g.B * g.S;
     g.H = c.hidden; g.A = c.num_actions; g.A1 = g.A + 1; g.C = c.in_channels; g.cat = c.compress_out + c.goal_dims;
     g.nstream = (c.dual && !c.fusion) ? 2 : 1; g.flat1 = c.comb_out * g.S; g.flat = c.fusion ? c.in_channels : g.nstream * g.flat1;
+    g.E = c.prev_action_dims; g.R = c.num_actions + c.prev_action_null; g.ldw = g.flat + g.E;   // (no route below depends on E)
     const int B = g.B, S = g.S, M49 = g.M49, H = g.H, C = g.C, flat = g.flat;
     p.infer = mode != EC_POLICY_LEARN; p.feat_bf16 = feat_bf16; p.vec = c.goal_in > 0;
     p.wide = !p.infer && g.A1 > 8;
@@ -1872,6 +1845,18 @@ struct Fwd : Ctx {
     using Ctx::Ctx;
     const int* goal_ids = nullptr;   // int32 ids in the workspace, or (goal_direct) the caller's int64 ids
     bool reuse = false;              // EC_POLICY_INFER_REUSE, and this workspace holds the tables of this plan
+    const long long* prev = nullptr; // previous actions [B] (handles with a previous-action embedding)
+    const float* masks_all = nullptr;
+
+    // weight_ih[:, :flat] where the GEMMs of the routes that keep the parameter's column order read it: the parameter itself, or on a
+    // handle with a previous-action embedding (row stride flat + E) its dense copy -- in the learn pass's / the act tables' area
+    // of the re-ordered weight, which those routes leave unused
+    const float* wih_plain() const { return g.E ? ws + (p.infer ? w.wihA : w.wihP) : W(P_WIH); }
+    // previous-action embedding: the table (with the other weight-derived tables) and, for a backward, the indices
+    void prev_action_tables() {
+        if (!reuse) ec_pa_table_launch(W(P_PAE), W(P_WIH), g.ldw, g.flat, ws + w.pt, g.R, 3 * g.H, g.E, s);
+        if (!p.infer) (void)hipMemcpyAsync(ws + w.paidx, prev, (size_t)g.B * 8, hipMemcpyDeviceToDevice, s);
+    }
 
     // coordinate goals: this call's per-frame bias rows (and, for a backward, the goal vectors and embeddings it will need)
     static size_t goal_vec_lds(const ec_policy_cfg& c, bool bwd) {
@@ -1963,9 +1948,11 @@ struct Fwd : Ctx {
             const long total = (long)g.B * g.flat1;
             hipLaunchKernelGGL(to_cmajor_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws + o.x4, ws + w.x,
                                g.S, c.comb_out, total, g.flat, sidx * g.flat1);
+            if (g.E && (!p.infer || !reuse))
+                ec_pa_rows_copy_launch(W(P_WIH), g.ldw, ws + (p.infer ? w.wihA : w.wihP), g.flat, 3 * g.H, g.flat, 0, s);
         } else if (p.wih == Wih::perm_learn || !reuse) {
             hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * g.H)), dim3(256), g.flat * sizeof(float), s, W(P_WIH),
-                               ws + (p.wih == Wih::perm_learn ? w.wihP : w.wihA), g.S, c.comb_out, 0);
+                               ws + (p.wih == Wih::perm_learn ? w.wihP : w.wihA), g.S, c.comb_out, 0, g.ldw);
         }
         return EC_OK;
     }
@@ -1982,14 +1969,22 @@ struct Fwd : Ctx {
                                    (float4*)(ws + w.wihF), 3 * H, flat);
             }
             const int nw = p.gi == Gi::act7 ? 7 : 8;                     // waves of a workgroup
-            hipLaunchKernelGGL(nw == 7 ? gi_act_kernel<7> : gi_act_kernel<8>, dim3((unsigned)(3 * H / 32), (unsigned)((B + 31) / 32)), dim3(64 * nw), 0, s,
+            const dim3 grid((unsigned)(3 * H / 32), (unsigned)((B + 31) / 32));
+            if (g.E)      // the previous action's table row rides in the fold (prev_action.hip's instance of the same body): as many launches
+                ec_pa_gi_act_launch(nw, xin, win, W(P_BIH), ws + w.gi, B, flat, 3 * H,
+                                    ec_gi_act_pa{ws + w.pt, prev, masks_all, c.prev_action_null, c.num_actions}, s);
+            else
+            hipLaunchKernelGGL(nw == 7 ? gi_act_kernel<7> : gi_act_kernel<8>, grid, dim3(64 * nw), 0, s,
                                xin, win, W(P_BIH), ws + w.gi, B, flat, 3 * H);
             return EC_OK;
         }
         const float* xin = p.wih == Wih::plain ? ws + w.x : ws + w.st[0].x4;
-        const float* win = p.wih == Wih::perm_learn ? ws + w.wihP : (p.wih == Wih::perm_act ? ws + w.wihA : W(P_WIH));
-        return ec_gemm_f32(xin, win, ws + w.gi, B, 3 * H, flat, flat, 1, 1, flat, 3 * H, p.gi == Gi::split_parts ? EC_GEMM_SPLIT_PARTS : 0,
-                           W(P_BIH), nullptr, nullptr, 0, nullptr, nullptr, p.gi_fold, stream);
+        const float* win = p.wih == Wih::perm_learn ? ws + w.wihP : (p.wih == Wih::perm_act ? ws + w.wihA : wih_plain());
+        RC(ec_gemm_f32(xin, win, ws + w.gi, B, 3 * H, flat, flat, 1, 1, flat, 3 * H, p.gi == Gi::split_parts ? EC_GEMM_SPLIT_PARTS : 0,
+                       W(P_BIH), nullptr, nullptr, 0, nullptr, nullptr, p.gi_fold, stream));
+        // the previous action's table row, onto part 0 of a split-K projection (the step kernel folds the parts in order)
+        if (g.E) ec_pa_add_launch(ws + w.gi, ws + w.pt, prev, masks_all, c.prev_action_null, c.num_actions, (long)B, 3 * H, s);
+        return EC_OK;
     }
 
     // the sequential recurrence; step t's new state goes to hs + t * N * H
@@ -2055,8 +2050,11 @@ bool tables_reusable(const ec_policy* h, const void* workspace, const Plan& p, i
 
 int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16, const int64_t* goal,
                         const float* goal_vec, const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int mode, float* hv,
-                        float* h_final, const SampleArgs& smp, ec_stream_t stream, const ForceArgs* wide = nullptr) {
+                        float* h_final, const SampleArgs& smp, ec_stream_t stream, const ForceArgs* wide = nullptr,
+                        const int64_t* prev_actions = nullptr, bool pa_entry = false) {
     if (!h || !params || !feat || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
+    // previous-action embedding: the _pa entry points on such a handle, with the actions; every other pairing is refused
+    if (pa_entry != (h->c.prev_action_dims > 0) || (pa_entry && !prev_actions)) return EC_ERR_ARG;
     if (h->c.goal_in > 0 ? (!goal_vec || goal) : (!goal || goal_vec)) return EC_ERR_ARG;   // the entry point of the handle's goal type
     if (h->c.dual && !feat2) return EC_ERR_ARG;
     if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
@@ -2070,6 +2068,7 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
     if (!h->c.fusion)
         for (int sidx = 0; sidx < p.g.nstream; ++sidx)   // dual encoder: the RGB stream, then the depth stream (own weights, own activations)
             RC(f.encoder_stream(sidx, sidx ? feat2 : feat));
+    if (p.g.E) { f.prev = (const long long*)prev_actions; f.masks_all = masks; f.prev_action_tables(); }
     RC(f.input_projection());
     float* hs = (p.hs_direct && h_final && h_final != h0) ? h_final : f.ws + p.w.hs;
     RC(f.recurrence(h0, masks, hs));
@@ -2081,6 +2080,7 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
 struct Bwd : Ctx {
     using Ctx::Ctx;
     float* grads = nullptr;
+    const float* masks_all = nullptr;   // (previous-action embedding: the null token's selector)
     bool parts_ok = true;         // the dx area is free for partial matrices (cleared once dx occupies it)
     float* G(int i, int sidx = 0) const { return grads + off(i, sidx); }
 
@@ -2201,11 +2201,19 @@ struct Bwd : Ctx {
             (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)3 * H * flat * 4, s);
             RC(tn_gru(ws + w.dgi, ws + w.st[0].x4, ws + w.gwihP, 3 * H, flat, B));
             hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * H)), dim3(256), flat * sizeof(float), s, ws + w.gwihP,
-                               G(P_WIH), g.S, c.comb_out, 1);
+                               G(P_WIH), g.S, c.comb_out, 1, g.ldw);
+        } else if (g.E) {                 // the dense gradient, then added back onto the parameter's rows (stride flat + E)
+            (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)3 * H * flat * 4, s);
+            RC(tn_gru(ws + w.dgi, ws + w.x, ws + w.gwihP, 3 * H, flat, B));
+            ec_pa_rows_copy_launch(ws + w.gwihP, flat, G(P_WIH), g.ldw, 3 * H, flat, 1, s);
         } else {
             RC(tn_gru(ws + w.dgi, ws + w.x, G(P_WIH), 3 * H, flat, B));
         }
         colsum(ws + w.dgi, G(P_BIH), B, 3 * H, 3 * H);
+        // previous-action embedding: its gradient and columns flat.. of weight_ih's (inside the recurrent section: before the event)
+        if (g.E)
+            ec_pa_grad_launch(ws + w.dgi, (const long long*)(ws + w.paidx), masks_all, c.prev_action_null, c.num_actions, W(P_PAE), W(P_WIH),
+                              g.ldw, flat, G(P_PAE), G(P_WIH), ws + w.pas, (long)B, 3 * H, g.E, s);
         return EC_OK;
     }
 
@@ -2213,7 +2221,7 @@ struct Bwd : Ctx {
     int input_grad() {
         const int B = g.B, H = g.H, flat = g.flat;
         if (p.wih != Wih::perm_learn)
-            return gemm(ws + w.dgi, W(P_WIH), ws + w.dx, B, flat, 3 * H, 3 * H, 1, flat, 1, flat, p.bwd3);
+            return gemm(ws + w.dgi, g.E ? ws + w.wihP : W(P_WIH), ws + w.dx, B, flat, 3 * H, 3 * H, 1, flat, 1, flat, p.bwd3);   // (E: the forward's dense copy)
         // The weight is transposed first (9.6 MB, into the gradient staging buffer, free again by now) so that BOTH operands are
         // K-contiguous: the GEMM's strided-B staging runs at half the rate (263 vs ~130 us at 32 actors, 770 vs ~540 at 128)
         hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((flat + 31) / 32), (unsigned)(3 * H / 32)), dim3(256), 0, s,
@@ -2331,6 +2339,9 @@ extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) {
     if (c.dual && c.fusion) return EC_ERR_ARG;
     if (c.goal_in < 0 || c.goal_in > 8 || (c.goal_in && c.fusion)) return EC_ERR_ARG;
     if (c.goal_in && c.dual) return EC_ERR_UNSUPPORTED;
+    if (c.prev_action_dims < 0 || c.prev_action_dims > 64 || (c.prev_action_null != 0 && c.prev_action_null != 1)) return EC_ERR_ARG;
+    if (c.prev_action_null && !c.prev_action_dims) return EC_ERR_ARG;
+    if (c.prev_action_dims && (c.dual || c.fusion)) return EC_ERR_UNSUPPORTED;   // (the two-tower and zero-shot agents: not built)
     if (c.in_channels <= 0 || c.spatial <= 0 || c.hidden <= 0 || (c.num_goals <= 0 && !c.goal_in) || c.num_actions <= 0) return EC_ERR_SHAPE;
     if ((c.in_channels & 3) || (c.hidden & 3)) return EC_ERR_SHAPE;
     if (c.fusion) {
@@ -2354,20 +2365,24 @@ extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) {
                                (size_t)c.compress_out * c.compress_hid, (size_t)c.compress_out,
                                (size_t)c.comb_hid * (c.compress_out + c.goal_dims), (size_t)c.comb_hid,
                                (size_t)c.comb_out * c.comb_hid, (size_t)c.comb_out,
-                               3 * H * flat, 3 * H * H, 3 * H, 3 * H,
+                               3 * H * (flat + c.prev_action_dims), 3 * H * H, 3 * H, 3 * H,
                                (size_t)c.num_actions * H, (size_t)c.num_actions, H, 1, 0, 0, 0, 0, 0, 0, 0, 0,
-                               c.goal_in ? (size_t)c.goal_dims : 0};
+                               c.goal_in ? (size_t)c.goal_dims : 0,
+                               (size_t)(c.num_actions + c.prev_action_null) * c.prev_action_dims};
     if (c.fusion)
         for (int i = P_EMB; i <= P_B4; ++i) n[i] = 0;      // no goal embedding / compressor / combiner: GRU + heads only
     if (c.dual)
         for (int i = P_W1; i <= P_B4; ++i) n[i + (P_W1D - P_W1)] = n[i];
-    // flat order: the enum's, except that embed_goal.bias follows embed_goal.weight
+    // flat order: the enum's, except that embed_goal.bias follows embed_goal.weight and the previous-action embedding follows
+    // critic.fc.bias (the depth stream's tensors have zero elements on such a handle: it is the last tensor)
     h->ntensors = 0;
     for (int i = 0; i < P_COUNT_DUAL; ++i) {
         h->order[h->ntensors++] = i;
         if (i == P_EMB && c.goal_in) h->order[h->ntensors++] = P_GB;
+        if (i == P_BC && c.prev_action_dims) h->order[h->ntensors++] = P_PAE;
     }
     if (!c.goal_in) h->order[h->ntensors++] = P_GB;          // (zero elements)
+    if (!c.prev_action_dims) h->order[h->ntensors++] = P_PAE; // (zero elements)
     size_t o = 0;
     for (int k = 0; k < P_COUNT; ++k) { const int i = h->order[k]; h->off[i] = o; h->num[i] = n[i]; o += (n[i] + 3) / 4 * 4; }   // 16-B aligned
     h->total = o;
@@ -2381,7 +2396,7 @@ extern "C" int ec_policy_set_goal_table(ec_policy_t* h, const float* table) {
     return EC_OK;
 }
 extern "C" int ec_policy_num_param_tensors(const ec_policy_t* h) {
-    return (h && h->c.dual) ? P_COUNT_DUAL : ((h && h->c.goal_in) ? P_COUNT_VEC : P_COUNT_SINGLE);
+    return ((h && h->c.dual) ? P_COUNT_DUAL : ((h && h->c.goal_in) ? P_COUNT_VEC : P_COUNT_SINGLE)) + ((h && h->c.prev_action_dims) ? 1 : 0);
 }
 extern "C" size_t ec_policy_flat_size(const ec_policy_t* h) { return h ? h->total : 0; }
 extern "C" int ec_policy_param_offset(const ec_policy_t* h, int idx, size_t* off, size_t* numel) {
@@ -2420,7 +2435,7 @@ extern "C" int ec_policy_act(const ec_policy_t* h, const float* params, const vo
                              const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                              int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                              uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream) {
-    if (!actions || !logp) return EC_ERR_ARG;
+    if (!actions || !logp || (h && h->c.prev_action_dims)) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa)
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;       // (the one-wave-per-row heads launch)
     const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, 1, N, workspace, ws_bytes,
@@ -2430,7 +2445,7 @@ extern "C" int ec_policy_act_vec(const ec_policy_t* h, const float* params, cons
                                  const float* goal_vec, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                                  int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                                  uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream) {
-    if (!actions || !logp) return EC_ERR_ARG;
+    if (!actions || !logp || (h && h->c.prev_action_dims)) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa)
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
     const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
@@ -2444,7 +2459,7 @@ extern "C" int ec_policy_act_greedy(const ec_policy_t* h, const float* params, c
                                     const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                                     int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                                     ec_stream_t stream) {
-    if (!actions || !logp) return EC_ERR_ARG;
+    if (!actions || !logp || (h && h->c.prev_action_dims)) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa)
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
     const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, 1, N, workspace, ws_bytes,
@@ -2454,7 +2469,7 @@ extern "C" int ec_policy_act_vec_greedy(const ec_policy_t* h, const float* param
                                         const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
                                         size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
                                         float* values, ec_stream_t stream) {
-    if (!actions || !logp) return EC_ERR_ARG;
+    if (!actions || !logp || (h && h->c.prev_action_dims)) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa)
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
     const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
@@ -2463,12 +2478,13 @@ extern "C" int ec_policy_act_vec_greedy(const ec_policy_t* h, const float* param
 
 // The act step in one call for every handle (include/ec_amd.h).  More than 7 actions: the stages in front as they are, then the
 // wide heads launch with the selection (and the forcing) in it; up to 7: what ec_policy_act* launch, then ec_teacher_force's launch.
-extern "C" int ec_policy_act_ex(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
-                                const int64_t* goal, const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
-                                size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
-                                float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
-                                const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
+static int policy_act_any(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                          const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, bool pa_entry, const float* h0,
+                          const float* masks, int N, void* workspace, size_t ws_bytes, int reuse_tables, float* hv, float* h_final,
+                          int64_t* actions, float* logp, float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
+                          const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
     if (!h || !actions || !logp) return EC_ERR_ARG;
+    if (pa_entry != (h->c.prev_action_dims > 0) || (pa_entry && !prev_actions)) return EC_ERR_ARG;
     if ((expert_actions != nullptr) != (expert_mask != nullptr)) return EC_ERR_ARG;
     if (!(force_p >= 0.f && force_p <= 1.f)) return EC_ERR_ARG;       // (NaN included)
     if (!expert_actions && force_p != 0.f) return EC_ERR_ARG;
@@ -2480,11 +2496,38 @@ extern "C" int ec_policy_act_ex(const ec_policy_t* h, const float* params, const
     const int mode = reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER;
     if (h->c.num_actions + 1 > 8)
         return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, 1, N, workspace, ws_bytes, mode, hv, h_final,
-                                   smp, stream, &force);
+                                   smp, stream, &force, prev_actions, pa_entry);
     const int rc = policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, 1, N, workspace, ws_bytes, mode, hv,
-                                       h_final, smp, stream);
+                                       h_final, smp, stream, nullptr, prev_actions, pa_entry);
     if (rc != EC_OK || !expert_actions) return rc;
     return ec_teacher_force(hv, expert_actions, expert_mask, force_p, actions, logp, N, h->c.num_actions, seed, step, first_actor, stream);
+}
+extern "C" int ec_policy_act_ex(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                                const int64_t* goal, const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
+                                size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
+                                float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
+                                const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
+    return policy_act_any(h, params, feat, feat2, feat_bf16, goal, goal_vec, nullptr, false, h0, masks, N, workspace, ws_bytes, reuse_tables,
+                          hv, h_final, actions, logp, values, greedy, seed, step, first_actor, expert_actions, expert_mask, force_p, stream);
+}
+
+// Handles with a previous-action embedding (include/ec_amd.h): ec_policy_forward_vec / ec_policy_act_ex with both goal arguments
+// and the previous actions
+extern "C" int ec_policy_forward_pa(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                                    const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, const float* h0,
+                                    const float* masks, int T, int N, void* workspace, size_t ws_bytes, int for_backward, float* hv,
+                                    float* h_final, ec_stream_t stream) {
+    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, T, N, workspace, ws_bytes, for_backward, hv,
+                               h_final, SampleArgs{}, stream, nullptr, prev_actions, true);
+}
+extern "C" int ec_policy_act_pa(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                                const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, const float* h0,
+                                const float* masks, int N, void* workspace, size_t ws_bytes, int reuse_tables, float* hv, float* h_final,
+                                int64_t* actions, float* logp, float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
+                                const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
+    return policy_act_any(h, params, feat, feat2, feat_bf16, goal, goal_vec, prev_actions, true, h0, masks, N, workspace, ws_bytes,
+                          reuse_tables, hv, h_final, actions, logp, values, greedy, seed, step, first_actor, expert_actions, expert_mask,
+                          force_p, stream);
 }
 
 extern "C" int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,
@@ -2511,6 +2554,7 @@ extern "C" int ec_policy_backward3(const ec_policy_t* h, const float* params, co
     if (ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
     Bwd b(h, p, params, workspace, stream);
     b.grads = grads;
+    b.masks_all = masks;
     RC(b.heads(dhv));
     RC(b.recurrence(masks, dh_final));
     RC(b.gru_grads());

@@ -135,6 +135,18 @@ class _Slice:
     pass
 
 
+def check_prev_actions(prev_actions: int, depth: bool, zeroshot: bool) -> int:
+    """``Worker`` / ``Evaluator`` ``(prev_actions=E)``: the embedding's width, refused where the policy library refuses it."""
+    E = int(prev_actions)
+    if not 0 <= E <= 64:
+        raise ValueError(f"prev_actions={prev_actions}: the embedding's width is 0 (off) or 1..64")
+    if E and depth:
+        raise ValueError("prev_actions > 0 with depth=True: the dual (RGB + depth) goal encoder with previous actions is not built")
+    if E and zeroshot:
+        raise ValueError("prev_actions > 0 with zeroshot=True: the zero-shot fusion policy with previous actions is not built")
+    return E
+
+
 def check_rgbd(encoder: str, zeroshot: bool, goal_in: int, frames_host: bool) -> None:
     """What ``depth=True`` (the RGB-D agent) cannot be combined with; raised before anything is allocated."""
     if encoder not in ("rn50", "rn50x16"):
@@ -147,6 +159,14 @@ def check_rgbd(encoder: str, zeroshot: bool, goal_in: int, frames_host: bool) ->
         raise ValueError("depth=True: host-resident frames (frames_host=True) have no depth staging path")
 
 
+def check_model_tensors(policy, sd, where: str) -> None:
+    """A checkpoint's ``model_state_dict`` against the handle's tensors: a missing one (a checkpoint written without the
+    previous-action embedding, loaded by an agent that has it) raises, naming the tensor and the file."""
+    for name in policy.offsets:
+        if name not in sd:
+            raise KeyError(f"{where}: the checkpoint lacks the tensor {name!r} {tuple(policy.shapes[name])} of this agent")
+
+
 class _SlicedActor:
     """What a training ``Worker`` and an ``evaluate.Evaluator`` share: the frozen encoder handles and the policy handle, the
     actor slices with their streams, act workspaces and feature buffers, and hot loop A's encode step.  The users set
@@ -157,6 +177,10 @@ class _SlicedActor:
     env's depth batch (``RN50Trunk.forward_depth``: same frozen weights, one-channel stem) into a second feature buffer
     ``sl.feat2``, and the policy is the dual-encoder variant."""
     depth = False
+    # the previous action's embedding ([U] VisualNavActorCritic add_prev_actions / Habitat's prev_action_embedding): its width
+    # (0: off) and whether row 0 is the null token of an episode's first step; set by the users before ``_build_model``
+    prev_action_dims = 0
+    prev_action_null = 0
 
     def _build_model(self, n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams):
         """Encoder handles (one per slice, weights shared), the policy handle and its flat parameters.  -> (encs, pools)"""
@@ -210,6 +234,8 @@ class _SlicedActor:
         if self.zeroshot:
             assert encoder == "rn50", "the zero-shot variant uses the CLIP-RN50 image embedding"
             pkw["fusion"] = 1
+        if self.prev_action_dims:
+            pkw.update(prev_action_dims=self.prev_action_dims, prev_action_null=self.prev_action_null)
         self.policy = PolicyHandle(**pkw)
         if self.zeroshot:
             # goal table: the CLIP text tower over the 12 goal prompts, once, L2-normalised; frozen
@@ -402,7 +428,7 @@ class Worker(_SlicedActor):
                  num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
                  overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False,
                  nav_metrics: bool = False, depth: bool = False, loss: str = "ppo", il_weight: float = 1.0,
-                 teacher_forcing=None):
+                 teacher_forcing=None, prev_actions: int = 0, prev_action_null_token: bool = True):
         """``loss``: what a rollout is trained on -- "ppo" (GAE, then the PPO loss: the default), "imitation" (the expert
         cross-entropy of [U] AllenAct's ``Imitation`` loss on the env's expert actions; no GAE launch) or "ppo+imitation"
         (``ppo_total + il_weight * imitation``: the PPO call writes d(total)/d(hv), the imitation call adds its term).
@@ -410,7 +436,15 @@ class Worker(_SlicedActor):
         (``imitation.LinearDecay`` / ``StepwiseLinearDecay``) giving the probability p with which a step that has an expert
         action TAKES it ([U] ``TeacherForcingDistr``; DAgger is a p that decays from 1): evaluated once per rollout, at the
         rollout's first ``total_steps``; one small launch behind every sampling act step while p > 0, none otherwise.  With
-        the defaults nothing of this runs and the env builds no expert.  The imitation normaliser (the number of steps with an
+        the defaults nothing of this runs and the env builds no expert.
+
+        ``prev_actions=E > 0``: the agent also conditions on its previous action ([U] VisualNavActorCritic ``add_prev_actions``,
+        ``action_embed_size=E``; Habitat's ``prev_action_embedding``, E = 32) -- ``PolicyHandle(prev_action_dims=E)``, one more
+        parameter tensor.  ``prev_action_null_token`` (default True, Habitat's rule): an episode's first step reads the null
+        row.  The rollout's ``actions`` are rows 1..T of a ``[T + 1, N]`` buffer whose row ``t`` is step ``t``'s previous action
+        (row 0: the previous rollout's last), so the act step's selection and the teacher forcing write where the next step
+        reads -- no copy.  Works with every ``loss``, teacher forcing, ``goal_in``, up to 256 actions, ``sync_actions``;
+        ``ValueError`` with ``depth=True`` or ``zeroshot=True``.  The imitation normaliser (the number of steps with an
         expert action in a minibatch range) is rank-local, as the advantage normalisation is.
 
         ``depth=True``: the RGB-D agent (readme_files/baselines_habitat.md:75; [U] a second ClipResNetPreprocessor on the
@@ -432,6 +466,8 @@ class Worker(_SlicedActor):
         (text tower run once -> [12, 1024] table) and the policy is the fusion=1 variant (GRU + heads trainable)."""
         if depth:
             check_rgbd(encoder, zeroshot, goal_in, frames_host)
+        self.prev_action_dims = check_prev_actions(prev_actions, bool(depth), bool(zeroshot))
+        self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
         self.depth = bool(depth)
         self.lib = _lib.load()
         self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
@@ -491,7 +527,12 @@ class Worker(_SlicedActor):
         self.opt = FlatAdam(self.params, lr=lr, max_grad_norm=max_grad_norm)
         N = n_actors
         # [T, N] rollout scalars (global; tiny)
-        self.actions = torch.zeros((T, N), dtype=torch.int64, device=d)
+        if self.prev_action_dims:     # row t: step t's previous action; rows 1..T ARE the rollout's actions, row 0 the last rollout's last
+            self.prev_actions = torch.zeros((T + 1, N), dtype=torch.int64, device=d)
+            self.actions = self.prev_actions[1:]
+        else:
+            self.prev_actions = None
+            self.actions = torch.zeros((T, N), dtype=torch.int64, device=d)
         self.logp = torch.zeros((T, N), dtype=torch.float32, device=d)
         self.values = torch.zeros((T + 1, N), dtype=torch.float32, device=d)
         self.returns = torch.zeros((T + 1, N), dtype=torch.float32, device=d)
@@ -523,7 +564,7 @@ class Worker(_SlicedActor):
             sl.rec_ready = torch.cuda.Event()
             sl.rec_ready.record()          # (torch creates the hipEvent_t at the first record: the library needs the handle)
             sl.sums = torch.zeros(4, dtype=torch.float64, device=d)
-            sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = None
+            sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = sl.prev = None
             # more than 16 actions: the wide loss kernel's partial-sum scratch, one per slice stream as for imitation
             sl.ppo_scratch = ppo_wide_scratch(d) if (self._ppo and self.A > PPO_NARROW_MAX_A) else None
             if self._il:      # the imitation loss's sums and partial-sum scratch: one per slice stream
@@ -548,11 +589,12 @@ class Worker(_SlicedActor):
         o, n, sp = sl.o, sl.n, _lib.stream_ptr()
         rs = slice(o, o + n)
         h_in, h_out = (self.h, self.h_next) if (t & 1) == 0 else (self.h_next, self.h)   # ping-pong by step parity
+        pa = self.prev_actions[t][rs] if self.prev_action_dims else None                  # (the bootstrap step reads row T)
         if sample and self._act_fused:
             # forward + CategoricalDistr.sample / log_prob in one call: the heads launch samples (ec_policy_act, one launch less)
             self.policy.act(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act,
                             self.hv_act[rs], h_out[rs], self.actions[t][rs], self.logp[t][rs], self.values[t][rs], self.seed,
-                            self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t))
+                            self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa)
             sl.act_tables_valid = True
             self._teacher_force_slice(sl, t)
             return
@@ -563,12 +605,13 @@ class Worker(_SlicedActor):
                                self.hv_act[rs], h_out[rs], self.actions[t][rs], self.logp[t][rs], self.values[t][rs], self.seed,
                                self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t),
                                expert_actions=self.env.expert_actions[t][rs] if tf else None,
-                               expert_mask=self.env.expert_mask[t][rs] if tf else None, force_p=self._tf_p if tf else 0.0)
+                               expert_mask=self.env.expert_mask[t][rs] if tf else None, force_p=self._tf_p if tf else 0.0,
+                               prev_actions=pa)
             sl.act_tables_valid = True
             return
         self.policy.forward(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n,
                             sl.ws_act, hv=self.hv_act[rs], h_final=h_out[rs], for_backward=False,
-                            reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t))      # (E1 depends on the parameters only)
+                            reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa)   # (E1 depends on the parameters only)
         sl.act_tables_valid = True
         if sample:
             _lib.check(self.lib.ec_sample_actions(self.hv_act[rs].data_ptr(), self.actions[t][rs].data_ptr(),
@@ -703,6 +746,8 @@ class Worker(_SlicedActor):
             sl.ret, sl.nadv = c(self.returns), c(self.nadv)
             if self._il:
                 sl.ex_a, sl.ex_m = c(self.env.expert_actions), c(self.env.expert_mask)
+            if self.prev_action_dims:
+                sl.prev = c(self.prev_actions)        # rows 0..T-1: every step's previous action
 
     def minibatch_ranges(self):
         """[U] allenact ``RolloutStorage.recurrent_generator``: the samplers (actors) are cut at
@@ -747,6 +792,14 @@ class Worker(_SlicedActor):
             return sl.ex_a, sl.ex_m
         c = lambda x: x.view(self.T, sl.n)[:, a:b].reshape(-1).contiguous()
         return c(sl.ex_a), c(sl.ex_m)
+
+    def _gather_prev(self, sl, a: int, b: int):
+        """The previous actions of the batch ``_gather_part(sl, a, b)`` returns, [T * (b - a)] (None without the embedding)."""
+        if not self.prev_action_dims:
+            return None
+        if a == 0 and b == sl.n:
+            return sl.prev
+        return sl.prev.view(self.T, sl.n)[:, a:b].reshape(-1).contiguous()
 
     def _expert_counts(self) -> Dict[tuple, torch.Tensor]:
         """The imitation normaliser of every minibatch range -- the number of this rollout's steps that have an expert action
@@ -822,7 +875,7 @@ class Worker(_SlicedActor):
                         #  run beside the other slice's GRU recurrence -- was measured in round 3: 53 -> 58 ms per update;
                         #  the step kernels wait for CUs the GEMM workgroups hold)
                         self.policy.forward(self.params, feat, goal, self.h_start[sl.o + a:sl.o + b], masks, T, m,
-                                            sl.ws_learn, hv=hv, feat2=feat2)
+                                            sl.ws_learn, hv=hv, feat2=feat2, prev_actions=self._gather_prev(sl, a, b))
                         if self._ppo:
                             ppo_loss_raw(hv, actions, logp, old_v, ret, nadv, self.A, grad_scale=grad_scale, dhv=dhv,
                                          sums=sl.sums, scratch=sl.ppo_scratch)
@@ -865,6 +918,8 @@ class Worker(_SlicedActor):
             sl.feat[0].copy_(sl.feat[self.T])
             if self.depth:
                 sl.feat2[0].copy_(sl.feat2[self.T])
+        if self.prev_action_dims:     # the next rollout's first step follows this rollout's last action
+            self.prev_actions[0].copy_(self.prev_actions[self.T])
         self.total_steps += self.T * sum(self.shard_counts)
         self.iter += 1
 
@@ -909,6 +964,7 @@ class Worker(_SlicedActor):
         minibatch shuffle stream (``_mb_rng`` restarts from the seed), the recurrent memory and the env's position -- a
         resumed run continues the optimisation, it is not a bit-for-bit continuation of the uninterrupted one."""
         ck = torch.load(path, map_location="cpu")
+        check_model_tensors(self.policy, ck["model_state_dict"], path)
         self.set_params(self.policy.flatten(ck["model_state_dict"], self.dev))
         o = ck["optimizer_state_dict"]
         self.opt.m.copy_(o["exp_avg"].to(self.dev).view_as(self.opt.m))

@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_rgbd
+from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_prev_actions, check_rgbd
 from .episodes import EpisodeTracker, NavEpisodeTracker, category_names, nav_env_tensors
 
 
@@ -45,18 +45,24 @@ class Evaluator(_SlicedActor):
     ``no_path``.  The act loop does not change.  ``env_seed``: the seed of the env the evaluator builds itself (default
     ``1000 + rank``, the ``Worker``'s).  ``depth=True``: the RGB-D agent of ``Worker(depth=True)`` -- a second feature ring per slice
     for the depth tower, the dual-encoder policy (a checkpoint then carries 25 tensors); an ``env=`` must also have ``depth`` and
-    ``observe_depth()``; refused with the combinations ``engine.check_rgbd`` names."""
+    ``observe_depth()``; refused with the combinations ``engine.check_rgbd`` names.  ``prev_actions=E > 0`` /
+    ``prev_action_null_token``: the agent of ``Worker(prev_actions=E)`` -- every step reads the actions the step before selected
+    (zeros before the first); a checkpoint then carries one more tensor, and one without it is refused by name; ``ValueError``
+    with ``depth=True`` or ``zeroshot=True``."""
 
     def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, encoder: str = "rn50",
                  encoder_sd=None, policy_sd=None, checkpoint: Optional[str] = None, deterministic: bool = False,
                  encoder_streams: int = 2, frames_u8: bool = False, goal_in: int = 0, num_actions: int = 6,
                  zeroshot: bool = False, sync_actions: bool = False, record: bool = False, env=None, text_sd=None,
                  goal_tokens=None, encoder_chunk: int = 0, record_capacity: int = 0, nav_metrics: bool = False,
-                 num_categories: Optional[int] = None, env_seed: Optional[int] = None, depth: bool = False):
+                 num_categories: Optional[int] = None, env_seed: Optional[int] = None, depth: bool = False,
+                 prev_actions: int = 0, prev_action_null_token: bool = True):
         if depth:       # the RGB-D agent (engine.Worker(depth=True)): the same refusals, before anything is built
             check_rgbd(encoder, zeroshot, goal_in, bool(env is not None and getattr(env, "host", False)))
             if env is not None and getattr(env, "depth", None) is None:
                 raise ValueError("depth=True: the env serves no depth frames (SyntheticEnv(..., depth=True) holds env.depth)")
+        self.prev_action_dims = check_prev_actions(prev_actions, bool(depth), bool(zeroshot))
+        self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
         self.depth = bool(depth)
         self.lib = _lib.load()
         self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
@@ -76,6 +82,7 @@ class Evaluator(_SlicedActor):
         if checkpoint is not None:
             ck = torch.load(checkpoint, map_location="cpu")
             policy_sd, self.checkpoint_steps = ck["model_state_dict"], int(ck.get("total_steps", 0))
+        self._checkpoint = checkpoint
         self._init(n_actors, T, seed, rank, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams, frames_u8, env,
                    record_capacity)
 
@@ -85,6 +92,11 @@ class Evaluator(_SlicedActor):
         self.N, self.T, self.rank = n_actors, T, rank
         N = n_actors
         d = self.dev
+        if self._checkpoint is not None and self.prev_action_dims:
+            # before the handle flattens it: a checkpoint of an agent without the embedding is refused by the tensor's name
+            from .synthetic import POLICY_PREV_ACTION_EMBEDDER
+            if POLICY_PREV_ACTION_EMBEDDER not in policy_sd:
+                raise KeyError(f"{self._checkpoint}: the checkpoint lacks the tensor {POLICY_PREV_ACTION_EMBEDDER!r} of this agent")
         encs, pools = self._build_model(n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams)
         self.h = torch.zeros((N, self.H), dtype=torch.float32, device=d)
         self.h_next = torch.zeros((N, self.H), dtype=torch.float32, device=d)
@@ -94,6 +106,7 @@ class Evaluator(_SlicedActor):
         self._logp = torch.zeros((1, N), dtype=torch.float32, device=d)
         self._values = torch.zeros((1, N), dtype=torch.float32, device=d)
         self.actions = self.logp = self.values = self.hv = None
+        self._prev_row = self._actions[0]       # what the next step reads as its previous actions: the last step's row (zeros at first)
         env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
         env_seed = self._env_seed if self._env_seed is not None else 1000 + rank
         dkw = dict(depth=True) if self.depth else {}
@@ -123,17 +136,19 @@ class Evaluator(_SlicedActor):
         feat, feat2 = sl.feat[self.k & 1], self._f2(sl, self.k & 1)
         hv, actions, logp, values = self._hv[row][rs], self._actions[row][rs], self._logp[row][rs], self._values[row][rs]
         key = self.chunk * (self.T + 1) + t
+        pa = self._prev_row[rs] if self.prev_action_dims else None
         if self._act_fused:
             self.policy.act(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
                             actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
-                            deterministic=self.deterministic, feat2=feat2)
+                            deterministic=self.deterministic, feat2=feat2, prev_actions=pa)
         elif self._act_wide:   # 8 to 256 actions: the wide heads launch selects (ec_policy_act_ex)
             self.policy.act_ex(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
                                actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
-                               deterministic=self.deterministic, feat2=feat2)
+                               deterministic=self.deterministic, feat2=feat2, prev_actions=pa)
         else:   # the switch off: the forward, then the stand-alone selection kernel
             self.policy.forward(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n, sl.ws_act,
-                                hv=hv, h_final=h_out[rs], for_backward=False, reuse_tables=sl.act_tables_valid, feat2=feat2)
+                                hv=hv, h_final=h_out[rs], for_backward=False, reuse_tables=sl.act_tables_valid, feat2=feat2,
+                                prev_actions=pa)
             if self.deterministic:
                 _lib.check(self.lib.ec_mode_actions(hv.data_ptr(), actions.data_ptr(), logp.data_ptr(), values.data_ptr(), n,
                                                     self.A, _lib.stream_ptr()), "ec_mode_actions")
@@ -175,6 +190,7 @@ class Evaluator(_SlicedActor):
                             self._act_slice(sl, t, row)
                             self._encode_slice(sl, rgb, (self.k + 1) & 1, dep)
                 self.k += 1
+                self._prev_row = self._actions[row]
             self._join()
             if self.nav_metrics:
                 self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None),
@@ -260,6 +276,10 @@ def main(argv=None) -> int:
     ap.add_argument("--frames-u8", action="store_true")
     ap.add_argument("--depth", action="store_true", help="the RGB-D agent: a depth tower beside the RGB tower, dual goal encoder (encoder rn50 / rn50x16)")
     ap.add_argument("--sync-actions", action="store_true")
+    ap.add_argument("--prev-actions", type=int, default=0, metavar="E",
+                    help="the agent conditions on its previous action through an E-wide embedding (0: off; AllenAct's default is 6, Habitat's 32)")
+    ap.add_argument("--no-prev-action-null-token", action="store_true",
+                    help="with --prev-actions: no null row for an episode's first step (action a is row a)")
     ap.add_argument("--json", default=None, metavar="OUT", help="also write the info dict to this file")
     ap.add_argument("--env-seed", type=int, default=None, help="seed of the synthetic env (default 1000, what Evaluator builds itself)")
     ap.add_argument("--nav-metrics", action="store_true", help="also SPL, SoftSPL, distance to goal, and the scores per object type")
@@ -286,7 +306,8 @@ def main(argv=None) -> int:
         print("evaluate: no --checkpoint given: using the seeded stand-in weights (an untrained agent)", file=sys.stderr)
     ev = Evaluator(a.actors, T=a.steps, seed=a.seed, env_seed=a.env_seed, encoder=a.encoder, checkpoint=a.checkpoint, deterministic=a.deterministic,
                    goal_in=a.goal_in, num_actions=a.num_actions, zeroshot=a.zeroshot, frames_u8=a.frames_u8,
-                   sync_actions=a.sync_actions, nav_metrics=a.nav_metrics, depth=a.depth,
+                   sync_actions=a.sync_actions, nav_metrics=a.nav_metrics, depth=a.depth, prev_actions=a.prev_actions,
+                   prev_action_null_token=not a.no_prev_action_null_token,
                    num_categories=len(names) if (names is not None and not a.goal_in) else None,
                    # every actor can end an episode at every step: the metrics file then misses none
                    record_capacity=a.chunks * a.steps * a.actors if a.metrics_json else 0)

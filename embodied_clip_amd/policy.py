@@ -42,10 +42,13 @@ class PolicyHandle:
     def __init__(self, **cfg: int):
         self.lib = _lib.load()
         self.cfg = dict(in_channels=2048, spatial=7, hidden=512, goal_dims=32, num_goals=12, num_actions=6,
-                        compress_hid=128, compress_out=32, comb_hid=128, comb_out=32, fusion=0, dual=0, goal_in=0)
+                        compress_hid=128, compress_out=32, comb_hid=128, comb_out=32, fusion=0, dual=0, goal_in=0,
+                        prev_action_dims=0, prev_action_null=0)
         self.cfg.update(cfg)
         self.goal_in = self.cfg["goal_in"]      # > 0: the goal of a frame is goal_in floats (PointNav), ec_policy_*_vec
-        self.param_order = policy_param_order(self.cfg["dual"], self.goal_in)
+        # > 0: the previous action's embedding (this wide) is concatenated to the GRU input; ec_policy_forward_pa / ec_policy_act_pa
+        self.prev_action_dims = self.cfg["prev_action_dims"]
+        self.param_order = policy_param_order(self.cfg["dual"], self.goal_in, self.prev_action_dims, self.cfg["prev_action_null"])
         c = _lib.PolicyCfg(**self.cfg)
         h = C.c_void_p()
         _lib.check(self.lib.ec_policy_create(C.byref(h), C.byref(c)), "ec_policy_create")
@@ -95,6 +98,16 @@ class PolicyHandle:
             assert goal.dtype == torch.int64 and goal.numel() == rows, (goal.dtype, tuple(goal.shape))
         return goal.data_ptr()
 
+    def _prev_ptr(self, prev_actions, rows: int) -> int:
+        """The previous actions of the ``_pa`` entry points: int64 [rows] on a handle with the embedding, None without."""
+        if not self.prev_action_dims:
+            assert prev_actions is None, "this handle has no previous-action embedding (prev_action_dims=0): pass prev_actions=None"
+            return 0
+        assert prev_actions is not None, "a handle with prev_action_dims > 0 needs prev_actions (int64, one per frame)"
+        assert prev_actions.dtype == torch.int64 and prev_actions.is_contiguous() and prev_actions.numel() == rows, \
+            (prev_actions.dtype, tuple(prev_actions.shape), rows)
+        return prev_actions.data_ptr()
+
     def workspace_bytes(self, T: int, N: int, backward: bool) -> int:
         return self.lib.ec_policy_workspace_bytes(self.h, T, N, int(backward))
 
@@ -108,26 +121,31 @@ class PolicyHandle:
         return OrderedDict((n, flat[o:o + k].view(self.shapes[n])) for n, (o, k) in self.offsets.items())
 
     def forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv=None, h_final=None, for_backward: bool = True,
-                reuse_tables: bool = False, feat2=None):
+                reuse_tables: bool = False, feat2=None, prev_actions=None):
         """feat: bf16 or fp32 NHWC rows [T*N, S*S, C]; returns (hv [T*N, A+1], h_final [N,H]).
         ``for_backward=True`` (default) keeps every activation ``backward`` needs and wants a workspace of
         ``workspace_bytes(T, N, True)``; ``False`` is the inference-only act step (``workspace_bytes(T, N, False)``).
         The kernel plan follows this flag, never the size of ``ws``.  ``reuse_tables`` (inference only): the weight-derived
         tables a previous ``for_backward=False`` call left in THIS ``ws`` are still valid (same parameters: the later act
-        steps of a rollout)."""
+        steps of a rollout).  ``prev_actions`` (handles with ``prev_action_dims > 0``, and only those): int64 [T*N], row
+        ``t * N + n`` = the action actor ``n`` took at step ``t - 1``."""
         assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
         dev = flat_params.device
         with _lib.tensor_guard(flat_params):
             mode = 1 if for_backward else (2 if reuse_tables else 0)
-            return self._forward(flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, mode, feat2)
+            return self._forward(flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, mode, feat2, prev_actions)
 
     def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
-            first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False):
+            first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None):
         """The act step in one call (``ec_policy_act``): the T = 1 inference forward whose heads launch also samples
         ``actions`` / ``logp`` (and copies ``values``) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions``.
         ``deterministic=True`` (evaluation): the heads launch takes ``CategoricalDistr.mode()`` instead, the first maximal logit
         (``ec_policy_act_greedy``; ``seed`` / ``step`` / ``first_actor`` are not used) -- ``forward`` + ``ec_mode_actions``."""
         assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
+        if self.prev_action_dims:            # (one entry point serves every act step of such a handle)
+            return self.act_ex(flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed, step, first_actor,
+                               reuse_tables, feat2, deterministic, prev_actions=prev_actions)
+        self._prev_ptr(prev_actions, N)
         name = ("ec_policy_act_vec" if self.goal_in else "ec_policy_act") + ("_greedy" if deterministic else "")
         key = () if deterministic else (seed, step, first_actor)
         with _lib.tensor_guard(flat_params):
@@ -140,7 +158,7 @@ class PolicyHandle:
 
     def act_ex(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
                first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, expert_actions=None,
-               expert_mask=None, force_p: float = 0.0):
+               expert_mask=None, force_p: float = 0.0, prev_actions=None):
         """The act step in one call for every handle, up to 256 actions (``ec_policy_act_ex``).  With more than 7 actions the
         heads launch of the wide action space computes the logits and selects (sample, or ``deterministic=True`` the first
         maximal logit) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions`` / ``ec_mode_actions`` on the
@@ -148,24 +166,35 @@ class PolicyHandle:
         forcing (``imitation.teacher_force``) in the same call -- inside the heads launch of a wide action space."""
         assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
         gp = self._goal_ptr(goal, N)
+        pp = self._prev_ptr(prev_actions, N)
         forcing = expert_actions is not None and force_p > 0.0
+        fn, name = (self.lib.ec_policy_act_pa, "ec_policy_act_pa") if pp else (self.lib.ec_policy_act_ex, "ec_policy_act_ex")
         with _lib.tensor_guard(flat_params):
-            _lib.check(self.lib.ec_policy_act_ex(
+            _lib.check(fn(
                 self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16),
-                0 if self.goal_in else gp, gp if self.goal_in else 0, h0.data_ptr(), masks.data_ptr(), N, ws.data_ptr(),
+                0 if self.goal_in else gp, gp if self.goal_in else 0, *((pp,) if pp else ()), h0.data_ptr(), masks.data_ptr(), N, ws.data_ptr(),
                 ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), h_final.data_ptr(), actions.data_ptr(),
                 logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
                 expert_actions.data_ptr() if forcing else 0, expert_mask.data_ptr() if forcing else 0,
-                force_p if forcing else 0.0, _lib.stream_ptr()), "ec_policy_act_ex")
+                force_p if forcing else 0.0, _lib.stream_ptr()), name)
         return hv, h_final
 
-    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None):
+    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None):
         if hv is None:
             hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)
         if h_final is None:
             h_final = torch.empty((N, self.H), dtype=torch.float32, device=dev)
         if self.cfg["dual"]:       # RGB + depth: feat = the RGB features, feat2 = the depth features (same shape / dtype)
             assert feat2 is not None and feat2.is_contiguous() and feat2.dtype == feat.dtype and feat2.shape == feat.shape
+        pp = self._prev_ptr(prev_actions, T * N)
+        if pp:
+            gp = self._goal_ptr(goal, T * N)
+            _lib.check(self.lib.ec_policy_forward_pa(
+                self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16),
+                0 if self.goal_in else gp, gp if self.goal_in else 0, pp, h0.data_ptr(), masks.data_ptr(), T, N, ws.data_ptr(),
+                ws.numel() * ws.element_size(), int(for_backward), hv.data_ptr(), h_final.data_ptr(), _lib.stream_ptr()),
+                "ec_policy_forward_pa")
+            return hv, h_final
         fn = self.lib.ec_policy_forward_vec if self.goal_in else self.lib.ec_policy_forward2
         _lib.check(fn(
             self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), self._goal_ptr(goal, T * N),
@@ -210,10 +239,11 @@ class _PolicyFn(torch.autograd.Function):
     backward is stated explicitly (``for_backward=need_grad``), so an act step always takes the act-step kernel plan."""
 
     @staticmethod
-    def forward(ctx, handle: PolicyHandle, owner, flat, feat, feat2, goal, h0, masks, T, N, *params):
+    def forward(ctx, handle: PolicyHandle, owner, flat, feat, feat2, goal, prev_actions, h0, masks, T, N, *params):
         need_grad = any(ctx.needs_input_grad)   # (grad mode is always off inside Function.forward)
         ws = torch.empty(handle.workspace_bytes(T, N, need_grad), dtype=torch.uint8, device=flat.device)
-        hv, h_final = handle.forward(flat, feat, goal, h0, masks, T, N, ws, for_backward=need_grad, feat2=feat2)
+        hv, h_final = handle.forward(flat, feat, goal, h0, masks, T, N, ws, for_backward=need_grad, feat2=feat2,
+                                     prev_actions=prev_actions)       # (a learn pass leaves the indices in ws for the backward)
         if need_grad:
             ctx.handle, ctx.owner, ctx.T, ctx.N = handle, owner, T, N
             ctx.feat2 = feat2                    # (the depth stream's features of the dual encoder, or None: frozen input)
@@ -238,7 +268,7 @@ class _PolicyFn(torch.autograd.Function):
         dhf = dh_final.contiguous() if dh_final is not None else None
         h.backward(flat, feat, masks, ctx.T, ctx.N, ws, dhv, dhf, g, feat2=ctx.feat2)
         grads = tuple(g[o:o + k].view(h.shapes[n]) for n, (o, k) in h.offsets.items())
-        return (None,) * 10 + grads
+        return (None,) * 11 + grads
 
 
 class _Holder(nn.Module):
@@ -265,7 +295,8 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
                  rgb_resnet_preprocessor_uuid: Optional[str] = None, depth_resnet_preprocessor_uuid: Optional[str] = None,
                  hidden_size: int = 512, goal_dims: int = 32, resnet_compressor_hidden_out_dims=(128, 32),
                  combiner_hidden_out_dims=(128, 32), state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 device="cuda"):
+                 device="cuda", add_prev_actions: bool = False, action_embed_size: int = 6,
+                 add_prev_action_null_token: bool = False):
         super().__init__(action_space=action_space, observation_space=observation_space)
         if rgb_resnet_preprocessor_uuid is None and depth_resnet_preprocessor_uuid is None:
             raise ValueError("one of rgb_resnet_preprocessor_uuid / depth_resnet_preprocessor_uuid is required")
@@ -289,6 +320,13 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
             goal_kw = dict(goal_in=int(observation_space.spaces[self.goal_uuid].shape[-1]))
         else:
             goal_kw = dict(num_goals=getattr(observation_space.spaces[self.goal_uuid], "n", 12))
+        # [U] VisualNavActorCritic(add_prev_actions, action_embed_size, add_prev_action_null_token): prev_action_embedder.fc.weight
+        # [action_space.n (+ 1), action_embed_size], concatenated to the GRU input (restated from the published source, parity unpinned)
+        self.add_prev_actions = bool(add_prev_actions)
+        if self.add_prev_actions:
+            if self.dual:
+                raise NotImplementedError("previous actions with the RGB-D encoder are not built")
+            goal_kw.update(prev_action_dims=int(action_embed_size), prev_action_null=int(bool(add_prev_action_null_token)))
         self.handle = PolicyHandle(in_channels=rs[0], spatial=rs[1], hidden=hidden_size, goal_dims=goal_dims,
                                    num_actions=action_space.n,
                                    compress_hid=resnet_compressor_hidden_out_dims[0],
@@ -425,7 +463,8 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
                 masks: torch.Tensor):
         """observations[resnet_uuid]: [T,N,C,S,S] fp32 (or bf16/fp32 channels-last [T,N,S,S,C] from
         ``ClipResNetPreprocessor.process_bf16_nhwc``); observations[goal_uuid]: [T,N] int (PointNav: [T,N,goal_in] float);
-        memory 'rnn': [1,N,H]; masks: [T,N,1].  -> (ActorCriticOutput, Memory)."""
+        memory 'rnn': [1,N,H]; masks: [T,N,1]; prev_actions: [T,N] or [T,N,1] integer, read only with ``add_prev_actions``.
+        -> (ActorCriticOutput, Memory)."""
         self.ensure_flat()
         goal = observations[self.goal_uuid]
         T, N = masks.shape[:2]
@@ -453,12 +492,17 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
             goal = goal.reshape(T * N).to(torch.int64).contiguous()
         h0 = memory.tensor("rnn").reshape(N, self._hidden_size).to(torch.float32).contiguous()
         m = masks.reshape(T * N).to(torch.float32).contiguous()
+        prev = None
+        if self.add_prev_actions:
+            assert prev_actions is not None and prev_actions.numel() == T * N, "add_prev_actions=True needs prev_actions [T, N] or [T, N, 1]"
+            prev = prev_actions.reshape(T * N).to(torch.int64).contiguous()
         if torch.is_grad_enabled():
             params = [p for _, p in self._named()]
-            hv, h_final = _PolicyFn.apply(self.handle, self, self._flat, rows, rows2, goal, h0, m, T, N, *params)
+            hv, h_final = _PolicyFn.apply(self.handle, self, self._flat, rows, rows2, goal, prev, h0, m, T, N, *params)
         else:   # act steps (the engine's no_grad rollout): straight to the inference plan, no autograd node, no 17-tensor argument list
             ws = torch.empty(self.handle.workspace_bytes(T, N, False), dtype=torch.uint8, device=self._flat.device)
-            hv, h_final = self.handle.forward(self._flat, rows, goal, h0, m, T, N, ws, for_backward=False, feat2=rows2)
+            hv, h_final = self.handle.forward(self._flat, rows, goal, h0, m, T, N, ws, for_backward=False, feat2=rows2,
+                                              prev_actions=prev)
         A = self.handle.A
         hv = hv.view(T, N, A + 1)
         out = ActorCriticOutput(distributions=CategoricalDistr(logits=hv[..., :A]), values=hv[..., A:], extras={})

@@ -345,7 +345,15 @@ POLICY_PARAM_ORDER_POINTNAV: Tuple[str, ...] = (
     "goal_visual_encoder.embed_goal.weight", "goal_visual_encoder.embed_goal.bias") + POLICY_PARAM_ORDER[1:]
 
 
-def policy_param_order(dual: int = 0, goal_in: int = 0) -> Tuple[str, ...]:
+# [U] allenact VisualNavActorCritic ``prev_action_embedder = FeatureEmbedding(action_space.n [+ 1], action_embed_size)`` (Habitat:
+# ``prev_action_embedding``): one more tensor, last in the flat order; ``weight_ih_l0`` grows by its width
+POLICY_PREV_ACTION_EMBEDDER = "prev_action_embedder.fc.weight"
+
+
+def policy_param_order(dual: int = 0, goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0) -> Tuple[str, ...]:
+    if prev_action_dims:
+        assert not dual, "previous actions with the RGB-D encoder are not built"
+        return policy_param_order(0, goal_in) + (POLICY_PREV_ACTION_EMBEDDER,)
     if goal_in:
         assert not dual, "the RGB-D PointNav encoder is not built"
         return POLICY_PARAM_ORDER_POINTNAV
@@ -355,11 +363,21 @@ def policy_param_order(dual: int = 0, goal_in: int = 0) -> Tuple[str, ...]:
 def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int = 512, goal_dims: int = 32,
                         num_goals: int = 12, num_actions: int = 6, compress_hid: int = 128,
                         compress_out: int = 32, comb_hid: int = 128, comb_out: int = 32, fusion: int = 0, dual: int = 0,
-                        goal_in: int = 0):
+                        goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0):
     """``fusion=1`` (zero-shot dual-encoder policy): the goal-embedding / compressor / combiner tensors have zero
     elements and the GRU reads the ``in_channels``-wide fused embedding.  ``dual=1``: RGB + depth streams (25 tensors,
     GRU input 2 * comb_out * spatial^2).  ``goal_in > 0`` (PointNav): 18 tensors, ``embed_goal.{weight,bias}`` in place
-    of ``embed_class.weight``; ``num_goals`` is ignored."""
+    of ``embed_class.weight``; ``num_goals`` is ignored.  ``prev_action_dims = E > 0``: ``weight_ih_l0`` is ``[3 * hidden,
+    flat + E]`` and ``prev_action_embedder.fc.weight`` ``[num_actions + prev_action_null, E]`` is the last tensor."""
+    if prev_action_dims:
+        assert not fusion and not dual and 1 <= prev_action_dims <= 64 and prev_action_null in (0, 1)
+        out = policy_param_shapes(in_channels, spatial, hidden, goal_dims, num_goals, num_actions, compress_hid, compress_out,
+                                  comb_hid, comb_out, goal_in=goal_in)
+        rows, flat = out["state_encoder.rnn.weight_ih_l0"]
+        out["state_encoder.rnn.weight_ih_l0"] = (rows, flat + prev_action_dims)
+        out[POLICY_PREV_ACTION_EMBEDDER] = (num_actions + prev_action_null, prev_action_dims)
+        return out
+    assert not prev_action_null, "the null token belongs to the previous-action embedding"
     if goal_in:
         assert not fusion and not dual
         one = policy_param_shapes(in_channels, spatial, hidden, goal_dims, num_goals, num_actions, compress_hid, compress_out,
@@ -420,7 +438,7 @@ def policy_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, torch.Tensor]":
             sd[k] = torch.zeros(shp)
         elif k.endswith("bias") or "bias_" in k:
             sd[k] = _normal(seed, k, shp, 0.02)
-        elif "embed_class" in k:
+        elif "embed_class" in k or k == POLICY_PREV_ACTION_EMBEDDER:      # nn.Embedding's N(0, 1)
             sd[k] = _normal(seed, k, shp, 1.0)
         else:
             fan_in = int(np.prod(shp[1:]))

@@ -419,6 +419,24 @@ typedef struct {
                         *    single encoder in the order above.  Use ec_policy_forward_vec / ec_policy_act_vec; the backward
                         *    entry points are the same.  EC_ERR_ARG with fusion = 1; EC_ERR_UNSUPPORTED with dual = 1 (the
                         *    RGB-D PointNav encoder is not built) */
+    int prev_action_dims;  /* E.  0: the GRU reads the goal encoder's output alone -- today's handle exactly (tensor count, flat
+                        *    size, workspace sizes, launch plan and bits).
+                        * E in 1..64: the embedding of the previous action is concatenated to the GRU input ([U] habitat_baselines
+                        *    PointNavResNetPolicy prev_action_embedding, width 32; [U] allenact VisualNavActorCritic
+                        *    add_prev_actions / action_embed_size, default 6) -- restated from the published sources, parity
+                        *    unpinned.  rnn.weight_ih_l0 becomes [3 * hidden, flat + E] (one tensor; flat = today's input width)
+                        *    and ONE more tensor, prev_action_embedder.fc.weight [num_actions + prev_action_null, E], is the
+                        *    last of the flat order.  Nothing [T*N, E]-shaped exists: the embedding reaches gi through the
+                        *    weight-derived table of ec_prev_action_table (built with the other tables: per EC_POLICY_INFER
+                        *    call, kept under EC_POLICY_INFER_REUSE, per learn pass).  No GEMM reads weight_ih in place on
+                        *    such a handle (its row stride need not be a multiple of 4): every route goes through a dense
+                        *    [3 * hidden, flat] copy, and the dense gradient is added back row by row.  Use ec_policy_forward_pa /
+                        *    ec_policy_act_pa; the backward entry points are the same.  EC_ERR_ARG outside 0..64;
+                        *    EC_ERR_UNSUPPORTED with dual = 1 or fusion = 1 (like goal_in with dual: the two-tower and the
+                        *    zero-shot agents with previous actions are not built) */
+    int prev_action_null;  /* 1: row 0 of the embedding is the null token of an episode's first step (masks == 0) and action a is
+                        *    row a + 1 (Habitat; allenact add_prev_action_null_token); 0: action a is row a.  EC_ERR_ARG outside
+                        *    {0, 1} and with prev_action_dims == 0 */
 } ec_policy_cfg;
 typedef struct ec_policy ec_policy_t;
 
@@ -658,6 +676,59 @@ int ec_ppo_loss_wide_scratch_doubles(void);
 int ec_ppo_loss_wide(const float* hv, const int64_t* actions, const float* old_logp, const float* old_values,
                      const float* returns, const float* norm_adv, float* dhv, double* sums4, double* scratch, long B, int A,
                      float clip, float value_clip, float vcoef, float ecoef, float grad_scale, ec_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Previous-action embedding of the recurrent input ([U] habitat_baselines PointNavResNetPolicy: prev_action_embedding =
+ * nn.Embedding(num_actions + 1, 32) indexed by ((prev_actions.float() + 1) * masks).long(); [U] allenact VisualNavActorCritic:
+ * add_prev_actions / action_embed_size / add_prev_action_null_token).  Restated from the published sources, which are not
+ * under the reference tree: parity unpinned.  The kernels alone first, then the policy entry points that use them.
+ *   A = number of actions (1..256), null_token in {0, 1}, R = A + null_token table rows, E = embedding width (1..64),
+ *   G = 3 * hidden gate columns, B = T * N frames; emb [R, E]; Wa = columns col0 .. col0 + E of a row-major matrix w with G
+ *   rows and leading dimension ld >= col0 + E (any ld: nothing here needs ld to be a multiple of 4).
+ *   idx[b] = null_token ? (masks[b] != 0 ? prev_actions[b] + 1 : 0) : prev_actions[b]
+ * An index outside [0, R) is never dereferenced: that frame adds nothing to gi and contributes nothing to any gradient.
+ * masks may be NULL when null_token is 0.  No floating-point atomics: two runs give the same bits. */
+/* pt[r, g] = sum_e emb[r, e] * w[g * ld + col0 + e], fp32 FMA in ascending e; pt [R, G] */
+int ec_prev_action_table(const float* emb, const float* w, long ld, int col0, float* pt, int A, int null_token, int G, int E,
+                         ec_stream_t stream);
+/* gi[b, :] += pt[idx[b], :]; gi [B, G] dense */
+int ec_prev_action_add(float* gi, const float* pt, const int64_t* prev_actions, const float* masks, int null_token, int A, long B,
+                       int G, ec_stream_t stream);
+/* dPT[r, :] = sum over {b : idx[b] == r} of dgi[b, :], then demb[r, e] += sum_g dPT[r, g] * Wa[g, e] (four contiguous quarters of
+ * g, each in ascending order, folded in order) and dw[g * ld + col0 + e] += sum_r dPT[r, g] * emb[r, e] (ascending r): both ADD
+ * onto what is there.
+ * The frames are cut into P = ceil(B / chunk) partitions of chunk = max(R, 128, ceil(B / 4096)) consecutive frames -- a function
+ * of B and R alone; a partition is summed in ascending b per (row, column), the partitions are folded in ascending order.  A
+ * table row that no frame selects has dPT == 0 exactly and adds exactly 0.
+ * scratch: ec_prev_action_grad_scratch_floats(B, G, A, null_token) = (P + 1) * R * G floats, owned by one stream at a time;
+ * since chunk >= R, P * R < B + R: the partitions' bins take less than (B + R) * G floats -- 1 / 18 of dgi for B = 32768, R = 7 --
+ * and on return scratch[0 .. R * G) holds dPT. */
+size_t ec_prev_action_grad_scratch_floats(long B, int G, int A, int null_token);
+int ec_prev_action_grad(const float* dgi, const int64_t* prev_actions, const float* masks, int null_token, int A, const float* emb,
+                        const float* w, long ld, int col0, float* demb, float* dw, float* scratch, long B, int G, int E,
+                        ec_stream_t stream);
+/* prev_action_dims > 0 handles.  ec_policy_forward_pa: the arguments of ec_policy_forward_vec with BOTH goal arguments (exactly
+ * one non-NULL, by the handle's goal type) and prev_actions int64 [T*N], row t * N + n = the action actor n took at step t - 1.
+ * ec_policy_act_pa: the arguments of ec_policy_act_ex and prev_actions int64 [N]: sampling, greedy selection, forcing, narrow
+ * and wide heads, both goal types.  Where the table is added: inside gi_act_kernel's fold, next to the bias, on the act step's
+ * 1568-wide route (an EC_POLICY_INFER_REUSE act step then issues exactly the launches of a prev_action_dims == 0 handle);
+ * ec_prev_action_add's launch behind the input projection on every other route (onto part 0 of a split-K projection).  A learn
+ * pass leaves the indices in its workspace; ec_policy_backward* then adds the embedding's gradient and columns flat.. of
+ * weight_ih's with ec_prev_action_grad's launches before `recurrent_grads_ready` is recorded.  An actor's result does not
+ * depend on how the actors are sliced; ec_policy_act_pa equals ec_policy_forward_pa at T = 1 followed by ec_sample_actions /
+ * ec_mode_actions bit for bit; with a zero embedding every output and every other tensor's gradient equals, bit for bit, those
+ * of the prev_action_dims == 0 handle that holds weight_ih[:, :flat] (the launch plan does not depend on prev_action_dims).
+ * Checked before any HIP call: every other forward / act entry point returns EC_ERR_ARG on such a handle; these return
+ * EC_ERR_ARG on a prev_action_dims == 0 handle and for a NULL prev_actions. */
+int ec_policy_forward_pa(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                         const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, const float* h0,
+                         const float* masks, int T, int N, void* workspace, size_t ws_bytes, int for_backward, float* hv,
+                         float* h_final, ec_stream_t stream);
+int ec_policy_act_pa(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
+                     const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, const float* h0, const float* masks,
+                     int N, void* workspace, size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions,
+                     float* logp, float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
+                     const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * CLIP VisionTransformer embedder == [U] allenact ClipViTEmbedder.forward over

@@ -1,0 +1,357 @@
+"""GPU: policy handles with a previous-action embedding (``prev_action_dims > 0``) against the CPU restatement in
+tests/_prev_action_ref.py, case by case as tests/test_gpu_pointnav.py does for coordinate goals.
+
+Tolerances are the policy path's own (test_gpu_policy.py / test_gpu_pointnav.py): forward rel-L2 < 2e-5, per-tensor gradient
+rel-L2 < 2e-4, the loss 1e-5 relative, the Adam update as in ``test_policy_backward_and_update_step_match_oracle``.  The fp32
+torch reference agrees with its float64 self to <= 1.4e-6 (forward) and <= 2.0e-6 (worst gradient tensor) at these shapes
+(tests/test_prev_action_ref.py measures each case and holds it to a tenth of its bound), so the bounds test the kernels.
+
+Cases are (T, N, S, C, H, E, null, A, goal_in, bf16 features) -- tests/_prev_action_ref.py::POLICY_CASES:
+  (1, 1, 7, ..)  (3, 5, 7, .., E 6, null 1 | 0)     the fused tail, the re-ordered weight_ih built from rows of stride 1574
+  (4, 33, 7, .., E 32, A 4, goal_in 3)  bf16        coordinate goals, Habitat's width
+  (6, 4, 3, .., E 5)                                S*S = 9, flat = 288: the routes that keep weight_ih's column order (dense copy,
+                                                    dense gradient added back), stride 293
+  (2, 16, 7, H = 512)  bf16                         the 512-wide recurrence kernels
+  (3, 5, 7, .., E 64, A 84)  (2, 3, 7, .., E 1, A 256)   the wide learn plan; R = 257 table rows
+"""
+import functools
+import os
+import sys
+
+import pytest
+import torch
+
+from embodied_clip_amd import synthetic as syn
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _prev_action_ref as ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+CASES = ref.POLICY_CASES
+WIH = "state_encoder.rnn.weight_ih_l0"
+IDENTITY_CASES = [CASES[1], CASES[3], CASES[4], CASES[5], CASES[6]]
+
+
+def _rel(a, b):
+    a, b = a.detach().float().cpu(), b.detach().float().cpu()
+    return ((a - b).norm() / b.norm().clamp_min(1e-20)).item()
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(*case):
+    """Inputs and the reference's forward / optimiser step, computed once per case and shared (never modified)."""
+    cfg, sd, batch = ref.policy_inputs(*case)
+    r = ref.policy_reference(sd, batch, case[6])
+    return dict(cfg=cfg, sd=sd, **r)
+
+
+def _gpu_inputs(cfg, b, dev, bf16):
+    T, N = b["feat"].shape[:2]
+    rows = b["feat"].permute(0, 1, 3, 4, 2).reshape(T * N, cfg["spatial"] ** 2, cfg["in_channels"]).contiguous()
+    rows = (rows.to(torch.bfloat16) if bf16 else rows).to(dev)
+    goal = (b["goal"].reshape(T * N, cfg["goal_in"]) if cfg["goal_in"] else b["goal"].reshape(T * N)).contiguous().to(dev)
+    return rows, goal, b["prev_actions"].reshape(-1).contiguous().to(dev), b["h0"][0].contiguous().to(dev), b["masks"].reshape(-1).to(dev)
+
+
+def _learn_step(cfg, sd, b, dev, bf16):
+    """forward (learn plan), PPO loss, backward twice on the GPU -> (handle, flat, hv, h_final, sums, grads, again)"""
+    from embodied_clip_amd import ppo
+    from embodied_clip_amd.policy import PolicyHandle
+    T, N = b["feat"].shape[:2]
+    h = PolicyHandle(**cfg)
+    flat = h.flatten(sd, dev)
+    rows, goal, prev, h0, m = _gpu_inputs(cfg, b, dev, bf16)
+    ws = torch.empty(h.workspace_bytes(T, N, True), dtype=torch.uint8, device=dev)
+    hv, hf = h.forward(flat, rows, goal, h0, m, T, N, ws, prev_actions=prev if cfg["prev_action_dims"] else None)
+    f = lambda t: t.reshape(-1).contiguous().to(dev)
+    dhv, sums = ppo.ppo_loss_raw(hv, f(b["actions"]), f(b["old_log_probs"]), f(b["old_values"]), f(b["returns"]),
+                                 f(b["norm_adv"]), cfg["num_actions"])
+    grads = torch.zeros_like(flat)
+    h.backward(flat, rows, m, T, N, ws, dhv, None, grads)
+    again = torch.zeros_like(flat)                       # the same backward once more (reads the same workspace)
+    h.backward(flat, rows, m, T, N, ws, dhv, None, again)
+    torch.cuda.synchronize()
+    return h, flat, hv, hf, sums, grads, again
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_forward_matches_reference(dev, case):
+    from embodied_clip_amd.policy import PolicyHandle
+    T, N, A, bf16 = case[0], case[1], case[7], case[9]
+    c = _case(*case)
+    h = PolicyHandle(**c["cfg"])
+    assert list(h.offsets)[-1] == ref.EMB_KEY and len(h.offsets) == (19 if case[8] else 18)
+    flat = h.flatten(c["sd"], dev)
+    rows, goal, prev, h0, m = _gpu_inputs(c["cfg"], c["batch"], dev, bf16)
+    ws = torch.empty(h.workspace_bytes(T, N, False), dtype=torch.uint8, device=dev)
+    hv, hf = h.forward(flat, rows, goal, h0, m, T, N, ws, for_backward=False, prev_actions=prev)
+    torch.cuda.synchronize()
+    hv = hv.view(T, N, -1)
+    errs = (_rel(hv[..., :A], c["logits"]), _rel(hv[..., A:], c["values"]), _rel(hf, c["h"][0]))
+    print("forward rel-L2 (logits, values, h):", errs)
+    assert max(errs) < 2e-5, errs
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_optimiser_step_matches_reference_and_is_deterministic(dev, case):
+    """forward, PPO loss, backward, clip, Adam: every gradient (the embedding's and the widened weight_ih's among them) and the
+    parameter update; the same backward twice gives the same bits (no float atomics on any route of such a handle's
+    previous-action path)."""
+    from embodied_clip_amd import ppo
+    T, N, A, bf16 = case[0], case[1], case[7], case[9]
+    c = _case(*case)
+    info, ref_grads, sd, sd_ref = c["info"], c["ref_grads"], c["sd"], c["sd_ref"]
+    h, flat, hv, _, sums, grads, again = _learn_step(c["cfg"], sd, c["batch"], dev, bf16)
+    hv3 = hv.view(T, N, -1)
+    assert _rel(hv3[..., :A], c["logits"]) < 2e-5 and _rel(hv3[..., A:], c["values"]) < 2e-5      # the learn plan's forward
+    total = ((sums[0] + 0.5 * sums[1] + 0.01 * sums[2]) / (T * N)).item()
+    assert abs(total - info["ppo_total"]) < 1e-5 * max(1.0, abs(info["ppo_total"]))
+    gv, ga = h.views(grads), h.views(again)
+    assert set(gv) == set(ref_grads) and ref.EMB_KEY in gv
+    errs = {name: _rel(gv[name], gref) for name, gref in ref_grads.items()}
+    print("gradient rel-L2:", errs)
+    for name, e in errs.items():
+        assert e < 2e-4, (name, e)
+    # the previous-action path twice: the same bits (the narrow handles' goal-embedding scatter alone keeps its float atomics)
+    flatE = h.shapes[WIH][1] - case[5]
+    assert float(gv[ref.EMB_KEY].abs().max()) > 0
+    assert torch.equal(gv[ref.EMB_KEY], ga[ref.EMB_KEY]) and torch.equal(gv[WIH][:, flatE:], ga[WIH][:, flatE:])
+    if case[8] or A + 1 > 8:                               # coordinate goals, wide handles: no float atomics anywhere
+        assert torch.equal(grads, again)
+    opt = ppo.FlatAdam(flat, lr=3e-4, max_grad_norm=0.5)
+    opt.step(grads)
+    torch.cuda.synchronize()
+    assert abs(opt.grad_norm() - info["grad_norm"]) < 1e-4 * info["grad_norm"]
+    pv = h.views(flat)
+    for name, pref in sd_ref.items():
+        # (the update, not the parameter: see test_policy_backward_and_update_step_match_oracle)
+        upd, upd_ref = pv[name].cpu() - sd[name], pref - sd[name]
+        well = ref_grads[name].abs() > 1e-6
+        assert ((upd - upd_ref).abs() * well).max() < 0.05 * 3e-4 + 1e-7, name
+        assert upd.abs().max() <= 3e-4 * 1.001 + 1e-7, name
+
+
+@pytest.mark.parametrize("case", IDENTITY_CASES)
+def test_zero_embedding_equals_the_handle_without_it(dev, case):
+    """Emb = 0: outputs and every other tensor's gradient are, bit for bit, those of the prev_action_dims = 0 handle that holds
+    weight_ih[:, :flat] (adding +0.0f is exact and the launch plan does not depend on the embedding's width); the embedding's own
+    gradient is not zero."""
+    T, N, E, bf16 = case[0], case[1], case[5], case[9]
+    c = _case(*case)
+    b = c["batch"]
+    sd_z = {k: v.clone() for k, v in c["sd"].items()}
+    sd_z[ref.EMB_KEY].zero_()
+    cfg0 = dict(c["cfg"], prev_action_dims=0, prev_action_null=0)
+    sd0 = {k: v.clone() for k, v in c["sd"].items() if k != ref.EMB_KEY}
+    flatw = sd0[WIH].shape[1] - E
+    sd0[WIH] = sd0[WIH][:, :flatw].contiguous()
+    hz, _, hv_z, hf_z, _, g_z, _ = _learn_step(c["cfg"], sd_z, b, dev, bf16)
+    h0_, _, hv_0, hf_0, _, g_0, _ = _learn_step(cfg0, sd0, b, dev, bf16)
+    assert hz.workspace_bytes(T, N, True) > h0_.workspace_bytes(T, N, True)
+    assert torch.equal(hv_z, hv_0) and torch.equal(hf_z, hf_0)
+    gz, g0 = hz.views(g_z), h0_.views(g_0)
+    atomics = not (case[8] or case[7] + 1 > 8)             # narrow integer-goal handles: the goal scatter's float atomics
+    for name, g in g0.items():
+        got = gz[name][:, :flatw] if name == WIH else gz[name]
+        if atomics and name.startswith("goal_visual_encoder"):
+            assert _rel(got, g) < 1e-5, name
+        else:
+            assert torch.equal(got, g), name
+    assert float(gz[ref.EMB_KEY].abs().max()) > 0 and not gz[WIH][:, flatw:].any()       # dWa = dPT^T . Emb = 0
+    # the act step of the same pair (T = 1 inference plan)
+    from embodied_clip_amd.policy import PolicyHandle
+    rows, goal, prev, h0, m = _gpu_inputs(c["cfg"], b, dev, bf16)
+    outs = []
+    for cfg, sd, pa in ((c["cfg"], sd_z, prev[:N].contiguous()), (cfg0, sd0, None)):
+        h = PolicyHandle(**cfg)
+        ws = torch.empty(h.workspace_bytes(1, N, False), dtype=torch.uint8, device=dev)
+        hv, hf = h.forward(h.flatten(sd, dev), rows[:N].contiguous(), goal[:N].contiguous(), h0, m[:N].contiguous(), 1, N, ws,
+                           for_backward=False, prev_actions=pa)
+        outs.append((hv.clone(), hf.clone()))
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
+def test_forward_does_not_depend_on_actor_slicing(dev):
+    """The act step of 37 actors == the act steps of actors [0, 19) and [19, 37), bit for bit."""
+    from embodied_clip_amd.policy import PolicyHandle
+    case = (1, 37, 7, 64, 32, 6, 1, 6, 0, True)
+    cfg, sd, b = ref.policy_inputs(*case)
+    h = PolicyHandle(**cfg)
+    flat = h.flatten(sd, dev)
+    rows, goal, prev, h0, m = _gpu_inputs(cfg, b, dev, True)
+
+    def run(a, z):
+        n = z - a
+        ws = torch.empty(h.workspace_bytes(1, n, False), dtype=torch.uint8, device=dev)
+        return h.forward(flat, rows[a:z].contiguous(), goal[a:z].contiguous(), h0[a:z].contiguous(), m[a:z].contiguous(), 1, n, ws,
+                         for_backward=False, prev_actions=prev[a:z].contiguous())
+    hv, hf = run(0, 37)
+    hv_a, hf_a = run(0, 19)
+    hv_b, hf_b = run(19, 37)
+    torch.cuda.synchronize()
+    assert torch.equal(hv, torch.cat([hv_a, hv_b])) and torch.equal(hf, torch.cat([hf_a, hf_b]))
+    assert len(set(prev.tolist())) > 1
+
+
+@pytest.mark.parametrize("N", [1, 5, 32, 33])
+@pytest.mark.parametrize("A,goal_in", [(6, 0), (84, 0), (4, 2)])
+def test_act_step_is_forward_plus_selection_with_table_reuse(dev, N, A, goal_in):
+    """``ec_policy_act_pa`` == ``ec_policy_forward_pa`` at T = 1 + ``ec_sample_actions`` / ``ec_mode_actions``, bit for bit (wide heads:
+    the final state bit for bit, the selection on the hv the heads launch wrote -- ``ec_policy_act_ex``'s own contract), at the
+    agent's real widths (2048 channels, 7 x 7, hidden 512: the 1568-wide input projection whose fold adds the table row), narrow
+    and wide heads, both goal types.  The second step reuses the tables with OTHER previous actions and equals a fresh call.
+    After the embedding changes, a REUSE call may answer from the stale table; a call without REUSE may not."""
+    from embodied_clip_amd import _lib
+    from embodied_clip_amd.policy import PolicyHandle
+    lib = _lib.load()
+    E = 6
+    kw = dict(num_actions=A, goal_in=goal_in, prev_action_dims=E, prev_action_null=1)
+    h = PolicyHandle(**kw)
+    sd = syn.policy_state_dict(5, **kw)
+    flat = h.flatten(sd, dev)
+    g = torch.Generator().manual_seed(9 + N)
+    feat = (torch.randn(N, 49, 2048, generator=g).abs() * 0.5).to(torch.bfloat16).to(dev)
+    goal = (syn.synthetic_goal_vectors(6, (N,), goal_in, rho_max=30.0) if goal_in else syn.synthetic_goals(6, (N,))).to(dev)
+    prevs = [torch.randint(0, A, (N,), generator=g).to(dev), ((torch.arange(N) * 5 + 1) % A).to(dev)]
+    h0 = (torch.randn(N, 512, generator=g) * 0.3).to(dev)
+    m = (torch.rand(N, generator=g) > 0.2).float().to(dev)
+    m[0] = 0.0 if N > 1 else 1.0
+    ws_a = torch.empty(h.workspace_bytes(1, N, False), dtype=torch.uint8, device=dev)
+    ws_b = torch.empty_like(ws_a)
+    z = lambda dt=torch.float32: torch.zeros(N, dtype=dt, device=dev)
+    for call, (reuse, greedy) in enumerate(((False, False), (True, False), (True, True))):
+        prev = prevs[call % 2]
+        hv_f, hf_f = h.forward(flat, feat, goal, h0, m, 1, N, torch.empty_like(ws_a), for_backward=False, prev_actions=prev)
+        hv_f, hf_f = hv_f.clone(), hf_f.clone()
+        hv_a, hf_a = h.forward(flat, feat, goal, h0, m, 1, N, ws_a, for_backward=False, reuse_tables=reuse, prev_actions=prev)
+        hv_b, hf_b = torch.empty_like(hv_a), torch.empty_like(hf_a)
+        act_b, lp_b, v_b = z(torch.int64), z(), z()
+        h.act_ex(flat, feat, goal, h0, m, N, ws_b, hv_b, hf_b, act_b, lp_b, v_b, 123, 40 + call, 1000, reuse_tables=reuse,
+                 deterministic=greedy, prev_actions=prev)
+        # wide heads: the act step's heads launch is ec_heads_wide's, not the forward's two GEMMs -- as for ec_policy_act_ex, the
+        # selection is held to the hv that launch wrote, and hv to the forward's within the forward bound
+        hv_sel = hv_b if A + 1 > 8 else hv_a
+        act_a, lp_a, v_a = z(torch.int64), z(), z()
+        if greedy:
+            _lib.check(lib.ec_mode_actions(hv_sel.data_ptr(), act_a.data_ptr(), lp_a.data_ptr(), v_a.data_ptr(), N, A, 0))
+        else:
+            _lib.check(lib.ec_sample_actions(hv_sel.data_ptr(), act_a.data_ptr(), lp_a.data_ptr(), v_a.data_ptr(), N, A, 123, 40 + call, 1000, 0))
+        torch.cuda.synchronize()
+        assert torch.equal(hv_a, hv_f) and torch.equal(hf_a, hf_f)              # reuse with other previous actions == fresh call
+        assert torch.equal(hf_a, hf_b) and (torch.equal(hv_a, hv_b) if A + 1 <= 8 else _rel(hv_b, hv_a) < 2e-5)
+        assert torch.equal(act_a, act_b) and torch.equal(lp_a, lp_b) and torch.equal(v_a, v_b)
+        assert (lp_a < 0).all() and int(act_a.max()) < A and int(act_a.min()) >= 0
+    # the previous action matters (N >= 5: some actor's row of the table differs between the two sets)
+    if N >= 5:
+        hv0, _ = h.forward(flat, feat, goal, h0, m, 1, N, ws_a, for_backward=False, reuse_tables=True, prev_actions=prevs[0])
+        hv0 = hv0.clone()
+        hv1, _ = h.forward(flat, feat, goal, h0, m, 1, N, ws_a, for_backward=False, reuse_tables=True, prev_actions=prevs[1])
+        assert not torch.equal(hv0, hv1)
+    # the embedding changes: without REUSE the table is rebuilt (the result equals a fresh workspace's); with REUSE it may be stale
+    flat2 = flat.clone()
+    o, k = h.offsets[ref.EMB_KEY]
+    flat2[o:o + k] += 0.5
+    hv_fresh, _ = h.forward(flat2, feat, goal, h0, m, 1, N, torch.empty_like(ws_a), for_backward=False, prev_actions=prevs[0])
+    hv_fresh = hv_fresh.clone()
+    hv_stale, _ = h.forward(flat2, feat, goal, h0, m, 1, N, ws_a, for_backward=False, reuse_tables=True, prev_actions=prevs[0])
+    hv_stale = hv_stale.clone()
+    hv_rebuilt, _ = h.forward(flat2, feat, goal, h0, m, 1, N, ws_a, for_backward=False, prev_actions=prevs[0])
+    torch.cuda.synchronize()
+    assert torch.equal(hv_rebuilt, hv_fresh) and not torch.equal(hv_stale, hv_fresh)
+
+
+def test_teacher_forcing_through_act_pa(dev):
+    """forcing at p = 1 through ``ec_policy_act_pa``: narrow heads (ec_teacher_force behind) and wide heads (inside the launch)"""
+    from embodied_clip_amd.policy import PolicyHandle
+    N = 5
+    for A in (6, 84):
+        kw = dict(num_actions=A, prev_action_dims=6, prev_action_null=1)
+        h = PolicyHandle(**kw)
+        flat = h.flatten(syn.policy_state_dict(5, **kw), dev)
+        g = torch.Generator().manual_seed(A)
+        feat = (torch.randn(N, 49, 2048, generator=g).abs() * 0.5).to(torch.bfloat16).to(dev)
+        goal, prev = syn.synthetic_goals(6, (N,)).to(dev), torch.randint(0, A, (N,), generator=g).to(dev)
+        h0, m = torch.zeros(N, 512, device=dev), torch.ones(N, device=dev)
+        expert = torch.randint(0, A, (N,), generator=g).to(dev)
+        emask = torch.tensor([1.0, 0.0, 1.0, 1.0, 0.0], device=dev)
+        ws = torch.empty(h.workspace_bytes(1, N, False), dtype=torch.uint8, device=dev)
+        outs = []
+        for forcing in (False, True):
+            hv, hf = torch.empty(N, A + 1, device=dev), torch.empty(N, 512, device=dev)
+            act, lp, v = torch.zeros(N, dtype=torch.int64, device=dev), torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+            h.act_ex(flat, feat, goal, h0, m, N, ws, hv, hf, act, lp, v, 7, 3, 0, prev_actions=prev,
+                     expert_actions=expert if forcing else None, expert_mask=emask if forcing else None, force_p=1.0 if forcing else 0.0)
+            outs.append((act.clone(), hv.clone()))
+        torch.cuda.synchronize()
+        on = emask != 0
+        assert torch.equal(outs[1][0][on], expert[on]) and torch.equal(outs[1][0][~on], outs[0][0][~on])
+        assert torch.equal(outs[0][1], outs[1][1])
+
+
+def test_learn_pass_without_the_reordered_weight_ih():
+    """One case in a fresh child process with the re-ordered weight_ih switched off (EC_WIH_PERM=0, read once per process): at
+    S = 7 the routes that keep weight_ih's column order -- the dense copy, the dense gradient added back row by row."""
+    import json
+    import subprocess
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, os.path.join(here, "_prev_action_mode_check.py")], env={**os.environ, "EC_WIH_PERM": "0"},
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    print(out)
+    assert out["wih_perm"] == "0" and out["deterministic"]
+    assert max(out["forward"]) < 2e-5 and max(out["act"]) < 2e-5, out
+    for name, e in out["grads"].items():
+        assert e < 2e-4, (name, e)
+
+
+def test_module_autograd_surface(dev):
+    """``ResnetTensorObjectNavActorCritic(add_prev_actions=True, action_embed_size=6, add_prev_action_null_token=True)``: the
+    upstream parameter name, ``prev_actions`` [T, N, 1] through autograd against the reference, ``.grad`` views of the flat
+    bucket, ``load_state_dict`` of a reference state dict."""
+    from embodied_clip_amd import spaces
+    from embodied_clip_amd.policy import Memory, ResnetTensorObjectNavActorCritic
+    from embodied_clip_amd.ppo import PPO
+    case = (4, 3, 7, 64, 32, 6, 1, 6, 0, False)
+    T, N, A = 4, 3, 6
+    c = _case(*case)
+    b, sd = c["batch"], c["sd"]
+    obs_space = spaces.Dict({"rgb_clip_resnet": spaces.Box(-1e9, 1e9, (64, 7, 7)), "goal_object_type_ind": spaces.Discrete(12)})
+    mk = lambda **kw: ResnetTensorObjectNavActorCritic(spaces.Discrete(A), obs_space, "goal_object_type_ind", "rgb_clip_resnet",
+                                                       hidden_size=32, device=dev, add_prev_actions=True, action_embed_size=6,
+                                                       add_prev_action_null_token=True, **kw)
+    model = mk()
+    names = [n for n, _ in model.named_parameters()]
+    assert names == list(syn.policy_param_order(prev_action_dims=6, prev_action_null=1)) and names[-1] == ref.EMB_KEY
+    assert tuple(model.prev_action_embedder.fc.weight.shape) == (A + 1, 6)
+    model.load_state_dict(sd)                                     # a reference state dict, by the upstream names
+    assert set(model.state_dict()) == set(sd)
+    obs = {"rgb_clip_resnet": b["feat"].to(dev), "goal_object_type_ind": b["goal"].to(dev)}
+    mem = Memory().check_append("rnn", b["h0"].to(dev), 1)
+    out, mem2 = model(obs, mem, b["prev_actions"].unsqueeze(-1).to(dev), b["masks"].to(dev))
+    assert _rel(out.distributions.logits, torch.log_softmax(c["logits"], -1)) < 2e-5 and _rel(out.values, c["values"]) < 2e-5
+    assert _rel(mem2.tensor("rnn"), c["h"]) < 2e-5
+    batch = dict(actions=b["actions"].to(dev), old_action_log_probs=b["old_log_probs"].to(dev), values=b["old_values"].to(dev),
+                 returns=b["returns"].to(dev), norm_adv_targ=b["norm_adv"].to(dev), adv_targ=b["norm_adv"].to(dev))
+    total, _ = PPO().loss(0, batch, out)
+    total.backward()
+    assert abs(float(total.detach()) - c["info"]["ppo_total"]) < 1e-5 * max(1.0, abs(c["info"]["ppo_total"]))
+    views = model.handle.views(model.flat_grads)
+    for n, p in model.named_parameters():
+        assert p.grad is not None and _rel(p.grad, c["ref_grads"][n]) < 2e-4, n
+        assert p.grad.data_ptr() == views[n].data_ptr()
+    with torch.no_grad():                                         # the no-grad act route reads prev_actions too
+        out2, _ = model(obs, Memory().check_append("rnn", b["h0"].to(dev), 1), b["prev_actions"].to(dev), b["masks"].to(dev))
+        other, _ = model(obs, Memory().check_append("rnn", b["h0"].to(dev), 1), (b["prev_actions"].to(dev) + 1) % A, b["masks"].to(dev))
+    assert _rel(out2.values, c["values"]) < 2e-5 and not torch.equal(other.values, out2.values)
+    plain = ResnetTensorObjectNavActorCritic(spaces.Discrete(A), obs_space, "goal_object_type_ind", "rgb_clip_resnet", hidden_size=32,
+                                             device=dev)
+    assert len(list(plain.parameters())) == 17 and not plain.add_prev_actions

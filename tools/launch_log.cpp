@@ -202,7 +202,9 @@ static int run_policy(const int* v) {
     const int T = v[13], N = v[14], mode = v[15], bf16 = v[16], reuse = v[17], goal_in = v[12], dual = v[11];
     if (mode < 0 || mode > 1 || (reuse && mode != 0)) return -100;
     void* h = nullptr;
-    int rc = sym<int (*)(P*, const int*)>("ec_policy_create")(&h, v);
+    int cfg[32] = {0};                                  // the 13 fields, zero-filled behind them (fields a later header adds read 0)
+    memcpy(cfg, v, 13 * sizeof(int));
+    int rc = sym<int (*)(P*, const int*)>("ec_policy_create")(&h, cfg);
     if (rc) return rc;
     const size_t ws = sym<size_t (*)(P, int, int, int)>("ec_policy_workspace_bytes")(h, T, N, mode);
     printf("W %zu\n", ws);
