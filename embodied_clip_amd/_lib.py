@@ -168,7 +168,16 @@ SIGNATURES = {
                          + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
     "ec_prev_action_grad": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p, c_void_p, C.c_long, c_int] + [c_void_p] * 3
                             + [C.c_long, c_int, c_int, c_void_p]),
+    # the recurrent cell: handles with an LSTM core (state rows [h | c] of width 2H), and the LSTM step kernels alone
+    "ec_policy_create_rnn": (c_int, [C.POINTER(c_void_p), c_void_p, c_int]),
+    "ec_policy_rnn_type": (c_int, [c_void_p]),
+    "ec_policy_state_width": (c_int, [c_void_p]),
+    "ec_lstm_step_fwd": (c_int, [c_void_p] * 4 + [C.c_long, c_void_p, c_void_p, C.c_long, c_void_p, C.c_long, c_void_p, c_int, c_int,
+                                 c_void_p]),
+    "ec_lstm_step_bwd": (c_int, [c_void_p] * 12 + [c_int, c_int, c_void_p]),
 }
+
+RNN_TYPES = {"GRU": 0, "LSTM": 1}      # include/ec_amd.h EC_RNN_GRU / EC_RNN_LSTM
 
 
 class PolicyCfg(C.Structure):

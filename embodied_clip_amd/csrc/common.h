@@ -349,6 +349,20 @@ void ec_pa_rows_copy_launch(const float* in, int ld_in, float* out, int ld_out, 
 void ec_pa_grad_launch(const float* dgi, const long long* prev, const float* masks, int null_token, int A, const float* emb,
                        const float* w, long ld, int col0, float* demb, float* dw, float* scratch, long B, int G, int E, hipStream_t s);
 
+// lstm.hip: the LSTM cell's step kernels for policy.hip's two recurrence() members (argument meanings: the kernels' headers).
+// ec_lstm_hidden_ok: H % 32 == 0 and the forward step's two operand tiles fit the LDS (every H % 256 == 0; else H <= 608).
+size_t ec_lstm_fwd_lds(int H);
+bool ec_lstm_hidden_ok(int H);
+void ec_lstm_fwd_launch(const float* gi, const float* whh, const float* bhh, const float* hprev, const float* cprev, long ld_prev,
+                        const float* mask, float* hout, long ld_h, float* cout, long ld_c, float* hout2, long ld_h2, float* gates,
+                        float* hp_s, float* cp_s, int N, int H, int gi_parts, long gi_pstride, hipStream_t s);
+void ec_lstm_bwd_gates_launch(const float* dhs, float* carry_h, float* carry_c, const float* gates, const float* cs, const float* cp_s,
+                              const float* mask, float* da, int N, int H, hipStream_t s);
+void ec_lstm_bwd_fused_launch(const float* da_next, const float* whhT, const float* mask_next, const float* dhs, float* carry_c,
+                              const float* gates, const float* cs, const float* cp_s, const float* mask, float* da, int N, int H,
+                              hipStream_t s);
+void ec_lstm_state_rows_launch(float* state, float* hpart, float* cpart, int N, int H, int split, hipStream_t s);
+
 #define EC_CHECK_LAUNCH()                                   \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \

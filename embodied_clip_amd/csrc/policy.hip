@@ -1502,6 +1502,7 @@ struct ec_policy {
     size_t off[P_COUNT], num[P_COUNT], total;
     int order[P_COUNT], ntensors;        // the flat buffer's tensor order (what ec_policy_param_offset's idx counts)
     const float* goal_table = nullptr;   // fusion == 1: borrowed f32 [num_goals, in_channels]
+    int rnn = EC_RNN_GRU;                // the recurrent cell (ec_policy_create_rnn)
     // EC_POLICY_INFER_REUSE bookkeeping: the key of the launch plan (make_plan) that built the weight-derived tables in a given
     // act workspace.  Which tables exist and where (E1, W1's planes in fragment order, the re-ordered weight_ih and its
     // fragment-order copy) are plan fields, and an inference plan is a function of exactly (handle, T, N, feature dtype): a
@@ -1637,6 +1638,7 @@ struct Geo {
     int H, A, A1, C, cat;         // hidden size; actions, actions + critic; feature channels; compress_out + goal_dims
     int nstream, flat1, flat;     // encoder streams (2: dual RGB + depth); one stream's / the whole GRU input width
     int E, R, ldw;                // previous-action embedding: width (0: none), table rows, weight_ih's row stride flat + E
+    int G, SW;                    // gate width 3H (GRU) | 4H (LSTM); state width H | 2H (an LSTM state row is [h | c])
 };
 
 struct Ws {   // float offsets into the workspace
@@ -1655,6 +1657,9 @@ struct Ws {   // float offsets into the workspace
     // previous-action embedding (all empty with prev_action_dims == 0): the table PT [R, 3H] (weight-derived: kept with E1 under
     // EC_POLICY_INFER_REUSE); the learn pass's copy of the int64 indices; ec_pa_grad_launch's scratch
     size_t pt, paidx, pas;
+    // LSTM handles (all empty on a GRU handle): the cell-state history [B, H]; the backward's dL/dc carry [N, H].  On such a handle
+    // `hn` holds the masked previous cell states, `dgi` the one gate gradient da, and `dghb` is empty.
+    size_t cs, dcc;
 };
 constexpr int GP_MAXY = 64;                   // row blocks of tn_small_part_kernel
 constexpr int HP_MAXY = 128;                  // row blocks of the wide heads' column sum
@@ -1663,11 +1668,14 @@ enum class C1 { pingpong, act_kernel, split_parts, plain };      // compressor c
 enum class Gi { act7, act8, split_parts, plain };                // GRU input projection (act7 / act8: gi_act_kernel<7 | 8>)
 enum class Wih { plain, perm_learn, perm_act };                  // weight_ih as stored / re-ordered per learn pass / per act-table build
 enum class Step { gemm_gates, fused32, fused16 };                // a recurrence step: GEMM + gate kernel / 32-tile / 16-tile fused kernel
+enum class Cell { gru, lstm };                                   // the recurrent cell (lstm.hip's kernels: always the 32-tile ones)
 
 struct Plan {
     Geo g;
+    Cell cell;
     bool vec;                     // coordinate goals (goal_in > 0): per-frame bias rows instead of the goal-id table
     bool wide;                    // learn pass with A + 1 > 8: the heads through one packed table, and no float atomics on any route
+    bool ordered;                 // no float atomics on any route of the backward: coordinate goals, wide handles, LSTM handles
     bool infer, feat_bf16;        // infer: EC_POLICY_INFER or _REUSE (stated by the caller, never inferred from the workspace size)
     ec_policy::Built key;         // what a REUSE call must match
     int act_parts;                // partial matrices the c1 / gi areas hold: ACT_PARTS for the act step's few rows, else 1
@@ -1684,10 +1692,11 @@ struct Plan {
     Ws w;
 };
 
-Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
-    const size_t B = g.B, M49 = g.M49, H = g.H, N = g.N, flat = g.flat, E1 = (size_t)c.num_goals * c.comb_hid;
+Ws layout(const ec_policy_cfg& c, const Geo& g, Cell cell, int parts, bool bwd) {
+    const size_t B = g.B, M49 = g.M49, H = g.H, N = g.N, flat = g.flat, E1 = (size_t)c.num_goals * c.comb_hid, G = g.G;
+    const bool lstm = cell == Cell::lstm;
     const size_t w1planes = c.fusion ? 0 : ((size_t)c.compress_hid * 3 * c.in_channels + 1) / 2;   // W1 as three bf16 planes
-    const size_t wih = c.fusion ? 0 : 3 * H * flat;                                                  // a re-ordered copy of weight_ih
+    const size_t wih = c.fusion ? 0 : G * flat;                                                  // a re-ordered copy of weight_ih
     Ws w; size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += al(n * 4) / 4; return r; };
     auto take_if = [&](bool on, size_t n) { return take(on ? n : 0); };   // an area that is not needed: empty, at the running offset
@@ -1700,9 +1709,9 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
         w.st[i].x4 = take_if(on, M49 * c.comb_out);
     }
     w.x = take(B * flat);
-    w.gi = take(B * 3 * H * parts);
-    w.gh = take(N * 3 * H);
-    w.gates = take(B * 3 * H);
+    w.gi = take(B * G * parts);
+    w.gh = take(N * G);
+    w.gates = take(B * G);
     w.hn = take(B * H); w.hp = take(B * H); w.hs = take(B * H);
     w.goal32 = take(B);
     w.w1p = take(w1planes);
@@ -1711,7 +1720,7 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
     // what only the learn pass and its backward need
     w.dhs = take_if(bwd, B * H);
     w.dhc = take_if(bwd, N * H);
-    w.dgi = take_if(bwd, B * 3 * H); w.dghb = take_if(bwd, B * 3 * H);
+    w.dgi = take_if(bwd, B * G); w.dghb = take_if(bwd && !lstm, B * G);
     w.dx = take_if(bwd, B * flat);
     w.dx4 = take_if(bwd, M49 * c.comb_out);
     w.dm1 = take_if(bwd, M49 * c.comb_hid);
@@ -1720,9 +1729,9 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
     w.dE1 = take_if(bwd, E1);
     w.tpart = take_if(bwd && !c.fusion, (size_t)TB_MAX_WG * 4 * TB_PART);              // tail_bwd_kernel's partial sets
     w.tpartE = take_if(bwd && !c.fusion, (size_t)TB_MAX_WG * 4 * c.num_goals * 128);   // ... and its per-wave dE1 tables
-    w.whhT = take_if(bwd, H * 3 * H);                                                     // W_hh^T (fused backward step)
+    w.whhT = take_if(bwd, H * G);                                                     // W_hh^T (fused backward step)
     w.wihP = take_if(bwd, wih); w.gwihP = take_if(bwd, wih);                              // weight_ih in pixel-major column order (EC_WIH_PERM) and its gradient
-    w.tA = take_if(bwd, B * 3 * H);                                                       // transposed operands of the GRU's weight-gradient GEMMs
+    w.tA = take_if(bwd, B * G);                                                       // transposed operands of the GRU's weight-gradient GEMMs
     w.tB = take_if(bwd, B * (flat > H ? flat : H));
     const bool vec = c.goal_in > 0;
     w.E1f = take_if(vec, B * c.comb_hid); w.Eg = take_if(vec, B * c.goal_dims);
@@ -1734,9 +1743,11 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, int parts, bool bwd) {
     w.hW = take_if(wide, (size_t)g.A1 * H + g.A1); w.hG = take_if(wide, (size_t)g.A1 * H + g.A1);
     w.hP = take_if(wide, (size_t)HP_MAXY * g.A1);
     const bool pa = g.E > 0;
-    w.pt = take_if(pa, (size_t)g.R * 3 * H);
+    w.pt = take_if(pa, (size_t)g.R * G);
     w.paidx = take_if(pa && bwd, 2 * B);
-    w.pas = take_if(pa && bwd, pa ? ec_pa_grad_scratch_floats((long)B, 3 * g.H, g.R) : 0);
+    w.pas = take_if(pa && bwd, pa ? ec_pa_grad_scratch_floats((long)B, g.G, g.R) : 0);
+    w.cs = take_if(lstm, B * H);
+    w.dcc = take_if(lstm && bwd, N * H);
     w.end = o;
     return w;
 }
@@ -1753,9 +1764,12 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     g.H = c.hidden; g.A = c.num_actions; g.A1 = g.A + 1; g.C = c.in_channels; g.cat = c.compress_out + c.goal_dims;
     g.nstream = (c.dual && !c.fusion) ? 2 : 1; g.flat1 = c.comb_out * g.S; g.flat = c.fusion ? c.in_channels : g.nstream * g.flat1;
     g.E = c.prev_action_dims; g.R = c.num_actions + c.prev_action_null; g.ldw = g.flat + g.E;   // (no route below depends on E)
+    p.cell = h->rnn == EC_RNN_LSTM ? Cell::lstm : Cell::gru;
+    g.G = (p.cell == Cell::lstm ? 4 : 3) * c.hidden; g.SW = (p.cell == Cell::lstm ? 2 : 1) * c.hidden;
     const int B = g.B, S = g.S, M49 = g.M49, H = g.H, C = g.C, flat = g.flat;
     p.infer = mode != EC_POLICY_LEARN; p.feat_bf16 = feat_bf16; p.vec = c.goal_in > 0;
     p.wide = !p.infer && g.A1 > 8;
+    p.ordered = p.vec || p.wide || p.cell == Cell::lstm;
     p.key = ec_policy::Built{T, N, feat_bf16 ? 1 : 0};
     // Act step: so few rows that the two long-K, small-M GEMMs (compressor conv 1, GRU input projection) run as ACT_PARTS K
     // slices whose partial matrices the consuming kernels fold in a fixed order (no float atomics: rollouts stay bit-reproducible)
@@ -1794,11 +1808,19 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     const Step fused = (cfg.gru_fused >= 2 && H == 512 && !p.infer) ? Step::fused16 : Step::fused32;
     p.step_fwd = step_ok ? fused : Step::gemm_gates;
     p.step_bwd = (cfg.gru_fused && (H % 256) == 0 && T > 1) ? fused : Step::gemm_gates;
+    // an LSTM handle: the 32-tile kernels of lstm.hip at every H (ec_policy_create_rnn admits only widths whose forward tiles fit);
+    // EC_GRU_FUSED=0 still selects the gate-plus-GEMM pair for its backward
+    if (p.cell == Cell::lstm) {
+        p.gru_lds = ec_lstm_fwd_lds(H);
+        p.step_fwd = Step::fused32;
+        if (p.step_bwd == Step::fused16) p.step_bwd = Step::fused32;
+    }
+    const bool step_ok_any = step_ok || p.cell == Cell::lstm;
     // GRU input projection.  Act step with a handful of rows: one launch, K split over the waves of a workgroup and folded
     // in-kernel (gi_act_kernel); else split-K only as separate partial matrices folded by the step kernel
     const int gi_nw = (flat % 56 == 0) ? 7 : ((flat % 64 == 0) ? 8 : 0);
-    if (cfg.act_split && p.wih == Wih::perm_act && T == 1 && B <= 256 && gi_nw != 0 && (3 * H) % 32 == 0) p.gi = gi_nw == 7 ? Gi::act7 : Gi::act8;
-    else p.gi = (act_on && step_ok && (flat + 31) / 32 >= ACT_PARTS) ? Gi::split_parts : Gi::plain;
+    if (cfg.act_split && p.wih == Wih::perm_act && T == 1 && B <= 256 && gi_nw != 0 && g.G % 32 == 0) p.gi = gi_nw == 7 ? Gi::act7 : Gi::act8;
+    else p.gi = (act_on && step_ok_any && (flat + 31) / 32 >= ACT_PARTS) ? Gi::split_parts : Gi::plain;
     p.gi_fold = p.gi == Gi::split_parts ? ACT_PARTS : 1;
     // EC_GEMM_BWD3 / EC_POLICY_FAST: the large gradient GEMMs (weight gradients over all T*N rows, dx = dgi @ W_ih) on the three
     // leading products of the bf16x3 split (relative product error 2^-16; gradients agree with the fp32 oracle to ~1e-5, not ~1e-6)
@@ -1809,7 +1831,7 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     // EC_DW1_TR (default 1): dW1 through the transpose-read kernel (dw_tn.hip), its partial tiles in the tail's partial sets
     p.dw1_planes = p.tail_bwd && cfg.dw1_tr && feat_bf16 && C % 256 == 0 && M49 >= 2048 &&
                    (size_t)ec_dw_tn_x3_splits(M49, C) * 128 * C <= (size_t)TB_MAX_WG * 4 * TB_PART;
-    p.w = layout(c, g, p.act_parts, mode == EC_POLICY_LEARN);
+    p.w = layout(c, g, p.cell, p.act_parts, mode == EC_POLICY_LEARN);
     return p;
 }
 
@@ -1854,7 +1876,7 @@ struct Fwd : Ctx {
     const float* wih_plain() const { return g.E ? ws + (p.infer ? w.wihA : w.wihP) : W(P_WIH); }
     // previous-action embedding: the table (with the other weight-derived tables) and, for a backward, the indices
     void prev_action_tables() {
-        if (!reuse) ec_pa_table_launch(W(P_PAE), W(P_WIH), g.ldw, g.flat, ws + w.pt, g.R, 3 * g.H, g.E, s);
+        if (!reuse) ec_pa_table_launch(W(P_PAE), W(P_WIH), g.ldw, g.flat, ws + w.pt, g.R, g.G, g.E, s);
         if (!p.infer) (void)hipMemcpyAsync(ws + w.paidx, prev, (size_t)g.B * 8, hipMemcpyDeviceToDevice, s);
     }
 
@@ -1949,9 +1971,9 @@ struct Fwd : Ctx {
             hipLaunchKernelGGL(to_cmajor_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws + o.x4, ws + w.x,
                                g.S, c.comb_out, total, g.flat, sidx * g.flat1);
             if (g.E && (!p.infer || !reuse))
-                ec_pa_rows_copy_launch(W(P_WIH), g.ldw, ws + (p.infer ? w.wihA : w.wihP), g.flat, 3 * g.H, g.flat, 0, s);
+                ec_pa_rows_copy_launch(W(P_WIH), g.ldw, ws + (p.infer ? w.wihA : w.wihP), g.flat, g.G, g.flat, 0, s);
         } else if (p.wih == Wih::perm_learn || !reuse) {
-            hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * g.H)), dim3(256), g.flat * sizeof(float), s, W(P_WIH),
+            hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)g.G), dim3(256), g.flat * sizeof(float), s, W(P_WIH),
                                ws + (p.wih == Wih::perm_learn ? w.wihP : w.wihA), g.S, c.comb_out, 0, g.ldw);
         }
         return EC_OK;
@@ -1959,37 +1981,61 @@ struct Fwd : Ctx {
 
     // GRU input projection for all T at once
     int input_projection() {
-        const int B = g.B, H = g.H, flat = g.flat;
+        const int B = g.B, G = g.G, flat = g.flat;
         if (p.gi == Gi::act7 || p.gi == Gi::act8) {
             const float* xin = ws + w.st[0].x4;
             const float* win = ws + w.wihF;                              // the re-ordered weight_ih in fragment order
             if (!reuse) {
-                const long nu = (long)3 * H * flat / 4;
+                const long nu = (long)G * flat / 4;
                 hipLaunchKernelGGL(frag_pack_f32_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, (const float4*)(ws + w.wihA),
-                                   (float4*)(ws + w.wihF), 3 * H, flat);
+                                   (float4*)(ws + w.wihF), G, flat);
             }
             const int nw = p.gi == Gi::act7 ? 7 : 8;                     // waves of a workgroup
-            const dim3 grid((unsigned)(3 * H / 32), (unsigned)((B + 31) / 32));
+            const dim3 grid((unsigned)(G / 32), (unsigned)((B + 31) / 32));
             if (g.E)      // the previous action's table row rides in the fold (prev_action.hip's instance of the same body): as many launches
-                ec_pa_gi_act_launch(nw, xin, win, W(P_BIH), ws + w.gi, B, flat, 3 * H,
+                ec_pa_gi_act_launch(nw, xin, win, W(P_BIH), ws + w.gi, B, flat, G,
                                     ec_gi_act_pa{ws + w.pt, prev, masks_all, c.prev_action_null, c.num_actions}, s);
             else
             hipLaunchKernelGGL(nw == 7 ? gi_act_kernel<7> : gi_act_kernel<8>, grid, dim3(64 * nw), 0, s,
-                               xin, win, W(P_BIH), ws + w.gi, B, flat, 3 * H);
+                               xin, win, W(P_BIH), ws + w.gi, B, flat, G);
             return EC_OK;
         }
         const float* xin = p.wih == Wih::plain ? ws + w.x : ws + w.st[0].x4;
         const float* win = p.wih == Wih::perm_learn ? ws + w.wihP : (p.wih == Wih::perm_act ? ws + w.wihA : wih_plain());
-        RC(ec_gemm_f32(xin, win, ws + w.gi, B, 3 * H, flat, flat, 1, 1, flat, 3 * H, p.gi == Gi::split_parts ? EC_GEMM_SPLIT_PARTS : 0,
+        RC(ec_gemm_f32(xin, win, ws + w.gi, B, G, flat, flat, 1, 1, flat, G, p.gi == Gi::split_parts ? EC_GEMM_SPLIT_PARTS : 0,
                        W(P_BIH), nullptr, nullptr, 0, nullptr, nullptr, p.gi_fold, stream));
         // the previous action's table row, onto part 0 of a split-K projection (the step kernel folds the parts in order)
-        if (g.E) ec_pa_add_launch(ws + w.gi, ws + w.pt, prev, masks_all, c.prev_action_null, c.num_actions, (long)B, 3 * H, s);
+        if (g.E) ec_pa_add_launch(ws + w.gi, ws + w.pt, prev, masks_all, c.prev_action_null, c.num_actions, (long)B, G, s);
+        return EC_OK;
+    }
+
+    // LSTM handle: one lstm.hip launch per step.  h0 and state_out are [N, 2H] rows [h | c]; the histories hs / cs are dense, so
+    // step 0 reads pitch 2H and every later step pitch H.  T == 1 inference with a state row of its own: the step stores h
+    // densely for the heads AND into the row, c into the row -- the GRU act step's launch count, no copy on the serial chain.
+    float* state_out = nullptr;      // the caller's h_final on an LSTM handle (or null)
+    int recurrence_lstm(const float* h0, const float* masks, float* hs) {
+        const int N = g.N, H = g.H, T = g.T;
+        float* cs = ws + w.cs;
+        const bool direct = p.hs_direct && state_out && state_out != h0;
+        const bool keep = !p.infer;      // learn pass: gates and the masked previous states for the backward
+        for (int t = 0; t < T; ++t) {
+            const size_t o4 = (size_t)t * N * g.G, o1 = (size_t)t * N * H;
+            const float* hprev = t == 0 ? h0 : hs + o1 - (size_t)N * H;
+            const float* cprev = t == 0 ? h0 + H : cs + o1 - (size_t)N * H;
+            ec_lstm_fwd_launch(ws + w.gi + o4, W(P_WHH), W(P_BHH), hprev, cprev, t == 0 ? 2L * H : (long)H, masks + (size_t)t * N, hs + o1, H,
+                               direct ? state_out + H : cs + o1, direct ? 2L * H : (long)H, direct ? state_out : nullptr, 2L * H,
+                               keep ? ws + w.gates + o4 : nullptr, keep ? ws + w.hp + o1 : nullptr, keep ? ws + w.hn + o1 : nullptr, N, H,
+                               p.gi_fold, (long)g.B * g.G, s);
+        }
+        if (state_out && !direct)
+            ec_lstm_state_rows_launch(state_out, hs + (size_t)(T - 1) * N * H, cs + (size_t)(T - 1) * N * H, N, H, 0, s);
         return EC_OK;
     }
 
     // the sequential recurrence; step t's new state goes to hs + t * N * H
     int recurrence(const float* h0, const float* masks, float* hs) {
         const int N = g.N, H = g.H;
+        if (p.cell == Cell::lstm) return recurrence_lstm(h0, masks, hs);
         const size_t gru16_lds = (size_t)(4 * 64 * 128 + 4 * 3 * 256) * sizeof(float);
         if (p.step_fwd == Step::fused32) allow_big_lds<gru_step_fwd_kernel>();
         if (p.step_fwd == Step::fused16) allow_big_lds<gru_step_fwd512_kernel>();
@@ -2070,9 +2116,11 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
             RC(f.encoder_stream(sidx, sidx ? feat2 : feat));
     if (p.g.E) { f.prev = (const long long*)prev_actions; f.masks_all = masks; f.prev_action_tables(); }
     RC(f.input_projection());
-    float* hs = (p.hs_direct && h_final && h_final != h0) ? h_final : f.ws + p.w.hs;
+    const bool lstm = p.cell == Cell::lstm;   // (the heads read the dense history; recurrence_lstm leaves the [h | c] rows in h_final)
+    float* hs = (!lstm && p.hs_direct && h_final && h_final != h0) ? h_final : f.ws + p.w.hs;
+    if (lstm) f.state_out = h_final;
     RC(f.recurrence(h0, masks, hs));
-    RC(f.heads(hs, hv, h_final, smp, wide));
+    RC(f.heads(hs, hv, lstm ? nullptr : h_final, smp, wide));
     EC_CHECK_LAUNCH();
     return EC_OK;
 }
@@ -2087,7 +2135,7 @@ struct Bwd : Ctx {
     // column sums (bias gradients) without atomics: row block y leaves its sums in cpart[y][Ncol] (the forward's per-step `gh`
     // scratch: N x 3H floats, idle in the backward), colsum_fold_kernel adds the row blocks in order onto the gradient
     void colsum(const float* Y, float* out, long M, int Ncol, int ld, float* cpart = nullptr, size_t cpart_cap = 0) {
-        if (!cpart) { cpart = ws + w.gh; cpart_cap = (size_t)g.N * 3 * g.H; }
+        if (!cpart) { cpart = ws + w.gh; cpart_cap = (size_t)g.N * g.G; }
         const bool wide = (Ncol & 3) == 0 && (ld & 3) == 0 && Ncol >= 256 && M >= 1024;
         long nby = (M + (wide ? 255 : 2047)) / (wide ? 256 : 2048);
         const long fit = (long)(cpart_cap / (size_t)Ncol);
@@ -2121,7 +2169,7 @@ struct Bwd : Ctx {
     // tail's unfused fallback GEMMs (EC_TAIL_FUSED=0, the dual encoder) run after dx exists and keep the atomic split
     int tn(const float* dY, int ldy, const void* X, int ldx, int x_bf16, float* dW, int Mo, int No, long K, int ldc) {
         // (coordinate goals, wide handles: no float atomics on any route -- without the partial-matrix area the GEMM walks K in one piece)
-        const int sk = ((p.vec || p.wide) && !parts_ok) ? 1 : pick_splitk(Mo, No, K), flags = (x_bf16 ? EC_GEMM_B_BF16 : 0) | p.bwd3;
+        const int sk = (p.ordered && !parts_ok) ? 1 : pick_splitk(Mo, No, K), flags = (x_bf16 ? EC_GEMM_B_BF16 : 0) | p.bwd3;
         if (parts_ok) return gemm_acc_split(dY, X, dW, Mo, No, K, 1, ldy, ldx, 1, ldc, flags, sk);
         return ec_gemm_f32(dY, X, dW, Mo, No, (int)K, 1, ldy, ldx, 1, ldc, EC_GEMM_ACCUMULATE | flags, nullptr, nullptr, nullptr, 0, nullptr,
                            nullptr, sk, stream);
@@ -2158,10 +2206,43 @@ struct Bwd : Ctx {
         return EC_OK;
     }
 
+    // LSTM, reverse time (lstm.hip).  dh_final is [N, 2H] rows [dh | dc]: its halves start the two carries.  Fused: step T-1 is
+    // the plain gate kernel, every earlier step ONE launch (back-projection of step t+1 + gates of step t, against a W_hh
+    // transposed once); else gate kernel + GEMM per step with split-K 1.  No float atomics on either route.
+    int recurrence_lstm(const float* masks, const float* dh_final) {
+        const int T = g.T, N = g.N, H = g.H, GW = g.G;
+        float* da = ws + w.dgi;
+        if (dh_final) ec_lstm_state_rows_launch(const_cast<float*>(dh_final), ws + w.dhc, ws + w.dcc, N, H, 1, s);
+        else {
+            (void)hipMemsetAsync(ws + w.dhc, 0, (size_t)N * H * 4, s);
+            (void)hipMemsetAsync(ws + w.dcc, 0, (size_t)N * H * 4, s);
+        }
+        const bool fused = p.step_bwd != Step::gemm_gates;
+        if (fused)
+            hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)(H / 32), (unsigned)(GW / 32)), dim3(256), 0, s, W(P_WHH), ws + w.whhT, GW, H);
+        for (int t = T - 1; t >= 0; --t) {
+            const size_t o4 = (size_t)t * N * GW, o1 = (size_t)t * N * H;
+            const float* m = masks + (size_t)t * N;
+            if (!fused || t == T - 1) {
+                ec_lstm_bwd_gates_launch(ws + w.dhs + o1, ws + w.dhc, ws + w.dcc, ws + w.gates + o4, ws + w.cs + o1, ws + w.hn + o1, m, da + o4,
+                                         N, H, s);
+                // dh_carry (left zero by the gate kernel) += m * (da @ W_hh)   (fused: inside the next launch)
+                if (!fused)
+                    RC(ec_gemm_f32(da + o4, W(P_WHH), ws + w.dhc, N, H, GW, GW, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr, nullptr, nullptr, 0,
+                                   nullptr, m, 1, stream));
+            } else {
+                ec_lstm_bwd_fused_launch(da + o4 + (size_t)N * GW, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dcc, ws + w.gates + o4,
+                                         ws + w.cs + o1, ws + w.hn + o1, m, da + o4, N, H, s);
+            }
+        }
+        return EC_OK;
+    }
+
     // GRU, reverse time.  Fused: step T-1 is the plain gate kernel (its carry is dh_final), every earlier step ONE fused launch
     // (back-projection of step t+1 + gates of step t); else gate kernel + GEMM per step
     int recurrence(const float* masks, const float* dh_final) {
         const int T = g.T, N = g.N, H = g.H;
+        if (p.cell == Cell::lstm) return recurrence_lstm(masks, dh_final);
         const size_t gb_lds = (size_t)2 * 32 * (256 + 4) * sizeof(float), gb16_lds = (size_t)(4 * 2 * 32 * 128 + 4 * 256) * sizeof(float);
         if (dh_final) (void)hipMemcpyAsync(ws + w.dhc, dh_final, (size_t)N * H * 4, hipMemcpyDeviceToDevice, s);
         else (void)hipMemsetAsync(ws + w.dhc, 0, (size_t)N * H * 4, s);
@@ -2193,40 +2274,42 @@ struct Bwd : Ctx {
     }
 
     // weight and bias gradients of the recurrence and of the input projection (TN over all T*N rows)
+    // (an LSTM handle's one gate gradient da lies in the dgi area and serves as both)
     int gru_grads() {
-        const int B = g.B, H = g.H, flat = g.flat;
-        RC(tn_gru(ws + w.dghb, ws + w.hp, G(P_WHH), 3 * H, H, B));
-        colsum(ws + w.dghb, G(P_BHH), B, 3 * H, 3 * H);
+        const int B = g.B, H = g.H, flat = g.flat, GW = g.G;
+        const float* dghb = ws + (p.cell == Cell::lstm ? w.dgi : w.dghb);
+        RC(tn_gru(dghb, ws + w.hp, G(P_WHH), GW, H, B));
+        colsum(dghb, G(P_BHH), B, GW, GW);
         if (p.wih == Wih::perm_learn) {   // gradient in the re-ordered weight's column order, then added back in the parameter's order
-            (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)3 * H * flat * 4, s);
-            RC(tn_gru(ws + w.dgi, ws + w.st[0].x4, ws + w.gwihP, 3 * H, flat, B));
-            hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(3 * H)), dim3(256), flat * sizeof(float), s, ws + w.gwihP,
+            (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)GW * flat * 4, s);
+            RC(tn_gru(ws + w.dgi, ws + w.st[0].x4, ws + w.gwihP, GW, flat, B));
+            hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(GW)), dim3(256), flat * sizeof(float), s, ws + w.gwihP,
                                G(P_WIH), g.S, c.comb_out, 1, g.ldw);
         } else if (g.E) {                 // the dense gradient, then added back onto the parameter's rows (stride flat + E)
-            (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)3 * H * flat * 4, s);
-            RC(tn_gru(ws + w.dgi, ws + w.x, ws + w.gwihP, 3 * H, flat, B));
-            ec_pa_rows_copy_launch(ws + w.gwihP, flat, G(P_WIH), g.ldw, 3 * H, flat, 1, s);
+            (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)GW * flat * 4, s);
+            RC(tn_gru(ws + w.dgi, ws + w.x, ws + w.gwihP, GW, flat, B));
+            ec_pa_rows_copy_launch(ws + w.gwihP, flat, G(P_WIH), g.ldw, GW, flat, 1, s);
         } else {
-            RC(tn_gru(ws + w.dgi, ws + w.x, G(P_WIH), 3 * H, flat, B));
+            RC(tn_gru(ws + w.dgi, ws + w.x, G(P_WIH), GW, flat, B));
         }
-        colsum(ws + w.dgi, G(P_BIH), B, 3 * H, 3 * H);
+        colsum(ws + w.dgi, G(P_BIH), B, GW, GW);
         // previous-action embedding: its gradient and columns flat.. of weight_ih's (inside the recurrent section: before the event)
         if (g.E)
             ec_pa_grad_launch(ws + w.dgi, (const long long*)(ws + w.paidx), masks_all, c.prev_action_null, c.num_actions, W(P_PAE), W(P_WIH),
-                              g.ldw, flat, G(P_PAE), G(P_WIH), ws + w.pas, (long)B, 3 * H, g.E, s);
+                              g.ldw, flat, G(P_PAE), G(P_WIH), ws + w.pas, (long)B, GW, g.E, s);
         return EC_OK;
     }
 
     // dx = dgi @ W_ih (channel-major), or dx4 = dgi @ (re-ordered weight_ih): already pixel-major
     int input_grad() {
-        const int B = g.B, H = g.H, flat = g.flat;
+        const int B = g.B, flat = g.flat, GW = g.G;
         if (p.wih != Wih::perm_learn)
-            return gemm(ws + w.dgi, g.E ? ws + w.wihP : W(P_WIH), ws + w.dx, B, flat, 3 * H, 3 * H, 1, flat, 1, flat, p.bwd3);   // (E: the forward's dense copy)
+            return gemm(ws + w.dgi, g.E ? ws + w.wihP : W(P_WIH), ws + w.dx, B, flat, GW, GW, 1, flat, 1, flat, p.bwd3);   // (E: the forward's dense copy)
         // The weight is transposed first (9.6 MB, into the gradient staging buffer, free again by now) so that BOTH operands are
         // K-contiguous: the GEMM's strided-B staging runs at half the rate (263 vs ~130 us at 32 actors, 770 vs ~540 at 128)
-        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((flat + 31) / 32), (unsigned)(3 * H / 32)), dim3(256), 0, s,
-                           ws + w.wihP, ws + w.gwihP, 3 * H, flat);
-        return gemm(ws + w.dgi, ws + w.gwihP, ws + w.dx4, B, flat, 3 * H, 3 * H, 1, 1, 3 * H, flat, p.bwd3);
+        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((flat + 31) / 32), (unsigned)(GW / 32)), dim3(256), 0, s,
+                           ws + w.wihP, ws + w.gwihP, GW, flat);
+        return gemm(ws + w.dgi, ws + w.gwihP, ws + w.dx4, B, flat, GW, GW, 1, 1, GW, flat, p.bwd3);
     }
 
     // goal half of target_obs_combiner.0 (dE1 = row-group sums of dm1 scattered by goal id)
@@ -2309,7 +2392,7 @@ struct Bwd : Ctx {
                            0, nullptr, nullptr, nullptr, 0, ws + o.m1, nullptr, 1, stream));
             RC(tn(ws + w.dm1, c.comb_hid, ws + o.c2, c.compress_out, 0, GS(P_W3), c.comb_hid, c.compress_out, M49, cat));
             if (p.vec) hipLaunchKernelGGL(frame_sum_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.dm1, ws + w.dE1f, S, c.comb_hid);
-            else if (p.wide) ec_goal_group_sum_launch(ws + w.dm1, goal32, ws + w.dE1, S, c.comb_hid, (long)B, c.num_goals, s);
+            else if (p.ordered) ec_goal_group_sum_launch(ws + w.dm1, goal32, ws + w.dE1, S, c.comb_hid, (long)B, c.num_goals, s);
             else
             hipLaunchKernelGGL(group_sum_scatter_kernel, dim3((unsigned)B), dim3(128), 0, s, ws + w.dm1, goal32, ws + w.dE1, S,
                                c.comb_hid, (long)B);
@@ -2331,8 +2414,13 @@ struct Bwd : Ctx {
 
 }  // namespace
 
-extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) {
+extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) { return ec_policy_create_rnn(out, cfg, EC_RNN_GRU); }
+extern "C" int ec_policy_rnn_type(const ec_policy_t* h) { return h ? h->rnn : -1; }
+extern "C" int ec_policy_state_width(const ec_policy_t* h) { return h ? (h->rnn == EC_RNN_LSTM ? 2 : 1) * h->c.hidden : 0; }
+
+extern "C" int ec_policy_create_rnn(ec_policy_t** out, const ec_policy_cfg* cfg, int rnn_type) {
     if (!out || !cfg) return EC_ERR_ARG;
+    if (rnn_type != EC_RNN_GRU && rnn_type != EC_RNN_LSTM) return EC_ERR_ARG;
     const ec_policy_cfg& c = *cfg;
     if (c.fusion != 0 && c.fusion != 1) return EC_ERR_ARG;
     if (c.dual != 0 && c.dual != 1) return EC_ERR_ARG;
@@ -2354,18 +2442,23 @@ extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) {
     }
     // (coordinate goals: W3[:, co:] and one pass of frames sit in the LDS of the two goal_vec kernels)
     if (c.goal_in && std::max(Fwd::goal_vec_lds(c, false), Fwd::goal_vec_lds(c, true)) > 64 * 1024) return EC_ERR_SHAPE;
+    if (rnn_type == EC_RNN_LSTM) {
+        if (c.dual || c.fusion) return EC_ERR_UNSUPPORTED;   // (the two-tower and zero-shot agents keep the GRU)
+        if (!ec_lstm_hidden_ok(c.hidden)) return EC_ERR_SHAPE; // (8 units x 4 gates per tile: hidden % 32 == 0, tiles within the LDS)
+    }
     ec_policy* h = new (std::nothrow) ec_policy();
     if (!h) return EC_ERR_ALLOC;
     h->c = c;
+    h->rnn = rnn_type;
     if (c.goal_in) h->c.num_goals = 0;   // ignored: no goal table anywhere (the table areas of the workspace are empty)
-    const size_t S = (size_t)c.spatial * c.spatial, H = c.hidden;
+    const size_t S = (size_t)c.spatial * c.spatial, H = c.hidden, GW = (rnn_type == EC_RNN_LSTM ? 4 : 3) * H;
     const size_t flat = c.fusion ? (size_t)c.in_channels : (size_t)(c.dual ? 2 : 1) * c.comb_out * S;
     size_t n[P_COUNT] = {c.goal_in ? (size_t)c.goal_dims * c.goal_in : (size_t)c.num_goals * c.goal_dims,
                                (size_t)c.compress_hid * c.in_channels, (size_t)c.compress_hid,
                                (size_t)c.compress_out * c.compress_hid, (size_t)c.compress_out,
                                (size_t)c.comb_hid * (c.compress_out + c.goal_dims), (size_t)c.comb_hid,
                                (size_t)c.comb_out * c.comb_hid, (size_t)c.comb_out,
-                               3 * H * (flat + c.prev_action_dims), 3 * H * H, 3 * H, 3 * H,
+                               GW * (flat + c.prev_action_dims), GW * H, GW, GW,
                                (size_t)c.num_actions * H, (size_t)c.num_actions, H, 1, 0, 0, 0, 0, 0, 0, 0, 0,
                                c.goal_in ? (size_t)c.goal_dims : 0,
                                (size_t)(c.num_actions + c.prev_action_null) * c.prev_action_dims};

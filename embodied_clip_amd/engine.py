@@ -147,6 +147,18 @@ def check_prev_actions(prev_actions: int, depth: bool, zeroshot: bool) -> int:
     return E
 
 
+def check_rnn_type(rnn_type: str, depth: bool, zeroshot: bool) -> str:
+    """``Worker`` / ``Evaluator`` ``(rnn_type=...)``: the recurrent cell, refused where the policy library refuses it; raised
+    before anything is allocated."""
+    if rnn_type not in ("GRU", "LSTM"):
+        raise ValueError(f"rnn_type={rnn_type!r}: 'GRU' or 'LSTM'")
+    if rnn_type == "LSTM" and depth:
+        raise ValueError("rnn_type='LSTM' with depth=True: the two-tower (RGB + depth) agent keeps the GRU; an LSTM core for it is not built")
+    if rnn_type == "LSTM" and zeroshot:
+        raise ValueError("rnn_type='LSTM' with zeroshot=True: the zero-shot fusion policy keeps the GRU; an LSTM core for it is not built")
+    return rnn_type
+
+
 def check_rgbd(encoder: str, zeroshot: bool, goal_in: int, frames_host: bool) -> None:
     """What ``depth=True`` (the RGB-D agent) cannot be combined with; raised before anything is allocated."""
     if encoder not in ("rn50", "rn50x16"):
@@ -161,10 +173,19 @@ def check_rgbd(encoder: str, zeroshot: bool, goal_in: int, frames_host: bool) ->
 
 def check_model_tensors(policy, sd, where: str) -> None:
     """A checkpoint's ``model_state_dict`` against the handle's tensors: a missing one (a checkpoint written without the
-    previous-action embedding, loaded by an agent that has it) raises, naming the tensor and the file."""
+    previous-action embedding, loaded by an agent that has it) raises, naming the tensor and the file; so does one whose
+    element count differs (a GRU checkpoint's ``3H``-row recurrent tensors into an LSTM agent, or the reverse), naming both shapes."""
     for name in policy.offsets:
         if name not in sd:
             raise KeyError(f"{where}: the checkpoint lacks the tensor {name!r} {tuple(policy.shapes[name])} of this agent")
+    for name in policy.offsets:         # (behind the missing-tensor check: an agent's extra tensor is named first)
+        want = tuple(policy.shapes[name])
+        n = 1
+        for dim in want:
+            n *= dim
+        if sd[name].numel() != n:       # e.g. a GRU checkpoint's [3H, .] recurrent tensors into an LSTM agent's [4H, .], or the reverse
+            raise ValueError(f"{where}: the tensor {name!r} is {tuple(sd[name].shape)} in the checkpoint and {want} in this agent "
+                             f"(rnn_type={getattr(policy, 'rnn_type', 'GRU')!r})")
 
 
 class _SlicedActor:
@@ -181,6 +202,8 @@ class _SlicedActor:
     # (0: off) and whether row 0 is the null token of an episode's first step; set by the users before ``_build_model``
     prev_action_dims = 0
     prev_action_null = 0
+    # the recurrent cell ([U] RNNStateEncoder rnn_type): "LSTM" makes every recurrent-memory buffer [N, 2H] rows [h | c]
+    rnn_type = "GRU"
 
     def _build_model(self, n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams):
         """Encoder handles (one per slice, weights shared), the policy handle and its flat parameters.  -> (encs, pools)"""
@@ -236,7 +259,9 @@ class _SlicedActor:
             pkw["fusion"] = 1
         if self.prev_action_dims:
             pkw.update(prev_action_dims=self.prev_action_dims, prev_action_null=self.prev_action_null)
-        self.policy = PolicyHandle(**pkw)
+        self.policy = PolicyHandle(rnn_type=self.rnn_type, **pkw)
+        if policy_sd is not None:   # (a checkpoint of the other recurrent cell: refused by the tensor's name, both shapes and the file)
+            check_model_tensors(self.policy, policy_sd, getattr(self, "_checkpoint", None) or "policy_sd")
         if self.zeroshot:
             # goal table: the CLIP text tower over the 12 goal prompts, once, L2-normalised; frozen
             tsd = self._text_sd if self._text_sd is not None else syn.text_state_dict(0)
@@ -245,7 +270,9 @@ class _SlicedActor:
             self.goal_table = ClipTextEncoder(tsd, device=d).goal_table(tok).contiguous()
             self.policy.set_goal_table(self.goal_table)
         self.H, self.A = self.policy.H, self.policy.A
-        self.params = self.policy.flatten(policy_sd if policy_sd is not None else syn.policy_state_dict(0, **pkw), d)
+        self.SW = self.policy.state_width        # width of a recurrent-memory row: H, or 2H ([h | c]) with an LSTM core
+        self.params = self.policy.flatten(policy_sd if policy_sd is not None
+                                          else syn.policy_state_dict(0, **pkw, rnn_type=self.rnn_type), d)
         return encs, pools
 
     def _build_slices(self, n_actors, encs, pools, feat_steps, n_comm, frames_host):
@@ -428,8 +455,12 @@ class Worker(_SlicedActor):
                  num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
                  overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False,
                  nav_metrics: bool = False, depth: bool = False, loss: str = "ppo", il_weight: float = 1.0,
-                 teacher_forcing=None, prev_actions: int = 0, prev_action_null_token: bool = True):
-        """``loss``: what a rollout is trained on -- "ppo" (GAE, then the PPO loss: the default), "imitation" (the expert
+                 teacher_forcing=None, prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU"):
+        """``rnn_type``: "GRU" (default) or "LSTM" ([U] RNNStateEncoder ``rnn_type``; the Habitat DD-PPO policies) -- the
+        recurrent memory ``h`` / ``h_next`` / ``h_start`` is then ``[N, 2 * hidden]`` rows ``[h | c]``, checkpoints carry the
+        ``4 * hidden``-row recurrent tensors under the same names.  ``ValueError`` with ``depth=True`` or ``zeroshot=True``.
+
+        ``loss``: what a rollout is trained on -- "ppo" (GAE, then the PPO loss: the default), "imitation" (the expert
         cross-entropy of [U] AllenAct's ``Imitation`` loss on the env's expert actions; no GAE launch) or "ppo+imitation"
         (``ppo_total + il_weight * imitation``: the PPO call writes d(total)/d(hv), the imitation call adds its term).
         ``il_weight`` is the imitation term's loss weight in both.  ``teacher_forcing``: None, or a callable of ``total_steps``
@@ -468,6 +499,7 @@ class Worker(_SlicedActor):
             check_rgbd(encoder, zeroshot, goal_in, frames_host)
         self.prev_action_dims = check_prev_actions(prev_actions, bool(depth), bool(zeroshot))
         self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
+        self.rnn_type = check_rnn_type(rnn_type, bool(depth), bool(zeroshot))
         self.depth = bool(depth)
         self.lib = _lib.load()
         self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
@@ -538,9 +570,9 @@ class Worker(_SlicedActor):
         self.returns = torch.zeros((T + 1, N), dtype=torch.float32, device=d)
         self.adv = torch.zeros((T, N), dtype=torch.float32, device=d)
         self.nadv = torch.zeros((T, N), dtype=torch.float32, device=d)
-        self.h_start = torch.zeros((N, self.H), dtype=torch.float32, device=d)
-        self.h = torch.zeros((N, self.H), dtype=torch.float32, device=d)
-        self.h_next = torch.zeros((N, self.H), dtype=torch.float32, device=d)
+        self.h_start = torch.zeros((N, self.SW), dtype=torch.float32, device=d)
+        self.h = torch.zeros((N, self.SW), dtype=torch.float32, device=d)
+        self.h_next = torch.zeros((N, self.SW), dtype=torch.float32, device=d)
         self.hv_act = torch.empty((N, self.A + 1), dtype=torch.float32, device=d)
         self.stats = torch.zeros(2, dtype=torch.float64, device=d)
         self.sums = torch.zeros(4, dtype=torch.float64, device=d)

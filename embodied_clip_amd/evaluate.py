@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_prev_actions, check_rgbd
+from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_prev_actions, check_rgbd, check_rnn_type
 from .episodes import EpisodeTracker, NavEpisodeTracker, category_names, nav_env_tensors
 
 
@@ -48,7 +48,9 @@ class Evaluator(_SlicedActor):
     ``observe_depth()``; refused with the combinations ``engine.check_rgbd`` names.  ``prev_actions=E > 0`` /
     ``prev_action_null_token``: the agent of ``Worker(prev_actions=E)`` -- every step reads the actions the step before selected
     (zeros before the first); a checkpoint then carries one more tensor, and one without it is refused by name; ``ValueError``
-    with ``depth=True`` or ``zeroshot=True``."""
+    with ``depth=True`` or ``zeroshot=True``.  ``rnn_type="LSTM"``: the agent of ``Worker(rnn_type="LSTM")`` -- the recurrent memory
+    is ``[N, 2 * hidden]`` rows ``[h | c]``; a checkpoint of the other cell is refused with the tensor's name and both shapes;
+    ``ValueError`` with ``depth=True`` or ``zeroshot=True``."""
 
     def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, encoder: str = "rn50",
                  encoder_sd=None, policy_sd=None, checkpoint: Optional[str] = None, deterministic: bool = False,
@@ -56,7 +58,8 @@ class Evaluator(_SlicedActor):
                  zeroshot: bool = False, sync_actions: bool = False, record: bool = False, env=None, text_sd=None,
                  goal_tokens=None, encoder_chunk: int = 0, record_capacity: int = 0, nav_metrics: bool = False,
                  num_categories: Optional[int] = None, env_seed: Optional[int] = None, depth: bool = False,
-                 prev_actions: int = 0, prev_action_null_token: bool = True):
+                 prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU"):
+        self.rnn_type = check_rnn_type(rnn_type, bool(depth), bool(zeroshot))
         if depth:       # the RGB-D agent (engine.Worker(depth=True)): the same refusals, before anything is built
             check_rgbd(encoder, zeroshot, goal_in, bool(env is not None and getattr(env, "host", False)))
             if env is not None and getattr(env, "depth", None) is None:
@@ -98,8 +101,8 @@ class Evaluator(_SlicedActor):
             if POLICY_PREV_ACTION_EMBEDDER not in policy_sd:
                 raise KeyError(f"{self._checkpoint}: the checkpoint lacks the tensor {POLICY_PREV_ACTION_EMBEDDER!r} of this agent")
         encs, pools = self._build_model(n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams)
-        self.h = torch.zeros((N, self.H), dtype=torch.float32, device=d)
-        self.h_next = torch.zeros((N, self.H), dtype=torch.float32, device=d)
+        self.h = torch.zeros((N, self.SW), dtype=torch.float32, device=d)
+        self.h_next = torch.zeros((N, self.SW), dtype=torch.float32, device=d)
         # one step's results (record=True: run() points these at the rows of the [chunks*T, ...] recordings instead)
         self._hv = torch.empty((1, N, self.A + 1), dtype=torch.float32, device=d)
         self._actions = torch.zeros((1, N), dtype=torch.int64, device=d)
@@ -280,6 +283,7 @@ def main(argv=None) -> int:
                     help="the agent conditions on its previous action through an E-wide embedding (0: off; AllenAct's default is 6, Habitat's 32)")
     ap.add_argument("--no-prev-action-null-token", action="store_true",
                     help="with --prev-actions: no null row for an episode's first step (action a is row a)")
+    ap.add_argument("--rnn-type", default="GRU", choices=("GRU", "LSTM"), help="the recurrent cell of the agent (and of its checkpoint)")
     ap.add_argument("--json", default=None, metavar="OUT", help="also write the info dict to this file")
     ap.add_argument("--env-seed", type=int, default=None, help="seed of the synthetic env (default 1000, what Evaluator builds itself)")
     ap.add_argument("--nav-metrics", action="store_true", help="also SPL, SoftSPL, distance to goal, and the scores per object type")
@@ -307,7 +311,7 @@ def main(argv=None) -> int:
     ev = Evaluator(a.actors, T=a.steps, seed=a.seed, env_seed=a.env_seed, encoder=a.encoder, checkpoint=a.checkpoint, deterministic=a.deterministic,
                    goal_in=a.goal_in, num_actions=a.num_actions, zeroshot=a.zeroshot, frames_u8=a.frames_u8,
                    sync_actions=a.sync_actions, nav_metrics=a.nav_metrics, depth=a.depth, prev_actions=a.prev_actions,
-                   prev_action_null_token=not a.no_prev_action_null_token,
+                   prev_action_null_token=not a.no_prev_action_null_token, rnn_type=a.rnn_type,
                    num_categories=len(names) if (names is not None and not a.goal_in) else None,
                    # every actor can end an episode at every step: the metrics file then misses none
                    record_capacity=a.chunks * a.steps * a.actors if a.metrics_json else 0)

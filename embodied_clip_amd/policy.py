@@ -39,8 +39,14 @@ from .allenact_compat import ActorCriticModel, ActorCriticOutput, CategoricalDis
 class PolicyHandle:
     """``ec_policy_t`` plus the flat-buffer layout."""
 
-    def __init__(self, **cfg: int):
+    def __init__(self, rnn_type: str = "GRU", **cfg: int):
+        """``rnn_type``: "GRU" (the default: ``ec_policy_create``'s handle exactly) or "LSTM" -- the recurrent state of an
+        actor is then one row ``[h | c]`` of width ``state_width == 2 * hidden``, which is what ``h0`` / ``h_final`` /
+        ``dh_final`` of every method below hold."""
         self.lib = _lib.load()
+        if rnn_type not in _lib.RNN_TYPES:
+            raise ValueError(f"rnn_type must be one of {sorted(_lib.RNN_TYPES)}, got {rnn_type!r}")
+        self.rnn_type = rnn_type
         self.cfg = dict(in_channels=2048, spatial=7, hidden=512, goal_dims=32, num_goals=12, num_actions=6,
                         compress_hid=128, compress_out=32, comb_hid=128, comb_out=32, fusion=0, dual=0, goal_in=0,
                         prev_action_dims=0, prev_action_null=0)
@@ -51,10 +57,11 @@ class PolicyHandle:
         self.param_order = policy_param_order(self.cfg["dual"], self.goal_in, self.prev_action_dims, self.cfg["prev_action_null"])
         c = _lib.PolicyCfg(**self.cfg)
         h = C.c_void_p()
-        _lib.check(self.lib.ec_policy_create(C.byref(h), C.byref(c)), "ec_policy_create")
+        _lib.check(self.lib.ec_policy_create_rnn(C.byref(h), C.byref(c), _lib.RNN_TYPES[rnn_type]), "ec_policy_create_rnn")
         self.h = h
         self.flat_size = self.lib.ec_policy_flat_size(h)
-        self.shapes = policy_param_shapes(**self.cfg)
+        self.state_width = self.lib.ec_policy_state_width(h)      # H, or 2H on an LSTM handle
+        self.shapes = policy_param_shapes(**self.cfg, rnn_type=rnn_type)
         self.offsets: "OrderedDict[str, Tuple[int, int]]" = OrderedDict()
         assert self.lib.ec_policy_num_param_tensors(h) == len(self.param_order)
         for i, name in enumerate(self.param_order):
@@ -98,6 +105,12 @@ class PolicyHandle:
             assert goal.dtype == torch.int64 and goal.numel() == rows, (goal.dtype, tuple(goal.shape))
         return goal.data_ptr()
 
+    def _state_ptr(self, t, N: int, what: str) -> int:
+        """A recurrent-state argument (``h0`` / ``h_final`` / ``dh_final``): f32 ``[N, state_width]``, contiguous."""
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N * self.state_width, \
+            (what, t.dtype, tuple(t.shape), (N, self.state_width))
+        return t.data_ptr()
+
     def _prev_ptr(self, prev_actions, rows: int) -> int:
         """The previous actions of the ``_pa`` entry points: int64 [rows] on a handle with the embedding, None without."""
         if not self.prev_action_dims:
@@ -122,7 +135,7 @@ class PolicyHandle:
 
     def forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv=None, h_final=None, for_backward: bool = True,
                 reuse_tables: bool = False, feat2=None, prev_actions=None):
-        """feat: bf16 or fp32 NHWC rows [T*N, S*S, C]; returns (hv [T*N, A+1], h_final [N,H]).
+        """feat: bf16 or fp32 NHWC rows [T*N, S*S, C]; returns (hv [T*N, A+1], h_final [N, state_width]).
         ``for_backward=True`` (default) keeps every activation ``backward`` needs and wants a workspace of
         ``workspace_bytes(T, N, True)``; ``False`` is the inference-only act step (``workspace_bytes(T, N, False)``).
         The kernel plan follows this flag, never the size of ``ws``.  ``reuse_tables`` (inference only): the weight-derived
@@ -151,8 +164,8 @@ class PolicyHandle:
         with _lib.tensor_guard(flat_params):
             _lib.check(getattr(self.lib, name)(
                 self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), self._goal_ptr(goal, N),
-                h0.data_ptr(), masks.data_ptr(), N, ws.data_ptr(), ws.numel() * ws.element_size(), int(reuse_tables),
-                hv.data_ptr(), h_final.data_ptr(), actions.data_ptr(), logp.data_ptr(), _lib.ptr(values), *key,
+                self._state_ptr(h0, N, "h0"), masks.data_ptr(), N, ws.data_ptr(), ws.numel() * ws.element_size(), int(reuse_tables),
+                hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(), logp.data_ptr(), _lib.ptr(values), *key,
                 _lib.stream_ptr()), name)
         return hv, h_final
 
@@ -172,8 +185,8 @@ class PolicyHandle:
         with _lib.tensor_guard(flat_params):
             _lib.check(fn(
                 self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16),
-                0 if self.goal_in else gp, gp if self.goal_in else 0, *((pp,) if pp else ()), h0.data_ptr(), masks.data_ptr(), N, ws.data_ptr(),
-                ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), h_final.data_ptr(), actions.data_ptr(),
+                0 if self.goal_in else gp, gp if self.goal_in else 0, *((pp,) if pp else ()), self._state_ptr(h0, N, "h0"), masks.data_ptr(), N,
+                ws.data_ptr(), ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
                 logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
                 expert_actions.data_ptr() if forcing else 0, expert_mask.data_ptr() if forcing else 0,
                 force_p if forcing else 0.0, _lib.stream_ptr()), name)
@@ -183,7 +196,9 @@ class PolicyHandle:
         if hv is None:
             hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)
         if h_final is None:
-            h_final = torch.empty((N, self.H), dtype=torch.float32, device=dev)
+            h_final = torch.empty((N, self.state_width), dtype=torch.float32, device=dev)
+        self._state_ptr(h0, N, "h0")
+        self._state_ptr(h_final, N, "h_final")
         if self.cfg["dual"]:       # RGB + depth: feat = the RGB features, feat2 = the depth features (same shape / dtype)
             assert feat2 is not None and feat2.is_contiguous() and feat2.dtype == feat.dtype and feat2.shape == feat.shape
         pp = self._prev_ptr(prev_actions, T * N)
@@ -211,6 +226,8 @@ class PolicyHandle:
     def _backward(self, flat_params, feat, masks, T, N, ws, dhv, dh_final, flat_grads, feat2=None, recurrent_ready=None):
         if self.cfg["dual"]:
             assert feat2 is not None and feat2.is_contiguous() and feat2.dtype == feat.dtype and feat2.shape == feat.shape
+        if dh_final is not None:
+            self._state_ptr(dh_final, N, "dh_final")
         ev = None
         if recurrent_ready is not None:
             ev = int(recurrent_ready.cuda_event)
@@ -296,8 +313,16 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
                  hidden_size: int = 512, goal_dims: int = 32, resnet_compressor_hidden_out_dims=(128, 32),
                  combiner_hidden_out_dims=(128, 32), state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  device="cuda", add_prev_actions: bool = False, action_embed_size: int = 6,
-                 add_prev_action_null_token: bool = False):
+                 add_prev_action_null_token: bool = False, rnn_type: str = "GRU", num_rnn_layers: int = 1):
         super().__init__(action_space=action_space, observation_space=observation_space)
+        # [U] RNNStateEncoder(input, hidden, num_layers=num_rnn_layers, rnn_type=rnn_type)
+        if num_rnn_layers != 1:
+            raise NotImplementedError("more than one recurrent layer is not built")
+        if rnn_type not in ("GRU", "LSTM"):
+            raise ValueError(f"rnn_type must be 'GRU' or 'LSTM', got {rnn_type!r}")
+        if rnn_type == "LSTM" and depth_resnet_preprocessor_uuid is not None:
+            raise NotImplementedError("an LSTM core with a depth tower is not built (the two-tower agent keeps the GRU)")
+        self.rnn_type = rnn_type
         if rgb_resnet_preprocessor_uuid is None and depth_resnet_preprocessor_uuid is None:
             raise ValueError("one of rgb_resnet_preprocessor_uuid / depth_resnet_preprocessor_uuid is required")
         self.goal_uuid = goal_sensor_uuid
@@ -332,11 +357,11 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
                                    compress_hid=resnet_compressor_hidden_out_dims[0],
                                    compress_out=resnet_compressor_hidden_out_dims[1],
                                    comb_hid=combiner_hidden_out_dims[0], comb_out=combiner_hidden_out_dims[1],
-                                   dual=int(self.dual), **goal_kw)
+                                   dual=int(self.dual), rnn_type=rnn_type, **goal_kw)
         dev = torch.device(device)
         if state_dict is None:
             from .synthetic import policy_state_dict
-            state_dict = policy_state_dict(0, **self.handle.cfg)
+            state_dict = policy_state_dict(0, **self.handle.cfg, rnn_type=rnn_type)
         self._flat = self.handle.flatten(state_dict, dev)
         self._flat_grad = torch.zeros_like(self._flat)
         for name, v in self.handle.views(self._flat).items():
@@ -448,7 +473,20 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
 
     @property
     def num_recurrent_layers(self) -> int:
-        return 1
+        """[U] RNNStateEncoder.num_recurrent_layers: ``num_layers * (2 if "LSTM" in rnn_type else 1)``."""
+        return 2 if self.rnn_type == "LSTM" else 1
+
+    @staticmethod
+    def memory_to_state(mem: torch.Tensor) -> torch.Tensor:
+        """Upstream's memory tensor ``[L, N, H]`` (L = 2 on an LSTM: h then c) -> the handle's state rows ``[N, L * H]``."""
+        L, N, H = mem.shape
+        return mem.permute(1, 0, 2).reshape(N, L * H).contiguous()
+
+    @staticmethod
+    def state_to_memory(state: torch.Tensor, L: int) -> torch.Tensor:
+        """The handle's state rows ``[N, L * H]`` -> upstream's memory tensor ``[L, N, H]``."""
+        N = state.shape[0]
+        return state.view(N, L, -1).permute(1, 0, 2).contiguous()
 
     @property
     def is_blind(self) -> bool:
@@ -463,7 +501,7 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
                 masks: torch.Tensor):
         """observations[resnet_uuid]: [T,N,C,S,S] fp32 (or bf16/fp32 channels-last [T,N,S,S,C] from
         ``ClipResNetPreprocessor.process_bf16_nhwc``); observations[goal_uuid]: [T,N] int (PointNav: [T,N,goal_in] float);
-        memory 'rnn': [1,N,H]; masks: [T,N,1]; prev_actions: [T,N] or [T,N,1] integer, read only with ``add_prev_actions``.
+        memory 'rnn': [1,N,H] ([2,N,H] on an LSTM: h then c, converted to the handle's [N,2H] rows here only); masks: [T,N,1]; prev_actions: [T,N] or [T,N,1] integer, read only with ``add_prev_actions``.
         -> (ActorCriticOutput, Memory)."""
         self.ensure_flat()
         goal = observations[self.goal_uuid]
@@ -490,7 +528,8 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
             goal = goal.reshape(T * N, self.handle.goal_in).to(torch.float32).contiguous()
         else:
             goal = goal.reshape(T * N).to(torch.int64).contiguous()
-        h0 = memory.tensor("rnn").reshape(N, self._hidden_size).to(torch.float32).contiguous()
+        L = self.num_recurrent_layers
+        h0 = self.memory_to_state(memory.tensor("rnn").reshape(L, N, self._hidden_size).to(torch.float32))
         m = masks.reshape(T * N).to(torch.float32).contiguous()
         prev = None
         if self.add_prev_actions:
@@ -506,7 +545,7 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
         A = self.handle.A
         hv = hv.view(T, N, A + 1)
         out = ActorCriticOutput(distributions=CategoricalDistr(logits=hv[..., :A]), values=hv[..., A:], extras={})
-        return out, memory.set_tensor("rnn", h_final.view(1, N, self._hidden_size))
+        return out, memory.set_tensor("rnn", self.state_to_memory(h_final, L))
 
 
 class ResnetTensorObjectNavActorCritic(_ResnetTensorGoalActorCritic):

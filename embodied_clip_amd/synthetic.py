@@ -350,6 +350,10 @@ POLICY_PARAM_ORDER_POINTNAV: Tuple[str, ...] = (
 POLICY_PREV_ACTION_EMBEDDER = "prev_action_embedder.fc.weight"
 
 
+POLICY_RNN_TENSORS = ("state_encoder.rnn.weight_ih_l0", "state_encoder.rnn.weight_hh_l0", "state_encoder.rnn.bias_ih_l0",
+                      "state_encoder.rnn.bias_hh_l0")
+
+
 def policy_param_order(dual: int = 0, goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0) -> Tuple[str, ...]:
     if prev_action_dims:
         assert not dual, "previous actions with the RGB-D encoder are not built"
@@ -363,12 +367,22 @@ def policy_param_order(dual: int = 0, goal_in: int = 0, prev_action_dims: int = 
 def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int = 512, goal_dims: int = 32,
                         num_goals: int = 12, num_actions: int = 6, compress_hid: int = 128,
                         compress_out: int = 32, comb_hid: int = 128, comb_out: int = 32, fusion: int = 0, dual: int = 0,
-                        goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0):
-    """``fusion=1`` (zero-shot dual-encoder policy): the goal-embedding / compressor / combiner tensors have zero
+                        goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0, rnn_type: str = "GRU"):
+    """``rnn_type="LSTM"`` (single tower only): the same names in the same order, the four ``state_encoder.rnn.*`` tensors with
+    ``4 * hidden`` rows (gate order i, f, g, o).  ``fusion=1`` (zero-shot dual-encoder policy): the goal-embedding / compressor / combiner tensors have zero
     elements and the GRU reads the ``in_channels``-wide fused embedding.  ``dual=1``: RGB + depth streams (25 tensors,
     GRU input 2 * comb_out * spatial^2).  ``goal_in > 0`` (PointNav): 18 tensors, ``embed_goal.{weight,bias}`` in place
     of ``embed_class.weight``; ``num_goals`` is ignored.  ``prev_action_dims = E > 0``: ``weight_ih_l0`` is ``[3 * hidden,
     flat + E]`` and ``prev_action_embedder.fc.weight`` ``[num_actions + prev_action_null, E]`` is the last tensor."""
+    if rnn_type != "GRU":
+        assert rnn_type == "LSTM", rnn_type
+        assert not fusion and not dual, "the two-tower and zero-shot agents keep the GRU"
+        out = policy_param_shapes(in_channels, spatial, hidden, goal_dims, num_goals, num_actions, compress_hid, compress_out,
+                                  comb_hid, comb_out, goal_in=goal_in, prev_action_dims=prev_action_dims,
+                                  prev_action_null=prev_action_null)
+        for k in POLICY_RNN_TENSORS:
+            out[k] = (4 * hidden,) + tuple(out[k][1:])
+        return out
     if prev_action_dims:
         assert not fusion and not dual and 1 <= prev_action_dims <= 64 and prev_action_null in (0, 1)
         out = policy_param_shapes(in_channels, spatial, hidden, goal_dims, num_goals, num_actions, compress_hid, compress_out,
@@ -430,11 +444,13 @@ def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int =
 
 def policy_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, torch.Tensor]":
     """Synthetic policy parameters; RoboTHOR default = 3,480,775 params (PointNav, ``goal_in=2, num_actions=4``:
-    3,479,461; ``embed_goal.weight`` ~ N(0, 1/goal_in), the generic fan-in rule below)."""
+    3,479,461; ``embed_goal.weight`` ~ N(0, 1/goal_in), the generic fan-in rule below).  ``rnn_type="LSTM"``: the recurrent
+    weights by the same rule, both recurrent biases zero ([U] RNNStateEncoder.init_weights: ``nn.init.constant_(param, 0)``)."""
     shapes = policy_param_shapes(**kw)
+    lstm = kw.get("rnn_type", "GRU") == "LSTM"
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     for k, shp in shapes.items():
-        if int(np.prod(shp)) == 0:
+        if int(np.prod(shp)) == 0 or (lstm and k in POLICY_RNN_TENSORS[2:]):
             sd[k] = torch.zeros(shp)
         elif k.endswith("bias") or "bias_" in k:
             sd[k] = _normal(seed, k, shp, 0.02)

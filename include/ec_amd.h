@@ -441,6 +441,24 @@ typedef struct {
 typedef struct ec_policy ec_policy_t;
 
 int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg);
+/* The recurrent cell ([U] allenact RNNStateEncoder(input, hidden, num_layers=1, rnn_type="GRU" | "LSTM"); the Habitat DD-PPO
+ * policies of readme_files/baselines_habitat.md:63-73 are LSTM policies).  ec_policy_create(out, cfg) ==
+ * ec_policy_create_rnn(out, cfg, EC_RNN_GRU): that handle is today's, bit for bit.  EC_RNN_LSTM: torch.nn.LSTM's cell under the
+ * episode mask, which resets BOTH states (restated from the published sources, parity unpinned):
+ *   hp = m*h_prev; cp = m*c_prev;  a = W_ih x + b_ih + W_hh hp + b_hh  (gate order i, f, g, o: rows 0..H-1, H..2H-1, ...)
+ *   i = s(a_i); f = s(a_f); g = tanh(a_g); o = s(a_o);  c = f*cp + i*g;  h = o*tanh(c)
+ * The same tensor names in the same order; rnn.weight_ih_l0 is [4H, flat (+E)], weight_hh_l0 [4H, H], both biases [4H].
+ * The recurrent state of an actor is ONE row [h | c] of width 2H (ec_policy_state_width): on an LSTM handle every h0, h_final
+ * and dh_final of the entry points below is f32 [N, 2H] where the comments say [N,H], and ec_policy_workspace_bytes grows by
+ * the cell-state history and the fourth gate.  Every entry point keeps its signature.  No float atomics on any route of an
+ * LSTM handle: two learn passes give equal bits, and an actor's result does not depend on how the actors are sliced.
+ * EC_ERR_ARG for any other rnn_type; EC_ERR_UNSUPPORTED for EC_RNN_LSTM with dual = 1 or fusion = 1 (the two-tower and the
+ * zero-shot agents keep the GRU); EC_ERR_SHAPE unless hidden % 32 == 0 (and hidden % 256 == 0 or hidden <= 608: the forward
+ * step's two operand tiles sit in LDS). */
+enum { EC_RNN_GRU = 0, EC_RNN_LSTM = 1 };
+int ec_policy_create_rnn(ec_policy_t** out, const ec_policy_cfg* cfg, int rnn_type);
+int ec_policy_rnn_type(const ec_policy_t* h);          /* EC_RNN_GRU | EC_RNN_LSTM (-1: NULL handle) */
+int ec_policy_state_width(const ec_policy_t* h);       /* H (GRU) or 2H (LSTM): the width of a row of h0 / h_final / dh_final */
 /* fusion == 1 only: borrow the device goal table f32 [num_goals, in_channels] (e.g. ec_text_forward over the goal
  * prompts, L2-normalised); frozen -- it receives no gradient. */
 int ec_policy_set_goal_table(ec_policy_t* h, const float* table);
@@ -449,9 +467,9 @@ int ec_policy_num_param_tensors(const ec_policy_t* h);
 size_t ec_policy_flat_size(const ec_policy_t* h);                      /* floats, incl. alignment padding */
 int ec_policy_param_offset(const ec_policy_t* h, int idx, size_t* off, size_t* numel);
 size_t ec_policy_workspace_bytes(const ec_policy_t* h, int T, int N, int for_backward);
-/* feat [T*N, S*S, C] NHWC (bf16 if feat_bf16 else f32); goal int64 [T*N]; h0 f32 [N,H];
- * masks f32 [T*N] (h is multiplied by masks[t] before step t: episode reset);
- * hv f32 [T*N, A+1] out: logits in cols 0..A-1, value in col A; h_final f32 [N,H] or NULL.
+/* feat [T*N, S*S, C] NHWC (bf16 if feat_bf16 else f32); goal int64 [T*N]; h0 f32 [N,H] (LSTM handle: [N,2H] rows [h | c]);
+ * masks f32 [T*N] (h -- on an LSTM handle h and c -- is multiplied by masks[t] before step t: episode reset);
+ * hv f32 [T*N, A+1] out: logits in cols 0..A-1, value in col A; h_final f32 [N,H] (LSTM handle: [N,2H]) or NULL.
  * for_backward (the kernel plan depends on this flag alone, never on the size of the buffer handed in):
  *   EC_POLICY_LEARN (1)        the workspace (ec_policy_workspace_bytes(.., 1)) keeps every activation ec_policy_backward needs;
  *                              with more than 7 actions also both heads as one packed [A + 1, H] table and its gradient (one GEMM
@@ -470,7 +488,8 @@ int ec_policy_forward2(const ec_policy_t* h, const float* params, const void* fe
                        void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream);
 /* The act step in ONE call ([U] allenact OnPolicyRLEngine.act: `actor_critic(...)`, then `distributions.sample()` and
  * `log_probs(actions)`): ec_policy_forward2 with T = 1 and EC_POLICY_INFER (reuse_tables = 0) / EC_POLICY_INFER_REUSE (1), whose
- * heads launch also samples -- actions int64 [N], logp f32 [N], values f32 [N] or NULL, keyed as in ec_sample_actions.  Bit-for-bit
+ * heads launch also samples -- actions int64 [N], logp f32 [N], values f32 [N] or NULL, keyed as in ec_sample_actions (h0, h_final:
+ * [N,H], on an LSTM handle [N,2H] -- there the step kernel stores h for the heads and the [h | c] row: as many launches).  Bit-for-bit
  * the results of ec_policy_forward2 followed by ec_sample_actions; one launch less on the act step's serial chain.
  * EC_ERR_UNSUPPORTED for more than 7 actions (use the two calls). */
 int ec_policy_act(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
@@ -505,7 +524,7 @@ int ec_policy_act_vec_greedy(const ec_policy_t* h, const float* params, const vo
                              const float* goal_vec, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                              int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                              ec_stream_t stream);
-/* dhv f32 [T*N, A+1] = dLoss/dhv; dh_final [N,H] or NULL; grads += dLoss/dparams.
+/* dhv f32 [T*N, A+1] = dLoss/dhv; dh_final [N,H] (LSTM handle: [N,2H] rows [dL/dh | dL/dc]) or NULL; grads += dLoss/dparams.
  * `workspace` must be the one the matching ec_policy_forward filled (for_backward size). */
 int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,
                        const float* masks, int T, int N, void* workspace, size_t ws_bytes, const float* dhv,
@@ -521,6 +540,26 @@ int ec_policy_backward2(const ec_policy_t* h, const float* params, const void* f
 int ec_policy_backward3(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                         const float* masks, int T, int N, void* workspace, size_t ws_bytes, const float* dhv,
                         const float* dh_final, float* grads, ec_event_t recurrent_grads_ready, ec_stream_t stream);
+
+/* The LSTM step alone (lstm.hip; what the two recurrences of an LSTM handle launch per time step).
+ * ec_lstm_step_fwd: a_in f32 [N,4H] = W_ih x + b_ih; whh [4H,H]; bhh [4H]; mask [N]; state_prev with row pitch ld_prev floats:
+ *   ld_prev >= 2H -- rows [h | c] (h of actor n at state_prev + n*ld_prev, c at + H); ld_prev == H -- two dense blocks [2,N,H]
+ *   (h first).  h_out / c_out: rows of pitch ld_h / ld_c >= H, not overlapping state_prev.  gates f32 [N,4H] out (i, f, g, o after
+ *   their activations) or NULL.  Rows past N are never written.  H % 32 == 0 (and H % 256 == 0 or H <= 608), else EC_ERR_SHAPE;
+ *   ld_prev a multiple of 4 and a_in, whh, state_prev 16-byte aligned.
+ * ec_lstm_step_bwd: ONE reverse step.  dhs [N,H] = dL/dh_t from the heads; gates [N,4H], c [N,H] = c_t, c_prev [N,H] = m_t*c_{t-1}
+ *   as the forward left them; mask [N] = m_t; da f32 [N,4H] out (gradient wrt a_t, gate order i, f, g, o); carry_c [N,H] in/out:
+ *   dL/dc_t from step t+1 in, m_t*dc*f out.
+ *   whhT == NULL (gate kernel + ec_gemm_f32, split-K 1): dh = dhs + carry_h; carry_h [N,H] in/out becomes m_t*(da whh).
+ *   whhT != NULL (the fused step; H % 256 == 0, else EC_ERR_SHAPE): whhT f32 [H,4H] = whh transposed; dh = dhs +
+ *     mask_next * (da_next whh) with da_next [N,4H], mask_next [N] of step t+1; carry_h and whh are not used (may be NULL).
+ *   No float atomics on either route. */
+int ec_lstm_step_fwd(const float* a_in, const float* whh, const float* bhh, const float* state_prev, long ld_prev,
+                     const float* mask, float* h_out, long ld_h, float* c_out, long ld_c, float* gates, int N, int H,
+                     ec_stream_t stream);
+int ec_lstm_step_bwd(const float* dhs, const float* gates, const float* c, const float* c_prev, const float* mask,
+                     const float* whh, const float* whhT, const float* da_next, const float* mask_next, float* carry_h,
+                     float* carry_c, float* da, int N, int H, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Rollout post-processing and the PPO update ([U] allenact onpolicy_sync:
