@@ -2307,7 +2307,8 @@ struct Bwd : Ctx {
             return gemm(ws + w.dgi, g.E ? ws + w.wihP : W(P_WIH), ws + w.dx, B, flat, GW, GW, 1, flat, 1, flat, p.bwd3);   // (E: the forward's dense copy)
         // The weight is transposed first (9.6 MB, into the gradient staging buffer, free again by now) so that BOTH operands are
         // K-contiguous: the GEMM's strided-B staging runs at half the rate (263 vs ~130 us at 32 actors, 770 vs ~540 at 128)
-        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((flat + 31) / 32), (unsigned)(GW / 32)), dim3(256), 0, s,
+        // (both grid dimensions rounded up: 3H is no multiple of 32 where H is none, the gate + GEMM route; the kernel guards the edges)
+        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((flat + 31) / 32), (unsigned)((GW + 31) / 32)), dim3(256), 0, s,
                            ws + w.wihP, ws + w.gwihP, GW, flat);
         return gemm(ws + w.dgi, ws + w.gwihP, ws + w.dx4, B, flat, GW, GW, 1, 1, GW, flat, p.bwd3);
     }

@@ -8,6 +8,7 @@ import importlib.util
 import json
 import os
 import shutil
+import sys
 
 import pytest
 
@@ -21,21 +22,12 @@ cases = g.cases
 CXX = os.environ.get("CXX", "c++")
 pytestmark = pytest.mark.skipif(shutil.which(CXX) is None, reason="host C++ compiler not found")
 
-# Every kernel csrc/policy.hip defines is in exactly one of these lists; an instance the library registers outside them fails
-# test_every_forward_instance_is_reached, so a new forward kernel cannot arrive without a case.
-FORWARD = ["c1_act_kernel<1, 8>", "c1_act_kernel<2, 4>", "c1_act_kernel<4, 4>", "frag_pack_f32_kernel", "frag_pack_planes_kernel",
-           "gi_act_kernel<7>", "gi_act_kernel<8>", "goal_to_i32_kernel", "goal_vec_fwd_kernel", "gru_gates_fwd_kernel",
-           "gru_step_fwd_kernel", "heads_fwd_kernel<8>", "permute_row_kernel", "tail_fwd_kernel<false>", "tail_fwd_kernel<true>",
-           "to_cmajor_kernel"]
-FORWARD_ELSEWHERE = {   # forward kernels no inference case of the table can reach -> what runs them
-    "gru_step_fwd512_kernel": "the learn pass at H = 512 (Step::fused16 needs !infer): tests/test_gpu_policy.py",
-    "fuse_goal_kernel<false>": "fusion = 1, the zero-shot policy (no compressor, no combiner): tests/test_gpu_zeroshot.py",
-    "fuse_goal_kernel<true>": "fusion = 1 with bf16 embeddings: tests/test_gpu_zeroshot.py",
-}
-BACKWARD = ["colsum4_kernel", "colsum_fold_kernel", "colsum_kernel", "frame_sum_kernel", "from_cmajor_kernel", "goal_vec_bwd_kernel",
-            "group_sum_scatter_kernel", "gru_gates_bwd_kernel", "gru_step_bwd512_kernel", "gru_step_bwd_kernel", "seg_fold_kernel",
-            "splitk_fold_kernel", "tail_bwd_fold_kernel", "tail_bwd_kernel<false>", "tail_bwd_kernel<true>", "tail_bwd_reduce_kernel",
-            "tn_small_part_kernel", "transpose_f32_kernel"]
+# Every kernel csrc/policy.hip defines is in exactly one of these lists (tests/_policy_kernel_lists.py, shared with
+# tests/test_learn_routes.py); an instance the library registers outside them fails test_every_forward_instance_is_reached, so
+# a new forward kernel cannot arrive without a case.
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _policy_kernel_lists import BACKWARD, FORWARD, FORWARD_ELSEWHERE  # noqa: E402
+
 TABLE_BUILDERS = ("split3_planes_kernel", "frag_pack_planes_kernel", "frag_pack_f32_kernel", "permute_row_kernel")
 
 

@@ -23,13 +23,16 @@
 //                                                   Bottleneck / BasicBlock tower; the torchvision towers have width 64) through
 //                                                   ec_rn50_forward / _u8 / _depth; `P <ec_rn50_num_ops> <ec_rn50_plan_hash>`
 //                                                   comes before its launches
-//   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse
+//   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse [dhf]
 //                                                   create + ec_policy_workspace_bytes + ec_policy_forward2 (goal_in > 0:
 //                                                   ec_policy_forward_vec) + destroy; mode 0 = EC_POLICY_INFER, 1 = _LEARN;
 //                                                   reuse 1: an EC_POLICY_INFER call builds the tables first (`B <rc>` ends
 //                                                   its launches), then the recorded call is EC_POLICY_INFER_REUSE in the
-//                                                   same workspace.  `W <bytes>` is the workspace size, `D <bytes>` a
-//                                                   device-to-device hipMemcpyAsync (policy commands only)
+//                                                   same workspace.  mode 2: the learn pass -- the EC_POLICY_LEARN forward
+//                                                   (`F <rc>` ends its launches), then ec_policy_backward2 in the same
+//                                                   workspace; dhf 1 (mode 2 only): with a dh_final tensor, else NULL.
+//                                                   `W <bytes>` is the workspace size, `D <bytes>` a device-to-device
+//                                                   hipMemcpyAsync (policy commands only)
 // Output: `K <kernel>` per registered kernel, then per command `C <command>`, one `L <kernel>|<grid>|<block>|<lds>` per
 // launch (with --args N: `|` + the first N bytes of the first kernel argument in hex, for the conv_igemm kernels) and `R <rc>`.
 #include <cxxabi.h>
@@ -196,17 +199,18 @@ static int run_tower(const std::string& kind, const int* v, const std::string& i
     return rc;
 }
 
-// v: the 13 ec_policy_cfg fields, then T, N, mode, bf16, reuse
+// v: the 13 ec_policy_cfg fields, then T, N, mode, bf16, reuse, dhf
 static int run_policy(const int* v) {
     typedef void* P;
-    const int T = v[13], N = v[14], mode = v[15], bf16 = v[16], reuse = v[17], goal_in = v[12], dual = v[11];
-    if (mode < 0 || mode > 1 || (reuse && mode != 0)) return -100;
+    const int T = v[13], N = v[14], mode = v[15], bf16 = v[16], reuse = v[17], dhf = v[18], goal_in = v[12], dual = v[11];
+    const bool learn_pass = mode == 2;
+    if (mode < 0 || mode > 2 || (reuse && mode != 0) || (dhf && !learn_pass)) return -100;
     void* h = nullptr;
     int cfg[32] = {0};                                  // the 13 fields, zero-filled behind them (fields a later header adds read 0)
     memcpy(cfg, v, 13 * sizeof(int));
     int rc = sym<int (*)(P*, const int*)>("ec_policy_create")(&h, cfg);
     if (rc) return rc;
-    const size_t ws = sym<size_t (*)(P, int, int, int)>("ec_policy_workspace_bytes")(h, T, N, mode);
+    const size_t ws = sym<size_t (*)(P, int, int, int)>("ec_policy_workspace_bytes")(h, T, N, mode != 0);
     printf("W %zu\n", ws);
     const P params = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4), feat = fake(1u << 30), feat2 = dual ? fake(1u << 30) : nullptr;
     const P goal = fake(1u << 20), h0 = fake(1u << 24), masks = fake(1u << 20), wsp = fake(ws), hv = fake(1u << 20), hf = fake(1u << 24);
@@ -216,7 +220,14 @@ static int run_policy(const int* v) {
         rc = fwd(h, params, feat, feat2, bf16, goal, h0, masks, T, N, wsp, ws, 0 /* EC_POLICY_INFER */, hv, hf, nullptr);
         printf("B %d\n", rc);
     }
-    if (!rc) rc = fwd(h, params, feat, feat2, bf16, goal, h0, masks, T, N, wsp, ws, reuse ? 2 /* EC_POLICY_INFER_REUSE */ : mode, hv, hf, nullptr);
+    if (!rc) rc = fwd(h, params, feat, feat2, bf16, goal, h0, masks, T, N, wsp, ws, reuse ? 2 /* EC_POLICY_INFER_REUSE */ : mode != 0, hv, hf, nullptr);
+    if (learn_pass) {
+        printf("F %d\n", rc);
+        const P dhv = fake(1u << 20), dhfin = dhf ? fake(1u << 24) : nullptr, grads = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4);
+        if (!rc)
+            rc = sym<int (*)(P, P, P, P, int, P, int, int, P, size_t, P, P, P, P)>("ec_policy_backward2")(h, params, feat, feat2, bf16, masks, T, N, wsp,
+                                                                                                        ws, dhv, dhfin, grads, nullptr);
+    }
     g_log_copies = 0;
     sym<void (*)(P)>("ec_policy_destroy")(h);
     return rc;
@@ -241,15 +252,15 @@ int main(int argc, char** argv) {
         if (!(ss >> cmd)) continue;
         line[strcspn(line, "\n")] = 0;
         printf("C %s\n", line);
-        int v[18] = {0}, n = 0, rc = -100;
+        int v[19] = {0}, n = 0, rc = -100;
         std::string kind;
         if (cmd == "trunk" || cmd == "tower") ss >> kind;
-        const int nmax = cmd == "policy" ? 18 : cmd == "tower" ? 9 : 10;
+        const int nmax = cmd == "policy" ? 19 : cmd == "tower" ? 9 : 10;
         while (n < nmax && ss >> v[n]) ++n;
         std::string input;
         if (cmd == "tower" && n == 9 && ss >> input) {
             rc = run_tower(kind, v, input);
-        } else if (cmd == "policy" && n == 18) {
+        } else if (cmd == "policy" && (n == 18 || n == 19)) {
             rc = run_policy(v);
         } else if (cmd == "conv" && n == 10) {
             const P r = v[8] ? resb : nullptr;
