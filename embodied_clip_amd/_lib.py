@@ -171,6 +171,10 @@ SIGNATURES = {
     # the recurrent cell: handles with an LSTM core (state rows [h | c] of width 2H), and the LSTM step kernels alone
     "ec_policy_create_rnn": (c_int, [C.POINTER(c_void_p), c_void_p, c_int]),
     "ec_policy_rnn_type": (c_int, [c_void_p]),
+    "ec_policy_create_rnn_layers": (c_int, [C.POINTER(c_void_p), c_void_p, c_int, c_int]),
+    "ec_policy_rnn_layers": (c_int, [c_void_p]),
+    "ec_rnn_stack_step_fwd": (c_int, [c_int, c_void_p, C.c_long] + [c_void_p] * 5 + [C.c_long, c_void_p, c_void_p, C.c_long, c_void_p, C.c_long,
+                                      c_void_p, C.c_long, c_int, c_int, c_void_p]),
     "ec_policy_state_width": (c_int, [c_void_p]),
     "ec_lstm_step_fwd": (c_int, [c_void_p] * 4 + [C.c_long, c_void_p, c_void_p, C.c_long, c_void_p, C.c_long, c_void_p, c_int, c_int,
                                  c_void_p]),

@@ -51,6 +51,7 @@ EcConfig read_config() {
     c.dw1_tr = env_int("EC_DW1_TR", 1);
     c.wih_perm = env_int("EC_WIH_PERM", 1);
     c.dw_transposed = env_int("EC_DW_TRANSPOSED", 1);
+    c.rnn_stack = env_int("EC_RNN_STACK", 1);
     c.vit_wide = env_int("EC_VIT_WIDE", 1);
     c.vit_bm192 = env_int("EC_VIT_BM192", 1);
     return c;

@@ -231,6 +231,8 @@ struct EcConfig {
     int dw1_tr;           // EC_DW1_TR        (1)   dW1 on the transpose-read kernel
     int wih_perm;         // EC_WIH_PERM      (1)   learn pass: re-ordered weight_ih instead of activation transposes
     int dw_transposed;    // EC_DW_TRANSPOSED (1)   GRU weight-gradient GEMMs on transposed (K-contiguous) operands
+    int rnn_stack;        // EC_RNN_STACK     (1)   act step of a multi-layer recurrent core: one launch per upper layer (rnn_stack.hip); 0: the general
+                          //                        layer-by-layer route.  NOT part of ec_config_hash(): no single-layer plan reads it
     // --- ViT / text GEMMs (ec_gemm_bf16_ln8).  NOT part of ec_config_hash(): the profile summaries under profiles/ are keyed by the hash as it was ---
     int vit_wide;         // EC_VIT_WIDE      (1)   0: 128-wide tiles only, 2: 256-wide wherever N allows
     int vit_bm192;        // EC_VIT_BM192     (1)   0: no 192-row tiles
@@ -363,7 +365,22 @@ void ec_lstm_bwd_fused_launch(const float* da_next, const float* whhT, const flo
                               hipStream_t s);
 void ec_lstm_state_rows_launch(float* state, float* hpart, float* cpart, int N, int H, int split, hipStream_t s);
 
-#define EC_CHECK_LAUNCH()                                   \
+// rnn_stack.hip: one launch for an upper layer's act step -- input projection, recurrent projection and cell (argument meanings:
+// the kernel's header).  gi != null: no x half, the projection as given (layer 0 of a GRU stack, states at a row pitch).
+struct ec_rnn_stack_args {
+    const float *x; long ld_x;
+    const float *wih, *whh, *bih, *bhh;
+    const float *hprev, *cprev; long ld_prev;
+    const float* mask;
+    float* hout; long ld_h;
+    float* cout; long ld_c;
+    float* hout2; long ld_h2;
+    const float* gi; int gi_parts; long gi_pstride;
+    int N, H;
+};
+void ec_rnn_stack_launch(int lstm, const ec_rnn_stack_args& a, hipStream_t s);
+
+#define EC_CHECK_LAUNCH()                                  \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \
         if (e__ != hipSuccess) return EC_ERR_LAUNCH;        \

@@ -1503,6 +1503,10 @@ struct ec_policy {
     int order[P_COUNT], ntensors;        // the flat buffer's tensor order (what ec_policy_param_offset's idx counts)
     const float* goal_table = nullptr;   // fusion == 1: borrowed f32 [num_goals, in_channels]
     int rnn = EC_RNN_GRU;                // the recurrent cell (ec_policy_create_rnn)
+    // recurrent layers (ec_policy_create_rnn_layers).  Layer l >= 1 owns weight_ih_l{l} [G, H], weight_hh_l{l} [G, H], bias_ih_l{l},
+    // bias_hh_l{l}: uoff / unum [l - 1][0..3], behind every other tensor of the flat order (indices nbase, nbase + 1, ...)
+    int layers = 1, nbase = 0;
+    size_t uoff[EC_RNN_MAX_LAYERS - 1][4] = {}, unum[EC_RNN_MAX_LAYERS - 1][4] = {};
     // EC_POLICY_INFER_REUSE bookkeeping: the key of the launch plan (make_plan) that built the weight-derived tables in a given
     // act workspace.  Which tables exist and where (E1, W1's planes in fragment order, the re-ordered weight_ih and its
     // fragment-order copy) are plan fields, and an inference plan is a function of exactly (handle, T, N, feature dtype): a
@@ -1639,6 +1643,7 @@ struct Geo {
     int nstream, flat1, flat;     // encoder streams (2: dual RGB + depth); one stream's / the whole GRU input width
     int E, R, ldw;                // previous-action embedding: width (0: none), table rows, weight_ih's row stride flat + E
     int G, SW;                    // gate width 3H (GRU) | 4H (LSTM); state width H | 2H (an LSTM state row is [h | c])
+    int L;                        // recurrent layers; a state row is [N, L * SW], layer l's state the slice at l * SW
 };
 
 struct Ws {   // float offsets into the workspace
@@ -1660,6 +1665,11 @@ struct Ws {   // float offsets into the workspace
     // LSTM handles (all empty on a GRU handle): the cell-state history [B, H]; the backward's dL/dc carry [N, H].  On such a handle
     // `hn` holds the masked previous cell states, `dgi` the one gate gradient da, and `dghb` is empty.
     size_t cs, dcc;
+    // layers l >= 1 of a multi-layer core (all empty with one layer), index l - 1: the layer's input projection gi [B, G], what its
+    // step kernels keep (gates [B, G]; hn, hp [B, H]), its state history hs [B, H] (the top layer's feeds the heads) and, on an
+    // LSTM handle, its cell-state history; uh0: a GRU stack's initial states as dense [L][N, H] blocks (its step kernels take no pitch)
+    size_t ugi[EC_RNN_MAX_LAYERS - 1], ugates[EC_RNN_MAX_LAYERS - 1], uhn[EC_RNN_MAX_LAYERS - 1], uhp[EC_RNN_MAX_LAYERS - 1],
+           uhs[EC_RNN_MAX_LAYERS - 1], ucs[EC_RNN_MAX_LAYERS - 1], uh0;
 };
 constexpr int GP_MAXY = 64;                   // row blocks of tn_small_part_kernel
 constexpr int HP_MAXY = 128;                  // row blocks of the wide heads' column sum
@@ -1687,6 +1697,7 @@ struct Plan {
     Gi gi; int gi_fold;           // partial matrices of gi the step kernel folds
     Step step_fwd, step_bwd; size_t gru_lds;   // (gru_step_fwd_kernel's tiles)
     bool hs_direct;               // T == 1 inference: the new state goes straight to h_final, the heads read it there
+    bool stack;                   // EC_RNN_STACK: act step of a multi-layer core, one launch per layer (rnn_stack.hip)
     bool dw_t, dw1_planes;        // EC_DW_TRANSPOSED; EC_DW1_TR (dc1 then only exists as bf16 planes)
     int bwd3;                     // EC_GEMM_3PRODUCTS or 0 for the backward's large gradient GEMMs
     Ws w;
@@ -1748,6 +1759,13 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, Cell cell, int parts, bool bwd) 
     w.pas = take_if(pa && bwd, pa ? ec_pa_grad_scratch_floats((long)B, g.G, g.R) : 0);
     w.cs = take_if(lstm, B * H);
     w.dcc = take_if(lstm && bwd, N * H);
+    for (int l = 1; l < EC_RNN_MAX_LAYERS; ++l) {
+        const bool on = l < g.L;
+        w.ugi[l - 1] = take_if(on, B * G); w.ugates[l - 1] = take_if(on, B * G);
+        w.uhn[l - 1] = take_if(on, B * H); w.uhp[l - 1] = take_if(on, B * H); w.uhs[l - 1] = take_if(on, B * H);
+        w.ucs[l - 1] = take_if(on && lstm, B * H);
+    }
+    w.uh0 = take_if(g.L > 1 && !lstm, (size_t)g.L * N * H);
     w.end = o;
     return w;
 }
@@ -1766,10 +1784,11 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     g.E = c.prev_action_dims; g.R = c.num_actions + c.prev_action_null; g.ldw = g.flat + g.E;   // (no route below depends on E)
     p.cell = h->rnn == EC_RNN_LSTM ? Cell::lstm : Cell::gru;
     g.G = (p.cell == Cell::lstm ? 4 : 3) * c.hidden; g.SW = (p.cell == Cell::lstm ? 2 : 1) * c.hidden;
+    g.L = h->layers;
     const int B = g.B, S = g.S, M49 = g.M49, H = g.H, C = g.C, flat = g.flat;
     p.infer = mode != EC_POLICY_LEARN; p.feat_bf16 = feat_bf16; p.vec = c.goal_in > 0;
     p.wide = !p.infer && g.A1 > 8;
-    p.ordered = p.vec || p.wide || p.cell == Cell::lstm;
+    p.ordered = p.vec || p.wide || p.cell == Cell::lstm || g.L > 1;
     p.key = ec_policy::Built{T, N, feat_bf16 ? 1 : 0};
     // Act step: so few rows that the two long-K, small-M GEMMs (compressor conv 1, GRU input projection) run as ACT_PARTS K
     // slices whose partial matrices the consuming kernels fold in a fixed order (no float atomics: rollouts stay bit-reproducible)
@@ -1816,6 +1835,8 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
         if (p.step_bwd == Step::fused16) p.step_bwd = Step::fused32;
     }
     const bool step_ok_any = step_ok || p.cell == Cell::lstm;
+    // a multi-layer core's act step: every layer one launch of the 32-tile geometry (a GRU whose fused step is off: the general route)
+    p.stack = g.L > 1 && cfg.rnn_stack && p.infer && T == 1 && p.step_fwd == Step::fused32 && ec_lstm_hidden_ok(H);
     // GRU input projection.  Act step with a handful of rows: one launch, K split over the waves of a workgroup and folded
     // in-kernel (gi_act_kernel); else split-K only as separate partial matrices folded by the step kernel
     const int gi_nw = (flat % 56 == 0) ? 7 : ((flat % 64 == 0) ? 8 : 0);
@@ -1856,6 +1877,16 @@ struct Ctx {
     // stream 1 (the dual encoder's depth stream) has its own compressor / combiner tensors
     size_t off(int i, int sidx = 0) const { return h->off[(sidx && i >= P_W1 && i <= P_B4) ? i + (P_W1D - P_W1) : i]; }
     const float* W(int i, int sidx = 0) const { return params + off(i, sidx); }
+    // layer l >= 1's tensor k (0 weight_ih, 1 weight_hh, 2 bias_ih, 3 bias_hh)
+    const float* UW(int l, int k) const { return params + h->uoff[l - 1][k]; }
+    // what a recurrence (forward or reverse) of ONE layer reads and writes; layer 0's is the single-layer handle's
+    struct Layer { const float *whh, *bhh; float *gi, *gates, *hn, *hp, *hs, *cs; int gi_fold; };
+    Layer layer(int l) const {
+        if (l == 0) return Layer{W(P_WHH), W(P_BHH), ws + w.gi, ws + w.gates, ws + w.hn, ws + w.hp, ws + w.hs, ws + w.cs, p.gi_fold};
+        return Layer{UW(l, 1), UW(l, 3), ws + w.ugi[l - 1], ws + w.ugates[l - 1], ws + w.uhn[l - 1], ws + w.uhp[l - 1], ws + w.uhs[l - 1],
+                     ws + w.ucs[l - 1], 1};
+    }
+    float* hs_top() const { return ws + (g.L > 1 ? w.uhs[g.L - 2] : w.hs); }   // the history the heads read
     // ec_gemm_f32 without its extras (row-group bias, ReLU mask, row scale, split-K)
     int gemm(const void* A, const void* B, float* Cp, int M, int N, int K, long sam, long sak, long sbk, long sbn, int ldc, int flags = 0,
              const float* bias = nullptr) const {
@@ -2013,29 +2044,36 @@ struct Fwd : Ctx {
     // step 0 reads pitch 2H and every later step pitch H.  T == 1 inference with a state row of its own: the step stores h
     // densely for the heads AND into the row, c into the row -- the GRU act step's launch count, no copy on the serial chain.
     float* state_out = nullptr;      // the caller's h_final on an LSTM handle (or null)
-    int recurrence_lstm(const float* h0, const float* masks, float* hs) {
+    Layer lay{};                     // the layer the recurrence() members run (set by the caller)
+    // h0 / so: this layer's slice of the state rows (pitch ld_s = L * 2H; one layer: the rows themselves)
+    int recurrence_lstm(const float* h0, const float* masks, float* hs, float* so, long ld_s) {
         const int N = g.N, H = g.H, T = g.T;
-        float* cs = ws + w.cs;
-        const bool direct = p.hs_direct && state_out && state_out != h0;
+        float* cs = lay.cs;
+        const bool direct = p.hs_direct && so && so != h0;
         const bool keep = !p.infer;      // learn pass: gates and the masked previous states for the backward
         for (int t = 0; t < T; ++t) {
             const size_t o4 = (size_t)t * N * g.G, o1 = (size_t)t * N * H;
             const float* hprev = t == 0 ? h0 : hs + o1 - (size_t)N * H;
             const float* cprev = t == 0 ? h0 + H : cs + o1 - (size_t)N * H;
-            ec_lstm_fwd_launch(ws + w.gi + o4, W(P_WHH), W(P_BHH), hprev, cprev, t == 0 ? 2L * H : (long)H, masks + (size_t)t * N, hs + o1, H,
-                               direct ? state_out + H : cs + o1, direct ? 2L * H : (long)H, direct ? state_out : nullptr, 2L * H,
-                               keep ? ws + w.gates + o4 : nullptr, keep ? ws + w.hp + o1 : nullptr, keep ? ws + w.hn + o1 : nullptr, N, H,
-                               p.gi_fold, (long)g.B * g.G, s);
+            ec_lstm_fwd_launch(lay.gi + o4, lay.whh, lay.bhh, hprev, cprev, t == 0 ? ld_s : (long)H, masks + (size_t)t * N, hs + o1, H,
+                               direct ? so + H : cs + o1, direct ? ld_s : (long)H, direct ? so : nullptr, ld_s,
+                               keep ? lay.gates + o4 : nullptr, keep ? lay.hp + o1 : nullptr, keep ? lay.hn + o1 : nullptr, N, H,
+                               lay.gi_fold, (long)g.B * g.G, s);
         }
-        if (state_out && !direct)
-            ec_lstm_state_rows_launch(state_out, hs + (size_t)(T - 1) * N * H, cs + (size_t)(T - 1) * N * H, N, H, 0, s);
+        if (so && !direct) {
+            if (g.L == 1) ec_lstm_state_rows_launch(so, hs + (size_t)(T - 1) * N * H, cs + (size_t)(T - 1) * N * H, N, H, 0, s);
+            else {
+                ec_pa_rows_copy_launch(hs + (size_t)(T - 1) * N * H, H, so, (int)ld_s, N, H, 0, s);
+                ec_pa_rows_copy_launch(cs + (size_t)(T - 1) * N * H, H, so + H, (int)ld_s, N, H, 0, s);
+            }
+        }
         return EC_OK;
     }
 
-    // the sequential recurrence; step t's new state goes to hs + t * N * H
+    // the sequential recurrence of layer `lay`; step t's new state goes to hs + t * N * H
     int recurrence(const float* h0, const float* masks, float* hs) {
         const int N = g.N, H = g.H;
-        if (p.cell == Cell::lstm) return recurrence_lstm(h0, masks, hs);
+        if (p.cell == Cell::lstm) return recurrence_lstm(h0, masks, hs, state_out, 2L * H);
         const size_t gru16_lds = (size_t)(4 * 64 * 128 + 4 * 3 * 256) * sizeof(float);
         if (p.step_fwd == Step::fused32) allow_big_lds<gru_step_fwd_kernel>();
         if (p.step_fwd == Step::fused16) allow_big_lds<gru_step_fwd512_kernel>();
@@ -2045,17 +2083,69 @@ struct Fwd : Ctx {
             const size_t o3 = (size_t)t * N * 3 * H, o1 = (size_t)t * N * H;
             if (p.step_fwd == Step::fused16) {
                 hipLaunchKernelGGL(gru_step_fwd512_kernel, dim3(32u, (unsigned)((N + 15) / 16)), dim3(256), gru16_lds, s,
-                                   ws + w.gi + o3, W(P_WHH), W(P_BHH), hprev, m, hs + o1, ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, N);
+                                   lay.gi + o3, lay.whh, lay.bhh, hprev, m, hs + o1, lay.gates + o3, lay.hn + o1, lay.hp + o1, N);
             } else if (p.step_fwd == Step::fused32) {
                 hipLaunchKernelGGL(gru_step_fwd_kernel, dim3((unsigned)(H / 8), (unsigned)((N + 31) / 32)), dim3(256), p.gru_lds, s,
-                                   ws + w.gi + o3, W(P_WHH), W(P_BHH), hprev, m, hs + o1, ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1,
-                                   N, H, p.gi_fold, (long)g.B * 3 * H);
+                                   lay.gi + o3, lay.whh, lay.bhh, hprev, m, hs + o1, lay.gates + o3, lay.hn + o1, lay.hp + o1,
+                                   N, H, lay.gi_fold, (long)g.B * 3 * H);
             } else {
-                RC(gemm(hprev, W(P_WHH), ws + w.gh, N, 3 * H, H, H, 1, 1, H, 3 * H));
-                hipLaunchKernelGGL(gru_gates_fwd_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, ws + w.gi + o3, ws + w.gh,
-                                   W(P_BHH), hprev, m, hs + o1, ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, N, H);
+                RC(gemm(hprev, lay.whh, ws + w.gh, N, 3 * H, H, H, 1, 1, H, 3 * H));
+                hipLaunchKernelGGL(gru_gates_fwd_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, lay.gi + o3, ws + w.gh,
+                                   lay.bhh, hprev, m, hs + o1, lay.gates + o3, lay.hn + o1, lay.hp + o1, N, H);
             }
         }
+        return EC_OK;
+    }
+
+    // A multi-layer core (g.L > 1).  h0 / h_final: [N, L * SW] rows, layer l's state the slice at l * SW.
+    //   * act step (p.stack, a state row of its own to write): layer 0's step with both states at the row pitch (an LSTM: lstm.hip's
+    //     kernel; a GRU: rnn_stack.hip's with the projection as given), then ONE rnn_stack.hip launch per upper layer, which reads
+    //     the layer below out of the new state row; the top layer also stores h densely for the heads.  No copy launch.
+    //   * otherwise layer by layer: layer l's whole recurrence with the single-layer step kernels, then one GEMM over all T * N rows
+    //     with the bias fused gives layer l + 1's input projection.
+    int recurrence_layers(const float* h0, const float* masks, float* h_final) {
+        const int L = g.L, N = g.N, H = g.H, T = g.T, B = g.B, SW = g.SW;
+        const long ld_s = (long)L * SW;
+        const bool lstm = p.cell == Cell::lstm;
+        if (p.stack && h_final && h_final != h0) {
+            lay = layer(0);
+            if (lstm) {
+                ec_lstm_fwd_launch(lay.gi, lay.whh, lay.bhh, h0, h0 + H, ld_s, masks, h_final, ld_s, h_final + H, ld_s, nullptr, 0, nullptr,
+                                   nullptr, nullptr, N, H, lay.gi_fold, (long)B * g.G, s);
+            } else {
+                ec_rnn_stack_args a{};
+                a.whh = lay.whh; a.bhh = lay.bhh; a.hprev = h0; a.ld_prev = ld_s; a.mask = masks; a.hout = h_final; a.ld_h = ld_s;
+                a.gi = lay.gi; a.gi_parts = lay.gi_fold; a.gi_pstride = (long)B * g.G; a.N = N; a.H = H;
+                ec_rnn_stack_launch(0, a, s);
+            }
+            for (int l = 1; l < L; ++l) {
+                ec_rnn_stack_args a{};
+                a.x = h_final + (size_t)(l - 1) * SW; a.ld_x = ld_s;
+                a.wih = UW(l, 0); a.whh = UW(l, 1); a.bih = UW(l, 2); a.bhh = UW(l, 3);
+                a.hprev = h0 + (size_t)l * SW; a.cprev = lstm ? a.hprev + H : nullptr; a.ld_prev = ld_s; a.mask = masks;
+                a.hout = h_final + (size_t)l * SW; a.ld_h = ld_s; a.cout = lstm ? a.hout + H : nullptr; a.ld_c = ld_s;
+                a.hout2 = l == L - 1 ? hs_top() : nullptr; a.ld_h2 = H;
+                a.gi_parts = 1; a.N = N; a.H = H;
+                ec_rnn_stack_launch(lstm ? 1 : 0, a, s);
+            }
+            return EC_OK;
+        }
+        const float* below = nullptr;
+        for (int l = 0; l < L; ++l) {
+            lay = layer(l);
+            if (l) RC(gemm(below, UW(l, 0), lay.gi, B, g.G, H, H, 1, 1, H, g.G, 0, UW(l, 2)));
+            if (lstm) {
+                RC(recurrence_lstm(h0 + (size_t)l * SW, masks, lay.hs, h_final ? h_final + (size_t)l * SW : nullptr, ld_s));
+            } else {
+                float* d0 = ws + w.uh0 + (size_t)l * N * H;
+                ec_pa_rows_copy_launch(h0 + (size_t)l * H, (int)ld_s, d0, H, N, H, 0, s);
+                RC(recurrence(d0, masks, lay.hs));
+            }
+            below = lay.hs;
+        }
+        if (!lstm && h_final)
+            for (int l = 0; l < L; ++l)
+                ec_pa_rows_copy_launch(layer(l).hs + (size_t)(T - 1) * N * H, H, h_final + (size_t)l * H, (int)ld_s, N, H, 0, s);
         return EC_OK;
     }
 
@@ -2118,7 +2208,15 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
     RC(f.input_projection());
     const bool lstm = p.cell == Cell::lstm;   // (the heads read the dense history; recurrence_lstm leaves the [h | c] rows in h_final)
     float* hs = (!lstm && p.hs_direct && h_final && h_final != h0) ? h_final : f.ws + p.w.hs;
+    if (p.g.L > 1) {       // a multi-layer core leaves every layer's state in h_final itself; the heads read the top layer's history
+        hs = f.hs_top();
+        RC(f.recurrence_layers(h0, masks, h_final));
+        RC(f.heads(hs, hv, nullptr, smp, wide));
+        EC_CHECK_LAUNCH();
+        return EC_OK;
+    }
     if (lstm) f.state_out = h_final;
+    f.lay = f.layer(0);
     RC(f.recurrence(h0, masks, hs));
     RC(f.heads(hs, hv, lstm ? nullptr : h_final, smp, wide));
     EC_CHECK_LAUNCH();
@@ -2192,47 +2290,53 @@ struct Bwd : Ctx {
             float* gt = ws + w.hG;
             RC(gemm(dhv, ws + w.hW, ws + w.dhs, B, H, A1, A1, 1, H, 1, H));
             (void)hipMemsetAsync(gt, 0, ((size_t)A1 * H + A1) * 4, s);
-            RC(gemm_acc_split(dhv, ws + w.hs, gt, A1, H, B, 1, A1, H, 1, H, 0, pick_splitk(A1, H, B)));
+            RC(gemm_acc_split(dhv, hs_top(), gt, A1, H, B, 1, A1, H, 1, H, 0, pick_splitk(A1, H, B)));
             colsum(dhv, gt + (size_t)A1 * H, B, A1, A1, ws + w.hP, (size_t)HP_MAXY * A1);
             ec_heads_unpack_add_launch(gt, G(P_WA), G(P_BA), G(P_WC), G(P_BC), A, H, s);
             return EC_OK;
         }
         RC(gemm(dhv, W(P_WA), ws + w.dhs, B, H, A, A1, 1, H, 1, H));
         RC(gemm(dhv + A, W(P_WC), ws + w.dhs, B, H, 1, A1, 1, H, 1, H, EC_GEMM_ACCUMULATE));
-        RC(gemm_acc_split(dhv, ws + w.hs, G(P_WA), A, H, B, 1, A1, H, 1, H, 0, pick_splitk(A, H, B)));
-        RC(gemm_acc_split(dhv + A, ws + w.hs, G(P_WC), 1, H, B, 1, A1, H, 1, H, 0, pick_splitk(1, H, B)));
+        RC(gemm_acc_split(dhv, hs_top(), G(P_WA), A, H, B, 1, A1, H, 1, H, 0, pick_splitk(A, H, B)));
+        RC(gemm_acc_split(dhv + A, hs_top(), G(P_WC), 1, H, B, 1, A1, H, 1, H, 0, pick_splitk(1, H, B)));
         colsum(dhv, G(P_BA), B, A, A1);
         colsum(dhv + A, G(P_BC), B, 1, A1);
         return EC_OK;
     }
 
+    Layer lay{};                  // the layer the recurrence() members run (set by the caller)
+    int lidx = 0;                 // ... and its index: dh_final's slice at lidx * SW starts its carries
     // LSTM, reverse time (lstm.hip).  dh_final is [N, 2H] rows [dh | dc]: its halves start the two carries.  Fused: step T-1 is
     // the plain gate kernel, every earlier step ONE launch (back-projection of step t+1 + gates of step t, against a W_hh
     // transposed once); else gate kernel + GEMM per step with split-K 1.  No float atomics on either route.
     int recurrence_lstm(const float* masks, const float* dh_final) {
         const int T = g.T, N = g.N, H = g.H, GW = g.G;
         float* da = ws + w.dgi;
-        if (dh_final) ec_lstm_state_rows_launch(const_cast<float*>(dh_final), ws + w.dhc, ws + w.dcc, N, H, 1, s);
+        if (dh_final && g.L > 1) {
+            const float* row = dh_final + (size_t)lidx * g.SW;
+            ec_pa_rows_copy_launch(row, g.L * g.SW, ws + w.dhc, H, N, H, 0, s);
+            ec_pa_rows_copy_launch(row + H, g.L * g.SW, ws + w.dcc, H, N, H, 0, s);
+        } else if (dh_final) ec_lstm_state_rows_launch(const_cast<float*>(dh_final), ws + w.dhc, ws + w.dcc, N, H, 1, s);
         else {
             (void)hipMemsetAsync(ws + w.dhc, 0, (size_t)N * H * 4, s);
             (void)hipMemsetAsync(ws + w.dcc, 0, (size_t)N * H * 4, s);
         }
         const bool fused = p.step_bwd != Step::gemm_gates;
         if (fused)
-            hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)(H / 32), (unsigned)(GW / 32)), dim3(256), 0, s, W(P_WHH), ws + w.whhT, GW, H);
+            hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)(H / 32), (unsigned)(GW / 32)), dim3(256), 0, s, lay.whh, ws + w.whhT, GW, H);
         for (int t = T - 1; t >= 0; --t) {
             const size_t o4 = (size_t)t * N * GW, o1 = (size_t)t * N * H;
             const float* m = masks + (size_t)t * N;
             if (!fused || t == T - 1) {
-                ec_lstm_bwd_gates_launch(ws + w.dhs + o1, ws + w.dhc, ws + w.dcc, ws + w.gates + o4, ws + w.cs + o1, ws + w.hn + o1, m, da + o4,
+                ec_lstm_bwd_gates_launch(ws + w.dhs + o1, ws + w.dhc, ws + w.dcc, lay.gates + o4, lay.cs + o1, lay.hn + o1, m, da + o4,
                                          N, H, s);
                 // dh_carry (left zero by the gate kernel) += m * (da @ W_hh)   (fused: inside the next launch)
                 if (!fused)
-                    RC(ec_gemm_f32(da + o4, W(P_WHH), ws + w.dhc, N, H, GW, GW, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr, nullptr, nullptr, 0,
+                    RC(ec_gemm_f32(da + o4, lay.whh, ws + w.dhc, N, H, GW, GW, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr, nullptr, nullptr, 0,
                                    nullptr, m, 1, stream));
             } else {
-                ec_lstm_bwd_fused_launch(da + o4 + (size_t)N * GW, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dcc, ws + w.gates + o4,
-                                         ws + w.cs + o1, ws + w.hn + o1, m, da + o4, N, H, s);
+                ec_lstm_bwd_fused_launch(da + o4 + (size_t)N * GW, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dcc, lay.gates + o4,
+                                         lay.cs + o1, lay.hn + o1, m, da + o4, N, H, s);
             }
         }
         return EC_OK;
@@ -2244,10 +2348,11 @@ struct Bwd : Ctx {
         const int T = g.T, N = g.N, H = g.H;
         if (p.cell == Cell::lstm) return recurrence_lstm(masks, dh_final);
         const size_t gb_lds = (size_t)2 * 32 * (256 + 4) * sizeof(float), gb16_lds = (size_t)(4 * 2 * 32 * 128 + 4 * 256) * sizeof(float);
-        if (dh_final) (void)hipMemcpyAsync(ws + w.dhc, dh_final, (size_t)N * H * 4, hipMemcpyDeviceToDevice, s);
+        if (dh_final && g.L > 1) ec_pa_rows_copy_launch(dh_final + (size_t)lidx * H, g.L * H, ws + w.dhc, H, N, H, 0, s);
+        else if (dh_final) (void)hipMemcpyAsync(ws + w.dhc, dh_final, (size_t)N * H * 4, hipMemcpyDeviceToDevice, s);
         else (void)hipMemsetAsync(ws + w.dhc, 0, (size_t)N * H * 4, s);
         if (p.step_bwd != Step::gemm_gates)
-            hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)(H / 32), (unsigned)(3 * H / 32)), dim3(256), 0, s, W(P_WHH), ws + w.whhT, 3 * H, H);
+            hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)(H / 32), (unsigned)(3 * H / 32)), dim3(256), 0, s, lay.whh, ws + w.whhT, 3 * H, H);
         if (p.step_bwd == Step::fused32) allow_big_lds<gru_step_bwd_kernel>();
         if (p.step_bwd == Step::fused16) allow_big_lds<gru_step_bwd512_kernel>();
         for (int t = T - 1; t >= 0; --t) {
@@ -2255,22 +2360,36 @@ struct Bwd : Ctx {
             const float* m = masks + (size_t)t * N;
             if (p.step_bwd == Step::gemm_gates || t == T - 1) {
                 hipLaunchKernelGGL(gru_gates_bwd_kernel, dim3((N * H + 255) / 256), dim3(256), 0, s, ws + w.dhs + o1, ws + w.dhc,
-                                   ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N, H);
+                                   lay.gates + o3, lay.hn + o1, lay.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N, H);
                 // dh_carry += m * (dghb @ W_hh)   (fused: step T-1's back-projection runs inside the next launch)
                 if (p.step_bwd == Step::gemm_gates)
-                    RC(ec_gemm_f32(ws + w.dghb + o3, W(P_WHH), ws + w.dhc, N, H, 3 * H, 3 * H, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr,
-                                   nullptr, nullptr, 0, nullptr, m, (p.vec || p.wide) ? 1 : step_splitk(N, H, 3 * H), stream));
+                    RC(ec_gemm_f32(ws + w.dghb + o3, lay.whh, ws + w.dhc, N, H, 3 * H, 3 * H, 1, H, 1, H, EC_GEMM_ACCUMULATE, nullptr,
+                                   nullptr, nullptr, 0, nullptr, m, p.ordered ? 1 : step_splitk(N, H, 3 * H), stream));
             } else if (p.step_bwd == Step::fused16) {
                 hipLaunchKernelGGL(gru_step_bwd512_kernel, dim3(32u, (unsigned)((N + 15) / 16)), dim3(256), gb16_lds, s,
                                    ws + w.dghb + o3 + (size_t)N * 3 * H, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dhc,
-                                   ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N);
+                                   lay.gates + o3, lay.hn + o1, lay.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N);
             } else {
                 hipLaunchKernelGGL(gru_step_bwd_kernel, dim3((unsigned)(H / 32), (unsigned)((N + 31) / 32)), dim3(256), gb_lds, s,
                                    ws + w.dghb + o3 + (size_t)N * 3 * H, ws + w.whhT, m + N, ws + w.dhs + o1, ws + w.dhc,
-                                   ws + w.gates + o3, ws + w.hn + o1, ws + w.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N, H);
+                                   lay.gates + o3, lay.hn + o1, lay.hp + o1, m, ws + w.dgi + o3, ws + w.dghb + o3, N, H);
             }
         }
         return EC_OK;
+    }
+
+    // Layer l >= 1 of a multi-layer core, behind its reverse recurrence: its four gradients (the input history is the layer below's
+    // state history), then dx = da W_ih over all T * N rows INTO the dhs area -- the reverse recurrence of layer l - 1 reads it as
+    // the heads' dhs was read at the top.  GEMMs in one K piece or K slices folded in order, ordered column sums: no float atomics.
+    int upper_layer_grads(int l) {
+        const int B = g.B, H = g.H, GW = g.G;
+        const float* dghb = ws + (p.cell == Cell::lstm ? w.dgi : w.dghb);
+        float* gu = grads;
+        RC(tn_gru(dghb, lay.hp, gu + h->uoff[l - 1][1], GW, H, B));
+        colsum(dghb, gu + h->uoff[l - 1][3], B, GW, GW);
+        RC(tn_gru(ws + w.dgi, layer(l - 1).hs, gu + h->uoff[l - 1][0], GW, H, B));
+        colsum(ws + w.dgi, gu + h->uoff[l - 1][2], B, GW, GW);
+        return gemm(ws + w.dgi, UW(l, 0), ws + w.dhs, B, H, GW, GW, 1, H, 1, H);
     }
 
     // weight and bias gradients of the recurrence and of the input projection (TN over all T*N rows)
@@ -2417,11 +2536,16 @@ struct Bwd : Ctx {
 
 extern "C" int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg) { return ec_policy_create_rnn(out, cfg, EC_RNN_GRU); }
 extern "C" int ec_policy_rnn_type(const ec_policy_t* h) { return h ? h->rnn : -1; }
-extern "C" int ec_policy_state_width(const ec_policy_t* h) { return h ? (h->rnn == EC_RNN_LSTM ? 2 : 1) * h->c.hidden : 0; }
-
+extern "C" int ec_policy_state_width(const ec_policy_t* h) { return h ? h->layers * (h->rnn == EC_RNN_LSTM ? 2 : 1) * h->c.hidden : 0; }
+extern "C" int ec_policy_rnn_layers(const ec_policy_t* h) { return h ? h->layers : 0; }
 extern "C" int ec_policy_create_rnn(ec_policy_t** out, const ec_policy_cfg* cfg, int rnn_type) {
+    return ec_policy_create_rnn_layers(out, cfg, rnn_type, 1);
+}
+
+extern "C" int ec_policy_create_rnn_layers(ec_policy_t** out, const ec_policy_cfg* cfg, int rnn_type, int num_layers) {
     if (!out || !cfg) return EC_ERR_ARG;
     if (rnn_type != EC_RNN_GRU && rnn_type != EC_RNN_LSTM) return EC_ERR_ARG;
+    if (num_layers < 1 || num_layers > EC_RNN_MAX_LAYERS) return EC_ERR_ARG;
     const ec_policy_cfg& c = *cfg;
     if (c.fusion != 0 && c.fusion != 1) return EC_ERR_ARG;
     if (c.dual != 0 && c.dual != 1) return EC_ERR_ARG;
@@ -2443,6 +2567,7 @@ extern "C" int ec_policy_create_rnn(ec_policy_t** out, const ec_policy_cfg* cfg,
     }
     // (coordinate goals: W3[:, co:] and one pass of frames sit in the LDS of the two goal_vec kernels)
     if (c.goal_in && std::max(Fwd::goal_vec_lds(c, false), Fwd::goal_vec_lds(c, true)) > 64 * 1024) return EC_ERR_SHAPE;
+    if (num_layers > 1 && (c.dual || c.fusion)) return EC_ERR_UNSUPPORTED;   // (the two-tower and zero-shot agents keep one layer)
     if (rnn_type == EC_RNN_LSTM) {
         if (c.dual || c.fusion) return EC_ERR_UNSUPPORTED;   // (the two-tower and zero-shot agents keep the GRU)
         if (!ec_lstm_hidden_ok(c.hidden)) return EC_ERR_SHAPE; // (8 units x 4 gates per tile: hidden % 32 == 0, tiles within the LDS)
@@ -2479,6 +2604,13 @@ extern "C" int ec_policy_create_rnn(ec_policy_t** out, const ec_policy_cfg* cfg,
     if (!c.prev_action_dims) h->order[h->ntensors++] = P_PAE; // (zero elements)
     size_t o = 0;
     for (int k = 0; k < P_COUNT; ++k) { const int i = h->order[k]; h->off[i] = o; h->num[i] = n[i]; o += (n[i] + 3) / 4 * 4; }   // 16-B aligned
+    // the upper layers' tensors END the flat order: layer 1, 2, 3; weight_ih, weight_hh, bias_ih, bias_hh each
+    h->layers = num_layers;
+    h->nbase = ec_policy_num_param_tensors(h) - 4 * (num_layers - 1);
+    for (int l = 1; l < num_layers; ++l) {
+        const size_t un[4] = {GW * H, GW * H, GW, GW};
+        for (int k = 0; k < 4; ++k) { h->uoff[l - 1][k] = o; h->unum[l - 1][k] = un[k]; o += (un[k] + 3) / 4 * 4; }
+    }
     h->total = o;
     *out = h;
     return EC_OK;
@@ -2490,11 +2622,19 @@ extern "C" int ec_policy_set_goal_table(ec_policy_t* h, const float* table) {
     return EC_OK;
 }
 extern "C" int ec_policy_num_param_tensors(const ec_policy_t* h) {
-    return ((h && h->c.dual) ? P_COUNT_DUAL : ((h && h->c.goal_in) ? P_COUNT_VEC : P_COUNT_SINGLE)) + ((h && h->c.prev_action_dims) ? 1 : 0);
+    return ((h && h->c.dual) ? P_COUNT_DUAL : ((h && h->c.goal_in) ? P_COUNT_VEC : P_COUNT_SINGLE)) + ((h && h->c.prev_action_dims) ? 1 : 0) +
+           (h ? 4 * (h->layers - 1) : 0);
 }
 extern "C" size_t ec_policy_flat_size(const ec_policy_t* h) { return h ? h->total : 0; }
 extern "C" int ec_policy_param_offset(const ec_policy_t* h, int idx, size_t* off, size_t* numel) {
-    if (!h || idx < 0 || idx >= P_COUNT_DUAL || !off || !numel) return EC_ERR_ARG;
+    if (!h || idx < 0 || !off || !numel) return EC_ERR_ARG;
+    if (h->layers > 1 && idx >= h->nbase) {           // an upper layer's tensor
+        const int u = idx - h->nbase;
+        if (u >= 4 * (h->layers - 1)) return EC_ERR_ARG;
+        *off = h->uoff[u / 4][u % 4]; *numel = h->unum[u / 4][u % 4];
+        return EC_OK;
+    }
+    if (idx >= P_COUNT_DUAL) return EC_ERR_ARG;
     *off = h->off[h->order[idx]]; *numel = h->num[h->order[idx]];
     return EC_OK;
 }
@@ -2650,7 +2790,11 @@ extern "C" int ec_policy_backward3(const ec_policy_t* h, const float* params, co
     b.grads = grads;
     b.masks_all = masks;
     RC(b.heads(dhv));
-    RC(b.recurrence(masks, dh_final));
+    for (int l = p.g.L - 1; l >= 0; --l) {       // top layer down; layer l - 1's dhs is layer l's dx
+        b.lay = b.layer(l); b.lidx = l;
+        RC(b.recurrence(masks, dh_final));
+        if (l) RC(b.upper_layer_grads(l));
+    }
     RC(b.gru_grads());
     // the gradients of the GRU and of both heads (tensors rnn.weight_ih_l0 .. critic.fc.bias: 92 % of the bucket) are final
     // here; what follows only writes the goal encoder's.  A caller that sums the bucket over ranks starts that section's

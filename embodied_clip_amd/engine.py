@@ -159,6 +159,18 @@ def check_rnn_type(rnn_type: str, depth: bool, zeroshot: bool) -> str:
     return rnn_type
 
 
+def check_rnn_layers(rnn_layers: int, depth: bool, zeroshot: bool) -> int:
+    """``Worker`` / ``Evaluator`` ``(rnn_layers=L)``: the recurrent depth ([U] RNNStateEncoder ``num_layers``), refused where the
+    policy library refuses it; raised before anything is allocated."""
+    if not (isinstance(rnn_layers, int) and not isinstance(rnn_layers, bool) and 1 <= rnn_layers <= 4):
+        raise ValueError(f"rnn_layers={rnn_layers!r}: an integer in 1..4")
+    if rnn_layers > 1 and depth:
+        raise ValueError("rnn_layers > 1 with depth=True: the two-tower (RGB + depth) agent keeps one recurrent layer")
+    if rnn_layers > 1 and zeroshot:
+        raise ValueError("rnn_layers > 1 with zeroshot=True: the zero-shot fusion policy keeps one recurrent layer")
+    return rnn_layers
+
+
 def check_rgbd(encoder: str, zeroshot: bool, goal_in: int, frames_host: bool) -> None:
     """What ``depth=True`` (the RGB-D agent) cannot be combined with; raised before anything is allocated."""
     if encoder not in ("rn50", "rn50x16"):
@@ -175,6 +187,10 @@ def check_model_tensors(policy, sd, where: str) -> None:
     """A checkpoint's ``model_state_dict`` against the handle's tensors: a missing one (a checkpoint written without the
     previous-action embedding, loaded by an agent that has it) raises, naming the tensor and the file; so does one whose
     element count differs (a GRU checkpoint's ``3H``-row recurrent tensors into an LSTM agent, or the reverse), naming both shapes."""
+    for name in sd:                     # a deeper checkpoint: an upper recurrent layer this agent does not have
+        if name.startswith("state_encoder.rnn.") and name not in policy.offsets:
+            raise ValueError(f"{where}: the checkpoint's tensor {name!r} {tuple(sd[name].shape)} belongs to a recurrent layer this agent "
+                             f"does not have (rnn_layers={getattr(policy, 'rnn_layers', 1)})")
     for name in policy.offsets:
         if name not in sd:
             raise KeyError(f"{where}: the checkpoint lacks the tensor {name!r} {tuple(policy.shapes[name])} of this agent")
@@ -204,6 +220,9 @@ class _SlicedActor:
     prev_action_null = 0
     # the recurrent cell ([U] RNNStateEncoder rnn_type): "LSTM" makes every recurrent-memory buffer [N, 2H] rows [h | c]
     rnn_type = "GRU"
+    # recurrent layers ([U] RNNStateEncoder num_layers): a memory row is [N, L * SW], layer-major
+    rnn_layers = 1
+    hidden_size = 512       # the recurrent width ([U] hidden_size); ``Worker`` / ``Evaluator`` ``(hidden=...)``
 
     def _build_model(self, n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams):
         """Encoder handles (one per slice, weights shared), the policy handle and its flat parameters.  -> (encs, pools)"""
@@ -259,7 +278,9 @@ class _SlicedActor:
             pkw["fusion"] = 1
         if self.prev_action_dims:
             pkw.update(prev_action_dims=self.prev_action_dims, prev_action_null=self.prev_action_null)
-        self.policy = PolicyHandle(rnn_type=self.rnn_type, **pkw)
+        if self.hidden_size != 512:
+            pkw["hidden"] = self.hidden_size
+        self.policy = PolicyHandle(rnn_type=self.rnn_type, rnn_layers=self.rnn_layers, **pkw)
         if policy_sd is not None:   # (a checkpoint of the other recurrent cell: refused by the tensor's name, both shapes and the file)
             check_model_tensors(self.policy, policy_sd, getattr(self, "_checkpoint", None) or "policy_sd")
         if self.zeroshot:
@@ -270,9 +291,9 @@ class _SlicedActor:
             self.goal_table = ClipTextEncoder(tsd, device=d).goal_table(tok).contiguous()
             self.policy.set_goal_table(self.goal_table)
         self.H, self.A = self.policy.H, self.policy.A
-        self.SW = self.policy.state_width        # width of a recurrent-memory row: H, or 2H ([h | c]) with an LSTM core
+        self.SW = self.policy.state_width        # width of a recurrent-memory row: L * H, or L * 2H ([h | c] per layer) with an LSTM core
         self.params = self.policy.flatten(policy_sd if policy_sd is not None
-                                          else syn.policy_state_dict(0, **pkw, rnn_type=self.rnn_type), d)
+                                          else syn.policy_state_dict(0, **pkw, rnn_type=self.rnn_type, rnn_layers=self.rnn_layers), d)
         return encs, pools
 
     def _build_slices(self, n_actors, encs, pools, feat_steps, n_comm, frames_host):
@@ -455,8 +476,16 @@ class Worker(_SlicedActor):
                  num_mini_batch: int = 1, sync_actions: bool = False, force_allreduce: bool = False,
                  overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False,
                  nav_metrics: bool = False, depth: bool = False, loss: str = "ppo", il_weight: float = 1.0,
-                 teacher_forcing=None, prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU"):
-        """``rnn_type``: "GRU" (default) or "LSTM" ([U] RNNStateEncoder ``rnn_type``; the Habitat DD-PPO policies) -- the
+                 teacher_forcing=None, prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU",
+                 rnn_layers: int = 1, hidden: int = 512):
+        """``hidden``: the recurrent width ([U] ``hidden_size``; 512 in every published config).
+
+        ``rnn_layers=L`` (1..4; [U] RNNStateEncoder ``num_layers``, 2 in the Habitat DD-PPO policies): the recurrent memory is
+        ``[N, L * SW]`` rows, layer-major (``policy.memory_to_state`` converts upstream's); a checkpoint carries the upper
+        layers' tensors ``state_encoder.rnn.*_l{k}`` and one of another depth is refused by tensor name; their gradients are
+        all-reduced with the sections outside ``recurrent_section()``.  ``ValueError`` with ``depth=True`` or ``zeroshot=True``.
+
+        ``rnn_type``: "GRU" (default) or "LSTM" ([U] RNNStateEncoder ``rnn_type``; the Habitat DD-PPO policies) -- the
         recurrent memory ``h`` / ``h_next`` / ``h_start`` is then ``[N, 2 * hidden]`` rows ``[h | c]``, checkpoints carry the
         ``4 * hidden``-row recurrent tensors under the same names.  ``ValueError`` with ``depth=True`` or ``zeroshot=True``.
 
@@ -500,6 +529,8 @@ class Worker(_SlicedActor):
         self.prev_action_dims = check_prev_actions(prev_actions, bool(depth), bool(zeroshot))
         self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
         self.rnn_type = check_rnn_type(rnn_type, bool(depth), bool(zeroshot))
+        self.rnn_layers = check_rnn_layers(rnn_layers, bool(depth), bool(zeroshot))
+        self.hidden_size = int(hidden)
         self.depth = bool(depth)
         self.lib = _lib.load()
         self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens

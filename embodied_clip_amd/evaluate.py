@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_prev_actions, check_rgbd, check_rnn_type
+from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_prev_actions, check_rgbd, check_rnn_layers, check_rnn_type
 from .episodes import EpisodeTracker, NavEpisodeTracker, category_names, nav_env_tensors
 
 
@@ -50,7 +50,8 @@ class Evaluator(_SlicedActor):
     (zeros before the first); a checkpoint then carries one more tensor, and one without it is refused by name; ``ValueError``
     with ``depth=True`` or ``zeroshot=True``.  ``rnn_type="LSTM"``: the agent of ``Worker(rnn_type="LSTM")`` -- the recurrent memory
     is ``[N, 2 * hidden]`` rows ``[h | c]``; a checkpoint of the other cell is refused with the tensor's name and both shapes;
-    ``ValueError`` with ``depth=True`` or ``zeroshot=True``."""
+    ``ValueError`` with ``depth=True`` or ``zeroshot=True``.  ``rnn_layers=L``: the agent of ``Worker(rnn_layers=L)`` -- the memory is
+    ``[N, L * SW]`` rows; a checkpoint of another depth is refused by tensor name; the same two ``ValueError``s."""
 
     def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, encoder: str = "rn50",
                  encoder_sd=None, policy_sd=None, checkpoint: Optional[str] = None, deterministic: bool = False,
@@ -58,8 +59,11 @@ class Evaluator(_SlicedActor):
                  zeroshot: bool = False, sync_actions: bool = False, record: bool = False, env=None, text_sd=None,
                  goal_tokens=None, encoder_chunk: int = 0, record_capacity: int = 0, nav_metrics: bool = False,
                  num_categories: Optional[int] = None, env_seed: Optional[int] = None, depth: bool = False,
-                 prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU"):
+                 prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU",
+                 rnn_layers: int = 1, hidden: int = 512):
+        self.hidden_size = int(hidden)
         self.rnn_type = check_rnn_type(rnn_type, bool(depth), bool(zeroshot))
+        self.rnn_layers = check_rnn_layers(rnn_layers, bool(depth), bool(zeroshot))
         if depth:       # the RGB-D agent (engine.Worker(depth=True)): the same refusals, before anything is built
             check_rgbd(encoder, zeroshot, goal_in, bool(env is not None and getattr(env, "host", False)))
             if env is not None and getattr(env, "depth", None) is None:
@@ -284,6 +288,7 @@ def main(argv=None) -> int:
     ap.add_argument("--no-prev-action-null-token", action="store_true",
                     help="with --prev-actions: no null row for an episode's first step (action a is row a)")
     ap.add_argument("--rnn-type", default="GRU", choices=("GRU", "LSTM"), help="the recurrent cell of the agent (and of its checkpoint)")
+    ap.add_argument("--rnn-layers", type=int, default=1, choices=(1, 2, 3, 4), help="recurrent layers of the agent (and of its checkpoint)")
     ap.add_argument("--json", default=None, metavar="OUT", help="also write the info dict to this file")
     ap.add_argument("--env-seed", type=int, default=None, help="seed of the synthetic env (default 1000, what Evaluator builds itself)")
     ap.add_argument("--nav-metrics", action="store_true", help="also SPL, SoftSPL, distance to goal, and the scores per object type")
@@ -311,7 +316,7 @@ def main(argv=None) -> int:
     ev = Evaluator(a.actors, T=a.steps, seed=a.seed, env_seed=a.env_seed, encoder=a.encoder, checkpoint=a.checkpoint, deterministic=a.deterministic,
                    goal_in=a.goal_in, num_actions=a.num_actions, zeroshot=a.zeroshot, frames_u8=a.frames_u8,
                    sync_actions=a.sync_actions, nav_metrics=a.nav_metrics, depth=a.depth, prev_actions=a.prev_actions,
-                   prev_action_null_token=not a.no_prev_action_null_token, rnn_type=a.rnn_type,
+                   prev_action_null_token=not a.no_prev_action_null_token, rnn_type=a.rnn_type, rnn_layers=a.rnn_layers,
                    num_categories=len(names) if (names is not None and not a.goal_in) else None,
                    # every actor can end an episode at every step: the metrics file then misses none
                    record_capacity=a.chunks * a.steps * a.actors if a.metrics_json else 0)

@@ -39,14 +39,19 @@ from .allenact_compat import ActorCriticModel, ActorCriticOutput, CategoricalDis
 class PolicyHandle:
     """``ec_policy_t`` plus the flat-buffer layout."""
 
-    def __init__(self, rnn_type: str = "GRU", **cfg: int):
-        """``rnn_type``: "GRU" (the default: ``ec_policy_create``'s handle exactly) or "LSTM" -- the recurrent state of an
+    def __init__(self, rnn_type: str = "GRU", rnn_layers: int = 1, **cfg: int):
+        """``rnn_layers = L`` (1..4; torch's ``num_layers``): the state row is layer-major, ``[h^0 | h^1 | ...]`` or
+        ``[h^0 | c^0 | h^1 | c^1 | ...]``, of width ``state_width == L * SW`` (``memory_to_state`` / ``state_to_memory`` convert
+        upstream's memory); the upper layers' tensors end ``param_order``.  ``rnn_type``: "GRU" (the default: ``ec_policy_create``'s handle exactly) or "LSTM" -- the recurrent state of an
         actor is then one row ``[h | c]`` of width ``state_width == 2 * hidden``, which is what ``h0`` / ``h_final`` /
         ``dh_final`` of every method below hold."""
         self.lib = _lib.load()
         if rnn_type not in _lib.RNN_TYPES:
             raise ValueError(f"rnn_type must be one of {sorted(_lib.RNN_TYPES)}, got {rnn_type!r}")
         self.rnn_type = rnn_type
+        if not (isinstance(rnn_layers, int) and 1 <= rnn_layers <= 4):
+            raise ValueError(f"rnn_layers must be 1..4, got {rnn_layers!r}")
+        self.rnn_layers = rnn_layers
         self.cfg = dict(in_channels=2048, spatial=7, hidden=512, goal_dims=32, num_goals=12, num_actions=6,
                         compress_hid=128, compress_out=32, comb_hid=128, comb_out=32, fusion=0, dual=0, goal_in=0,
                         prev_action_dims=0, prev_action_null=0)
@@ -54,14 +59,18 @@ class PolicyHandle:
         self.goal_in = self.cfg["goal_in"]      # > 0: the goal of a frame is goal_in floats (PointNav), ec_policy_*_vec
         # > 0: the previous action's embedding (this wide) is concatenated to the GRU input; ec_policy_forward_pa / ec_policy_act_pa
         self.prev_action_dims = self.cfg["prev_action_dims"]
-        self.param_order = policy_param_order(self.cfg["dual"], self.goal_in, self.prev_action_dims, self.cfg["prev_action_null"])
+        if rnn_layers > 1 and (self.cfg["dual"] or self.cfg["fusion"]):
+            raise ValueError("the two-tower and zero-shot agents keep one recurrent layer")
+        self.param_order = policy_param_order(self.cfg["dual"], self.goal_in, self.prev_action_dims, self.cfg["prev_action_null"],
+                                              rnn_layers=rnn_layers)
         c = _lib.PolicyCfg(**self.cfg)
         h = C.c_void_p()
-        _lib.check(self.lib.ec_policy_create_rnn(C.byref(h), C.byref(c), _lib.RNN_TYPES[rnn_type]), "ec_policy_create_rnn")
+        _lib.check(self.lib.ec_policy_create_rnn_layers(C.byref(h), C.byref(c), _lib.RNN_TYPES[rnn_type], rnn_layers),
+                   "ec_policy_create_rnn_layers")
         self.h = h
         self.flat_size = self.lib.ec_policy_flat_size(h)
-        self.state_width = self.lib.ec_policy_state_width(h)      # H, or 2H on an LSTM handle
-        self.shapes = policy_param_shapes(**self.cfg, rnn_type=rnn_type)
+        self.state_width = self.lib.ec_policy_state_width(h)      # L * (H, or 2H on an LSTM handle)
+        self.shapes = policy_param_shapes(**self.cfg, rnn_type=rnn_type, rnn_layers=rnn_layers)
         self.offsets: "OrderedDict[str, Tuple[int, int]]" = OrderedDict()
         assert self.lib.ec_policy_num_param_tensors(h) == len(self.param_order)
         for i, name in enumerate(self.param_order):
@@ -244,8 +253,31 @@ class PolicyHandle:
         o0 = self.offsets["state_encoder.rnn.weight_ih_l0"][0]
         o1, k1 = self.offsets["critic.fc.bias"]
         end = o1 + k1
-        later = [o for (o, _) in self.offsets.values() if o >= end]      # (the depth stream's tensors of the dual encoder)
+        later = [o for (o, _) in self.offsets.values() if o >= end]      # (the dual encoder's depth stream; upper recurrent layers)
         return slice(o0, min(later) if later else self.flat_size)
+
+
+def memory_to_state(mem: torch.Tensor, rnn_type: str = "GRU", rnn_layers: int = 1) -> torch.Tensor:
+    """Upstream's recurrent memory -> the handle's state rows.  ``mem``: ``[L, N, H]`` (GRU) or ``[2L, N, H]`` (LSTM: all ``h``
+    layers, then all ``c`` layers -- ``torch.cat([h, c], 0)``, [U] RNNStateEncoder).  Returns ``[N, L * SW]``, layer-major:
+    ``[h^0 | h^1 | ...]`` or ``[h^0 | c^0 | h^1 | c^1 | ...]``."""
+    L = rnn_layers
+    k = 2 if rnn_type == "LSTM" else 1
+    if rnn_type not in _lib.RNN_TYPES or mem.dim() != 3 or mem.shape[0] != k * L:
+        raise ValueError(f"memory of a {L}-layer {rnn_type} is [{k * L}, N, H], got {tuple(mem.shape)}")
+    _, N, H = mem.shape
+    # [k, L, N, H] -> [N, L, k, H]
+    return mem.reshape(k, L, N, H).permute(2, 1, 0, 3).reshape(N, L * k * H).contiguous()
+
+
+def state_to_memory(state: torch.Tensor, rnn_type: str = "GRU", rnn_layers: int = 1) -> torch.Tensor:
+    """The inverse of ``memory_to_state``: ``[N, L * SW]`` rows -> ``[L, N, H]`` / ``[2L, N, H]``."""
+    L = rnn_layers
+    k = 2 if rnn_type == "LSTM" else 1
+    if rnn_type not in _lib.RNN_TYPES or state.dim() != 2 or state.shape[1] % (k * L):
+        raise ValueError(f"state rows of a {L}-layer {rnn_type} are [N, {k * L} * H], got {tuple(state.shape)}")
+    N, H = state.shape[0], state.shape[1] // (k * L)
+    return state.reshape(N, L, k, H).permute(2, 1, 0, 3).reshape(k * L, N, H).contiguous()
 
 
 class _PolicyFn(torch.autograd.Function):

@@ -354,7 +354,19 @@ POLICY_RNN_TENSORS = ("state_encoder.rnn.weight_ih_l0", "state_encoder.rnn.weigh
                       "state_encoder.rnn.bias_hh_l0")
 
 
-def policy_param_order(dual: int = 0, goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0) -> Tuple[str, ...]:
+def policy_rnn_layer_tensors(layer: int) -> Tuple[str, ...]:
+    """The four tensors of recurrent layer ``layer`` ([U] torch.nn.GRU / nn.LSTM: ``weight_ih_l{k}``, ``weight_hh_l{k}``, ...)."""
+    return tuple(k[:-1] + str(layer) for k in POLICY_RNN_TENSORS)
+
+
+def policy_param_order(dual: int = 0, goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0,
+                       rnn_layers: int = 1) -> Tuple[str, ...]:
+    """``rnn_layers = L > 1``: the upper layers' tensors END the order (layer 1, 2, ...; ``weight_ih``, ``weight_hh``,
+    ``bias_ih``, ``bias_hh`` each), so every tensor of the single-layer policy keeps its index."""
+    if rnn_layers != 1:
+        assert 1 <= rnn_layers <= 4 and not dual, "1..4 recurrent layers; the two-tower agent keeps one"
+        return policy_param_order(0, goal_in, prev_action_dims, prev_action_null) + tuple(
+            k for l in range(1, rnn_layers) for k in policy_rnn_layer_tensors(l))
     if prev_action_dims:
         assert not dual, "previous actions with the RGB-D encoder are not built"
         return policy_param_order(0, goal_in) + (POLICY_PREV_ACTION_EMBEDDER,)
@@ -367,13 +379,26 @@ def policy_param_order(dual: int = 0, goal_in: int = 0, prev_action_dims: int = 
 def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int = 512, goal_dims: int = 32,
                         num_goals: int = 12, num_actions: int = 6, compress_hid: int = 128,
                         compress_out: int = 32, comb_hid: int = 128, comb_out: int = 32, fusion: int = 0, dual: int = 0,
-                        goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0, rnn_type: str = "GRU"):
-    """``rnn_type="LSTM"`` (single tower only): the same names in the same order, the four ``state_encoder.rnn.*`` tensors with
+                        goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0, rnn_type: str = "GRU",
+                        rnn_layers: int = 1):
+    """``rnn_layers = L > 1`` (single tower only): layer ``l >= 1`` adds ``weight_ih_l{l}`` / ``weight_hh_l{l}`` ``[G, hidden]`` and
+    two ``[G]`` biases behind every other tensor.  ``rnn_type="LSTM"`` (single tower only): the same names in the same order, the four ``state_encoder.rnn.*`` tensors with
     ``4 * hidden`` rows (gate order i, f, g, o).  ``fusion=1`` (zero-shot dual-encoder policy): the goal-embedding / compressor / combiner tensors have zero
     elements and the GRU reads the ``in_channels``-wide fused embedding.  ``dual=1``: RGB + depth streams (25 tensors,
     GRU input 2 * comb_out * spatial^2).  ``goal_in > 0`` (PointNav): 18 tensors, ``embed_goal.{weight,bias}`` in place
     of ``embed_class.weight``; ``num_goals`` is ignored.  ``prev_action_dims = E > 0``: ``weight_ih_l0`` is ``[3 * hidden,
     flat + E]`` and ``prev_action_embedder.fc.weight`` ``[num_actions + prev_action_null, E]`` is the last tensor."""
+    if rnn_layers != 1:
+        assert 1 <= rnn_layers <= 4 and not fusion and not dual, "1..4 recurrent layers; the two-tower and zero-shot agents keep one"
+        out = policy_param_shapes(in_channels, spatial, hidden, goal_dims, num_goals, num_actions, compress_hid, compress_out,
+                                  comb_hid, comb_out, goal_in=goal_in, prev_action_dims=prev_action_dims,
+                                  prev_action_null=prev_action_null, rnn_type=rnn_type)
+        G = out[POLICY_RNN_TENSORS[1]][0]
+        for l in range(1, rnn_layers):
+            wih, whh, bih, bhh = policy_rnn_layer_tensors(l)
+            out[wih] = out[whh] = (G, hidden)
+            out[bih] = out[bhh] = (G,)
+        return out
     if rnn_type != "GRU":
         assert rnn_type == "LSTM", rnn_type
         assert not fusion and not dual, "the two-tower and zero-shot agents keep the GRU"
@@ -445,12 +470,13 @@ def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int =
 def policy_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, torch.Tensor]":
     """Synthetic policy parameters; RoboTHOR default = 3,480,775 params (PointNav, ``goal_in=2, num_actions=4``:
     3,479,461; ``embed_goal.weight`` ~ N(0, 1/goal_in), the generic fan-in rule below).  ``rnn_type="LSTM"``: the recurrent
-    weights by the same rule, both recurrent biases zero ([U] RNNStateEncoder.init_weights: ``nn.init.constant_(param, 0)``)."""
+    weights by the same rule, both recurrent biases zero ([U] RNNStateEncoder.init_weights: ``nn.init.constant_(param, 0)``).
+    ``rnn_layers=L``: the upper layers' tensors by the rules of layer 0's."""
     shapes = policy_param_shapes(**kw)
     lstm = kw.get("rnn_type", "GRU") == "LSTM"
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     for k, shp in shapes.items():
-        if int(np.prod(shp)) == 0 or (lstm and k in POLICY_RNN_TENSORS[2:]):
+        if int(np.prod(shp)) == 0 or (lstm and k.startswith("state_encoder.rnn.bias_")):
             sd[k] = torch.zeros(shp)
         elif k.endswith("bias") or "bias_" in k:
             sd[k] = _normal(seed, k, shp, 0.02)

@@ -458,7 +458,28 @@ int ec_policy_create(ec_policy_t** out, const ec_policy_cfg* cfg);
 enum { EC_RNN_GRU = 0, EC_RNN_LSTM = 1 };
 int ec_policy_create_rnn(ec_policy_t** out, const ec_policy_cfg* cfg, int rnn_type);
 int ec_policy_rnn_type(const ec_policy_t* h);          /* EC_RNN_GRU | EC_RNN_LSTM (-1: NULL handle) */
-int ec_policy_state_width(const ec_policy_t* h);       /* H (GRU) or 2H (LSTM): the width of a row of h0 / h_final / dh_final */
+int ec_policy_state_width(const ec_policy_t* h);       /* L * (H (GRU) or 2H (LSTM)): the width of a row of h0 / h_final / dh_final */
+/* Recurrent depth ([U] allenact RNNStateEncoder(.., num_layers = L, ..); the published Habitat DD-PPO configs say
+ * num_recurrent_layers: 2): torch.nn.GRU / torch.nn.LSTM with num_layers = L (1..EC_RNN_MAX_LAYERS) and dropout = 0 under the
+ * episode mask.  Layer 0 is the single-layer handle's; layer l >= 1 at step t takes x = h^{l-1}_t against weight_ih_l{l} [G,H],
+ * weight_hh_l{l} [G,H], bias_ih_l{l} [G], bias_hh_l{l} [G] (G = 3H | 4H).  The mask multiplies the previous state (h, and c on an
+ * LSTM handle) of EVERY layer and never a layer's input; the heads read the top layer's h.
+ *   ec_policy_create_rnn(out, cfg, t) == ec_policy_create_rnn_layers(out, cfg, t, 1): plan, workspace sizes, launches and bits of
+ *   that handle are unchanged.  EC_ERR_ARG outside 1..EC_RNN_MAX_LAYERS; EC_ERR_UNSUPPORTED for num_layers > 1 with dual = 1 or
+ *   fusion = 1.
+ * State: an actor's state stays ONE row of width L * SW (SW = H | 2H), layer-major -- [h^0 | h^1 | ...] on a GRU handle,
+ *   [h^0 | c^0 | h^1 | c^1 | ...] on an LSTM handle; layer l's state is the slice at l * SW.  Every h0, h_final and dh_final of the
+ *   entry points below is f32 [N, L*SW] where the comments say [N,H]; every entry point keeps its signature.
+ * Tensors: the upper layers' four tensors each END the flat order (layer 1, 2, 3; weight_ih, weight_hh, bias_ih, bias_hh), behind
+ *   prev_action_embedder.fc.weight where that exists: every tensor of the single-layer handle keeps its index and offset.
+ * Act step (T = 1 inference): ONE launch per layer (rnn_stack.hip: input projection, recurrent projection and cell together;
+ *   EC_RNN_STACK=0 in the environment: the general route); it needs h_final != h0, else -- and for every T > 1 pass -- the layers
+ *   run one after the other, each with the single-layer step kernels and one GEMM for the next layer's input projection.  The
+ *   backward runs from the top layer down.  No float atomics on any route of a handle with L > 1: two learn passes give equal
+ *   bits, and an actor's result does not depend on how the actors are sliced. */
+#define EC_RNN_MAX_LAYERS 4
+int ec_policy_create_rnn_layers(ec_policy_t** out, const ec_policy_cfg* cfg, int rnn_type, int num_layers);
+int ec_policy_rnn_layers(const ec_policy_t* h);        /* L (0: NULL handle) */
 /* fusion == 1 only: borrow the device goal table f32 [num_goals, in_channels] (e.g. ec_text_forward over the goal
  * prompts, L2-normalised); frozen -- it receives no gradient. */
 int ec_policy_set_goal_table(ec_policy_t* h, const float* table);
@@ -560,6 +581,22 @@ int ec_lstm_step_fwd(const float* a_in, const float* whh, const float* bhh, cons
 int ec_lstm_step_bwd(const float* dhs, const float* gates, const float* c, const float* c_prev, const float* mask,
                      const float* whh, const float* whhT, const float* da_next, const float* mask_next, float* carry_h,
                      float* carry_c, float* da, int N, int H, ec_stream_t stream);
+
+/* One act step of an UPPER layer alone (rnn_stack.hip; what the act step of a multi-layer handle launches per layer l >= 1): the
+ * input projection, the recurrent projection and the cell in one launch.  rnn_type EC_RNN_GRU | EC_RNN_LSTM; G = 3H | 4H.
+ *   x f32, rows of pitch ld_x >= H floats: the layer's input (the state of the layer below);  wih, whh f32 [G,H];  bih, bhh [G];
+ *   state_prev, rows of pitch ld_prev: h of actor n at state_prev + n*ld_prev (GRU: ld_prev >= H), and on an LSTM c at + H
+ *   (ld_prev >= 2H);  mask f32 [N] multiplies the previous state, never x.
+ *   h_out (pitch ld_h >= H), c_out (pitch ld_c >= H; LSTM only, ignored on a GRU), h_out2 (pitch ld_h2 >= H) or NULL: a second
+ *   copy of h.  Rows past N are never written.
+ * Alignment: x, wih, whh, state_prev 16-byte aligned and ld_x, ld_prev multiples of 4 floats (EC_ERR_ARG / EC_ERR_SHAPE).
+ * Non-overlap: no output element may be an element of x or of the previous state of ANY actor (other workgroups still read
+ *   those rows); slices of one state row at different column offsets do not overlap.
+ * H % 32 == 0 and (H % 256 == 0 or H <= 608), else EC_ERR_SHAPE.  Wave partials are summed in a fixed order, the x part before
+ * the h part: equal bits at every pitch and every actor slicing.  No atomics. */
+int ec_rnn_stack_step_fwd(int rnn_type, const float* x, long ld_x, const float* wih, const float* whh, const float* bih,
+                          const float* bhh, const float* state_prev, long ld_prev, const float* mask, float* h_out, long ld_h,
+                          float* c_out, long ld_c, float* h_out2, long ld_h2, int N, int H, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Rollout post-processing and the PPO update ([U] allenact onpolicy_sync:

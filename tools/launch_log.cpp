@@ -23,7 +23,7 @@
 //                                                   Bottleneck / BasicBlock tower; the torchvision towers have width 64) through
 //                                                   ec_rn50_forward / _u8 / _depth; `P <ec_rn50_num_ops> <ec_rn50_plan_hash>`
 //                                                   comes before its launches
-//   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse [dhf]
+//   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse [dhf [core]]
 //                                                   create + ec_policy_workspace_bytes + ec_policy_forward2 (goal_in > 0:
 //                                                   ec_policy_forward_vec) + destroy; mode 0 = EC_POLICY_INFER, 1 = _LEARN;
 //                                                   reuse 1: an EC_POLICY_INFER call builds the tables first (`B <rc>` ends
@@ -31,6 +31,8 @@
 //                                                   same workspace.  mode 2: the learn pass -- the EC_POLICY_LEARN forward
 //                                                   (`F <rc>` ends its launches), then ec_policy_backward2 in the same
 //                                                   workspace; dhf 1 (mode 2 only): with a dh_final tensor, else NULL.
+//                                                   core = 10 * rnn_type + num_layers (2: a two-layer GRU, 12: a two-layer
+//                                                   LSTM): ec_policy_create_rnn_layers instead of ec_policy_create.
 //                                                   `W <bytes>` is the workspace size, `D <bytes>` a device-to-device
 //                                                   hipMemcpyAsync (policy commands only)
 // Output: `K <kernel>` per registered kernel, then per command `C <command>`, one `L <kernel>|<grid>|<block>|<lds>` per
@@ -199,7 +201,7 @@ static int run_tower(const std::string& kind, const int* v, const std::string& i
     return rc;
 }
 
-// v: the 13 ec_policy_cfg fields, then T, N, mode, bf16, reuse, dhf
+// v: the 13 ec_policy_cfg fields, then T, N, mode, bf16, reuse, dhf, core
 static int run_policy(const int* v) {
     typedef void* P;
     const int T = v[13], N = v[14], mode = v[15], bf16 = v[16], reuse = v[17], dhf = v[18], goal_in = v[12], dual = v[11];
@@ -208,7 +210,8 @@ static int run_policy(const int* v) {
     void* h = nullptr;
     int cfg[32] = {0};                                  // the 13 fields, zero-filled behind them (fields a later header adds read 0)
     memcpy(cfg, v, 13 * sizeof(int));
-    int rc = sym<int (*)(P*, const int*)>("ec_policy_create")(&h, cfg);
+    int rc = v[19] ? sym<int (*)(P*, const int*, int, int)>("ec_policy_create_rnn_layers")(&h, cfg, v[19] / 10, v[19] % 10)
+                   : sym<int (*)(P*, const int*)>("ec_policy_create")(&h, cfg);
     if (rc) return rc;
     const size_t ws = sym<size_t (*)(P, int, int, int)>("ec_policy_workspace_bytes")(h, T, N, mode != 0);
     printf("W %zu\n", ws);
@@ -252,15 +255,15 @@ int main(int argc, char** argv) {
         if (!(ss >> cmd)) continue;
         line[strcspn(line, "\n")] = 0;
         printf("C %s\n", line);
-        int v[19] = {0}, n = 0, rc = -100;
+        int v[20] = {0}, n = 0, rc = -100;
         std::string kind;
         if (cmd == "trunk" || cmd == "tower") ss >> kind;
-        const int nmax = cmd == "policy" ? 19 : cmd == "tower" ? 9 : 10;
+        const int nmax = cmd == "policy" ? 20 : cmd == "tower" ? 9 : 10;
         while (n < nmax && ss >> v[n]) ++n;
         std::string input;
         if (cmd == "tower" && n == 9 && ss >> input) {
             rc = run_tower(kind, v, input);
-        } else if (cmd == "policy" && (n == 18 || n == 19)) {
+        } else if (cmd == "policy" && n >= 18 && n <= 20) {
             rc = run_policy(v);
         } else if (cmd == "conv" && n == 10) {
             const P r = v[8] ? resb : nullptr;
