@@ -179,6 +179,16 @@ SIGNATURES = {
     "ec_lstm_step_fwd": (c_int, [c_void_p] * 4 + [C.c_long, c_void_p, c_void_p, C.c_long, c_void_p, C.c_long, c_void_p, c_int, c_int,
                                  c_void_p]),
     "ec_lstm_step_bwd": (c_int, [c_void_p] * 12 + [c_int, c_int, c_void_p]),
+    # the pooled-embedding net (habitat-lab's PointNavResNetNet over one pooled CLIP vector per frame) and its two act-step kernels alone
+    "ec_policy_create_pooled": (c_int, [C.POINTER(c_void_p), c_void_p]),
+    "ec_policy_is_pooled": (c_int, [c_void_p]),
+    "ec_policy_forward_pooled": (c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 3),
+    "ec_policy_act_pooled": (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
+                             + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_pooled_fc_act": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
+    "ec_pooled_step0_fwd": (c_int, [c_int, c_void_p, C.c_long] + [c_void_p] * 7 + [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                    c_int, c_void_p, C.c_long, c_void_p, c_void_p, C.c_long, c_void_p, C.c_long, c_void_p, C.c_long, c_int,
+                                    c_int, c_void_p]),
 }
 
 RNN_TYPES = {"GRU": 0, "LSTM": 1}      # include/ec_amd.h EC_RNN_GRU / EC_RNN_LSTM
@@ -188,6 +198,14 @@ class PolicyCfg(C.Structure):
     _fields_ = [(n, c_int) for n in ("in_channels", "spatial", "hidden", "goal_dims", "num_goals", "num_actions",
                                      "compress_hid", "compress_out", "comb_hid", "comb_out", "fusion", "dual", "goal_in",
                                      "prev_action_dims", "prev_action_null")]
+
+
+class PooledCfg(C.Structure):
+    """``ec_pooled_cfg`` (include/ec_amd.h)."""
+    _fields_ = [("embed_in", c_int), ("hidden", c_int), ("embed_dims", c_int), ("num_goals", c_int), ("num_sensors", c_int),
+                ("sensor_in", c_int * 3), ("num_actions", c_int), ("prev_action_dims", c_int), ("prev_action_null", c_int),
+                ("rnn_type", c_int), ("num_layers", c_int)]
+
 
 _lib = None
 

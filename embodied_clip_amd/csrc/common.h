@@ -233,6 +233,8 @@ struct EcConfig {
     int dw_transposed;    // EC_DW_TRANSPOSED (1)   GRU weight-gradient GEMMs on transposed (K-contiguous) operands
     int rnn_stack;        // EC_RNN_STACK     (1)   act step of a multi-layer recurrent core: one launch per upper layer (rnn_stack.hip); 0: the general
                           //                        layer-by-layer route.  NOT part of ec_config_hash(): no single-layer plan reads it
+    int pooled_act;       // EC_POOLED_ACT    (1)   act step of a pooled-embedding handle: pooled_fc_act_kernel + pooled_step0_kernel (pooled_net.hip);
+                          //                        0: the general route.  NOT part of ec_config_hash(): no other handle's plan reads it
     // --- ViT / text GEMMs (ec_gemm_bf16_ln8).  NOT part of ec_config_hash(): the profile summaries under profiles/ are keyed by the hash as it was ---
     int vit_wide;         // EC_VIT_WIDE      (1)   0: 128-wide tiles only, 2: 256-wide wherever N allows
     int vit_bm192;        // EC_VIT_BM192     (1)   0: no 192-row tiles
@@ -285,7 +287,8 @@ __device__ __forceinline__ int ec_pa_index(const long long* __restrict__ prev, c
 // prev_action.hip's instance, which adds the previous action's row of the table PT in the fold, behind the bias (PA).  The PA = false
 // instantiation is gi_act_kernel's arithmetic as it was.
 struct ec_gi_act_pa { const float* pt; const long long* prev; const float* masks; int null_token, A; };
-template <int NW, bool PA>
+// RELU (pooled_net.hip's instance, PA = false only): max(. + bias, 0) is stored -- visual_fc of the pooled-embedding net.
+template <int NW, bool PA, bool RELU = false>
 __device__ __forceinline__ void ec_gi_act_body(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
                                                float* __restrict__ gi, int N, int K, int NO, const ec_gi_act_pa pax) {
     __shared__ float part[NW][32][33];
@@ -327,7 +330,10 @@ __device__ __forceinline__ void ec_gi_act_body(const float* __restrict__ x, cons
 #pragma unroll
         for (int w2 = 1; w2 < NW; ++w2) v += part[w2][row][col];
         if (!PA) {
-            if (n0 + row < N) gi[(long)(n0 + row) * NO + j0 + col] = v + (bias ? bias[j0 + col] : 0.f);
+            if (n0 + row < N) {
+                const float o = v + (bias ? bias[j0 + col] : 0.f);
+                gi[(long)(n0 + row) * NO + j0 + col] = RELU ? fmaxf(o, 0.f) : o;
+            }
         } else if (n0 + row < N) {
             float o = v + (bias ? bias[j0 + col] : 0.f);
             const int r = ec_pa_index(pax.prev, pax.masks, n0 + row, pax.null_token, pax.A);
@@ -379,6 +385,25 @@ struct ec_rnn_stack_args {
     int N, H;
 };
 void ec_rnn_stack_launch(int lstm, const ec_rnn_stack_args& a, hipStream_t s);
+
+// pooled_net.hip: the pooled-embedding net's own launches for policy.hip (argument meanings: the kernels' headers).
+//   tables: SV [G, K] and sb [G] from the sensor blocks of weight_ih_l0 (row stride ld, sensor i's block at column col0 + i * ed)
+//   rows_add: gi[b] = (((gi[b] + sb) + gt[goal[b]]) + pt[row(b)]) + sum_k sv[:, k] sensors[b, k]; every part optional
+//   sensor_grads: from dSV [G, K] and dsb [G], dW_ih[:, blk_i] += dSV_i W_i^T + dsb b_i^T, dW_i += W_ih[:, blk_i]^T dSV_i,
+//   db_i += W_ih[:, blk_i]^T dsb -- one thread per output, ascending inner index
+struct ec_pooled_sensors { int ns, k[3], K, ed; const float* w[3]; const float* b[3]; float* dw[3]; float* db[3]; };
+struct ec_pooled_side {
+    const float* sb; const float* gt; const long long* goal; int num_goals;
+    const float* pt; const long long* prev; const float* masks; int null_token, A;
+    const float* sv; const float* sens; int K;
+};
+void ec_pooled_tables_launch(const float* wih, long ld, int col0, const ec_pooled_sensors& sn, float* sv, float* sb, int G, hipStream_t s);
+void ec_pooled_rows_add_launch(float* gi, const ec_pooled_side& sd, long B, int G, hipStream_t s);
+void ec_pooled_sensor_grads_launch(const float* wih, float* dwih, long ld, int col0, const ec_pooled_sensors& sn, const float* dsv,
+                                   const float* dsb, int G, hipStream_t s);
+void ec_pooled_frag_pack_launch(const float* w, float* wfrag, int N, int K, hipStream_t s);
+void ec_pooled_fc_act_launch(const float* e, const float* wfrag, const float* b, float* v, int N, int D, int H, hipStream_t s);
+void ec_pooled_step0_launch(int lstm, const ec_rnn_stack_args& a, const ec_pooled_side& sd, hipStream_t s);
 
 #define EC_CHECK_LAUNCH()                                  \
     do {                                                    \

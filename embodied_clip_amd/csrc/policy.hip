@@ -1507,6 +1507,16 @@ struct ec_policy {
     // bias_hh_l{l}: uoff / unum [l - 1][0..3], behind every other tensor of the flat order (indices nbase, nbase + 1, ...)
     int layers = 1, nbase = 0;
     size_t uoff[EC_RNN_MAX_LAYERS - 1][4] = {}, unum[EC_RNN_MAX_LAYERS - 1][4] = {};
+    // The pooled-embedding net (ec_policy_create_pooled).  Its plan is the fusion handle's -- no compressor, no combiner, the
+    // recurrent core reads a [T*N, in_channels] matrix -- with in_channels = hidden: that matrix is v = ReLU(visual_fc(e)).
+    // Tensors in front of weight_ih_l0, index into off / num: visual_fc weight, bias; the goal-id embedding; sensor i's weight, bias
+    struct Pooled {
+        bool on = false;
+        int D = 0, ed = 0, ids = 0, ns = 0, k[3] = {0, 0, 0}, K = 0;   // ids: 1 with a goal-id embedding; K = sum k
+        int npre = 0;                                                  // tensors in front of weight_ih_l0
+        size_t off[9] = {}, num[9] = {};
+        int side() const { return ed * (ids + ns); }                   // columns of weight_ih_l0 between v's and the previous action's
+    } pl;
     // EC_POLICY_INFER_REUSE bookkeeping: the key of the launch plan (make_plan) that built the weight-derived tables in a given
     // act workspace.  Which tables exist and where (E1, W1's planes in fragment order, the re-ordered weight_ih and its
     // fragment-order copy) are plan fields, and an inference plan is a function of exactly (handle, T, N, feature dtype): a
@@ -1641,7 +1651,9 @@ struct Geo {
     int S, M49;                   // pixels per frame; B * S rows through compressor and combiner (0 in fusion mode)
     int H, A, A1, C, cat;         // hidden size; actions, actions + critic; feature channels; compress_out + goal_dims
     int nstream, flat1, flat;     // encoder streams (2: dual RGB + depth); one stream's / the whole GRU input width
-    int E, R, ldw;                // previous-action embedding: width (0: none), table rows, weight_ih's row stride flat + E
+    int E, R, ldw;                // previous-action embedding: width (0: none), table rows, weight_ih's row stride flat + X + E
+    int X, pcol;                  // pooled-embedding net: the goal-id / sensor columns of weight_ih (0 elsewhere); the previous action's first column flat + X
+    bool pooled; int D, PK, PG;   // pooled-embedding net: embedding width, sensor floats per frame, goal-table rows
     int G, SW;                    // gate width 3H (GRU) | 4H (LSTM); state width H | 2H (an LSTM state row is [h | c])
     int L;                        // recurrent layers; a state row is [N, L * SW], layer l's state the slice at l * SW
 };
@@ -1670,6 +1682,11 @@ struct Ws {   // float offsets into the workspace
     // LSTM handle, its cell-state history; uh0: a GRU stack's initial states as dense [L][N, H] blocks (its step kernels take no pitch)
     size_t ugi[EC_RNN_MAX_LAYERS - 1], ugates[EC_RNN_MAX_LAYERS - 1], uhn[EC_RNN_MAX_LAYERS - 1], uhp[EC_RNN_MAX_LAYERS - 1],
            uhs[EC_RNN_MAX_LAYERS - 1], ucs[EC_RNN_MAX_LAYERS - 1], uh0;
+    // pooled-embedding net (all empty on every other handle).  Weight-derived, kept under EC_POLICY_INFER_REUSE: the goal-id table
+    // GT [PG, G], SV [G, K], sb [G], visual_fc's weight in fragment order (act route); the learn pass's copies of the goal ids and
+    // the sensor floats; the backward's dSV / dsb and the goal table's binned-sum scratch.  v [B, H] is the `x` area, dv `dx`, the
+    // dense copy of weight_ih[:, :H] `wihA` (inference) / `wihP` (learn pass), as on a handle with a previous-action embedding.
+    size_t gt, sv, sb, fcF, pgoal, psens, dsv, dsb, gts;
 };
 constexpr int GP_MAXY = 64;                   // row blocks of tn_small_part_kernel
 constexpr int HP_MAXY = 128;                  // row blocks of the wide heads' column sum
@@ -1679,6 +1696,7 @@ enum class Gi { act7, act8, split_parts, plain };                // GRU input pr
 enum class Wih { plain, perm_learn, perm_act };                  // weight_ih as stored / re-ordered per learn pass / per act-table build
 enum class Step { gemm_gates, fused32, fused16 };                // a recurrence step: GEMM + gate kernel / 32-tile / 16-tile fused kernel
 enum class Cell { gru, lstm };                                   // the recurrent cell (lstm.hip's kernels: always the 32-tile ones)
+enum { PL_FCW, PL_FCB, PL_GEMB, PL_SW0, PL_SB0 };                // ec_policy::Pooled::off / num (sensor i: PL_SW0 + 2 i, PL_SB0 + 2 i)
 
 struct Plan {
     Geo g;
@@ -1698,16 +1716,17 @@ struct Plan {
     Step step_fwd, step_bwd; size_t gru_lds;   // (gru_step_fwd_kernel's tiles)
     bool hs_direct;               // T == 1 inference: the new state goes straight to h_final, the heads read it there
     bool stack;                   // EC_RNN_STACK: act step of a multi-layer core, one launch per layer (rnn_stack.hip)
+    bool pact;                    // EC_POOLED_ACT: act step of a pooled-embedding handle on pooled_net.hip's two kernels (given h_final != h0)
     bool dw_t, dw1_planes;        // EC_DW_TRANSPOSED; EC_DW1_TR (dc1 then only exists as bf16 planes)
     int bwd3;                     // EC_GEMM_3PRODUCTS or 0 for the backward's large gradient GEMMs
     Ws w;
 };
 
-Ws layout(const ec_policy_cfg& c, const Geo& g, Cell cell, int parts, bool bwd) {
+Ws layout(const ec_policy_cfg& c, const Geo& g, Cell cell, int parts, bool bwd, bool pact) {
     const size_t B = g.B, M49 = g.M49, H = g.H, N = g.N, flat = g.flat, E1 = (size_t)c.num_goals * c.comb_hid, G = g.G;
     const bool lstm = cell == Cell::lstm;
     const size_t w1planes = c.fusion ? 0 : ((size_t)c.compress_hid * 3 * c.in_channels + 1) / 2;   // W1 as three bf16 planes
-    const size_t wih = c.fusion ? 0 : G * flat;                                                  // a re-ordered copy of weight_ih
+    const size_t wih = (c.fusion && !g.pooled) ? 0 : G * flat;                                   // a re-ordered / dense copy of weight_ih
     Ws w; size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += al(n * 4) / 4; return r; };
     auto take_if = [&](bool on, size_t n) { return take(on ? n : 0); };   // an area that is not needed: empty, at the running offset
@@ -1726,7 +1745,7 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, Cell cell, int parts, bool bwd) 
     w.hn = take(B * H); w.hp = take(B * H); w.hs = take(B * H);
     w.goal32 = take(B);
     w.w1p = take(w1planes);
-    w.wihA = take_if(!c.dual, wih); w.wihF = take_if(!c.dual, wih);
+    w.wihA = take_if(!c.dual, wih); w.wihF = take_if(!c.dual && !g.pooled, wih);
     w.w1pF = take(w1planes);
     // what only the learn pass and its backward need
     w.dhs = take_if(bwd, B * H);
@@ -1766,6 +1785,13 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, Cell cell, int parts, bool bwd) 
         w.ucs[l - 1] = take_if(on && lstm, B * H);
     }
     w.uh0 = take_if(g.L > 1 && !lstm, (size_t)g.L * N * H);
+    const bool pl = g.pooled, pids = pl && g.PG > 0, psn = pl && g.PK > 0;
+    w.gt = take_if(pids, (size_t)g.PG * G);
+    w.sv = take_if(psn, G * (size_t)g.PK); w.sb = take_if(psn, G);
+    w.fcF = take_if(pact && !bwd, H * (size_t)g.D);   // (at every T of an inference workspace: its size stays monotone in T)
+    w.pgoal = take_if(pids && bwd, 2 * B); w.psens = take_if(psn && bwd, B * (size_t)g.PK);
+    w.dsv = take_if(psn && bwd, G * (size_t)g.PK); w.dsb = take_if(psn && bwd, G);
+    w.gts = take_if(pids && bwd, pids ? ec_pa_grad_scratch_floats((long)B, g.G, g.PG) : 0);
     w.end = o;
     return w;
 }
@@ -1781,14 +1807,15 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     g.S = c.spatial * c.spatial; g.M49 = c.fusion ? 0 : g.B * g.S;
     g.H = c.hidden; g.A = c.num_actions; g.A1 = g.A + 1; g.C = c.in_channels; g.cat = c.compress_out + c.goal_dims;
     g.nstream = (c.dual && !c.fusion) ? 2 : 1; g.flat1 = c.comb_out * g.S; g.flat = c.fusion ? c.in_channels : g.nstream * g.flat1;
-    g.E = c.prev_action_dims; g.R = c.num_actions + c.prev_action_null; g.ldw = g.flat + g.E;   // (no route below depends on E)
+    g.pooled = h->pl.on; g.X = h->pl.side(); g.D = h->pl.D; g.PK = h->pl.K; g.PG = h->pl.ids ? c.num_goals : 0;
+    g.E = c.prev_action_dims; g.R = c.num_actions + c.prev_action_null; g.pcol = g.flat + g.X; g.ldw = g.pcol + g.E;   // (no route below depends on E)
     p.cell = h->rnn == EC_RNN_LSTM ? Cell::lstm : Cell::gru;
     g.G = (p.cell == Cell::lstm ? 4 : 3) * c.hidden; g.SW = (p.cell == Cell::lstm ? 2 : 1) * c.hidden;
     g.L = h->layers;
     const int B = g.B, S = g.S, M49 = g.M49, H = g.H, C = g.C, flat = g.flat;
     p.infer = mode != EC_POLICY_LEARN; p.feat_bf16 = feat_bf16; p.vec = c.goal_in > 0;
     p.wide = !p.infer && g.A1 > 8;
-    p.ordered = p.vec || p.wide || p.cell == Cell::lstm || g.L > 1;
+    p.ordered = p.vec || p.wide || p.cell == Cell::lstm || g.L > 1 || g.pooled;
     p.key = ec_policy::Built{T, N, feat_bf16 ? 1 : 0};
     // Act step: so few rows that the two long-K, small-M GEMMs (compressor conv 1, GRU input projection) run as ACT_PARTS K
     // slices whose partial matrices the consuming kernels fold in a fixed order (no float atomics: rollouts stay bit-reproducible)
@@ -1837,6 +1864,9 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     const bool step_ok_any = step_ok || p.cell == Cell::lstm;
     // a multi-layer core's act step: every layer one launch of the 32-tile geometry (a GRU whose fused step is off: the general route)
     p.stack = g.L > 1 && cfg.rnn_stack && p.infer && T == 1 && p.step_fwd == Step::fused32 && ec_lstm_hidden_ok(H);
+    // a pooled-embedding handle's act step: visual_fc on the gi_act geometry (K = D over 7 or 8 waves), then layer 0 in one launch
+    const bool pact_any = g.pooled && cfg.pooled_act && ec_lstm_hidden_ok(H) && (g.D % 56 == 0 || g.D % 64 == 0);   // (a handle that can take it)
+    p.pact = pact_any && p.infer && T == 1;
     // GRU input projection.  Act step with a handful of rows: one launch, K split over the waves of a workgroup and folded
     // in-kernel (gi_act_kernel); else split-K only as separate partial matrices folded by the step kernel
     const int gi_nw = (flat % 56 == 0) ? 7 : ((flat % 64 == 0) ? 8 : 0);
@@ -1852,7 +1882,7 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     // EC_DW1_TR (default 1): dW1 through the transpose-read kernel (dw_tn.hip), its partial tiles in the tail's partial sets
     p.dw1_planes = p.tail_bwd && cfg.dw1_tr && feat_bf16 && C % 256 == 0 && M49 >= 2048 &&
                    (size_t)ec_dw_tn_x3_splits(M49, C) * 128 * C <= (size_t)TB_MAX_WG * 4 * TB_PART;
-    p.w = layout(c, g, p.cell, p.act_parts, mode == EC_POLICY_LEARN);
+    p.w = layout(c, g, p.cell, p.act_parts, mode == EC_POLICY_LEARN, pact_any);
     return p;
 }
 
@@ -1887,6 +1917,18 @@ struct Ctx {
                      ws + w.ucs[l - 1], 1};
     }
     float* hs_top() const { return ws + (g.L > 1 ? w.uhs[g.L - 2] : w.hs); }   // the history the heads read
+    // the pooled-embedding net: tensor i in front of weight_ih_l0; the sensors' nn.Linear tensors (and, for a backward, their gradients)
+    const float* PW(int i) const { return params + h->pl.off[i]; }
+    ec_pooled_sensors pooled_sensors(float* grads) const {
+        const ec_policy::Pooled& q = h->pl;
+        ec_pooled_sensors sn{};
+        sn.ns = q.ns; sn.K = q.K; sn.ed = q.ed;
+        for (int i = 0; i < q.ns; ++i) {
+            sn.k[i] = q.k[i]; sn.w[i] = PW(PL_SW0 + 2 * i); sn.b[i] = PW(PL_SB0 + 2 * i);
+            if (grads) { sn.dw[i] = grads + q.off[PL_SW0 + 2 * i]; sn.db[i] = grads + q.off[PL_SB0 + 2 * i]; }
+        }
+        return sn;
+    }
     // ec_gemm_f32 without its extras (row-group bias, ReLU mask, row scale, split-K)
     int gemm(const void* A, const void* B, float* Cp, int M, int N, int K, long sam, long sak, long sbk, long sbn, int ldc, int flags = 0,
              const float* bias = nullptr) const {
@@ -1904,11 +1946,44 @@ struct Fwd : Ctx {
     // weight_ih[:, :flat] where the GEMMs of the routes that keep the parameter's column order read it: the parameter itself, or on a
     // handle with a previous-action embedding (row stride flat + E) its dense copy -- in the learn pass's / the act tables' area
     // of the re-ordered weight, which those routes leave unused
-    const float* wih_plain() const { return g.E ? ws + (p.infer ? w.wihA : w.wihP) : W(P_WIH); }
+    const float* wih_plain() const { return g.ldw != g.flat ? ws + (p.infer ? w.wihA : w.wihP) : W(P_WIH); }
     // previous-action embedding: the table (with the other weight-derived tables) and, for a backward, the indices
     void prev_action_tables() {
-        if (!reuse) ec_pa_table_launch(W(P_PAE), W(P_WIH), g.ldw, g.flat, ws + w.pt, g.R, g.G, g.E, s);
+        if (!reuse) ec_pa_table_launch(W(P_PAE), W(P_WIH), g.ldw, g.pcol, ws + w.pt, g.R, g.G, g.E, s);
         if (!p.infer) (void)hipMemcpyAsync(ws + w.paidx, prev, (size_t)g.B * 8, hipMemcpyDeviceToDevice, s);
+    }
+
+    // ---- the pooled-embedding net (pooled_net.hip's kernels; the tables of prev_action.hip) ----
+    ec_pooled_side side{};           // what layer 0's input projection adds per frame (pooled_front fills it)
+    bool pact = false;               // this call runs the act route (p.pact and a state row of its own to write)
+    float* wih_dense() const { return ws + (p.infer ? w.wihA : w.wihP); }
+    // The weight-derived tables (unless reused), the learn pass's copies of the side inputs, v = ReLU(visual_fc(e)) into the `x`
+    // area and -- on the general route -- the input projection with the table rows added.  The act route leaves the projection to
+    // pooled_step0_kernel.
+    int pooled_front(const float* embed, const long long* goal, const float* sens) {
+        const ec_policy::Pooled& q = h->pl;
+        const int B = g.B, H = g.H, GW = g.G;
+        if (!reuse) {
+            ec_pa_rows_copy_launch(W(P_WIH), g.ldw, wih_dense(), H, GW, H, 0, s);
+            if (q.ids) ec_pa_table_launch(PW(PL_GEMB), W(P_WIH), g.ldw, H, ws + w.gt, g.PG, GW, q.ed, s);
+            if (q.ns) ec_pooled_tables_launch(W(P_WIH), g.ldw, H + q.ids * q.ed, pooled_sensors(nullptr), ws + w.sv, ws + w.sb, GW, s);
+            if (p.pact) ec_pooled_frag_pack_launch(PW(PL_FCW), ws + w.fcF, H, q.D, s);
+        }
+        if (g.E) prev_action_tables();
+        if (!p.infer) {
+            if (q.ids) (void)hipMemcpyAsync(ws + w.pgoal, goal, (size_t)B * 8, hipMemcpyDeviceToDevice, s);
+            if (q.ns) (void)hipMemcpyAsync(ws + w.psens, sens, (size_t)B * q.K * 4, hipMemcpyDeviceToDevice, s);
+        }
+        side = ec_pooled_side{q.ns ? ws + w.sb : nullptr, q.ids ? ws + w.gt : nullptr, goal, g.PG, g.E ? ws + w.pt : nullptr, prev, masks_all,
+                              c.prev_action_null, c.num_actions, q.ns ? ws + w.sv : nullptr, sens, q.K};
+        if (pact) {
+            ec_pooled_fc_act_launch(embed, ws + w.fcF, PW(PL_FCB), ws + w.x, B, q.D, H, s);
+            return EC_OK;
+        }
+        RC(gemm(embed, PW(PL_FCW), ws + w.x, B, H, q.D, q.D, 1, 1, q.D, H, EC_GEMM_RELU, PW(PL_FCB)));
+        RC(gemm(ws + w.x, wih_dense(), ws + w.gi, B, GW, H, H, 1, 1, H, GW, 0, W(P_BIH)));
+        ec_pooled_rows_add_launch(ws + w.gi, side, (long)B, GW, s);
+        return EC_OK;
     }
 
     // coordinate goals: this call's per-frame bias rows (and, for a backward, the goal vectors and embeddings it will need)
@@ -2097,6 +2172,38 @@ struct Fwd : Ctx {
         return EC_OK;
     }
 
+    // the act step's upper layers, one rnn_stack.hip launch each: layer l reads layer l - 1 out of the new state rows
+    void stack_upper_layers(const float* h0, const float* masks, float* h_final) {
+        const int L = g.L, N = g.N, H = g.H, SW = g.SW;
+        const long ld_s = (long)L * SW;
+        const bool lstm = p.cell == Cell::lstm;
+        for (int l = 1; l < L; ++l) {
+            ec_rnn_stack_args a{};
+            a.x = h_final + (size_t)(l - 1) * SW; a.ld_x = ld_s;
+            a.wih = UW(l, 0); a.whh = UW(l, 1); a.bih = UW(l, 2); a.bhh = UW(l, 3);
+            a.hprev = h0 + (size_t)l * SW; a.cprev = lstm ? a.hprev + H : nullptr; a.ld_prev = ld_s; a.mask = masks;
+            a.hout = h_final + (size_t)l * SW; a.ld_h = ld_s; a.cout = lstm ? a.hout + H : nullptr; a.ld_c = ld_s;
+            a.hout2 = l == L - 1 ? hs_top() : nullptr; a.ld_h2 = H;
+            a.gi_parts = 1; a.N = N; a.H = H;
+            ec_rnn_stack_launch(lstm ? 1 : 0, a, s);
+        }
+    }
+    // A pooled-embedding handle's act route: layer 0 in one launch (both projections, the table rows, the cell; states at the row
+    // pitch, with one layer also a dense h for the heads), then the upper layers as above
+    void pooled_act_recurrence(const float* h0, const float* masks, float* h_final) {
+        const int L = g.L, H = g.H;
+        const long ld_s = (long)L * g.SW;
+        const bool lstm = p.cell == Cell::lstm;
+        ec_rnn_stack_args a{};
+        a.x = ws + w.x; a.ld_x = H; a.wih = wih_dense(); a.whh = W(P_WHH); a.bih = W(P_BIH); a.bhh = W(P_BHH);
+        a.hprev = h0; a.cprev = lstm ? h0 + H : nullptr; a.ld_prev = ld_s; a.mask = masks;
+        a.hout = h_final; a.ld_h = ld_s; a.cout = lstm ? h_final + H : nullptr; a.ld_c = ld_s;
+        a.hout2 = L == 1 ? ws + w.hs : nullptr; a.ld_h2 = H;
+        a.gi_parts = 1; a.N = g.N; a.H = H;
+        ec_pooled_step0_launch(lstm ? 1 : 0, a, side, s);
+        stack_upper_layers(h0, masks, h_final);
+    }
+
     // A multi-layer core (g.L > 1).  h0 / h_final: [N, L * SW] rows, layer l's state the slice at l * SW.
     //   * act step (p.stack, a state row of its own to write): layer 0's step with both states at the row pitch (an LSTM: lstm.hip's
     //     kernel; a GRU: rnn_stack.hip's with the projection as given), then ONE rnn_stack.hip launch per upper layer, which reads
@@ -2118,16 +2225,7 @@ struct Fwd : Ctx {
                 a.gi = lay.gi; a.gi_parts = lay.gi_fold; a.gi_pstride = (long)B * g.G; a.N = N; a.H = H;
                 ec_rnn_stack_launch(0, a, s);
             }
-            for (int l = 1; l < L; ++l) {
-                ec_rnn_stack_args a{};
-                a.x = h_final + (size_t)(l - 1) * SW; a.ld_x = ld_s;
-                a.wih = UW(l, 0); a.whh = UW(l, 1); a.bih = UW(l, 2); a.bhh = UW(l, 3);
-                a.hprev = h0 + (size_t)l * SW; a.cprev = lstm ? a.hprev + H : nullptr; a.ld_prev = ld_s; a.mask = masks;
-                a.hout = h_final + (size_t)l * SW; a.ld_h = ld_s; a.cout = lstm ? a.hout + H : nullptr; a.ld_c = ld_s;
-                a.hout2 = l == L - 1 ? hs_top() : nullptr; a.ld_h2 = H;
-                a.gi_parts = 1; a.N = N; a.H = H;
-                ec_rnn_stack_launch(lstm ? 1 : 0, a, s);
-            }
+            stack_upper_layers(h0, masks, h_final);
             return EC_OK;
         }
         const float* below = nullptr;
@@ -2157,9 +2255,14 @@ struct Fwd : Ctx {
         } else if (p.wide) {    // learn pass: both heads as one [A + 1, H] table (kept for the backward), one GEMM with the bias fused
             ec_heads_pack_launch(W(P_WA), W(P_BA), W(P_WC), W(P_BC), ws + w.hW, A, H, s);
             RC(gemm(hs, ws + w.hW, hv, B, A1, H, H, 1, 1, H, A1, 0, ws + w.hW + (size_t)A1 * H));
-        } else if (wide) {      // ec_policy_act_ex: heads and selection in one launch (wide_actions.hip), no workspace of its own
+        } else if (wide || g.pooled) {
+            // ec_policy_act_ex: heads and selection in one launch (wide_actions.hip), no workspace of its own.  A pooled-embedding
+            // handle's inference forward takes the same launch without a selection: a row's logits then do not depend on how the
+            // actors are sliced, and the act step equals the forward bit for bit
+            const ForceArgs none{};
+            const ForceArgs* fa = wide ? wide : &none;
             RC(ec_heads_wide_launch(hs, W(P_WA), W(P_BA), W(P_WC), W(P_BC), hv, (long)B, H, A, smp.actions, smp.logp, smp.values, smp.greedy,
-                                    smp.seed, smp.step, smp.first_actor, wide->expert, wide->mask, wide->p, s));
+                                    smp.seed, smp.step, smp.first_actor, fa->expert, fa->mask, fa->p, s));
         } else {
             RC(gemm(hs, W(P_WA), hv, B, A, H, H, 1, 1, H, A1, 0, W(P_BA)));
             RC(gemm(hs, W(P_WC), hv + A, B, 1, H, H, 1, 1, H, A1, 0, W(P_BC)));
@@ -2184,21 +2287,43 @@ bool tables_reusable(const ec_policy* h, const void* workspace, const Plan& p, i
     return false;
 }
 
+struct PooledIn { const float* sensors; };      // the pooled-embedding net's entry points: feat = the embedding rows, and the sensor floats
+
 int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16, const int64_t* goal,
                         const float* goal_vec, const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int mode, float* hv,
                         float* h_final, const SampleArgs& smp, ec_stream_t stream, const ForceArgs* wide = nullptr,
-                        const int64_t* prev_actions = nullptr, bool pa_entry = false) {
+                        const int64_t* prev_actions = nullptr, bool pa_entry = false, const PooledIn* pin = nullptr) {
     if (!h || !params || !feat || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
+    if ((pin != nullptr) != h->pl.on) return EC_ERR_ARG;          // the pooled-embedding net has entry points of its own
+    if (pin) {
+        // a NULL argument matches a part the handle does not have, and the reverse
+        if ((goal != nullptr) != (h->pl.ids != 0) || (pin->sensors != nullptr) != (h->pl.ns > 0) ||
+            (prev_actions != nullptr) != (h->c.prev_action_dims > 0) || goal_vec || feat2 || feat_bf16)
+            return EC_ERR_ARG;
+        if (((uintptr_t)feat & 15) != 0) return EC_ERR_ARG;
+    } else {
     // previous-action embedding: the _pa entry points on such a handle, with the actions; every other pairing is refused
     if (pa_entry != (h->c.prev_action_dims > 0) || (pa_entry && !prev_actions)) return EC_ERR_ARG;
     if (h->c.goal_in > 0 ? (!goal_vec || goal) : (!goal || goal_vec)) return EC_ERR_ARG;   // the entry point of the handle's goal type
     if (h->c.dual && !feat2) return EC_ERR_ARG;
+    }
     if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
     if (mode < 0 || mode > EC_POLICY_INFER_REUSE) return EC_ERR_ARG;
     const Plan p = make_plan(h, T, N, mode, feat_bf16 != 0);
     if (ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
     Fwd f(h, p, params, workspace, stream);
     f.reuse = tables_reusable(h, workspace, p, mode);
+    if (pin) {
+        f.prev = (const long long*)prev_actions; f.masks_all = masks;
+        f.pact = p.pact && h_final && h_final != h0;
+        RC(f.pooled_front((const float*)feat, (const long long*)goal, pin->sensors));
+        if (f.pact) {
+            f.pooled_act_recurrence(h0, masks, h_final);
+            RC(f.heads(f.hs_top(), hv, nullptr, smp, wide));
+            EC_CHECK_LAUNCH();
+            return EC_OK;
+        }
+    } else {
     if (p.vec) RC(f.goal_rows(goal_vec));
     else RC(f.goal_and_fusion(feat, goal));
     if (!h->c.fusion)
@@ -2206,6 +2331,7 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
             RC(f.encoder_stream(sidx, sidx ? feat2 : feat));
     if (p.g.E) { f.prev = (const long long*)prev_actions; f.masks_all = masks; f.prev_action_tables(); }
     RC(f.input_projection());
+    }
     const bool lstm = p.cell == Cell::lstm;   // (the heads read the dense history; recurrence_lstm leaves the [h | c] rows in h_final)
     float* hs = (!lstm && p.hs_direct && h_final && h_final != h0) ? h_final : f.ws + p.w.hs;
     if (p.g.L > 1) {       // a multi-layer core leaves every layer's state in h_final itself; the heads read the top layer's history
@@ -2404,7 +2530,7 @@ struct Bwd : Ctx {
             RC(tn_gru(ws + w.dgi, ws + w.st[0].x4, ws + w.gwihP, GW, flat, B));
             hipLaunchKernelGGL(permute_row_kernel, dim3((unsigned)(GW)), dim3(256), flat * sizeof(float), s, ws + w.gwihP,
                                G(P_WIH), g.S, c.comb_out, 1, g.ldw);
-        } else if (g.E) {                 // the dense gradient, then added back onto the parameter's rows (stride flat + E)
+        } else if (g.ldw != flat) {       // the dense gradient, then added back onto the parameter's rows (stride flat + E; the pooled net's: flat + X + E)
             (void)hipMemsetAsync(ws + w.gwihP, 0, (size_t)GW * flat * 4, s);
             RC(tn_gru(ws + w.dgi, ws + w.x, ws + w.gwihP, GW, flat, B));
             ec_pa_rows_copy_launch(ws + w.gwihP, flat, G(P_WIH), g.ldw, GW, flat, 1, s);
@@ -2415,7 +2541,40 @@ struct Bwd : Ctx {
         // previous-action embedding: its gradient and columns flat.. of weight_ih's (inside the recurrent section: before the event)
         if (g.E)
             ec_pa_grad_launch(ws + w.dgi, (const long long*)(ws + w.paidx), masks_all, c.prev_action_null, c.num_actions, W(P_PAE), W(P_WIH),
-                              g.ldw, flat, G(P_PAE), G(P_WIH), ws + w.pas, (long)B, GW, g.E, s);
+                              g.ldw, g.pcol, G(P_PAE), G(P_WIH), ws + w.pas, (long)B, GW, g.E, s);
+        return EC_OK;
+    }
+
+    // ---- the pooled-embedding net ----
+    // From layer 0's dgi: the goal-id table's gradient as prev_action.hip's binned ordered sum (the same problem with no null row and
+    // no mask), chained to the embedding and to its columns of weight_ih; dSV = dgi^T s by K slices folded in order and dsb = the
+    // ordered column sum, chained by pooled_net.hip's two launches to the sensors' columns of weight_ih and to W_i, b_i.  Everything
+    // that lands inside weight_ih's gradient is done here, before the recurrent section is declared final.
+    int pooled_side_grads() {
+        const ec_policy::Pooled& q = h->pl;
+        const int B = g.B, GW = g.G;
+        if (q.ids)
+            ec_pa_grad_launch(ws + w.dgi, (const long long*)(ws + w.pgoal), nullptr, 0, g.PG, PW(PL_GEMB), W(P_WIH), g.ldw, g.flat,
+                              grads + q.off[PL_GEMB], G(P_WIH), ws + w.gts, (long)B, GW, q.ed, s);
+        if (q.ns) {
+            (void)hipMemsetAsync(ws + w.dsv, 0, (size_t)GW * q.K * 4, s);
+            (void)hipMemsetAsync(ws + w.dsb, 0, (size_t)GW * 4, s);
+            RC(tn(ws + w.dgi, GW, ws + w.psens, q.K, 0, ws + w.dsv, GW, q.K, B, q.K));
+            colsum(ws + w.dgi, ws + w.dsb, B, GW, GW);
+            ec_pooled_sensor_grads_launch(W(P_WIH), G(P_WIH), g.ldw, g.flat + q.ids * q.ed, pooled_sensors(grads), ws + w.dsv, ws + w.dsb, GW, s);
+        }
+        return EC_OK;
+    }
+    // dv = (dgi W_ih[:, :H]) where v > 0 (the forward's dense copy; v is the `x` area), then visual_fc's two gradients over the
+    // embedding rows.  dv occupies the partial-matrix area: the weight gradient walks K in one piece (no float atomics).
+    int pooled_fc_grads(const float* embed) {
+        const ec_policy::Pooled& q = h->pl;
+        const int B = g.B, H = g.H, GW = g.G;
+        RC(ec_gemm_f32(ws + w.dgi, ws + w.wihP, ws + w.dx, B, H, GW, GW, 1, H, 1, H, p.bwd3, nullptr, nullptr, nullptr, 0, ws + w.x, nullptr, 1,
+                       stream));
+        parts_ok = false;
+        RC(tn(ws + w.dx, H, embed, q.D, 0, grads + q.off[PL_FCW], H, q.D, B, q.D));
+        colsum(ws + w.dx, grads + q.off[PL_FCB], B, H, H);
         return EC_OK;
     }
 
@@ -2617,11 +2776,12 @@ extern "C" int ec_policy_create_rnn_layers(ec_policy_t** out, const ec_policy_cf
 }
 extern "C" void ec_policy_destroy(ec_policy_t* h) { delete h; }
 extern "C" int ec_policy_set_goal_table(ec_policy_t* h, const float* table) {
-    if (!h || !table || !h->c.fusion) return EC_ERR_ARG;
+    if (!h || !table || !h->c.fusion || h->pl.on) return EC_ERR_ARG;
     h->goal_table = table;
     return EC_OK;
 }
 extern "C" int ec_policy_num_param_tensors(const ec_policy_t* h) {
+    if (h && h->pl.on) return h->pl.npre + 8 + (h->c.prev_action_dims ? 1 : 0) + 4 * (h->layers - 1);
     return ((h && h->c.dual) ? P_COUNT_DUAL : ((h && h->c.goal_in) ? P_COUNT_VEC : P_COUNT_SINGLE)) + ((h && h->c.prev_action_dims) ? 1 : 0) +
            (h ? 4 * (h->layers - 1) : 0);
 }
@@ -2632,6 +2792,19 @@ extern "C" int ec_policy_param_offset(const ec_policy_t* h, int idx, size_t* off
         const int u = idx - h->nbase;
         if (u >= 4 * (h->layers - 1)) return EC_ERR_ARG;
         *off = h->uoff[u / 4][u % 4]; *numel = h->unum[u / 4][u % 4];
+        return EC_OK;
+    }
+    if (h->pl.on) {                                   // visual_fc, the goal encoders, then weight_ih_l0 .. critic bias, the previous action's
+        const int k = idx - h->pl.npre;
+        if (k >= 8 + (h->c.prev_action_dims ? 1 : 0)) return EC_ERR_ARG;
+        if (k < 0) {
+            int t = idx;                              // (the goal-id embedding's slot is skipped on a handle without one)
+            if (!h->pl.ids && t >= PL_GEMB) ++t;
+            *off = h->pl.off[t]; *numel = h->pl.num[t];
+        } else {
+            const int i = k < 8 ? P_WIH + k : P_PAE;
+            *off = h->off[i]; *numel = h->num[i];
+        }
         return EC_OK;
     }
     if (idx >= P_COUNT_DUAL) return EC_ERR_ARG;
@@ -2669,7 +2842,7 @@ extern "C" int ec_policy_act(const ec_policy_t* h, const float* params, const vo
                              const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                              int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                              uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream) {
-    if (!actions || !logp || (h && h->c.prev_action_dims)) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa)
+    if (!actions || !logp || (h && (h->c.prev_action_dims || h->pl.on))) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa; pooled: ec_policy_act_pooled)
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;       // (the one-wave-per-row heads launch)
     const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, 1, N, workspace, ws_bytes,
@@ -2679,7 +2852,7 @@ extern "C" int ec_policy_act_vec(const ec_policy_t* h, const float* params, cons
                                  const float* goal_vec, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                                  int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                                  uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream) {
-    if (!actions || !logp || (h && h->c.prev_action_dims)) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa)
+    if (!actions || !logp || (h && (h->c.prev_action_dims || h->pl.on))) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa; pooled: ec_policy_act_pooled)
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
     const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
@@ -2693,7 +2866,7 @@ extern "C" int ec_policy_act_greedy(const ec_policy_t* h, const float* params, c
                                     const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                                     int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                                     ec_stream_t stream) {
-    if (!actions || !logp || (h && h->c.prev_action_dims)) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa)
+    if (!actions || !logp || (h && (h->c.prev_action_dims || h->pl.on))) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa; pooled: ec_policy_act_pooled)
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
     const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, 1, N, workspace, ws_bytes,
@@ -2703,7 +2876,7 @@ extern "C" int ec_policy_act_vec_greedy(const ec_policy_t* h, const float* param
                                         const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
                                         size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
                                         float* values, ec_stream_t stream) {
-    if (!actions || !logp || (h && h->c.prev_action_dims)) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa)
+    if (!actions || !logp || (h && (h->c.prev_action_dims || h->pl.on))) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa; pooled: ec_policy_act_pooled)
     if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
     const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
     return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
@@ -2716,9 +2889,11 @@ static int policy_act_any(const ec_policy_t* h, const float* params, const void*
                           const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, bool pa_entry, const float* h0,
                           const float* masks, int N, void* workspace, size_t ws_bytes, int reuse_tables, float* hv, float* h_final,
                           int64_t* actions, float* logp, float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
-                          const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
+                          const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream,
+                          const PooledIn* pin = nullptr) {
     if (!h || !actions || !logp) return EC_ERR_ARG;
-    if (pa_entry != (h->c.prev_action_dims > 0) || (pa_entry && !prev_actions)) return EC_ERR_ARG;
+    if ((pin != nullptr) != h->pl.on) return EC_ERR_ARG;
+    if (!pin && (pa_entry != (h->c.prev_action_dims > 0) || (pa_entry && !prev_actions))) return EC_ERR_ARG;
     if ((expert_actions != nullptr) != (expert_mask != nullptr)) return EC_ERR_ARG;
     if (!(force_p >= 0.f && force_p <= 1.f)) return EC_ERR_ARG;       // (NaN included)
     if (!expert_actions && force_p != 0.f) return EC_ERR_ARG;
@@ -2730,9 +2905,9 @@ static int policy_act_any(const ec_policy_t* h, const float* params, const void*
     const int mode = reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER;
     if (h->c.num_actions + 1 > 8)
         return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, 1, N, workspace, ws_bytes, mode, hv, h_final,
-                                   smp, stream, &force, prev_actions, pa_entry);
+                                   smp, stream, &force, prev_actions, pa_entry, pin);
     const int rc = policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, 1, N, workspace, ws_bytes, mode, hv,
-                                       h_final, smp, stream, nullptr, prev_actions, pa_entry);
+                                       h_final, smp, stream, nullptr, prev_actions, pa_entry, pin);
     if (rc != EC_OK || !expert_actions) return rc;
     return ec_teacher_force(hv, expert_actions, expert_mask, force_p, actions, logp, N, h->c.num_actions, seed, step, first_actor, stream);
 }
@@ -2764,6 +2939,85 @@ extern "C" int ec_policy_act_pa(const ec_policy_t* h, const float* params, const
                           force_p, stream);
 }
 
+// The pooled-embedding net (include/ec_amd.h): a handle whose plan is the fusion handle's with in_channels = hidden, its own
+// tensors in front of weight_ih_l0, and the two entry points below
+extern "C" int ec_policy_is_pooled(const ec_policy_t* h) { return (h && h->pl.on) ? 1 : 0; }
+extern "C" int ec_policy_create_pooled(ec_policy_t** out, const ec_pooled_cfg* cfg) {
+    if (!out || !cfg) return EC_ERR_ARG;
+    const ec_pooled_cfg& q = *cfg;
+    if (q.rnn_type != EC_RNN_GRU && q.rnn_type != EC_RNN_LSTM) return EC_ERR_ARG;
+    if (q.num_layers < 1 || q.num_layers > EC_RNN_MAX_LAYERS) return EC_ERR_ARG;
+    if (q.num_sensors < 0 || q.num_sensors > 3 || q.num_goals < 0 || q.num_goals > 256) return EC_ERR_ARG;
+    if (q.num_goals == 0 && q.num_sensors == 0) return EC_ERR_ARG;            // the net needs a goal
+    int K = 0;
+    for (int i = 0; i < q.num_sensors; ++i) {
+        if (q.sensor_in[i] < 1 || q.sensor_in[i] > 8) return EC_ERR_ARG;
+        K += q.sensor_in[i];
+    }
+    if (K > 8) return EC_ERR_ARG;
+    if (q.embed_dims < 1 || q.embed_dims > 64) return EC_ERR_ARG;
+    if (q.num_actions < 2 || q.num_actions > 256) return EC_ERR_ARG;
+    if (q.prev_action_dims < 0 || q.prev_action_dims > 64 || (q.prev_action_null != 0 && q.prev_action_null != 1)) return EC_ERR_ARG;
+    if (q.prev_action_null && !q.prev_action_dims) return EC_ERR_ARG;
+    if (q.embed_in < 64 || q.embed_in > 4096 || (q.embed_in & 3)) return EC_ERR_SHAPE;
+    if (q.hidden <= 0 || (q.hidden & 3)) return EC_ERR_SHAPE;
+    if (q.rnn_type == EC_RNN_LSTM && !ec_lstm_hidden_ok(q.hidden)) return EC_ERR_SHAPE;
+    ec_policy* h = new (std::nothrow) ec_policy();
+    if (!h) return EC_ERR_ALLOC;
+    ec_policy_cfg& c = h->c;
+    c = ec_policy_cfg{};
+    c.in_channels = q.hidden; c.spatial = 1; c.hidden = q.hidden; c.num_goals = q.num_goals; c.num_actions = q.num_actions;
+    c.fusion = 1;                        // (the plan's: M49 = 0, flat = in_channels; no goal table is ever read)
+    c.prev_action_dims = q.prev_action_dims; c.prev_action_null = q.prev_action_null;
+    h->rnn = q.rnn_type; h->layers = q.num_layers;
+    ec_policy::Pooled& pl = h->pl;
+    pl.on = true; pl.D = q.embed_in; pl.ed = q.embed_dims; pl.ids = q.num_goals > 0 ? 1 : 0; pl.ns = q.num_sensors; pl.K = K;
+    for (int i = 0; i < q.num_sensors; ++i) pl.k[i] = q.sensor_in[i];
+    pl.npre = 2 + pl.ids + 2 * pl.ns;
+    const size_t H = q.hidden, GW = (q.rnn_type == EC_RNN_LSTM ? 4 : 3) * H, ld = H + pl.side() + q.prev_action_dims;
+    size_t o = 0;
+    auto put = [&](size_t& off, size_t& num, size_t n) { off = o; num = n; o += (n + 3) / 4 * 4; };   // 16-B aligned
+    put(pl.off[PL_FCW], pl.num[PL_FCW], H * pl.D);
+    put(pl.off[PL_FCB], pl.num[PL_FCB], H);
+    put(pl.off[PL_GEMB], pl.num[PL_GEMB], (size_t)q.num_goals * pl.ed);
+    for (int i = 0; i < pl.ns; ++i) {
+        put(pl.off[PL_SW0 + 2 * i], pl.num[PL_SW0 + 2 * i], (size_t)pl.ed * pl.k[i]);
+        put(pl.off[PL_SB0 + 2 * i], pl.num[PL_SB0 + 2 * i], (size_t)pl.ed);
+    }
+    for (int i = 0; i < P_COUNT; ++i) { h->off[i] = 0; h->num[i] = 0; h->order[i] = i; }
+    const size_t n8[8] = {GW * ld, GW * H, GW, GW, (size_t)q.num_actions * H, (size_t)q.num_actions, H, 1};
+    for (int k = 0; k < 8; ++k) put(h->off[P_WIH + k], h->num[P_WIH + k], n8[k]);
+    h->off[P_PAE] = o;
+    if (q.prev_action_dims) put(h->off[P_PAE], h->num[P_PAE], (size_t)(q.num_actions + q.prev_action_null) * q.prev_action_dims);
+    h->ntensors = ec_policy_num_param_tensors(h) - 4 * (q.num_layers - 1);
+    h->nbase = h->ntensors;
+    for (int l = 1; l < q.num_layers; ++l) {
+        const size_t un[4] = {GW * H, GW * H, GW, GW};
+        for (int k = 0; k < 4; ++k) put(h->uoff[l - 1][k], h->unum[l - 1][k], un[k]);
+    }
+    h->total = o;
+    *out = h;
+    return EC_OK;
+}
+extern "C" int ec_policy_forward_pooled(const ec_policy_t* h, const float* params, const float* embed, const int64_t* goal,
+                                        const float* sensors, const int64_t* prev_actions, const float* h0, const float* masks, int T,
+                                        int N, void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final,
+                                        ec_stream_t stream) {
+    const PooledIn pin{sensors};
+    return policy_forward_impl(h, params, embed, nullptr, 0, goal, nullptr, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final,
+                               SampleArgs{}, stream, nullptr, prev_actions, false, &pin);
+}
+extern "C" int ec_policy_act_pooled(const ec_policy_t* h, const float* params, const float* embed, const int64_t* goal,
+                                    const float* sensors, const int64_t* prev_actions, const float* h0, const float* masks, int N,
+                                    void* workspace, size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions,
+                                    float* logp, float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
+                                    const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
+    const PooledIn pin{sensors};
+    return policy_act_any(h, params, embed, nullptr, 0, goal, nullptr, prev_actions, false, h0, masks, N, workspace, ws_bytes, reuse_tables,
+                          hv, h_final, actions, logp, values, greedy, seed, step, first_actor, expert_actions, expert_mask, force_p, stream,
+                          &pin);
+}
+
 extern "C" int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,
                                   const float* masks, int T, int N, void* workspace, size_t ws_bytes, const float* dhv,
                                   const float* dh_final, float* grads, ec_stream_t stream) {
@@ -2783,8 +3037,9 @@ extern "C" int ec_policy_backward3(const ec_policy_t* h, const float* params, co
                                    const float* dh_final, float* grads, ec_event_t recurrent_grads_ready, ec_stream_t stream) {
     if (!h || !params || !feat || !masks || !workspace || !dhv || !grads) return EC_ERR_ARG;
     if (h->c.dual && !feat2) return EC_ERR_ARG;
+    if (h->pl.on && ((uintptr_t)feat & 15) != 0) return EC_ERR_ARG;      // (the embedding rows are read as float4)
     if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
-    const Plan p = make_plan(h, T, N, EC_POLICY_LEARN, feat_bf16 != 0);
+    const Plan p = make_plan(h, T, N, EC_POLICY_LEARN, feat_bf16 != 0 && !h->pl.on);
     if (ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
     Bwd b(h, p, params, workspace, stream);
     b.grads = grads;
@@ -2796,11 +3051,14 @@ extern "C" int ec_policy_backward3(const ec_policy_t* h, const float* params, co
         if (l) RC(b.upper_layer_grads(l));
     }
     RC(b.gru_grads());
+    if (h->pl.on) RC(b.pooled_side_grads());
     // the gradients of the GRU and of both heads (tensors rnn.weight_ih_l0 .. critic.fc.bias: 92 % of the bucket) are final
     // here; what follows only writes the goal encoder's.  A caller that sums the bucket over ranks starts that section's
     // all-reduce behind this event, under the rest of this backward
     if (recurrent_grads_ready && hipEventRecord((hipEvent_t)recurrent_grads_ready, b.s) != hipSuccess) return EC_ERR_LAUNCH;
-    if (!h->c.fusion) {   // (fusion: the image embedding and the goal table are frozen, nothing trainable upstream of the GRU)
+    if (h->pl.on) {
+        RC(b.pooled_fc_grads((const float*)feat));
+    } else if (!h->c.fusion) {   // (fusion: the image embedding and the goal table are frozen, nothing trainable upstream of the GRU)
         b.parts_ok = p.wih == Wih::perm_learn;   // the plain path writes dx into the partial-matrix area now
         RC(b.input_grad());
         for (int sidx = 0; sidx < p.g.nstream; ++sidx) RC(b.encoder_stream(sidx, sidx ? feat2 : feat));

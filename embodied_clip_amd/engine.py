@@ -54,7 +54,7 @@ class SyntheticEnv:
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
                  frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False, expert: bool = False,
-                 num_actions: int = 6):
+                 num_actions: int = 6, sensors: int = 0):
         self.N, self.T = n_actors, T
         self.host = host
         # frames_u8: raw uint8 frames (what the simulator renders); normalisation is then fused into the stem kernel.
@@ -92,6 +92,10 @@ class SyntheticEnv:
             dbase = syn.normalize_depth(syn.synthetic_depth(seed + 5, n_actors, res).to(device))
             self.depth = torch.stack([dbase.roll(shifts=s + 1, dims=0).roll(shifts=7 * (s + 1), dims=2)
                                       for s in range(pool_steps)]).contiguous()   # [P, N, R, R, 1] fp32
+        if sensors:
+            # the pooled-embedding net's small float sensors (GPS, compass, a 3-float point goal): K floats per actor and step,
+            # f32 [T+1, N, K], from a seed of their own -- nothing else the env builds changes
+            self.sensors = torch.randn(T + 1, n_actors, int(sensors), generator=torch.Generator().manual_seed(seed + 8)).to(device).contiguous()
         self._k = 0
 
     def observe(self, actions_host: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -121,13 +125,16 @@ class NavSyntheticEnv(SyntheticEnv):
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
                  frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False, expert: bool = False,
-                 num_actions: int = 6):
-        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in, depth, expert, num_actions)
+                 num_actions: int = 6, sensors: int = 0):
+        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in, depth, expert, num_actions, sensors)
         self.num_goals = 0 if goal_in else 12
         step_dist, start_dist, goal_dist = syn.synthetic_navigation(seed + 4, self.masks[1:], self.success)
         self.step_dist = step_dist.to(device).contiguous()
         self.start_dist = start_dist.to(device).contiguous()
         self.goal_dist = goal_dist.to(device).contiguous()
+
+
+_NO_SIDE: Dict = {}      # (no extra keyword of the policy calls)
 
 
 class _Slice:
@@ -183,6 +190,38 @@ def check_rgbd(encoder: str, zeroshot: bool, goal_in: int, frames_host: bool) ->
         raise ValueError("depth=True: host-resident frames (frames_host=True) have no depth staging path")
 
 
+def check_net(net: str, pooling: str, sensors, goal_ids: bool, encoder: str, depth: bool, zeroshot: bool, goal_in: int):
+    """``Worker`` / ``Evaluator`` ``(net=..., pooling=..., sensors=..., goal_ids=...)``: "goal_encoder" (the default: AllenAct's
+    ResnetTensorGoalEncoder agent) or "pooled" (habitat-lab's PointNavResNetNet over the pooled embedding, ``PolicyHandle.pooled``).
+    Raised before anything is allocated.  -> (pooled, pooling, sensors)"""
+    if net not in ("goal_encoder", "pooled"):
+        raise ValueError(f"net={net!r}: 'goal_encoder' or 'pooled'")
+    if net == "goal_encoder":
+        if tuple(sensors):
+            raise ValueError("sensors=... belongs to net='pooled'")
+        return False, None, ()
+    sensors = tuple(int(k) for k in sensors)
+    if pooling not in ("attnpool", "avgpool"):
+        raise ValueError(f"pooling={pooling!r}: 'attnpool' or 'avgpool'")
+    if depth:
+        raise ValueError("net='pooled' with depth=True: the pooled net has no depth stream")
+    if zeroshot:
+        raise ValueError("net='pooled' with zeroshot=True: the zero-shot fusion policy is another net")
+    if goal_in:
+        raise ValueError("net='pooled' with goal_in > 0: coordinate goals reach the pooled net as sensors=(k,)")
+    if encoder == "vit":
+        raise ValueError("net='pooled' with encoder='vit': the ViT's CLS vector is not built")
+    if encoder in IMAGENET_ENCODERS and pooling == "attnpool":
+        raise ValueError("net='pooled', pooling='attnpool': the ImageNet towers have no attention pool; use pooling='avgpool'")
+    if encoder not in ("rn50",) and encoder not in IMAGENET_ENCODERS:
+        raise ValueError(f"net='pooled': encoder 'rn50' (both poolings) or an ImageNet tower ('avgpool'), not {encoder!r}")
+    if len(sensors) > 3 or any(k < 1 for k in sensors) or sum(sensors) > 8:
+        raise ValueError(f"sensors={sensors!r}: at most 3 sensors of at least one float each, 8 floats in all")
+    if not goal_ids and not sensors:
+        raise ValueError("net='pooled' needs a goal: goal_ids=True or at least one sensor")
+    return True, pooling, sensors
+
+
 def check_model_tensors(policy, sd, where: str) -> None:
     """A checkpoint's ``model_state_dict`` against the handle's tensors: a missing one (a checkpoint written without the
     previous-action embedding, loaded by an agent that has it) raises, naming the tensor and the file; so does one whose
@@ -223,10 +262,29 @@ class _SlicedActor:
     # recurrent layers ([U] RNNStateEncoder num_layers): a memory row is [N, L * SW], layer-major
     rnn_layers = 1
     hidden_size = 512       # the recurrent width ([U] hidden_size); ``Worker`` / ``Evaluator`` ``(hidden=...)``
+    # net="pooled" (check_net): the pooled-embedding net over one vector per frame -- how the tower is pooled, the widths of the
+    # env's float sensors, whether the goal id is embedded; set by the users before ``_build_model``
+    pooled_net = False
+    pooling = None
+    net_sensors = ()
+    goal_ids = True
+
+    # how a frame becomes ONE fp32 vector in the rollout buffer: "attnpool" (the zero-shot agent, the pooled net), "avgpool" (the
+    # pooled net), or None (feature maps); ``_build_model`` sets it
+    _embed = None
+
+    def _goal(self, t: int, rs):
+        """step ``t``'s goal argument of the policy calls for the actors ``rs`` (None: a pooled net without a goal-id embedding)"""
+        return self.env.goals[t][rs] if (self.goal_ids or not self.pooled_net) else None
+
+    def _side(self, t: int, rs):
+        """... and the pooled net's sensor rows, as a keyword (nothing for every other net)"""
+        return {"sensors": self.env.sensors[t][rs]} if self.net_sensors else {}
 
     def _build_model(self, n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams):
         """Encoder handles (one per slice, weights shared), the policy handle and its flat parameters.  -> (encs, pools)"""
         self.encoder = encoder
+        self._embed = "attnpool" if self.zeroshot else self.pooling
         # two slices (each with its own act -> encode chain on its own stream) from 48 actors on: measured round 3 at
         # 32 / 48 / 64 actors, one vs two slices: 26.8 / 29.0 / 35.0 k vs 26.1 / 31.8 / 36.8 k env-frames/s
         two_min = int(os.environ.get("EC_TWO_SLICE_MIN", "48"))          # (experiment switch for the rule above)
@@ -244,7 +302,7 @@ class _SlicedActor:
             encs = [RN50Trunk(sd, device=d, chunk=encoder_chunk)]
             encs += [RN50Trunk(sd, device=d, chunk=encoder_chunk, weights_from=encs[0] if share else None) for _ in range(ns - 1)]
             self.S, self.C = encs[0].out_spatial, encs[0].out_channels
-            if self.zeroshot:
+            if self._embed == "attnpool":
                 pools = [AttentionPool(sd, device=d)]
                 pools += [AttentionPool(sd, device=d, weights_from=pools[0] if share else None) for _ in range(ns - 1)]
                 self.trunk_S, self.trunk_C = self.S, self.C
@@ -268,6 +326,19 @@ class _SlicedActor:
             self.S, self.C = 7, encs[0].D
         else:
             raise ValueError(encoder)
+        if self._embed == "avgpool":      # AdaptiveAvgPool2d(1) of the trunk output (ec_spatial_mean_bf16): D = the trunk's channels
+            self.trunk_S, self.trunk_C = self.S, self.C
+            self.S = 1
+        if self.pooled_net:
+            self.policy = PolicyHandle.pooled(self.C, hidden=self.hidden_size, num_goals=12 if self.goal_ids else 0, sensors=self.net_sensors,
+                                              num_actions=self._num_actions, prev_action_dims=self.prev_action_dims,
+                                              prev_action_null=self.prev_action_null, rnn_type=self.rnn_type, rnn_layers=self.rnn_layers)
+            if policy_sd is not None:     # (a checkpoint of another net: refused by the first tensor it lacks, by name)
+                check_model_tensors(self.policy, policy_sd, getattr(self, "_checkpoint", None) or "policy_sd")
+            self.H, self.A, self.SW = self.policy.H, self.policy.A, self.policy.state_width
+            self.params = self.policy.flatten(policy_sd if policy_sd is not None
+                                              else syn.policy_state_dict(0, pooled=self.policy.pooled_cfg), d)
+            return encs, pools
         pkw = dict(in_channels=self.C, spatial=self.S, num_actions=self._num_actions)
         if self.goal_in:
             pkw["goal_in"] = self.goal_in
@@ -336,10 +407,10 @@ class _SlicedActor:
             sl.o, sl.n, sl.enc, sl.pool = i * n, n, encs[i], pools[i]
             sl.stream = slice_streams[i]
             # zero-shot: the rollout buffer holds fp32 image embeddings [T+1, n, 1, 1024]; else bf16 feature maps
-            sl.feat = torch.empty((feat_steps, n, S2, self.C), dtype=torch.float32 if self.zeroshot else torch.bfloat16, device=d)
+            sl.feat = torch.empty((feat_steps, n, S2, self.C), dtype=torch.float32 if self._embed else torch.bfloat16, device=d)
             sl.feat2 = torch.empty_like(sl.feat) if self.depth else None      # the depth tower's features
             sl.trunk_out = (torch.empty((n, self.trunk_S, self.trunk_S, self.trunk_C), dtype=torch.bfloat16, device=d)
-                            if self.zeroshot else None)
+                            if self._embed else None)
             sl.tok = (torch.empty((n, encs[i].L, encs[i].D), dtype=torch.bfloat16, device=d) if encoder == "vit" else None)
             sl.ws_act = torch.empty(self.policy.workspace_bytes(1, n, False), dtype=torch.uint8, device=d)
             sl.act_tables_valid = False     # weight-derived tables in ws_act (rebuilt by the first act step after an update)
@@ -428,9 +499,13 @@ class _SlicedActor:
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(torch.cuda.current_stream())
-        if self.zeroshot:
+        if self._embed:
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.trunk_out)
-            sl.pool.forward(sl.trunk_out, sl.feat[t].view(sl.n, self.C))     # AttentionPool2d -> rollout slice
+            if self._embed == "attnpool":
+                sl.pool.forward(sl.trunk_out, sl.feat[t].view(sl.n, self.C))     # AttentionPool2d -> rollout slice
+            else:                                                               # AdaptiveAvgPool2d(1) -> rollout slice
+                _lib.check(self.lib.ec_spatial_mean_bf16(sl.trunk_out.data_ptr(), sl.feat[t].data_ptr(), sl.n, self.trunk_S * self.trunk_S,
+                                                         self.trunk_C, _lib.stream_ptr()), "ec_spatial_mean_bf16")
         elif self.encoder in ("rn50", "rn50x16") or self.encoder in IMAGENET_ENCODERS:
             # the last conv writes straight into the rollout slice
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.feat[t])
@@ -477,8 +552,18 @@ class Worker(_SlicedActor):
                  overlap_allreduce: bool = True, goal_in: int = 0, num_actions: int = 6, track_episodes: bool = False,
                  nav_metrics: bool = False, depth: bool = False, loss: str = "ppo", il_weight: float = 1.0,
                  teacher_forcing=None, prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU",
-                 rnn_layers: int = 1, hidden: int = 512):
-        """``hidden``: the recurrent width ([U] ``hidden_size``; 512 in every published config).
+                 rnn_layers: int = 1, hidden: int = 512, net: str = "goal_encoder", pooling: str = "attnpool", sensors=(),
+                 goal_ids: bool = True):
+        """``net="pooled"``: the Habitat DD-PPO net ([U] habitat-lab ``PointNavResNetNet``, restated, parity unpinned;
+        ``PolicyHandle.pooled``) -- the frozen tower pooled to ONE vector per frame (``pooling="attnpool"``: CLIP's attention pool,
+        D = 1024, ``encoder="rn50"``; ``"avgpool"``: ``ec_spatial_mean_bf16`` over the trunk output, D = its channels, also on the
+        ImageNet towers), ``visual_fc``, the goal id (``goal_ids``) and / or the env's float ``sensors=(k_1, ...)``, the previous
+        action, the recurrent core.  The rollout buffer is fp32 ``[T + 1, n, 1, D]``.  Every ``loss`` mode, teacher forcing, up to
+        256 actions, ``prev_actions``, ``rnn_type``, ``rnn_layers``, ``num_mini_batch``, ``sync_actions`` and checkpoints work; a
+        checkpoint of another net is refused by tensor name.  ``ValueError`` before any allocation with ``depth``, ``zeroshot``,
+        ``goal_in``, ``encoder="vit"`` or ``pooling="attnpool"`` on an ImageNet tower.
+
+        ``hidden``: the recurrent width ([U] ``hidden_size``; 512 in every published config).
 
         ``rnn_layers=L`` (1..4; [U] RNNStateEncoder ``num_layers``, 2 in the Habitat DD-PPO policies): the recurrent memory is
         ``[N, L * SW]`` rows, layer-major (``policy.memory_to_state`` converts upstream's); a checkpoint carries the upper
@@ -524,6 +609,8 @@ class Worker(_SlicedActor):
         ``zeroshot=True`` (BASELINE config 5, readme_files/zeroshot_objectnav.md): the observation is the CLIP image
         EMBEDDING (RN50 trunk + AttentionPool2d, 1024-d), the goal is the frozen CLIP text embedding of its prompt
         (text tower run once -> [12, 1024] table) and the policy is the fusion=1 variant (GRU + heads trainable)."""
+        self.pooled_net, self.pooling, self.net_sensors = check_net(net, pooling, sensors, goal_ids, encoder, bool(depth), bool(zeroshot), goal_in)
+        self.goal_ids = bool(goal_ids)
         if depth:
             check_rgbd(encoder, zeroshot, goal_in, frames_host)
         self.prev_action_dims = check_prev_actions(prev_actions, bool(depth), bool(zeroshot))
@@ -611,6 +698,8 @@ class Worker(_SlicedActor):
         dkw = dict(depth=True) if self.depth else {}
         if self._il or self.teacher_forcing is not None:
             dkw.update(expert=True, num_actions=self._num_actions)
+        if self.net_sensors:
+            dkw.update(sensors=sum(self.net_sensors))
         self.env = env_cls(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in, **dkw)
         if self.nav_metrics:      # per-category rows for goal ids; coordinate goals have no categories
             self.episodes = NavEpisodeTracker(N, d, num_categories=0 if self.goal_in else self.env.num_goals)
@@ -627,7 +716,7 @@ class Worker(_SlicedActor):
             sl.rec_ready = torch.cuda.Event()
             sl.rec_ready.record()          # (torch creates the hipEvent_t at the first record: the library needs the handle)
             sl.sums = torch.zeros(4, dtype=torch.float64, device=d)
-            sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = sl.prev = None
+            sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = sl.prev = sl.sens = None
             # more than 16 actions: the wide loss kernel's partial-sum scratch, one per slice stream as for imitation
             sl.ppo_scratch = ppo_wide_scratch(d) if (self._ppo and self.A > PPO_NARROW_MAX_A) else None
             if self._il:      # the imitation loss's sums and partial-sum scratch: one per slice stream
@@ -653,28 +742,31 @@ class Worker(_SlicedActor):
         rs = slice(o, o + n)
         h_in, h_out = (self.h, self.h_next) if (t & 1) == 0 else (self.h_next, self.h)   # ping-pong by step parity
         pa = self.prev_actions[t][rs] if self.prev_action_dims else None                  # (the bootstrap step reads row T)
+        # (the pooled net's goal / sensor arguments; every other net: the goal row and no keyword, without a call on this host chain)
+        goal, side = (self._goal(t, rs), self._side(t, rs)) if self.pooled_net else (self.env.goals[t][rs], _NO_SIDE)
         if sample and self._act_fused:
             # forward + CategoricalDistr.sample / log_prob in one call: the heads launch samples (ec_policy_act, one launch less)
-            self.policy.act(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act,
+            self.policy.act(self.params, sl.feat[t], goal, h_in[rs], self.env.masks[t][rs], n, sl.ws_act,
                             self.hv_act[rs], h_out[rs], self.actions[t][rs], self.logp[t][rs], self.values[t][rs], self.seed,
-                            self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa)
+                            self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa,
+                            **side)
             sl.act_tables_valid = True
             self._teacher_force_slice(sl, t)
             return
         if sample and self._act_wide:
             # the same for 8 to 256 actions (ec_policy_act_ex): the wide heads launch samples and, while p > 0, forces
             tf = self._tf_p > 0.0
-            self.policy.act_ex(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act,
+            self.policy.act_ex(self.params, sl.feat[t], goal, h_in[rs], self.env.masks[t][rs], n, sl.ws_act,
                                self.hv_act[rs], h_out[rs], self.actions[t][rs], self.logp[t][rs], self.values[t][rs], self.seed,
                                self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t),
                                expert_actions=self.env.expert_actions[t][rs] if tf else None,
                                expert_mask=self.env.expert_mask[t][rs] if tf else None, force_p=self._tf_p if tf else 0.0,
-                               prev_actions=pa)
+                               prev_actions=pa, **side)
             sl.act_tables_valid = True
             return
-        self.policy.forward(self.params, sl.feat[t], self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n,
+        self.policy.forward(self.params, sl.feat[t], goal, h_in[rs], self.env.masks[t][rs], 1, n,
                             sl.ws_act, hv=self.hv_act[rs], h_final=h_out[rs], for_backward=False,
-                            reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa)   # (E1 depends on the parameters only)
+                            reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa, **side)   # (E1 depends on the parameters only)
         sl.act_tables_valid = True
         if sample:
             _lib.check(self.lib.ec_sample_actions(self.hv_act[rs].data_ptr(), self.actions[t][rs].data_ptr(),
@@ -804,6 +896,8 @@ class Worker(_SlicedActor):
             c = lambda x: x[:T, rs].reshape(-1).contiguous()
             # (coordinate goals keep their last dimension: [T*n, goal_in] rows)
             sl.goal = self.env.goals[:T, rs].reshape(T * sl.n, -1).contiguous() if self.goal_in else c(self.env.goals)
+            if self.net_sensors:      # the pooled net's sensor rows [T*n, K]
+                sl.sens = self.env.sensors[:T, rs].reshape(T * sl.n, -1).contiguous()
             sl.masks = c(self.env.masks)
             sl.actions, sl.logp, sl.old_v = c(self.actions), c(self.logp), c(self.values)
             sl.ret, sl.nadv = c(self.returns), c(self.nadv)
@@ -863,6 +957,14 @@ class Worker(_SlicedActor):
         if a == 0 and b == sl.n:
             return sl.prev
         return sl.prev.view(self.T, sl.n)[:, a:b].reshape(-1).contiguous()
+
+    def _gather_side(self, sl, a: int, b: int):
+        """The pooled net's sensor rows of the batch ``_gather_part(sl, a, b)`` returns, as a keyword (nothing for every other net)."""
+        if not self.net_sensors:
+            return {}
+        if a == 0 and b == sl.n:
+            return {"sensors": sl.sens}
+        return {"sensors": sl.sens.view(self.T, sl.n, -1)[:, a:b].reshape(self.T * (b - a), -1).contiguous()}
 
     def _expert_counts(self) -> Dict[tuple, torch.Tensor]:
         """The imitation normaliser of every minibatch range -- the number of this rollout's steps that have an expert action
@@ -937,8 +1039,11 @@ class Worker(_SlicedActor):
                         # (staggering the slices -- slice 1's forward starting when slice 0's is done, so that wide GEMMs
                         #  run beside the other slice's GRU recurrence -- was measured in round 3: 53 -> 58 ms per update;
                         #  the step kernels wait for CUs the GEMM workgroups hold)
+                        if self.pooled_net and not self.goal_ids:
+                            goal = None
                         self.policy.forward(self.params, feat, goal, self.h_start[sl.o + a:sl.o + b], masks, T, m,
-                                            sl.ws_learn, hv=hv, feat2=feat2, prev_actions=self._gather_prev(sl, a, b))
+                                            sl.ws_learn, hv=hv, feat2=feat2, prev_actions=self._gather_prev(sl, a, b),
+                                            **self._gather_side(sl, a, b))
                         if self._ppo:
                             ppo_loss_raw(hv, actions, logp, old_v, ret, nadv, self.A, grad_scale=grad_scale, dhv=dhv,
                                          sums=sl.sums, scratch=sl.ppo_scratch)

@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_prev_actions, check_rgbd, check_rnn_layers, check_rnn_type
+from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_net, check_prev_actions, check_rgbd, check_rnn_layers, check_rnn_type
 from .episodes import EpisodeTracker, NavEpisodeTracker, category_names, nav_env_tensors
 
 
@@ -60,7 +60,13 @@ class Evaluator(_SlicedActor):
                  goal_tokens=None, encoder_chunk: int = 0, record_capacity: int = 0, nav_metrics: bool = False,
                  num_categories: Optional[int] = None, env_seed: Optional[int] = None, depth: bool = False,
                  prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU",
-                 rnn_layers: int = 1, hidden: int = 512):
+                 rnn_layers: int = 1, hidden: int = 512, net: str = "goal_encoder", pooling: str = "attnpool", sensors=(),
+                 goal_ids: bool = True):
+        # net="pooled": the agent of Worker(net="pooled", ...) -- the same arguments, the same refusals; an env= must hold `sensors`
+        self.pooled_net, self.pooling, self.net_sensors = check_net(net, pooling, sensors, goal_ids, encoder, bool(depth), bool(zeroshot), goal_in)
+        self.goal_ids = bool(goal_ids)
+        if self.net_sensors and env is not None and getattr(env, "sensors", None) is None:
+            raise ValueError("net='pooled' with sensors: the env serves no sensor vectors (SyntheticEnv(..., sensors=K) holds env.sensors)")
         self.hidden_size = int(hidden)
         self.rnn_type = check_rnn_type(rnn_type, bool(depth), bool(zeroshot))
         self.rnn_layers = check_rnn_layers(rnn_layers, bool(depth), bool(zeroshot))
@@ -99,7 +105,7 @@ class Evaluator(_SlicedActor):
         self.N, self.T, self.rank = n_actors, T, rank
         N = n_actors
         d = self.dev
-        if self._checkpoint is not None and self.prev_action_dims:
+        if self._checkpoint is not None and self.prev_action_dims and not self.pooled_net:
             # before the handle flattens it: a checkpoint of an agent without the embedding is refused by the tensor's name
             from .synthetic import POLICY_PREV_ACTION_EMBEDDER
             if POLICY_PREV_ACTION_EMBEDDER not in policy_sd:
@@ -117,6 +123,8 @@ class Evaluator(_SlicedActor):
         env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
         env_seed = self._env_seed if self._env_seed is not None else 1000 + rank
         dkw = dict(depth=True) if self.depth else {}
+        if self.net_sensors:
+            dkw.update(sensors=sum(self.net_sensors))
         self.env = env if env is not None else env_cls(N, T, d, seed=env_seed, frames_u8=frames_u8, goal_in=self.goal_in, **dkw)
         assert (self.env.N, self.env.T) == (N, T), "the env's actor count and rollout length are the evaluator's"
         if self.nav_metrics:
@@ -145,17 +153,17 @@ class Evaluator(_SlicedActor):
         key = self.chunk * (self.T + 1) + t
         pa = self._prev_row[rs] if self.prev_action_dims else None
         if self._act_fused:
-            self.policy.act(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
+            self.policy.act(self.params, feat, self._goal(t, rs), h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
                             actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
-                            deterministic=self.deterministic, feat2=feat2, prev_actions=pa)
+                            deterministic=self.deterministic, feat2=feat2, prev_actions=pa, **self._side(t, rs))
         elif self._act_wide:   # 8 to 256 actions: the wide heads launch selects (ec_policy_act_ex)
-            self.policy.act_ex(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
+            self.policy.act_ex(self.params, feat, self._goal(t, rs), h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
                                actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
-                               deterministic=self.deterministic, feat2=feat2, prev_actions=pa)
+                               deterministic=self.deterministic, feat2=feat2, prev_actions=pa, **self._side(t, rs))
         else:   # the switch off: the forward, then the stand-alone selection kernel
-            self.policy.forward(self.params, feat, self.env.goals[t][rs], h_in[rs], self.env.masks[t][rs], 1, n, sl.ws_act,
+            self.policy.forward(self.params, feat, self._goal(t, rs), h_in[rs], self.env.masks[t][rs], 1, n, sl.ws_act,
                                 hv=hv, h_final=h_out[rs], for_backward=False, reuse_tables=sl.act_tables_valid, feat2=feat2,
-                                prev_actions=pa)
+                                prev_actions=pa, **self._side(t, rs))
             if self.deterministic:
                 _lib.check(self.lib.ec_mode_actions(hv.data_ptr(), actions.data_ptr(), logp.data_ptr(), values.data_ptr(), n,
                                                     self.A, _lib.stream_ptr()), "ec_mode_actions")
@@ -289,6 +297,11 @@ def main(argv=None) -> int:
                     help="with --prev-actions: no null row for an episode's first step (action a is row a)")
     ap.add_argument("--rnn-type", default="GRU", choices=("GRU", "LSTM"), help="the recurrent cell of the agent (and of its checkpoint)")
     ap.add_argument("--rnn-layers", type=int, default=1, choices=(1, 2, 3, 4), help="recurrent layers of the agent (and of its checkpoint)")
+    ap.add_argument("--net", default="goal_encoder", choices=("goal_encoder", "pooled"),
+                    help="pooled: the Habitat DD-PPO net over the pooled embedding (PolicyHandle.pooled)")
+    ap.add_argument("--pooling", default="attnpool", choices=("attnpool", "avgpool"), help="with --net pooled: how the tower is pooled")
+    ap.add_argument("--sensors", default="", metavar="K1,K2", help="with --net pooled: the widths of the env's float sensors, e.g. 2,2 (GPS, compass) or 3")
+    ap.add_argument("--no-goal-ids", action="store_true", help="with --net pooled: no goal-id embedding (PointNav: --sensors 3)")
     ap.add_argument("--json", default=None, metavar="OUT", help="also write the info dict to this file")
     ap.add_argument("--env-seed", type=int, default=None, help="seed of the synthetic env (default 1000, what Evaluator builds itself)")
     ap.add_argument("--nav-metrics", action="store_true", help="also SPL, SoftSPL, distance to goal, and the scores per object type")
@@ -317,6 +330,7 @@ def main(argv=None) -> int:
                    goal_in=a.goal_in, num_actions=a.num_actions, zeroshot=a.zeroshot, frames_u8=a.frames_u8,
                    sync_actions=a.sync_actions, nav_metrics=a.nav_metrics, depth=a.depth, prev_actions=a.prev_actions,
                    prev_action_null_token=not a.no_prev_action_null_token, rnn_type=a.rnn_type, rnn_layers=a.rnn_layers,
+                   net=a.net, pooling=a.pooling, sensors=tuple(int(k) for k in a.sensors.split(",") if k), goal_ids=not a.no_goal_ids,
                    num_categories=len(names) if (names is not None and not a.goal_in) else None,
                    # every actor can end an episode at every step: the metrics file then misses none
                    record_capacity=a.chunks * a.steps * a.actors if a.metrics_json else 0)

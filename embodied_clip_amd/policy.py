@@ -257,6 +257,180 @@ class PolicyHandle:
         return slice(o0, min(later) if later else self.flat_size)
 
 
+# ---- the pooled-embedding net ------------------------------------------------------------------
+# [U] habitat-lab ``PointNavResNetNet`` (habitat_baselines/rl/ddppo/policy/resnet_policy.py) over ONE pooled CLIP vector per frame,
+# the Habitat DD-PPO branch of readme_files/baselines_habitat.md.  Restated from the published sources, which are not under the
+# reference tree: parity unpinned.  The ONE table of tensor names (Habitat's, without the ``net.`` prefix) in flat order:
+POOLED_SENSOR_NAMES = {(3,): ("tgt_embeding",), (2, 2): ("gps_embedding", "compass_embedding")}   # (sic: upstream's spelling)
+POOLED_EMBEDDING_TENSORS = ("obj_categories_embedding.weight", "prev_action_embedding.weight")    # nn.Embedding: N(0, 1)
+
+
+def pooled_sensor_names(sensors) -> Tuple[str, ...]:
+    """Habitat's module names for the usual sensor sets (PointNav's 3-float goal; ObjectNav's GPS + compass), else by position."""
+    sensors = tuple(int(k) for k in sensors)
+    return POOLED_SENSOR_NAMES.get(sensors, tuple(f"sensor{i}_embedding" for i in range(len(sensors))))
+
+
+def pooled_param_shapes(embed_in: int, hidden: int = 512, num_goals: int = 12, sensors=(), num_actions: int = 6,
+                        prev_action_dims: int = 0, prev_action_null: int = 1, rnn_type: str = "GRU", rnn_layers: int = 1,
+                        embed_dims: int = 32) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Tensor name -> shape in the flat order of ``ec_policy_create_pooled``.  ``weight_ih_l0``'s columns: ``v`` (hidden), the
+    goal-id embedding, the sensors in order, the previous action."""
+    sensors = tuple(int(k) for k in sensors)
+    G = (4 if rnn_type == "LSTM" else 3) * hidden
+    ids = 1 if num_goals > 0 else 0
+    out: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    out["visual_fc.1.weight"] = (hidden, embed_in)
+    out["visual_fc.1.bias"] = (hidden,)
+    if ids:
+        out["obj_categories_embedding.weight"] = (num_goals, embed_dims)
+    for name, k in zip(pooled_sensor_names(sensors), sensors):
+        out[f"{name}.weight"] = (embed_dims, k)
+        out[f"{name}.bias"] = (embed_dims,)
+    out["state_encoder.rnn.weight_ih_l0"] = (G, hidden + embed_dims * (ids + len(sensors)) + prev_action_dims)
+    out["state_encoder.rnn.weight_hh_l0"] = (G, hidden)
+    out["state_encoder.rnn.bias_ih_l0"] = (G,)
+    out["state_encoder.rnn.bias_hh_l0"] = (G,)
+    out["action_distribution.linear.weight"] = (num_actions, hidden)
+    out["action_distribution.linear.bias"] = (num_actions,)
+    out["critic.fc.weight"] = (1, hidden)
+    out["critic.fc.bias"] = (1,)
+    if prev_action_dims:
+        out["prev_action_embedding.weight"] = (num_actions + prev_action_null, prev_action_dims)
+    for l in range(1, rnn_layers):
+        out[f"state_encoder.rnn.weight_ih_l{l}"] = (G, hidden)
+        out[f"state_encoder.rnn.weight_hh_l{l}"] = (G, hidden)
+        out[f"state_encoder.rnn.bias_ih_l{l}"] = (G,)
+        out[f"state_encoder.rnn.bias_hh_l{l}"] = (G,)
+    return out
+
+
+class PooledPolicyHandle(PolicyHandle):
+    """``ec_policy_create_pooled``'s handle (``PolicyHandle.pooled``): ``forward`` / ``act`` take the embedding rows f32 ``[T*N, D]`` as
+    ``feat`` and ``goal=`` (int64 ids, handles with ``num_goals > 0``), ``sensors=`` (f32 ``[T*N, K]``, handles with sensors),
+    ``prev_actions=``; ``backward``, ``flatten``, ``views``, ``recurrent_section`` are the base class's."""
+
+    def __init__(self, embed_in: int, hidden: int = 512, num_goals: int = 12, sensors=(), num_actions: int = 6,
+                 prev_action_dims: int = 0, prev_action_null: int = 1, rnn_type: str = "GRU", rnn_layers: int = 1, embed_dims: int = 32):
+        self.lib = _lib.load()
+        if rnn_type not in _lib.RNN_TYPES:
+            raise ValueError(f"rnn_type must be one of {sorted(_lib.RNN_TYPES)}, got {rnn_type!r}")
+        if not (isinstance(rnn_layers, int) and 1 <= rnn_layers <= 4):
+            raise ValueError(f"rnn_layers must be 1..4, got {rnn_layers!r}")
+        sensors = tuple(int(k) for k in sensors)
+        if len(sensors) > 3 or any(k < 1 for k in sensors) or sum(sensors) > 8:
+            raise ValueError(f"at most 3 sensors of at least one float each, 8 floats in all, got {sensors!r}")
+        if not num_goals and not sensors:
+            raise ValueError("the pooled net needs a goal: num_goals > 0 or at least one sensor")
+        if not prev_action_dims:
+            prev_action_null = 0
+        self.rnn_type, self.rnn_layers = rnn_type, rnn_layers
+        self.sensors, self.K = sensors, sum(sensors)
+        self.pooled_cfg = dict(embed_in=embed_in, hidden=hidden, num_goals=num_goals, sensors=sensors, num_actions=num_actions,
+                               prev_action_dims=prev_action_dims, prev_action_null=prev_action_null, rnn_type=rnn_type,
+                               rnn_layers=rnn_layers, embed_dims=embed_dims)
+        self.cfg = dict(hidden=hidden, num_goals=num_goals, num_actions=num_actions, prev_action_dims=prev_action_dims,
+                        prev_action_null=prev_action_null, dual=0, fusion=0, goal_in=0, embed_in=embed_in)
+        self.goal_in = 0
+        self.prev_action_dims = prev_action_dims
+        c = _lib.PooledCfg(embed_in=embed_in, hidden=hidden, embed_dims=embed_dims, num_goals=num_goals, num_sensors=len(sensors),
+                           sensor_in=(C.c_int * 3)(*(sensors + (0,) * (3 - len(sensors)))), num_actions=num_actions,
+                           prev_action_dims=prev_action_dims, prev_action_null=prev_action_null, rnn_type=_lib.RNN_TYPES[rnn_type],
+                           num_layers=rnn_layers)
+        h = C.c_void_p()
+        _lib.check(self.lib.ec_policy_create_pooled(C.byref(h), C.byref(c)), "ec_policy_create_pooled")
+        self.h = h
+        self.flat_size = self.lib.ec_policy_flat_size(h)
+        self.state_width = self.lib.ec_policy_state_width(h)
+        self.shapes = pooled_param_shapes(**self.pooled_cfg)
+        self.param_order = tuple(self.shapes)
+        self.offsets = OrderedDict()
+        assert self.lib.ec_policy_num_param_tensors(h) == len(self.param_order)
+        for i, name in enumerate(self.param_order):
+            off, num = C.c_size_t(), C.c_size_t()
+            _lib.check(self.lib.ec_policy_param_offset(h, i, C.byref(off), C.byref(num)))
+            n = 1
+            for d in self.shapes[name]:
+                n *= d
+            assert n == num.value, (name, n, num.value)
+            self.offsets[name] = (off.value, num.value)
+
+    def set_goal_table(self, table):
+        raise ValueError("the pooled net has no goal table")
+
+    def memory_to_state(self, mem: torch.Tensor) -> torch.Tensor:
+        return memory_to_state(mem, self.rnn_type, self.rnn_layers)
+
+    def state_to_memory(self, state: torch.Tensor) -> torch.Tensor:
+        return state_to_memory(state, self.rnn_type, self.rnn_layers)
+
+    def _side_ptrs(self, feat, goal, sensors, prev_actions, rows: int):
+        D = self.pooled_cfg["embed_in"]
+        assert feat.dtype == torch.float32 and feat.is_contiguous() and feat.numel() == rows * D, (feat.dtype, tuple(feat.shape), (rows, D))
+        if self.pooled_cfg["num_goals"]:
+            assert goal is not None and goal.dtype == torch.int64 and goal.is_contiguous() and goal.numel() == rows, "goal: int64, one id per frame"
+        else:
+            assert goal is None, "this handle has no goal-id embedding (num_goals=0): pass goal=None"
+        if self.K:
+            assert sensors is not None and sensors.dtype == torch.float32 and sensors.is_contiguous() and sensors.numel() == rows * self.K, \
+                f"sensors: float32 [{rows}, {self.K}]"
+        else:
+            assert sensors is None, "this handle has no sensors: pass sensors=None"
+        return _lib.ptr(goal), _lib.ptr(sensors), self._prev_ptr(prev_actions, rows)
+
+    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None,
+                 sensors=None):
+        if hv is None:
+            hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)
+        if h_final is None:
+            h_final = torch.empty((N, self.state_width), dtype=torch.float32, device=dev)
+        gp, sp, pp = self._side_ptrs(feat, goal, sensors, prev_actions, T * N)
+        _lib.check(self.lib.ec_policy_forward_pooled(
+            self.h, flat_params.data_ptr(), feat.data_ptr(), gp, sp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), T, N, ws.data_ptr(),
+            ws.numel() * ws.element_size(), int(for_backward), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), _lib.stream_ptr()),
+            "ec_policy_forward_pooled")
+        return hv, h_final
+
+    def forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv=None, h_final=None, for_backward: bool = True,
+                reuse_tables: bool = False, feat2=None, prev_actions=None, sensors=None):
+        assert feat2 is None
+        with _lib.tensor_guard(flat_params):
+            mode = 1 if for_backward else (2 if reuse_tables else 0)
+            return self._forward(flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, flat_params.device, mode, None, prev_actions, sensors)
+
+    def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
+            first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None, sensors=None,
+            expert_actions=None, expert_mask=None, force_p: float = 0.0):
+        """``ec_policy_act_pooled``: the T = 1 inference forward and the selection (sample, ``deterministic=True`` the first maximal
+        logit, optional teacher forcing) in one call, 2..256 actions."""
+        assert feat2 is None
+        gp, sp, pp = self._side_ptrs(feat, goal, sensors, prev_actions, N)
+        forcing = expert_actions is not None and force_p > 0.0
+        with _lib.tensor_guard(flat_params):
+            _lib.check(self.lib.ec_policy_act_pooled(
+                self.h, flat_params.data_ptr(), feat.data_ptr(), gp, sp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), N, ws.data_ptr(),
+                ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
+                logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
+                expert_actions.data_ptr() if forcing else 0, expert_mask.data_ptr() if forcing else 0, force_p if forcing else 0.0,
+                _lib.stream_ptr()), "ec_policy_act_pooled")
+        return hv, h_final
+
+    act_ex = act
+
+    def _backward(self, flat_params, feat, masks, T, N, ws, dhv, dh_final, flat_grads, feat2=None, recurrent_ready=None):
+        assert feat.dtype == torch.float32 and feat.is_contiguous()
+        return super()._backward(flat_params, feat, masks, T, N, ws, dhv, dh_final, flat_grads, None, recurrent_ready)
+
+
+def _pooled(embed_in: int, hidden: int = 512, num_goals: int = 12, sensors=(), num_actions: int = 6, prev_action_dims: int = 0,
+            prev_action_null: int = 1, rnn_type: str = "GRU", rnn_layers: int = 1) -> PooledPolicyHandle:
+    """``PolicyHandle.pooled(...)``: the handle of the pooled-embedding net (``PooledPolicyHandle``)."""
+    return PooledPolicyHandle(embed_in, hidden, num_goals, sensors, num_actions, prev_action_dims, prev_action_null, rnn_type, rnn_layers)
+
+
+PolicyHandle.pooled = staticmethod(_pooled)
+
+
 def memory_to_state(mem: torch.Tensor, rnn_type: str = "GRU", rnn_layers: int = 1) -> torch.Tensor:
     """Upstream's recurrent memory -> the handle's state rows.  ``mem``: ``[L, N, H]`` (GRU) or ``[2L, N, H]`` (LSTM: all ``h``
     layers, then all ``c`` layers -- ``torch.cat([h, c], 0)``, [U] RNNStateEncoder).  Returns ``[N, L * SW]``, layer-major:

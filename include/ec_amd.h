@@ -807,6 +807,84 @@ int ec_policy_act_pa(const ec_policy_t* h, const float* params, const void* feat
                      const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The pooled-embedding net: habitat-lab's PointNavResNetNet over ONE vector per frame (the pooled CLIP embedding) -- the
+ * Habitat DD-PPO branch of readme_files/baselines_habitat.md.  [U] restated from the published habitat-lab sources
+ * (habitat_baselines/rl/ddppo/policy/resnet_policy.py), which are not under the reference tree: parity unpinned.
+ *   v   = ReLU(W_fc e + b_fc)                      e: pooled embedding [D]; visual_fc W_fc [H, D]
+ *   x   = [ v | Emb_goal[goal] | W_1 s_1 + b_1 | ... | W_S s_S + b_S | Emb_prev[(prev + 1) * mask] ]
+ *   h   = RNN(x, m * h_prev)                       GRU | LSTM, 1..EC_RNN_MAX_LAYERS layers
+ *   logits = W_a h + b_a ; value = W_c h + b_c
+ * s_i are small float sensors (PointNav's (rho, cos -phi, sin -phi); ObjectNav's GPS and (cos c, sin c) compass); the caller
+ * hands over the embeddings' inputs, the polar / compass transforms are its own.
+ * Flat parameter order: visual_fc weight [H, D], bias [H]; obj_categories_embedding.weight [num_goals, embed_dims] if
+ * num_goals > 0; per sensor weight [embed_dims, k_i], bias [embed_dims]; state_encoder.rnn.{weight_ih,weight_hh,bias_ih,bias_hh}_l0
+ * with weight_ih_l0 [G, H + embed_dims * (ids + S) + E] (ids = num_goals > 0; column order: the x above); actor weight, bias;
+ * critic weight, bias; prev_action_embedding.weight [A + null, E] if E > 0; the upper layers' four tensors per layer.
+ * Nothing [T*N, embed_dims]-shaped exists: every side input reaches the input projection through weight-derived tables
+ * (Wg, W_i', Wp: the column blocks of weight_ih_l0 behind its first H columns)
+ *   GT = Emb_goal Wg^T [num_goals, G];  PT = ec_prev_action_table;  SV[:, cols_i] = W_i' W_i [G, K];  sb = sum_i W_i' b_i [G]
+ *   gi = v weight_ih_l0[:, :H]^T + b_ih + sb + GT[goal] + PT[row] + SV s     (s: the K = sum k_i sensor floats, k ascending)
+ * built per EC_POLICY_INFER call, kept under EC_POLICY_INFER_REUSE, rebuilt per learn pass, with a dense [G, H] copy of
+ * weight_ih_l0[:, :H]: no GEMM reads weight_ih_l0 in place.  No float atomics on any route of such a handle: two learn passes
+ * give equal bits, and an actor's result does not depend on how the actors are sliced.
+ * ec_policy_create_pooled: EC_ERR_ARG for a NULL argument, num_goals == 0 && num_sensors == 0 (the net needs a goal),
+ * num_sensors outside 0..3, a sensor width < 1, K > 8, embed_dims outside 1..64, num_goals outside 0..256, num_actions outside
+ * 2..256, the previous-action fields as in ec_policy_cfg, rnn_type / num_layers as in ec_policy_create_rnn_layers;
+ * EC_ERR_SHAPE for embed_in outside 64..4096 or % 4, and for a hidden ec_policy_create_rnn(EC_RNN_LSTM) refuses.
+ * The handle answers ec_policy_num_param_tensors / _flat_size / _param_offset / _workspace_bytes / _state_width / _rnn_type /
+ * _rnn_layers / _destroy, and ec_policy_backward3 (feat = the embedding rows f32 [T*N, D]; feat2 and feat_bf16 are ignored).
+ * Every other forward / act entry point returns EC_ERR_ARG on it, and the two below EC_ERR_ARG on every other handle.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+    int embed_in;        /* D: 64..4096, % 4 == 0 */
+    int hidden;          /* H: the widths ec_policy_create_rnn admits */
+    int embed_dims;      /* 32; 1..64: width of the goal-id embedding and of every sensor embedding */
+    int num_goals;       /* 0: no goal-id embedding; else nn.Embedding(num_goals, embed_dims) */
+    int num_sensors;     /* 0..3 */
+    int sensor_in[3];    /* k_i >= 1, K = sum k_i <= 8 */
+    int num_actions;     /* 2..256 */
+    int prev_action_dims, prev_action_null;   /* as in ec_policy_cfg */
+    int rnn_type, num_layers;                 /* EC_RNN_GRU | EC_RNN_LSTM, 1..EC_RNN_MAX_LAYERS */
+} ec_pooled_cfg;
+int ec_policy_create_pooled(ec_policy_t** out, const ec_pooled_cfg* cfg);
+int ec_policy_is_pooled(const ec_policy_t* h);         /* 1 | 0 (0: NULL handle) */
+/* embed f32 [T*N, D] (16-byte aligned); goal int64 [T*N] (num_goals > 0) | NULL; sensors f32 [T*N, K] (num_sensors > 0) | NULL;
+ * prev_actions int64 [T*N] (prev_action_dims > 0) | NULL -- a NULL argument must match a part the handle does not have, and the
+ * reverse, else EC_ERR_ARG.  The other arguments: ec_policy_forward2's.  A goal id outside [0, num_goals) adds nothing.  A learn
+ * pass leaves goal ids, sensors and previous actions in the workspace for ec_policy_backward3.
+ * T > 1, and T = 1 on the general route: ec_gemm_f32 with ReLU, an ec_gemm_f32 input projection, one rows-add launch for the
+ * tables, then the step kernels and heads of every other handle.  T = 1 inference with D % 56 == 0 or D % 64 == 0 and
+ * h_final != h0 (EC_POOLED_ACT=0 in the environment: the general route): 2 + L launches with reused tables --
+ * pooled_fc_act_kernel, pooled_step0_kernel (layer 0: both projections, the table rows and the cell), one rnn_stack launch per
+ * upper layer, the heads.  Inference heads: up to 7 actions the one-wave-per-row launch, above it ec_heads_wide's launch (with
+ * or without a selection), so a row of hv does not depend on how the actors are sliced on any inference route. */
+int ec_policy_forward_pooled(const ec_policy_t* h, const float* params, const float* embed, const int64_t* goal,
+                             const float* sensors, const int64_t* prev_actions, const float* h0, const float* masks, int T, int N,
+                             void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream);
+/* The same at T = 1 in one call with the selection arguments of ec_policy_act_ex (2..256 actions: the narrow sampling heads
+ * up to 7, ec_heads_wide above): bit for bit ec_policy_forward_pooled followed by the stand-alone selection. */
+int ec_policy_act_pooled(const ec_policy_t* h, const float* params, const float* embed, const int64_t* goal, const float* sensors,
+                         const int64_t* prev_actions, const float* h0, const float* masks, int N, void* workspace,
+                         size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
+                         int greedy, uint64_t seed, uint64_t step, int first_actor, const int64_t* expert_actions,
+                         const float* expert_mask, float force_p, ec_stream_t stream);
+/* The two act-step kernels alone (tests, benchmarks).
+ * ec_pooled_fc_act: v [N, H] = ReLU(e [N, D] w [H, D]^T + b); wfrag: H * D floats of scratch that receive w in MFMA fragment
+ *   order.  A workgroup owns a 32 x 32 output tile, its 7 (D % 56 == 0) or 8 (D % 64 == 0) waves split K = D on
+ *   v_mfma_f32_32x32x2_f32 and fold through LDS in wave order.  EC_ERR_SHAPE unless one of the two holds and H % 32 == 0;
+ *   EC_ERR_ARG for a NULL or misaligned (16 bytes) e, w, wfrag.
+ * ec_pooled_step0_fwd: ec_rnn_stack_step_fwd whose x half also receives, in this order, sb [G] | NULL, gt[goal[n]] ([num_goals, G],
+ *   goal int64 [N]) | both NULL, pt[row(prev[n], mask[n])] ([A + null_token, G], prev int64 [N]) | both NULL, and
+ *   sum_k sv[:, k] sensors[n, k] (sv [G, K], sensors [N, K], K <= 8, k ascending) | both NULL.  In place (h_out == state_prev)
+ *   is refused with EC_ERR_ARG: a workgroup reads rows of state_prev that another one writes. */
+int ec_pooled_fc_act(const float* e, const float* w, const float* b, float* wfrag, float* v, int N, int D, int H, ec_stream_t stream);
+int ec_pooled_step0_fwd(int rnn_type, const float* x, long ld_x, const float* wih, const float* whh, const float* bih,
+                        const float* bhh, const float* sb, const float* gt, const int64_t* goal, int num_goals, const float* pt,
+                        const int64_t* prev_actions, int null_token, int A, const float* sv, const float* sensors, int K,
+                        const float* state_prev, long ld_prev, const float* mask, float* h_out, long ld_h, float* c_out, long ld_c,
+                        float* h_out2, long ld_h2, int N, int H, ec_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * CLIP VisionTransformer embedder == [U] allenact ClipViTEmbedder.forward over
  * [U] openai/CLIP VisionTransformer: patch-embed, class +
  * positional embedding, ln_pre, then `layers_run` ResidualAttentionBlocks

@@ -35,6 +35,11 @@
 //                                                   LSTM): ec_policy_create_rnn_layers instead of ec_policy_create.
 //                                                   `W <bytes>` is the workspace size, `D <bytes>` a device-to-device
 //                                                   hipMemcpyAsync (policy commands only)
+//   pooled D H ed goals ns k0 k1 k2 A E null rnn L T N mode reuse inplace act
+//                                                   ec_policy_create_pooled + ec_policy_workspace_bytes + ec_policy_forward_pooled
+//                                                   (+ ec_policy_backward2 with mode 2) + destroy; mode / reuse / `W` / `B` / `F` / `D`
+//                                                   as for `policy`; inplace 1: h_final == h0;
+//                                                   act 1 (T = 1, mode 0): ec_policy_act_pooled, sampling, instead of the forward
 // Output: `K <kernel>` per registered kernel, then per command `C <command>`, one `L <kernel>|<grid>|<block>|<lds>` per
 // launch (with --args N: `|` + the first N bytes of the first kernel argument in hex, for the conv_igemm kernels) and `R <rc>`.
 #include <cxxabi.h>
@@ -236,6 +241,49 @@ static int run_policy(const int* v) {
     return rc;
 }
 
+// v: embed_in hidden embed_dims num_goals num_sensors k0 k1 k2 num_actions prev_action_dims prev_action_null rnn_type num_layers,
+// then T, N, mode, reuse, inplace, act
+static int run_pooled(const int* v) {
+    typedef void* P;
+    const int T = v[13], N = v[14], mode = v[15], reuse = v[16], inplace = v[17], act = v[18];
+    const bool learn_pass = mode == 2;
+    if (mode < 0 || mode > 2 || (reuse && mode != 0) || (act && (mode != 0 || T != 1))) return -100;
+    void* h = nullptr;
+    int cfg[13];
+    memcpy(cfg, v, sizeof cfg);                         // ec_pooled_cfg: thirteen ints in this order
+    int rc = sym<int (*)(P*, const int*)>("ec_policy_create_pooled")(&h, cfg);
+    if (rc) return rc;
+    const size_t ws = sym<size_t (*)(P, int, int, int)>("ec_policy_workspace_bytes")(h, T, N, mode != 0);
+    printf("W %zu\n", ws);
+    const P params = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4), embed = fake(1u << 30);
+    const P goal = v[3] ? fake(1u << 20) : nullptr, sens = v[4] ? fake(1u << 20) : nullptr, prev = v[9] ? fake(1u << 20) : nullptr;
+    const P h0 = fake(1u << 24), masks = fake(1u << 20), wsp = fake(ws), hv = fake(1u << 24), hf = inplace ? h0 : fake(1u << 24);
+    auto fwd_ = sym<int (*)(P, P, P, P, P, P, P, P, int, int, P, size_t, int, P, P, P)>("ec_policy_forward_pooled");
+    auto act_ = sym<int (*)(P, P, P, P, P, P, P, P, int, P, size_t, int, P, P, P, P, P, int, uint64_t, uint64_t, int, P, P, float, P)>(
+        "ec_policy_act_pooled");
+    const P actions = fake(1u << 20), logp = fake(1u << 20);
+    auto fwd = [&](P h_, P pr, P e, P g, P sn, P pv, P h0_, P m, int T_, int N_, P w, size_t wb, int md, P hv_, P hf_, P st) {
+        if (!act) return fwd_(h_, pr, e, g, sn, pv, h0_, m, T_, N_, w, wb, md, hv_, hf_, st);
+        return act_(h_, pr, e, g, sn, pv, h0_, m, N_, w, wb, md == 2, hv_, hf_, actions, logp, nullptr, 0, 1, 2, 0, nullptr, nullptr, 0.f, st);
+    };
+    g_log_copies = 1;
+    if (reuse) {
+        rc = fwd(h, params, embed, goal, sens, prev, h0, masks, T, N, wsp, ws, 0 /* EC_POLICY_INFER */, hv, hf, nullptr);
+        printf("B %d\n", rc);
+    }
+    if (!rc) rc = fwd(h, params, embed, goal, sens, prev, h0, masks, T, N, wsp, ws, reuse ? 2 /* EC_POLICY_INFER_REUSE */ : mode != 0, hv, hf, nullptr);
+    if (learn_pass) {
+        printf("F %d\n", rc);
+        const P dhv = fake(1u << 24), grads = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4);
+        if (!rc)
+            rc = sym<int (*)(P, P, P, P, int, P, int, int, P, size_t, P, P, P, P)>("ec_policy_backward2")(h, params, embed, nullptr, 0, masks, T, N, wsp,
+                                                                                                        ws, dhv, nullptr, grads, nullptr);
+    }
+    g_log_copies = 0;
+    sym<void (*)(P)>("ec_policy_destroy")(h);
+    return rc;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) { fprintf(stderr, "usage: launch_log LIB [--args N] < commands\n"); return 2; }
     if (argc >= 4 && !strcmp(argv[2], "--args")) g_dump_args = atoi(argv[3]);
@@ -258,13 +306,15 @@ int main(int argc, char** argv) {
         int v[20] = {0}, n = 0, rc = -100;
         std::string kind;
         if (cmd == "trunk" || cmd == "tower") ss >> kind;
-        const int nmax = cmd == "policy" ? 20 : cmd == "tower" ? 9 : 10;
+        const int nmax = cmd == "policy" ? 20 : cmd == "pooled" ? 19 : cmd == "tower" ? 9 : 10;
         while (n < nmax && ss >> v[n]) ++n;
         std::string input;
         if (cmd == "tower" && n == 9 && ss >> input) {
             rc = run_tower(kind, v, input);
         } else if (cmd == "policy" && n >= 18 && n <= 20) {
             rc = run_policy(v);
+        } else if (cmd == "pooled" && n == 19) {
+            rc = run_pooled(v);
         } else if (cmd == "conv" && n == 10) {
             const P r = v[8] ? resb : nullptr;
             if (v[9] == 0)
