@@ -67,6 +67,11 @@ SIGNATURES = {
     "ec_stem_conv1_depth": (c_int, [c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "ec_rn50_forward_depth": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int,
                                       c_void_p]),
+    # the RGB-D encoder of the pooled net: both modalities in one pass of the plan, maps summed and average-pooled
+    "ec_spatial_mean_pair_bf16": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    "ec_rn50_rgbd_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "ec_rn50_embed_rgbd": (c_int, [c_void_p, c_void_p, c_int, C.POINTER(c_float), C.POINTER(c_float), c_void_p, c_float, c_float,
+                                   c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
     "ec_rn50_num_ops": (c_int, [c_void_p]),
     "ec_rn50_plan_hash": (C.c_uint64, [c_void_p]),
     "ec_rn50_set_conv8_min_tiles": (c_int, [c_void_p, c_int]),

@@ -53,6 +53,7 @@ EcConfig read_config() {
     c.dw_transposed = env_int("EC_DW_TRANSPOSED", 1);
     c.rnn_stack = env_int("EC_RNN_STACK", 1);
     c.pooled_act = env_int("EC_POOLED_ACT", 1);
+    c.rgbd_joint = env_int("EC_RGBD_JOINT", 1);
     c.vit_wide = env_int("EC_VIT_WIDE", 1);
     c.vit_bm192 = env_int("EC_VIT_BM192", 1);
     return c;

@@ -235,6 +235,8 @@ struct EcConfig {
                           //                        layer-by-layer route.  NOT part of ec_config_hash(): no single-layer plan reads it
     int pooled_act;       // EC_POOLED_ACT    (1)   act step of a pooled-embedding handle: pooled_fc_act_kernel + pooled_step0_kernel (pooled_net.hip);
                           //                        0: the general route.  NOT part of ec_config_hash(): no other handle's plan reads it
+    int rgbd_joint;       // EC_RGBD_JOINT    (1)   ec_rn50_embed_rgbd: the RGB and the depth frames of a chunk in ONE pass of the plan at twice the frames;
+                          //                        0: two passes, RGB then depth.  NOT part of ec_config_hash(): no plan reads it, only the pass count
     // --- ViT / text GEMMs (ec_gemm_bf16_ln8).  NOT part of ec_config_hash(): the profile summaries under profiles/ are keyed by the hash as it was ---
     int vit_wide;         // EC_VIT_WIDE      (1)   0: 128-wide tiles only, 2: 256-wide wherever N allows
     int vit_bm192;        // EC_VIT_BM192     (1)   0: no 192-row tiles

@@ -472,19 +472,24 @@ extern "C" size_t ec_rn50_workspace_bytes(const ec_rn50_t* h, int batch) {
 namespace {
 // What the frames are: the stem op is the only one that looks at them.
 struct FrameIn {
-    enum Kind { F32, U8, DEPTH } kind;
-    const void* p;                 // F32: fp32 [B,R,R,3]; U8: uint8 [B,R,R,3]; DEPTH: fp32 [B,R,R] (one channel)
-    const float *mean3, *std3;     // U8: host pointers
-    float scale, shift;            // DEPTH: value = depth * scale + shift
-    const float* stem_w9;          // DEPTH: the stem weights summed over the input channels, f32 [9][stem channels]
+    enum Kind { F32, U8, DEPTH, RGBD } kind;
+    const void* p;                 // F32: fp32 [B,R,R,3]; U8: uint8 [B,R,R,3]; DEPTH: fp32 [B,R,R] (one channel); RGBD: the RGB frames
+    const float *mean3, *std3;     // uint8 RGB frames: host pointers
+    float scale, shift;            // DEPTH, RGBD: value = depth * scale + shift
+    const float* stem_w9;          // DEPTH, RGBD: the stem weights summed over the input channels, f32 [9][stem channels]
+    const float* depth = nullptr;  // RGBD: the depth frames fp32 [B,R,R] that pair with p, frame by frame
+    bool rgb_u8 = false;           // RGBD: p is uint8
+    bool u8() const { return kind == U8 || (kind == RGBD && rgb_u8); }
 };
 struct Run {   // one chunk of frames on its way through the plan
     const ec_rn50* h;
     const FrameIn& in;
-    const void* frames; int nb;   // this chunk's frames
+    const void* frames;    // this chunk's RGB frames, or NULL
+    const float* depth;    // this chunk's depth frames, or NULL.  With both, the chunk is nb / 2 RGB frames, then nb / 2 depth frames
+    int nb;                // frames on their way through the plan
     unsigned char* base;   // the workspace: NBUF buffers of bufsz bytes
     size_t bufsz;
-    void* out;             // this chunk's rows of the caller's feature tensor
+    void* out;             // where the last op writes: this chunk's rows of the caller's feature tensor, or of the RGB-D pass's map region
     hipStream_t stream;
     bool pooled_emitted;   // the last OP_CONV_POOLOUT wrote the pooled copy of its output: the OP_POOL marked pool_of is skipped
     void* buf(int id) const { return id == BUF_OUT ? out : base + (size_t)id * bufsz; }
@@ -510,12 +515,19 @@ int run_stem(const Run& r, const Op& o) {
     const Conv& c = o.c;
     const float* bias = r.h->bias + c.at.b;
     if (o.kind == OP_STEM7)
-        return ec_stem7_pool(r.frames, in.kind == FrameIn::U8 ? 1 : 0, in.mean3, in.std3, r.h->stem_w, bias, r.buf(c.dst), r.nb, c.H, c.W, r.stream);
-    if (in.kind == FrameIn::DEPTH)
-        return ec_stem_conv1_depth((const float*)r.frames, in.scale, in.shift, in.stem_w9, bias, r.buf(c.dst), r.nb, c.H, c.W, c.Cout, r.stream);
-    if (in.kind == FrameIn::U8)
-        return ec_stem_conv1_u8((const uint8_t*)r.frames, in.mean3, in.std3, r.h->stem_w, bias, r.buf(c.dst), r.nb, c.H, c.W, c.Cout, r.stream);
-    return ec_stem_conv1((const float*)r.frames, r.h->stem_w, bias, r.buf(c.dst), r.nb, c.H, c.W, c.Cout, r.stream);
+        return ec_stem7_pool(r.frames, in.u8() ? 1 : 0, in.mean3, in.std3, r.h->stem_w, bias, r.buf(c.dst), r.nb, c.H, c.W, r.stream);
+    // RGB frames fill the destination's first rows, depth frames the rows behind them: a joint RGB-D chunk is two launches into one
+    // buffer, and every later op sees nb frames of the same tensor
+    const int n_rgb = !r.frames ? 0 : r.depth ? r.nb / 2 : r.nb;
+    int rc = EC_OK;
+    if (n_rgb && in.u8())
+        rc = ec_stem_conv1_u8((const uint8_t*)r.frames, in.mean3, in.std3, r.h->stem_w, bias, r.buf(c.dst), n_rgb, c.H, c.W, c.Cout, r.stream);
+    else if (n_rgb)
+        rc = ec_stem_conv1((const float*)r.frames, r.h->stem_w, bias, r.buf(c.dst), n_rgb, c.H, c.W, c.Cout, r.stream);
+    if (rc != EC_OK || !r.depth) return rc;
+    const size_t frame_out = (size_t)((c.H - 1) / 2 + 1) * ((c.W - 1) / 2 + 1) * c.Cout;   // (the stem conv strides by 2, pad 1)
+    return ec_stem_conv1_depth(r.depth, in.scale, in.shift, in.stem_w9, bias, (uint16_t*)r.buf(c.dst) + (size_t)n_rgb * frame_out, r.nb - n_rgb,
+                               c.H, c.W, c.Cout, r.stream);
 }
 
 int run_pool(Run& r, const Op& o) {
@@ -593,26 +605,35 @@ int run_btail(const Run& r, const Op& o) {
     return rc == EC_OK ? run_conv(r, c2) : rc;
 }
 
+// An RGB-D chunk of nb pairs: one pass of the plan at 2 nb frames (EC_RGBD_JOINT, default 1), or two passes at nb frames, RGB then depth.
+// The only place that chooses, per chunk.  Measured at 32 / 64 / 128 pairs (profiles/rgbd_pooled_bench.txt) the joint pass is
+// 14-26 % faster than two forwards, two pools and an add, so no pair count is sent to the composed route.
+bool rgbd_joint(int /*pairs*/) { return ec_config().rgbd_joint != 0; }
+
+// feat: bf16 [batch, S, S, C], the last op's output -- or, for FrameIn::RGBD, f32 [batch, C]: the mean over the pixels of the RGB
+// frame's map plus the depth frame's (ec_spatial_mean_pair_bf16), `batch` and `chunk` counting PAIRS; the maps of a chunk live in
+// the workspace behind the NBUF buffers (ec_rn50_rgbd_workspace_bytes).
 int rn50_run(const ec_rn50_t* h, const FrameIn& in, int batch, void* workspace, size_t ws_bytes, void* feat, int chunk,
              ec_stream_t stream_main) {
-    if (!h || !in.p || !workspace || !feat) return EC_ERR_ARG;
+    const bool rgbd = in.kind == FrameIn::RGBD;
+    if (!h || !in.p || !workspace || !feat || (rgbd && !in.depth)) return EC_ERR_ARG;
     if (batch <= 0) return EC_ERR_SHAPE;
-    if (in.kind == FrameIn::DEPTH && (h->ops.empty() || h->ops.front().kind != OP_STEM1))
+    if ((in.kind == FrameIn::DEPTH || rgbd) && (h->ops.empty() || h->ops.front().kind != OP_STEM1))
         return EC_ERR_UNSUPPORTED;   // the 7x7 stem of the torchvision towers has no one-channel kernel
     if (chunk <= 0 || chunk > batch) chunk = batch;
+    const int per = rgbd ? 2 : 1;   // frames in the buffers per unit of `chunk`
     {   // the conv kernels address activations through 32-bit buffer descriptors (< 2 GiB per tensor)
-        const long maxc = ((1L << 31) - 1) / (long)(h->max_elems_per_frame * 2);
+        const long maxc = ((1L << 31) - 1) / (long)(h->max_elems_per_frame * 2) / per;
         if (chunk > maxc) chunk = (int)(maxc > 0 ? maxc : 1);
     }
-    if (ws_bytes < ec_rn50_workspace_bytes(h, chunk)) return EC_ERR_WORKSPACE;
+    if (ws_bytes < (rgbd ? ec_rn50_rgbd_workspace_bytes(h, chunk) : ec_rn50_workspace_bytes(h, chunk))) return EC_ERR_WORKSPACE;
     const ec_min_tiles_scope mint_scope(h->conv8_min_tiles);   // this handle's dispatch threshold, for this call only
-    const size_t bufsz = align_up(h->max_elems_per_frame * 2 * (size_t)chunk, 256);
+    const size_t bufsz = align_up(h->max_elems_per_frame * 2 * (size_t)chunk * per, 256);
     // bytes per frame: a depth frame has ONE channel
-    const size_t frame_bytes = (size_t)h->res * h->res * (in.kind == FrameIn::DEPTH ? 1 : 3) * (in.kind == FrameIn::U8 ? 1 : 4);
+    const size_t frame_bytes = (size_t)h->res * h->res * (in.kind == FrameIn::DEPTH ? 1 : 3) * (in.u8() ? 1 : 4);
     const size_t out_stride = (size_t)h->out_sp * h->out_sp * h->out_c;
-    for (int b0 = 0; b0 < batch; b0 += chunk) {
-        Run r{h, in, (const unsigned char*)in.p + (size_t)b0 * frame_bytes, std::min(chunk, batch - b0), (unsigned char*)workspace, bufsz,
-              (uint16_t*)feat + (size_t)b0 * out_stride, (hipStream_t)stream_main, false};
+    const hipStream_t stream = (hipStream_t)stream_main;
+    auto pass = [&](Run r) -> int {   // the one walk over the plan
         for (const Op& o : h->ops) {
             int rc;
             switch (o.kind) {
@@ -628,10 +649,53 @@ int rn50_run(const ec_rn50_t* h, const FrameIn& in, int batch, void* workspace, 
             }
             if (rc != EC_OK) return rc;
         }
+        return EC_OK;
+    };
+    unsigned char* const base = (unsigned char*)workspace;
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+        const int nb = std::min(chunk, batch - b0);
+        const void* frames = (const unsigned char*)in.p + (size_t)b0 * frame_bytes;
+        int rc;
+        if (!rgbd) {
+            const bool d = in.kind == FrameIn::DEPTH;
+            rc = pass(Run{h, in, d ? nullptr : frames, d ? (const float*)frames : nullptr, nb, base, bufsz,
+                          (uint16_t*)feat + (size_t)b0 * out_stride, stream, false});
+        } else {
+            const float* dep = in.depth + (size_t)b0 * h->res * h->res;
+            uint16_t* map = (uint16_t*)(base + NBUF * bufsz);   // [2 nb, S, S, C]: the RGB frames' maps, then the depth frames'
+            if (rgbd_joint(nb)) {
+                rc = pass(Run{h, in, frames, dep, 2 * nb, base, bufsz, map, stream, false});
+            } else {
+                rc = pass(Run{h, in, frames, nullptr, nb, base, bufsz, map, stream, false});
+                if (rc == EC_OK) rc = pass(Run{h, in, nullptr, dep, nb, base, bufsz, map + (size_t)nb * out_stride, stream, false});
+            }
+            if (rc == EC_OK)
+                rc = ec_spatial_mean_pair_bf16(map, map + (size_t)nb * out_stride, (float*)feat + (size_t)b0 * h->out_c, nb,
+                                               h->out_sp * h->out_sp, h->out_c, stream_main);
+        }
+        if (rc != EC_OK) return rc;
     }
     return EC_OK;
 }
 }  // namespace
+
+extern "C" size_t ec_rn50_rgbd_workspace_bytes(const ec_rn50_t* h, int pairs) {
+    if (!h || pairs <= 0) return 0;
+    const size_t map = (size_t)2 * pairs * h->out_sp * h->out_sp * h->out_c * sizeof(uint16_t);
+    return ec_rn50_workspace_bytes(h, 2 * pairs) + align_up(map, 256);
+}
+
+// [U] ResNetCLIPEncoder.forward with rgb and depth (habitat branch): the trunk on both frames of every pair, the two maps summed and
+// average-pooled to ONE vector.  Both towers read the same weights, so a chunk of nb pairs is one pass of the plan at 2 nb frames.
+extern "C" int ec_rn50_embed_rgbd(const ec_rn50_t* h, const void* rgb, int rgb_u8, const float* h_mean3, const float* h_std3,
+                                  const float* depth, float scale, float shift, const float* stem_w9, int pairs, void* workspace,
+                                  size_t ws_bytes, float* embed, int chunk, ec_stream_t stream) {
+    if (!depth || !stem_w9 || (rgb_u8 && (!h_mean3 || !h_std3))) return EC_ERR_ARG;
+    FrameIn in{FrameIn::RGBD, rgb, h_mean3, h_std3, scale, shift, stem_w9};
+    in.depth = depth;
+    in.rgb_u8 = rgb_u8 != 0;
+    return rn50_run(h, in, pairs, workspace, ws_bytes, embed, chunk, stream);
+}
 
 extern "C" int ec_rn50_forward(const ec_rn50_t* h, const float* rgb, int batch, void* workspace, size_t ws_bytes,
                                void* feat, int chunk, ec_stream_t stream) {

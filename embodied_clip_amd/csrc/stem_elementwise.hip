@@ -352,7 +352,73 @@ __global__ __launch_bounds__(256) void spatial_mean_kernel(const uint16_t* __res
     out[i] = s / (float)HW;
 }
 
+// mean over HW of (a + b), bf16 [B, HW, C] each -> fp32 [B, C].  100 KB in and 8 KB out per 2048 x 49 pair: pure streaming, so the
+// grid is shaped for small launches -- a workgroup owns one pair and a slab of PM_G 8-channel groups (512 contiguous bytes of
+// every pixel row), its 8 row parts take the pixels hw = part, part + 8, ... with one 16-byte load per tensor and pixel (all of a
+// part's loads are independent), and the parts' fp32 partials are folded through LDS in part order: 32 pairs x 2048 channels are
+// 256 workgroups of 4 waves.  No atomics: the summation order is fixed by the shape alone.
+constexpr int PM_G = 32, PM_PARTS = 8;
+__global__ __launch_bounds__(256) void spatial_mean_pair_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b,
+                                                               float* __restrict__ out, int HW, int C8, int slabs) {
+    __shared__ __attribute__((aligned(16))) float part[PM_PARTS][PM_G * 8];
+    const int n = blockIdx.x / slabs, g0 = (blockIdx.x % slabs) * PM_G;
+    const int gl = threadIdx.x % PM_G, p = threadIdx.x / PM_G, g = g0 + gl;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (g < C8) {
+        const long row0 = (long)n * HW * C8 + g;
+        const uint4* pa = reinterpret_cast<const uint4*>(a) + row0;
+        const uint4* pb = reinterpret_cast<const uint4*>(b) + row0;
+#pragma unroll 4
+        for (int hw = p; hw < HW; hw += PM_PARTS) {
+            const uint4 va = pa[(long)hw * C8], vb = pb[(long)hw * C8];
+            acc[0] += ec_lo(va.x) + ec_lo(vb.x); acc[1] += ec_hi(va.x) + ec_hi(vb.x);
+            acc[2] += ec_lo(va.y) + ec_lo(vb.y); acc[3] += ec_hi(va.y) + ec_hi(vb.y);
+            acc[4] += ec_lo(va.z) + ec_lo(vb.z); acc[5] += ec_hi(va.z) + ec_hi(vb.z);
+            acc[6] += ec_lo(va.w) + ec_lo(vb.w); acc[7] += ec_hi(va.w) + ec_hi(vb.w);
+        }
+    }
+    *reinterpret_cast<float4*>(&part[p][gl * 8]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    *reinterpret_cast<float4*>(&part[p][gl * 8 + 4]) = make_float4(acc[4], acc[5], acc[6], acc[7]);
+    __syncthreads();
+    const int c = g0 * 8 + (int)threadIdx.x;      // one output channel per thread: 256 consecutive floats per workgroup
+    if (c < C8 * 8) {
+        float s = part[0][threadIdx.x];
+#pragma unroll
+        for (int q = 1; q < PM_PARTS; ++q) s += part[q][threadIdx.x];
+        out[(long)n * C8 * 8 + c] = s / (float)HW;
+    }
+}
+
+// ... any C, any alignment: one thread per (pair, channel), 2-byte loads
+__global__ __launch_bounds__(256) void spatial_mean_pair_scalar_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b,
+                                                                      float* __restrict__ out, int HW, int C, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long off = (i / C) * HW * C + (i % C);
+    float s = 0.f;
+    for (int hw = 0; hw < HW; ++hw) s += ec_bf2f(a[off + (long)hw * C]) + ec_bf2f(b[off + (long)hw * C]);
+    out[i] = s / (float)HW;
+}
+
 }  // namespace
+
+extern "C" int ec_spatial_mean_pair_bf16(const void* a, const void* b, float* out, int B, int HW, int C, ec_stream_t stream) {
+    if (!a || !b || !out) return EC_ERR_ARG;
+    if (B <= 0 || HW <= 0 || C <= 0) return EC_ERR_SHAPE;
+    if ((C & 7) == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0) {
+        const int C8 = C / 8, slabs = (C8 + PM_G - 1) / PM_G;
+        if ((long)B * slabs > 0x7fffffffL) return EC_ERR_SHAPE;
+        hipLaunchKernelGGL(spatial_mean_pair_kernel, dim3((unsigned)(B * slabs)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)a,
+                           (const uint16_t*)b, out, HW, C8, slabs);
+    } else {
+        const long total = (long)B * C;
+        if ((total + 255) / 256 > 0x7fffffffL) return EC_ERR_SHAPE;
+        hipLaunchKernelGGL(spatial_mean_pair_scalar_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const uint16_t*)a, (const uint16_t*)b, out, HW, C, total);
+    }
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
 
 extern "C" int ec_stem_conv1(const float* rgb, const float* w, const float* bias, void* out, int B, int H, int W,
                              int Cout, ec_stream_t stream) {

@@ -169,6 +169,7 @@ class RN50Trunk:
         self.out_channels = self.lib.ec_rn50_out_channels(self.h)
         self.out_spatial = self.lib.ec_rn50_out_spatial(self.h)
         self._ws: Optional[torch.Tensor] = None
+        self._ws_rgbd: Optional[torch.Tensor] = None      # embed_rgbd's: the plan's buffers at twice the frames plus the maps
         self._resize: Optional[ClipResizeCrop] = None
 
     _pack = staticmethod(pack_rn50)
@@ -262,6 +263,38 @@ class RN50Trunk:
         _lib.check(self.lib.ec_rn50_forward_depth(self.h, depth.data_ptr(), float(scale), float(shift), self.stem_w9.data_ptr(),
                                                   B, ws.data_ptr(), ws.numel(), out.data_ptr(), chunk, _lib.stream_ptr()),
                    "ec_rn50_forward_depth")
+        return out
+
+    @_lib.on_device
+    def embed_rgbd(self, rgb: torch.Tensor, depth: torch.Tensor, out: Optional[torch.Tensor] = None, scale: float = 1.0,
+                   shift: float = 0.0, mean=(0.48145466, 0.4578275, 0.40821073),
+                   std=(0.26862954, 0.26130258, 0.27577711)) -> torch.Tensor:
+        """The RGB-D encoder of the Habitat DD-PPO net ([U] habitat branch ``ResNetCLIPEncoder`` with rgb and depth; restated,
+        parity unpinned): ``adaptive_avg_pool2d(trunk(rgb) + trunk(depth), 1).flatten(1)`` -> fp32 [B, C].  rgb: device fp32
+        [B, R, R, 3] (normalised) or uint8 (raw; /255 and ``mean`` / ``std`` fused into the stem); depth as ``forward_depth``.
+        Both frames of a pair go through the plan in ONE pass at 2 B frames (``ec_rn50_embed_rgbd``; ``chunk`` counts pairs)."""
+        assert rgb.is_cuda and rgb.dtype in (torch.float32, torch.uint8) and rgb.is_contiguous()
+        assert depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
+        assert depth.dim() in (3, 4) and (depth.dim() == 3 or depth.shape[3] == 1), depth.shape
+        B, R, R2 = depth.shape[:3]
+        assert R == self.input_resolution and R2 == R, depth.shape
+        assert tuple(rgb.shape) == (B, R, R, 3), (rgb.shape, depth.shape)
+        if self.stem_w9 is None:
+            raise _lib.EcError("embed_rgbd: this tower has no one-channel stem (CLIP ModifiedResNet towers only)")
+        Cc = self.out_channels
+        if out is None:
+            out = torch.empty((B, Cc), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == B * Cc
+        chunk = self.chunk if self.chunk > 0 else B
+        need = self.lib.ec_rn50_rgbd_workspace_bytes(self.h, min(chunk, B))
+        if self._ws_rgbd is None or self._ws_rgbd.numel() < need:
+            self._ws_rgbd = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._ws_rgbd
+        u8 = rgb.dtype == torch.uint8
+        m3, s3 = ((C.c_float * 3)(*mean), (C.c_float * 3)(*std)) if u8 else (None, None)
+        _lib.check(self.lib.ec_rn50_embed_rgbd(self.h, rgb.data_ptr(), int(u8), m3, s3, depth.data_ptr(), float(scale), float(shift),
+                                               self.stem_w9.data_ptr(), B, ws.data_ptr(), ws.numel(), out.data_ptr(), chunk,
+                                               _lib.stream_ptr()), "ec_rn50_embed_rgbd")
         return out
 
     @_lib.on_device

@@ -203,8 +203,11 @@ def check_net(net: str, pooling: str, sensors, goal_ids: bool, encoder: str, dep
     sensors = tuple(int(k) for k in sensors)
     if pooling not in ("attnpool", "avgpool"):
         raise ValueError(f"pooling={pooling!r}: 'attnpool' or 'avgpool'")
-    if depth:
-        raise ValueError("net='pooled' with depth=True: the pooled net has no depth stream")
+    if depth and pooling != "avgpool":
+        # [U] ResNetCLIPEncoder removes the attention pool when it encodes rgb + depth: the two maps are summed and average-pooled
+        raise ValueError("net='pooled' with depth=True: the RGB-D encoder sums the two towers' maps and average-pools them; use pooling='avgpool'")
+    if depth and encoder in IMAGENET_ENCODERS:
+        raise ValueError(f"net='pooled' with depth=True: the 7x7 stem of {encoder!r} has no one-channel form; encoder='rn50'")
     if zeroshot:
         raise ValueError("net='pooled' with zeroshot=True: the zero-shot fusion policy is another net")
     if goal_in:
@@ -249,10 +252,19 @@ class _SlicedActor:
     ``self.lib``, ``self.dev`` / ``self.device``, ``self.zeroshot``, ``self._text_sd``, ``self._goal_tokens``, ``self.goal_in``,
     ``self._num_actions`` and ``self.depth`` first, and ``self.env`` between ``_build_model`` and ``_build_slices``.
 
-    ``self.depth`` (the RGB-D agent, readme_files/baselines_habitat.md:75): every slice's trunk handle also encodes the
-    env's depth batch (``RN50Trunk.forward_depth``: same frozen weights, one-channel stem) into a second feature buffer
-    ``sl.feat2``, and the policy is the dual-encoder variant."""
+    ``self.depth`` (an RGB-D agent, readme_files/baselines_habitat.md:75): the env serves depth frames and ``_observe`` hands
+    them to the encode step.  What the agent does with them is ``self.dual``:
+
+    * ``dual`` (``depth`` with the goal-encoder net; [U] AllenAct's two preprocessors): every slice's trunk handle also encodes
+      the depth batch (``RN50Trunk.forward_depth``: same frozen weights, one-channel stem) into a second feature buffer
+      ``sl.feat2``, and the policy is the dual-encoder variant.
+    * ``depth`` with the pooled net ([U] habitat branch ``ResNetCLIPEncoder``): ``RN50Trunk.embed_rgbd`` encodes both frames of
+      a pair in one pass into ONE vector; no second buffer, and the policy is the RGB pooled net's."""
     depth = False
+
+    @property
+    def dual(self) -> bool:
+        return self.depth and not self.pooled_net
     # the previous action's embedding ([U] VisualNavActorCritic add_prev_actions / Habitat's prev_action_embedding): its width
     # (0: off) and whether row 0 is the null token of an episode's first step; set by the users before ``_build_model``
     prev_action_dims = 0
@@ -342,7 +354,7 @@ class _SlicedActor:
         pkw = dict(in_channels=self.C, spatial=self.S, num_actions=self._num_actions)
         if self.goal_in:
             pkw["goal_in"] = self.goal_in
-        if self.depth:      # [U] ResnetDualTensorGoalEncoder: 25 tensors, rgb_* / depth_* compressors and combiners
+        if self.dual:      # [U] ResnetDualTensorGoalEncoder: 25 tensors, rgb_* / depth_* compressors and combiners
             pkw["dual"] = 1
         if self.zeroshot:
             assert encoder == "rn50", "the zero-shot variant uses the CLIP-RN50 image embedding"
@@ -408,9 +420,9 @@ class _SlicedActor:
             sl.stream = slice_streams[i]
             # zero-shot: the rollout buffer holds fp32 image embeddings [T+1, n, 1, 1024]; else bf16 feature maps
             sl.feat = torch.empty((feat_steps, n, S2, self.C), dtype=torch.float32 if self._embed else torch.bfloat16, device=d)
-            sl.feat2 = torch.empty_like(sl.feat) if self.depth else None      # the depth tower's features
+            sl.feat2 = torch.empty_like(sl.feat) if self.dual else None      # the depth tower's features
             sl.trunk_out = (torch.empty((n, self.trunk_S, self.trunk_S, self.trunk_C), dtype=torch.bfloat16, device=d)
-                            if self._embed else None)
+                            if self._embed and not self.depth else None)      # (embed_rgbd keeps its maps in its own workspace)
             sl.tok = (torch.empty((n, encs[i].L, encs[i].D), dtype=torch.bfloat16, device=d) if encoder == "vit" else None)
             sl.ws_act = torch.empty(self.policy.workspace_bytes(1, n, False), dtype=torch.uint8, device=d)
             sl.act_tables_valid = False     # weight-derived tables in ws_act (rebuilt by the first act step after an update)
@@ -448,12 +460,12 @@ class _SlicedActor:
     @property
     def feat2(self) -> Optional[torch.Tensor]:
         """The depth tower's features, laid out as ``feat`` (``depth=True``; else None)."""
-        if not self.depth:
+        if not self.dual:
             return None
         return self.slices[0].feat2 if self.ns == 1 else torch.cat([sl.feat2 for sl in self.slices], dim=1)
 
     def _f2(self, sl, t: int):
-        return sl.feat2[t] if self.depth else None
+        return sl.feat2[t] if self.dual else None
 
     def _observe(self, actions_host=None):
         """env.step: the next RGB batch and (``depth=True``) the depth batch that goes with it."""
@@ -499,7 +511,11 @@ class _SlicedActor:
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(torch.cuda.current_stream())
-        if self._embed:
+        if self._embed and self.depth:
+            # the pooled RGB-D agent: both frames of every pair through the plan in one pass, the two maps summed and average-pooled
+            # straight into the rollout slice (the depth wire form is synthetic.normalize_depth: scale 1, shift 0)
+            sl.enc.embed_rgbd(src, dep[sl.o:sl.o + sl.n], sl.feat[t].view(sl.n, self.C))
+        elif self._embed:
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.trunk_out)
             if self._embed == "attnpool":
                 sl.pool.forward(sl.trunk_out, sl.feat[t].view(sl.n, self.C))     # AttentionPool2d -> rollout slice
@@ -509,7 +525,7 @@ class _SlicedActor:
         elif self.encoder in ("rn50", "rn50x16") or self.encoder in IMAGENET_ENCODERS:
             # the last conv writes straight into the rollout slice
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.feat[t])
-            if self.depth:      # the depth tower: the same handle on the one-channel batch, behind the RGB tower on this stream
+            if self.dual:      # the depth tower: the same handle on the one-channel batch, behind the RGB tower on this stream
                 sl.enc.forward_depth(dep[sl.o:sl.o + sl.n], sl.feat2[t])
         else:
             sl.enc.forward(src, sl.tok)
@@ -560,8 +576,19 @@ class Worker(_SlicedActor):
         ImageNet towers), ``visual_fc``, the goal id (``goal_ids``) and / or the env's float ``sensors=(k_1, ...)``, the previous
         action, the recurrent core.  The rollout buffer is fp32 ``[T + 1, n, 1, D]``.  Every ``loss`` mode, teacher forcing, up to
         256 actions, ``prev_actions``, ``rnn_type``, ``rnn_layers``, ``num_mini_batch``, ``sync_actions`` and checkpoints work; a
-        checkpoint of another net is refused by tensor name.  ``ValueError`` before any allocation with ``depth``, ``zeroshot``,
+        checkpoint of another net is refused by tensor name.  ``ValueError`` before any allocation with ``zeroshot``,
         ``goal_in``, ``encoder="vit"`` or ``pooling="attnpool"`` on an ImageNet tower.
+
+        ``net="pooled", pooling="avgpool", depth=True`` (``encoder="rn50"``): the same net on RGB-D frames
+        (readme_files/baselines_habitat.md:75; [U] habitat branch ``ResNetCLIPEncoder`` with rgb and depth, restated, parity
+        unpinned) -- the embedding is ``adaptive_avg_pool2d(trunk(rgb) + trunk(depth), 1)``, D = 2048, one
+        ``RN50Trunk.embed_rgbd`` call per slice and env step that runs both frames of every pair through the trunk in ONE pass.
+        ``feat2`` is None and the rollout buffer is the RGB avgpool net's; ``frames_u8`` (uint8 RGB, fp32 depth), both cells,
+        1..4 layers and ``prev_actions`` work.  A checkpoint has exactly the RGB avgpool net's tensors, so it loads into
+        ``Worker(net="pooled", pooling="avgpool")`` with or without ``depth``.  The depth frames arrive as
+        ``synthetic.normalize_depth`` serves them (upstream quantises depth to uint8 and applies CLIP's RGB mean / std: a
+        deviation).  ``ValueError`` with ``pooling="attnpool"`` (upstream removes the attention pool there), an
+        ImageNet tower, ``frames_host`` or ``zeroshot``.
 
         ``hidden``: the recurrent width ([U] ``hidden_size``; 512 in every published config).
 
@@ -613,10 +640,11 @@ class Worker(_SlicedActor):
         self.goal_ids = bool(goal_ids)
         if depth:
             check_rgbd(encoder, zeroshot, goal_in, frames_host)
-        self.prev_action_dims = check_prev_actions(prev_actions, bool(depth), bool(zeroshot))
+        two_tower = bool(depth) and not self.pooled_net     # (the pooled RGB-D agent's policy handle is the RGB pooled net's: nothing to refuse)
+        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot))
         self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
-        self.rnn_type = check_rnn_type(rnn_type, bool(depth), bool(zeroshot))
-        self.rnn_layers = check_rnn_layers(rnn_layers, bool(depth), bool(zeroshot))
+        self.rnn_type = check_rnn_type(rnn_type, two_tower, bool(zeroshot))
+        self.rnn_layers = check_rnn_layers(rnn_layers, two_tower, bool(zeroshot))
         self.hidden_size = int(hidden)
         self.depth = bool(depth)
         self.lib = _lib.load()
@@ -980,7 +1008,7 @@ class Worker(_SlicedActor):
     def _gather_feat2(self, sl, a: int, b: int):
         """The depth features of the batch ``_gather_part(sl, a, b)`` returns (``depth=True``; else None): the whole slice in
         place, a partial range through a staging buffer of its own, sized as ``feat_mb``."""
-        if not self.depth:
+        if not self.dual:
             return None
         T, S2 = self.T, self.S * self.S
         if a == 0 and b == sl.n:
@@ -1084,7 +1112,7 @@ class Worker(_SlicedActor):
     def after_update(self):
         for sl in self.slices:
             sl.feat[0].copy_(sl.feat[self.T])
-            if self.depth:
+            if self.dual:
                 sl.feat2[0].copy_(sl.feat2[self.T])
         if self.prev_action_dims:     # the next rollout's first step follows this rollout's last action
             self.prev_actions[0].copy_(self.prev_actions[self.T])

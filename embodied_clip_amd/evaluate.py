@@ -45,7 +45,9 @@ class Evaluator(_SlicedActor):
     ``no_path``.  The act loop does not change.  ``env_seed``: the seed of the env the evaluator builds itself (default
     ``1000 + rank``, the ``Worker``'s).  ``depth=True``: the RGB-D agent of ``Worker(depth=True)`` -- a second feature ring per slice
     for the depth tower, the dual-encoder policy (a checkpoint then carries 25 tensors); an ``env=`` must also have ``depth`` and
-    ``observe_depth()``; refused with the combinations ``engine.check_rgbd`` names.  ``prev_actions=E > 0`` /
+    ``observe_depth()``; refused with the combinations ``engine.check_rgbd`` names.  With ``net="pooled", pooling="avgpool"`` it is
+    the agent of ``Worker(net="pooled", pooling="avgpool", depth=True)`` instead: one ``RN50Trunk.embed_rgbd`` call per slice and
+    step, no second ring, the RGB avgpool net's checkpoint.  ``prev_actions=E > 0`` /
     ``prev_action_null_token``: the agent of ``Worker(prev_actions=E)`` -- every step reads the actions the step before selected
     (zeros before the first); a checkpoint then carries one more tensor, and one without it is refused by name; ``ValueError``
     with ``depth=True`` or ``zeroshot=True``.  ``rnn_type="LSTM"``: the agent of ``Worker(rnn_type="LSTM")`` -- the recurrent memory
@@ -68,13 +70,14 @@ class Evaluator(_SlicedActor):
         if self.net_sensors and env is not None and getattr(env, "sensors", None) is None:
             raise ValueError("net='pooled' with sensors: the env serves no sensor vectors (SyntheticEnv(..., sensors=K) holds env.sensors)")
         self.hidden_size = int(hidden)
-        self.rnn_type = check_rnn_type(rnn_type, bool(depth), bool(zeroshot))
-        self.rnn_layers = check_rnn_layers(rnn_layers, bool(depth), bool(zeroshot))
+        two_tower = bool(depth) and not self.pooled_net     # (the pooled RGB-D agent's policy handle is the RGB pooled net's)
+        self.rnn_type = check_rnn_type(rnn_type, two_tower, bool(zeroshot))
+        self.rnn_layers = check_rnn_layers(rnn_layers, two_tower, bool(zeroshot))
         if depth:       # the RGB-D agent (engine.Worker(depth=True)): the same refusals, before anything is built
             check_rgbd(encoder, zeroshot, goal_in, bool(env is not None and getattr(env, "host", False)))
             if env is not None and getattr(env, "depth", None) is None:
                 raise ValueError("depth=True: the env serves no depth frames (SyntheticEnv(..., depth=True) holds env.depth)")
-        self.prev_action_dims = check_prev_actions(prev_actions, bool(depth), bool(zeroshot))
+        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot))
         self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
         self.depth = bool(depth)
         self.lib = _lib.load()
@@ -289,7 +292,8 @@ def main(argv=None) -> int:
     ap.add_argument("--num-actions", type=int, default=6)
     ap.add_argument("--zeroshot", action="store_true")
     ap.add_argument("--frames-u8", action="store_true")
-    ap.add_argument("--depth", action="store_true", help="the RGB-D agent: a depth tower beside the RGB tower, dual goal encoder (encoder rn50 / rn50x16)")
+    ap.add_argument("--depth", action="store_true", help="the RGB-D agent: a depth tower beside the RGB tower, dual goal encoder (encoder rn50 / rn50x16); with --net pooled "
+                    "--pooling avgpool: the Habitat RGB-D encoder, both towers' maps summed and average-pooled")
     ap.add_argument("--sync-actions", action="store_true")
     ap.add_argument("--prev-actions", type=int, default=0, metavar="E",
                     help="the agent conditions on its previous action through an E-wide embedding (0: off; AllenAct's default is 6, Habitat's 32)")

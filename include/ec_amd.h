@@ -289,6 +289,13 @@ int ec_nchw_f32_to_nhwc_bf16(const float* in, void* out, int B, int HW, int C, i
 /* AdaptiveAvgPool2d(1)+Flatten on the fp32-cast features
  * (thor_image_features.py:63-66,113; preprocessor pool=True). bf16 [B,HW,C] -> f32 [B,C]. */
 int ec_spatial_mean_bf16(const void* in, float* out, int B, int HW, int C, ec_stream_t stream);
+/* [U] ResNetCLIPEncoder.forward, rgb + depth (habitat branch; restated, parity unpinned):
+ * adaptive_avg_pool2d(a + b, 1).flatten(1) on the fp32-cast maps.
+ * a, b bf16 [B,HW,C]; out f32 [B,C]; out[n,c] = (1/HW) * sum_hw (float(a[n,hw,c]) + float(b[n,hw,c])).
+ * Every C >= 1: 16-byte loads when C % 8 == 0 and a, b are 16-byte aligned, 2-byte loads otherwise.  The summation order is
+ * fixed (no float atomics): two calls give equal bits.  Checked before any HIP call: NULL -> EC_ERR_ARG; B, HW or
+ * C <= 0 -> EC_ERR_SHAPE. */
+int ec_spatial_mean_pair_bf16(const void* a, const void* b, float* out, int B, int HW, int C, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * CLIP ModifiedResNet trunk (stem + layer1..4, attnpool detached):
@@ -341,6 +348,22 @@ int ec_rn50_forward_u8(const ec_rn50_t* h, const uint8_t* rgb_u8_nhwc, const flo
  * (7x7 stem) returns EC_ERR_UNSUPPORTED; NULL pointers EC_ERR_ARG. */
 int ec_rn50_forward_depth(const ec_rn50_t* h, const float* depth, float scale, float shift, const float* stem_w9, int batch,
                           void* workspace, size_t ws_bytes, void* feat_bf16_nhwc, int chunk, ec_stream_t stream);
+/* The RGB-D encoder of the Habitat DD-PPO net ([U] habitat branch ResNetCLIPEncoder with rgb and depth; restated, parity
+ * unpinned): the trunk on the RGB frame and on the depth frame of every pair, the two maps summed and average-pooled:
+ * embed f32 [pairs, out_channels] = adaptive_avg_pool2d(trunk(rgb) + trunk(depth), 1).flatten(1).  Replaces two trunk forwards,
+ * the add and the pool.  Both towers read the same weights, so a chunk of nb pairs is ONE pass of ec_rn50_forward's plan at
+ * 2 nb frames: the stem's first conv is two launches into one buffer (ec_stem_conv1 / _u8 on rows [0, nb), ec_stem_conv1_depth on
+ * rows [nb, 2 nb)), every later op runs once, and ec_spatial_mean_pair_bf16 ends the chunk.  EC_RGBD_JOINT=0: two passes at nb
+ * frames (RGB, then depth) and the same pool.
+ * rgb f32 or (rgb_u8 != 0) uint8 [pairs,R,R,3], the latter with host mean / std as ec_rn50_forward_u8; depth, scale, shift,
+ * stem_w9 as ec_rn50_forward_depth.  `pairs` and `chunk` count PAIRS.  workspace: ec_rn50_rgbd_workspace_bytes(h, chunk) --
+ * the plan's buffers at 2 * chunk frames plus the chunk's maps.  Checked before the first launch: NULL rgb, depth, stem_w9,
+ * workspace or embed (h_mean3 / h_std3 with rgb_u8) -> EC_ERR_ARG; pairs <= 0 -> EC_ERR_SHAPE; a handle of the torchvision towers
+ * (7x7 stem) -> EC_ERR_UNSUPPORTED; a short workspace -> EC_ERR_WORKSPACE. */
+size_t ec_rn50_rgbd_workspace_bytes(const ec_rn50_t* h, int pairs);
+int ec_rn50_embed_rgbd(const ec_rn50_t* h, const void* rgb, int rgb_u8, const float* h_mean3, const float* h_std3,
+                       const float* depth, float scale, float shift, const float* stem_w9, int pairs, void* workspace,
+                       size_t ws_bytes, float* embed, int chunk, ec_stream_t stream);
 /* Number of ops in the handle's launch plan (from 128 frames on one kernel launch each: 38 for CLIP RN50 at 224 x 224;
  * smaller launches run the five fused layer-3 blocks as three launches each).  Tests and tools/ key on it. */
 int ec_rn50_num_ops(const ec_rn50_t* h);

@@ -18,11 +18,12 @@
 //   bneck123 B H W C                                ec_bneck3_pack_weights + ec_bneck_conv123_bf16
 //   tail  B Ho Wo planes inplanes Cout              ec_basic_tail_s2_bf16
 //   trunk clip50|tv50|tv18|vitb32 frames min_tiles  create + ec_*_set_conv8_min_tiles + one forward + destroy
-//   tower clip|tvb|tvbasic width l1 l2 l3 l4 res frames min_tiles chunk f32|u8|depth
+//   tower clip|tvb|tvbasic width l1 l2 l3 l4 res frames min_tiles chunk f32|u8|depth|rgbd
 //                                                   the same for an explicit ResNet architecture (CLIP tower, torchvision
 //                                                   Bottleneck / BasicBlock tower; the torchvision towers have width 64) through
 //                                                   ec_rn50_forward / _u8 / _depth; `P <ec_rn50_num_ops> <ec_rn50_plan_hash>`
-//                                                   comes before its launches
+//                                                   comes before its launches.  rgbd: ec_rn50_embed_rgbd on fp32 RGB frames,
+//                                                   `frames` and `chunk` counting pairs
 //   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse [dhf [core]]
 //                                                   create + ec_policy_workspace_bytes + ec_policy_forward2 (goal_in > 0:
 //                                                   ec_policy_forward_vec) + destroy; mode 0 = EC_POLICY_INFER, 1 = _LEARN;
@@ -200,7 +201,11 @@ static int run_tower(const std::string& kind, const int* v, const std::string& i
     else if (input == "depth")
         rc = sym<int (*)(P, P, float, float, P, int, P, size_t, P, int, P)>("ec_rn50_forward_depth")(h, rgb, 0.2f, -0.5f, w9, frames, wsp, ws, out,
                                                                                                     chunk, nullptr);
-    else
+    else if (input == "rgbd") {   // `frames` counts pairs; a workspace of the entry point's own size
+        const size_t ws2 = sym<size_t (*)(P, int)>("ec_rn50_rgbd_workspace_bytes")(h, frames);
+        rc = sym<int (*)(P, P, int, const float*, const float*, P, float, float, P, int, P, size_t, P, int, P)>("ec_rn50_embed_rgbd")(
+            h, rgb, 0, nullptr, nullptr, fake(1u << 30), 0.2f, -0.5f, w9, frames, fake(ws2), ws2, out, chunk, nullptr);
+    } else
         rc = -100;
     sym<void (*)(P)>("ec_rn50_destroy")(h);
     return rc;
