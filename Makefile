@@ -5,12 +5,13 @@ ARCH  ?= gfx950
 CSRC  := embodied_clip_amd/csrc
 OUT   := embodied_clip_amd/lib/libec_amd.so
 SRCS  := $(wildcard $(CSRC)/*.hip)
+HDRS  := $(wildcard $(CSRC)/*.h) include/ec_amd.h
 OBJS  := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 FLAGS := --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -Wall -Wno-unused-function -Wno-unused-but-set-variable -ffp-contract=fast $(EXTRA)
 
 all: $(OUT)
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/common.h include/ec_amd.h
+build/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -23,7 +24,7 @@ $(OUT): $(OBJS)
 # 8-wave kernel).  Used by tools/bench_bneck.py --stamps and tools/stamps8.py through tools/_toolslib.py.
 TOOLS_OUT  := embodied_clip_amd/lib/libec_amd_tools.so
 TOOLS_OBJS := $(patsubst $(CSRC)/%.hip,build_tools/%.o,$(SRCS))
-build_tools/%.o: $(CSRC)/%.hip $(CSRC)/common.h include/ec_amd.h
+build_tools/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build_tools
 	$(HIPCC) $(FLAGS) -DEC_TOOLS -DEC_CONV8_PROFILE -c $< -o $@
 $(TOOLS_OUT): $(TOOLS_OBJS)

@@ -75,6 +75,7 @@ SIGNATURES = {
     "ec_rn50_num_ops": (c_int, [c_void_p]),
     "ec_rn50_plan_hash": (C.c_uint64, [c_void_p]),
     "ec_rn50_set_conv8_min_tiles": (c_int, [c_void_p, c_int]),
+    "ec_rn50_set_l1_rebuild": (c_int, [c_void_p, c_int]),
     "ec_text_create": (c_int, [C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                c_size_t]),
     "ec_text_destroy": (None, [c_void_p]),
@@ -85,6 +86,7 @@ SIGNATURES = {
     "ec_probe_pool3": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ec_conv1x1_pair_pool_bf16": (c_int, [c_void_p] * 9 + [c_int] * 6 + [c_void_p]),
     "ec_conv1x1_pair_bf16": (c_int, [c_void_p] * 11 + [C.c_long, c_int, c_int, c_int, c_void_p]),
+    "ec_conv1x1_pair_rebuild_bf16": (c_int, [c_void_p] * 13 + [C.c_long, c_int, c_int, c_int, c_void_p]),
     "ec_stem_conv1_u8": (c_int, [c_void_p, C.POINTER(c_float), C.POINTER(c_float), c_void_p, c_void_p, c_void_p]
                          + [c_int] * 4 + [c_void_p]),
     "ec_rn50_forward_u8": (c_int, [c_void_p, c_void_p, C.POINTER(c_float), C.POINTER(c_float), c_int, c_void_p,

@@ -22,17 +22,10 @@
 //   * y and z leave through a small per-wave LDS staging image so every global access is a 16-B row chunk.
 #include <stdlib.h>
 
-#include <type_traits>
-#include <utility>
-
-#include "common.h"
+#include "conv_pair_common.h"
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // native vector: plain loads/stores, SROA-friendly
-constexpr int PX = 32;         // pixels per wave tile
-constexpr int NY = 256;        // channels of y
-constexpr int KA = 64;         // channels of a0 / a1
 constexpr int SP = 272;        // staging pitch in bytes of a 128-channel half row (+16: 2-way instead of 32-way conflicts)
 constexpr int STG = PX * SP;   // staging bytes per wave
 
@@ -50,45 +43,6 @@ __device__ __forceinline__ float pq_xor1(float v) {   // lane ^ 1 within a quad
 }
 __device__ __forceinline__ float pq_xor2(float v) {   // lane ^ 2 within a quad
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-}
-
-__device__ __forceinline__ int pw_off(int row, int chunk) {   // 128-B rows, XOR swizzle on the 16-B chunk
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
-// Software-pipelined LDS fragment stream for kernels that run ONE wave per SIMD: left to the compiler every MFMA gets its
-// own `ds_read_b128 -> s_waitcnt lgkmcnt(0)` in front (it sinks operand reads to their use), i.e. the full LDS latency per
-// MFMA with nothing to hide it.  Here the reads are inline asm, LEAD steps ahead of the MFMA that consumes them, and the
-// waits carry the fragment register so the MFMA cannot be scheduled above its wait (LDS returns data in order:
-// "lgkmcnt(n)" = all but the newest n have arrived; compiler-generated LDS traffic in between only makes the waits
-// conservative).  addr(i): LDS byte address (VGPR) and immediate offset of step i; mma(i, frag) consumes it.
-template <int I, int LEAD, class AddrFn>
-__device__ __forceinline__ void lsm_issue(u32x4 (&ring)[LEAD], AddrFn& addr) {
-    const auto a = addr(std::integral_constant<int, I>{});
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[I % LEAD]) : "v"(a.first), "n"(decltype(a.second)::value));
-}
-template <int I, int NSTEP, int LEAD, class AddrFn, class MmaFn>
-__device__ __forceinline__ void lsm_step(u32x4 (&ring)[LEAD], AddrFn& addr, MmaFn& mma) {
-    if constexpr (I < NSTEP) {
-        constexpr int after = (LEAD - 1 < NSTEP - 1 - I) ? LEAD - 1 : NSTEP - 1 - I;   // reads issued after read I
-        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[I % LEAD]) : "n"(after));
-        mma(std::integral_constant<int, I>{}, ring[I % LEAD]);
-        if constexpr (I + LEAD < NSTEP) lsm_issue<I + LEAD, LEAD>(ring, addr);
-        lsm_step<I + 1, NSTEP, LEAD>(ring, addr, mma);
-    }
-}
-template <int I, int N, int LEAD, class AddrFn>
-__device__ __forceinline__ void lsm_prologue(u32x4 (&ring)[LEAD], AddrFn& addr) {
-    if constexpr (I < N) {
-        lsm_issue<I, LEAD>(ring, addr);
-        lsm_prologue<I + 1, N, LEAD>(ring, addr);
-    }
-}
-template <int NSTEP, int LEAD, class AddrFn, class MmaFn>
-__device__ __forceinline__ void lds_stream_mfma(AddrFn addr, MmaFn mma) {
-    u32x4 ring[LEAD];
-    lsm_prologue<0, (LEAD < NSTEP ? LEAD : NSTEP), LEAD>(ring, addr);
-    lsm_step<0, NSTEP, LEAD>(ring, addr, mma);
 }
 
 // PL: the tile is a 4 x 8 block of pixels in quad order (row r of the tile = window (r >> 2), corner r & 3), so a 2 x 2
@@ -114,6 +68,10 @@ __global__ __launch_bounds__(256, 1) void conv1x1_pair_kernel(PairArgs p) {
     unsigned wk_off[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) wk_off[ks] = (unsigned)pw_off(px, 2 * ks + h);
+    // The bias vectors are read as a fragment stream too: a lane's four biases of epilogue step (j, g) are channels 32 j + 8 g + 4 h ..,
+    // 32 B per step.  Left to the compiler each bias read sits right in front of its use behind an `s_waitcnt lgkmcnt(0)`: the full
+    // LDS latency once per four output values, with a single wave per SIMD to hide it.
+    const unsigned b_lds = w_lds + (unsigned)(W0_BYTES + W2_BYTES) + 16u * h;
     // tile row r -> pixel offset from the tile's first pixel
     auto roff = [&](int r) -> int {
         if (!PL) return r;
@@ -234,16 +192,14 @@ __global__ __launch_bounds__(256, 1) void conv1x1_pair_kernel(PairArgs p) {
                     ((*reinterpret_cast<u32x4*>(stg + ((I * 64 + lane) >> 4) * SP + ((I * 64 + lane) & 15) * 16) = rc[hf * 8 + I]), ...);
                 }(std::make_integer_sequence<int, 8>{});
             }
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const int j = hf * 4 + jj;
-                unsigned pk[8];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
+            lds_stream_mfma<16, 4>(
+                [&](auto ic) { return std::pair<unsigned, std::integral_constant<int, hf * 512 + 32 * decltype(ic)::value>>{b_lds, {}}; },
+                [&](auto ic, const u32x4& bq) {
+                    constexpr int i = decltype(ic)::value, jj = i / 4, g = i % 4, j = hf * 4 + jj;
                     const int lc = 32 * jj + 8 * g + 4 * h;                       // channel within the half
-                    const float4 bv = *reinterpret_cast<const float4*>(sBy + hf * 128 + lc);
-                    float v0 = acc[j][4 * g + 0] + bv.x, v1 = acc[j][4 * g + 1] + bv.y;
-                    float v2 = acc[j][4 * g + 2] + bv.z, v3 = acc[j][4 * g + 3] + bv.w;
+                    const f32x4_t bv = __builtin_bit_cast(f32x4_t, bq);
+                    float v0 = acc[j][4 * g + 0] + bv[0], v1 = acc[j][4 * g + 1] + bv[1];
+                    float v2 = acc[j][4 * g + 2] + bv[2], v3 = acc[j][4 * g + 3] + bv[3];
                     uint2* slot = reinterpret_cast<uint2*>(stg + px * SP + lc * 2);
                     if (RES) {
                         const uint2 rr = *slot;
@@ -254,11 +210,10 @@ __global__ __launch_bounds__(256, 1) void conv1x1_pair_kernel(PairArgs p) {
                     o.x = ec_pack2(v0, v1);
                     o.y = ec_pack2(v2, v3);
                     *slot = o;
-                    pk[2 * g] = o.x; pk[2 * g + 1] = o.y;
-                }
-                P[j][0] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-                P[j][1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-            }
+                    uint4& pq = P[j][g >> 1];
+                    if constexpr (g & 1) { pq.z = o.x; pq.w = o.y; }
+                    else { pq.x = o.x; pq.y = o.y; }
+                });
             if constexpr (PL) {
                 // AvgPool2d(2)(y) from the staged half: window w = tile rows 4w..4w+3 (quad order); a lane takes two
                 // (window, 8-channel chunk) items: mean of the ROUNDED bf16 values, summed as (r0 + r1) + (r2 + r3) like
@@ -282,7 +237,9 @@ __global__ __launch_bounds__(256, 1) void conv1x1_pair_kernel(PairArgs p) {
                     *reinterpret_cast<u32x4*>(p.yp + (pool_base + (w >> 2) * (p.W / 2) + (w & 3)) * NY + hf * 128 + c * 8) = po;
                 }
             }
-            if (!PL || p.y) {   // (layer-1 -> layer-2 boundary: nobody reads the full-resolution y -- its consumers are z and y_pooled)
+            // y == NULL: not stored.  (Layer-1 -> layer-2 boundary: nobody reads the full-resolution y -- its consumers are z and
+            // y_pooled; the block-0 boundary in front of conv1x1_pair_rebuild_kernel: that launch rebuilds y from a0 and a1.)
+            if (p.y) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int idx = i * 64 + lane;
@@ -313,17 +270,17 @@ __global__ __launch_bounds__(256, 1) void conv1x1_pair_kernel(PairArgs p) {
         // ---- epilogue 2 ----
         constexpr int ZP = N2 * 2 + 16;            // staging pitch of a z row
         constexpr int ZC = N2 / 8;                 // 16-B chunks per z row
-#pragma unroll
-        for (int n = 0; n < FN2; ++n)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
+        lds_stream_mfma<4 * FN2, 4>(
+            [&](auto ic) { return std::pair<unsigned, std::integral_constant<int, NY * 4 + 32 * decltype(ic)::value>>{b_lds, {}}; },
+            [&](auto ic, const u32x4& bq) {
+                constexpr int i = decltype(ic)::value, n = i / 4, g = i % 4;
                 const int lc = 32 * n + 8 * g + 4 * h;
-                const float4 bv = *reinterpret_cast<const float4*>(sBz + lc);
+                const f32x4_t bv = __builtin_bit_cast(f32x4_t, bq);
                 uint2 o;
-                o.x = ec_pack2(fmaxf(acc2[n][4 * g + 0] + bv.x, 0.f), fmaxf(acc2[n][4 * g + 1] + bv.y, 0.f));
-                o.y = ec_pack2(fmaxf(acc2[n][4 * g + 2] + bv.z, 0.f), fmaxf(acc2[n][4 * g + 3] + bv.w, 0.f));
+                o.x = ec_pack2(fmaxf(acc2[n][4 * g + 0] + bv[0], 0.f), fmaxf(acc2[n][4 * g + 1] + bv[1], 0.f));
+                o.y = ec_pack2(fmaxf(acc2[n][4 * g + 2] + bv[2], 0.f), fmaxf(acc2[n][4 * g + 3] + bv[3], 0.f));
                 *reinterpret_cast<uint2*>(stg + px * ZP + lc * 2) = o;
-            }
+            });
 #pragma unroll
         for (int i = 0; i < PX * ZC / 64; ++i) {
             const int idx = i * 64 + lane;
@@ -744,10 +701,11 @@ int launch_regw(const RegwArgs& p, hipStream_t s, int groups = 1) {
 extern "C" int ec_conv1x1_pair_bf16(const void* a0, const void* w0, const float* b0, const void* a1, const void* w1,
                                     const float* b1, const void* res, void* y, const void* w2, const float* b2, void* z,
                                     long M, int K0, int N, int N2, ec_stream_t stream) {
-    if (!a0 || !w0 || !b0 || !y || !w2 || !b2 || !z) return EC_ERR_ARG;
+    if (!a0 || !w0 || !b0 || !w2 || !b2 || !z) return EC_ERR_ARG;   // y may be NULL (layer-1 geometry): not stored
     if ((a1 != nullptr) != (w1 != nullptr) || (a1 != nullptr) != (b1 != nullptr)) return EC_ERR_ARG;
     if (M <= 0 || (M % PX) != 0 || M / PX > 0x7fffffffL) return EC_ERR_SHAPE;
     if (K0 == K2 && N == NY2 && N2 == NZ2) {            // layer-2 geometry: weights in registers (residual form only)
+        if (!y) return EC_ERR_ARG;           // (this kernel always stores y)
         if (a1 || !res) return EC_ERR_SHAPE;
         Pair2Args q{(const uint16_t*)a0, (const uint16_t*)w0, (const uint16_t*)w2, (const uint16_t*)res, b0, b2, (uint16_t*)y,
                     (uint16_t*)z, (int)(M / PX)};

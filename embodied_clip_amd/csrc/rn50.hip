@@ -62,6 +62,9 @@ struct Op {
     // OP_BTAIL (conv_basic.hip): a BasicBlock's stride-2 tail, relu(c2(conv1's output) + ds(block input)), as one `cat` GEMM
     Conv c1, c2, c3, ds, next_c1;
     bool fold_ds;        // OP_PAIR: the block's downsample conv is folded in as a second K operand (its output is never materialised)
+    bool no_y;           // OP_PAIR: y is not stored: the next boundary launch rebuilds it (ec_rn50_set_l1_rebuild)
+    bool rebuild;        // OP_PAIR: ... and this is that launch (conv_pair_rebuild.hip): the identity is relu(id_c3 + id_ds), the
+    Conv id_c3, id_ds;   //          PREVIOUS block's conv3 and folded downsample conv, recomputed from their inputs
     int pooled_dst;      // OP_PAIR at the layer-1 -> layer-2 boundary: buffer for AvgPool2d(2)(y), the next block's downsample input; or BUF_NONE
     bool fold_c1;        // OP_BNECK: the whole block in one launch
     size_t wpack_off;    // OP_BNECK: its streaming-order weights in wbneck (ec_bneck_pack_weights / ec_bneck3_pack_weights)
@@ -81,6 +84,8 @@ struct ec_rn50 {
     const float* bias;
     size_t n_w, n_b;
     int conv8_min_tiles = 0;      // 0 = library default (ec_rn50_set_conv8_min_tiles)
+    int layers4[4] = {0, 0, 0, 0};
+    int l1_rebuild = 0;           // layer 1's block-0 output is rebuilt, not stored (ec_rn50_set_l1_rebuild)
     uint16_t* wbneck = nullptr;   // weights the plan's launches read in their own layout: Cat::w_off, Op::wpack_off, Conv::wimg_off
     float* bias_cat = nullptr;    // summed biases of the K-concatenated GEMMs (Cat::b_off)
     ~ec_rn50() {
@@ -103,12 +108,16 @@ struct Blk {
     bool ds, last_of_layer;
     Slot c1, c2, c3, dsc;     // (a BasicBlock has no c3; dsc only where the block downsamples)
 };
-struct Arch { TowerKind kind; int width, R1; Slot stem[3], total; std::vector<Blk> B; };   // R1: resolution behind the stem
+struct Arch {
+    TowerKind kind; int width, R1;   // R1: resolution behind the stem
+    bool l1_rebuild;                 // block 0's output is never stored: its input lives in that buffer instead (walk_arch)
+    Slot stem[3], total; std::vector<Blk> B;
+};
 
 // The architecture before any op is planned, in the order ec_amd.h documents: stem convs (CLIP: conv1's weights are passed apart,
 // fp32; the 7x7 stem: all of them), then per block conv1, conv2, conv3, [downsample] (BasicBlock: conv1, conv2, [downsample])
-Arch walk_arch(TowerKind kind, int width, int sc, const int* layers4, int R) {
-    Arch a{kind, width, R};
+Arch walk_arch(TowerKind kind, int width, int sc, const int* layers4, int R, bool l1_rebuild = false) {
+    Arch a{kind, width, R, l1_rebuild};
     Slot& at = a.total;
     auto take = [&](size_t Cout, size_t K) { const Slot s = at; at.w += Cout * K; at.b += Cout; return s; };
     a.stem[0] = take(kind == CLIP ? sc : width, 0);
@@ -131,6 +140,9 @@ Arch walk_arch(TowerKind kind, int width, int sc, const int* layers4, int R) {
             x = k.y; inplanes = k.planes * expansion; R = k.Ro;
         }
     if (!a.B.empty()) a.B.back().out = BUF_OUT;
+    // Block 1's boundary launch reads block 0's input across the whole tensor while it writes its own output: the two must not
+    // share a buffer.  Block 0's output buffer holds nothing, so the stem writes the block input there.
+    if (l1_rebuild && !a.B.empty()) a.B[0].x = a.B[0].y;
     return a;
 }
 
@@ -235,11 +247,22 @@ Given plan_bottleneck(Plan& p, const Arch& a, size_t i, Given g) {
         return Given{};
     }
     if (f == F_PAIR1 || f == F_PAIR1_POOL) {
+        // l1_rebuild: block 0's boundary stores no y; block 1's rebuilds it from block 0's conv2 output (buffer 2) and input, so
+        // block 1's conv2 writes buffer 3 (free inside layer 1 until the layer-1 -> layer-2 boundary writes the pooled copy)
+        const bool rb0 = a.l1_rebuild && i == 0, rb1 = a.l1_rebuild && i == 1;
+        if (rb1) c2.dst = 3;
         p.conv(c2);
         o.kind = OP_PAIR;
-        o.c3 = mk_conv(2, k.out, k.ds ? BUF_NONE : x, R, R, planes, planes * 4, 1, 0, EC_ACT_RELU, k.c3);
+        o.c3 = mk_conv(c2.dst, k.out, k.ds || rb1 ? BUF_NONE : x, R, R, planes, planes * 4, 1, 0, EC_ACT_RELU, k.c3);
         o.fold_ds = k.ds;   // block 0: the downsample conv (x -> 256) is folded in as a second K = 64 operand
         if (k.ds) o.ds = mk_conv(x, BUF_NONE, BUF_NONE, R, R, inplanes, planes * 4, 1, 0, EC_ACT_NONE, k.dsc);
+        o.no_y = rb0;
+        if (rb1) {
+            const Blk& b0 = a.B[0];
+            o.rebuild = true;
+            o.id_c3 = mk_conv(2, BUF_NONE, BUF_NONE, R, R, b0.planes, b0.planes * 4, 1, 0, EC_ACT_RELU, b0.c3);
+            o.id_ds = mk_conv(b0.x, BUF_NONE, BUF_NONE, R, R, b0.inplanes, b0.planes * 4, 1, 0, EC_ACT_NONE, b0.dsc);
+        }
         o.next_c1 = mk_conv(k.out, 1, BUF_NONE, R, R, planes * 4, nx->planes, 1, 0, EC_ACT_RELU, nx->c1);
         o.pooled_dst = f == F_PAIR1_POOL ? 3 : BUF_NONE;
         if (f == F_PAIR1_POOL) p.track(R / 2, R / 2, planes * 4);
@@ -319,20 +342,27 @@ void plan_basic(Plan& p, const Blk& k) {
 }
 
 // Weights the plan's fused / K-concatenated / image-resident launches read in their own layout (device copies owned by the handle)
-int pack_plan_weights(ec_rn50* h) {
-    size_t tot = 0, btot = 0;
-    // offsets: the concatenated GEMMs ([Cout][Ka + Kb] weights, summed bias), then per fused bottleneck one packed block (its conv2
-    // comes first in it: what the image-resident kernel reads when conv2 runs alone) and the image-resident 3x3 convs
-    auto cat_n = [](const Op& o) { return (size_t)(o.kind == OP_CAT ? o.c.Cout : o.c2.Cout); };
-    for (Op& o : h->ops)
+size_t cat_n(const Op& o) { return (size_t)(o.kind == OP_CAT ? o.c.Cout : o.c2.Cout); }
+
+// offsets: the concatenated GEMMs ([Cout][Ka + Kb] weights, summed bias), then per fused bottleneck one packed block (its conv2
+// comes first in it: what the image-resident kernel reads when conv2 runs alone) and the image-resident 3x3 convs.
+// A function of the op list alone: a plan rebuilt for the same tower (ec_rn50_set_l1_rebuild) finds its weights where they are.
+void plan_offsets(std::vector<Op>& ops, size_t& tot, size_t& btot) {
+    tot = btot = 0;
+    for (Op& o : ops)
         if (o.kind == OP_CAT || o.kind == OP_BTAIL) {
             o.cat.w_off = tot; tot += cat_n(o) * (size_t)(o.cat.Ka + o.cat.Kb);
             o.cat.b_off = btot; btot += cat_n(o);
         }
-    for (Op& o : h->ops) {
+    for (Op& o : ops) {
         if (o.kind == OP_BNECK) { o.wpack_off = o.c2.wimg_off = tot; tot += ec_bneck3_packed_elems(o.c2.Cin); }   // (room for conv1 too)
         if (o.kind == OP_CONV && o.c.img_max) { o.c.wimg_off = tot; tot += (size_t)o.c.Cout * 9 * o.c.Cin; }
     }
+}
+
+int pack_plan_weights(ec_rn50* h) {
+    size_t tot = 0, btot = 0;
+    plan_offsets(h->ops, tot, btot);
     if (btot && hipMalloc(&h->bias_cat, btot * sizeof(float)) != hipSuccess) { h->bias_cat = nullptr; return EC_ERR_LAUNCH; }
     if (!tot) return EC_OK;
     if (hipMalloc(&h->wbneck, tot * sizeof(uint16_t)) != hipSuccess) { h->wbneck = nullptr; return EC_ERR_LAUNCH; }
@@ -360,25 +390,17 @@ int pack_plan_weights(ec_rn50* h) {
     return EC_OK;
 }
 
-// The one builder: the towers differ in their stem and in their block planner
-int rn50_build(ec_rn50_t** out, TowerKind kind, int width, const int* layers4, int input_resolution, const void* stem_w,
-               const void* w_bf16, size_t n_w, const float* bias, size_t n_bias) {
-    if (!out || !layers4 || !stem_w || !w_bf16 || !bias) return EC_ERR_ARG;
-    if (width % 32 != 0 || width < 32 || input_resolution % 32 != 0) return EC_ERR_SHAPE;
-    if (kind == TV_BASIC && (input_resolution < 32 || layers4[0] < 1 || layers4[1] < 1 || layers4[2] < 1 || layers4[3] < 1)) return EC_ERR_SHAPE;
-    // stem channels: width/2, rounded up to the 32-channel granule of the conv kernels (RN50x16: 48 -> 64; the
-    // packer zero-pads the weights, so the padded channels are exactly 0 after ReLU and contribute nothing)
-    const int sc = (width / 2 + 31) / 32 * 32, res = input_resolution;
-    const Arch a = walk_arch(kind, width, sc, layers4, res / 4);
-    if (n_w != a.total.w || n_bias != a.total.b) return EC_ERR_SHAPE;
-    ec_rn50* h = new (std::nothrow) ec_rn50();
-    if (!h) return EC_ERR_ALLOC;
-    h->width = width; h->res = res; h->tv = kind;
-    h->stem_w = (const float*)stem_w; h->w = (const uint16_t*)w_bf16; h->bias = bias;
-    h->n_w = a.total.w; h->n_b = a.total.b;
-    Plan p{h->ops};
-    const int x0 = a.B.empty() ? BUF_OUT : 0;   // the stem's output is the first block's input
-    if (kind == CLIP) {   // conv1 strides by 2 itself: frame -> buffer 1 at R x R x sc
+// stem channels: width/2, rounded up to the 32-channel granule of the conv kernels (RN50x16: 48 -> 64; the
+// packer zero-pads the weights, so the padded channels are exactly 0 after ReLU and contribute nothing)
+int stem_channels(int width) { return (width / 2 + 31) / 32 * 32; }
+
+// The op list of a tower, stem first; -> the largest activation per frame (bf16 elements)
+size_t plan_tower(std::vector<Op>& ops, const Arch& a, int res) {
+    ops.clear();
+    Plan p{ops};
+    const int width = a.width, sc = stem_channels(width);
+    const int x0 = a.B.empty() ? BUF_OUT : a.B[0].x;   // the stem's output is the first block's input
+    if (a.kind == CLIP) {   // conv1 strides by 2 itself: frame -> buffer 1 at R x R x sc
         const int R = res / 2;
         p.push(Op{OP_STEM1, mk_conv(BUF_IN, 1, BUF_NONE, res, res, 3, sc, 3, 0, EC_ACT_RELU, a.stem[0])}, R, R, sc);
         p.conv(mk_conv(1, 2, BUF_NONE, R, R, sc, sc, 3, 0, EC_ACT_RELU, a.stem[1]));
@@ -388,11 +410,35 @@ int rn50_build(ec_rn50_t** out, TowerKind kind, int width, const int* layers4, i
     }
     Given g;
     for (size_t i = 0; i < a.B.size(); ++i)
-        if (kind == TV_BASIC) plan_basic(p, a.B[i]);
+        if (a.kind == TV_BASIC) plan_basic(p, a.B[i]);
         else g = plan_bottleneck(p, a, i, g);
+    return p.mx;
+}
+
+// ec_rn50_set_l1_rebuild: a CLIP tower whose layer1.0 boundary folds the downsample conv and whose layer1.1 boundary is a plain
+// fused pair too (not the pooled one: layer 1 has a third block)
+bool l1_rebuild_ok(const Arch& a) {
+    return a.kind == CLIP && a.B.size() >= 3 && a.B[0].ds && block_form(a, 0) == F_PAIR1 && block_form(a, 1) == F_PAIR1;
+}
+
+// The one builder: the towers differ in their stem and in their block planner
+int rn50_build(ec_rn50_t** out, TowerKind kind, int width, const int* layers4, int input_resolution, const void* stem_w,
+               const void* w_bf16, size_t n_w, const float* bias, size_t n_bias) {
+    if (!out || !layers4 || !stem_w || !w_bf16 || !bias) return EC_ERR_ARG;
+    if (width % 32 != 0 || width < 32 || input_resolution % 32 != 0) return EC_ERR_SHAPE;
+    if (kind == TV_BASIC && (input_resolution < 32 || layers4[0] < 1 || layers4[1] < 1 || layers4[2] < 1 || layers4[3] < 1)) return EC_ERR_SHAPE;
+    const int res = input_resolution;
+    const Arch a = walk_arch(kind, width, stem_channels(width), layers4, res / 4);
+    if (n_w != a.total.w || n_bias != a.total.b) return EC_ERR_SHAPE;
+    ec_rn50* h = new (std::nothrow) ec_rn50();
+    if (!h) return EC_ERR_ALLOC;
+    h->width = width; h->res = res; h->tv = kind;
+    std::copy(layers4, layers4 + 4, h->layers4);
+    h->stem_w = (const float*)stem_w; h->w = (const uint16_t*)w_bf16; h->bias = bias;
+    h->n_w = a.total.w; h->n_b = a.total.b;
+    h->max_elems_per_frame = plan_tower(h->ops, a, res);
     h->out_c = a.B.empty() ? width : a.B.back().planes * (kind == TV_BASIC ? 1 : 4);
     h->out_sp = a.B.empty() ? a.R1 : a.B.back().Ro;
-    h->max_elems_per_frame = p.mx;
     const int rc = pack_plan_weights(h);
     if (rc != EC_OK) { delete h; return rc; }
     *out = h;
@@ -436,6 +482,7 @@ extern "C" uint64_t ec_rn50_plan_hash(const ec_rn50_t* h) {
     };
     mix(ec_version()); mix((long)ec_config_hash());
     mix(h->width); mix(h->res); mix(h->conv8_min_tiles); mix(h->tv);
+    if (h->l1_rebuild) mix(h->l1_rebuild);   // (only while on: a default handle keeps the key its summaries were measured on)
     for (const Op& o : h->ops) {
         // The 24 values per op and their order are FROZEN (the flat op record of the versions the summaries under profiles/ were
         // measured on): a plan that launches the same kernels must keep its key.  0 kind, 1 src, 2 dst, 3 res, 4 H, 5 W, 6 Cin, 7 Cout,
@@ -461,6 +508,23 @@ extern "C" uint64_t ec_rn50_plan_hash(const ec_rn50_t* h) {
 extern "C" int ec_rn50_set_conv8_min_tiles(ec_rn50_t* h, int n) {
     if (!h) return EC_ERR_ARG;
     h->conv8_min_tiles = n > 0 ? n : 0;
+    return EC_OK;
+}
+
+// The plan is rebuilt from the architecture, as at creation.  The packed weights stay where they are: their offsets are a function
+// of the op kinds (plan_offsets), and layer 1 has no packed weights.
+extern "C" int ec_rn50_set_l1_rebuild(ec_rn50_t* h, int on) {
+    if (!h) return EC_ERR_ARG;
+    const Arch a = walk_arch((TowerKind)h->tv, h->width, stem_channels(h->width), h->layers4, h->res / 4, on != 0);
+    if (!l1_rebuild_ok(a)) return EC_ERR_UNSUPPORTED;
+    if ((on != 0) == (h->l1_rebuild != 0)) return EC_OK;
+    std::vector<Op> ops;
+    const size_t mx = plan_tower(ops, a, h->res);
+    size_t tot = 0, btot = 0;
+    plan_offsets(ops, tot, btot);
+    if (mx != h->max_elems_per_frame) return EC_ERR_UNSUPPORTED;   // (cannot happen: the ops' shapes are those of the default plan)
+    h->ops.swap(ops);
+    h->l1_rebuild = on != 0;
     return EC_OK;
 }
 
@@ -554,7 +618,8 @@ int run_cat(const Run& r, const Op& o) {   // conv3 | downsample conv over the c
 }
 
 // The boundary launch is its own route function too: EC_ERR_SHAPE for a row count that is no multiple of its tile (e.g. an odd number
-// of 28x28 frames), and the two convs run separately.  (With the downsample conv folded in, or the pooled copy, there is no such route.)
+// of 28x28 frames), and the two convs run separately.  (With the downsample conv folded in, the pooled copy or the rebuilt identity
+// there is no such route: those forms are planned only where 32-pixel tiles divide the frame.)
 int run_pair(const Run& r, const Op& o) {
     const ec_rn50* h = r.h;
     const Conv &c3 = o.c3, &c1 = o.next_c1;
@@ -562,9 +627,14 @@ int run_pair(const Run& r, const Op& o) {
         // (the full-resolution block output is dead here: the next block reads c1.dst and pooled_dst only)
         return ec_conv1x1_pair_pool_bf16(r.buf(c3.src), h->w + c3.at.w, h->bias + c3.at.b, r.buf(c3.res), nullptr, r.buf(o.pooled_dst),
                                          h->w + c1.at.w, h->bias + c1.at.b, r.buf(c1.dst), r.nb, c3.H, c3.W, c3.Cin, c3.Cout, c1.Cout, r.stream);
+    if (o.rebuild)   // the identity is the previous block's output, rebuilt from that block's conv2 output and input
+        return ec_conv1x1_pair_rebuild_bf16(r.buf(c3.src), h->w + c3.at.w, h->bias + c3.at.b, r.buf(o.id_c3.src), h->w + o.id_c3.at.w,
+                                            h->bias + o.id_c3.at.b, r.buf(o.id_ds.src), h->w + o.id_ds.at.w, h->bias + o.id_ds.at.b,
+                                            r.buf(c3.dst), h->w + c1.at.w, h->bias + c1.at.b, r.buf(c1.dst), (long)r.nb * c3.H * c3.W,
+                                            c3.Cin, c3.Cout, c1.Cout, r.stream);
     int rc = ec_conv1x1_pair_bf16(r.buf(c3.src), h->w + c3.at.w, h->bias + c3.at.b, o.fold_ds ? r.buf(o.ds.src) : nullptr,
                                   o.fold_ds ? h->w + o.ds.at.w : nullptr, o.fold_ds ? h->bias + o.ds.at.b : nullptr, r.opt(c3.res),
-                                  r.buf(c3.dst), h->w + c1.at.w, h->bias + c1.at.b, r.buf(c1.dst), (long)r.nb * c3.H * c3.W, c3.Cin, c3.Cout,
+                                  o.no_y ? nullptr : r.buf(c3.dst), h->w + c1.at.w, h->bias + c1.at.b, r.buf(c1.dst), (long)r.nb * c3.H * c3.W, c3.Cin, c3.Cout,
                                   c1.Cout, r.stream);
     if (rc == EC_ERR_SHAPE && !o.fold_ds) {
         rc = run_conv(r, c3);

@@ -198,6 +198,16 @@ class RN50Trunk:
         """Dispatch threshold of THIS handle's conv launches (0 = default; see ``ec_rn50_set_conv8_min_tiles``)."""
         _lib.check(self.lib.ec_rn50_set_conv8_min_tiles(self.h, int(n)), "ec_rn50_set_conv8_min_tiles")
 
+    def set_l1_rebuild(self, on: bool = True) -> bool:
+        """Layer 1's block-0 output is rebuilt by the next boundary launch instead of being stored and read back (see
+        ``ec_rn50_set_l1_rebuild``): same launches, bit-identical features, less HBM traffic.  -> False where the tower has no such
+        plan (not CLIP width 64 with three layer-1 blocks): the handle is unchanged."""
+        rc = self.lib.ec_rn50_set_l1_rebuild(self.h, int(bool(on)))
+        if rc == -6:      # EC_ERR_UNSUPPORTED
+            return False
+        _lib.check(rc, "ec_rn50_set_l1_rebuild")
+        return True
+
     def _workspace(self, n: int) -> torch.Tensor:
         need = self.lib.ec_rn50_workspace_bytes(self.h, n)
         if self._ws is None or self._ws.numel() < need:
@@ -737,17 +747,34 @@ def gemm_bf16(a, w, bias=None, res=None, act=0):
 
 
 @_guard_first
-def conv1x1_pair_bf16(a0, w0, b0, w2, b2, a1=None, w1=None, b1=None, res=None):
+def conv1x1_pair_bf16(a0, w0, b0, w2, b2, a1=None, w1=None, b1=None, res=None, store_y=True):
     """y = relu(a0 @ w0.T + b0 [+ a1 @ w1.T + b1] [+ res]) bf16 [M,256];  z = relu(y @ w2.T + b2) bf16 [M,N2].
-    a0/a1 bf16 [M,64], w0/w1 bf16 [256,64], res bf16 [M,256], w2 bf16 [N2,256] (layer-1 Bottleneck boundary)."""
+    a0/a1 bf16 [M,64], w0/w1 bf16 [256,64], res bf16 [M,256], w2 bf16 [N2,256] (layer-1 Bottleneck boundary).
+    ``store_y=False``: y is not stored (-> None, z)."""
     lib = _lib.load()
     M, K0 = a0.shape
     N, N2 = w0.shape[0], w2.shape[0]
-    y = torch.empty((M, N), dtype=torch.bfloat16, device=a0.device)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=a0.device) if store_y else None
     z = torch.empty((M, N2), dtype=torch.bfloat16, device=a0.device)
     _lib.check(lib.ec_conv1x1_pair_bf16(a0.data_ptr(), w0.data_ptr(), b0.data_ptr(), _lib.ptr(a1), _lib.ptr(w1),
-                                        _lib.ptr(b1), _lib.ptr(res), y.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                        _lib.ptr(b1), _lib.ptr(res), _lib.ptr(y), w2.data_ptr(), b2.data_ptr(),
                                         z.data_ptr(), M, K0, N, N2, _lib.stream_ptr()), "ec_conv1x1_pair_bf16")
+    return y, z
+
+
+@_guard_first
+def conv1x1_pair_rebuild_bf16(a, w3, b3, i0, wi0, bi0, i1, wi1, bi1, w2, b2):
+    """The boundary behind ``conv1x1_pair_bf16(i0, wi0, bi0, ..., a1=i1, w1=wi1, b1=bi1, store_y=False)``: the identity
+    relu(i0 @ wi0.T + bi0 + i1 @ wi1.T + bi1) is rebuilt, not read.  y = relu(a @ w3.T + b3 + identity) bf16 [M,256];
+    z = relu(y @ w2.T + b2) bf16 [M,64].  a/i0/i1 bf16 [M,64], w3/wi0/wi1 bf16 [256,64], w2 bf16 [64,256]."""
+    lib = _lib.load()
+    M, K0 = a.shape
+    N, N2 = w3.shape[0], w2.shape[0]
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    z = torch.empty((M, N2), dtype=torch.bfloat16, device=a.device)
+    _lib.check(lib.ec_conv1x1_pair_rebuild_bf16(a.data_ptr(), w3.data_ptr(), b3.data_ptr(), i0.data_ptr(), wi0.data_ptr(), bi0.data_ptr(),
+                                                i1.data_ptr(), wi1.data_ptr(), bi1.data_ptr(), y.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                                z.data_ptr(), M, K0, N, N2, _lib.stream_ptr()), "ec_conv1x1_pair_rebuild_bf16")
     return y, z
 
 

@@ -442,6 +442,11 @@ class _SlicedActor:
         self._conv8_min_tiles = (50 if n >= 128 else (75 if n >= 64 else 0)) if ns == 2 else 0
         for e in encs:
             e.set_conv8_min_tiles(self._conv8_min_tiles)
+        # CLIP RN50: layer 1's block-0 output is rebuilt at the next boundary, not stored (ec_rn50_set_l1_rebuild): bit-identical
+        # features, 768 B per 56 x 56 pixel less HBM traffic.  A tower without that plan (other layer counts) says so and keeps its own
+        if encoder == "rn50":
+            for e in encs:
+                e.set_l1_rebuild(True)
         # A/B switch.  Up to 7 actions: the narrow heads launch samples (ec_policy_act).  8 to 256: the wide heads launch computes
         # the logits, selects and forces (ec_policy_act_ex).  Off, above 256, or a hidden size whose rows do not fit the wide
         # launch's LDS (ec_heads_wide: H <= 3576): the forward, then the stand-alone selection calls

@@ -190,10 +190,26 @@ int ec_stem_conv1_depth(const float* depth, float scale, float shift, const floa
  *   z = relu(y . w2^T + b2)                               [M,N2]   == the next block's relu(bn1(conv1(x)))
  * ([U] openai/CLIP clip/model.py Bottleneck.forward; call site thor_image_features.py:109).
  * a0,a1 bf16 [M,64]; w0,w1 bf16 [256,64]; res,y bf16 [M,256]; w2 bf16 [N2,256]; z bf16 [M,N2].
- * K0 must be 64, N 256, N2 64 or 128 (64 only with a1), M a multiple of 32; else EC_ERR_SHAPE. */
+ * K0 must be 64, N 256, N2 64 or 128 (64 only with a1), M a multiple of 32; else EC_ERR_SHAPE.
+ * y may be NULL at these widths: it is not stored then (z is the same bits) -- for a caller whose next launch rebuilds y
+ * (ec_conv1x1_pair_rebuild_bf16). */
 int ec_conv1x1_pair_bf16(const void* a0, const void* w0, const float* b0, const void* a1, const void* w1,
                          const float* b1, const void* res, void* y, const void* w2, const float* b2, void* z,
                          long M, int K0, int N, int N2, ec_stream_t stream);
+
+/* The NEXT boundary behind a ec_conv1x1_pair_bf16(a0 = i0, a1 = i1, res = NULL, y = NULL) launch: the identity is rebuilt from
+ * that launch's inputs instead of being read from memory:
+ *   id = relu(i0 . wi0^T + bi0 + i1 . wi1^T + bi1)        [M,256]  never stored; == the y of that launch, bit for bit
+ *   y  = relu(a . w3^T + b3 + id)                         [M,256]  == relu(bn3(conv3(out)) + identity) of layer1.1
+ *   z  = relu(y . w2^T + b2)                              [M,64]   == layer1.2's relu(bn1(conv1(x)))
+ * ([U] openai/CLIP clip/model.py Bottleneck.forward; call site thor_image_features.py:109).  y and z are bit-identical to
+ * ec_conv1x1_pair_bf16(a, w3, b3, res = id, ...).  a, i0, i1 bf16 [M,64]; w3, wi0, wi1 bf16 [256,64]; w2 bf16 [64,256].
+ * Reads 384 B and writes 640 B per pixel (with the identity read from memory: 640 B and 640 B, and 512 B written in front).
+ * NULL -> EC_ERR_ARG; M not a positive multiple of 32, K0 != 64, N != 256 or N2 != 64 -> EC_ERR_SHAPE. */
+int ec_conv1x1_pair_rebuild_bf16(const void* a, const void* w3, const float* b3, const void* i0, const void* wi0,
+                                 const float* bi0, const void* i1, const void* wi1, const float* bi1, void* y,
+                                 const void* w2, const float* b2, void* z, long M, int K0, int N, int N2,
+                                 ec_stream_t stream);
 
 /* Same fused pair at the layer-1 -> layer-2 boundary (res given, N2 = 128), which ALSO emits y_pooled =
  * AvgPool2d(2)(y) bf16 [B, H/2, W/2, 256] -- the input of the next block's downsample path ([U] Bottleneck:
@@ -375,6 +391,14 @@ uint64_t ec_rn50_plan_hash(const ec_rn50_t* h);
  * two streams (engine.Worker with 128-frame slices) sets 50 on both handles: each launch then occupies fewer, fully
  * used CUs.  Part of the plan hash; affects only this handle's forwards (it is not process state). */
 int ec_rn50_set_conv8_min_tiles(ec_rn50_t* h, int n);
+/* Tuning property of the handle (no reference counterpart), off by default: layer 1's block-0 output -- 512 B per pixel written
+ * by the layer1.0 boundary launch and read back once as the identity of layer1.1 -- is not stored; the layer1.1 boundary launch
+ * rebuilds it from block 0's conv2 output and block input (ec_conv1x1_pair_rebuild_bf16).  Same number of launches, features
+ * bit-identical, 768 B per 56 x 56 pixel less HBM traffic.  Accepted only on a CLIP tower whose layer1.0 and layer1.1 boundaries
+ * run as fused pairs (width 64, layer 1 of at least three blocks, EC_RN50_FUSE on); EC_ERR_UNSUPPORTED otherwise, and the handle
+ * is unchanged.  The plan is rebuilt (same workspace size); part of the plan hash only while on.  Not to be called while a
+ * forward of this handle is being issued. */
+int ec_rn50_set_l1_rebuild(ec_rn50_t* h, int on);
 
 
 /* ------------------------------------------------------------------------

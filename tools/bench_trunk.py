@@ -11,10 +11,13 @@ ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--chunk", type=int, default=0)
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--min-tiles", type=int, default=0, help="ec_rn50_set_conv8_min_tiles (the engine sets 50 for 2 x >= 128 frames)")
+ap.add_argument("--l1-rebuild", action="store_true", help="ec_rn50_set_l1_rebuild: layer 1's block-0 output rebuilt, not stored (the engine's setting)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 trunk = RN50Trunk(syn.rn50_visual_state_dict(0), device=dev, chunk=a.chunk)
 trunk.set_conv8_min_tiles(a.min_tiles)
+if a.l1_rebuild:
+    assert trunk.set_l1_rebuild(True)
 rgb = syn.synthetic_rgb(1, 8).to(dev).repeat((a.batch + 7) // 8, 1, 1, 1)[:a.batch].contiguous()
 out = trunk.forward(rgb)
 torch.cuda.synchronize()

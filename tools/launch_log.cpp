@@ -4,7 +4,7 @@
 // come first in the library's symbol lookup.
 //
 //   c++ -O1 -std=c++17 -rdynamic -o launch_log tools/launch_log.cpp -ldl
-//   launch_log LIB [--args N] < commands
+//   launch_log LIB [--args N | --args-of SUBSTR N] < commands
 //
 // Commands, one per line (tests/golden/make_conv_routes_golden.py writes them):
 //   conv  B H W Cin Cout ksize pool act res ldo     ec_conv_bf16 (ldo = 0) / ec_conv_bf16_ld
@@ -23,7 +23,10 @@
 //                                                   Bottleneck / BasicBlock tower; the torchvision towers have width 64) through
 //                                                   ec_rn50_forward / _u8 / _depth; `P <ec_rn50_num_ops> <ec_rn50_plan_hash>`
 //                                                   comes before its launches.  rgbd: ec_rn50_embed_rgbd on fp32 RGB frames,
-//                                                   `frames` and `chunk` counting pairs
+//                                                   `frames` and `chunk` counting pairs.  A `+l1` behind the input kind
+//                                                   (f32+l1, ...): ec_rn50_set_l1_rebuild(h, 1) first, `S <rc>` in front of `P`;
+//                                                   `+l1off`: on, then off again
+//   rebuild M K0 N N2                               ec_conv1x1_pair_rebuild_bf16
 //   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse [dhf [core]]
 //                                                   create + ec_policy_workspace_bytes + ec_policy_forward2 (goal_in > 0:
 //                                                   ec_policy_forward_vec) + destroy; mode 0 = EC_POLICY_INFER, 1 = _LEARN;
@@ -42,7 +45,8 @@
 //                                                   as for `policy`; inplace 1: h_final == h0;
 //                                                   act 1 (T = 1, mode 0): ec_policy_act_pooled, sampling, instead of the forward
 // Output: `K <kernel>` per registered kernel, then per command `C <command>`, one `L <kernel>|<grid>|<block>|<lds>` per
-// launch (with --args N: `|` + the first N bytes of the first kernel argument in hex, for the conv_igemm kernels) and `R <rc>`.
+// launch (with --args N: `|` + the first N bytes of the first kernel argument in hex, for the conv_igemm kernels; --args-of SUBSTR N:
+// for the kernels whose name contains SUBSTR) and `R <rc>`.
 #include <cxxabi.h>
 #include <dlfcn.h>
 #include <stdint.h>
@@ -60,6 +64,7 @@ struct dim3 { unsigned x, y, z; };
 static std::map<const void*, std::string> g_kernels;
 static struct { dim3 grid, block; size_t lds; void* stream; } g_cfg;
 static int g_dump_args = 0;
+static std::string g_dump_of = "conv_igemm";
 static int g_log_copies = 0;                   // policy commands: hipMemcpyAsync is part of the recorded sequence
 static uintptr_t g_next = 0x100000000000ull;   // fake device addresses; never dereferenced
 static void* fake(size_t bytes) { void* p = (void*)g_next; g_next += (bytes + 0xfffff) & ~(size_t)0xfffff; return p; }
@@ -83,7 +88,7 @@ int hipLaunchKernel(const void* fn, dim3 g, dim3 b, void** args, size_t lds, voi
     auto it = g_kernels.find(fn);
     const std::string name = it == g_kernels.end() ? "?" : it->second;
     printf("L %s|%u,%u,%u|%u,%u,%u|%zu", name.c_str(), g.x, g.y, g.z, b.x, b.y, b.z, lds);
-    if (g_dump_args && name.find("conv_igemm") != std::string::npos) {
+    if (g_dump_args && name.find(g_dump_of) != std::string::npos) {
         printf("|");
         for (int i = 0; i < g_dump_args; ++i) printf("%02x", ((const unsigned char*)args[0])[i]);
     }
@@ -169,8 +174,11 @@ static int run_trunk(const std::string& kind, int frames, int min_tiles) {
 }
 
 // v: width, the four layer counts, resolution, frames, min_tiles, chunk
-static int run_tower(const std::string& kind, const int* v, const std::string& input) {
+static int run_tower(const std::string& kind, const int* v, const std::string& input_) {
     typedef void* P;
+    const size_t plus = input_.find('+');
+    const std::string input = input_.substr(0, plus), opt = plus == std::string::npos ? "" : input_.substr(plus);
+    if (!opt.empty() && opt != "+l1" && opt != "+l1off") return -100;
     const int width = v[0], *layers = v + 1, res = v[5], frames = v[6], min_tiles = v[7], chunk = v[8];
     const bool clip = kind == "clip", basic = kind == "tvbasic";
     if ((!clip && kind != "tvb" && !basic) || (!clip && width != 64) || width <= 0) return -100;
@@ -189,6 +197,8 @@ static int run_tower(const std::string& kind, const int* v, const std::string& i
     }
     if (rc) return rc;
     sym<int (*)(P, int)>("ec_rn50_set_conv8_min_tiles")(h, min_tiles);
+    if (!opt.empty()) printf("S %d\n", sym<int (*)(P, int)>("ec_rn50_set_l1_rebuild")(h, 1));
+    if (opt == "+l1off") printf("S %d\n", sym<int (*)(P, int)>("ec_rn50_set_l1_rebuild")(h, 0));
     printf("P %d %016llx\n", sym<int (*)(P)>("ec_rn50_num_ops")(h), (unsigned long long)sym<uint64_t (*)(P)>("ec_rn50_plan_hash")(h));
     const size_t ws = sym<size_t (*)(P, int)>("ec_rn50_workspace_bytes")(h, frames);
     const P wsp = fake(ws);
@@ -290,8 +300,9 @@ static int run_pooled(const int* v) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { fprintf(stderr, "usage: launch_log LIB [--args N] < commands\n"); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: launch_log LIB [--args N | --args-of SUBSTR N] < commands\n"); return 2; }
     if (argc >= 4 && !strcmp(argv[2], "--args")) g_dump_args = atoi(argv[3]);
+    if (argc >= 5 && !strcmp(argv[2], "--args-of")) { g_dump_of = argv[3]; g_dump_args = atoi(argv[4]); }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_LOCAL);
     if (!g_lib) { fprintf(stderr, "launch_log: %s\n", dlerror()); return 2; }
     {
@@ -340,6 +351,9 @@ int main(int argc, char** argv) {
             rc = sym<int (*)(P, P, P, P, P, P, P, P, P, P, P, long, int, int, int, P)>("ec_conv1x1_pair_bf16")(
                 in, w, bias, v[4] ? in : nullptr, v[4] ? w : nullptr, v[4] ? bias : nullptr, v[5] ? resb : nullptr, out, w, bias, out, (long)v[0],
                 v[1], v[2], v[3], nullptr);
+        } else if (cmd == "rebuild" && n == 4) {
+            rc = sym<int (*)(P, P, P, P, P, P, P, P, P, P, P, P, P, long, int, int, int, P)>("ec_conv1x1_pair_rebuild_bf16")(
+                in, w, bias, in, w, bias, in, w, bias, out, w, bias, out, (long)v[0], v[1], v[2], v[3], nullptr);
         } else if (cmd == "pairpool" && n == 7) {
             rc = sym<int (*)(P, P, P, P, P, P, P, P, P, int, int, int, int, int, int, P)>("ec_conv1x1_pair_pool_bf16")(
                 in, w, bias, resb, v[6] ? out : nullptr, out, w, bias, out, v[0], v[1], v[2], v[3], v[4], v[5], nullptr);
