@@ -196,6 +196,15 @@ SIGNATURES = {
     "ec_pooled_step0_fwd": (c_int, [c_int, c_void_p, C.c_long] + [c_void_p] * 7 + [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                     c_int, c_void_p, C.c_long, c_void_p, c_void_p, C.c_long, c_void_p, C.c_long, c_void_p, C.c_long, c_int,
                                     c_int, c_void_p]),
+    # the two-view rearrangement net (ResNetRearrangeActorCriticRNN over two frozen CLIP maps per frame) and its front's kernels alone
+    "ec_policy_create_two_view": (c_int, [C.POINTER(c_void_p), c_void_p]),
+    "ec_policy_is_two_view": (c_int, [c_void_p]),
+    "ec_policy_forward_two_view": (c_int, [c_void_p] * 7 + [c_int, c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 3),
+    "ec_policy_act_two_view": (c_int, [c_void_p] * 7 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
+                               + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_two_view_workspace_bytes": (c_size_t, [C.c_long] + [c_int] * 5),
+    "ec_two_view_fwd": (c_int, [c_void_p] * 9 + [C.c_long] + [c_int] * 4 + [c_void_p, c_size_t, c_int, c_void_p]),
+    "ec_two_view_bwd": (c_int, [c_void_p] * 10 + [C.c_long] + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),
 }
 
 RNN_TYPES = {"GRU": 0, "LSTM": 1}      # include/ec_amd.h EC_RNN_GRU / EC_RNN_LSTM
@@ -212,6 +221,12 @@ class PooledCfg(C.Structure):
     _fields_ = [("embed_in", c_int), ("hidden", c_int), ("embed_dims", c_int), ("num_goals", c_int), ("num_sensors", c_int),
                 ("sensor_in", c_int * 3), ("num_actions", c_int), ("prev_action_dims", c_int), ("prev_action_null", c_int),
                 ("rnn_type", c_int), ("num_layers", c_int)]
+
+
+class TwoViewCfg(C.Structure):
+    """``ec_two_view_cfg`` (include/ec_amd.h)."""
+    _fields_ = [(n, c_int) for n in ("in_channels", "spatial", "hidden", "attn_hidden", "num_actions", "prev_action_dims",
+                                     "prev_action_null", "rnn_type", "num_layers")]
 
 
 _lib = None

@@ -356,6 +356,8 @@ size_t ec_pa_grad_scratch_floats(long B, int G, int R);
 void ec_pa_gi_act_launch(int nw, const float* x, const float* W, const float* bias, float* gi, int N, int K, int NO, ec_gi_act_pa pa,
                          hipStream_t s);
 void ec_pa_rows_copy_launch(const float* in, int ld_in, float* out, int ld_out, int rows, int cols, int add, hipStream_t s);
+void ec_pa_bins_launch(const float* dgi, const long long* prev, const float* masks, int null_token, int A, float* scratch, long B, int G,
+                       hipStream_t s);      // the binned ordered sum alone: dPT [R, G] in front of the scratch
 void ec_pa_grad_launch(const float* dgi, const long long* prev, const float* masks, int null_token, int A, const float* emb,
                        const float* w, long ld, int col0, float* demb, float* dw, float* scratch, long B, int G, int E, hipStream_t s);
 
@@ -406,6 +408,25 @@ void ec_pooled_sensor_grads_launch(const float* wih, float* dwih, long ld, int c
 void ec_pooled_frag_pack_launch(const float* w, float* wfrag, int N, int K, hipStream_t s);
 void ec_pooled_fc_act_launch(const float* e, const float* wfrag, const float* b, float* v, int N, int D, int H, hipStream_t s);
 void ec_pooled_step0_launch(int lstm, const ec_rnn_stack_args& a, const ec_pooled_side& sd, hipStream_t s);
+
+// two_view.hip: the two-view rearrangement net's front for policy.hip (argument meanings: the kernels' headers).
+//   planes: [W_a; W_e] as three bf16 planes in fragment order (ec_tv_planes_floats floats; weight-derived)
+//   fwd: v [B, H]; a [B, S2] the probabilities and act [B S2, A1 + H] the post-ReLU activations (attention columns first), each
+//   stored if non-null -- what bwd reads, with ec_tv_bwd_scratch_floats floats of scratch; bwd ADDS onto the six gradients
+struct ec_tv_shape { long B; int S2, C, H, A1; };
+struct ec_tv_fwd_args {
+    const uint16_t *u, *w; const void* wp;
+    const float *be, *ba, *w2, *b2;
+    float *v, *a, *act;
+    long B; int S2, C, H, A1;
+};
+bool ec_tv_shape_ok(const ec_tv_shape& q);
+size_t ec_tv_planes_floats(const ec_tv_shape& q);
+size_t ec_tv_bwd_scratch_floats(const ec_tv_shape& q);
+void ec_tv_pack_launch(const float* We, const float* Wa, void* planes, const ec_tv_shape& q, hipStream_t s);
+void ec_tv_fwd_launch(const ec_tv_fwd_args& a, hipStream_t s);
+void ec_tv_bwd_launch(const void* u, const void* w, const float* w2, const float* dv, const float* a, const float* act, float* scratch,
+                      float* dWe, float* dbe, float* dWa, float* dba, float* dw2, float* db2, const ec_tv_shape& q, hipStream_t s);
 
 #define EC_CHECK_LAUNCH()                                  \
     do {                                                    \

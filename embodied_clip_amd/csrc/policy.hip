@@ -1516,6 +1516,10 @@ struct ec_policy {
         int npre = 0;                                                  // tensors in front of weight_ih_l0
         size_t off[9] = {}, num[9] = {};
         int side() const { return ed * (ids + ns); }                   // columns of weight_ih_l0 between v's and the previous action's
+        // The two-view rearrangement net (ec_policy_create_two_view): the pooled plan from v onwards, with two_view.hip's trainable
+        // front in place of visual_fc.  off / num [TV_WE .. TV_B2]: its six tensors; no goal-id embedding, no sensors, D unused
+        bool tv = false;
+        int tvC = 0, tvS2 = 0, tvA1 = 0;
     } pl;
     // EC_POLICY_INFER_REUSE bookkeeping: the key of the launch plan (make_plan) that built the weight-derived tables in a given
     // act workspace.  Which tables exist and where (E1, W1's planes in fragment order, the re-ordered weight_ih and its
@@ -1654,6 +1658,7 @@ struct Geo {
     int E, R, ldw;                // previous-action embedding: width (0: none), table rows, weight_ih's row stride flat + X + E
     int X, pcol;                  // pooled-embedding net: the goal-id / sensor columns of weight_ih (0 elsewhere); the previous action's first column flat + X
     bool pooled; int D, PK, PG;   // pooled-embedding net: embedding width, sensor floats per frame, goal-table rows
+    bool tv; int tvC, tvS2, tvA1; // two-view net (a pooled plan with another front): feature channels, pixels per frame, attention width
     int G, SW;                    // gate width 3H (GRU) | 4H (LSTM); state width H | 2H (an LSTM state row is [h | c])
     int L;                        // recurrent layers; a state row is [N, L * SW], layer l's state the slice at l * SW
 };
@@ -1687,6 +1692,10 @@ struct Ws {   // float offsets into the workspace
     // the sensor floats; the backward's dSV / dsb and the goal table's binned-sum scratch.  v [B, H] is the `x` area, dv `dx`, the
     // dense copy of weight_ih[:, :H] `wihA` (inference) / `wihP` (learn pass), as on a handle with a previous-action embedding.
     size_t gt, sv, sb, fcF, pgoal, psens, dsv, dsb, gts;
+    // two-view net (all empty on every other handle): the combined conv weight as bf16 planes in fragment order (weight-derived,
+    // kept under EC_POLICY_INFER_REUSE); the learn pass's attention probabilities [B, S2] and post-ReLU activations [B S2, A1 + H];
+    // the backward's scratch (ec_tv_bwd_scratch_floats)
+    size_t tvw, tva, tvact, tvs;
 };
 constexpr int GP_MAXY = 64;                   // row blocks of tn_small_part_kernel
 constexpr int HP_MAXY = 128;                  // row blocks of the wide heads' column sum
@@ -1697,6 +1706,8 @@ enum class Wih { plain, perm_learn, perm_act };                  // weight_ih as
 enum class Step { gemm_gates, fused32, fused16 };                // a recurrence step: GEMM + gate kernel / 32-tile / 16-tile fused kernel
 enum class Cell { gru, lstm };                                   // the recurrent cell (lstm.hip's kernels: always the 32-tile ones)
 enum { PL_FCW, PL_FCB, PL_GEMB, PL_SW0, PL_SB0 };                // ec_policy::Pooled::off / num (sensor i: PL_SW0 + 2 i, PL_SB0 + 2 i)
+enum { TV_WE, TV_BE, TV_WA, TV_BA, TV_W2, TV_B2, TV_NPRE };      // ... of a two-view handle
+constexpr int PA_TABLE_MAX_E = 64;                               // widest previous-action embedding of prev_action.hip's table / chain kernels
 
 struct Plan {
     Geo g;
@@ -1792,6 +1803,11 @@ Ws layout(const ec_policy_cfg& c, const Geo& g, Cell cell, int parts, bool bwd, 
     w.pgoal = take_if(pids && bwd, 2 * B); w.psens = take_if(psn && bwd, B * (size_t)g.PK);
     w.dsv = take_if(psn && bwd, G * (size_t)g.PK); w.dsb = take_if(psn && bwd, G);
     w.gts = take_if(pids && bwd, pids ? ec_pa_grad_scratch_floats((long)B, g.G, g.PG) : 0);
+    const ec_tv_shape tvs{(long)B, g.tvS2, g.tvC, g.H, g.tvA1};
+    w.tvw = take_if(g.tv, g.tv ? ec_tv_planes_floats(tvs) : 0);
+    w.tva = take_if(g.tv && bwd, B * (size_t)g.tvS2);
+    w.tvact = take_if(g.tv && bwd, B * (size_t)g.tvS2 * (H + (size_t)g.tvA1));
+    w.tvs = take_if(g.tv && bwd, g.tv ? ec_tv_bwd_scratch_floats(tvs) : 0);
     w.end = o;
     return w;
 }
@@ -1808,6 +1824,7 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     g.H = c.hidden; g.A = c.num_actions; g.A1 = g.A + 1; g.C = c.in_channels; g.cat = c.compress_out + c.goal_dims;
     g.nstream = (c.dual && !c.fusion) ? 2 : 1; g.flat1 = c.comb_out * g.S; g.flat = c.fusion ? c.in_channels : g.nstream * g.flat1;
     g.pooled = h->pl.on; g.X = h->pl.side(); g.D = h->pl.D; g.PK = h->pl.K; g.PG = h->pl.ids ? c.num_goals : 0;
+    g.tv = h->pl.tv; g.tvC = h->pl.tvC; g.tvS2 = h->pl.tvS2; g.tvA1 = h->pl.tvA1;
     g.E = c.prev_action_dims; g.R = c.num_actions + c.prev_action_null; g.pcol = g.flat + g.X; g.ldw = g.pcol + g.E;   // (no route below depends on E)
     p.cell = h->rnn == EC_RNN_LSTM ? Cell::lstm : Cell::gru;
     g.G = (p.cell == Cell::lstm ? 4 : 3) * c.hidden; g.SW = (p.cell == Cell::lstm ? 2 : 1) * c.hidden;
@@ -1865,7 +1882,8 @@ Plan make_plan(const ec_policy* h, int T, int N, int mode, bool feat_bf16) {
     // a multi-layer core's act step: every layer one launch of the 32-tile geometry (a GRU whose fused step is off: the general route)
     p.stack = g.L > 1 && cfg.rnn_stack && p.infer && T == 1 && p.step_fwd == Step::fused32 && ec_lstm_hidden_ok(H);
     // a pooled-embedding handle's act step: visual_fc on the gi_act geometry (K = D over 7 or 8 waves), then layer 0 in one launch
-    const bool pact_any = g.pooled && cfg.pooled_act && ec_lstm_hidden_ok(H) && (g.D % 56 == 0 || g.D % 64 == 0);   // (a handle that can take it)
+    // (a two-view handle: its front's launch stands where visual_fc's does)
+    const bool pact_any = g.pooled && cfg.pooled_act && ec_lstm_hidden_ok(H) && (g.tv || g.D % 56 == 0 || g.D % 64 == 0);   // (a handle that can take it)
     p.pact = pact_any && p.infer && T == 1;
     // GRU input projection.  Act step with a handful of rows: one launch, K split over the waves of a workgroup and folded
     // in-kernel (gi_act_kernel); else split-K only as separate partial matrices folded by the step kernel
@@ -1948,9 +1966,14 @@ struct Fwd : Ctx {
     // of the re-ordered weight, which those routes leave unused
     const float* wih_plain() const { return g.ldw != g.flat ? ws + (p.infer ? w.wihA : w.wihP) : W(P_WIH); }
     // previous-action embedding: the table (with the other weight-derived tables) and, for a backward, the indices
-    void prev_action_tables() {
-        if (!reuse) ec_pa_table_launch(W(P_PAE), W(P_WIH), g.ldw, g.pcol, ws + w.pt, g.R, g.G, g.E, s);
+    // (E above PA_TABLE_MAX_E, a two-view handle alone: PT = Emb . W_ih[:, pcol:]^T as one ec_gemm_f32)
+    int prev_action_tables() {
+        if (!reuse) {
+            if (g.E > PA_TABLE_MAX_E) RC(gemm(W(P_PAE), W(P_WIH) + g.pcol, ws + w.pt, g.R, g.G, g.E, g.E, 1, 1, g.ldw, g.G));
+            else ec_pa_table_launch(W(P_PAE), W(P_WIH), g.ldw, g.pcol, ws + w.pt, g.R, g.G, g.E, s);
+        }
         if (!p.infer) (void)hipMemcpyAsync(ws + w.paidx, prev, (size_t)g.B * 8, hipMemcpyDeviceToDevice, s);
+        return EC_OK;
     }
 
     // ---- the pooled-embedding net (pooled_net.hip's kernels; the tables of prev_action.hip) ----
@@ -1969,7 +1992,7 @@ struct Fwd : Ctx {
             if (q.ns) ec_pooled_tables_launch(W(P_WIH), g.ldw, H + q.ids * q.ed, pooled_sensors(nullptr), ws + w.sv, ws + w.sb, GW, s);
             if (p.pact) ec_pooled_frag_pack_launch(PW(PL_FCW), ws + w.fcF, H, q.D, s);
         }
-        if (g.E) prev_action_tables();
+        if (g.E) RC(prev_action_tables());
         if (!p.infer) {
             if (q.ids) (void)hipMemcpyAsync(ws + w.pgoal, goal, (size_t)B * 8, hipMemcpyDeviceToDevice, s);
             if (q.ns) (void)hipMemcpyAsync(ws + w.psens, sens, (size_t)B * q.K * 4, hipMemcpyDeviceToDevice, s);
@@ -1983,6 +2006,28 @@ struct Fwd : Ctx {
         RC(gemm(embed, PW(PL_FCW), ws + w.x, B, H, q.D, q.D, 1, 1, q.D, H, EC_GEMM_RELU, PW(PL_FCB)));
         RC(gemm(ws + w.x, wih_dense(), ws + w.gi, B, GW, H, H, 1, 1, H, GW, 0, W(P_BIH)));
         ec_pooled_rows_add_launch(ws + w.gi, side, (long)B, GW, s);
+        return EC_OK;
+    }
+
+    // The two-view net's front: the weight-derived tables (unless reused), then v = the attention-pooled encoder of (u, w) into
+    // the `x` area -- a learn pass also keeps the probabilities and the post-ReLU activations -- and, on the general route, the
+    // input projection with the previous action's table row added
+    ec_tv_shape tv_shape() const { return ec_tv_shape{(long)g.B, g.tvS2, g.tvC, g.H, g.tvA1}; }
+    int two_view_front(const void* u, const void* v2) {
+        const int B = g.B, H = g.H, GW = g.G;
+        if (!reuse) {
+            ec_pa_rows_copy_launch(W(P_WIH), g.ldw, wih_dense(), H, GW, H, 0, s);
+            ec_tv_pack_launch(PW(TV_WE), PW(TV_WA), ws + w.tvw, tv_shape(), s);
+        }
+        if (g.E) RC(prev_action_tables());
+        side = ec_pooled_side{nullptr, nullptr, nullptr, 0, g.E ? ws + w.pt : nullptr, prev, masks_all, c.prev_action_null, c.num_actions,
+                              nullptr, nullptr, 0};
+        const ec_tv_fwd_args a{(const uint16_t*)u, (const uint16_t*)v2, ws + w.tvw, PW(TV_BE), PW(TV_BA), PW(TV_W2), PW(TV_B2), ws + w.x,
+                               p.infer ? nullptr : ws + w.tva, p.infer ? nullptr : ws + w.tvact, (long)B, g.tvS2, g.tvC, H, g.tvA1};
+        ec_tv_fwd_launch(a, s);
+        if (pact) return EC_OK;
+        RC(gemm(ws + w.x, wih_dense(), ws + w.gi, B, GW, H, H, 1, 1, H, GW, 0, W(P_BIH)));
+        if (g.E) ec_pooled_rows_add_launch(ws + w.gi, side, (long)B, GW, s);
         return EC_OK;
     }
 
@@ -2287,7 +2332,8 @@ bool tables_reusable(const ec_policy* h, const void* workspace, const Plan& p, i
     return false;
 }
 
-struct PooledIn { const float* sensors; };      // the pooled-embedding net's entry points: feat = the embedding rows, and the sensor floats
+// the pooled-embedding net's entry points: feat = the embedding rows, and the sensor floats; the two-view net's (tv): feat, feat2 = u, w
+struct PooledIn { const float* sensors; bool tv = false; };
 
 int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16, const int64_t* goal,
                         const float* goal_vec, const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int mode, float* hv,
@@ -2295,7 +2341,11 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
                         const int64_t* prev_actions = nullptr, bool pa_entry = false, const PooledIn* pin = nullptr) {
     if (!h || !params || !feat || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
     if ((pin != nullptr) != h->pl.on) return EC_ERR_ARG;          // the pooled-embedding net has entry points of its own
-    if (pin) {
+    if (pin && pin->tv != h->pl.tv) return EC_ERR_ARG;            // ... and so has the two-view net
+    if (pin && pin->tv) {
+        if (!feat2 || goal || goal_vec || pin->sensors || (prev_actions != nullptr) != (h->c.prev_action_dims > 0)) return EC_ERR_ARG;
+        if ((((uintptr_t)feat | (uintptr_t)feat2) & 15) != 0) return EC_ERR_ARG;
+    } else if (pin) {
         // a NULL argument matches a part the handle does not have, and the reverse
         if ((goal != nullptr) != (h->pl.ids != 0) || (pin->sensors != nullptr) != (h->pl.ns > 0) ||
             (prev_actions != nullptr) != (h->c.prev_action_dims > 0) || goal_vec || feat2 || feat_bf16)
@@ -2316,7 +2366,8 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
     if (pin) {
         f.prev = (const long long*)prev_actions; f.masks_all = masks;
         f.pact = p.pact && h_final && h_final != h0;
-        RC(f.pooled_front((const float*)feat, (const long long*)goal, pin->sensors));
+        if (pin->tv) RC(f.two_view_front(feat, feat2));
+        else RC(f.pooled_front((const float*)feat, (const long long*)goal, pin->sensors));
         if (f.pact) {
             f.pooled_act_recurrence(h0, masks, h_final);
             RC(f.heads(f.hs_top(), hv, nullptr, smp, wide));
@@ -2329,7 +2380,7 @@ int policy_forward_impl(const ec_policy_t* h, const float* params, const void* f
     if (!h->c.fusion)
         for (int sidx = 0; sidx < p.g.nstream; ++sidx)   // dual encoder: the RGB stream, then the depth stream (own weights, own activations)
             RC(f.encoder_stream(sidx, sidx ? feat2 : feat));
-    if (p.g.E) { f.prev = (const long long*)prev_actions; f.masks_all = masks; f.prev_action_tables(); }
+    if (p.g.E) { f.prev = (const long long*)prev_actions; f.masks_all = masks; RC(f.prev_action_tables()); }
     RC(f.input_projection());
     }
     const bool lstm = p.cell == Cell::lstm;   // (the heads read the dense history; recurrence_lstm leaves the [h | c] rows in h_final)
@@ -2539,9 +2590,17 @@ struct Bwd : Ctx {
         }
         colsum(ws + w.dgi, G(P_BIH), B, GW, GW);
         // previous-action embedding: its gradient and columns flat.. of weight_ih's (inside the recurrent section: before the event)
-        if (g.E)
+        if (g.E > PA_TABLE_MAX_E) {
+            // (a two-view handle alone) the same binned ordered sum over frames -- it does not depend on E -- leaves dPT [R, G] in front
+            // of the scratch; dEmb += dPT Wa and dWa += dPT^T Emb on ec_gemm_f32, the second through the transpose-read routine
+            ec_pa_bins_launch(ws + w.dgi, (const long long*)(ws + w.paidx), masks_all, c.prev_action_null, c.num_actions, ws + w.pas, (long)B,
+                              GW, s);
+            RC(gemm(ws + w.pas, W(P_WIH) + g.pcol, G(P_PAE), g.R, g.E, GW, GW, 1, g.ldw, 1, g.E, EC_GEMM_ACCUMULATE | p.bwd3));
+            RC(tn(ws + w.pas, GW, W(P_PAE), g.E, 0, G(P_WIH) + g.pcol, GW, g.E, g.R, g.ldw));
+        } else if (g.E) {
             ec_pa_grad_launch(ws + w.dgi, (const long long*)(ws + w.paidx), masks_all, c.prev_action_null, c.num_actions, W(P_PAE), W(P_WIH),
                               g.ldw, g.pcol, G(P_PAE), G(P_WIH), ws + w.pas, (long)B, GW, g.E, s);
+        }
         return EC_OK;
     }
 
@@ -2575,6 +2634,20 @@ struct Bwd : Ctx {
         parts_ok = false;
         RC(tn(ws + w.dx, H, embed, q.D, 0, grads + q.off[PL_FCW], H, q.D, B, q.D));
         colsum(ws + w.dx, grads + q.off[PL_FCB], B, H, H);
+        return EC_OK;
+    }
+
+    // The two-view net: dv = dgi W_ih[:, :H] with no mask (v is not rectified after pooling), then the front's six gradients from the
+    // probabilities and activations the forward kept (two_view.hip: ordered sums only)
+    int two_view_grads(const void* u, const void* v2) {
+        const ec_policy::Pooled& q = h->pl;
+        const int B = g.B, H = g.H, GW = g.G;
+        RC(ec_gemm_f32(ws + w.dgi, ws + w.wihP, ws + w.dx, B, H, GW, GW, 1, H, 1, H, p.bwd3, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1,
+                       stream));
+        parts_ok = false;
+        ec_tv_bwd_launch(u, v2, PW(TV_W2), ws + w.dx, ws + w.tva, ws + w.tvact, ws + w.tvs, grads + q.off[TV_WE], grads + q.off[TV_BE],
+                         grads + q.off[TV_WA], grads + q.off[TV_BA], grads + q.off[TV_W2], grads + q.off[TV_B2],
+                         ec_tv_shape{(long)B, g.tvS2, g.tvC, H, g.tvA1}, s);
         return EC_OK;
     }
 
@@ -2799,7 +2872,7 @@ extern "C" int ec_policy_param_offset(const ec_policy_t* h, int idx, size_t* off
         if (k >= 8 + (h->c.prev_action_dims ? 1 : 0)) return EC_ERR_ARG;
         if (k < 0) {
             int t = idx;                              // (the goal-id embedding's slot is skipped on a handle without one)
-            if (!h->pl.ids && t >= PL_GEMB) ++t;
+            if (!h->pl.tv && !h->pl.ids && t >= PL_GEMB) ++t;
             *off = h->pl.off[t]; *numel = h->pl.num[t];
         } else {
             const int i = k < 8 ? P_WIH + k : P_PAE;
@@ -2892,7 +2965,7 @@ static int policy_act_any(const ec_policy_t* h, const float* params, const void*
                           const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream,
                           const PooledIn* pin = nullptr) {
     if (!h || !actions || !logp) return EC_ERR_ARG;
-    if ((pin != nullptr) != h->pl.on) return EC_ERR_ARG;
+    if ((pin != nullptr) != h->pl.on || (pin && pin->tv != h->pl.tv)) return EC_ERR_ARG;
     if (!pin && (pa_entry != (h->c.prev_action_dims > 0) || (pa_entry && !prev_actions))) return EC_ERR_ARG;
     if ((expert_actions != nullptr) != (expert_mask != nullptr)) return EC_ERR_ARG;
     if (!(force_p >= 0.f && force_p <= 1.f)) return EC_ERR_ARG;       // (NaN included)
@@ -2941,7 +3014,7 @@ extern "C" int ec_policy_act_pa(const ec_policy_t* h, const float* params, const
 
 // The pooled-embedding net (include/ec_amd.h): a handle whose plan is the fusion handle's with in_channels = hidden, its own
 // tensors in front of weight_ih_l0, and the two entry points below
-extern "C" int ec_policy_is_pooled(const ec_policy_t* h) { return (h && h->pl.on) ? 1 : 0; }
+extern "C" int ec_policy_is_pooled(const ec_policy_t* h) { return (h && h->pl.on && !h->pl.tv) ? 1 : 0; }
 extern "C" int ec_policy_create_pooled(ec_policy_t** out, const ec_pooled_cfg* cfg) {
     if (!out || !cfg) return EC_ERR_ARG;
     const ec_pooled_cfg& q = *cfg;
@@ -3018,6 +3091,72 @@ extern "C" int ec_policy_act_pooled(const ec_policy_t* h, const float* params, c
                           &pin);
 }
 
+// The two-view rearrangement net (include/ec_amd.h): the pooled-embedding handle's plan from v onwards, two_view.hip's front
+extern "C" int ec_policy_is_two_view(const ec_policy_t* h) { return (h && h->pl.tv) ? 1 : 0; }
+extern "C" int ec_policy_create_two_view(ec_policy_t** out, const ec_two_view_cfg* cfg) {
+    if (!out || !cfg) return EC_ERR_ARG;
+    const ec_two_view_cfg& q = *cfg;
+    if (q.rnn_type != EC_RNN_GRU && q.rnn_type != EC_RNN_LSTM) return EC_ERR_ARG;
+    if (q.num_layers < 1 || q.num_layers > EC_RNN_MAX_LAYERS) return EC_ERR_ARG;
+    if (q.num_actions < 2 || q.num_actions > 256) return EC_ERR_ARG;
+    if (q.prev_action_dims < 0 || q.prev_action_dims > 512 || (q.prev_action_null != 0 && q.prev_action_null != 1)) return EC_ERR_ARG;
+    if (q.prev_action_null && !q.prev_action_dims) return EC_ERR_ARG;
+    if (q.spatial < 1 || q.spatial > 8) return EC_ERR_SHAPE;
+    if (!ec_tv_shape_ok(ec_tv_shape{1, q.spatial * q.spatial, q.in_channels, q.hidden, q.attn_hidden})) return EC_ERR_SHAPE;
+    ec_policy* h = new (std::nothrow) ec_policy();
+    if (!h) return EC_ERR_ALLOC;
+    ec_policy_cfg& c = h->c;
+    c = ec_policy_cfg{};
+    c.in_channels = q.hidden; c.spatial = 1; c.hidden = q.hidden; c.num_goals = 0; c.num_actions = q.num_actions;
+    c.fusion = 1;                        // (the plan's: M49 = 0, flat = in_channels = hidden; no goal table is ever read)
+    c.prev_action_dims = q.prev_action_dims; c.prev_action_null = q.prev_action_null;
+    h->rnn = q.rnn_type; h->layers = q.num_layers;
+    ec_policy::Pooled& pl = h->pl;
+    pl.on = true; pl.tv = true; pl.tvC = q.in_channels; pl.tvS2 = q.spatial * q.spatial; pl.tvA1 = q.attn_hidden;
+    pl.npre = TV_NPRE;
+    const size_t H = q.hidden, GW = (q.rnn_type == EC_RNN_LSTM ? 4 : 3) * H, ld = H + q.prev_action_dims, K3 = 3 * (size_t)q.in_channels;
+    size_t o = 0;
+    auto put = [&](size_t& off, size_t& num, size_t n) { off = o; num = n; o += (n + 3) / 4 * 4; };   // 16-B aligned
+    put(pl.off[TV_WE], pl.num[TV_WE], H * K3);
+    put(pl.off[TV_BE], pl.num[TV_BE], H);
+    put(pl.off[TV_WA], pl.num[TV_WA], (size_t)q.attn_hidden * K3);
+    put(pl.off[TV_BA], pl.num[TV_BA], (size_t)q.attn_hidden);
+    put(pl.off[TV_W2], pl.num[TV_W2], (size_t)q.attn_hidden);
+    put(pl.off[TV_B2], pl.num[TV_B2], 1);
+    for (int i = 0; i < P_COUNT; ++i) { h->off[i] = 0; h->num[i] = 0; h->order[i] = i; }
+    const size_t n8[8] = {GW * ld, GW * H, GW, GW, (size_t)q.num_actions * H, (size_t)q.num_actions, H, 1};
+    for (int k = 0; k < 8; ++k) put(h->off[P_WIH + k], h->num[P_WIH + k], n8[k]);
+    h->off[P_PAE] = o;
+    if (q.prev_action_dims) put(h->off[P_PAE], h->num[P_PAE], (size_t)(q.num_actions + q.prev_action_null) * q.prev_action_dims);
+    h->ntensors = ec_policy_num_param_tensors(h) - 4 * (q.num_layers - 1);
+    h->nbase = h->ntensors;
+    for (int l = 1; l < q.num_layers; ++l) {
+        const size_t un[4] = {GW * H, GW * H, GW, GW};
+        for (int k = 0; k < 4; ++k) put(h->uoff[l - 1][k], h->unum[l - 1][k], un[k]);
+    }
+    h->total = o;
+    *out = h;
+    return EC_OK;
+}
+extern "C" int ec_policy_forward_two_view(const ec_policy_t* h, const float* params, const void* feat, const void* feat2,
+                                          const int64_t* prev_actions, const float* h0, const float* masks, int T, int N,
+                                          void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final,
+                                          ec_stream_t stream) {
+    const PooledIn pin{nullptr, true};
+    return policy_forward_impl(h, params, feat, feat2, 0, nullptr, nullptr, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final,
+                               SampleArgs{}, stream, nullptr, prev_actions, false, &pin);
+}
+extern "C" int ec_policy_act_two_view(const ec_policy_t* h, const float* params, const void* feat, const void* feat2,
+                                      const int64_t* prev_actions, const float* h0, const float* masks, int N, void* workspace,
+                                      size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
+                                      float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
+                                      const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
+    const PooledIn pin{nullptr, true};
+    return policy_act_any(h, params, feat, feat2, 0, nullptr, nullptr, prev_actions, false, h0, masks, N, workspace, ws_bytes, reuse_tables,
+                          hv, h_final, actions, logp, values, greedy, seed, step, first_actor, expert_actions, expert_mask, force_p, stream,
+                          &pin);
+}
+
 extern "C" int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,
                                   const float* masks, int T, int N, void* workspace, size_t ws_bytes, const float* dhv,
                                   const float* dh_final, float* grads, ec_stream_t stream) {
@@ -3038,6 +3177,7 @@ extern "C" int ec_policy_backward3(const ec_policy_t* h, const float* params, co
     if (!h || !params || !feat || !masks || !workspace || !dhv || !grads) return EC_ERR_ARG;
     if (h->c.dual && !feat2) return EC_ERR_ARG;
     if (h->pl.on && ((uintptr_t)feat & 15) != 0) return EC_ERR_ARG;      // (the embedding rows are read as float4)
+    if (h->pl.tv && (!feat2 || !feat_bf16 || ((uintptr_t)feat2 & 15) != 0)) return EC_ERR_ARG;   // (two views, both bf16)
     if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
     const Plan p = make_plan(h, T, N, EC_POLICY_LEARN, feat_bf16 != 0 && !h->pl.on);
     if (ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
@@ -3056,7 +3196,9 @@ extern "C" int ec_policy_backward3(const ec_policy_t* h, const float* params, co
     // here; what follows only writes the goal encoder's.  A caller that sums the bucket over ranks starts that section's
     // all-reduce behind this event, under the rest of this backward
     if (recurrent_grads_ready && hipEventRecord((hipEvent_t)recurrent_grads_ready, b.s) != hipSuccess) return EC_ERR_LAUNCH;
-    if (h->pl.on) {
+    if (h->pl.tv) {
+        RC(b.two_view_grads(feat, feat2));
+    } else if (h->pl.on) {
         RC(b.pooled_fc_grads((const float*)feat));
     } else if (!h->c.fusion) {   // (fusion: the image embedding and the goal table are frozen, nothing trainable upstream of the GRU)
         b.parts_ok = p.wih == Wih::perm_learn;   // the plain path writes dx into the partial-matrix area now

@@ -201,8 +201,9 @@ size_t ec_pa_grad_scratch_floats(long B, int G, int R) {
     const long chunk = pa_chunk(B, R);
     return (size_t)((B + chunk - 1) / chunk + 1) * R * G;
 }
-void ec_pa_grad_launch(const float* dgi, const long long* prev, const float* masks, int null_token, int A, const float* emb,
-                       const float* w, long ld, int col0, float* demb, float* dw, float* scratch, long B, int G, int E, hipStream_t s) {
+// the binned ordered sum alone: dPT [R, G] into the first R * G floats of the scratch (the partitions' bins behind it)
+void ec_pa_bins_launch(const float* dgi, const long long* prev, const float* masks, int null_token, int A, float* scratch, long B, int G,
+                       hipStream_t s) {
     const int R = A + null_token;
     const long chunk = pa_chunk(B, R);
     const int P = (int)((B + chunk - 1) / chunk);
@@ -217,6 +218,12 @@ void ec_pa_grad_launch(const float* dgi, const long long* prev, const float* mas
     hipLaunchKernelGGL(pa_bin_kernel, dim3((unsigned)((G + PA_COLS - 1) / PA_COLS), (unsigned)P), dim3(64), lds, s, dgi,
                        prev, masks, null_token, A, part, B, G, chunk);
     hipLaunchKernelGGL(pa_fold_kernel, dim3((unsigned)((RG + 255) / 256)), dim3(256), 0, s, part, dpt, RG, P);
+}
+void ec_pa_grad_launch(const float* dgi, const long long* prev, const float* masks, int null_token, int A, const float* emb,
+                       const float* w, long ld, int col0, float* demb, float* dw, float* scratch, long B, int G, int E, hipStream_t s) {
+    const int R = A + null_token;
+    const float* dpt = scratch;
+    ec_pa_bins_launch(dgi, prev, masks, null_token, A, scratch, B, G, s);
     hipLaunchKernelGGL(pa_demb_kernel, dim3((unsigned)R), dim3(256), 0, s, dpt, w, ld, col0, demb, G, E);
     hipLaunchKernelGGL(pa_dw_kernel, dim3((unsigned)G), dim3(64), 0, s, dpt, emb, dw, ld, col0, R, G, E);
 }

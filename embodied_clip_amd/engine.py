@@ -54,7 +54,7 @@ class SyntheticEnv:
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
                  frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False, expert: bool = False,
-                 num_actions: int = 6, sensors: int = 0):
+                 num_actions: int = 6, sensors: int = 0, goal_view: bool = False):
         self.N, self.T = n_actors, T
         self.host = host
         # frames_u8: raw uint8 frames (what the simulator renders); normalisation is then fused into the stem kernel.
@@ -96,6 +96,14 @@ class SyntheticEnv:
             # the pooled-embedding net's small float sensors (GPS, compass, a 3-float point goal): K floats per actor and step,
             # f32 [T+1, N, K], from a seed of their own -- nothing else the env builds changes
             self.sensors = torch.randn(T + 1, n_actors, int(sensors), generator=torch.Generator().manual_seed(seed + 8)).to(device).contiguous()
+        if goal_view:
+            # the two-view rearrangement net: a second RGB frame per actor and step, the view of the GOAL state from the same pose, in
+            # the frames' wire form and construction, from a seed and hash stream of its own -- nothing else the env builds changes
+            gbase = syn.synthetic_rgb_u8(seed + 9, n_actors, res).to(device)
+            if not frames_u8:
+                gbase = syn.normalize_rgb(gbase)
+            self.goal_frames = torch.stack([gbase.roll(shifts=s + 1, dims=0).roll(shifts=7 * (s + 1), dims=2)
+                                            for s in range(pool_steps)]).contiguous()   # [P, N, R, R, 3] fp32 | uint8, on the device
         self._k = 0
 
     def observe(self, actions_host: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -117,6 +125,14 @@ class SyntheticEnv:
         """The depth batch that goes with ``observe_at(k)``."""
         return self.depth[k % self.pool_steps]
 
+    def observe_goal_view(self) -> torch.Tensor:
+        """The goal-state views that go with the frames ``observe()`` served last (``goal_view=True`` envs)."""
+        return self.goal_frames[(self._k - 1) % self.pool_steps]
+
+    def observe_goal_view_at(self, k: int) -> torch.Tensor:
+        """The goal-state views that go with ``observe_at(k)``."""
+        return self.goal_frames[k % self.pool_steps]
+
 
 class NavSyntheticEnv(SyntheticEnv):
     """``SyntheticEnv`` (the same frames, masks, goals, rewards, success) plus the geometry the navigation metrics read:
@@ -125,8 +141,8 @@ class NavSyntheticEnv(SyntheticEnv):
 
     def __init__(self, n_actors: int, T: int, device, seed: int, pool_steps: int = 4, res: int = 224,
                  frames_u8: bool = False, host: bool = False, goal_in: int = 0, depth: bool = False, expert: bool = False,
-                 num_actions: int = 6, sensors: int = 0):
-        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in, depth, expert, num_actions, sensors)
+                 num_actions: int = 6, sensors: int = 0, goal_view: bool = False):
+        super().__init__(n_actors, T, device, seed, pool_steps, res, frames_u8, host, goal_in, depth, expert, num_actions, sensors, goal_view)
         self.num_goals = 0 if goal_in else 12
         step_dist, start_dist, goal_dist = syn.synthetic_navigation(seed + 4, self.masks[1:], self.success)
         self.step_dist = step_dist.to(device).contiguous()
@@ -142,11 +158,12 @@ class _Slice:
     pass
 
 
-def check_prev_actions(prev_actions: int, depth: bool, zeroshot: bool) -> int:
-    """``Worker`` / ``Evaluator`` ``(prev_actions=E)``: the embedding's width, refused where the policy library refuses it."""
+def check_prev_actions(prev_actions: int, depth: bool, zeroshot: bool, max_dims: int = 64) -> int:
+    """``Worker`` / ``Evaluator`` ``(prev_actions=E)``: the embedding's width, refused where the policy library refuses it
+    (``max_dims``: 512 on the two-view net, whose upstream width is the hidden size)."""
     E = int(prev_actions)
-    if not 0 <= E <= 64:
-        raise ValueError(f"prev_actions={prev_actions}: the embedding's width is 0 (off) or 1..64")
+    if not 0 <= E <= max_dims:
+        raise ValueError(f"prev_actions={prev_actions}: the embedding's width is 0 (off) or 1..{max_dims}")
     if E and depth:
         raise ValueError("prev_actions > 0 with depth=True: the dual (RGB + depth) goal encoder with previous actions is not built")
     if E and zeroshot:
@@ -193,9 +210,27 @@ def check_rgbd(encoder: str, zeroshot: bool, goal_in: int, frames_host: bool) ->
 def check_net(net: str, pooling: str, sensors, goal_ids: bool, encoder: str, depth: bool, zeroshot: bool, goal_in: int):
     """``Worker`` / ``Evaluator`` ``(net=..., pooling=..., sensors=..., goal_ids=...)``: "goal_encoder" (the default: AllenAct's
     ResnetTensorGoalEncoder agent) or "pooled" (habitat-lab's PointNavResNetNet over the pooled embedding, ``PolicyHandle.pooled``).
+    "two_view": the rearrangement agent ([U] ResNetRearrangeActorCriticRNN, ``PolicyHandle.two_view``) -- a pooled plan over the
+    feature MAPS of two views: no goal input at all, so it returns (True, None, ()) and its users clear ``goal_ids``.
     Raised before anything is allocated.  -> (pooled, pooling, sensors)"""
-    if net not in ("goal_encoder", "pooled"):
-        raise ValueError(f"net={net!r}: 'goal_encoder' or 'pooled'")
+    if net not in ("goal_encoder", "pooled", "two_view"):
+        raise ValueError(f"net={net!r}: 'goal_encoder', 'pooled' or 'two_view'")
+    if net == "two_view":
+        if depth:
+            raise ValueError("net='two_view' with depth=True: the second feature buffer holds the goal view; an RGB-D rearrangement agent is not built")
+        if zeroshot:
+            raise ValueError("net='two_view' with zeroshot=True: the zero-shot fusion policy is another net")
+        if goal_in:
+            raise ValueError("net='two_view' with goal_in > 0: the goal IS the second view; the net has no coordinate goal")
+        if tuple(sensors):
+            raise ValueError("net='two_view' with sensors=...: float sensors belong to net='pooled'")
+        if not goal_ids:
+            raise ValueError("net='two_view' with goal_ids=False: the switch belongs to net='pooled' (this net has no goal-id input either way)")
+        if pooling != "attnpool":
+            raise ValueError("net='two_view' with pooling=...: the net reads the 7 x 7 feature maps and pools them itself")
+        if encoder == "vit":
+            raise ValueError("net='two_view' with encoder='vit': the ViT's patch tokens as a second view are not built")
+        return True, None, ()
     if net == "goal_encoder":
         if tuple(sensors):
             raise ValueError("sensors=... belongs to net='pooled'")
@@ -262,9 +297,13 @@ class _SlicedActor:
       a pair in one pass into ONE vector; no second buffer, and the policy is the RGB pooled net's."""
     depth = False
 
+    # net="two_view" (check_net): the rearrangement agent -- the env also serves the goal-state view, every slice encodes it with its
+    # one trunk handle into ``sl.feat2`` (the RGB-D agent's second buffer), and the policy is ``PolicyHandle.two_view``
+    two_view_net = False
+
     @property
     def dual(self) -> bool:
-        return self.depth and not self.pooled_net
+        return (self.depth and not self.pooled_net) or self.two_view_net
     # the previous action's embedding ([U] VisualNavActorCritic add_prev_actions / Habitat's prev_action_embedding): its width
     # (0: off) and whether row 0 is the null token of an episode's first step; set by the users before ``_build_model``
     prev_action_dims = 0
@@ -341,6 +380,16 @@ class _SlicedActor:
         if self._embed == "avgpool":      # AdaptiveAvgPool2d(1) of the trunk output (ec_spatial_mean_bf16): D = the trunk's channels
             self.trunk_S, self.trunk_C = self.S, self.C
             self.S = 1
+        if self.two_view_net:
+            self.policy = PolicyHandle.two_view(self.C, hidden=self.hidden_size, num_actions=self._num_actions,
+                                                prev_action_dims=self.prev_action_dims, prev_action_null=self.prev_action_null,
+                                                rnn_type=self.rnn_type, rnn_layers=self.rnn_layers, spatial=self.S)
+            if policy_sd is not None:     # (a checkpoint of another net: refused by the first tensor it lacks, by name)
+                check_model_tensors(self.policy, policy_sd, getattr(self, "_checkpoint", None) or "policy_sd")
+            self.H, self.A, self.SW = self.policy.H, self.policy.A, self.policy.state_width
+            self.params = self.policy.flatten(policy_sd if policy_sd is not None
+                                              else syn.policy_state_dict(0, two_view=self.policy.two_view_cfg), d)
+            return encs, pools
         if self.pooled_net:
             self.policy = PolicyHandle.pooled(self.C, hidden=self.hidden_size, num_goals=12 if self.goal_ids else 0, sensors=self.net_sensors,
                                               num_actions=self._num_actions, prev_action_dims=self.prev_action_dims,
@@ -475,7 +524,7 @@ class _SlicedActor:
     def _observe(self, actions_host=None):
         """env.step: the next RGB batch and (``depth=True``) the depth batch that goes with it."""
         rgb = self.env.observe(actions_host) if actions_host is not None else self.env.observe()
-        return rgb, (self.env.observe_depth() if self.depth else None)
+        return rgb, (self.env.observe_depth() if self.depth else (self.env.observe_goal_view() if self.two_view_net else None))
 
     @property
     def enc_streams(self):
@@ -530,7 +579,10 @@ class _SlicedActor:
         elif self.encoder in ("rn50", "rn50x16") or self.encoder in IMAGENET_ENCODERS:
             # the last conv writes straight into the rollout slice
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.feat[t])
-            if self.dual:      # the depth tower: the same handle on the one-channel batch, behind the RGB tower on this stream
+            if self.two_view_net:   # the goal-state view: the same handle, a second call behind the first on this stream (two calls, not
+                g2 = dep[sl.o:sl.o + sl.n]     # one over the stacked 2n frames: the frames of a slice are not contiguous with their goal views)
+                (sl.enc.forward_u8 if g2.dtype == torch.uint8 else sl.enc.forward)(g2, sl.feat2[t])
+            elif self.dual:    # the depth tower: the same handle on the one-channel batch, behind the RGB tower on this stream
                 sl.enc.forward_depth(dep[sl.o:sl.o + sl.n], sl.feat2[t])
         else:
             sl.enc.forward(src, sl.tok)
@@ -575,7 +627,15 @@ class Worker(_SlicedActor):
                  teacher_forcing=None, prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU",
                  rnn_layers: int = 1, hidden: int = 512, net: str = "goal_encoder", pooling: str = "attnpool", sensors=(),
                  goal_ids: bool = True):
-        """``net="pooled"``: the Habitat DD-PPO net ([U] habitat-lab ``PointNavResNetNet``, restated, parity unpinned;
+        """``net="two_view"``: the rearrangement agent ([U] ai2thor-rearrangement ``ResNetRearrangeActorCriticRNN``, restated, parity
+        unpinned; ``PolicyHandle.two_view``) -- the env also serves the goal-state view of every actor and step
+        (``SyntheticEnv(goal_view=True)``), every slice's trunk handle encodes it behind the current view into ``feat2``, and the
+        trainable attention-pooled front reads both maps.  No goal input.  Works with every ``loss``, teacher forcing, up to 256
+        actions, both cells, ``rnn_layers``, ``prev_actions`` up to 512 (upstream's width is ``hidden``), ``num_mini_batch``,
+        ``sync_actions``, ``frames_u8`` and checkpoints; ``ValueError`` (``check_net``) with ``depth``, ``zeroshot``, ``goal_in``,
+        ``sensors``, ``goal_ids=False``, ``pooling=``, ``encoder="vit"``, ``frames_host``.
+
+        ``net="pooled"``: the Habitat DD-PPO net ([U] habitat-lab ``PointNavResNetNet``, restated, parity unpinned;
         ``PolicyHandle.pooled``) -- the frozen tower pooled to ONE vector per frame (``pooling="attnpool"``: CLIP's attention pool,
         D = 1024, ``encoder="rn50"``; ``"avgpool"``: ``ec_spatial_mean_bf16`` over the trunk output, D = its channels, also on the
         ImageNet towers), ``visual_fc``, the goal id (``goal_ids``) and / or the env's float ``sensors=(k_1, ...)``, the previous
@@ -642,11 +702,14 @@ class Worker(_SlicedActor):
         EMBEDDING (RN50 trunk + AttentionPool2d, 1024-d), the goal is the frozen CLIP text embedding of its prompt
         (text tower run once -> [12, 1024] table) and the policy is the fusion=1 variant (GRU + heads trainable)."""
         self.pooled_net, self.pooling, self.net_sensors = check_net(net, pooling, sensors, goal_ids, encoder, bool(depth), bool(zeroshot), goal_in)
-        self.goal_ids = bool(goal_ids)
+        self.two_view_net = net == "two_view"
+        self.goal_ids = bool(goal_ids) and not self.two_view_net
+        if self.two_view_net and frames_host:
+            raise ValueError("net='two_view': host-resident frames (frames_host=True) have no staging path for the goal view")
         if depth:
             check_rgbd(encoder, zeroshot, goal_in, frames_host)
         two_tower = bool(depth) and not self.pooled_net     # (the pooled RGB-D agent's policy handle is the RGB pooled net's: nothing to refuse)
-        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot))
+        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot), 512 if self.two_view_net else 64)
         self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
         self.rnn_type = check_rnn_type(rnn_type, two_tower, bool(zeroshot))
         self.rnn_layers = check_rnn_layers(rnn_layers, two_tower, bool(zeroshot))
@@ -733,6 +796,8 @@ class Worker(_SlicedActor):
             dkw.update(expert=True, num_actions=self._num_actions)
         if self.net_sensors:
             dkw.update(sensors=sum(self.net_sensors))
+        if self.two_view_net:
+            dkw.update(goal_view=True)
         self.env = env_cls(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in, **dkw)
         if self.nav_metrics:      # per-category rows for goal ids; coordinate goals have no categories
             self.episodes = NavEpisodeTracker(N, d, num_categories=0 if self.goal_in else self.env.num_goals)
@@ -879,7 +944,8 @@ class Worker(_SlicedActor):
                 for sl in self.slices:
                     wait(sl)                                                 # this slice's actions[t] are on the host
                     rgb = self.env.observe_at(k0 + t, self._actions_host)   # env.step of this slice's samplers
-                    dep = self.env.observe_depth_at(k0 + t) if self.depth else None
+                    dep = (self.env.observe_depth_at(k0 + t) if self.depth
+                           else (self.env.observe_goal_view_at(k0 + t) if self.two_view_net else None))
                     with self._on(sl):
                         self._encode_slice(sl, rgb, t + 1, dep)
                         if t + 1 < T:

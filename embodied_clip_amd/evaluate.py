@@ -66,7 +66,10 @@ class Evaluator(_SlicedActor):
                  goal_ids: bool = True):
         # net="pooled": the agent of Worker(net="pooled", ...) -- the same arguments, the same refusals; an env= must hold `sensors`
         self.pooled_net, self.pooling, self.net_sensors = check_net(net, pooling, sensors, goal_ids, encoder, bool(depth), bool(zeroshot), goal_in)
-        self.goal_ids = bool(goal_ids)
+        self.two_view_net = net == "two_view"     # the agent of Worker(net="two_view"): an env= must hold `goal_frames` on the device
+        self.goal_ids = bool(goal_ids) and not self.two_view_net
+        if self.two_view_net and env is not None and (getattr(env, "goal_frames", None) is None or getattr(env, "host", False)):
+            raise ValueError("net='two_view': the env serves no goal-state views on the device (SyntheticEnv(..., goal_view=True) holds env.goal_frames)")
         if self.net_sensors and env is not None and getattr(env, "sensors", None) is None:
             raise ValueError("net='pooled' with sensors: the env serves no sensor vectors (SyntheticEnv(..., sensors=K) holds env.sensors)")
         self.hidden_size = int(hidden)
@@ -77,7 +80,7 @@ class Evaluator(_SlicedActor):
             check_rgbd(encoder, zeroshot, goal_in, bool(env is not None and getattr(env, "host", False)))
             if env is not None and getattr(env, "depth", None) is None:
                 raise ValueError("depth=True: the env serves no depth frames (SyntheticEnv(..., depth=True) holds env.depth)")
-        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot))
+        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot), 512 if self.two_view_net else 64)
         self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
         self.depth = bool(depth)
         self.lib = _lib.load()
@@ -128,6 +131,8 @@ class Evaluator(_SlicedActor):
         dkw = dict(depth=True) if self.depth else {}
         if self.net_sensors:
             dkw.update(sensors=sum(self.net_sensors))
+        if self.two_view_net:
+            dkw.update(goal_view=True)
         self.env = env if env is not None else env_cls(N, T, d, seed=env_seed, frames_u8=frames_u8, goal_in=self.goal_in, **dkw)
         assert (self.env.N, self.env.T) == (N, T), "the env's actor count and rollout length are the evaluator's"
         if self.nav_metrics:
@@ -301,8 +306,9 @@ def main(argv=None) -> int:
                     help="with --prev-actions: no null row for an episode's first step (action a is row a)")
     ap.add_argument("--rnn-type", default="GRU", choices=("GRU", "LSTM"), help="the recurrent cell of the agent (and of its checkpoint)")
     ap.add_argument("--rnn-layers", type=int, default=1, choices=(1, 2, 3, 4), help="recurrent layers of the agent (and of its checkpoint)")
-    ap.add_argument("--net", default="goal_encoder", choices=("goal_encoder", "pooled"),
-                    help="pooled: the Habitat DD-PPO net over the pooled embedding (PolicyHandle.pooled)")
+    ap.add_argument("--net", default="goal_encoder", choices=("goal_encoder", "pooled", "two_view"),
+                    help="pooled: the Habitat DD-PPO net over the pooled embedding (PolicyHandle.pooled); two_view: the rearrangement agent over the "
+                         "current and the goal-state view (PolicyHandle.two_view)")
     ap.add_argument("--pooling", default="attnpool", choices=("attnpool", "avgpool"), help="with --net pooled: how the tower is pooled")
     ap.add_argument("--sensors", default="", metavar="K1,K2", help="with --net pooled: the widths of the env's float sensors, e.g. 2,2 (GPS, compass) or 3")
     ap.add_argument("--no-goal-ids", action="store_true", help="with --net pooled: no goal-id embedding (PointNav: --sensors 3)")

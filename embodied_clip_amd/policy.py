@@ -431,6 +431,151 @@ def _pooled(embed_in: int, hidden: int = 512, num_goals: int = 12, sensors=(), n
 PolicyHandle.pooled = staticmethod(_pooled)
 
 
+# ---- the two-view rearrangement net --------------------------------------------------------------
+# [U] ai2thor-rearrangement ``ResNetRearrangeActorCriticRNN`` (the 1-Phase Embodied CLIP ResNet50 IL agent of
+# readme_files/baselines_ithor_rearrangement.md) over TWO frozen CLIP maps per frame: the current view and the goal-state view.
+# Restated from the published sources, which are not under the reference tree: parity unpinned.  The ONE table of tensor names in
+# flat order; the three convs keep upstream's 4-D ``nn.Conv2d`` shapes, so an upstream state dict flattens unchanged.
+TWO_VIEW_PREV_ACTION_EMBEDDER = "prev_action_embedder.weight"     # nn.Embedding(A + 1, E); upstream E = hidden
+
+
+def two_view_param_shapes(in_channels: int = 2048, hidden: int = 512, num_actions: int = 84, attn_hidden: int = 32,
+                          prev_action_dims: int = 0, prev_action_null: int = 1, rnn_type: str = "LSTM", rnn_layers: int = 1,
+                          spatial: int = 7) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Tensor name -> shape in the flat order of ``ec_policy_create_two_view``.  ``weight_ih_l0``'s columns: ``v`` (hidden), then
+    the previous action's embedding."""
+    G = (4 if rnn_type == "LSTM" else 3) * hidden
+    out: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    out["visual_encoder.0.weight"] = (hidden, 3 * in_channels, 1, 1)
+    out["visual_encoder.0.bias"] = (hidden,)
+    out["visual_attention.0.weight"] = (attn_hidden, 3 * in_channels, 1, 1)
+    out["visual_attention.0.bias"] = (attn_hidden,)
+    out["visual_attention.2.weight"] = (1, attn_hidden, 1, 1)
+    out["visual_attention.2.bias"] = (1,)
+    out["state_encoder.rnn.weight_ih_l0"] = (G, hidden + prev_action_dims)
+    out["state_encoder.rnn.weight_hh_l0"] = (G, hidden)
+    out["state_encoder.rnn.bias_ih_l0"] = (G,)
+    out["state_encoder.rnn.bias_hh_l0"] = (G,)
+    out["actor.linear.weight"] = (num_actions, hidden)
+    out["actor.linear.bias"] = (num_actions,)
+    out["critic.fc.weight"] = (1, hidden)
+    out["critic.fc.bias"] = (1,)
+    if prev_action_dims:
+        out[TWO_VIEW_PREV_ACTION_EMBEDDER] = (num_actions + prev_action_null, prev_action_dims)
+    for l in range(1, rnn_layers):
+        out[f"state_encoder.rnn.weight_ih_l{l}"] = (G, hidden)
+        out[f"state_encoder.rnn.weight_hh_l{l}"] = (G, hidden)
+        out[f"state_encoder.rnn.bias_ih_l{l}"] = (G,)
+        out[f"state_encoder.rnn.bias_hh_l{l}"] = (G,)
+    return out
+
+
+class TwoViewPolicyHandle(PolicyHandle):
+    """``ec_policy_create_two_view``'s handle (``PolicyHandle.two_view``): ``forward`` / ``act`` / ``backward`` take the current
+    view's features as ``feat`` and the goal view's as ``feat2``, both bf16 ``[T*N, S2, C]``, and ``prev_actions=``; ``goal`` is
+    None.  ``flatten``, ``views``, ``recurrent_section`` are the base class's."""
+
+    def __init__(self, in_channels: int, hidden: int = 512, num_actions: int = 84, attn_hidden: int = 32, prev_action_dims: int = 0,
+                 prev_action_null: int = 1, rnn_type: str = "LSTM", rnn_layers: int = 1, spatial: int = 7):
+        self.lib = _lib.load()
+        if rnn_type not in _lib.RNN_TYPES:
+            raise ValueError(f"rnn_type must be one of {sorted(_lib.RNN_TYPES)}, got {rnn_type!r}")
+        if not (isinstance(rnn_layers, int) and 1 <= rnn_layers <= 4):
+            raise ValueError(f"rnn_layers must be 1..4, got {rnn_layers!r}")
+        if not prev_action_dims:
+            prev_action_null = 0
+        self.rnn_type, self.rnn_layers = rnn_type, rnn_layers
+        self.two_view_cfg = dict(in_channels=in_channels, hidden=hidden, num_actions=num_actions, attn_hidden=attn_hidden,
+                                 prev_action_dims=prev_action_dims, prev_action_null=prev_action_null, rnn_type=rnn_type,
+                                 rnn_layers=rnn_layers, spatial=spatial)
+        self.cfg = dict(hidden=hidden, num_goals=0, num_actions=num_actions, prev_action_dims=prev_action_dims,
+                        prev_action_null=prev_action_null, dual=0, fusion=0, goal_in=0, in_channels=in_channels, spatial=spatial)
+        self.goal_in = 0
+        self.prev_action_dims = prev_action_dims
+        c = _lib.TwoViewCfg(in_channels=in_channels, spatial=spatial, hidden=hidden, attn_hidden=attn_hidden, num_actions=num_actions,
+                            prev_action_dims=prev_action_dims, prev_action_null=prev_action_null, rnn_type=_lib.RNN_TYPES[rnn_type],
+                            num_layers=rnn_layers)
+        h = C.c_void_p()
+        _lib.check(self.lib.ec_policy_create_two_view(C.byref(h), C.byref(c)), "ec_policy_create_two_view")
+        self.h = h
+        self.flat_size = self.lib.ec_policy_flat_size(h)
+        self.state_width = self.lib.ec_policy_state_width(h)
+        self.shapes = two_view_param_shapes(**self.two_view_cfg)
+        self.param_order = tuple(self.shapes)
+        self.offsets = OrderedDict()
+        assert self.lib.ec_policy_num_param_tensors(h) == len(self.param_order)
+        for i, name in enumerate(self.param_order):
+            off, num = C.c_size_t(), C.c_size_t()
+            _lib.check(self.lib.ec_policy_param_offset(h, i, C.byref(off), C.byref(num)))
+            n = 1
+            for d in self.shapes[name]:
+                n *= d
+            assert n == num.value, (name, n, num.value)
+            self.offsets[name] = (off.value, num.value)
+
+    def set_goal_table(self, table):
+        raise ValueError("the two-view net has no goal table")
+
+    def memory_to_state(self, mem: torch.Tensor) -> torch.Tensor:
+        return memory_to_state(mem, self.rnn_type, self.rnn_layers)
+
+    def state_to_memory(self, state: torch.Tensor) -> torch.Tensor:
+        return state_to_memory(state, self.rnn_type, self.rnn_layers)
+
+    def _views_ptrs(self, feat, feat2, goal, prev_actions, rows: int):
+        n = rows * self.cfg["spatial"] ** 2 * self.cfg["in_channels"]
+        assert goal is None, "the two-view net has no goal input: pass goal=None"
+        for t in (feat, feat2):
+            assert t is not None and t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == n, \
+                "feat (current view) and feat2 (goal view): bf16 [rows, S2, C]"
+        return feat.data_ptr(), feat2.data_ptr(), self._prev_ptr(prev_actions, rows)
+
+    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None):
+        if hv is None:
+            hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)
+        if h_final is None:
+            h_final = torch.empty((N, self.state_width), dtype=torch.float32, device=dev)
+        up, wp, pp = self._views_ptrs(feat, feat2, goal, prev_actions, T * N)
+        _lib.check(self.lib.ec_policy_forward_two_view(
+            self.h, flat_params.data_ptr(), up, wp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), T, N, ws.data_ptr(),
+            ws.numel() * ws.element_size(), int(for_backward), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), _lib.stream_ptr()),
+            "ec_policy_forward_two_view")
+        return hv, h_final
+
+    def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
+            first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None,
+            expert_actions=None, expert_mask=None, force_p: float = 0.0):
+        """``ec_policy_act_two_view``: the T = 1 inference forward and the selection (sample, ``deterministic=True`` the first maximal
+        logit, optional teacher forcing) in one call, 2..256 actions."""
+        up, wp, pp = self._views_ptrs(feat, feat2, goal, prev_actions, N)
+        forcing = expert_actions is not None and force_p > 0.0
+        with _lib.tensor_guard(flat_params):
+            _lib.check(self.lib.ec_policy_act_two_view(
+                self.h, flat_params.data_ptr(), up, wp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), N, ws.data_ptr(),
+                ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
+                logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
+                expert_actions.data_ptr() if forcing else 0, expert_mask.data_ptr() if forcing else 0, force_p if forcing else 0.0,
+                _lib.stream_ptr()), "ec_policy_act_two_view")
+        return hv, h_final
+
+    act_ex = act
+
+    def _backward(self, flat_params, feat, masks, T, N, ws, dhv, dh_final, flat_grads, feat2=None, recurrent_ready=None):
+        for t in (feat, feat2):
+            assert t is not None and t.dtype == torch.bfloat16 and t.is_contiguous(), "feat and feat2: the two views' bf16 features"
+        return super()._backward(flat_params, feat, masks, T, N, ws, dhv, dh_final, flat_grads, feat2, recurrent_ready)
+
+
+def _two_view(in_channels: int, hidden: int = 512, num_actions: int = 84, attn_hidden: int = 32, prev_action_dims: int = 0,
+              prev_action_null: int = 1, rnn_type: str = "LSTM", rnn_layers: int = 1, spatial: int = 7) -> TwoViewPolicyHandle:
+    """``PolicyHandle.two_view(...)``: the handle of the two-view rearrangement net (``TwoViewPolicyHandle``)."""
+    return TwoViewPolicyHandle(in_channels, hidden, num_actions, attn_hidden, prev_action_dims, prev_action_null, rnn_type, rnn_layers,
+                               spatial)
+
+
+PolicyHandle.two_view = staticmethod(_two_view)
+
+
 def memory_to_state(mem: torch.Tensor, rnn_type: str = "GRU", rnn_layers: int = 1) -> torch.Tensor:
     """Upstream's recurrent memory -> the handle's state rows.  ``mem``: ``[L, N, H]`` (GRU) or ``[2L, N, H]`` (LSTM: all ``h``
     layers, then all ``c`` layers -- ``torch.cat([h, c], 0)``, [U] RNNStateEncoder).  Returns ``[N, L * SW]``, layer-major:

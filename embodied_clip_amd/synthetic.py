@@ -380,8 +380,10 @@ def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int =
                         num_goals: int = 12, num_actions: int = 6, compress_hid: int = 128,
                         compress_out: int = 32, comb_hid: int = 128, comb_out: int = 32, fusion: int = 0, dual: int = 0,
                         goal_in: int = 0, prev_action_dims: int = 0, prev_action_null: int = 0, rnn_type: str = "GRU",
-                        rnn_layers: int = 1, pooled=None):
-    """``pooled`` (a dict of ``policy.pooled_param_shapes``'s keywords, e.g. ``dict(embed_in=1024, sensors=(2, 2))``): the
+                        rnn_layers: int = 1, pooled=None, two_view=None):
+    """``two_view`` (a dict of ``policy.two_view_param_shapes``'s keywords, e.g. ``dict(in_channels=2048, hidden=512, num_actions=84)``):
+    the two-view rearrangement net's tensors instead (``PolicyHandle.two_view``), read like ``pooled``.
+    ``pooled`` (a dict of ``policy.pooled_param_shapes``'s keywords, e.g. ``dict(embed_in=1024, sensors=(2, 2))``): the
     pooled-embedding net's tensors instead (``PolicyHandle.pooled``); every other keyword but ``rnn_type`` / ``rnn_layers`` is ignored.
     ``rnn_layers = L > 1`` (single tower only): layer ``l >= 1`` adds ``weight_ih_l{l}`` / ``weight_hh_l{l}`` ``[G, hidden]`` and
     two ``[G]`` biases behind every other tensor.  ``rnn_type="LSTM"`` (single tower only): the same names in the same order, the four ``state_encoder.rnn.*`` tensors with
@@ -390,6 +392,9 @@ def policy_param_shapes(in_channels: int = 2048, spatial: int = 7, hidden: int =
     GRU input 2 * comb_out * spatial^2).  ``goal_in > 0`` (PointNav): 18 tensors, ``embed_goal.{weight,bias}`` in place
     of ``embed_class.weight``; ``num_goals`` is ignored.  ``prev_action_dims = E > 0``: ``weight_ih_l0`` is ``[3 * hidden,
     flat + E]`` and ``prev_action_embedder.fc.weight`` ``[num_actions + prev_action_null, E]`` is the last tensor."""
+    if two_view is not None:
+        from .policy import two_view_param_shapes    # (the table of names lives with the handle)
+        return two_view_param_shapes(**{"rnn_type": rnn_type, "rnn_layers": rnn_layers, **two_view})
     if pooled is not None:
         from .policy import pooled_param_shapes      # (the table of names lives with the handle)
         return pooled_param_shapes(**{"rnn_type": rnn_type, "rnn_layers": rnn_layers, **pooled})
@@ -478,14 +483,15 @@ def policy_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, torch.Tensor]":
     weights by the same rule, both recurrent biases zero ([U] RNNStateEncoder.init_weights: ``nn.init.constant_(param, 0)``).
     ``rnn_layers=L``: the upper layers' tensors by the rules of layer 0's."""
     shapes = policy_param_shapes(**kw)
-    lstm = kw.get("rnn_type", (kw.get("pooled") or {}).get("rnn_type", "GRU")) == "LSTM"
+    lstm = kw.get("rnn_type", (kw.get("pooled") or kw.get("two_view") or {}).get("rnn_type", "GRU")) == "LSTM"
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     for k, shp in shapes.items():
         if int(np.prod(shp)) == 0 or (lstm and k.startswith("state_encoder.rnn.bias_")):
             sd[k] = torch.zeros(shp)
         elif k.endswith("bias") or "bias_" in k:
             sd[k] = _normal(seed, k, shp, 0.02)
-        elif "embed_class" in k or k in (POLICY_PREV_ACTION_EMBEDDER, "obj_categories_embedding.weight", "prev_action_embedding.weight"):
+        elif "embed_class" in k or k in (POLICY_PREV_ACTION_EMBEDDER, "obj_categories_embedding.weight", "prev_action_embedding.weight",
+                                         "prev_action_embedder.weight"):
             sd[k] = _normal(seed, k, shp, 1.0)                            # nn.Embedding's N(0, 1)
         else:
             fan_in = int(np.prod(shp[1:]))

@@ -932,6 +932,80 @@ int ec_pooled_step0_fwd(int rnn_type, const float* x, long ld_x, const float* wi
                         float* h_out2, long ld_h2, int N, int H, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The two-view rearrangement net: the 1-Phase Embodied CLIP ResNet50 IL agent of
+ * readme_files/baselines_ithor_rearrangement.md.  [U] restated from the published ai2thor-rearrangement / allenact sources
+ * (ResNetRearrangeActorCriticRNN), which are not under the reference tree: parity unpinned.  Per frame, u and w are the frozen
+ * CLIP maps [S2, C] (NHWC rows, bf16) of the current view and of the goal-state view from the same pose, c_p = [u_p | w_p | u_p * w_p]:
+ *   e_p = ReLU(W_e c_p + b_e)                      visual_encoder.0      Conv2d(3C, H, 1)
+ *   m_p = ReLU(W_a c_p + b_a)                      visual_attention.0    Conv2d(3C, A1, 1), A1 = 32
+ *   l_p = <w_2, m_p> + b_2                         visual_attention.2    Conv2d(A1, 1, 1)
+ *   a   = softmax_p(l)                             over the S2 pixels of the frame
+ *   v   = (1/S2) sum_p a_p e_p                     a MEAN over the pixels, not a sum
+ *   x   = [ v | Emb_prev[(prev + 1) * mask] ]      then the recurrent core and the heads of the pooled-embedding net
+ * Unlike every other front this one is TRAINABLE (the towers stay frozen: no gradient reaches u or w).
+ * Flat parameter order: visual_encoder.0 weight [H, 3C], bias [H]; visual_attention.0 weight [A1, 3C], bias [A1];
+ * visual_attention.2 weight [1, A1], bias [1]; state_encoder.rnn.{weight_ih,weight_hh,bias_ih,bias_hh}_l0 with weight_ih_l0
+ * [G, H + E]; actor weight, bias; critic weight, bias; prev_action_embedder.weight [A + null, E] if E > 0; the upper layers' four
+ * tensors per layer.
+ * The plan is the pooled-embedding handle's from v onwards (dense copy of weight_ih_l0[:, :H], the previous-action table, step
+ * kernels, rnn_stack for upper layers, wide / narrow heads); v is not rectified after pooling, so the backward masks nothing on
+ * dv.  On THIS handle the previous-action width E may reach 512 (upstream's is H): above 64 the table PT = Emb W_ih[:, H:]^T and
+ * its chain to the two gradients run on ec_gemm_f32 (K in one piece) behind the same binned ordered sum over frames.
+ * No float atomics on any route: two learn passes give equal bits, an actor's result does not depend on how the actors are sliced.
+ * ec_policy_create_two_view: EC_ERR_ARG for a NULL argument, num_actions outside 2..256, prev_action_dims outside 0..512,
+ * prev_action_null not 0 | 1 or set without prev_action_dims, rnn_type / num_layers as in ec_policy_create_rnn_layers;
+ * EC_ERR_SHAPE for in_channels outside 64..4096 or % 64, spatial * spatial outside 1..64, attn_hidden outside 32..128 or % 32, and
+ * for a hidden ec_policy_create_rnn(EC_RNN_LSTM) refuses.
+ * The handle answers ec_policy_num_param_tensors / _flat_size / _param_offset / _workspace_bytes / _state_width / _rnn_type /
+ * _rnn_layers / _destroy, and ec_policy_backward3 (feat = u, feat2 = w, both bf16: feat_bf16 = 0 or a NULL feat2 is EC_ERR_ARG).
+ * Every other forward / act entry point returns EC_ERR_ARG on it, and the two below EC_ERR_ARG on every other handle.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+    int in_channels;     /* C: 64..4096, % 64 == 0 */
+    int spatial;         /* 7: S2 = spatial * spatial in 1..64 */
+    int hidden;          /* H: the widths ec_policy_create_rnn(EC_RNN_LSTM) admits */
+    int attn_hidden;     /* A1 = 32; 32..128, % 32 == 0 */
+    int num_actions;     /* 2..256 */
+    int prev_action_dims, prev_action_null;   /* E in 0..512; null as in ec_policy_cfg */
+    int rnn_type, num_layers;                 /* EC_RNN_GRU | EC_RNN_LSTM, 1..EC_RNN_MAX_LAYERS */
+} ec_two_view_cfg;
+int ec_policy_create_two_view(ec_policy_t** out, const ec_two_view_cfg* cfg);
+int ec_policy_is_two_view(const ec_policy_t* h);       /* 1 | 0 (0: NULL handle) */
+/* feat = u, feat2 = w: bf16 [T*N, S2, C], 16-byte aligned; prev_actions int64 [T*N] (prev_action_dims > 0) | NULL -- NULL must
+ * match a handle without the embedding, and the reverse, else EC_ERR_ARG.  The other arguments: ec_policy_forward2's.  A learn
+ * pass leaves the attention probabilities, the post-ReLU activations of both convs and the previous actions in the workspace
+ * for ec_policy_backward3.  T = 1 inference with h_final != h0 (EC_POOLED_ACT=0: the general route): the front's launch, then
+ * pooled_step0_kernel, one rnn_stack launch per upper layer and the heads, as on the pooled-embedding handle. */
+int ec_policy_forward_two_view(const ec_policy_t* h, const float* params, const void* feat, const void* feat2,
+                               const int64_t* prev_actions, const float* h0, const float* masks, int T, int N, void* workspace,
+                               size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream);
+/* The same at T = 1 in one call with the selection arguments of ec_policy_act_pooled: bit for bit
+ * ec_policy_forward_two_view followed by the stand-alone selection. */
+int ec_policy_act_two_view(const ec_policy_t* h, const float* params, const void* feat, const void* feat2,
+                           const int64_t* prev_actions, const float* h0, const float* masks, int N, void* workspace,
+                           size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
+                           int greedy, uint64_t seed, uint64_t step, int first_actor, const int64_t* expert_actions,
+                           const float* expert_mask, float force_p, ec_stream_t stream);
+/* The front's two kernels alone (tests, benchmarks; two_view.hip).  u, w bf16 [B, S2, C]; We [H, 3C], be [H], Wa [A1, 3C],
+ * ba [A1], w2 [A1], b2 [1]; v f32 [B, H].  Shapes: C % 64 == 0 in 64..4096, S2 in 1..64, H as above, A1 % 32 == 0 in 32..128,
+ * else EC_ERR_SHAPE; NULL or a misaligned (16 bytes) u, w, We, Wa, dWe, dWa, workspace -> EC_ERR_ARG; a short workspace ->
+ * EC_ERR_WORKSPACE.  ec_two_view_workspace_bytes: 0 for a refused shape.
+ * ec_two_view_fwd: K = 3C walked once on v_mfma_f32_32x32x16_bf16 against the combined [A1 + H, 3C] weight as three bf16 planes;
+ *   the product columns are formed while staging (exact: two bf16 planes), [u | w | u * w] never exists in memory.  A workgroup
+ *   owns whole frames (3 frames of 49 pixels in 160 rows: 91.9 % useful rows; 1 in 64 for launches of few frames); a frame's v
+ *   has the same bits however the frames are sliced.  save != 0 (workspace sized with for_backward = 1): keeps the probabilities
+ *   and both convs' post-ReLU activations for ec_two_view_bwd.
+ * ec_two_view_bwd: ADDS the six gradients of sum(v * dv) onto dWe, dbe, dWa, dba, dw2, db2, from the workspace the saving
+ *   forward of the same shapes left.  Ordered sums only: two calls give equal bits. */
+size_t ec_two_view_workspace_bytes(long B, int S2, int C, int H, int A1, int for_backward);
+int ec_two_view_fwd(const void* u, const void* w, const float* We, const float* be, const float* Wa, const float* ba,
+                    const float* w2, const float* b2, float* v, long B, int S2, int C, int H, int A1, void* workspace,
+                    size_t ws_bytes, int save, ec_stream_t stream);
+int ec_two_view_bwd(const void* u, const void* w, const float* w2, const float* dv, float* dWe, float* dbe, float* dWa,
+                    float* dba, float* dw2, float* db2, long B, int S2, int C, int H, int A1, void* workspace, size_t ws_bytes,
+                    ec_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * CLIP VisionTransformer embedder == [U] allenact ClipViTEmbedder.forward over
  * [U] openai/CLIP VisionTransformer: patch-embed, class +
  * positional embedding, ln_pre, then `layers_run` ResidualAttentionBlocks
