@@ -260,6 +260,8 @@ _PATCH_TARGETS = (
     # the ImageNet baselines (objectnav_robothor_rgb_resnet{18,50}gru_ddppo: readme_files/imagenet_vs_objectnav.md,
     # baselines_robothor_objectnav.md:47)
     ("allenact.embodiedai.preprocessors.resnet", ("ResNetPreprocessor",)),
+    # the 1-Phase rearrangement model (readme_files/baselines_ithor_rearrangement.md): [U] ai2thor-rearrangement rearrange/baseline_models.py
+    ("rearrange.baseline_models", ("ResNetRearrangeActorCriticRNN",)),
 )
 
 
@@ -276,7 +278,8 @@ def install_into_allenact(verbose: bool = False) -> List[str]:
     ours = {"ClipResNetPreprocessor": cp.ClipResNetPreprocessor, "ClipViTPreprocessor": cp.ClipViTPreprocessor,
             "ResnetTensorObjectNavActorCritic": pol.ResnetTensorObjectNavActorCritic,
             "ResnetTensorPointNavActorCritic": pol.ResnetTensorPointNavActorCritic, "PPO": ppo.PPO,
-            "ResNetPreprocessor": ip.ResNetPreprocessor, "Imitation": il.Imitation}
+            "ResNetPreprocessor": ip.ResNetPreprocessor, "Imitation": il.Imitation,
+            "ResNetRearrangeActorCriticRNN": pol.ResNetRearrangeActorCriticRNN}
     done = []
     for modname, attrs in _PATCH_TARGETS:
         try:
@@ -284,7 +287,7 @@ def install_into_allenact(verbose: bool = False) -> List[str]:
         except Exception:  # noqa: BLE001 - optional module
             continue
         for a in attrs:
-            if hasattr(mod, a) or modname.endswith(("clip_preprocessors", "object_nav_models", "point_nav_models")):
+            if hasattr(mod, a) or modname.endswith(("clip_preprocessors", "object_nav_models", "point_nav_models", "baseline_models")):
                 setattr(mod, a, ours[a])
                 done.append(f"{modname}.{a}")
     if verbose:

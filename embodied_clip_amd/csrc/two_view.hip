@@ -586,3 +586,81 @@ extern "C" int ec_two_view_bwd(const void* u, const void* w, const float* w2, co
     EC_CHECK_LAUNCH();
     return EC_OK;
 }
+
+// ---- the plugin class's bridge: both views' fp32 NCHW maps -> bf16 pixel-major rows -------------------------------------------------
+// AllenAct hands ResNetRearrangeActorCriticRNN two fp32 [B, C, HW] tensors per call; the kernels above read bf16 [B, HW, C].  This is
+// nchw_to_nhwc_bf16_kernel (stem_elementwise.hip: one workgroup per frame and 64-channel slab, a [HW][65] float tile, 4-byte loads,
+// 2-byte stores, atomicOr on the flag) for TWO tensors in ONE launch (blockIdx.y = the view), run on every act step: the values
+// are rounded to nearest even, and *changed is SET (never cleared: the caller reads it when it can afford to) when one of them
+// was not a bf16 value already.  Both sides move 16 bytes per lane:
+//   in   the slab's [64][HW] floats are one contiguous 16-byte aligned run: float4 loads, lane after lane;
+//   LDS  float tile [64][P], P = HW | 1.  Odd HW (7 x 7, 3 x 3, 1 x 1 maps): P == HW, the tile IS the run, and a float4 goes in as
+//        one 16-byte store.  Even HW: one pad column and four ds_write_b32 per lane (addresses 4 words apart across lanes: 4-way
+//        on the 32 store banks, which costs a store 2 x -- the price of the odd pitch the reads need, paid by the even maps only);
+//   out  lane l -> (pixel hw, 8-channel piece j) with j = (l & 3) + 4 * (l >> 5) and hw = 8 * group + ((l >> 2) & 7): its eight
+//        ds_read_b32 hit word (8 j + k) P + hw.  Within a 32-lane half j takes four values, 8 j P mod 32 is {0, 8, 16, 24} in
+//        some order because P is odd, and hw eight consecutive ones: 32 distinct banks for every k.  The wave then stores eight
+//        pixels' 128-byte runs of the row-major output, each as 8 x 16 bytes.
+// The flag is a plain store of the constant 1 by lane 0 of a wave that saw such a value: every writer stores the same word.
+namespace {
+
+constexpr int PR_TC = 64;     // channels per slab
+
+__global__ __launch_bounds__(256) void nchw_pair_to_nhwc_bf16_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                    uint16_t* __restrict__ out_a, uint16_t* __restrict__ out_b,
+                                                                    int HW, int C, int P, int* changed) {
+    extern __shared__ __attribute__((aligned(16))) float ptile[];   // [PR_TC][P]
+    const int slabs = C / PR_TC;
+    const long frame = blockIdx.x / slabs;
+    const int c0 = (int)(blockIdx.x % slabs) * PR_TC;
+    const float* src = (blockIdx.y ? b : a) + (frame * C + c0) * HW;
+    uint16_t* dst = (blockIdx.y ? out_b : out_a) + frame * HW * C + c0;
+    const float4* src4 = reinterpret_cast<const float4*>(src);
+    const int n4 = (PR_TC / 4) * HW;
+    int bad = 0;
+    auto off_grid = [](float v) -> int { return ((__float_as_uint(v) & 0xffffu) != 0u) && (v == v); };   // (NaNs are left to the consumer)
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        const float4 v = src4[i];
+        bad |= off_grid(v.x) | off_grid(v.y) | off_grid(v.z) | off_grid(v.w);
+        if (P == HW) {
+            reinterpret_cast<float4*>(ptile)[i] = v;
+        } else {
+            const float x[4] = {v.x, v.y, v.z, v.w};
+            int c = (4 * i) / HW, hw = 4 * i - c * HW;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                ptile[c * P + hw] = x[k];
+                if (++hw == HW) { hw = 0; ++c; }
+            }
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, j = (lane & 3) + 4 * (lane >> 5);
+    for (int hw = 8 * (threadIdx.x >> 6) + ((lane >> 2) & 7); hw < HW; hw += 32) {
+        const float* t = ptile + 8 * j * P + hw;
+        uint4 o;
+        o.x = ec_pack2(t[0], t[P]);
+        o.y = ec_pack2(t[2 * P], t[3 * P]);
+        o.z = ec_pack2(t[4 * P], t[5 * P]);
+        o.w = ec_pack2(t[6 * P], t[7 * P]);
+        *reinterpret_cast<uint4*>(dst + (long)hw * C + 8 * j) = o;
+    }
+    if (__builtin_amdgcn_ballot_w64(bad != 0) != 0 && lane == 0) *changed = 1;
+}
+
+}  // namespace
+
+extern "C" int ec_nchw_f32_pair_to_nhwc_bf16(const float* a, const float* b, void* out_a, void* out_b, long B, int HW, int C,
+                                             int* changed, ec_stream_t stream) {
+    if (!a || !b || !out_a || !out_b || !changed) return EC_ERR_ARG;
+    if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out_a | (uintptr_t)out_b | (uintptr_t)changed) & 15) != 0) return EC_ERR_ARG;
+    if (B <= 0 || HW < 1 || HW > 64 || C <= 0 || C % PR_TC != 0) return EC_ERR_SHAPE;
+    if (B > 0x7fffffffL) return EC_ERR_SHAPE;
+    const long blocks = B * (long)(C / PR_TC);
+    if (blocks > 0x7fffffffL) return EC_ERR_SHAPE;      // (one workgroup per frame and slab in grid.x)
+    const int P = HW | 1;
+    hipLaunchKernelGGL(nchw_pair_to_nhwc_bf16_kernel, dim3((unsigned)blocks, 2), dim3(256), (size_t)PR_TC * P * sizeof(float),
+                       (hipStream_t)stream, a, b, (uint16_t*)out_a, (uint16_t*)out_b, HW, C, P, changed);
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}

@@ -653,67 +653,16 @@ def _set_nested(root: nn.Module, dotted: str, p: nn.Parameter):
     m.register_parameter(parts[-1], p)
 
 
-class _ResnetTensorGoalActorCritic(ActorCriticModel):
-    """What the ObjectNav and the PointNav model share: everything but the goal's type.  ``_coordinate_goal`` False: the goal
-    observation is an integer id per frame (``embed_class``); True: a float vector per frame (``embed_goal``), its width
-    read off the goal sensor's observation space."""
-    _coordinate_goal = False
+class _FlatBucketActorCritic(ActorCriticModel):
+    """What every drop-in model class shares: the parameters are views of ONE flat buffer (``self._flat``) in the order of
+    ``self.handle``, their ``.grad``s views of one flat gradient bucket (``self._flat_grad``), and ``_PolicyFn`` may borrow
+    ``self._g_scratch``.  A subclass sets ``handle``, calls ``_adopt(state_dict, device)`` once, and ``ensure_flat()`` at the
+    top of ``forward``."""
 
-    def __init__(self, action_space, observation_space, goal_sensor_uuid: str,
-                 rgb_resnet_preprocessor_uuid: Optional[str] = None, depth_resnet_preprocessor_uuid: Optional[str] = None,
-                 hidden_size: int = 512, goal_dims: int = 32, resnet_compressor_hidden_out_dims=(128, 32),
-                 combiner_hidden_out_dims=(128, 32), state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 device="cuda", add_prev_actions: bool = False, action_embed_size: int = 6,
-                 add_prev_action_null_token: bool = False, rnn_type: str = "GRU", num_rnn_layers: int = 1):
-        super().__init__(action_space=action_space, observation_space=observation_space)
-        # [U] RNNStateEncoder(input, hidden, num_layers=num_rnn_layers, rnn_type=rnn_type)
-        if num_rnn_layers != 1:
-            raise NotImplementedError("more than one recurrent layer is not built")
-        if rnn_type not in ("GRU", "LSTM"):
-            raise ValueError(f"rnn_type must be 'GRU' or 'LSTM', got {rnn_type!r}")
-        if rnn_type == "LSTM" and depth_resnet_preprocessor_uuid is not None:
-            raise NotImplementedError("an LSTM core with a depth tower is not built (the two-tower agent keeps the GRU)")
-        self.rnn_type = rnn_type
-        if rgb_resnet_preprocessor_uuid is None and depth_resnet_preprocessor_uuid is None:
-            raise ValueError("one of rgb_resnet_preprocessor_uuid / depth_resnet_preprocessor_uuid is required")
-        self.goal_uuid = goal_sensor_uuid
-        self.dual = rgb_resnet_preprocessor_uuid is not None and depth_resnet_preprocessor_uuid is not None
-        self.resnet_uuid = (rgb_resnet_preprocessor_uuid if rgb_resnet_preprocessor_uuid is not None
-                            else depth_resnet_preprocessor_uuid)
-        self.depth_uuid = depth_resnet_preprocessor_uuid if self.dual else None
-        self._hidden_size = hidden_size
+    def _adopt(self, state_dict: Dict[str, torch.Tensor], device) -> None:
+        """Flatten ``state_dict`` on ``device`` and register every tensor of the handle's table as a Parameter view."""
         self._g_scratch: Optional[torch.Tensor] = None
-        if self.resnet_uuid not in observation_space.spaces:
-            raise NotImplementedError("blind agent (no visual tensor in the observation space) is not built")
-        if self.dual and self.depth_uuid not in observation_space.spaces:
-            raise ValueError(f"{self.depth_uuid!r} is not in the observation space")
-        rs = observation_space.spaces[self.resnet_uuid].shape        # (C, S, S)
-        if self.dual and tuple(observation_space.spaces[self.depth_uuid].shape) != tuple(rs):
-            raise ValueError("the RGB and depth feature tensors must have the same shape")
-        if self._coordinate_goal:
-            if self.dual:
-                raise NotImplementedError("the RGB-D PointNav encoder is not built")
-            goal_kw = dict(goal_in=int(observation_space.spaces[self.goal_uuid].shape[-1]))
-        else:
-            goal_kw = dict(num_goals=getattr(observation_space.spaces[self.goal_uuid], "n", 12))
-        # [U] VisualNavActorCritic(add_prev_actions, action_embed_size, add_prev_action_null_token): prev_action_embedder.fc.weight
-        # [action_space.n (+ 1), action_embed_size], concatenated to the GRU input (restated from the published source, parity unpinned)
-        self.add_prev_actions = bool(add_prev_actions)
-        if self.add_prev_actions:
-            if self.dual:
-                raise NotImplementedError("previous actions with the RGB-D encoder are not built")
-            goal_kw.update(prev_action_dims=int(action_embed_size), prev_action_null=int(bool(add_prev_action_null_token)))
-        self.handle = PolicyHandle(in_channels=rs[0], spatial=rs[1], hidden=hidden_size, goal_dims=goal_dims,
-                                   num_actions=action_space.n,
-                                   compress_hid=resnet_compressor_hidden_out_dims[0],
-                                   compress_out=resnet_compressor_hidden_out_dims[1],
-                                   comb_hid=combiner_hidden_out_dims[0], comb_out=combiner_hidden_out_dims[1],
-                                   dual=int(self.dual), rnn_type=rnn_type, **goal_kw)
-        dev = torch.device(device)
-        if state_dict is None:
-            from .synthetic import policy_state_dict
-            state_dict = policy_state_dict(0, **self.handle.cfg, rnn_type=rnn_type)
-        self._flat = self.handle.flatten(state_dict, dev)
+        self._flat = self.handle.flatten(state_dict, torch.device(device))
         self._flat_grad = torch.zeros_like(self._flat)
         for name, v in self.handle.views(self._flat).items():
             _set_nested(self, name, nn.Parameter(v))
@@ -774,6 +723,69 @@ class _ResnetTensorGoalActorCritic(ActorCriticModel):
     def flat_grads(self) -> torch.Tensor:
         self.ensure_flat()
         return self._flat_grad
+
+
+class _ResnetTensorGoalActorCritic(_FlatBucketActorCritic):
+    """What the ObjectNav and the PointNav model share: everything but the goal's type.  ``_coordinate_goal`` False: the goal
+    observation is an integer id per frame (``embed_class``); True: a float vector per frame (``embed_goal``), its width
+    read off the goal sensor's observation space."""
+    _coordinate_goal = False
+
+    def __init__(self, action_space, observation_space, goal_sensor_uuid: str,
+                 rgb_resnet_preprocessor_uuid: Optional[str] = None, depth_resnet_preprocessor_uuid: Optional[str] = None,
+                 hidden_size: int = 512, goal_dims: int = 32, resnet_compressor_hidden_out_dims=(128, 32),
+                 combiner_hidden_out_dims=(128, 32), state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                 device="cuda", add_prev_actions: bool = False, action_embed_size: int = 6,
+                 add_prev_action_null_token: bool = False, rnn_type: str = "GRU", num_rnn_layers: int = 1):
+        super().__init__(action_space=action_space, observation_space=observation_space)
+        # [U] RNNStateEncoder(input, hidden, num_layers=num_rnn_layers, rnn_type=rnn_type)
+        if num_rnn_layers != 1:
+            raise NotImplementedError("more than one recurrent layer is not built")
+        if rnn_type not in ("GRU", "LSTM"):
+            raise ValueError(f"rnn_type must be 'GRU' or 'LSTM', got {rnn_type!r}")
+        if rnn_type == "LSTM" and depth_resnet_preprocessor_uuid is not None:
+            raise NotImplementedError("an LSTM core with a depth tower is not built (the two-tower agent keeps the GRU)")
+        self.rnn_type = rnn_type
+        if rgb_resnet_preprocessor_uuid is None and depth_resnet_preprocessor_uuid is None:
+            raise ValueError("one of rgb_resnet_preprocessor_uuid / depth_resnet_preprocessor_uuid is required")
+        self.goal_uuid = goal_sensor_uuid
+        self.dual = rgb_resnet_preprocessor_uuid is not None and depth_resnet_preprocessor_uuid is not None
+        self.resnet_uuid = (rgb_resnet_preprocessor_uuid if rgb_resnet_preprocessor_uuid is not None
+                            else depth_resnet_preprocessor_uuid)
+        self.depth_uuid = depth_resnet_preprocessor_uuid if self.dual else None
+        self._hidden_size = hidden_size
+        self._g_scratch: Optional[torch.Tensor] = None
+        if self.resnet_uuid not in observation_space.spaces:
+            raise NotImplementedError("blind agent (no visual tensor in the observation space) is not built")
+        if self.dual and self.depth_uuid not in observation_space.spaces:
+            raise ValueError(f"{self.depth_uuid!r} is not in the observation space")
+        rs = observation_space.spaces[self.resnet_uuid].shape        # (C, S, S)
+        if self.dual and tuple(observation_space.spaces[self.depth_uuid].shape) != tuple(rs):
+            raise ValueError("the RGB and depth feature tensors must have the same shape")
+        if self._coordinate_goal:
+            if self.dual:
+                raise NotImplementedError("the RGB-D PointNav encoder is not built")
+            goal_kw = dict(goal_in=int(observation_space.spaces[self.goal_uuid].shape[-1]))
+        else:
+            goal_kw = dict(num_goals=getattr(observation_space.spaces[self.goal_uuid], "n", 12))
+        # [U] VisualNavActorCritic(add_prev_actions, action_embed_size, add_prev_action_null_token): prev_action_embedder.fc.weight
+        # [action_space.n (+ 1), action_embed_size], concatenated to the GRU input (restated from the published source, parity unpinned)
+        self.add_prev_actions = bool(add_prev_actions)
+        if self.add_prev_actions:
+            if self.dual:
+                raise NotImplementedError("previous actions with the RGB-D encoder are not built")
+            goal_kw.update(prev_action_dims=int(action_embed_size), prev_action_null=int(bool(add_prev_action_null_token)))
+        self.handle = PolicyHandle(in_channels=rs[0], spatial=rs[1], hidden=hidden_size, goal_dims=goal_dims,
+                                   num_actions=action_space.n,
+                                   compress_hid=resnet_compressor_hidden_out_dims[0],
+                                   compress_out=resnet_compressor_hidden_out_dims[1],
+                                   comb_hid=combiner_hidden_out_dims[0], comb_out=combiner_hidden_out_dims[1],
+                                   dual=int(self.dual), rnn_type=rnn_type, **goal_kw)
+        dev = torch.device(device)
+        if state_dict is None:
+            from .synthetic import policy_state_dict
+            state_dict = policy_state_dict(0, **self.handle.cfg, rnn_type=rnn_type)
+        self._adopt(state_dict, dev)
 
     # -- learn-pass feature rows ------------------------------------------------------------------
     def _bf16_rows(self, feat: torch.Tensor, T: int, N: int, slot: int = 0):
@@ -928,3 +940,181 @@ class ResnetTensorPointNavActorCritic(_ResnetTensorGoalActorCritic):
     ``goal_visual_encoder.embed_goal.{weight,bias}`` first; single-tower only.
     """
     _coordinate_goal = True
+
+
+class ResNetRearrangeActorCriticRNN(_FlatBucketActorCritic):
+    """[U] ai2thor-rearrangement ``rearrange/baseline_models.py`` ``ResNetRearrangeActorCriticRNN(action_space, observation_space,
+    rgb_uuid, unshuffled_rgb_uuid, hidden_size=512, num_rnn_layers=1, rnn_type="GRU")`` -- the model of the 1-Phase Embodied CLIP
+    ResNet50 IL experiment (readme_files/baselines_ithor_rearrangement.md) and of its ImageNet twin, over ``PolicyHandle.two_view``.
+    Restated from the published source, which is not under the reference tree: parity unpinned.
+
+    Behind upstream's keywords: ``prev_action_embedding_dim`` (0: ``prev_actions`` is not read; upstream's embedder is
+    ``hidden_size`` wide) with ``add_prev_action_null_token``; ``attn_hidden`` (upstream's 32); ``state_dict`` / ``device``;
+    ``feature_rounding``.  ``in_channels`` and ``spatial`` are read off ``observation_space.spaces[rgb_uuid].shape``.
+
+    Parameters carry upstream's names (``two_view_param_shapes``): ``state_dict()`` / ``load_state_dict()`` exchange checkpoints
+    with upstream's model and with the ``model_state_dict`` of ``Worker(net="two_view").save_checkpoint``.
+
+    Features.  ``observations[rgb_uuid]`` and ``observations[unshuffled_rgb_uuid]``: fp32 ``[T, N, C, s, s]`` (AllenAct's
+    contract), or channels-last ``[T, N, s, s, C]`` bf16 (passed through untouched) or fp32 (cast), as ``process_bf16_nhwc``
+    returns them.  The handle reads bf16 rows: fp32 NCHW tensors of both views go through ``ec_nchw_f32_pair_to_nhwc_bf16`` in
+    ONE launch, which rounds to nearest even.  In the learn pass (``T > 1``, grad enabled) both views' rows are kept per storage
+    version, so the epochs of one rollout convert once; act steps convert on every call.
+
+    ``feature_rounding``: this project's preprocessors widen bf16 features to fp32, so rounding them changes nothing.  Features of
+    a foreign fp32 preprocessor are not bf16 values, and the kernel raises a sticky device flag for them.
+      * ``"error"`` (default): the flag is read once per learn-pass conversion and by ``check_features()``; a set flag raises
+        ``ValueError``.  Act steps never read it (no host stall per env step): between two checks they RUN ON ROUNDED VALUES,
+        and the next check reports it.
+      * ``"nearest"``: the flag is never read; the documented deviation from upstream is round-to-nearest-even of the features.
+    """
+
+    def __init__(self, action_space, observation_space, rgb_uuid: str, unshuffled_rgb_uuid: str, hidden_size: int = 512,
+                 num_rnn_layers: int = 1, rnn_type: str = "GRU", prev_action_embedding_dim: int = 0,
+                 add_prev_action_null_token: bool = True, attn_hidden: int = 32,
+                 state_dict: Optional[Dict[str, torch.Tensor]] = None, device="cuda", feature_rounding: str = "error"):
+        super().__init__(action_space=action_space, observation_space=observation_space)
+        if rnn_type not in ("GRU", "LSTM"):
+            raise ValueError(f"rnn_type must be 'GRU' or 'LSTM', got {rnn_type!r}")
+        if not (isinstance(num_rnn_layers, int) and 1 <= num_rnn_layers <= 4):
+            raise ValueError(f"num_rnn_layers must be 1..4, got {num_rnn_layers!r}")
+        if feature_rounding not in ("error", "nearest"):
+            raise ValueError(f"feature_rounding must be 'error' or 'nearest', got {feature_rounding!r}")
+        for uuid in (rgb_uuid, unshuffled_rgb_uuid):
+            if uuid not in observation_space.spaces:
+                raise ValueError(f"{uuid!r} is not in the observation space")
+        rs = tuple(observation_space.spaces[rgb_uuid].shape)                     # (C, s, s)
+        if tuple(observation_space.spaces[unshuffled_rgb_uuid].shape) != rs:
+            raise ValueError(f"{rgb_uuid!r} and {unshuffled_rgb_uuid!r} must have the same shape, got {rs} and "
+                             f"{tuple(observation_space.spaces[unshuffled_rgb_uuid].shape)}")
+        if len(rs) != 3 or rs[1] != rs[2]:
+            raise ValueError(f"the feature maps are (C, s, s), got {rs}")
+        self.rgb_uuid, self.unshuffled_rgb_uuid = rgb_uuid, unshuffled_rgb_uuid
+        self.rnn_type, self.num_rnn_layers = rnn_type, num_rnn_layers
+        self.feature_rounding = feature_rounding
+        self._hidden_size = hidden_size
+        self.prev_action_embedding_dim = int(prev_action_embedding_dim)
+        self.handle = PolicyHandle.two_view(in_channels=int(rs[0]), hidden=hidden_size, num_actions=action_space.n,
+                                            attn_hidden=attn_hidden, prev_action_dims=self.prev_action_embedding_dim,
+                                            prev_action_null=int(bool(add_prev_action_null_token)), rnn_type=rnn_type,
+                                            rnn_layers=num_rnn_layers, spatial=int(rs[1]))
+        if state_dict is None:
+            from .synthetic import policy_state_dict
+            state_dict = policy_state_dict(0, two_view=self.handle.two_view_cfg)
+        self._changed: Optional[torch.Tensor] = None       # the conversion kernel's sticky flag (device int32), made on first use
+        self._rows_cache: Optional[tuple] = None           # (weakref(base u), weakref(base w), key, rows u, rows w)
+        self._adopt(state_dict, device)
+
+    # -- feature rows --------------------------------------------------------------------------------
+    def _flag(self, device) -> torch.Tensor:
+        if self._changed is None or self._changed.device != device:
+            self._changed = torch.zeros(4, dtype=torch.int32, device=device)       # (16 bytes: word 0 is the flag)
+        return self._changed
+
+    def check_features(self) -> None:
+        """``feature_rounding="error"``: read the conversion kernel's flag (one host sync), clear it, and raise ``ValueError`` if a
+        feature since the last check was not a bf16 value.  Call it wherever a stall is affordable, e.g. once per rollout."""
+        if self.feature_rounding != "error" or self._changed is None:
+            return
+        if int(self._changed[0].item()) != 0:
+            self._changed.zero_()
+            raise ValueError(
+                f"observations {self.rgb_uuid!r} / {self.unshuffled_rgb_uuid!r} hold fp32 values that are not bf16 values: the "
+                "two-view kernels read bf16 features and have been given the values rounded to nearest even.  Use this project's "
+                "ClipResNetPreprocessor / ResNetPreprocessor (their fp32 output is widened bf16), or construct the model with "
+                "feature_rounding='nearest' to accept the rounding.")
+
+    def _pair_rows(self, u: torch.Tensor, w: torch.Tensor, rows: int):
+        """fp32 NCHW ``[T, N, C, s, s]`` x 2 -> bf16 rows ``[rows, S2, C]`` x 2 in one launch; never reads the flag."""
+        c = self.handle.cfg
+        S2, Cin = c["spatial"] ** 2, c["in_channels"]
+        u, w = u.contiguous(), w.contiguous()
+        out = torch.empty((2, rows, S2, Cin), dtype=torch.bfloat16, device=u.device)
+        with _lib.tensor_guard(u):
+            _lib.check(self.handle.lib.ec_nchw_f32_pair_to_nhwc_bf16(u.data_ptr(), w.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                                                     rows, S2, Cin, self._flag(u.device).data_ptr(), _lib.stream_ptr()),
+                       "ec_nchw_f32_pair_to_nhwc_bf16")
+        return out[0], out[1]
+
+    @staticmethod
+    def _storage_key(t: torch.Tensor):
+        base = t._base if t._base is not None else t
+        try:                                             # (inference-mode tensors have no version counter)
+            version = base._version
+        except RuntimeError:
+            return base, None
+        return base, (t.data_ptr(), tuple(t.shape), tuple(t.stride()), version)
+
+    def _rows(self, u: torch.Tensor, w: torch.Tensor, T: int, N: int):
+        c = self.handle.cfg
+        s, Cin = c["spatial"], c["in_channels"]
+        nchw, nhwc = (T, N, Cin, s, s), (T, N, s, s, Cin)
+        for uuid, t in ((self.rgb_uuid, u), (self.unshuffled_rgb_uuid, w)):
+            if tuple(t.shape) not in (nchw, nhwc) or t.dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError(f"observation {uuid!r}: fp32 {list(nchw)}, or bf16 / fp32 channels-last {list(nhwc)}; got "
+                                 f"{t.dtype} {list(t.shape)}")
+        # (C == s makes the two shapes one: an fp32 tensor is then AllenAct's NCHW, a bf16 one the preprocessor's channels-last)
+        last = [tuple(t.shape) == nhwc and not (nchw == nhwc and t.dtype == torch.float32) for t in (u, w)]
+        if all(last):        # channels-last: bf16 as it is, fp32 cast
+            return tuple(t.reshape(T * N, s * s, Cin).to(torch.bfloat16).contiguous() for t in (u, w))
+        if any(last) or u.dtype != torch.float32 or w.dtype != torch.float32 or u.device != w.device:
+            raise ValueError(f"observations {self.rgb_uuid!r} and {self.unshuffled_rgb_uuid!r} must come in the same form on one "
+                             f"device, fp32 {list(nchw)} or channels-last {list(nhwc)} (bf16 only channels-last)")
+        if not (T > 1 and torch.is_grad_enabled()):
+            return self._pair_rows(u, w, T * N)          # act step: every call, no flag read
+        # learn pass: the rows of both views are kept while the SAME storages (base tensor, view geometry, version counter) come
+        # back -- the update epochs of one rollout.  As on _bf16_rows, the key relies on the version counter: the storage must be
+        # filled through torch ops (or RN50Trunk.to_nchw_f32(out=...), which bumps the counter itself)
+        import weakref
+        (bu, ku), (bw, kw) = self._storage_key(u), self._storage_key(w)
+        hit = self._rows_cache
+        if (hit is not None and ku is not None and kw is not None and hit[0]() is bu and hit[1]() is bw and hit[2] == (ku, kw)):
+            return hit[3], hit[4]
+        self._rows_cache = None
+        ru, rw = self._pair_rows(u, w, T * N)
+        self.check_features()                            # (one host sync per rollout storage version; "nearest": none)
+        if ku is not None and kw is not None:
+            self._rows_cache = (weakref.ref(bu), weakref.ref(bw), (ku, kw), ru, rw)
+        return ru, rw
+
+    # -- ActorCriticModel surface ----------------------------------------------------------------
+    @property
+    def recurrent_hidden_state_size(self) -> int:
+        return self._hidden_size
+
+    @property
+    def num_recurrent_layers(self) -> int:
+        """[U] RNNStateEncoder.num_recurrent_layers: ``num_layers * (2 if "LSTM" in rnn_type else 1)``."""
+        return self.num_rnn_layers * (2 if self.rnn_type == "LSTM" else 1)
+
+    def _recurrent_memory_specification(self):
+        return dict(rnn=((("layer", self.num_recurrent_layers), ("sampler", None),
+                          ("hidden", self.recurrent_hidden_state_size)), torch.float32))
+
+    def forward(self, observations: Dict[str, torch.Tensor], memory: Memory, prev_actions: torch.Tensor,
+                masks: torch.Tensor):
+        """observations[rgb_uuid], observations[unshuffled_rgb_uuid]: see the class docstring; memory 'rnn': ``[L, N, H]`` (GRU) or
+        ``[2L, N, H]`` (LSTM: every layer's h, then every layer's c); masks: ``[T, N, 1]``; prev_actions: ``[T, N]`` or
+        ``[T, N, 1]`` integer, read only with ``prev_action_embedding_dim > 0``.  -> (ActorCriticOutput, Memory)."""
+        self.ensure_flat()
+        T, N = masks.shape[:2]
+        h = self.handle
+        rows_u, rows_w = self._rows(observations[self.rgb_uuid], observations[self.unshuffled_rgb_uuid], T, N)
+        k = self.num_recurrent_layers
+        h0 = h.memory_to_state(memory.tensor("rnn").reshape(k, N, self._hidden_size).to(torch.float32))
+        m = masks.reshape(T * N).to(torch.float32).contiguous()
+        prev = None
+        if self.prev_action_embedding_dim:
+            assert prev_actions is not None and prev_actions.numel() == T * N, \
+                "prev_action_embedding_dim > 0 needs prev_actions [T, N] or [T, N, 1]"
+            prev = prev_actions.reshape(T * N).to(torch.int64).contiguous()
+        if torch.is_grad_enabled():
+            params = [p for _, p in self._named()]
+            hv, h_final = _PolicyFn.apply(h, self, self._flat, rows_u, rows_w, None, prev, h0, m, T, N, *params)
+        else:   # act steps: straight to the inference plan, no autograd node
+            ws = torch.empty(h.workspace_bytes(T, N, False), dtype=torch.uint8, device=self._flat.device)
+            hv, h_final = h.forward(self._flat, rows_u, None, h0, m, T, N, ws, for_backward=False, feat2=rows_w, prev_actions=prev)
+        A = h.A
+        hv = hv.view(T, N, A + 1)
+        out = ActorCriticOutput(distributions=CategoricalDistr(logits=hv[..., :A]), values=hv[..., A:], extras={})
+        return out, memory.set_tensor("rnn", h.state_to_memory(h_final))

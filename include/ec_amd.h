@@ -301,6 +301,15 @@ int ec_nhwc_bf16_to_nchw_f32(const void* in, float* out, int B, int HW, int C, e
  * observations): fp32 [B,C,HW] -> bf16 [B,HW,C]; *inexact (device int, zeroed by the caller) is OR-ed with 1 when some
  * value is not exactly representable in bf16 -- the caller then keeps its fp32 path.  C % 64 == 0. */
 int ec_nchw_f32_to_nhwc_bf16(const float* in, void* out, int B, int HW, int C, int* inexact, ec_stream_t stream);
+/* ... for two tensors of one shape in ONE launch ([U] ai2thor-rearrangement ResNetRearrangeActorCriticRNN.forward's two
+ * observations, the current and the unshuffled view, on every act step): a, b fp32 [B, C, HW].
+ * out_a, out_b bf16 [B, HW, C]: round to nearest even.  *changed (device int) is set to 1 if any
+ * non-NaN element of either input is not already a bf16 value; it is never cleared by the call
+ * (sticky: the caller zeroes it).
+ * Checked before any HIP call: a, b, out_a, out_b or changed NULL or not 16-byte aligned -> EC_ERR_ARG; B <= 0, HW outside
+ * 1..64 or C % 64 != 0 -> EC_ERR_SHAPE. */
+int ec_nchw_f32_pair_to_nhwc_bf16(const float* a, const float* b, void* out_a, void* out_b, long B,
+                                  int HW, int C, int* changed, ec_stream_t stream);
 
 /* AdaptiveAvgPool2d(1)+Flatten on the fp32-cast features
  * (thor_image_features.py:63-66,113; preprocessor pool=True). bf16 [B,HW,C] -> f32 [B,C]. */
