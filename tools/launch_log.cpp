@@ -11,6 +11,9 @@
 //   s2    B H W Cin Cout ksize act res              ec_conv_bf16_s2
 //   gemm  M N K act res                             ec_gemm_bf16
 //   x3    M N K act                                 ec_gemm_bf16a_x3
+//   f32   M N K sam sak sbk sbn ldc flags bias gbias gidx group dmask rowscale splitk aoff boff
+//                                                   ec_gemm_f32; bias .. rowscale (but group) are 0 / 1 = NULL / a fake pointer;
+//                                                   aoff / boff: byte offsets of A / B from a 1 MiB-aligned base
 //   pair  M K0 N N2 two res                         ec_conv1x1_pair_bf16 (two: the second product a1 . w1^T + b1; res: the residual)
 //   pairpool B H W K0 N N2 y                        ec_conv1x1_pair_pool_bf16 (y = 0: y = NULL, not stored)
 //   img   B H C pool ldo                            ec_conv3x3_img_pack + ec_conv3x3_img_bf16_ld (ldo = 0: dense)
@@ -322,7 +325,7 @@ int main(int argc, char** argv) {
         int v[20] = {0}, n = 0, rc = -100;
         std::string kind;
         if (cmd == "trunk" || cmd == "tower") ss >> kind;
-        const int nmax = cmd == "policy" ? 20 : cmd == "pooled" ? 19 : cmd == "tower" ? 9 : 10;
+        const int nmax = cmd == "policy" ? 20 : cmd == "pooled" ? 19 : cmd == "f32" ? 18 : cmd == "tower" ? 9 : 10;
         while (n < nmax && ss >> v[n]) ++n;
         std::string input;
         if (cmd == "tower" && n == 9 && ss >> input) {
@@ -347,6 +350,11 @@ int main(int argc, char** argv) {
                                                                                    v[2], v[3], nullptr);
         } else if (cmd == "x3" && n == 4) {
             rc = sym<int (*)(P, P, P, P, long, int, int, int, P)>("ec_gemm_bf16a_x3")(in, w, bias, out, (long)v[0], v[1], v[2], v[3], nullptr);
+        } else if (cmd == "f32" && n == 18) {
+            const P a_ = (P)((uintptr_t)in + (uintptr_t)v[16]), b_ = (P)((uintptr_t)w + (uintptr_t)v[17]);
+            rc = sym<int (*)(P, P, P, int, int, int, long, long, long, long, int, int, P, P, P, int, P, P, int, P)>("ec_gemm_f32")(
+                a_, b_, out, v[0], v[1], v[2], (long)v[3], (long)v[4], (long)v[5], (long)v[6], v[7], v[8], v[9] ? bias : nullptr,
+                v[10] ? bias : nullptr, v[11] ? resb : nullptr, v[12], v[13] ? resb : nullptr, v[14] ? bias : nullptr, v[15], nullptr);
         } else if (cmd == "pair" && n == 6) {
             rc = sym<int (*)(P, P, P, P, P, P, P, P, P, P, P, long, int, int, int, P)>("ec_conv1x1_pair_bf16")(
                 in, w, bias, v[4] ? in : nullptr, v[4] ? w : nullptr, v[4] ? bias : nullptr, v[5] ? resb : nullptr, out, w, bias, out, (long)v[0],
