@@ -426,6 +426,7 @@ extern "C" int ec_stem_conv1(const float* rgb, const float* w, const float* bias
     if (B <= 0 || H < 2 || W < 2) return EC_ERR_SHAPE;
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const int tx = (Wo + ST - 1) / ST, ty = (Ho + ST - 1) / ST;
+    if ((long)B * tx * ty > 0x7fffffffL) return EC_ERR_SHAPE;
     dim3 grid((unsigned)(B * tx * ty));
     hipStream_t s = (hipStream_t)stream;
     const float3 z = make_float3(0.f, 0.f, 0.f);
@@ -450,6 +451,7 @@ extern "C" int ec_stem_conv1_u8(const uint8_t* rgb_u8, const float* mean3, const
     if (B <= 0 || H < 2 || W < 2) return EC_ERR_SHAPE;
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const int tx = (Wo + ST - 1) / ST, ty = (Ho + ST - 1) / ST;
+    if ((long)B * tx * ty > 0x7fffffffL) return EC_ERR_SHAPE;
     dim3 grid((unsigned)(B * tx * ty));
     hipStream_t s = (hipStream_t)stream;
     // (u8/255 - mean)/std == u8 * (1/(255 std)) - mean/std

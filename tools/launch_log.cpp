@@ -47,6 +47,14 @@
 //                                                   (+ ec_policy_backward2 with mode 2) + destroy; mode / reuse / `W` / `B` / `F` / `D`
 //                                                   as for `policy`; inplace 1: h_final == h0;
 //                                                   act 1 (T = 1, mode 0): ec_policy_act_pooled, sampling, instead of the forward
+//   stem  B H W Cout u8                             ec_stem_conv1 (u8 = 0) / ec_stem_conv1_u8 (the staging branch is chosen inside the
+//                                                   kernel: the record is the instance and the grid)
+//   stem7 B H W u8                                  ec_stem7_pool on fp32 (u8 = 0) / uint8 frames
+//   dstem B H W Cout                                ec_stem_conv1_depth
+//   avgpool B H W C ldo                             ec_avgpool2_bf16 (ldo = 0) / ec_avgpool2_bf16_ld
+//   tonchw B HW C                                   ec_nhwc_bf16_to_nchw_f32
+//   tonhwc B HW C                                   ec_nchw_f32_to_nhwc_bf16
+//   mean  B HW C                                    ec_spatial_mean_bf16
 // Output: `K <kernel>` per registered kernel, then per command `C <command>`, one `L <kernel>|<grid>|<block>|<lds>` per
 // launch (with --args N: `|` + the first N bytes of the first kernel argument in hex, for the conv_igemm kernels; --args-of SUBSTR N:
 // for the kernels whose name contains SUBSTR) and `R <rc>`.
@@ -315,6 +323,7 @@ int main(int argc, char** argv) {
     }
     typedef void* P;
     const P in = fake(1), w = fake(1), bias = fake(1), resb = fake(1), out = fake(1);
+    static const float kMean3[3] = {0.485f, 0.456f, 0.406f}, kStd3[3] = {0.229f, 0.224f, 0.225f};   // read on the host by the u8 entry points
     char line[256];
     while (fgets(line, sizeof line, stdin)) {
         std::istringstream ss(line);
@@ -383,6 +392,29 @@ int main(int argc, char** argv) {
         } else if (cmd == "tail" && n == 6) {
             rc = sym<int (*)(P, P, P, P, P, int, int, int, int, int, int, P)>("ec_basic_tail_s2_bf16")(in, resb, w, bias, out, v[0], v[1], v[2], v[3],
                                                                                                      v[4], v[5], nullptr);
+        } else if (cmd == "stem" && n == 5) {
+            if (v[4])
+                rc = sym<int (*)(P, const float*, const float*, P, P, P, int, int, int, int, P)>("ec_stem_conv1_u8")(in, kMean3, kStd3, w, bias, out, v[0],
+                                                                                                                    v[1], v[2], v[3], nullptr);
+            else
+                rc = sym<int (*)(P, P, P, P, int, int, int, int, P)>("ec_stem_conv1")(in, w, bias, out, v[0], v[1], v[2], v[3], nullptr);
+        } else if (cmd == "stem7" && n == 4) {
+            rc = sym<int (*)(P, int, const float*, const float*, P, P, P, int, int, int, P)>("ec_stem7_pool")(in, v[3], kMean3, kStd3, w, bias, out, v[0],
+                                                                                                             v[1], v[2], nullptr);
+        } else if (cmd == "dstem" && n == 4) {
+            rc = sym<int (*)(P, float, float, P, P, P, int, int, int, int, P)>("ec_stem_conv1_depth")(in, 4.f, -2.f, w, bias, out, v[0], v[1], v[2], v[3],
+                                                                                                     nullptr);
+        } else if (cmd == "avgpool" && n == 5) {
+            if (v[4] == 0)
+                rc = sym<int (*)(P, P, int, int, int, int, P)>("ec_avgpool2_bf16")(in, out, v[0], v[1], v[2], v[3], nullptr);
+            else
+                rc = sym<int (*)(P, P, int, int, int, int, int, P)>("ec_avgpool2_bf16_ld")(in, out, v[0], v[1], v[2], v[3], v[4], nullptr);
+        } else if (cmd == "tonchw" && n == 3) {
+            rc = sym<int (*)(P, P, int, int, int, P)>("ec_nhwc_bf16_to_nchw_f32")(in, out, v[0], v[1], v[2], nullptr);
+        } else if (cmd == "tonhwc" && n == 3) {
+            rc = sym<int (*)(P, P, int, int, int, P, P)>("ec_nchw_f32_to_nhwc_bf16")(in, out, v[0], v[1], v[2], resb, nullptr);
+        } else if (cmd == "mean" && n == 3) {
+            rc = sym<int (*)(P, P, int, int, int, P)>("ec_spatial_mean_bf16")(in, out, v[0], v[1], v[2], nullptr);
         } else if (cmd == "trunk" && n == 2) {
             rc = run_trunk(kind, v[0], v[1]);
         } else {
