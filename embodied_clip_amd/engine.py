@@ -48,6 +48,11 @@ IMAGENET_ENCODERS = {
 }
 
 
+def _frame_pool(base: torch.Tensor, pool_steps: int) -> torch.Tensor:
+    """[P, N, R, R, c]: pool entry s is the base batch shifted by s + 1 actors and 7 (s + 1) columns, so consecutive steps differ."""
+    return torch.stack([base.roll(shifts=s + 1, dims=0).roll(shifts=7 * (s + 1), dims=2) for s in range(pool_steps)])
+
+
 class SyntheticEnv:
     """N synthetic actors: a pool of pre-rendered, CLIP-normalised 224x224 frames in HBM,
     random goal ids, episode resets w.p. 1/100, RoboTHOR-style rewards."""
@@ -64,13 +69,10 @@ class SyntheticEnv:
         base = syn.synthetic_rgb_u8(seed, n_actors, res)
         if not frames_u8:   # (on the device when the pool lives there: 256 frames take 6 s on the host)
             base = syn.normalize_rgb(base if host else base.to(device))
-        frames = []
-        for s in range(pool_steps):   # distinct frame batches so consecutive steps differ
-            frames.append(base.roll(shifts=s + 1, dims=0).roll(shifts=7 * (s + 1), dims=2))
+        frames = _frame_pool(base, pool_steps)
         # host=True: the pool stays in PINNED HOST memory (what the simulators hand over through the plugin contract);
         # the worker then streams each step's frames over PCIe on a copy stream (Worker._encode_slice)
-        self.frames = (torch.stack(frames).contiguous().pin_memory() if host
-                       else torch.stack(frames).to(device).contiguous())   # [P, N, R, R, 3] fp32 | uint8
+        self.frames = (frames.contiguous().pin_memory() if host else frames.to(device).contiguous())   # [P, N, R, R, 3] fp32 | uint8
         self.pool_steps = pool_steps
         masks = torch.cat([torch.ones(1, n_actors, 1), syn.synthetic_masks(seed + 1, T, n_actors)], 0)
         self.masks = masks.reshape(T + 1, n_actors).to(device).contiguous()
@@ -86,12 +88,14 @@ class SyntheticEnv:
         self.rewards = syn.synthetic_rewards(seed + 3, masks[1:]).reshape(T, n_actors).to(device).contiguous()
         # success flag of the step that ends an episode: the +10 reward of synthetic_rewards (episode metrics / evaluation)
         self.success = ((self.rewards > 1) & (self.masks[1:] == 0)).to(torch.float32).contiguous()
+        # the second per-step input, served by observe_second(): the depth frames or the goal-state views (an env built with both
+        # serves the goal views there; observe_depth() / observe_goal_view() name either)
+        self._second = None
         if depth:
             # RGB-D: one-channel depth frames from a hash stream of their own, normalised (synthetic.normalize_depth), with
-            # the frames' construction: pool entry s is the base batch shifted by s + 1 actors and 7 (s + 1) columns
+            # the frames' construction
             dbase = syn.normalize_depth(syn.synthetic_depth(seed + 5, n_actors, res).to(device))
-            self.depth = torch.stack([dbase.roll(shifts=s + 1, dims=0).roll(shifts=7 * (s + 1), dims=2)
-                                      for s in range(pool_steps)]).contiguous()   # [P, N, R, R, 1] fp32
+            self.depth = self._second = _frame_pool(dbase, pool_steps).contiguous()   # [P, N, R, R, 1] fp32
         if sensors:
             # the pooled-embedding net's small float sensors (GPS, compass, a 3-float point goal): K floats per actor and step,
             # f32 [T+1, N, K], from a seed of their own -- nothing else the env builds changes
@@ -102,8 +106,7 @@ class SyntheticEnv:
             gbase = syn.synthetic_rgb_u8(seed + 9, n_actors, res).to(device)
             if not frames_u8:
                 gbase = syn.normalize_rgb(gbase)
-            self.goal_frames = torch.stack([gbase.roll(shifts=s + 1, dims=0).roll(shifts=7 * (s + 1), dims=2)
-                                            for s in range(pool_steps)]).contiguous()   # [P, N, R, R, 3] fp32 | uint8, on the device
+            self.goal_frames = self._second = _frame_pool(gbase, pool_steps).contiguous()   # [P, N, R, R, 3] fp32 | uint8, on the device
         self._k = 0
 
     def observe(self, actions_host: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -117,21 +120,27 @@ class SyntheticEnv:
         """The batch ``observe()`` serves as its k-th call (per-slice env stepping: every slice asks for step k itself)."""
         return self.frames[k % self.pool_steps]
 
+    def observe_second(self, pool: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The second input that goes with the frames ``observe()`` served last: the depth batch (``depth=True`` envs) or the
+        goal-state views (``goal_view=True`` envs)."""
+        return self.observe_second_at(self._k - 1, pool)
+
+    def observe_second_at(self, k: int, pool: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """... that goes with ``observe_at(k)``."""
+        return (self._second if pool is None else pool)[k % self.pool_steps]
+
+    # (the pair above under the names of what it serves, for tools and tests)
     def observe_depth(self) -> torch.Tensor:
-        """The depth batch that goes with the frames ``observe()`` served last (``depth=True`` envs)."""
-        return self.depth[(self._k - 1) % self.pool_steps]
+        return self.observe_second(self.depth)
 
     def observe_depth_at(self, k: int) -> torch.Tensor:
-        """The depth batch that goes with ``observe_at(k)``."""
-        return self.depth[k % self.pool_steps]
+        return self.observe_second_at(k, self.depth)
 
     def observe_goal_view(self) -> torch.Tensor:
-        """The goal-state views that go with the frames ``observe()`` served last (``goal_view=True`` envs)."""
-        return self.goal_frames[(self._k - 1) % self.pool_steps]
+        return self.observe_second(self.goal_frames)
 
     def observe_goal_view_at(self, k: int) -> torch.Tensor:
-        """The goal-state views that go with ``observe_at(k)``."""
-        return self.goal_frames[k % self.pool_steps]
+        return self.observe_second_at(k, self.goal_frames)
 
 
 class NavSyntheticEnv(SyntheticEnv):
@@ -148,9 +157,6 @@ class NavSyntheticEnv(SyntheticEnv):
         self.step_dist = step_dist.to(device).contiguous()
         self.start_dist = start_dist.to(device).contiguous()
         self.goal_dist = goal_dist.to(device).contiguous()
-
-
-_NO_SIDE: Dict = {}      # (no extra keyword of the policy calls)
 
 
 class _Slice:
@@ -283,9 +289,9 @@ def check_model_tensors(policy, sd, where: str) -> None:
 
 class _SlicedActor:
     """What a training ``Worker`` and an ``evaluate.Evaluator`` share: the frozen encoder handles and the policy handle, the
-    actor slices with their streams, act workspaces and feature buffers, and hot loop A's encode step.  The users set
-    ``self.lib``, ``self.dev`` / ``self.device``, ``self.zeroshot``, ``self._text_sd``, ``self._goal_tokens``, ``self.goal_in``,
-    ``self._num_actions`` and ``self.depth`` first, and ``self.env`` between ``_build_model`` and ``_build_slices``.
+    actor slices with their streams, act workspaces and feature buffers, and hot loop A's encode step.  The users call
+    ``_configure`` (the agent description) first, set ``self.dev`` / ``self.device``, ``self.nav_metrics``, ``self._text_sd`` and
+    ``self._goal_tokens``, and set ``self.env`` between ``_build_model`` and ``_build_slices``.
 
     ``self.depth`` (an RGB-D agent, readme_files/baselines_habitat.md:75): the env serves depth frames and ``_observe`` hands
     them to the encode step.  What the agent does with them is ``self.dual``:
@@ -324,13 +330,96 @@ class _SlicedActor:
     # pooled net), or None (feature maps); ``_build_model`` sets it
     _embed = None
 
-    def _goal(self, t: int, rs):
-        """step ``t``'s goal argument of the policy calls for the actors ``rs`` (None: a pooled net without a goal-id embedding)"""
-        return self.env.goals[t][rs] if (self.goal_ids or not self.pooled_net) else None
+    def _configure(self, encoder, net, pooling, sensors, goal_ids, goal_in, depth, zeroshot, num_actions, prev_actions,
+                   prev_action_null_token, rnn_type, rnn_layers, hidden, frames_host=False, env=None):
+        """The agent description: every refusal, then the attributes the rest of the class reads.  Called first by both users, so a
+        refused combination raises before anything is allocated or the library is loaded.  ``frames_host``: the Worker's;
+        ``env``: the Evaluator's optional ``env=``, which must serve what the agent reads."""
+        host = bool(frames_host or (env is not None and getattr(env, "host", False)))
+        self.pooled_net, self.pooling, self.net_sensors = check_net(net, pooling, sensors, goal_ids, encoder, bool(depth), bool(zeroshot), goal_in)
+        self.two_view_net = net == "two_view"
+        self.goal_ids = bool(goal_ids) and not self.two_view_net
+        if self.two_view_net and frames_host:
+            raise ValueError("net='two_view': host-resident frames (frames_host=True) have no staging path for the goal view")
+        if self.two_view_net and env is not None and (getattr(env, "goal_frames", None) is None or host):
+            raise ValueError("net='two_view': the env serves no goal-state views on the device (SyntheticEnv(..., goal_view=True) holds env.goal_frames)")
+        if self.net_sensors and env is not None and getattr(env, "sensors", None) is None:
+            raise ValueError("net='pooled' with sensors: the env serves no sensor vectors (SyntheticEnv(..., sensors=K) holds env.sensors)")
+        if depth:
+            check_rgbd(encoder, zeroshot, goal_in, host)
+            if env is not None and getattr(env, "depth", None) is None:
+                raise ValueError("depth=True: the env serves no depth frames (SyntheticEnv(..., depth=True) holds env.depth)")
+        two_tower = bool(depth) and not self.pooled_net     # (the pooled RGB-D agent's policy handle is the RGB pooled net's: nothing to refuse)
+        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot), 512 if self.two_view_net else 64)
+        self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
+        self.rnn_type = check_rnn_type(rnn_type, two_tower, bool(zeroshot))
+        self.rnn_layers = check_rnn_layers(rnn_layers, two_tower, bool(zeroshot))
+        self.hidden_size = int(hidden)
+        self.depth = bool(depth)
+        assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
+        self.zeroshot, self.goal_in, self._num_actions = zeroshot, goal_in, num_actions
+        # what the policy calls of this agent take beside the features (read per step as plain attributes): the env's goal rows
+        # (not on a pooled net without the goal-id embedding, nor on the two-view net) and the pooled net's sensor rows
+        self._has_goal = self.goal_ids or not self.pooled_net
+        self._has_sensors = bool(self.net_sensors)
+        self._has_second = self.depth or self.two_view_net      # the env's second per-step input: depth frames / goal-state views
+        self.lib = _lib.load()
 
-    def _side(self, t: int, rs):
-        """... and the pooled net's sensor rows, as a keyword (nothing for every other net)"""
-        return {"sensors": self.env.sensors[t][rs]} if self.net_sensors else {}
+    def _env_recipe(self, expert: bool = False):
+        """The env this agent reads.  -> (class, keywords beside the sizes, the seed and the frames' form)"""
+        kw = dict(goal_in=self.goal_in)
+        if self.depth:
+            kw["depth"] = True
+        if expert:
+            kw.update(expert=True, num_actions=self._num_actions)
+        if self.net_sensors:
+            kw["sensors"] = sum(self.net_sensors)
+        if self.two_view_net:
+            kw["goal_view"] = True
+        return (NavSyntheticEnv if self.nav_metrics else SyntheticEnv), kw
+
+    def _episode_tracker(self, num_categories=None, capacity: int = 0):
+        """``nav_metrics``: per-category rows for goal ids (default: the env's ``num_goals``); coordinate goals have no categories."""
+        if not self.nav_metrics:
+            return EpisodeTracker(self.N, self.dev, capacity=capacity)
+        C = 0 if self.goal_in else (num_categories if num_categories is not None else getattr(self.env, "num_goals", 12))
+        return NavEpisodeTracker(self.N, self.dev, num_categories=C, capacity=capacity)
+
+    def _update_episodes(self):
+        """Fold the env's ``rewards`` / ``masks`` / ``success`` (and the navigation geometry) of one rollout into the tracker."""
+        nav = nav_env_tensors(self.env, self.episodes.C > 0) if self.nav_metrics else ()
+        self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None), *nav)
+
+    def _encoder_handles(self, ns, make):
+        """``make(weights_from)`` once, then ``ns - 1`` handles that borrow the first one's device weights."""
+        share = os.environ.get("EC_SHARE_WEIGHTS", "1") != "0"
+        first = make(None)
+        return [first] + [make(first if share else None) for _ in range(ns - 1)]
+
+    def _policy_recipe(self, encoder):
+        """The agent's policy.  -> (constructor, its keywords, the name under which ``synthetic.policy_state_dict`` takes the same
+        keywords for the seeded stand-in weights: None = as they are)"""
+        rnn = dict(rnn_type=self.rnn_type, rnn_layers=self.rnn_layers)
+        pa = dict(prev_action_dims=self.prev_action_dims, prev_action_null=self.prev_action_null)
+        if self.two_view_net:
+            return PolicyHandle.two_view, dict(in_channels=self.C, hidden=self.hidden_size, num_actions=self._num_actions, spatial=self.S,
+                                               **pa, **rnn), "two_view"
+        if self.pooled_net:
+            return PolicyHandle.pooled, dict(embed_in=self.C, hidden=self.hidden_size, num_goals=12 if self.goal_ids else 0,
+                                             sensors=self.net_sensors, num_actions=self._num_actions, **pa, **rnn), "pooled"
+        kw = dict(in_channels=self.C, spatial=self.S, num_actions=self._num_actions, **rnn)
+        if self.goal_in:
+            kw["goal_in"] = self.goal_in
+        if self.dual:      # [U] ResnetDualTensorGoalEncoder: 25 tensors, rgb_* / depth_* compressors and combiners
+            kw["dual"] = 1
+        if self.zeroshot:
+            assert encoder == "rn50", "the zero-shot variant uses the CLIP-RN50 image embedding"
+            kw["fusion"] = 1
+        if self.prev_action_dims:
+            kw.update(pa)
+        if self.hidden_size != 512:
+            kw["hidden"] = self.hidden_size
+        return PolicyHandle, kw, None
 
     def _build_model(self, n_actors, encoder, encoder_sd, policy_sd, encoder_chunk, encoder_streams):
         """Encoder handles (one per slice, weights shared), the policy handle and its flat parameters.  -> (encs, pools)"""
@@ -349,13 +438,10 @@ class _SlicedActor:
             sd = encoder_sd if encoder_sd is not None else (
                 syn.rn50_visual_state_dict(0) if encoder == "rn50" else
                 syn.rn50_visual_state_dict(0, width=96, layers=(6, 8, 18, 8), output_dim=768, heads=48))
-            share = os.environ.get("EC_SHARE_WEIGHTS", "1") != "0"
-            encs = [RN50Trunk(sd, device=d, chunk=encoder_chunk)]
-            encs += [RN50Trunk(sd, device=d, chunk=encoder_chunk, weights_from=encs[0] if share else None) for _ in range(ns - 1)]
+            encs = self._encoder_handles(ns, lambda w: RN50Trunk(sd, device=d, chunk=encoder_chunk, weights_from=w))
             self.S, self.C = encs[0].out_spatial, encs[0].out_channels
             if self._embed == "attnpool":
-                pools = [AttentionPool(sd, device=d)]
-                pools += [AttentionPool(sd, device=d, weights_from=pools[0] if share else None) for _ in range(ns - 1)]
+                pools = self._encoder_handles(ns, lambda w: AttentionPool(sd, device=d, weights_from=w))
                 self.trunk_S, self.trunk_C = self.S, self.C
                 self.S, self.C = 1, pools[0].out_dim
         elif encoder in IMAGENET_ENCODERS:
@@ -363,57 +449,22 @@ class _SlicedActor:
             # / ..._resnet50gru_ddppo): ResNet-18 / 34 -> 512 x 7 x 7, ResNet-50 -> 2048 x 7 x 7, same policy and PPO
             layers, block, cls = IMAGENET_ENCODERS[encoder]
             sd = encoder_sd if encoder_sd is not None else syn.tv_resnet_state_dict(0, layers=layers, block=block)
-            share = os.environ.get("EC_SHARE_WEIGHTS", "1") != "0"
-            encs = [cls(sd, device=d, chunk=encoder_chunk)]
-            encs += [cls(sd, device=d, chunk=encoder_chunk, weights_from=encs[0] if share else None) for _ in range(ns - 1)]
+            encs = self._encoder_handles(ns, lambda w: cls(sd, device=d, chunk=encoder_chunk, weights_from=w))
             self.S, self.C = encs[0].out_spatial, encs[0].out_channels
         elif encoder == "vit":
             # BASELINE config 3 (builder-defined fusion, SURVEY.md §8d note): ClipViTEmbedder tokens, CLS dropped,
             # the 49 patch tokens are the 7x7 channels-last "feature map" [n,49,768] of the goal encoder
             sd = encoder_sd if encoder_sd is not None else syn.vit_visual_state_dict(0)
-            share = os.environ.get("EC_SHARE_WEIGHTS", "1") != "0"
-            encs = [ViTEmbedder(sd, device=d)]
-            encs += [ViTEmbedder(sd, device=d, weights_from=encs[0] if share else None) for _ in range(ns - 1)]
+            encs = self._encoder_handles(ns, lambda w: ViTEmbedder(sd, device=d, weights_from=w))
             self.S, self.C = 7, encs[0].D
         else:
             raise ValueError(encoder)
         if self._embed == "avgpool":      # AdaptiveAvgPool2d(1) of the trunk output (ec_spatial_mean_bf16): D = the trunk's channels
             self.trunk_S, self.trunk_C = self.S, self.C
             self.S = 1
-        if self.two_view_net:
-            self.policy = PolicyHandle.two_view(self.C, hidden=self.hidden_size, num_actions=self._num_actions,
-                                                prev_action_dims=self.prev_action_dims, prev_action_null=self.prev_action_null,
-                                                rnn_type=self.rnn_type, rnn_layers=self.rnn_layers, spatial=self.S)
-            if policy_sd is not None:     # (a checkpoint of another net: refused by the first tensor it lacks, by name)
-                check_model_tensors(self.policy, policy_sd, getattr(self, "_checkpoint", None) or "policy_sd")
-            self.H, self.A, self.SW = self.policy.H, self.policy.A, self.policy.state_width
-            self.params = self.policy.flatten(policy_sd if policy_sd is not None
-                                              else syn.policy_state_dict(0, two_view=self.policy.two_view_cfg), d)
-            return encs, pools
-        if self.pooled_net:
-            self.policy = PolicyHandle.pooled(self.C, hidden=self.hidden_size, num_goals=12 if self.goal_ids else 0, sensors=self.net_sensors,
-                                              num_actions=self._num_actions, prev_action_dims=self.prev_action_dims,
-                                              prev_action_null=self.prev_action_null, rnn_type=self.rnn_type, rnn_layers=self.rnn_layers)
-            if policy_sd is not None:     # (a checkpoint of another net: refused by the first tensor it lacks, by name)
-                check_model_tensors(self.policy, policy_sd, getattr(self, "_checkpoint", None) or "policy_sd")
-            self.H, self.A, self.SW = self.policy.H, self.policy.A, self.policy.state_width
-            self.params = self.policy.flatten(policy_sd if policy_sd is not None
-                                              else syn.policy_state_dict(0, pooled=self.policy.pooled_cfg), d)
-            return encs, pools
-        pkw = dict(in_channels=self.C, spatial=self.S, num_actions=self._num_actions)
-        if self.goal_in:
-            pkw["goal_in"] = self.goal_in
-        if self.dual:      # [U] ResnetDualTensorGoalEncoder: 25 tensors, rgb_* / depth_* compressors and combiners
-            pkw["dual"] = 1
-        if self.zeroshot:
-            assert encoder == "rn50", "the zero-shot variant uses the CLIP-RN50 image embedding"
-            pkw["fusion"] = 1
-        if self.prev_action_dims:
-            pkw.update(prev_action_dims=self.prev_action_dims, prev_action_null=self.prev_action_null)
-        if self.hidden_size != 512:
-            pkw["hidden"] = self.hidden_size
-        self.policy = PolicyHandle(rnn_type=self.rnn_type, rnn_layers=self.rnn_layers, **pkw)
-        if policy_sd is not None:   # (a checkpoint of the other recurrent cell: refused by the tensor's name, both shapes and the file)
+        make, pkw, sd_name = self._policy_recipe(encoder)
+        self.policy = make(**pkw)
+        if policy_sd is not None:   # a checkpoint of another net, cell or depth: refused by the tensor's name (and both shapes), with the file
             check_model_tensors(self.policy, policy_sd, getattr(self, "_checkpoint", None) or "policy_sd")
         if self.zeroshot:
             # goal table: the CLIP text tower over the 12 goal prompts, once, L2-normalised; frozen
@@ -424,8 +475,9 @@ class _SlicedActor:
             self.policy.set_goal_table(self.goal_table)
         self.H, self.A = self.policy.H, self.policy.A
         self.SW = self.policy.state_width        # width of a recurrent-memory row: L * H, or L * 2H ([h | c] per layer) with an LSTM core
-        self.params = self.policy.flatten(policy_sd if policy_sd is not None
-                                          else syn.policy_state_dict(0, **pkw, rnn_type=self.rnn_type, rnn_layers=self.rnn_layers), d)
+        if policy_sd is None:       # the seeded stand-in weights
+            policy_sd = syn.policy_state_dict(0, **({sd_name: pkw} if sd_name else pkw))
+        self.params = self.policy.flatten(policy_sd, d)
         return encs, pools
 
     def _build_slices(self, n_actors, encs, pools, feat_steps, n_comm, frames_host):
@@ -522,9 +574,9 @@ class _SlicedActor:
         return sl.feat2[t] if self.dual else None
 
     def _observe(self, actions_host=None):
-        """env.step: the next RGB batch and (``depth=True``) the depth batch that goes with it."""
+        """env.step: the next RGB batch and the second input that goes with it (depth frames / goal-state views; else None)."""
         rgb = self.env.observe(actions_host) if actions_host is not None else self.env.observe()
-        return rgb, (self.env.observe_depth() if self.depth else (self.env.observe_goal_view() if self.two_view_net else None))
+        return rgb, (self.env.observe_second() if self._has_second else None)
 
     @property
     def enc_streams(self):
@@ -701,24 +753,9 @@ class Worker(_SlicedActor):
         ``zeroshot=True`` (BASELINE config 5, readme_files/zeroshot_objectnav.md): the observation is the CLIP image
         EMBEDDING (RN50 trunk + AttentionPool2d, 1024-d), the goal is the frozen CLIP text embedding of its prompt
         (text tower run once -> [12, 1024] table) and the policy is the fusion=1 variant (GRU + heads trainable)."""
-        self.pooled_net, self.pooling, self.net_sensors = check_net(net, pooling, sensors, goal_ids, encoder, bool(depth), bool(zeroshot), goal_in)
-        self.two_view_net = net == "two_view"
-        self.goal_ids = bool(goal_ids) and not self.two_view_net
-        if self.two_view_net and frames_host:
-            raise ValueError("net='two_view': host-resident frames (frames_host=True) have no staging path for the goal view")
-        if depth:
-            check_rgbd(encoder, zeroshot, goal_in, frames_host)
-        two_tower = bool(depth) and not self.pooled_net     # (the pooled RGB-D agent's policy handle is the RGB pooled net's: nothing to refuse)
-        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot), 512 if self.two_view_net else 64)
-        self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
-        self.rnn_type = check_rnn_type(rnn_type, two_tower, bool(zeroshot))
-        self.rnn_layers = check_rnn_layers(rnn_layers, two_tower, bool(zeroshot))
-        self.hidden_size = int(hidden)
-        self.depth = bool(depth)
-        self.lib = _lib.load()
-        self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
-        assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
-        self.goal_in, self._num_actions = goal_in, num_actions
+        self._configure(encoder, net, pooling, sensors, goal_ids, goal_in, depth, zeroshot, num_actions, prev_actions,
+                        prev_action_null_token, rnn_type, rnn_layers, hidden, frames_host=frames_host)
+        self._text_sd, self._goal_tokens = text_sd, goal_tokens
         self.track_episodes = track_episodes
         if nav_metrics and not track_episodes:
             raise ValueError("Worker(nav_metrics=True) needs track_episodes=True")
@@ -790,19 +827,9 @@ class Worker(_SlicedActor):
         self.hv_act = torch.empty((N, self.A + 1), dtype=torch.float32, device=d)
         self.stats = torch.zeros(2, dtype=torch.float64, device=d)
         self.sums = torch.zeros(4, dtype=torch.float64, device=d)
-        env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
-        dkw = dict(depth=True) if self.depth else {}
-        if self._il or self.teacher_forcing is not None:
-            dkw.update(expert=True, num_actions=self._num_actions)
-        if self.net_sensors:
-            dkw.update(sensors=sum(self.net_sensors))
-        if self.two_view_net:
-            dkw.update(goal_view=True)
-        self.env = env_cls(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, goal_in=self.goal_in, **dkw)
-        if self.nav_metrics:      # per-category rows for goal ids; coordinate goals have no categories
-            self.episodes = NavEpisodeTracker(N, d, num_categories=0 if self.goal_in else self.env.num_goals)
-        else:
-            self.episodes = EpisodeTracker(N, d) if self.track_episodes else None
+        env_cls, ekw = self._env_recipe(expert=self._il or self.teacher_forcing is not None)
+        self.env = env_cls(N, T, d, seed=1000 + rank, frames_u8=frames_u8, host=frames_host, **ekw)
+        self.episodes = self._episode_tracker() if self.track_episodes else None
         self._build_slices(n_actors, encs, pools, T + 1, 1 if (world > 1 or self.force_allreduce) else 0, frames_host)
         if self.comm_stream is None:
             self.comm_stream = torch.cuda.Stream(device=d)
@@ -814,13 +841,13 @@ class Worker(_SlicedActor):
             sl.rec_ready = torch.cuda.Event()
             sl.rec_ready.record()          # (torch creates the hipEvent_t at the first record: the library needs the handle)
             sl.sums = torch.zeros(4, dtype=torch.float64, device=d)
-            sl.goal = sl.masks = sl.actions = sl.logp = sl.old_v = sl.ret = sl.nadv = sl.prev = sl.sens = None
+            sl.cols = None             # this rollout's [T, n, ...] columns of the slice (update() fills them)
+            sl.feat_mb = sl.feat2_mb = None      # staging of the feature columns of a partial range (gather() makes them)
             # more than 16 actions: the wide loss kernel's partial-sum scratch, one per slice stream as for imitation
             sl.ppo_scratch = ppo_wide_scratch(d) if (self._ppo and self.A > PPO_NARROW_MAX_A) else None
             if self._il:      # the imitation loss's sums and partial-sum scratch: one per slice stream
                 sl.il_sums = torch.zeros(3, dtype=torch.float64, device=d)
                 sl.il_scratch = imitation_scratch(d)
-                sl.ex_a = sl.ex_m = None
         if self._il:          # one normaliser per minibatch range (update() fills them once per rollout)
             self._il_denoms = torch.zeros(self.num_mini_batch, dtype=torch.float64, device=d)
         self.seed = seed + 7919 * rank
@@ -840,14 +867,14 @@ class Worker(_SlicedActor):
         rs = slice(o, o + n)
         h_in, h_out = (self.h, self.h_next) if (t & 1) == 0 else (self.h_next, self.h)   # ping-pong by step parity
         pa = self.prev_actions[t][rs] if self.prev_action_dims else None                  # (the bootstrap step reads row T)
-        # (the pooled net's goal / sensor arguments; every other net: the goal row and no keyword, without a call on this host chain)
-        goal, side = (self._goal(t, rs), self._side(t, rs)) if self.pooled_net else (self.env.goals[t][rs], _NO_SIDE)
+        goal = self.env.goals[t][rs] if self._has_goal else None            # (what the agent description decided: plain attributes,
+        sens = self.env.sensors[t][rs] if self._has_sensors else None       #  no call on this host chain)
         if sample and self._act_fused:
             # forward + CategoricalDistr.sample / log_prob in one call: the heads launch samples (ec_policy_act, one launch less)
             self.policy.act(self.params, sl.feat[t], goal, h_in[rs], self.env.masks[t][rs], n, sl.ws_act,
                             self.hv_act[rs], h_out[rs], self.actions[t][rs], self.logp[t][rs], self.values[t][rs], self.seed,
                             self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa,
-                            **side)
+                            sensors=sens)
             sl.act_tables_valid = True
             self._teacher_force_slice(sl, t)
             return
@@ -859,12 +886,12 @@ class Worker(_SlicedActor):
                                self.iter * (self.T + 1) + t, o, reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t),
                                expert_actions=self.env.expert_actions[t][rs] if tf else None,
                                expert_mask=self.env.expert_mask[t][rs] if tf else None, force_p=self._tf_p if tf else 0.0,
-                               prev_actions=pa, **side)
+                               prev_actions=pa, sensors=sens)
             sl.act_tables_valid = True
             return
         self.policy.forward(self.params, sl.feat[t], goal, h_in[rs], self.env.masks[t][rs], 1, n,
                             sl.ws_act, hv=self.hv_act[rs], h_final=h_out[rs], for_backward=False,
-                            reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa, **side)   # (E1 depends on the parameters only)
+                            reuse_tables=sl.act_tables_valid, feat2=self._f2(sl, t), prev_actions=pa, sensors=sens)   # (E1 depends on the parameters only)
         sl.act_tables_valid = True
         if sample:
             _lib.check(self.lib.ec_sample_actions(self.hv_act[rs].data_ptr(), self.actions[t][rs].data_ptr(),
@@ -944,8 +971,7 @@ class Worker(_SlicedActor):
                 for sl in self.slices:
                     wait(sl)                                                 # this slice's actions[t] are on the host
                     rgb = self.env.observe_at(k0 + t, self._actions_host)   # env.step of this slice's samplers
-                    dep = (self.env.observe_depth_at(k0 + t) if self.depth
-                           else (self.env.observe_goal_view_at(k0 + t) if self.two_view_net else None))
+                    dep = self.env.observe_second_at(k0 + t) if self._has_second else None
                     with self._on(sl):
                         self._encode_slice(sl, rgb, t + 1, dep)
                         if t + 1 < T:
@@ -980,30 +1006,30 @@ class Worker(_SlicedActor):
                                        self.returns.data_ptr(), self.adv.data_ptr(), self.nadv.data_ptr(),
                                        self.stats.data_ptr(), self.T, self.N, self.gamma, self.tau, 1e-5,
                                        _lib.stream_ptr()), "ec_gae")
-        if self.nav_metrics:
-            self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None),
-                                 *nav_env_tensors(self.env, self.episodes.C > 0))
-        elif self.episodes is not None:
-            self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None))
+        if self.episodes is not None:
+            self._update_episodes()
 
     # ---- HOT LOOP B ---------------------------------------------------------------------------
-    def _gather_slice_batches(self):
-        """Contiguous [T*n] copies of the slice's columns of the [T, N] rollout scalars (once per iteration)."""
-        T = self.T
+    def _rollout_columns(self):
+        """name -> the [T (+ 1), N, ...] storage of every per-step column THIS agent's learn pass reads beside the features."""
+        cols = dict(masks=self.env.masks, actions=self.actions, logp=self.logp, old_values=self.values, returns=self.returns,
+                    advantages=self.nadv)
+        if self._has_goal:            # int64 ids [., N], or (coordinate goals) f32 [., N, goal_in]
+            cols["goal"] = self.env.goals
+        if self._has_sensors:         # the pooled net's sensor rows [., N, K]
+            cols["sensors"] = self.env.sensors
+        if self._il:
+            cols.update(expert_actions=self.env.expert_actions, expert_mask=self.env.expert_mask)
+        if self.prev_action_dims:     # rows 0..T-1: every step's previous action
+            cols["prev_actions"] = self.prev_actions
+        return cols
+
+    def _gather_columns(self):
+        """Every slice's table of columns: contiguous [T, n, ...] copies of its actors' part of the rollout storage (once per
+        iteration)."""
+        cols = self._rollout_columns()
         for sl in self.slices:
-            rs = slice(sl.o, sl.o + sl.n)
-            c = lambda x: x[:T, rs].reshape(-1).contiguous()
-            # (coordinate goals keep their last dimension: [T*n, goal_in] rows)
-            sl.goal = self.env.goals[:T, rs].reshape(T * sl.n, -1).contiguous() if self.goal_in else c(self.env.goals)
-            if self.net_sensors:      # the pooled net's sensor rows [T*n, K]
-                sl.sens = self.env.sensors[:T, rs].reshape(T * sl.n, -1).contiguous()
-            sl.masks = c(self.env.masks)
-            sl.actions, sl.logp, sl.old_v = c(self.actions), c(self.logp), c(self.values)
-            sl.ret, sl.nadv = c(self.returns), c(self.nadv)
-            if self._il:
-                sl.ex_a, sl.ex_m = c(self.env.expert_actions), c(self.env.expert_mask)
-            if self.prev_action_dims:
-                sl.prev = c(self.prev_actions)        # rows 0..T-1: every step's previous action
+            sl.cols = {name: x[:self.T, sl.o:sl.o + sl.n].contiguous() for name, x in cols.items()}
 
     def minibatch_ranges(self):
         """[U] allenact ``RolloutStorage.recurrent_generator``: the samplers (actors) are cut at
@@ -1024,46 +1050,30 @@ class Worker(_SlicedActor):
                 best = max(best, b - a)
         return best
 
-    def _gather_part(self, sl, a: int, b: int):
-        """Contiguous [T * (b - a)] batch of actors [a, b) of slice ``sl`` (slice-local indices) in the slice's staging
-        buffers; the whole slice is used in place."""
-        T = self.T
-        if a == 0 and b == sl.n:
-            return (sl.feat[:T].view(T * sl.n, self.S * self.S, self.C), sl.goal, sl.masks, sl.actions, sl.logp, sl.old_v,
-                    sl.ret, sl.nadv)
-        m = b - a
-        if getattr(sl, "feat_mb", None) is None:                   # staging for partial-slice minibatches (allocated on first use),
-            mmax = self._max_partial_range(sl)                      # sized to the largest PARTIAL range, not the whole slice
-            sl.feat_mb = torch.empty((T, mmax, self.S * self.S, self.C), dtype=sl.feat.dtype, device=self.dev)
-        fm = sl.feat_mb.view(-1)[:T * m * self.S * self.S * self.C].view(T, m, self.S * self.S, self.C)
-        fm.copy_(sl.feat[:T, a:b])
-        c = lambda x: x.view(T, sl.n)[:, a:b].reshape(-1).contiguous()
-        goal = sl.goal.view(T, sl.n, -1)[:, a:b].reshape(T * m, -1).contiguous() if self.goal_in else c(sl.goal)
-        return (fm.view(T * m, self.S * self.S, self.C), goal, c(sl.masks), c(sl.actions), c(sl.logp), c(sl.old_v),
-                c(sl.ret), c(sl.nadv))
-
-    def _gather_expert(self, sl, a: int, b: int):
-        """The expert actions and mask of the batch ``_gather_part(sl, a, b)`` returns, [T * (b - a)] each."""
-        if a == 0 and b == sl.n:
-            return sl.ex_a, sl.ex_m
-        c = lambda x: x.view(self.T, sl.n)[:, a:b].reshape(-1).contiguous()
-        return c(sl.ex_a), c(sl.ex_m)
-
-    def _gather_prev(self, sl, a: int, b: int):
-        """The previous actions of the batch ``_gather_part(sl, a, b)`` returns, [T * (b - a)] (None without the embedding)."""
-        if not self.prev_action_dims:
-            return None
-        if a == 0 and b == sl.n:
-            return sl.prev
-        return sl.prev.view(self.T, sl.n)[:, a:b].reshape(-1).contiguous()
-
-    def _gather_side(self, sl, a: int, b: int):
-        """The pooled net's sensor rows of the batch ``_gather_part(sl, a, b)`` returns, as a keyword (nothing for every other net)."""
-        if not self.net_sensors:
-            return {}
-        if a == 0 and b == sl.n:
-            return {"sensors": sl.sens}
-        return {"sensors": sl.sens.view(self.T, sl.n, -1)[:, a:b].reshape(self.T * (b - a), -1).contiguous()}
+    def gather(self, sl, a: int, b: int) -> Dict[str, torch.Tensor]:
+        """The learn batch of actors [a, b) of slice ``sl`` (slice-local indices): {column: contiguous [T * (b - a), ...] rows} over
+        ``feat``, ``feat2`` (an agent with a second feature buffer) and the slice's table (``_rollout_columns``).  The whole slice is
+        used in place; a partial range is a copy -- of the features through the staging buffers ``sl.feat_mb`` / ``sl.feat2_mb``,
+        allocated on first use and sized to the largest PARTIAL range, not the whole slice."""
+        T, m, S2 = self.T, b - a, self.S * self.S
+        whole = a == 0 and b == sl.n
+        out = {}
+        for name, src in (("feat", sl.feat), ("feat2", sl.feat2)):
+            if src is None:
+                continue
+            if whole:
+                out[name] = src[:T].view(T * m, S2, self.C)
+                continue
+            stage = getattr(sl, name + "_mb")
+            if stage is None:
+                stage = torch.empty((T, self._max_partial_range(sl), S2, self.C), dtype=src.dtype, device=self.dev)
+                setattr(sl, name + "_mb", stage)
+            fm = stage.view(-1)[:T * m * S2 * self.C].view(T, m, S2, self.C)
+            fm.copy_(src[:T, a:b])
+            out[name] = fm.view(T * m, S2, self.C)
+        for name, col in sl.cols.items():      # [T, n, ...] -> [T * m, ...]
+            out[name] = (col if whole else col[:, a:b].contiguous()).view((T * m,) + col.shape[2:])
+        return out
 
     def _expert_counts(self) -> Dict[tuple, torch.Tensor]:
         """The imitation normaliser of every minibatch range -- the number of this rollout's steps that have an expert action
@@ -1075,21 +1085,6 @@ class Worker(_SlicedActor):
             _lib.check(self.lib.ec_expert_count(self.env.expert_mask.data_ptr(), self.T, self.N, s0, s1,
                                                 out[(s0, s1)].data_ptr(), _lib.stream_ptr()), "ec_expert_count")
         return out
-
-    def _gather_feat2(self, sl, a: int, b: int):
-        """The depth features of the batch ``_gather_part(sl, a, b)`` returns (``depth=True``; else None): the whole slice in
-        place, a partial range through a staging buffer of its own, sized as ``feat_mb``."""
-        if not self.dual:
-            return None
-        T, S2 = self.T, self.S * self.S
-        if a == 0 and b == sl.n:
-            return sl.feat2[:T].view(T * sl.n, S2, self.C)
-        m = b - a
-        if getattr(sl, "feat2_mb", None) is None:
-            sl.feat2_mb = torch.empty((T, self._max_partial_range(sl), S2, self.C), dtype=sl.feat2.dtype, device=self.dev)
-        fm = sl.feat2_mb.view(-1)[:T * m * S2 * self.C].view(T, m, S2, self.C)
-        fm.copy_(sl.feat2[:T, a:b])
-        return fm.view(T * m, S2, self.C)
 
     def _sum_parts(self, parts, sec: slice):
         """self.grads[sec] = sum of the slices' gradient buckets over ``sec`` (one slice: its bucket IS self.grads)."""
@@ -1111,7 +1106,7 @@ class Worker(_SlicedActor):
     def update(self):
         T = self.T
         collective = collective_active(self.world, self.force_allreduce)
-        self._gather_slice_batches()
+        self._gather_columns()
         il_denoms = self._expert_counts() if self._il else None      # (the _fork() below orders the slice streams behind it)
         for _ in range(self.update_repeats):
             for (s0, s1, nmb_global) in self.minibatch_ranges():
@@ -1128,8 +1123,8 @@ class Worker(_SlicedActor):
                 for (sl, a, b) in parts:
                     with self._on(sl):
                         m = b - a
-                        feat, goal, masks, actions, logp, old_v, ret, nadv = self._gather_part(sl, a, b)
-                        feat2 = self._gather_feat2(sl, a, b)
+                        g = self.gather(sl, a, b)
+                        feat, feat2, masks = g["feat"], g.get("feat2"), g["masks"]
                         hv, dhv = sl.hv[:T * m], sl.dhv[:T * m]
                         # d(total)/d(hv) carries 1/B_part inside the loss kernel: rescale to the mean over the WHOLE
                         # local minibatch (m / nmb), then local_bsize / global_bsize (nmb / nmb_global: the sum of the
@@ -1138,19 +1133,16 @@ class Worker(_SlicedActor):
                         # (staggering the slices -- slice 1's forward starting when slice 0's is done, so that wide GEMMs
                         #  run beside the other slice's GRU recurrence -- was measured in round 3: 53 -> 58 ms per update;
                         #  the step kernels wait for CUs the GEMM workgroups hold)
-                        if self.pooled_net and not self.goal_ids:
-                            goal = None
-                        self.policy.forward(self.params, feat, goal, self.h_start[sl.o + a:sl.o + b], masks, T, m,
-                                            sl.ws_learn, hv=hv, feat2=feat2, prev_actions=self._gather_prev(sl, a, b),
-                                            **self._gather_side(sl, a, b))
+                        self.policy.forward(self.params, feat, g.get("goal"), self.h_start[sl.o + a:sl.o + b], masks, T, m,
+                                            sl.ws_learn, hv=hv, feat2=feat2, prev_actions=g.get("prev_actions"),
+                                            sensors=g.get("sensors"))
                         if self._ppo:
-                            ppo_loss_raw(hv, actions, logp, old_v, ret, nadv, self.A, grad_scale=grad_scale, dhv=dhv,
-                                         sums=sl.sums, scratch=sl.ppo_scratch)
+                            ppo_loss_raw(hv, g["actions"], g["logp"], g["old_values"], g["returns"], g["advantages"], self.A,
+                                         grad_scale=grad_scale, dhv=dhv, sums=sl.sums, scratch=sl.ppo_scratch)
                         if self._il:
                             # the kernel divides by the RANGE's normaliser (shared by the parts), so only local / global
                             # minibatch size is left to apply; after a PPO call the term is added to its dhv
-                            ex_a, ex_m = self._gather_expert(sl, a, b)
-                            imitation_loss_raw(hv, ex_a, ex_m, self.A, weight=self.il_weight,
+                            imitation_loss_raw(hv, g["expert_actions"], g["expert_mask"], self.A, weight=self.il_weight,
                                                grad_scale=(s1 - s0) / nmb_global, denom=il_denoms[(s0, s1)], dhv=dhv,
                                                sums=sl.il_sums, scratch=sl.il_scratch, accumulate=self._ppo)
                         sl.grads.zero_()

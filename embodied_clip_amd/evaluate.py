@@ -23,8 +23,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .engine import NavSyntheticEnv, SyntheticEnv, _SlicedActor, check_net, check_prev_actions, check_rgbd, check_rnn_layers, check_rnn_type
-from .episodes import EpisodeTracker, NavEpisodeTracker, category_names, nav_env_tensors
+from .engine import _SlicedActor
+from .episodes import category_names, nav_env_tensors
 
 
 class Evaluator(_SlicedActor):
@@ -43,17 +43,14 @@ class Evaluator(_SlicedActor):
     ``env.goals`` as the categories (``num_categories``, default the env's ``num_goals``; 0 with coordinate goals); the default
     env is then a ``NavSyntheticEnv`` and ``info()`` carries ``spl``, ``soft_spl``, ``dist_to_goal``, ``path_length``,
     ``no_path``.  The act loop does not change.  ``env_seed``: the seed of the env the evaluator builds itself (default
-    ``1000 + rank``, the ``Worker``'s).  ``depth=True``: the RGB-D agent of ``Worker(depth=True)`` -- a second feature ring per slice
-    for the depth tower, the dual-encoder policy (a checkpoint then carries 25 tensors); an ``env=`` must also have ``depth`` and
-    ``observe_depth()``; refused with the combinations ``engine.check_rgbd`` names.  With ``net="pooled", pooling="avgpool"`` it is
-    the agent of ``Worker(net="pooled", pooling="avgpool", depth=True)`` instead: one ``RN50Trunk.embed_rgbd`` call per slice and
-    step, no second ring, the RGB avgpool net's checkpoint.  ``prev_actions=E > 0`` /
-    ``prev_action_null_token``: the agent of ``Worker(prev_actions=E)`` -- every step reads the actions the step before selected
-    (zeros before the first); a checkpoint then carries one more tensor, and one without it is refused by name; ``ValueError``
-    with ``depth=True`` or ``zeroshot=True``.  ``rnn_type="LSTM"``: the agent of ``Worker(rnn_type="LSTM")`` -- the recurrent memory
-    is ``[N, 2 * hidden]`` rows ``[h | c]``; a checkpoint of the other cell is refused with the tensor's name and both shapes;
-    ``ValueError`` with ``depth=True`` or ``zeroshot=True``.  ``rnn_layers=L``: the agent of ``Worker(rnn_layers=L)`` -- the memory is
-    ``[N, L * SW]`` rows; a checkpoint of another depth is refused by tensor name; the same two ``ValueError``s."""
+    ``1000 + rank``, the ``Worker``'s).
+
+    The agent keywords (``encoder``, ``net``, ``pooling``, ``sensors``, ``goal_ids``, ``goal_in``, ``depth``, ``zeroshot``,
+    ``num_actions``, ``prev_actions``, ``prev_action_null_token``, ``rnn_type``, ``rnn_layers``, ``hidden``) are ``engine.Worker``'s:
+    the same agents (documented there), the same refusals before anything is built, the same checkpoints -- one of another net,
+    cell, depth or without the previous-action embedding is refused by tensor name.  An ``env=`` must serve what the agent reads:
+    ``depth`` / ``goal_frames`` on the device with ``observe_second()`` (``depth=True`` / ``net="two_view"``), ``sensors``
+    (``net="pooled"`` with sensors)."""
 
     def __init__(self, n_actors: int, T: int = 128, device="cuda:0", seed: int = 0, rank: int = 0, encoder: str = "rn50",
                  encoder_sd=None, policy_sd=None, checkpoint: Optional[str] = None, deterministic: bool = False,
@@ -64,32 +61,12 @@ class Evaluator(_SlicedActor):
                  prev_actions: int = 0, prev_action_null_token: bool = True, rnn_type: str = "GRU",
                  rnn_layers: int = 1, hidden: int = 512, net: str = "goal_encoder", pooling: str = "attnpool", sensors=(),
                  goal_ids: bool = True):
-        # net="pooled": the agent of Worker(net="pooled", ...) -- the same arguments, the same refusals; an env= must hold `sensors`
-        self.pooled_net, self.pooling, self.net_sensors = check_net(net, pooling, sensors, goal_ids, encoder, bool(depth), bool(zeroshot), goal_in)
-        self.two_view_net = net == "two_view"     # the agent of Worker(net="two_view"): an env= must hold `goal_frames` on the device
-        self.goal_ids = bool(goal_ids) and not self.two_view_net
-        if self.two_view_net and env is not None and (getattr(env, "goal_frames", None) is None or getattr(env, "host", False)):
-            raise ValueError("net='two_view': the env serves no goal-state views on the device (SyntheticEnv(..., goal_view=True) holds env.goal_frames)")
-        if self.net_sensors and env is not None and getattr(env, "sensors", None) is None:
-            raise ValueError("net='pooled' with sensors: the env serves no sensor vectors (SyntheticEnv(..., sensors=K) holds env.sensors)")
-        self.hidden_size = int(hidden)
-        two_tower = bool(depth) and not self.pooled_net     # (the pooled RGB-D agent's policy handle is the RGB pooled net's)
-        self.rnn_type = check_rnn_type(rnn_type, two_tower, bool(zeroshot))
-        self.rnn_layers = check_rnn_layers(rnn_layers, two_tower, bool(zeroshot))
-        if depth:       # the RGB-D agent (engine.Worker(depth=True)): the same refusals, before anything is built
-            check_rgbd(encoder, zeroshot, goal_in, bool(env is not None and getattr(env, "host", False)))
-            if env is not None and getattr(env, "depth", None) is None:
-                raise ValueError("depth=True: the env serves no depth frames (SyntheticEnv(..., depth=True) holds env.depth)")
-        self.prev_action_dims = check_prev_actions(prev_actions, two_tower, bool(zeroshot), 512 if self.two_view_net else 64)
-        self.prev_action_null = int(bool(prev_action_null_token)) if self.prev_action_dims else 0
-        self.depth = bool(depth)
-        self.lib = _lib.load()
-        self.zeroshot, self._text_sd, self._goal_tokens = zeroshot, text_sd, goal_tokens
-        assert not (goal_in and zeroshot), "coordinate goals go through the goal encoder, not the zero-shot fusion"
+        self._configure(encoder, net, pooling, sensors, goal_ids, goal_in, depth, zeroshot, num_actions, prev_actions,
+                        prev_action_null_token, rnn_type, rnn_layers, hidden, env=env)
+        self._text_sd, self._goal_tokens = text_sd, goal_tokens
         assert policy_sd is None or checkpoint is None, "policy_sd and checkpoint both name the weights"
         if sync_actions not in (False, True):
             raise ValueError("Evaluator: sync_actions is False or True (one vectorised env for all actors)")
-        self.goal_in, self._num_actions = goal_in, num_actions
         self.nav_metrics, self._num_categories, self._env_seed = nav_metrics, num_categories, env_seed
         if nav_metrics and env is not None:
             nav_env_tensors(env, False)     # an env that cannot be scored fails here, before anything is built
@@ -126,21 +103,11 @@ class Evaluator(_SlicedActor):
         self._values = torch.zeros((1, N), dtype=torch.float32, device=d)
         self.actions = self.logp = self.values = self.hv = None
         self._prev_row = self._actions[0]       # what the next step reads as its previous actions: the last step's row (zeros at first)
-        env_cls = NavSyntheticEnv if self.nav_metrics else SyntheticEnv
+        env_cls, ekw = self._env_recipe()
         env_seed = self._env_seed if self._env_seed is not None else 1000 + rank
-        dkw = dict(depth=True) if self.depth else {}
-        if self.net_sensors:
-            dkw.update(sensors=sum(self.net_sensors))
-        if self.two_view_net:
-            dkw.update(goal_view=True)
-        self.env = env if env is not None else env_cls(N, T, d, seed=env_seed, frames_u8=frames_u8, goal_in=self.goal_in, **dkw)
+        self.env = env if env is not None else env_cls(N, T, d, seed=env_seed, frames_u8=frames_u8, **ekw)
         assert (self.env.N, self.env.T) == (N, T), "the env's actor count and rollout length are the evaluator's"
-        if self.nav_metrics:
-            C = 0 if self.goal_in else (self._num_categories if self._num_categories is not None
-                                        else getattr(self.env, "num_goals", 12))
-            self.episodes = NavEpisodeTracker(N, d, num_categories=C, capacity=record_capacity)
-        else:
-            self.episodes = EpisodeTracker(N, d, capacity=record_capacity)
+        self.episodes = self._episode_tracker(self._num_categories, record_capacity)
         self._build_slices(n_actors, encs, pools, 2, 0, bool(self.env.host))
         self.seed = seed + 7919 * rank
         self.chunk = 0                  # chunks played so far (the sampling key's iteration; carries across run() calls)
@@ -160,18 +127,20 @@ class Evaluator(_SlicedActor):
         hv, actions, logp, values = self._hv[row][rs], self._actions[row][rs], self._logp[row][rs], self._values[row][rs]
         key = self.chunk * (self.T + 1) + t
         pa = self._prev_row[rs] if self.prev_action_dims else None
+        goal = self.env.goals[t][rs] if self._has_goal else None            # (as Worker._act_slice)
+        sens = self.env.sensors[t][rs] if self._has_sensors else None
         if self._act_fused:
-            self.policy.act(self.params, feat, self._goal(t, rs), h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
+            self.policy.act(self.params, feat, goal, h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
                             actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
-                            deterministic=self.deterministic, feat2=feat2, prev_actions=pa, **self._side(t, rs))
+                            deterministic=self.deterministic, feat2=feat2, prev_actions=pa, sensors=sens)
         elif self._act_wide:   # 8 to 256 actions: the wide heads launch selects (ec_policy_act_ex)
-            self.policy.act_ex(self.params, feat, self._goal(t, rs), h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
+            self.policy.act_ex(self.params, feat, goal, h_in[rs], self.env.masks[t][rs], n, sl.ws_act, hv, h_out[rs],
                                actions, logp, values, self.seed, key, o, reuse_tables=sl.act_tables_valid,
-                               deterministic=self.deterministic, feat2=feat2, prev_actions=pa, **self._side(t, rs))
+                               deterministic=self.deterministic, feat2=feat2, prev_actions=pa, sensors=sens)
         else:   # the switch off: the forward, then the stand-alone selection kernel
-            self.policy.forward(self.params, feat, self._goal(t, rs), h_in[rs], self.env.masks[t][rs], 1, n, sl.ws_act,
+            self.policy.forward(self.params, feat, goal, h_in[rs], self.env.masks[t][rs], 1, n, sl.ws_act,
                                 hv=hv, h_final=h_out[rs], for_backward=False, reuse_tables=sl.act_tables_valid, feat2=feat2,
-                                prev_actions=pa, **self._side(t, rs))
+                                prev_actions=pa, sensors=sens)
             if self.deterministic:
                 _lib.check(self.lib.ec_mode_actions(hv.data_ptr(), actions.data_ptr(), logp.data_ptr(), values.data_ptr(), n,
                                                     self.A, _lib.stream_ptr()), "ec_mode_actions")
@@ -215,11 +184,7 @@ class Evaluator(_SlicedActor):
                 self.k += 1
                 self._prev_row = self._actions[row]
             self._join()
-            if self.nav_metrics:
-                self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None),
-                                     *nav_env_tensors(self.env, self.episodes.C > 0))
-            else:
-                self.episodes.update(self.env.rewards, self.env.masks, getattr(self.env, "success", None))
+            self._update_episodes()
             self.chunk += 1
         return self.info()
 

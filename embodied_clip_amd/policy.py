@@ -46,12 +46,7 @@ class PolicyHandle:
         actor is then one row ``[h | c]`` of width ``state_width == 2 * hidden``, which is what ``h0`` / ``h_final`` /
         ``dh_final`` of every method below hold."""
         self.lib = _lib.load()
-        if rnn_type not in _lib.RNN_TYPES:
-            raise ValueError(f"rnn_type must be one of {sorted(_lib.RNN_TYPES)}, got {rnn_type!r}")
-        self.rnn_type = rnn_type
-        if not (isinstance(rnn_layers, int) and 1 <= rnn_layers <= 4):
-            raise ValueError(f"rnn_layers must be 1..4, got {rnn_layers!r}")
-        self.rnn_layers = rnn_layers
+        self.rnn_type, self.rnn_layers = self._check_rnn(rnn_type, rnn_layers)
         self.cfg = dict(in_channels=2048, spatial=7, hidden=512, goal_dims=32, num_goals=12, num_actions=6,
                         compress_hid=128, compress_out=32, comb_hid=128, comb_out=32, fusion=0, dual=0, goal_in=0,
                         prev_action_dims=0, prev_action_null=0)
@@ -67,10 +62,25 @@ class PolicyHandle:
         h = C.c_void_p()
         _lib.check(self.lib.ec_policy_create_rnn_layers(C.byref(h), C.byref(c), _lib.RNN_TYPES[rnn_type], rnn_layers),
                    "ec_policy_create_rnn_layers")
+        self._bind_layout(h, policy_param_shapes(**self.cfg, rnn_type=rnn_type, rnn_layers=rnn_layers), self.param_order)
+
+    @staticmethod
+    def _check_rnn(rnn_type, rnn_layers):
+        """The recurrent arguments of every handle constructor.  -> (rnn_type, rnn_layers)"""
+        if rnn_type not in _lib.RNN_TYPES:
+            raise ValueError(f"rnn_type must be one of {sorted(_lib.RNN_TYPES)}, got {rnn_type!r}")
+        if not (isinstance(rnn_layers, int) and 1 <= rnn_layers <= 4):
+            raise ValueError(f"rnn_layers must be 1..4, got {rnn_layers!r}")
+        return rnn_type, rnn_layers
+
+    def _bind_layout(self, h, shapes, param_order=None) -> None:
+        """Adopt the created ``ec_policy_t`` and read its flat layout: ``flat_size``, ``state_width`` (L * (H, or 2H on an LSTM
+        handle)) and every tensor's (offset, elements), checked against ``shapes`` (name -> shape, in flat order)."""
         self.h = h
         self.flat_size = self.lib.ec_policy_flat_size(h)
-        self.state_width = self.lib.ec_policy_state_width(h)      # L * (H, or 2H on an LSTM handle)
-        self.shapes = policy_param_shapes(**self.cfg, rnn_type=rnn_type, rnn_layers=rnn_layers)
+        self.state_width = self.lib.ec_policy_state_width(h)
+        self.shapes = shapes
+        self.param_order = tuple(shapes) if param_order is None else param_order
         self.offsets: "OrderedDict[str, Tuple[int, int]]" = OrderedDict()
         assert self.lib.ec_policy_num_param_tensors(h) == len(self.param_order)
         for i, name in enumerate(self.param_order):
@@ -90,8 +100,12 @@ class PolicyHandle:
         except Exception:
             pass
 
+    _net_name = None        # ("pooled" / "two-view" on the handles of the nets that have no goal table)
+
     def set_goal_table(self, table: torch.Tensor) -> None:
         """``fusion=1``: frozen goal table f32 [num_goals, in_channels] (CLIP text embeddings of the goal prompts)."""
+        if self._net_name:
+            raise ValueError(f"the {self._net_name} net has no goal table")
         assert table.dtype == torch.float32 and table.is_contiguous()
         assert tuple(table.shape) == (self.cfg["num_goals"], self.cfg["in_channels"]), table.shape
         self._goal_table = table          # the handle borrows the pointer: keep the tensor alive
@@ -130,6 +144,27 @@ class PolicyHandle:
             (prev_actions.dtype, tuple(prev_actions.shape), rows)
         return prev_actions.data_ptr()
 
+    def _outputs(self, hv, h_final, T: int, N: int, dev):
+        """``hv`` [T*N, A+1] and ``h_final`` [N, state_width] of a forward: the caller's, or fresh ones on ``dev``."""
+        if hv is None:
+            hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)
+        if h_final is None:
+            h_final = torch.empty((N, self.state_width), dtype=torch.float32, device=dev)
+        return hv, h_final
+
+    @staticmethod
+    def _forcing_args(expert_actions, expert_mask, force_p: float):
+        """The teacher-forcing triple that ends the one-call act entry points (zeros: no forcing)."""
+        if expert_actions is not None and force_p > 0.0:
+            return expert_actions.data_ptr(), expert_mask.data_ptr(), force_p
+        return 0, 0, 0.0
+
+    def memory_to_state(self, mem: torch.Tensor) -> torch.Tensor:
+        return memory_to_state(mem, self.rnn_type, self.rnn_layers)
+
+    def state_to_memory(self, state: torch.Tensor) -> torch.Tensor:
+        return state_to_memory(state, self.rnn_type, self.rnn_layers)
+
     def workspace_bytes(self, T: int, N: int, backward: bool) -> int:
         return self.lib.ec_policy_workspace_bytes(self.h, T, N, int(backward))
 
@@ -143,27 +178,29 @@ class PolicyHandle:
         return OrderedDict((n, flat[o:o + k].view(self.shapes[n])) for n, (o, k) in self.offsets.items())
 
     def forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv=None, h_final=None, for_backward: bool = True,
-                reuse_tables: bool = False, feat2=None, prev_actions=None):
+                reuse_tables: bool = False, feat2=None, prev_actions=None, sensors=None):
         """feat: bf16 or fp32 NHWC rows [T*N, S*S, C]; returns (hv [T*N, A+1], h_final [N, state_width]).
         ``for_backward=True`` (default) keeps every activation ``backward`` needs and wants a workspace of
         ``workspace_bytes(T, N, True)``; ``False`` is the inference-only act step (``workspace_bytes(T, N, False)``).
         The kernel plan follows this flag, never the size of ``ws``.  ``reuse_tables`` (inference only): the weight-derived
         tables a previous ``for_backward=False`` call left in THIS ``ws`` are still valid (same parameters: the later act
         steps of a rollout).  ``prev_actions`` (handles with ``prev_action_dims > 0``, and only those): int64 [T*N], row
-        ``t * N + n`` = the action actor ``n`` took at step ``t - 1``."""
+        ``t * N + n`` = the action actor ``n`` took at step ``t - 1``.  ``sensors`` (the pooled net's handle, and only that one): f32
+        ``[T*N, K]``; None on every other handle."""
         assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
         dev = flat_params.device
         with _lib.tensor_guard(flat_params):
             mode = 1 if for_backward else (2 if reuse_tables else 0)
-            return self._forward(flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, mode, feat2, prev_actions)
+            return self._forward(flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, mode, feat2, prev_actions, sensors)
 
     def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
-            first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None):
+            first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None, sensors=None):
         """The act step in one call (``ec_policy_act``): the T = 1 inference forward whose heads launch also samples
         ``actions`` / ``logp`` (and copies ``values``) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions``.
         ``deterministic=True`` (evaluation): the heads launch takes ``CategoricalDistr.mode()`` instead, the first maximal logit
         (``ec_policy_act_greedy``; ``seed`` / ``step`` / ``first_actor`` are not used) -- ``forward`` + ``ec_mode_actions``."""
         assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
+        assert sensors is None, "this handle has no sensors: pass sensors=None"
         if self.prev_action_dims:            # (one entry point serves every act step of such a handle)
             return self.act_ex(flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed, step, first_actor,
                                reuse_tables, feat2, deterministic, prev_actions=prev_actions)
@@ -180,16 +217,16 @@ class PolicyHandle:
 
     def act_ex(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
                first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, expert_actions=None,
-               expert_mask=None, force_p: float = 0.0, prev_actions=None):
+               expert_mask=None, force_p: float = 0.0, prev_actions=None, sensors=None):
         """The act step in one call for every handle, up to 256 actions (``ec_policy_act_ex``).  With more than 7 actions the
         heads launch of the wide action space computes the logits and selects (sample, or ``deterministic=True`` the first
         maximal logit) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions`` / ``ec_mode_actions`` on the
         ``hv`` it writes, bit for bit; with up to 7 it is ``act``.  ``expert_actions`` / ``expert_mask`` / ``force_p``: teacher
         forcing (``imitation.teacher_force``) in the same call -- inside the heads launch of a wide action space."""
         assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
+        assert sensors is None, "this handle has no sensors: pass sensors=None"
         gp = self._goal_ptr(goal, N)
         pp = self._prev_ptr(prev_actions, N)
-        forcing = expert_actions is not None and force_p > 0.0
         fn, name = (self.lib.ec_policy_act_pa, "ec_policy_act_pa") if pp else (self.lib.ec_policy_act_ex, "ec_policy_act_ex")
         with _lib.tensor_guard(flat_params):
             _lib.check(fn(
@@ -197,15 +234,13 @@ class PolicyHandle:
                 0 if self.goal_in else gp, gp if self.goal_in else 0, *((pp,) if pp else ()), self._state_ptr(h0, N, "h0"), masks.data_ptr(), N,
                 ws.data_ptr(), ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
                 logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
-                expert_actions.data_ptr() if forcing else 0, expert_mask.data_ptr() if forcing else 0,
-                force_p if forcing else 0.0, _lib.stream_ptr()), name)
+                *self._forcing_args(expert_actions, expert_mask, force_p), _lib.stream_ptr()), name)
         return hv, h_final
 
-    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None):
-        if hv is None:
-            hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)
-        if h_final is None:
-            h_final = torch.empty((N, self.state_width), dtype=torch.float32, device=dev)
+    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None,
+                 sensors=None):
+        assert sensors is None, "this handle has no sensors: pass sensors=None"
+        hv, h_final = self._outputs(hv, h_final, T, N, dev)
         self._state_ptr(h0, N, "h0")
         self._state_ptr(h_final, N, "h_final")
         if self.cfg["dual"]:       # RGB + depth: feat = the RGB features, feat2 = the depth features (same shape / dtype)
@@ -309,14 +344,12 @@ class PooledPolicyHandle(PolicyHandle):
     """``ec_policy_create_pooled``'s handle (``PolicyHandle.pooled``): ``forward`` / ``act`` take the embedding rows f32 ``[T*N, D]`` as
     ``feat`` and ``goal=`` (int64 ids, handles with ``num_goals > 0``), ``sensors=`` (f32 ``[T*N, K]``, handles with sensors),
     ``prev_actions=``; ``backward``, ``flatten``, ``views``, ``recurrent_section`` are the base class's."""
+    _net_name = "pooled"
 
     def __init__(self, embed_in: int, hidden: int = 512, num_goals: int = 12, sensors=(), num_actions: int = 6,
                  prev_action_dims: int = 0, prev_action_null: int = 1, rnn_type: str = "GRU", rnn_layers: int = 1, embed_dims: int = 32):
         self.lib = _lib.load()
-        if rnn_type not in _lib.RNN_TYPES:
-            raise ValueError(f"rnn_type must be one of {sorted(_lib.RNN_TYPES)}, got {rnn_type!r}")
-        if not (isinstance(rnn_layers, int) and 1 <= rnn_layers <= 4):
-            raise ValueError(f"rnn_layers must be 1..4, got {rnn_layers!r}")
+        self.rnn_type, self.rnn_layers = self._check_rnn(rnn_type, rnn_layers)
         sensors = tuple(int(k) for k in sensors)
         if len(sensors) > 3 or any(k < 1 for k in sensors) or sum(sensors) > 8:
             raise ValueError(f"at most 3 sensors of at least one float each, 8 floats in all, got {sensors!r}")
@@ -324,7 +357,6 @@ class PooledPolicyHandle(PolicyHandle):
             raise ValueError("the pooled net needs a goal: num_goals > 0 or at least one sensor")
         if not prev_action_dims:
             prev_action_null = 0
-        self.rnn_type, self.rnn_layers = rnn_type, rnn_layers
         self.sensors, self.K = sensors, sum(sensors)
         self.pooled_cfg = dict(embed_in=embed_in, hidden=hidden, num_goals=num_goals, sensors=sensors, num_actions=num_actions,
                                prev_action_dims=prev_action_dims, prev_action_null=prev_action_null, rnn_type=rnn_type,
@@ -339,30 +371,7 @@ class PooledPolicyHandle(PolicyHandle):
                            num_layers=rnn_layers)
         h = C.c_void_p()
         _lib.check(self.lib.ec_policy_create_pooled(C.byref(h), C.byref(c)), "ec_policy_create_pooled")
-        self.h = h
-        self.flat_size = self.lib.ec_policy_flat_size(h)
-        self.state_width = self.lib.ec_policy_state_width(h)
-        self.shapes = pooled_param_shapes(**self.pooled_cfg)
-        self.param_order = tuple(self.shapes)
-        self.offsets = OrderedDict()
-        assert self.lib.ec_policy_num_param_tensors(h) == len(self.param_order)
-        for i, name in enumerate(self.param_order):
-            off, num = C.c_size_t(), C.c_size_t()
-            _lib.check(self.lib.ec_policy_param_offset(h, i, C.byref(off), C.byref(num)))
-            n = 1
-            for d in self.shapes[name]:
-                n *= d
-            assert n == num.value, (name, n, num.value)
-            self.offsets[name] = (off.value, num.value)
-
-    def set_goal_table(self, table):
-        raise ValueError("the pooled net has no goal table")
-
-    def memory_to_state(self, mem: torch.Tensor) -> torch.Tensor:
-        return memory_to_state(mem, self.rnn_type, self.rnn_layers)
-
-    def state_to_memory(self, state: torch.Tensor) -> torch.Tensor:
-        return state_to_memory(state, self.rnn_type, self.rnn_layers)
+        self._bind_layout(h, pooled_param_shapes(**self.pooled_cfg))
 
     def _side_ptrs(self, feat, goal, sensors, prev_actions, rows: int):
         D = self.pooled_cfg["embed_in"]
@@ -380,23 +389,14 @@ class PooledPolicyHandle(PolicyHandle):
 
     def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None,
                  sensors=None):
-        if hv is None:
-            hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)
-        if h_final is None:
-            h_final = torch.empty((N, self.state_width), dtype=torch.float32, device=dev)
+        assert feat2 is None
+        hv, h_final = self._outputs(hv, h_final, T, N, dev)
         gp, sp, pp = self._side_ptrs(feat, goal, sensors, prev_actions, T * N)
         _lib.check(self.lib.ec_policy_forward_pooled(
             self.h, flat_params.data_ptr(), feat.data_ptr(), gp, sp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), T, N, ws.data_ptr(),
             ws.numel() * ws.element_size(), int(for_backward), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), _lib.stream_ptr()),
             "ec_policy_forward_pooled")
         return hv, h_final
-
-    def forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv=None, h_final=None, for_backward: bool = True,
-                reuse_tables: bool = False, feat2=None, prev_actions=None, sensors=None):
-        assert feat2 is None
-        with _lib.tensor_guard(flat_params):
-            mode = 1 if for_backward else (2 if reuse_tables else 0)
-            return self._forward(flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, flat_params.device, mode, None, prev_actions, sensors)
 
     def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
             first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None, sensors=None,
@@ -405,14 +405,12 @@ class PooledPolicyHandle(PolicyHandle):
         logit, optional teacher forcing) in one call, 2..256 actions."""
         assert feat2 is None
         gp, sp, pp = self._side_ptrs(feat, goal, sensors, prev_actions, N)
-        forcing = expert_actions is not None and force_p > 0.0
         with _lib.tensor_guard(flat_params):
             _lib.check(self.lib.ec_policy_act_pooled(
                 self.h, flat_params.data_ptr(), feat.data_ptr(), gp, sp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), N, ws.data_ptr(),
                 ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
                 logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
-                expert_actions.data_ptr() if forcing else 0, expert_mask.data_ptr() if forcing else 0, force_p if forcing else 0.0,
-                _lib.stream_ptr()), "ec_policy_act_pooled")
+                *self._forcing_args(expert_actions, expert_mask, force_p), _lib.stream_ptr()), "ec_policy_act_pooled")
         return hv, h_final
 
     act_ex = act
@@ -474,17 +472,14 @@ class TwoViewPolicyHandle(PolicyHandle):
     """``ec_policy_create_two_view``'s handle (``PolicyHandle.two_view``): ``forward`` / ``act`` / ``backward`` take the current
     view's features as ``feat`` and the goal view's as ``feat2``, both bf16 ``[T*N, S2, C]``, and ``prev_actions=``; ``goal`` is
     None.  ``flatten``, ``views``, ``recurrent_section`` are the base class's."""
+    _net_name = "two-view"
 
     def __init__(self, in_channels: int, hidden: int = 512, num_actions: int = 84, attn_hidden: int = 32, prev_action_dims: int = 0,
                  prev_action_null: int = 1, rnn_type: str = "LSTM", rnn_layers: int = 1, spatial: int = 7):
         self.lib = _lib.load()
-        if rnn_type not in _lib.RNN_TYPES:
-            raise ValueError(f"rnn_type must be one of {sorted(_lib.RNN_TYPES)}, got {rnn_type!r}")
-        if not (isinstance(rnn_layers, int) and 1 <= rnn_layers <= 4):
-            raise ValueError(f"rnn_layers must be 1..4, got {rnn_layers!r}")
+        self.rnn_type, self.rnn_layers = self._check_rnn(rnn_type, rnn_layers)
         if not prev_action_dims:
             prev_action_null = 0
-        self.rnn_type, self.rnn_layers = rnn_type, rnn_layers
         self.two_view_cfg = dict(in_channels=in_channels, hidden=hidden, num_actions=num_actions, attn_hidden=attn_hidden,
                                  prev_action_dims=prev_action_dims, prev_action_null=prev_action_null, rnn_type=rnn_type,
                                  rnn_layers=rnn_layers, spatial=spatial)
@@ -497,30 +492,7 @@ class TwoViewPolicyHandle(PolicyHandle):
                             num_layers=rnn_layers)
         h = C.c_void_p()
         _lib.check(self.lib.ec_policy_create_two_view(C.byref(h), C.byref(c)), "ec_policy_create_two_view")
-        self.h = h
-        self.flat_size = self.lib.ec_policy_flat_size(h)
-        self.state_width = self.lib.ec_policy_state_width(h)
-        self.shapes = two_view_param_shapes(**self.two_view_cfg)
-        self.param_order = tuple(self.shapes)
-        self.offsets = OrderedDict()
-        assert self.lib.ec_policy_num_param_tensors(h) == len(self.param_order)
-        for i, name in enumerate(self.param_order):
-            off, num = C.c_size_t(), C.c_size_t()
-            _lib.check(self.lib.ec_policy_param_offset(h, i, C.byref(off), C.byref(num)))
-            n = 1
-            for d in self.shapes[name]:
-                n *= d
-            assert n == num.value, (name, n, num.value)
-            self.offsets[name] = (off.value, num.value)
-
-    def set_goal_table(self, table):
-        raise ValueError("the two-view net has no goal table")
-
-    def memory_to_state(self, mem: torch.Tensor) -> torch.Tensor:
-        return memory_to_state(mem, self.rnn_type, self.rnn_layers)
-
-    def state_to_memory(self, state: torch.Tensor) -> torch.Tensor:
-        return state_to_memory(state, self.rnn_type, self.rnn_layers)
+        self._bind_layout(h, two_view_param_shapes(**self.two_view_cfg))
 
     def _views_ptrs(self, feat, feat2, goal, prev_actions, rows: int):
         n = rows * self.cfg["spatial"] ** 2 * self.cfg["in_channels"]
@@ -530,11 +502,10 @@ class TwoViewPolicyHandle(PolicyHandle):
                 "feat (current view) and feat2 (goal view): bf16 [rows, S2, C]"
         return feat.data_ptr(), feat2.data_ptr(), self._prev_ptr(prev_actions, rows)
 
-    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None):
-        if hv is None:
-            hv = torch.empty((T * N, self.A + 1), dtype=torch.float32, device=dev)
-        if h_final is None:
-            h_final = torch.empty((N, self.state_width), dtype=torch.float32, device=dev)
+    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None,
+                 sensors=None):
+        assert sensors is None, "this handle has no sensors: pass sensors=None"
+        hv, h_final = self._outputs(hv, h_final, T, N, dev)
         up, wp, pp = self._views_ptrs(feat, feat2, goal, prev_actions, T * N)
         _lib.check(self.lib.ec_policy_forward_two_view(
             self.h, flat_params.data_ptr(), up, wp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), T, N, ws.data_ptr(),
@@ -544,18 +515,17 @@ class TwoViewPolicyHandle(PolicyHandle):
 
     def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
             first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None,
-            expert_actions=None, expert_mask=None, force_p: float = 0.0):
+            expert_actions=None, expert_mask=None, force_p: float = 0.0, sensors=None):
         """``ec_policy_act_two_view``: the T = 1 inference forward and the selection (sample, ``deterministic=True`` the first maximal
         logit, optional teacher forcing) in one call, 2..256 actions."""
+        assert sensors is None, "this handle has no sensors: pass sensors=None"
         up, wp, pp = self._views_ptrs(feat, feat2, goal, prev_actions, N)
-        forcing = expert_actions is not None and force_p > 0.0
         with _lib.tensor_guard(flat_params):
             _lib.check(self.lib.ec_policy_act_two_view(
                 self.h, flat_params.data_ptr(), up, wp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), N, ws.data_ptr(),
                 ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
                 logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
-                expert_actions.data_ptr() if forcing else 0, expert_mask.data_ptr() if forcing else 0, force_p if forcing else 0.0,
-                _lib.stream_ptr()), "ec_policy_act_two_view")
+                *self._forcing_args(expert_actions, expert_mask, force_p), _lib.stream_ptr()), "ec_policy_act_two_view")
         return hv, h_final
 
     act_ex = act
@@ -842,14 +812,12 @@ class _ResnetTensorGoalActorCritic(_FlatBucketActorCritic):
     @staticmethod
     def memory_to_state(mem: torch.Tensor) -> torch.Tensor:
         """Upstream's memory tensor ``[L, N, H]`` (L = 2 on an LSTM: h then c) -> the handle's state rows ``[N, L * H]``."""
-        L, N, H = mem.shape
-        return mem.permute(1, 0, 2).reshape(N, L * H).contiguous()
+        return memory_to_state(mem, "GRU", mem.shape[0])      # (one layer: an LSTM's [h; c] is laid out as two GRU layers' rows)
 
     @staticmethod
     def state_to_memory(state: torch.Tensor, L: int) -> torch.Tensor:
         """The handle's state rows ``[N, L * H]`` -> upstream's memory tensor ``[L, N, H]``."""
-        N = state.shape[0]
-        return state.view(N, L, -1).permute(1, 0, 2).contiguous()
+        return state_to_memory(state, "GRU", L)
 
     @property
     def is_blind(self) -> bool:
