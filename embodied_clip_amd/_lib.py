@@ -15,6 +15,32 @@ LIB_PATH = os.environ.get("EC_AMD_LIB") or os.path.join(_HERE, "lib", "libec_amd
 
 c_void_p, c_int, c_size_t, c_float = C.c_void_p, C.c_int, C.c_size_t, C.c_float
 
+# ---- the policy entry points' argument lists, built from groups that are each stated once (include/ec_amd.h; the counts and
+# classes are held to the header by tests/test_cabi_signatures.py)
+_P = c_void_p
+_FEAT = [_P, _P, c_int]                           # feat, feat2, feat_bf16
+_STATE = [_P, _P]                                 # h0, masks
+_NW = [c_int, _P, c_size_t, c_int]                # N, workspace, ws_bytes, mode flag (for_backward / reuse_tables)
+_ACT_OUT = [_P, _P, _P]                           # actions, logp, values
+_KEY = [C.c_uint64, C.c_uint64, c_int]            # seed, step, first_actor
+_SELECT = [c_int] + _KEY + [_P, _P, c_float]      # greedy, the key, then the forcing block: expert_actions, expert_mask, force_p
+
+
+def _policy_fwd(lead):
+    """handle, params | the face's leading arguments | h0, masks | T N workspace ... | hv, h_final | stream"""
+    return c_int, [_P, _P] + lead + _STATE + [c_int] + _NW + [_P, _P] + [_P]
+
+
+def _policy_act(lead, select):
+    """... | N workspace ... | hv, h_final | the act outputs | the selection block | stream"""
+    return c_int, [_P, _P] + lead + _STATE + _NW + [_P, _P] + _ACT_OUT + select + [_P]
+
+
+def _policy_bwd(lead, events=0):
+    """handle, params | features | masks | T N workspace ws_bytes | dhv, dh_final, grads | [event] | stream"""
+    return c_int, [_P, _P] + lead + [_P] + [c_int, c_int, _P, c_size_t] + [_P, _P, _P] + [_P] * events + [_P]
+
+
 # name -> (restype, argtypes); must list every symbol include/ec_amd.h declares
 # (tests/test_cabi_symbols.py parses the header and checks both directions).
 SIGNATURES = {
@@ -100,29 +126,19 @@ SIGNATURES = {
     "ec_policy_flat_size": (c_size_t, [c_void_p]),
     "ec_policy_param_offset": (c_int, [c_void_p, c_int, C.POINTER(c_size_t), C.POINTER(c_size_t)]),
     "ec_policy_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
-    "ec_policy_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                  c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
-    "ec_policy_forward2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                   c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
-    "ec_policy_act": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
-                      + [C.c_uint64, C.c_uint64, c_int, c_void_p]),
-    "ec_policy_forward_vec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                      c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
-    "ec_policy_act_vec": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
-                          + [C.c_uint64, C.c_uint64, c_int, c_void_p]),
+    "ec_policy_forward": _policy_fwd([_P, c_int, _P]),   # feat, feat_bf16, goal
+    "ec_policy_forward2": _policy_fwd(_FEAT + [_P]),          # ..., goal
+    "ec_policy_act": _policy_act(_FEAT + [_P], _KEY),
+    "ec_policy_forward_vec": _policy_fwd(_FEAT + [_P]),       # ..., goal_vec
+    "ec_policy_act_vec": _policy_act(_FEAT + [_P], _KEY),
     # evaluation (readme_files/baselines_robothor_objectnav.md:66-68 `--eval`, baselines_habitat.md:89-97 `--run-type eval`,
     # zeroshot_objectnav.md:20-27): the act entry points without seed / step / first_actor -- CategoricalDistr.mode()
-    "ec_policy_act_greedy": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
-                             + [c_void_p]),
-    "ec_policy_act_vec_greedy": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
-                                 + [c_void_p]),
-    "ec_policy_backward2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t,
-                                    c_void_p, c_void_p, c_void_p, c_void_p]),
-    "ec_policy_backward3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ec_policy_act_greedy": _policy_act(_FEAT + [_P], []),
+    "ec_policy_act_vec_greedy": _policy_act(_FEAT + [_P], []),
+    "ec_policy_backward2": _policy_bwd(_FEAT),
+    "ec_policy_backward3": _policy_bwd(_FEAT, events=1),
     "ec_policy_set_goal_table": (c_int, [c_void_p, c_void_p]),
-    "ec_policy_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t,
-                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ec_policy_backward": _policy_bwd([_P, c_int]),
     "ec_gae": (c_int, [c_void_p] * 7 + [c_int, c_int, c_float, c_float, c_float, c_void_p]),
     "ec_ppo_loss": (c_int, [c_void_p] * 8 + [C.c_long, c_int, c_float, c_float, c_float, c_float, c_void_p]),
     "ec_ppo_loss_ex": (c_int, [c_void_p] * 8 + [C.c_long, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p]),
@@ -163,17 +179,15 @@ SIGNATURES = {
     # wide action spaces (up to 256 actions): heads + selection in one launch, the act step for every handle, the PPO loss
     "ec_heads_wide": (c_int, [c_void_p] * 6 + [C.c_long, c_int, c_int] + [c_void_p] * 3 + [c_int, C.c_uint64, C.c_uint64, c_int]
                       + [c_void_p] * 2 + [c_float, c_void_p]),
-    "ec_policy_act_ex": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
-                         + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_policy_act_ex": _policy_act(_FEAT + [_P, _P], _SELECT),   # ..., goal, goal_vec
     "ec_ppo_loss_wide_scratch_doubles": (c_int, []),
     "ec_ppo_loss_wide": (c_int, [c_void_p] * 9 + [C.c_long, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p]),
     # previous-action embedding (the kernels alone): the weight-derived table, its gather-add onto gi, the binned ordered gradient
     "ec_prev_action_table": (c_int, [c_void_p, c_void_p, C.c_long, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ec_prev_action_add": (c_int, [c_void_p] * 4 + [c_int, c_int, C.c_long, c_int, c_void_p]),
     "ec_prev_action_grad_scratch_floats": (c_size_t, [C.c_long, c_int, c_int, c_int]),
-    "ec_policy_forward_pa": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 3),
-    "ec_policy_act_pa": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
-                         + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_policy_forward_pa": _policy_fwd(_FEAT + [_P, _P, _P]),   # ..., goal, goal_vec, prev_actions
+    "ec_policy_act_pa": _policy_act(_FEAT + [_P, _P, _P], _SELECT),
     "ec_prev_action_grad": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p, c_void_p, C.c_long, c_int] + [c_void_p] * 3
                             + [C.c_long, c_int, c_int, c_void_p]),
     # the recurrent cell: handles with an LSTM core (state rows [h | c] of width 2H), and the LSTM step kernels alone
@@ -190,9 +204,8 @@ SIGNATURES = {
     # the pooled-embedding net (habitat-lab's PointNavResNetNet over one pooled CLIP vector per frame) and its two act-step kernels alone
     "ec_policy_create_pooled": (c_int, [C.POINTER(c_void_p), c_void_p]),
     "ec_policy_is_pooled": (c_int, [c_void_p]),
-    "ec_policy_forward_pooled": (c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 3),
-    "ec_policy_act_pooled": (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
-                             + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_policy_forward_pooled": _policy_fwd([_P] * 4),   # embed, goal, sensors, prev_actions
+    "ec_policy_act_pooled": _policy_act([_P] * 4, _SELECT),
     "ec_pooled_fc_act": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     "ec_pooled_step0_fwd": (c_int, [c_int, c_void_p, C.c_long] + [c_void_p] * 7 + [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                     c_int, c_void_p, C.c_long, c_void_p, c_void_p, C.c_long, c_void_p, C.c_long, c_void_p, C.c_long, c_int,
@@ -200,9 +213,8 @@ SIGNATURES = {
     # the two-view rearrangement net (ResNetRearrangeActorCriticRNN over two frozen CLIP maps per frame) and its front's kernels alone
     "ec_policy_create_two_view": (c_int, [C.POINTER(c_void_p), c_void_p]),
     "ec_policy_is_two_view": (c_int, [c_void_p]),
-    "ec_policy_forward_two_view": (c_int, [c_void_p] * 7 + [c_int, c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 3),
-    "ec_policy_act_two_view": (c_int, [c_void_p] * 7 + [c_int, c_void_p, c_size_t, c_int] + [c_void_p] * 5
-                               + [c_int, C.c_uint64, C.c_uint64, c_int] + [c_void_p] * 2 + [c_float, c_void_p]),
+    "ec_policy_forward_two_view": _policy_fwd([_P] * 3),   # feat, feat2, prev_actions
+    "ec_policy_act_two_view": _policy_act([_P] * 3, _SELECT),
     "ec_two_view_workspace_bytes": (c_size_t, [C.c_long] + [c_int] * 5),
     "ec_two_view_fwd": (c_int, [c_void_p] * 9 + [C.c_long] + [c_int] * 4 + [c_void_p, c_size_t, c_int, c_void_p]),
     "ec_two_view_bwd": (c_int, [c_void_p] * 10 + [C.c_long] + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),

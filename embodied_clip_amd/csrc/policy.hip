@@ -1499,25 +1499,48 @@ constexpr int P_COUNT_SINGLE = P_BC + 1, P_COUNT_DUAL = P_B4D + 1, P_COUNT_VEC =
 
 struct ec_policy {
     ec_policy_cfg c;
-    size_t off[P_COUNT], num[P_COUNT], total;
-    int order[P_COUNT], ntensors;        // the flat buffer's tensor order (what ec_policy_param_offset's idx counts)
+    size_t off[P_COUNT] = {}, total = 0;
+    // The flat buffer's tensors in flat order -- what ec_policy_param_offset's idx counts -- written by put() alone, which every
+    // constructor calls tensor by tensor in that order.  count: ec_policy_num_param_tensors; slots >= count: the indices the lookup
+    // answers (ec_policy_create_rnn_layers says which handle has more of them than tensors)
+    struct Tensor { size_t off, num; };
+    Tensor table[P_COUNT + 4 * (EC_RNN_MAX_LAYERS - 1)] = {};
+    int count = 0, slots = 0;
+    // `n` floats behind everything put so far, 16-byte aligned; -> their offset.  listed = false: a part this handle does not
+    // have (n = 0) -- it gets the offset, and no index
+    size_t put(size_t n, bool listed = true) {
+        const size_t at = total;
+        if (listed) table[slots++] = Tensor{at, n};
+        total += (n + 3) / 4 * 4;
+        return at;
+    }
     const float* goal_table = nullptr;   // fusion == 1: borrowed f32 [num_goals, in_channels]
     int rnn = EC_RNN_GRU;                // the recurrent cell (ec_policy_create_rnn)
     // recurrent layers (ec_policy_create_rnn_layers).  Layer l >= 1 owns weight_ih_l{l} [G, H], weight_hh_l{l} [G, H], bias_ih_l{l},
-    // bias_hh_l{l}: uoff / unum [l - 1][0..3], behind every other tensor of the flat order (indices nbase, nbase + 1, ...)
-    int layers = 1, nbase = 0;
-    size_t uoff[EC_RNN_MAX_LAYERS - 1][4] = {}, unum[EC_RNN_MAX_LAYERS - 1][4] = {};
+    // bias_hh_l{l}: uoff [l - 1][0..3], behind every other tensor of the flat order
+    int layers = 1;
+    size_t uoff[EC_RNN_MAX_LAYERS - 1][4] = {};
+    // The part of the flat order that every handle shares (c, rnn and layers are set): weight_ih_l0 [G, in0], weight_hh_l0,
+    // bias_ih_l0, bias_hh_l0, the actor's weight and bias, the critic's; the previous-action table of a handle that has one;
+    // then layer 1, 2, ...: weight_ih, weight_hh, bias_ih, bias_hh each
+    void put_core(size_t in0) {
+        const size_t H = c.hidden, A = c.num_actions, E = c.prev_action_dims, GW = (rnn == EC_RNN_LSTM ? 4 : 3) * H;
+        const size_t n8[8] = {GW * in0, GW * H, GW, GW, A * H, A, H, 1}, un[4] = {GW * H, GW * H, GW, GW};
+        for (int k = 0; k < 8; ++k) off[P_WIH + k] = put(n8[k]);
+        off[P_PAE] = put((A + c.prev_action_null) * E, E != 0);
+        for (int l = 1; l < layers; ++l)
+            for (int k = 0; k < 4; ++k) uoff[l - 1][k] = put(un[k]);
+    }
     // The pooled-embedding net (ec_policy_create_pooled).  Its plan is the fusion handle's -- no compressor, no combiner, the
     // recurrent core reads a [T*N, in_channels] matrix -- with in_channels = hidden: that matrix is v = ReLU(visual_fc(e)).
-    // Tensors in front of weight_ih_l0, index into off / num: visual_fc weight, bias; the goal-id embedding; sensor i's weight, bias
+    // Tensors in front of weight_ih_l0, index into off: visual_fc weight, bias; the goal-id embedding; sensor i's weight, bias
     struct Pooled {
         bool on = false;
         int D = 0, ed = 0, ids = 0, ns = 0, k[3] = {0, 0, 0}, K = 0;   // ids: 1 with a goal-id embedding; K = sum k
-        int npre = 0;                                                  // tensors in front of weight_ih_l0
-        size_t off[9] = {}, num[9] = {};
+        size_t off[9] = {};
         int side() const { return ed * (ids + ns); }                   // columns of weight_ih_l0 between v's and the previous action's
         // The two-view rearrangement net (ec_policy_create_two_view): the pooled plan from v onwards, with two_view.hip's trainable
-        // front in place of visual_fc.  off / num [TV_WE .. TV_B2]: its six tensors; no goal-id embedding, no sensors, D unused
+        // front in place of visual_fc.  off [TV_WE .. TV_B2]: its six tensors; no goal-id embedding, no sensors, D unused
         bool tv = false;
         int tvC = 0, tvS2 = 0, tvA1 = 0;
     } pl;
@@ -1705,7 +1728,7 @@ enum class Gi { act7, act8, split_parts, plain };                // GRU input pr
 enum class Wih { plain, perm_learn, perm_act };                  // weight_ih as stored / re-ordered per learn pass / per act-table build
 enum class Step { gemm_gates, fused32, fused16 };                // a recurrence step: GEMM + gate kernel / 32-tile / 16-tile fused kernel
 enum class Cell { gru, lstm };                                   // the recurrent cell (lstm.hip's kernels: always the 32-tile ones)
-enum { PL_FCW, PL_FCB, PL_GEMB, PL_SW0, PL_SB0 };                // ec_policy::Pooled::off / num (sensor i: PL_SW0 + 2 i, PL_SB0 + 2 i)
+enum { PL_FCW, PL_FCB, PL_GEMB, PL_SW0, PL_SB0 };                // ec_policy::Pooled::off (sensor i: PL_SW0 + 2 i, PL_SB0 + 2 i)
 enum { TV_WE, TV_BE, TV_WA, TV_BA, TV_W2, TV_B2, TV_NPRE };      // ... of a two-view handle
 constexpr int PA_TABLE_MAX_E = 64;                               // widest previous-action embedding of prev_action.hip's table / chain kernels
 
@@ -2332,72 +2355,133 @@ bool tables_reusable(const ec_policy* h, const void* workspace, const Plan& p, i
     return false;
 }
 
-// the pooled-embedding net's entry points: feat = the embedding rows, and the sensor floats; the two-view net's (tv): feat, feat2 = u, w
-struct PooledIn { const float* sensors; bool tv = false; };
+// What one forward or act call is given.  Every exported forward / act function fills one record and hands it on; nothing
+// between the C ABI and the stages of Fwd takes these one by one.  A plain aggregate on the caller's stack: no allocation, no lock.
+enum class Face { tensor, tensor_pa, pooled, two_view };     // the group of entry points; a handle answers exactly one (face_of)
+struct Call {
+    Face face = Face::tensor;
+    const float* params = nullptr;
+    const void *feat = nullptr, *feat2 = nullptr;             // pooled: feat = the embedding rows; two_view: the views u, w
+    int feat_bf16 = 0;
+    const int64_t* goal = nullptr;
+    const float* goal_vec = nullptr;
+    const int64_t* prev_actions = nullptr;
+    const float *sensors = nullptr, *h0 = nullptr, *masks = nullptr;
+    int T = 1, N = 0;
+    void* workspace = nullptr;
+    size_t ws_bytes = 0;
+    int mode = EC_POLICY_INFER;
+    float *hv = nullptr, *h_final = nullptr;
+    SampleArgs smp{};                   // an act call: the selection; seed / step / first_actor as the caller gave them
+    const ForceArgs* force = nullptr;   // the one-call act step of every handle (ec_policy_act_ex and after); nullptr: the narrow entry points
+    ec_stream_t stream = nullptr;
+};
+inline int act_mode(int reuse_tables) { return reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER; }
 
-int policy_forward_impl(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16, const int64_t* goal,
-                        const float* goal_vec, const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int mode, float* hv,
-                        float* h_final, const SampleArgs& smp, ec_stream_t stream, const ForceArgs* wide = nullptr,
-                        const int64_t* prev_actions = nullptr, bool pa_entry = false, const PooledIn* pin = nullptr) {
-    if (!h || !params || !feat || !h0 || !masks || !workspace || !hv) return EC_ERR_ARG;
-    if ((pin != nullptr) != h->pl.on) return EC_ERR_ARG;          // the pooled-embedding net has entry points of its own
-    if (pin && pin->tv != h->pl.tv) return EC_ERR_ARG;            // ... and so has the two-view net
-    if (pin && pin->tv) {
-        if (!feat2 || goal || goal_vec || pin->sensors || (prev_actions != nullptr) != (h->c.prev_action_dims > 0)) return EC_ERR_ARG;
-        if ((((uintptr_t)feat | (uintptr_t)feat2) & 15) != 0) return EC_ERR_ARG;
-    } else if (pin) {
-        // a NULL argument matches a part the handle does not have, and the reverse
-        if ((goal != nullptr) != (h->pl.ids != 0) || (pin->sensors != nullptr) != (h->pl.ns > 0) ||
-            (prev_actions != nullptr) != (h->c.prev_action_dims > 0) || goal_vec || feat2 || feat_bf16)
-            return EC_ERR_ARG;
-        if (((uintptr_t)feat & 15) != 0) return EC_ERR_ARG;
-    } else {
-    // previous-action embedding: the _pa entry points on such a handle, with the actions; every other pairing is refused
-    if (pa_entry != (h->c.prev_action_dims > 0) || (pa_entry && !prev_actions)) return EC_ERR_ARG;
-    if (h->c.goal_in > 0 ? (!goal_vec || goal) : (!goal || goal_vec)) return EC_ERR_ARG;   // the entry point of the handle's goal type
-    if (h->c.dual && !feat2) return EC_ERR_ARG;
+Face face_of(const ec_policy* h) {
+    return h->pl.tv ? Face::two_view : h->pl.on ? Face::pooled : h->c.prev_action_dims > 0 ? Face::tensor_pa : Face::tensor;
+}
+// more than 7 actions: heads and selection (and forcing) are wide_actions.hip's one launch
+bool wide_heads(const ec_policy* h) { return h->c.num_actions + 1 > 8; }
+
+// Every rule by which a forward (and the forward of an act call) is accepted, but the workspace size, which takes the plan.
+// One rule per line; the order is the precedence of the codes.
+int check_call(const ec_policy* h, const Call& c) {
+    if (!h || !c.params || !c.feat || !c.h0 || !c.masks || !c.workspace || !c.hv) return EC_ERR_ARG;
+    if (c.face != face_of(h)) return EC_ERR_ARG;              // each kind of handle has entry points of its own
+    const bool tensor = c.face == Face::tensor || c.face == Face::tensor_pa, pooled = c.face == Face::pooled, tv = c.face == Face::two_view;
+    // a NULL argument matches a part the handle does not have, and the reverse
+    if ((c.prev_actions != nullptr) != (h->c.prev_action_dims > 0)) return EC_ERR_ARG;
+    if (tensor && (h->c.goal_in > 0 ? (!c.goal_vec || c.goal) : (!c.goal || c.goal_vec))) return EC_ERR_ARG;   // the handle's goal type
+    if (tensor && h->c.dual && !c.feat2) return EC_ERR_ARG;
+    if (pooled && ((c.goal != nullptr) != (h->pl.ids != 0) || (c.sensors != nullptr) != (h->pl.ns > 0))) return EC_ERR_ARG;
+    if (pooled && (c.goal_vec || c.feat2 || c.feat_bf16)) return EC_ERR_ARG;
+    if (tv && (!c.feat2 || c.goal || c.goal_vec || c.sensors)) return EC_ERR_ARG;
+    if (!tensor && ((uintptr_t)c.feat & 15) != 0) return EC_ERR_ARG;                                           // (read as 16-byte vectors)
+    if (tv && ((uintptr_t)c.feat2 & 15) != 0) return EC_ERR_ARG;
+    if (c.T <= 0 || c.N <= 0) return EC_ERR_SHAPE;
+    if (c.mode < 0 || c.mode > EC_POLICY_INFER_REUSE) return EC_ERR_ARG;
+    return EC_OK;
+}
+
+// The rules of an act call that come in front of check_call's.  Pinned as they are: without a handle the narrow entry points
+// answer EC_ERR_UNSUPPORTED and the others EC_ERR_ARG, and only the others look at first_actor.
+int check_act(const ec_policy* h, const Call& c) {
+    const SampleArgs& s = c.smp;
+    if (!c.force) {      // ec_policy_act, _vec, _greedy, _vec_greedy: plain tensor handles, the one-wave-per-row heads launch
+        if (!s.actions || !s.logp || (h && face_of(h) != Face::tensor)) return EC_ERR_ARG;
+        if (!h || wide_heads(h)) return EC_ERR_UNSUPPORTED;
+        return EC_OK;
     }
-    if (T <= 0 || N <= 0) return EC_ERR_SHAPE;
-    if (mode < 0 || mode > EC_POLICY_INFER_REUSE) return EC_ERR_ARG;
-    const Plan p = make_plan(h, T, N, mode, feat_bf16 != 0);
-    if (ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
-    Fwd f(h, p, params, workspace, stream);
-    f.reuse = tables_reusable(h, workspace, p, mode);
-    if (pin) {
-        f.prev = (const long long*)prev_actions; f.masks_all = masks;
+    const ForceArgs& f = *c.force;
+    if (!h || !s.actions || !s.logp) return EC_ERR_ARG;
+    if (c.face != face_of(h)) return EC_ERR_ARG;
+    if (c.face == Face::tensor_pa && !c.prev_actions) return EC_ERR_ARG;
+    if ((f.expert != nullptr) != (f.mask != nullptr)) return EC_ERR_ARG;
+    if (!(f.p >= 0.f && f.p <= 1.f)) return EC_ERR_ARG;       // (NaN included)
+    if (!f.expert && f.p != 0.f) return EC_ERR_ARG;
+    if (f.expert && s.greedy) return EC_ERR_ARG;              // forcing belongs to the sampling act step
+    if (h->c.num_actions > 256) return EC_ERR_UNSUPPORTED;
+    if (s.first_actor < 0) return EC_ERR_SHAPE;
+    return EC_OK;
+}
+
+int policy_forward_impl(const ec_policy_t* h, const Call& c) {
+    RC(check_call(h, c));
+    const Plan p = make_plan(h, c.T, c.N, c.mode, c.feat_bf16 != 0);
+    if (c.ws_bytes < p.w.end * 4) return EC_ERR_WORKSPACE;
+    const ForceArgs* wide = (c.force && wide_heads(h)) ? c.force : nullptr;
+    const float *h0 = c.h0, *masks = c.masks;
+    float *hv = c.hv, *h_final = c.h_final;
+    Fwd f(h, p, c.params, c.workspace, c.stream);
+    f.reuse = tables_reusable(h, c.workspace, p, c.mode);
+    f.prev = (const long long*)c.prev_actions; f.masks_all = masks;
+    if (h->pl.on) {
         f.pact = p.pact && h_final && h_final != h0;
-        if (pin->tv) RC(f.two_view_front(feat, feat2));
-        else RC(f.pooled_front((const float*)feat, (const long long*)goal, pin->sensors));
+        if (h->pl.tv) RC(f.two_view_front(c.feat, c.feat2));
+        else RC(f.pooled_front((const float*)c.feat, (const long long*)c.goal, c.sensors));
         if (f.pact) {
             f.pooled_act_recurrence(h0, masks, h_final);
-            RC(f.heads(f.hs_top(), hv, nullptr, smp, wide));
+            RC(f.heads(f.hs_top(), hv, nullptr, c.smp, wide));
             EC_CHECK_LAUNCH();
             return EC_OK;
         }
     } else {
-    if (p.vec) RC(f.goal_rows(goal_vec));
-    else RC(f.goal_and_fusion(feat, goal));
-    if (!h->c.fusion)
-        for (int sidx = 0; sidx < p.g.nstream; ++sidx)   // dual encoder: the RGB stream, then the depth stream (own weights, own activations)
-            RC(f.encoder_stream(sidx, sidx ? feat2 : feat));
-    if (p.g.E) { f.prev = (const long long*)prev_actions; f.masks_all = masks; RC(f.prev_action_tables()); }
-    RC(f.input_projection());
+        if (p.vec) RC(f.goal_rows(c.goal_vec));
+        else RC(f.goal_and_fusion(c.feat, c.goal));
+        if (!h->c.fusion)
+            for (int sidx = 0; sidx < p.g.nstream; ++sidx)   // dual encoder: the RGB stream, then the depth stream (own weights, own activations)
+                RC(f.encoder_stream(sidx, sidx ? c.feat2 : c.feat));
+        if (p.g.E) RC(f.prev_action_tables());
+        RC(f.input_projection());
     }
     const bool lstm = p.cell == Cell::lstm;   // (the heads read the dense history; recurrence_lstm leaves the [h | c] rows in h_final)
     float* hs = (!lstm && p.hs_direct && h_final && h_final != h0) ? h_final : f.ws + p.w.hs;
     if (p.g.L > 1) {       // a multi-layer core leaves every layer's state in h_final itself; the heads read the top layer's history
         hs = f.hs_top();
         RC(f.recurrence_layers(h0, masks, h_final));
-        RC(f.heads(hs, hv, nullptr, smp, wide));
+        RC(f.heads(hs, hv, nullptr, c.smp, wide));
         EC_CHECK_LAUNCH();
         return EC_OK;
     }
     if (lstm) f.state_out = h_final;
     f.lay = f.layer(0);
     RC(f.recurrence(h0, masks, hs));
-    RC(f.heads(hs, hv, lstm ? nullptr : h_final, smp, wide));
+    RC(f.heads(hs, hv, lstm ? nullptr : h_final, c.smp, wide));
     EC_CHECK_LAUNCH();
     return EC_OK;
+}
+
+// An act call: the T = 1 inference forward whose heads launch selects.  More than 7 actions: the stages in front as they are,
+// then the wide heads launch with the selection (and the forcing) in it; up to 7: the one-wave-per-row heads launch, then
+// ec_teacher_force's.
+int policy_act(const ec_policy_t* h, Call c) {
+    RC(check_act(h, c));
+    if (c.smp.greedy) { c.smp.seed = 0; c.smp.step = 0; c.smp.first_actor = 0; }     // (the mode does not read them)
+    RC(policy_forward_impl(h, c));
+    if (!c.force || !c.force->expert || wide_heads(h)) return EC_OK;
+    return ec_teacher_force(c.hv, (const int64_t*)c.force->expert, c.force->mask, c.force->p, (int64_t*)c.smp.actions, c.smp.logp, c.N,
+                            h->c.num_actions, c.smp.seed, c.smp.step, c.smp.first_actor, c.stream);
 }
 
 struct Bwd : Ctx {
@@ -2807,43 +2891,29 @@ extern "C" int ec_policy_create_rnn_layers(ec_policy_t** out, const ec_policy_cf
     ec_policy* h = new (std::nothrow) ec_policy();
     if (!h) return EC_ERR_ALLOC;
     h->c = c;
-    h->rnn = rnn_type;
+    h->rnn = rnn_type; h->layers = num_layers;
     if (c.goal_in) h->c.num_goals = 0;   // ignored: no goal table anywhere (the table areas of the workspace are empty)
-    const size_t S = (size_t)c.spatial * c.spatial, H = c.hidden, GW = (rnn_type == EC_RNN_LSTM ? 4 : 3) * H;
+    const size_t S = (size_t)c.spatial * c.spatial;
     const size_t flat = c.fusion ? (size_t)c.in_channels : (size_t)(c.dual ? 2 : 1) * c.comb_out * S;
-    size_t n[P_COUNT] = {c.goal_in ? (size_t)c.goal_dims * c.goal_in : (size_t)c.num_goals * c.goal_dims,
-                               (size_t)c.compress_hid * c.in_channels, (size_t)c.compress_hid,
-                               (size_t)c.compress_out * c.compress_hid, (size_t)c.compress_out,
-                               (size_t)c.comb_hid * (c.compress_out + c.goal_dims), (size_t)c.comb_hid,
-                               (size_t)c.comb_out * c.comb_hid, (size_t)c.comb_out,
-                               GW * (flat + c.prev_action_dims), GW * H, GW, GW,
-                               (size_t)c.num_actions * H, (size_t)c.num_actions, H, 1, 0, 0, 0, 0, 0, 0, 0, 0,
-                               c.goal_in ? (size_t)c.goal_dims : 0,
-                               (size_t)(c.num_actions + c.prev_action_null) * c.prev_action_dims};
-    if (c.fusion)
-        for (int i = P_EMB; i <= P_B4; ++i) n[i] = 0;      // no goal embedding / compressor / combiner: GRU + heads only
+    // the goal embedding (coordinate goals: embed_goal.weight, then its bias), compressor and combiner: no elements on a fusion handle
+    const size_t enc = c.fusion ? 0 : 1;
+    const size_t n[1 + 8] = {c.goal_in ? (size_t)c.goal_dims * c.goal_in : (size_t)c.num_goals * c.goal_dims,
+                             (size_t)c.compress_hid * c.in_channels, (size_t)c.compress_hid,
+                             (size_t)c.compress_out * c.compress_hid, (size_t)c.compress_out,
+                             (size_t)c.comb_hid * (c.compress_out + c.goal_dims), (size_t)c.comb_hid,
+                             (size_t)c.comb_out * c.comb_hid, (size_t)c.comb_out};
+    h->off[P_EMB] = h->put(enc * n[0]);
+    h->off[P_GB] = h->put(c.goal_in ? (size_t)c.goal_dims : 0, c.goal_in != 0);
+    for (int i = P_W1; i <= P_B4; ++i) h->off[i] = h->put(enc * n[i]);
+    h->put_core(flat + c.prev_action_dims);
+    // the dual encoder's depth stream: the compressor's and combiner's shapes again
     if (c.dual)
-        for (int i = P_W1; i <= P_B4; ++i) n[i + (P_W1D - P_W1)] = n[i];
-    // flat order: the enum's, except that embed_goal.bias follows embed_goal.weight and the previous-action embedding follows
-    // critic.fc.bias (the depth stream's tensors have zero elements on such a handle: it is the last tensor)
-    h->ntensors = 0;
-    for (int i = 0; i < P_COUNT_DUAL; ++i) {
-        h->order[h->ntensors++] = i;
-        if (i == P_EMB && c.goal_in) h->order[h->ntensors++] = P_GB;
-        if (i == P_BC && c.prev_action_dims) h->order[h->ntensors++] = P_PAE;
-    }
-    if (!c.goal_in) h->order[h->ntensors++] = P_GB;          // (zero elements)
-    if (!c.prev_action_dims) h->order[h->ntensors++] = P_PAE; // (zero elements)
-    size_t o = 0;
-    for (int k = 0; k < P_COUNT; ++k) { const int i = h->order[k]; h->off[i] = o; h->num[i] = n[i]; o += (n[i] + 3) / 4 * 4; }   // 16-B aligned
-    // the upper layers' tensors END the flat order: layer 1, 2, 3; weight_ih, weight_hh, bias_ih, bias_hh each
-    h->layers = num_layers;
-    h->nbase = ec_policy_num_param_tensors(h) - 4 * (num_layers - 1);
-    for (int l = 1; l < num_layers; ++l) {
-        const size_t un[4] = {GW * H, GW * H, GW, GW};
-        for (int k = 0; k < 4; ++k) { h->uoff[l - 1][k] = o; h->unum[l - 1][k] = un[k]; o += (un[k] + 3) / 4 * 4; }
-    }
-    h->total = o;
+        for (int i = P_W1; i <= P_B4; ++i) h->off[i + (P_W1D - P_W1)] = h->put(n[i]);
+    h->count = h->slots;
+    // (kept as it was: a one-layer handle without the depth stream answers the indices up to the dual handle's count too, with
+    // no elements at the end of the buffer)
+    static_assert(P_COUNT_VEC + 1 <= P_COUNT_DUAL);   // (the most tensors such a handle has: coordinate goals and previous actions)
+    while (num_layers == 1 && h->slots < P_COUNT_DUAL) h->put(0);
     *out = h;
     return EC_OK;
 }
@@ -2853,35 +2923,12 @@ extern "C" int ec_policy_set_goal_table(ec_policy_t* h, const float* table) {
     h->goal_table = table;
     return EC_OK;
 }
-extern "C" int ec_policy_num_param_tensors(const ec_policy_t* h) {
-    if (h && h->pl.on) return h->pl.npre + 8 + (h->c.prev_action_dims ? 1 : 0) + 4 * (h->layers - 1);
-    return ((h && h->c.dual) ? P_COUNT_DUAL : ((h && h->c.goal_in) ? P_COUNT_VEC : P_COUNT_SINGLE)) + ((h && h->c.prev_action_dims) ? 1 : 0) +
-           (h ? 4 * (h->layers - 1) : 0);
-}
+extern "C" int ec_policy_num_param_tensors(const ec_policy_t* h) { return h ? h->count : P_COUNT_SINGLE; }   // (NULL: kept as it was)
 extern "C" size_t ec_policy_flat_size(const ec_policy_t* h) { return h ? h->total : 0; }
 extern "C" int ec_policy_param_offset(const ec_policy_t* h, int idx, size_t* off, size_t* numel) {
     if (!h || idx < 0 || !off || !numel) return EC_ERR_ARG;
-    if (h->layers > 1 && idx >= h->nbase) {           // an upper layer's tensor
-        const int u = idx - h->nbase;
-        if (u >= 4 * (h->layers - 1)) return EC_ERR_ARG;
-        *off = h->uoff[u / 4][u % 4]; *numel = h->unum[u / 4][u % 4];
-        return EC_OK;
-    }
-    if (h->pl.on) {                                   // visual_fc, the goal encoders, then weight_ih_l0 .. critic bias, the previous action's
-        const int k = idx - h->pl.npre;
-        if (k >= 8 + (h->c.prev_action_dims ? 1 : 0)) return EC_ERR_ARG;
-        if (k < 0) {
-            int t = idx;                              // (the goal-id embedding's slot is skipped on a handle without one)
-            if (!h->pl.tv && !h->pl.ids && t >= PL_GEMB) ++t;
-            *off = h->pl.off[t]; *numel = h->pl.num[t];
-        } else {
-            const int i = k < 8 ? P_WIH + k : P_PAE;
-            *off = h->off[i]; *numel = h->num[i];
-        }
-        return EC_OK;
-    }
-    if (idx >= P_COUNT_DUAL) return EC_ERR_ARG;
-    *off = h->off[h->order[idx]]; *numel = h->num[h->order[idx]];
+    if (idx >= h->slots) return EC_ERR_ARG;
+    *off = h->table[idx].off; *numel = h->table[idx].num;
     return EC_OK;
 }
 extern "C" size_t ec_policy_workspace_bytes(const ec_policy_t* h, int T, int N, int for_backward) {
@@ -2889,23 +2936,25 @@ extern "C" size_t ec_policy_workspace_bytes(const ec_policy_t* h, int T, int N, 
     return make_plan(h, T, N, for_backward != 0 ? EC_POLICY_LEARN : EC_POLICY_INFER, false).w.end * 4;
 }
 
+// ---- the forward and act entry points: each fills a Call and hands it on ----
 extern "C" int ec_policy_forward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16, const int64_t* goal,
                                  const float* h0, const float* masks, int T, int N, void* workspace, size_t ws_bytes, int for_backward,
                                  float* hv, float* h_final, ec_stream_t stream) {
     return ec_policy_forward2(h, params, feat, nullptr, feat_bf16, goal, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final, stream);
 }
-
 extern "C" int ec_policy_forward2(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                   const int64_t* goal, const float* h0, const float* masks, int T, int N, void* workspace,
                                   size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream) {
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final,
-                               SampleArgs{}, stream);
+    return policy_forward_impl(h, {.face = Face::tensor, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal = goal,
+                                   .h0 = h0, .masks = masks, .T = T, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = for_backward,
+                                   .hv = hv, .h_final = h_final, .stream = stream});
 }
 extern "C" int ec_policy_forward_vec(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                      const float* goal_vec, const float* h0, const float* masks, int T, int N, void* workspace,
                                      size_t ws_bytes, int for_backward, float* hv, float* h_final, ec_stream_t stream) {
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, T, N, workspace, ws_bytes, for_backward, hv,
-                               h_final, SampleArgs{}, stream);
+    return policy_forward_impl(h, {.face = Face::tensor, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal_vec = goal_vec,
+                                   .h0 = h0, .masks = masks, .T = T, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = for_backward,
+                                   .hv = hv, .h_final = h_final, .stream = stream});
 }
 
 // The act step in ONE call ([U] allenact OnPolicyRLEngine.act: actor_critic(...) then distributions.sample() / log_probs()):
@@ -2915,21 +2964,17 @@ extern "C" int ec_policy_act(const ec_policy_t* h, const float* params, const vo
                              const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                              int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                              uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream) {
-    if (!actions || !logp || (h && (h->c.prev_action_dims || h->pl.on))) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa; pooled: ec_policy_act_pooled)
-    if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;       // (the one-wave-per-row heads launch)
-    const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, 1, N, workspace, ws_bytes,
-                               reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
+    return policy_act(h, {.face = Face::tensor, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal = goal, .h0 = h0,
+                          .masks = masks, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = act_mode(reuse_tables), .hv = hv,
+                          .h_final = h_final, .smp = {(long long*)actions, logp, values, seed, step, first_actor, 0}, .stream = stream});
 }
 extern "C" int ec_policy_act_vec(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                  const float* goal_vec, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                                  int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                                  uint64_t seed, uint64_t step, int first_actor, ec_stream_t stream) {
-    if (!actions || !logp || (h && (h->c.prev_action_dims || h->pl.on))) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa; pooled: ec_policy_act_pooled)
-    if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
-    const SampleArgs smp{(long long*)actions, logp, values, seed, step, first_actor};
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
-                               reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
+    return policy_act(h, {.face = Face::tensor, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal_vec = goal_vec,
+                          .h0 = h0, .masks = masks, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = act_mode(reuse_tables), .hv = hv,
+                          .h_final = h_final, .smp = {(long long*)actions, logp, values, seed, step, first_actor, 0}, .stream = stream});
 }
 
 // The evaluation act step (readme_files/baselines_robothor_objectnav.md:66-68 `--eval`, baselines_habitat.md:89-97
@@ -2939,58 +2984,30 @@ extern "C" int ec_policy_act_greedy(const ec_policy_t* h, const float* params, c
                                     const int64_t* goal, const float* h0, const float* masks, int N, void* workspace, size_t ws_bytes,
                                     int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp, float* values,
                                     ec_stream_t stream) {
-    if (!actions || !logp || (h && (h->c.prev_action_dims || h->pl.on))) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa; pooled: ec_policy_act_pooled)
-    if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
-    const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, nullptr, h0, masks, 1, N, workspace, ws_bytes,
-                               reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
+    return policy_act(h, {.face = Face::tensor, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal = goal, .h0 = h0,
+                          .masks = masks, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = act_mode(reuse_tables), .hv = hv,
+                          .h_final = h_final, .smp = {(long long*)actions, logp, values, 0, 0, 0, 1}, .stream = stream});
 }
 extern "C" int ec_policy_act_vec_greedy(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                         const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
                                         size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
                                         float* values, ec_stream_t stream) {
-    if (!actions || !logp || (h && (h->c.prev_action_dims || h->pl.on))) return EC_ERR_ARG;      // (previous actions: ec_policy_act_pa; pooled: ec_policy_act_pooled)
-    if (!h || h->c.num_actions + 1 > 8) return EC_ERR_UNSUPPORTED;
-    const SampleArgs smp{(long long*)actions, logp, values, 0, 0, 0, 1};
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, nullptr, goal_vec, h0, masks, 1, N, workspace, ws_bytes,
-                               reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER, hv, h_final, smp, stream);
+    return policy_act(h, {.face = Face::tensor, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal_vec = goal_vec,
+                          .h0 = h0, .masks = masks, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = act_mode(reuse_tables), .hv = hv,
+                          .h_final = h_final, .smp = {(long long*)actions, logp, values, 0, 0, 0, 1}, .stream = stream});
 }
 
-// The act step in one call for every handle (include/ec_amd.h).  More than 7 actions: the stages in front as they are, then the
-// wide heads launch with the selection (and the forcing) in it; up to 7: what ec_policy_act* launch, then ec_teacher_force's launch.
-static int policy_act_any(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
-                          const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, bool pa_entry, const float* h0,
-                          const float* masks, int N, void* workspace, size_t ws_bytes, int reuse_tables, float* hv, float* h_final,
-                          int64_t* actions, float* logp, float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
-                          const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream,
-                          const PooledIn* pin = nullptr) {
-    if (!h || !actions || !logp) return EC_ERR_ARG;
-    if ((pin != nullptr) != h->pl.on || (pin && pin->tv != h->pl.tv)) return EC_ERR_ARG;
-    if (!pin && (pa_entry != (h->c.prev_action_dims > 0) || (pa_entry && !prev_actions))) return EC_ERR_ARG;
-    if ((expert_actions != nullptr) != (expert_mask != nullptr)) return EC_ERR_ARG;
-    if (!(force_p >= 0.f && force_p <= 1.f)) return EC_ERR_ARG;       // (NaN included)
-    if (!expert_actions && force_p != 0.f) return EC_ERR_ARG;
-    if (expert_actions && greedy) return EC_ERR_ARG;                   // forcing belongs to the sampling act step
-    if (h->c.num_actions > 256) return EC_ERR_UNSUPPORTED;
-    if (first_actor < 0) return EC_ERR_SHAPE;
-    const SampleArgs smp{(long long*)actions, logp, values, greedy ? 0 : seed, greedy ? 0 : step, greedy ? 0 : first_actor, greedy ? 1 : 0};
-    const ForceArgs force{(const long long*)expert_actions, expert_mask, force_p};
-    const int mode = reuse_tables ? EC_POLICY_INFER_REUSE : EC_POLICY_INFER;
-    if (h->c.num_actions + 1 > 8)
-        return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, 1, N, workspace, ws_bytes, mode, hv, h_final,
-                                   smp, stream, &force, prev_actions, pa_entry, pin);
-    const int rc = policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, 1, N, workspace, ws_bytes, mode, hv,
-                                       h_final, smp, stream, nullptr, prev_actions, pa_entry, pin);
-    if (rc != EC_OK || !expert_actions) return rc;
-    return ec_teacher_force(hv, expert_actions, expert_mask, force_p, actions, logp, N, h->c.num_actions, seed, step, first_actor, stream);
-}
+// The act step in one call for every handle (include/ec_amd.h): selection by flag, and teacher forcing behind it
 extern "C" int ec_policy_act_ex(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                 const int64_t* goal, const float* goal_vec, const float* h0, const float* masks, int N, void* workspace,
                                 size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
                                 float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
                                 const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
-    return policy_act_any(h, params, feat, feat2, feat_bf16, goal, goal_vec, nullptr, false, h0, masks, N, workspace, ws_bytes, reuse_tables,
-                          hv, h_final, actions, logp, values, greedy, seed, step, first_actor, expert_actions, expert_mask, force_p, stream);
+    const ForceArgs force{(const long long*)expert_actions, expert_mask, force_p};
+    return policy_act(h, {.face = Face::tensor, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal = goal,
+                          .goal_vec = goal_vec, .h0 = h0, .masks = masks, .N = N, .workspace = workspace, .ws_bytes = ws_bytes,
+                          .mode = act_mode(reuse_tables), .hv = hv, .h_final = h_final,
+                          .smp = {(long long*)actions, logp, values, seed, step, first_actor, greedy ? 1 : 0}, .force = &force, .stream = stream});
 }
 
 // Handles with a previous-action embedding (include/ec_amd.h): ec_policy_forward_vec / ec_policy_act_ex with both goal arguments
@@ -2999,17 +3016,20 @@ extern "C" int ec_policy_forward_pa(const ec_policy_t* h, const float* params, c
                                     const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, const float* h0,
                                     const float* masks, int T, int N, void* workspace, size_t ws_bytes, int for_backward, float* hv,
                                     float* h_final, ec_stream_t stream) {
-    return policy_forward_impl(h, params, feat, feat2, feat_bf16, goal, goal_vec, h0, masks, T, N, workspace, ws_bytes, for_backward, hv,
-                               h_final, SampleArgs{}, stream, nullptr, prev_actions, true);
+    return policy_forward_impl(h, {.face = Face::tensor_pa, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal = goal,
+                                   .goal_vec = goal_vec, .prev_actions = prev_actions, .h0 = h0, .masks = masks, .T = T, .N = N,
+                                   .workspace = workspace, .ws_bytes = ws_bytes, .mode = for_backward, .hv = hv, .h_final = h_final, .stream = stream});
 }
 extern "C" int ec_policy_act_pa(const ec_policy_t* h, const float* params, const void* feat, const void* feat2, int feat_bf16,
                                 const int64_t* goal, const float* goal_vec, const int64_t* prev_actions, const float* h0,
                                 const float* masks, int N, void* workspace, size_t ws_bytes, int reuse_tables, float* hv, float* h_final,
                                 int64_t* actions, float* logp, float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
                                 const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
-    return policy_act_any(h, params, feat, feat2, feat_bf16, goal, goal_vec, prev_actions, true, h0, masks, N, workspace, ws_bytes,
-                          reuse_tables, hv, h_final, actions, logp, values, greedy, seed, step, first_actor, expert_actions, expert_mask,
-                          force_p, stream);
+    const ForceArgs force{(const long long*)expert_actions, expert_mask, force_p};
+    return policy_act(h, {.face = Face::tensor_pa, .params = params, .feat = feat, .feat2 = feat2, .feat_bf16 = feat_bf16, .goal = goal,
+                          .goal_vec = goal_vec, .prev_actions = prev_actions, .h0 = h0, .masks = masks, .N = N, .workspace = workspace,
+                          .ws_bytes = ws_bytes, .mode = act_mode(reuse_tables), .hv = hv, .h_final = h_final,
+                          .smp = {(long long*)actions, logp, values, seed, step, first_actor, greedy ? 1 : 0}, .force = &force, .stream = stream});
 }
 
 // The pooled-embedding net (include/ec_amd.h): a handle whose plan is the fusion handle's with in_channels = hidden, its own
@@ -3046,29 +3066,16 @@ extern "C" int ec_policy_create_pooled(ec_policy_t** out, const ec_pooled_cfg* c
     ec_policy::Pooled& pl = h->pl;
     pl.on = true; pl.D = q.embed_in; pl.ed = q.embed_dims; pl.ids = q.num_goals > 0 ? 1 : 0; pl.ns = q.num_sensors; pl.K = K;
     for (int i = 0; i < q.num_sensors; ++i) pl.k[i] = q.sensor_in[i];
-    pl.npre = 2 + pl.ids + 2 * pl.ns;
-    const size_t H = q.hidden, GW = (q.rnn_type == EC_RNN_LSTM ? 4 : 3) * H, ld = H + pl.side() + q.prev_action_dims;
-    size_t o = 0;
-    auto put = [&](size_t& off, size_t& num, size_t n) { off = o; num = n; o += (n + 3) / 4 * 4; };   // 16-B aligned
-    put(pl.off[PL_FCW], pl.num[PL_FCW], H * pl.D);
-    put(pl.off[PL_FCB], pl.num[PL_FCB], H);
-    put(pl.off[PL_GEMB], pl.num[PL_GEMB], (size_t)q.num_goals * pl.ed);
+    const size_t H = q.hidden;
+    pl.off[PL_FCW] = h->put(H * pl.D);
+    pl.off[PL_FCB] = h->put(H);
+    pl.off[PL_GEMB] = h->put((size_t)q.num_goals * pl.ed, pl.ids != 0);
     for (int i = 0; i < pl.ns; ++i) {
-        put(pl.off[PL_SW0 + 2 * i], pl.num[PL_SW0 + 2 * i], (size_t)pl.ed * pl.k[i]);
-        put(pl.off[PL_SB0 + 2 * i], pl.num[PL_SB0 + 2 * i], (size_t)pl.ed);
+        pl.off[PL_SW0 + 2 * i] = h->put((size_t)pl.ed * pl.k[i]);
+        pl.off[PL_SB0 + 2 * i] = h->put((size_t)pl.ed);
     }
-    for (int i = 0; i < P_COUNT; ++i) { h->off[i] = 0; h->num[i] = 0; h->order[i] = i; }
-    const size_t n8[8] = {GW * ld, GW * H, GW, GW, (size_t)q.num_actions * H, (size_t)q.num_actions, H, 1};
-    for (int k = 0; k < 8; ++k) put(h->off[P_WIH + k], h->num[P_WIH + k], n8[k]);
-    h->off[P_PAE] = o;
-    if (q.prev_action_dims) put(h->off[P_PAE], h->num[P_PAE], (size_t)(q.num_actions + q.prev_action_null) * q.prev_action_dims);
-    h->ntensors = ec_policy_num_param_tensors(h) - 4 * (q.num_layers - 1);
-    h->nbase = h->ntensors;
-    for (int l = 1; l < q.num_layers; ++l) {
-        const size_t un[4] = {GW * H, GW * H, GW, GW};
-        for (int k = 0; k < 4; ++k) put(h->uoff[l - 1][k], h->unum[l - 1][k], un[k]);
-    }
-    h->total = o;
+    h->put_core(H + pl.side() + q.prev_action_dims);
+    h->count = h->slots;
     *out = h;
     return EC_OK;
 }
@@ -3076,19 +3083,20 @@ extern "C" int ec_policy_forward_pooled(const ec_policy_t* h, const float* param
                                         const float* sensors, const int64_t* prev_actions, const float* h0, const float* masks, int T,
                                         int N, void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final,
                                         ec_stream_t stream) {
-    const PooledIn pin{sensors};
-    return policy_forward_impl(h, params, embed, nullptr, 0, goal, nullptr, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final,
-                               SampleArgs{}, stream, nullptr, prev_actions, false, &pin);
+    return policy_forward_impl(h, {.face = Face::pooled, .params = params, .feat = embed, .goal = goal, .prev_actions = prev_actions,
+                                   .sensors = sensors, .h0 = h0, .masks = masks, .T = T, .N = N, .workspace = workspace, .ws_bytes = ws_bytes,
+                                   .mode = for_backward, .hv = hv, .h_final = h_final, .stream = stream});
 }
 extern "C" int ec_policy_act_pooled(const ec_policy_t* h, const float* params, const float* embed, const int64_t* goal,
                                     const float* sensors, const int64_t* prev_actions, const float* h0, const float* masks, int N,
                                     void* workspace, size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions,
                                     float* logp, float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
                                     const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
-    const PooledIn pin{sensors};
-    return policy_act_any(h, params, embed, nullptr, 0, goal, nullptr, prev_actions, false, h0, masks, N, workspace, ws_bytes, reuse_tables,
-                          hv, h_final, actions, logp, values, greedy, seed, step, first_actor, expert_actions, expert_mask, force_p, stream,
-                          &pin);
+    const ForceArgs force{(const long long*)expert_actions, expert_mask, force_p};
+    return policy_act(h, {.face = Face::pooled, .params = params, .feat = embed, .goal = goal, .prev_actions = prev_actions, .sensors = sensors,
+                          .h0 = h0, .masks = masks, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = act_mode(reuse_tables), .hv = hv,
+                          .h_final = h_final, .smp = {(long long*)actions, logp, values, seed, step, first_actor, greedy ? 1 : 0}, .force = &force,
+                          .stream = stream});
 }
 
 // The two-view rearrangement net (include/ec_amd.h): the pooled-embedding handle's plan from v onwards, two_view.hip's front
@@ -3113,28 +3121,15 @@ extern "C" int ec_policy_create_two_view(ec_policy_t** out, const ec_two_view_cf
     h->rnn = q.rnn_type; h->layers = q.num_layers;
     ec_policy::Pooled& pl = h->pl;
     pl.on = true; pl.tv = true; pl.tvC = q.in_channels; pl.tvS2 = q.spatial * q.spatial; pl.tvA1 = q.attn_hidden;
-    pl.npre = TV_NPRE;
-    const size_t H = q.hidden, GW = (q.rnn_type == EC_RNN_LSTM ? 4 : 3) * H, ld = H + q.prev_action_dims, K3 = 3 * (size_t)q.in_channels;
-    size_t o = 0;
-    auto put = [&](size_t& off, size_t& num, size_t n) { off = o; num = n; o += (n + 3) / 4 * 4; };   // 16-B aligned
-    put(pl.off[TV_WE], pl.num[TV_WE], H * K3);
-    put(pl.off[TV_BE], pl.num[TV_BE], H);
-    put(pl.off[TV_WA], pl.num[TV_WA], (size_t)q.attn_hidden * K3);
-    put(pl.off[TV_BA], pl.num[TV_BA], (size_t)q.attn_hidden);
-    put(pl.off[TV_W2], pl.num[TV_W2], (size_t)q.attn_hidden);
-    put(pl.off[TV_B2], pl.num[TV_B2], 1);
-    for (int i = 0; i < P_COUNT; ++i) { h->off[i] = 0; h->num[i] = 0; h->order[i] = i; }
-    const size_t n8[8] = {GW * ld, GW * H, GW, GW, (size_t)q.num_actions * H, (size_t)q.num_actions, H, 1};
-    for (int k = 0; k < 8; ++k) put(h->off[P_WIH + k], h->num[P_WIH + k], n8[k]);
-    h->off[P_PAE] = o;
-    if (q.prev_action_dims) put(h->off[P_PAE], h->num[P_PAE], (size_t)(q.num_actions + q.prev_action_null) * q.prev_action_dims);
-    h->ntensors = ec_policy_num_param_tensors(h) - 4 * (q.num_layers - 1);
-    h->nbase = h->ntensors;
-    for (int l = 1; l < q.num_layers; ++l) {
-        const size_t un[4] = {GW * H, GW * H, GW, GW};
-        for (int k = 0; k < 4; ++k) put(h->uoff[l - 1][k], h->unum[l - 1][k], un[k]);
-    }
-    h->total = o;
+    const size_t H = q.hidden, A1 = q.attn_hidden, K3 = 3 * (size_t)q.in_channels;
+    pl.off[TV_WE] = h->put(H * K3);
+    pl.off[TV_BE] = h->put(H);
+    pl.off[TV_WA] = h->put(A1 * K3);
+    pl.off[TV_BA] = h->put(A1);
+    pl.off[TV_W2] = h->put(A1);
+    pl.off[TV_B2] = h->put(1);
+    h->put_core(H + q.prev_action_dims);
+    h->count = h->slots;
     *out = h;
     return EC_OK;
 }
@@ -3142,19 +3137,20 @@ extern "C" int ec_policy_forward_two_view(const ec_policy_t* h, const float* par
                                           const int64_t* prev_actions, const float* h0, const float* masks, int T, int N,
                                           void* workspace, size_t ws_bytes, int for_backward, float* hv, float* h_final,
                                           ec_stream_t stream) {
-    const PooledIn pin{nullptr, true};
-    return policy_forward_impl(h, params, feat, feat2, 0, nullptr, nullptr, h0, masks, T, N, workspace, ws_bytes, for_backward, hv, h_final,
-                               SampleArgs{}, stream, nullptr, prev_actions, false, &pin);
+    return policy_forward_impl(h, {.face = Face::two_view, .params = params, .feat = feat, .feat2 = feat2, .prev_actions = prev_actions, .h0 = h0,
+                                   .masks = masks, .T = T, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = for_backward, .hv = hv,
+                                   .h_final = h_final, .stream = stream});
 }
 extern "C" int ec_policy_act_two_view(const ec_policy_t* h, const float* params, const void* feat, const void* feat2,
                                       const int64_t* prev_actions, const float* h0, const float* masks, int N, void* workspace,
                                       size_t ws_bytes, int reuse_tables, float* hv, float* h_final, int64_t* actions, float* logp,
                                       float* values, int greedy, uint64_t seed, uint64_t step, int first_actor,
                                       const int64_t* expert_actions, const float* expert_mask, float force_p, ec_stream_t stream) {
-    const PooledIn pin{nullptr, true};
-    return policy_act_any(h, params, feat, feat2, 0, nullptr, nullptr, prev_actions, false, h0, masks, N, workspace, ws_bytes, reuse_tables,
-                          hv, h_final, actions, logp, values, greedy, seed, step, first_actor, expert_actions, expert_mask, force_p, stream,
-                          &pin);
+    const ForceArgs force{(const long long*)expert_actions, expert_mask, force_p};
+    return policy_act(h, {.face = Face::two_view, .params = params, .feat = feat, .feat2 = feat2, .prev_actions = prev_actions, .h0 = h0,
+                          .masks = masks, .N = N, .workspace = workspace, .ws_bytes = ws_bytes, .mode = act_mode(reuse_tables), .hv = hv,
+                          .h_final = h_final, .smp = {(long long*)actions, logp, values, seed, step, first_actor, greedy ? 1 : 0}, .force = &force,
+                          .stream = stream});
 }
 
 extern "C" int ec_policy_backward(const ec_policy_t* h, const float* params, const void* feat, int feat_bf16,

@@ -152,12 +152,44 @@ class PolicyHandle:
             h_final = torch.empty((N, self.state_width), dtype=torch.float32, device=dev)
         return hv, h_final
 
+    # ---- the one forward and the one act path.  A call's arguments are: the handle and the parameters; the leading pointers of
+    # the handle's face (``_face``, the one hook a subclass supplies); the state block; for an act call the outputs and the
+    # selection block; the stream.
+
+    def _face(self, kind: str, feat, goal, feat2, prev_actions, sensors, rows: int, deterministic: bool = False):
+        """Check the inputs of a call over ``rows`` frames; -> (entry-point name, the pointers between ``params`` and ``h0``).
+        ``kind``: "forward", "act" (the narrow act entry points: a handle without previous actions) or "act_ex"."""
+        assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
+        assert sensors is None, "this handle has no sensors: pass sensors=None"
+        if kind == "forward" and self.cfg["dual"]:    # RGB + depth: feat = the RGB features, feat2 = the depth features (same shape / dtype)
+            assert feat2 is not None and feat2.is_contiguous() and feat2.dtype == feat.dtype and feat2.shape == feat.shape
+        fp, f2, bf = feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16)
+        pp, gp = self._prev_ptr(prev_actions, rows), self._goal_ptr(goal, rows)
+        if kind == "act":
+            return ("ec_policy_act_vec" if self.goal_in else "ec_policy_act") + ("_greedy" if deterministic else ""), (fp, f2, bf, gp)
+        if kind == "forward" and not pp:
+            return ("ec_policy_forward_vec" if self.goal_in else "ec_policy_forward2"), (fp, f2, bf, gp)
+        ids, vec = (0, gp) if self.goal_in else (gp, 0)      # these entry points take the ids and the coordinates
+        if pp:
+            return ("ec_policy_forward_pa" if kind == "forward" else "ec_policy_act_pa"), (fp, f2, bf, ids, vec, pp)
+        return "ec_policy_act_ex", (fp, f2, bf, ids, vec)
+
+    def _state_block(self, h0, masks, sizes, ws, flag, hv, h_final):
+        """State in, masks, ``sizes`` ((T, N) of a forward, (N,) of an act call), workspace, the mode flag, ``hv`` and state out."""
+        N = sizes[-1]
+        return (self._state_ptr(h0, N, "h0"), masks.data_ptr(), *sizes, ws.data_ptr(), ws.numel() * ws.element_size(), int(flag),
+                hv.data_ptr(), self._state_ptr(h_final, N, "h_final"))
+
     @staticmethod
-    def _forcing_args(expert_actions, expert_mask, force_p: float):
-        """The teacher-forcing triple that ends the one-call act entry points (zeros: no forcing)."""
+    def _select_block(deterministic, seed, step, first_actor, expert_actions, expert_mask, force_p: float):
+        """The selection arguments of the one-call act entry points, ending in the teacher-forcing triple (zeros: no forcing)."""
         if expert_actions is not None and force_p > 0.0:
-            return expert_actions.data_ptr(), expert_mask.data_ptr(), force_p
-        return 0, 0, 0.0
+            return int(deterministic), seed, step, first_actor, expert_actions.data_ptr(), expert_mask.data_ptr(), force_p
+        return int(deterministic), seed, step, first_actor, 0, 0, 0.0
+
+    def _call(self, name: str, flat_params, *args):
+        with _lib.tensor_guard(flat_params):
+            _lib.check(getattr(self.lib, name)(self.h, flat_params.data_ptr(), *args, _lib.stream_ptr()), name)
 
     def memory_to_state(self, mem: torch.Tensor) -> torch.Tensor:
         return memory_to_state(mem, self.rnn_type, self.rnn_layers)
@@ -187,11 +219,11 @@ class PolicyHandle:
         steps of a rollout).  ``prev_actions`` (handles with ``prev_action_dims > 0``, and only those): int64 [T*N], row
         ``t * N + n`` = the action actor ``n`` took at step ``t - 1``.  ``sensors`` (the pooled net's handle, and only that one): f32
         ``[T*N, K]``; None on every other handle."""
-        assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
-        dev = flat_params.device
-        with _lib.tensor_guard(flat_params):
-            mode = 1 if for_backward else (2 if reuse_tables else 0)
-            return self._forward(flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, mode, feat2, prev_actions, sensors)
+        mode = 1 if for_backward else (2 if reuse_tables else 0)
+        hv, h_final = self._outputs(hv, h_final, T, N, flat_params.device)
+        name, lead = self._face("forward", feat, goal, feat2, prev_actions, sensors, T * N)
+        self._call(name, flat_params, *lead, *self._state_block(h0, masks, (T, N), ws, mode, hv, h_final))
+        return hv, h_final
 
     def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
             first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None, sensors=None):
@@ -199,20 +231,12 @@ class PolicyHandle:
         ``actions`` / ``logp`` (and copies ``values``) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions``.
         ``deterministic=True`` (evaluation): the heads launch takes ``CategoricalDistr.mode()`` instead, the first maximal logit
         (``ec_policy_act_greedy``; ``seed`` / ``step`` / ``first_actor`` are not used) -- ``forward`` + ``ec_mode_actions``."""
-        assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
-        assert sensors is None, "this handle has no sensors: pass sensors=None"
         if self.prev_action_dims:            # (one entry point serves every act step of such a handle)
             return self.act_ex(flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed, step, first_actor,
-                               reuse_tables, feat2, deterministic, prev_actions=prev_actions)
-        self._prev_ptr(prev_actions, N)
-        name = ("ec_policy_act_vec" if self.goal_in else "ec_policy_act") + ("_greedy" if deterministic else "")
-        key = () if deterministic else (seed, step, first_actor)
-        with _lib.tensor_guard(flat_params):
-            _lib.check(getattr(self.lib, name)(
-                self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), self._goal_ptr(goal, N),
-                self._state_ptr(h0, N, "h0"), masks.data_ptr(), N, ws.data_ptr(), ws.numel() * ws.element_size(), int(reuse_tables),
-                hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(), logp.data_ptr(), _lib.ptr(values), *key,
-                _lib.stream_ptr()), name)
+                               reuse_tables, feat2, deterministic, prev_actions=prev_actions, sensors=sensors)
+        name, lead = self._face("act", feat, goal, feat2, prev_actions, sensors, N, deterministic)
+        self._call(name, flat_params, *lead, *self._state_block(h0, masks, (N,), ws, reuse_tables, hv, h_final),
+                   actions.data_ptr(), logp.data_ptr(), _lib.ptr(values), *(() if deterministic else (seed, step, first_actor)))
         return hv, h_final
 
     def act_ex(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
@@ -223,42 +247,10 @@ class PolicyHandle:
         maximal logit) -- the results of ``forward(for_backward=False)`` + ``ec_sample_actions`` / ``ec_mode_actions`` on the
         ``hv`` it writes, bit for bit; with up to 7 it is ``act``.  ``expert_actions`` / ``expert_mask`` / ``force_p``: teacher
         forcing (``imitation.teacher_force``) in the same call -- inside the heads launch of a wide action space."""
-        assert feat.is_contiguous() and feat.dtype in (torch.bfloat16, torch.float32)
-        assert sensors is None, "this handle has no sensors: pass sensors=None"
-        gp = self._goal_ptr(goal, N)
-        pp = self._prev_ptr(prev_actions, N)
-        fn, name = (self.lib.ec_policy_act_pa, "ec_policy_act_pa") if pp else (self.lib.ec_policy_act_ex, "ec_policy_act_ex")
-        with _lib.tensor_guard(flat_params):
-            _lib.check(fn(
-                self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16),
-                0 if self.goal_in else gp, gp if self.goal_in else 0, *((pp,) if pp else ()), self._state_ptr(h0, N, "h0"), masks.data_ptr(), N,
-                ws.data_ptr(), ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
-                logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
-                *self._forcing_args(expert_actions, expert_mask, force_p), _lib.stream_ptr()), name)
-        return hv, h_final
-
-    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None,
-                 sensors=None):
-        assert sensors is None, "this handle has no sensors: pass sensors=None"
-        hv, h_final = self._outputs(hv, h_final, T, N, dev)
-        self._state_ptr(h0, N, "h0")
-        self._state_ptr(h_final, N, "h_final")
-        if self.cfg["dual"]:       # RGB + depth: feat = the RGB features, feat2 = the depth features (same shape / dtype)
-            assert feat2 is not None and feat2.is_contiguous() and feat2.dtype == feat.dtype and feat2.shape == feat.shape
-        pp = self._prev_ptr(prev_actions, T * N)
-        if pp:
-            gp = self._goal_ptr(goal, T * N)
-            _lib.check(self.lib.ec_policy_forward_pa(
-                self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16),
-                0 if self.goal_in else gp, gp if self.goal_in else 0, pp, h0.data_ptr(), masks.data_ptr(), T, N, ws.data_ptr(),
-                ws.numel() * ws.element_size(), int(for_backward), hv.data_ptr(), h_final.data_ptr(), _lib.stream_ptr()),
-                "ec_policy_forward_pa")
-            return hv, h_final
-        fn = self.lib.ec_policy_forward_vec if self.goal_in else self.lib.ec_policy_forward2
-        _lib.check(fn(
-            self.h, flat_params.data_ptr(), feat.data_ptr(), _lib.ptr(feat2), int(feat.dtype == torch.bfloat16), self._goal_ptr(goal, T * N),
-            h0.data_ptr(), masks.data_ptr(), T, N, ws.data_ptr(), ws.numel() * ws.element_size(), int(for_backward),
-            hv.data_ptr(), h_final.data_ptr(), _lib.stream_ptr()), "ec_policy_forward_vec" if self.goal_in else "ec_policy_forward2")
+        name, lead = self._face("act_ex", feat, goal, feat2, prev_actions, sensors, N)
+        self._call(name, flat_params, *lead, *self._state_block(h0, masks, (N,), ws, reuse_tables, hv, h_final),
+                   actions.data_ptr(), logp.data_ptr(), _lib.ptr(values),
+                   *self._select_block(deterministic, seed, step, first_actor, expert_actions, expert_mask, force_p))
         return hv, h_final
 
     def backward(self, flat_params, feat, masks, T, N, ws, dhv, dh_final, flat_grads, feat2=None, recurrent_ready=None):
@@ -373,7 +365,8 @@ class PooledPolicyHandle(PolicyHandle):
         _lib.check(self.lib.ec_policy_create_pooled(C.byref(h), C.byref(c)), "ec_policy_create_pooled")
         self._bind_layout(h, pooled_param_shapes(**self.pooled_cfg))
 
-    def _side_ptrs(self, feat, goal, sensors, prev_actions, rows: int):
+    def _face(self, kind: str, feat, goal, feat2, prev_actions, sensors, rows: int, deterministic: bool = False):
+        assert feat2 is None
         D = self.pooled_cfg["embed_in"]
         assert feat.dtype == torch.float32 and feat.is_contiguous() and feat.numel() == rows * D, (feat.dtype, tuple(feat.shape), (rows, D))
         if self.pooled_cfg["num_goals"]:
@@ -385,33 +378,16 @@ class PooledPolicyHandle(PolicyHandle):
                 f"sensors: float32 [{rows}, {self.K}]"
         else:
             assert sensors is None, "this handle has no sensors: pass sensors=None"
-        return _lib.ptr(goal), _lib.ptr(sensors), self._prev_ptr(prev_actions, rows)
-
-    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None,
-                 sensors=None):
-        assert feat2 is None
-        hv, h_final = self._outputs(hv, h_final, T, N, dev)
-        gp, sp, pp = self._side_ptrs(feat, goal, sensors, prev_actions, T * N)
-        _lib.check(self.lib.ec_policy_forward_pooled(
-            self.h, flat_params.data_ptr(), feat.data_ptr(), gp, sp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), T, N, ws.data_ptr(),
-            ws.numel() * ws.element_size(), int(for_backward), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), _lib.stream_ptr()),
-            "ec_policy_forward_pooled")
-        return hv, h_final
+        name = "ec_policy_forward_pooled" if kind == "forward" else "ec_policy_act_pooled"
+        return name, (feat.data_ptr(), _lib.ptr(goal), _lib.ptr(sensors), self._prev_ptr(prev_actions, rows))
 
     def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
             first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None, sensors=None,
             expert_actions=None, expert_mask=None, force_p: float = 0.0):
         """``ec_policy_act_pooled``: the T = 1 inference forward and the selection (sample, ``deterministic=True`` the first maximal
         logit, optional teacher forcing) in one call, 2..256 actions."""
-        assert feat2 is None
-        gp, sp, pp = self._side_ptrs(feat, goal, sensors, prev_actions, N)
-        with _lib.tensor_guard(flat_params):
-            _lib.check(self.lib.ec_policy_act_pooled(
-                self.h, flat_params.data_ptr(), feat.data_ptr(), gp, sp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), N, ws.data_ptr(),
-                ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
-                logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
-                *self._forcing_args(expert_actions, expert_mask, force_p), _lib.stream_ptr()), "ec_policy_act_pooled")
-        return hv, h_final
+        return PolicyHandle.act_ex(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed, step, first_actor,
+                                   reuse_tables, feat2, deterministic, expert_actions, expert_mask, force_p, prev_actions, sensors)
 
     act_ex = act
 
@@ -494,39 +470,23 @@ class TwoViewPolicyHandle(PolicyHandle):
         _lib.check(self.lib.ec_policy_create_two_view(C.byref(h), C.byref(c)), "ec_policy_create_two_view")
         self._bind_layout(h, two_view_param_shapes(**self.two_view_cfg))
 
-    def _views_ptrs(self, feat, feat2, goal, prev_actions, rows: int):
+    def _face(self, kind: str, feat, goal, feat2, prev_actions, sensors, rows: int, deterministic: bool = False):
+        assert sensors is None, "this handle has no sensors: pass sensors=None"
         n = rows * self.cfg["spatial"] ** 2 * self.cfg["in_channels"]
         assert goal is None, "the two-view net has no goal input: pass goal=None"
         for t in (feat, feat2):
             assert t is not None and t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == n, \
                 "feat (current view) and feat2 (goal view): bf16 [rows, S2, C]"
-        return feat.data_ptr(), feat2.data_ptr(), self._prev_ptr(prev_actions, rows)
-
-    def _forward(self, flat_params, feat, goal, h0, masks, T, N, ws, hv, h_final, dev, for_backward=True, feat2=None, prev_actions=None,
-                 sensors=None):
-        assert sensors is None, "this handle has no sensors: pass sensors=None"
-        hv, h_final = self._outputs(hv, h_final, T, N, dev)
-        up, wp, pp = self._views_ptrs(feat, feat2, goal, prev_actions, T * N)
-        _lib.check(self.lib.ec_policy_forward_two_view(
-            self.h, flat_params.data_ptr(), up, wp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), T, N, ws.data_ptr(),
-            ws.numel() * ws.element_size(), int(for_backward), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), _lib.stream_ptr()),
-            "ec_policy_forward_two_view")
-        return hv, h_final
+        name = "ec_policy_forward_two_view" if kind == "forward" else "ec_policy_act_two_view"
+        return name, (feat.data_ptr(), feat2.data_ptr(), self._prev_ptr(prev_actions, rows))
 
     def act(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed: int = 0, step: int = 0,
             first_actor: int = 0, reuse_tables: bool = False, feat2=None, deterministic: bool = False, prev_actions=None,
             expert_actions=None, expert_mask=None, force_p: float = 0.0, sensors=None):
         """``ec_policy_act_two_view``: the T = 1 inference forward and the selection (sample, ``deterministic=True`` the first maximal
         logit, optional teacher forcing) in one call, 2..256 actions."""
-        assert sensors is None, "this handle has no sensors: pass sensors=None"
-        up, wp, pp = self._views_ptrs(feat, feat2, goal, prev_actions, N)
-        with _lib.tensor_guard(flat_params):
-            _lib.check(self.lib.ec_policy_act_two_view(
-                self.h, flat_params.data_ptr(), up, wp, pp, self._state_ptr(h0, N, "h0"), masks.data_ptr(), N, ws.data_ptr(),
-                ws.numel() * ws.element_size(), int(reuse_tables), hv.data_ptr(), self._state_ptr(h_final, N, "h_final"), actions.data_ptr(),
-                logp.data_ptr(), _lib.ptr(values), int(deterministic), seed, step, first_actor,
-                *self._forcing_args(expert_actions, expert_mask, force_p), _lib.stream_ptr()), "ec_policy_act_two_view")
-        return hv, h_final
+        return PolicyHandle.act_ex(self, flat_params, feat, goal, h0, masks, N, ws, hv, h_final, actions, logp, values, seed, step, first_actor,
+                                   reuse_tables, feat2, deterministic, expert_actions, expert_mask, force_p, prev_actions, sensors)
 
     act_ex = act
 

@@ -4,7 +4,7 @@
 // come first in the library's symbol lookup.
 //
 //   c++ -O1 -std=c++17 -rdynamic -o launch_log tools/launch_log.cpp -ldl
-//   launch_log LIB [--args N | --args-of SUBSTR N] < commands
+//   launch_log LIB [--args N | --args-of SUBSTR N [INDEX] ...] < commands
 //
 // Commands, one per line (tests/golden/make_conv_routes_golden.py writes them):
 //   conv  B H W Cin Cout ksize pool act res ldo     ec_conv_bf16 (ldo = 0) / ec_conv_bf16_ld
@@ -30,7 +30,7 @@
 //                                                   (f32+l1, ...): ec_rn50_set_l1_rebuild(h, 1) first, `S <rc>` in front of `P`;
 //                                                   `+l1off`: on, then off again
 //   rebuild M K0 N N2                               ec_conv1x1_pair_rebuild_bf16
-//   policy <the 13 ec_policy_cfg fields, in order> T N mode bf16 reuse [dhf [core]]
+//   policy <the first 13 ec_policy_cfg fields, in order> T N mode bf16 reuse [dhf [core [pad pnull [face]]]]
 //                                                   create + ec_policy_workspace_bytes + ec_policy_forward2 (goal_in > 0:
 //                                                   ec_policy_forward_vec) + destroy; mode 0 = EC_POLICY_INFER, 1 = _LEARN;
 //                                                   reuse 1: an EC_POLICY_INFER call builds the tables first (`B <rc>` ends
@@ -40,6 +40,12 @@
 //                                                   workspace; dhf 1 (mode 2 only): with a dh_final tensor, else NULL.
 //                                                   core = 10 * rnn_type + num_layers (2: a two-layer GRU, 12: a two-layer
 //                                                   LSTM): ec_policy_create_rnn_layers instead of ec_policy_create.
+//                                                   pad pnull: ec_policy_cfg's prev_action_dims and prev_action_null.
+//                                                   face: the entry point in place of the forward -- 1 ec_policy_act / _vec,
+//                                                   2 ec_policy_act_greedy / _vec_greedy, 3 ec_policy_act_ex, 4 the same with
+//                                                   forcing pointers (force_p 0.25), 5 ec_policy_forward_pa, 6 ec_policy_act_pa,
+//                                                   7 the same with forcing pointers; the act faces want T = 1 and mode 0 and
+//                                                   pass seed 1, step 2, first_actor 3.
 //                                                   `W <bytes>` is the workspace size, `D <bytes>` a device-to-device
 //                                                   hipMemcpyAsync (policy commands only)
 //   pooled D H ed goals ns k0 k1 k2 A E null rnn L T N mode reuse inplace act
@@ -47,6 +53,10 @@
 //                                                   (+ ec_policy_backward2 with mode 2) + destroy; mode / reuse / `W` / `B` / `F` / `D`
 //                                                   as for `policy`; inplace 1: h_final == h0;
 //                                                   act 1 (T = 1, mode 0): ec_policy_act_pooled, sampling, instead of the forward
+//   twoview C S H A1 A E null rnn L T N mode reuse inplace act
+//                                                   ec_policy_create_two_view (the nine ec_two_view_cfg fields) + the rest as for
+//                                                   `pooled` with ec_policy_forward_two_view, both views bf16; act 1 (T = 1,
+//                                                   mode 0): ec_policy_act_two_view, sampling; act 2: with forcing pointers
 //   stem  B H W Cout u8                             ec_stem_conv1 (u8 = 0) / ec_stem_conv1_u8 (the staging branch is chosen inside the
 //                                                   kernel: the record is the instance and the grid)
 //   stem7 B H W u8                                  ec_stem7_pool on fp32 (u8 = 0) / uint8 frames
@@ -57,7 +67,8 @@
 //   mean  B HW C                                    ec_spatial_mean_bf16
 // Output: `K <kernel>` per registered kernel, then per command `C <command>`, one `L <kernel>|<grid>|<block>|<lds>` per
 // launch (with --args N: `|` + the first N bytes of the first kernel argument in hex, for the conv_igemm kernels; --args-of SUBSTR N:
-// for the kernels whose name contains SUBSTR) and `R <rc>`.
+// for the kernels whose name contains SUBSTR; --args-of SUBSTR N INDEX: of kernel argument INDEX, which has to be at least N bytes
+// long; --args-of may repeat) and `R <rc>`.
 #include <cxxabi.h>
 #include <dlfcn.h>
 #include <stdint.h>
@@ -74,8 +85,8 @@ struct dim3 { unsigned x, y, z; };
 
 static std::map<const void*, std::string> g_kernels;
 static struct { dim3 grid, block; size_t lds; void* stream; } g_cfg;
-static int g_dump_args = 0;
-static std::string g_dump_of = "conv_igemm";
+struct Dump { std::string of; int index, bytes; };   // kernels whose name contains `of`: the first `bytes` bytes of argument `index`
+static std::vector<Dump> g_dumps;
 static int g_log_copies = 0;                   // policy commands: hipMemcpyAsync is part of the recorded sequence
 static uintptr_t g_next = 0x100000000000ull;   // fake device addresses; never dereferenced
 static void* fake(size_t bytes) { void* p = (void*)g_next; g_next += (bytes + 0xfffff) & ~(size_t)0xfffff; return p; }
@@ -99,9 +110,10 @@ int hipLaunchKernel(const void* fn, dim3 g, dim3 b, void** args, size_t lds, voi
     auto it = g_kernels.find(fn);
     const std::string name = it == g_kernels.end() ? "?" : it->second;
     printf("L %s|%u,%u,%u|%u,%u,%u|%zu", name.c_str(), g.x, g.y, g.z, b.x, b.y, b.z, lds);
-    if (g_dump_args && name.find(g_dump_of) != std::string::npos) {
+    for (const Dump& d : g_dumps) {
+        if (name.find(d.of) == std::string::npos) continue;
         printf("|");
-        for (int i = 0; i < g_dump_args; ++i) printf("%02x", ((const unsigned char*)args[0])[i]);
+        for (int i = 0; i < d.bytes; ++i) printf("%02x", ((const unsigned char*)args[d.index])[i]);
     }
     printf("\n");
     return 0;
@@ -232,15 +244,18 @@ static int run_tower(const std::string& kind, const int* v, const std::string& i
     return rc;
 }
 
-// v: the 13 ec_policy_cfg fields, then T, N, mode, bf16, reuse, dhf, core
+// v: the first 13 ec_policy_cfg fields, then T, N, mode, bf16, reuse, dhf, core, prev_action_dims, prev_action_null, face
 static int run_policy(const int* v) {
     typedef void* P;
-    const int T = v[13], N = v[14], mode = v[15], bf16 = v[16], reuse = v[17], dhf = v[18], goal_in = v[12], dual = v[11];
-    const bool learn_pass = mode == 2;
+    typedef uint64_t U;
+    const int T = v[13], N = v[14], mode = v[15], bf16 = v[16], reuse = v[17], dhf = v[18], goal_in = v[12], dual = v[11], face = v[22];
+    const bool learn_pass = mode == 2, act = (face >= 1 && face <= 4) || face >= 6;
     if (mode < 0 || mode > 2 || (reuse && mode != 0) || (dhf && !learn_pass)) return -100;
+    if (face < 0 || face > 7 || (act && (mode != 0 || T != 1))) return -100;
     void* h = nullptr;
-    int cfg[32] = {0};                                  // the 13 fields, zero-filled behind them (fields a later header adds read 0)
+    int cfg[32] = {0};                                  // the 15 fields, zero-filled behind them (fields a later header adds read 0)
     memcpy(cfg, v, 13 * sizeof(int));
+    cfg[13] = v[20]; cfg[14] = v[21];
     int rc = v[19] ? sym<int (*)(P*, const int*, int, int)>("ec_policy_create_rnn_layers")(&h, cfg, v[19] / 10, v[19] % 10)
                    : sym<int (*)(P*, const int*)>("ec_policy_create")(&h, cfg);
     if (rc) return rc;
@@ -248,13 +263,43 @@ static int run_policy(const int* v) {
     printf("W %zu\n", ws);
     const P params = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4), feat = fake(1u << 30), feat2 = dual ? fake(1u << 30) : nullptr;
     const P goal = fake(1u << 20), h0 = fake(1u << 24), masks = fake(1u << 20), wsp = fake(ws), hv = fake(1u << 20), hf = fake(1u << 24);
-    auto fwd = sym<int (*)(P, P, P, P, int, P, P, P, int, int, P, size_t, int, P, P, P)>(goal_in > 0 ? "ec_policy_forward_vec" : "ec_policy_forward2");
+    const P prev = fake(1u << 20), actions = fake(1u << 20), logp = fake(1u << 20), values = fake(1u << 20);
+    const bool force = face == 4 || face == 7;
+    const P expert = force ? fake(1u << 20) : nullptr, emask = force ? fake(1u << 20) : nullptr;
+    const P ids = goal_in > 0 ? nullptr : goal, vec = goal_in > 0 ? goal : nullptr;
+    const char* vs = goal_in > 0 ? "_vec" : "";
+    auto name = [&](const char* a, const char* b) { return std::string(a) + vs + b; };
+    // one call of the face's entry point in EC_POLICY_* mode `md`
+    auto fwd = [&](int md) -> int {
+        switch (face) {
+        case 0:
+            return sym<int (*)(P, P, P, P, int, P, P, P, int, int, P, size_t, int, P, P, P)>(goal_in > 0 ? "ec_policy_forward_vec" : "ec_policy_forward2")(
+                h, params, feat, feat2, bf16, goal, h0, masks, T, N, wsp, ws, md, hv, hf, nullptr);
+        case 1:
+            return sym<int (*)(P, P, P, P, int, P, P, P, int, P, size_t, int, P, P, P, P, P, U, U, int, P)>(name("ec_policy_act", "").c_str())(
+                h, params, feat, feat2, bf16, goal, h0, masks, N, wsp, ws, md == 2, hv, hf, actions, logp, values, 1, 2, 3, nullptr);
+        case 2:
+            return sym<int (*)(P, P, P, P, int, P, P, P, int, P, size_t, int, P, P, P, P, P, P)>(name("ec_policy_act", "_greedy").c_str())(
+                h, params, feat, feat2, bf16, goal, h0, masks, N, wsp, ws, md == 2, hv, hf, actions, logp, values, nullptr);
+        case 3: case 4:
+            return sym<int (*)(P, P, P, P, int, P, P, P, P, int, P, size_t, int, P, P, P, P, P, int, U, U, int, P, P, float, P)>("ec_policy_act_ex")(
+                h, params, feat, feat2, bf16, ids, vec, h0, masks, N, wsp, ws, md == 2, hv, hf, actions, logp, values, 0, 1, 2, 3, expert, emask,
+                force ? 0.25f : 0.f, nullptr);
+        case 5:
+            return sym<int (*)(P, P, P, P, int, P, P, P, P, P, int, int, P, size_t, int, P, P, P)>("ec_policy_forward_pa")(
+                h, params, feat, feat2, bf16, ids, vec, prev, h0, masks, T, N, wsp, ws, md, hv, hf, nullptr);
+        default:
+            return sym<int (*)(P, P, P, P, int, P, P, P, P, P, int, P, size_t, int, P, P, P, P, P, int, U, U, int, P, P, float, P)>("ec_policy_act_pa")(
+                h, params, feat, feat2, bf16, ids, vec, prev, h0, masks, N, wsp, ws, md == 2, hv, hf, actions, logp, values, 0, 1, 2, 3, expert,
+                emask, force ? 0.25f : 0.f, nullptr);
+        }
+    };
     g_log_copies = 1;
     if (reuse) {
-        rc = fwd(h, params, feat, feat2, bf16, goal, h0, masks, T, N, wsp, ws, 0 /* EC_POLICY_INFER */, hv, hf, nullptr);
+        rc = fwd(0 /* EC_POLICY_INFER */);
         printf("B %d\n", rc);
     }
-    if (!rc) rc = fwd(h, params, feat, feat2, bf16, goal, h0, masks, T, N, wsp, ws, reuse ? 2 /* EC_POLICY_INFER_REUSE */ : mode != 0, hv, hf, nullptr);
+    if (!rc) rc = fwd(reuse ? 2 /* EC_POLICY_INFER_REUSE */ : mode != 0);
     if (learn_pass) {
         printf("F %d\n", rc);
         const P dhv = fake(1u << 20), dhfin = dhf ? fake(1u << 24) : nullptr, grads = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4);
@@ -310,10 +355,57 @@ static int run_pooled(const int* v) {
     return rc;
 }
 
+// v: the nine ec_two_view_cfg fields (in_channels spatial hidden attn_hidden num_actions prev_action_dims prev_action_null rnn_type
+// num_layers), then T, N, mode, reuse, inplace, act
+static int run_two_view(const int* v) {
+    typedef void* P;
+    const int T = v[9], N = v[10], mode = v[11], reuse = v[12], inplace = v[13], act = v[14];
+    const bool learn_pass = mode == 2;
+    if (mode < 0 || mode > 2 || (reuse && mode != 0) || act < 0 || act > 2 || (act && (mode != 0 || T != 1))) return -100;
+    void* h = nullptr;
+    int cfg[9];
+    memcpy(cfg, v, sizeof cfg);                         // ec_two_view_cfg: nine ints in this order
+    int rc = sym<int (*)(P*, const int*)>("ec_policy_create_two_view")(&h, cfg);
+    if (rc) return rc;
+    const size_t ws = sym<size_t (*)(P, int, int, int)>("ec_policy_workspace_bytes")(h, T, N, mode != 0);
+    printf("W %zu\n", ws);
+    const P params = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4), u = fake(1u << 30), w = fake(1u << 30);
+    const P prev = v[5] ? fake(1u << 20) : nullptr;
+    const P h0 = fake(1u << 24), masks = fake(1u << 20), wsp = fake(ws), hv = fake(1u << 24), hf = inplace ? h0 : fake(1u << 24);
+    const P actions = fake(1u << 20), logp = fake(1u << 20), expert = act == 2 ? fake(1u << 20) : nullptr, emask = act == 2 ? fake(1u << 20) : nullptr;
+    auto fwd = [&](int md) -> int {
+        if (!act)
+            return sym<int (*)(P, P, P, P, P, P, P, int, int, P, size_t, int, P, P, P)>("ec_policy_forward_two_view")(
+                h, params, u, w, prev, h0, masks, T, N, wsp, ws, md, hv, hf, nullptr);
+        return sym<int (*)(P, P, P, P, P, P, P, int, P, size_t, int, P, P, P, P, P, int, uint64_t, uint64_t, int, P, P, float, P)>(
+            "ec_policy_act_two_view")(h, params, u, w, prev, h0, masks, N, wsp, ws, md == 2, hv, hf, actions, logp, nullptr, 0, 1, 2, 3, expert,
+                                      emask, act == 2 ? 0.25f : 0.f, nullptr);
+    };
+    g_log_copies = 1;
+    if (reuse) {
+        rc = fwd(0 /* EC_POLICY_INFER */);
+        printf("B %d\n", rc);
+    }
+    if (!rc) rc = fwd(reuse ? 2 /* EC_POLICY_INFER_REUSE */ : mode != 0);
+    if (learn_pass) {
+        printf("F %d\n", rc);
+        const P dhv = fake(1u << 24), grads = fake(sym<size_t (*)(P)>("ec_policy_flat_size")(h) * 4);
+        if (!rc)
+            rc = sym<int (*)(P, P, P, P, int, P, int, int, P, size_t, P, P, P, P)>("ec_policy_backward2")(h, params, u, w, 1, masks, T, N, wsp, ws, dhv,
+                                                                                                        nullptr, grads, nullptr);
+    }
+    g_log_copies = 0;
+    sym<void (*)(P)>("ec_policy_destroy")(h);
+    return rc;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 2) { fprintf(stderr, "usage: launch_log LIB [--args N | --args-of SUBSTR N] < commands\n"); return 2; }
-    if (argc >= 4 && !strcmp(argv[2], "--args")) g_dump_args = atoi(argv[3]);
-    if (argc >= 5 && !strcmp(argv[2], "--args-of")) { g_dump_of = argv[3]; g_dump_args = atoi(argv[4]); }
+    if (argc < 2) { fprintf(stderr, "usage: launch_log LIB [--args N | --args-of SUBSTR N [INDEX] ...] < commands\n"); return 2; }
+    if (argc >= 4 && !strcmp(argv[2], "--args")) g_dumps.push_back({"conv_igemm", 0, atoi(argv[3])});
+    for (int i = 2; i + 2 < argc && !strcmp(argv[i], "--args-of"); i += 3) {
+        g_dumps.push_back({argv[i + 1], 0, atoi(argv[i + 2])});
+        if (i + 3 < argc && strcmp(argv[i + 3], "--args-of")) g_dumps.back().index = atoi(argv[i++ + 3]);
+    }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_LOCAL);
     if (!g_lib) { fprintf(stderr, "launch_log: %s\n", dlerror()); return 2; }
     {
@@ -331,18 +423,20 @@ int main(int argc, char** argv) {
         if (!(ss >> cmd)) continue;
         line[strcspn(line, "\n")] = 0;
         printf("C %s\n", line);
-        int v[20] = {0}, n = 0, rc = -100;
+        int v[24] = {0}, n = 0, rc = -100;
         std::string kind;
         if (cmd == "trunk" || cmd == "tower") ss >> kind;
-        const int nmax = cmd == "policy" ? 20 : cmd == "pooled" ? 19 : cmd == "f32" ? 18 : cmd == "tower" ? 9 : 10;
+        const int nmax = cmd == "policy" ? 23 : cmd == "pooled" ? 19 : cmd == "twoview" ? 15 : cmd == "f32" ? 18 : cmd == "tower" ? 9 : 10;
         while (n < nmax && ss >> v[n]) ++n;
         std::string input;
         if (cmd == "tower" && n == 9 && ss >> input) {
             rc = run_tower(kind, v, input);
-        } else if (cmd == "policy" && n >= 18 && n <= 20) {
+        } else if (cmd == "policy" && n >= 18 && n <= 23 && n != 21) {
             rc = run_policy(v);
         } else if (cmd == "pooled" && n == 19) {
             rc = run_pooled(v);
+        } else if (cmd == "twoview" && n == 15) {
+            rc = run_two_view(v);
         } else if (cmd == "conv" && n == 10) {
             const P r = v[8] ? resb : nullptr;
             if (v[9] == 0)
