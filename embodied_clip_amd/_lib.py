@@ -164,6 +164,12 @@ SIGNATURES = {
     "ec_ln_fold_bf16": (c_int, [c_void_p] * 7 + [c_int] * 2 + [c_void_p]),
     "ec_gemm_bf16_ln": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 2 + [c_int, c_void_p, C.POINTER(c_int), c_void_p]),
     "ec_bf16_to_f32": (c_int, [c_void_p, c_void_p, C.c_long, C.c_long, C.c_long, c_void_p]),
+    # the class embedding alone (ClipViTEmbedder, class_emb_only): both routes behind one call, and the CLS tail's kernels one at a time
+    "ec_vit_cls_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "ec_vit_embed_cls": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ec_gemm_rows_bf16": (c_int, [c_void_p, C.c_long, c_void_p, c_void_p, c_void_p, C.c_long, c_void_p, C.c_long] + [c_int] * 5 + [c_void_p]),
+    "ec_vit_cls_rows_ln": (c_int, [c_void_p, C.c_long] + [c_void_p] * 3 + [c_int, c_int, c_void_p]),
+    "ec_vit_cls_attn": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "ec_attnpool_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ec_attnpool_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 8 + [c_size_t, c_void_p,
                                     c_void_p]),

@@ -236,12 +236,18 @@ class ClipResNetPreprocessor(_PreprocessorBase):
 class ClipViTPreprocessor(_PreprocessorBase):
     """[U] ``ClipViTPreprocessor(rgb_input_uuid, clip_model_type, class_emb_only, device, device_ids, output_uuid)``
     (allenact master; named by BASELINE.json).  ``process(obs)``: fp32 NHWC [N,224,224,3] ->
-    fp32 [N,50,768] tokens after ``resblocks[:-1]`` (``class_emb_only`` -> [N,768])."""
+    fp32 [N,50,768] tokens after ``resblocks[:-1]`` (``class_emb_only`` -> [N,768]).
+    ``cls_shortcut`` (with ``class_emb_only``): the class vector through ``ViTEmbedder.embed_cls`` -- the same roundings, not
+    bit-identical to token 0 of the full forward; the default keeps today's path."""
 
     def __init__(self, rgb_input_uuid: str, clip_model_type: str, class_emb_only: bool = False,
                  device: Optional[torch.device] = None, device_ids: Optional[List[torch.device]] = None,
-                 output_uuid: str = "rgb_clip_vit", state_dict=None, weights_path: Optional[str] = None, **kwargs: Any):
+                 output_uuid: str = "rgb_clip_vit", state_dict=None, weights_path: Optional[str] = None,
+                 cls_shortcut: bool = False, **kwargs: Any):
         assert clip_model_type in ("ViT-B/32", "ViT-B/16", "ViT-L/14")
+        if cls_shortcut and not class_emb_only:
+            raise ValueError("cls_shortcut=True belongs to class_emb_only=True: the shortcut computes the class vector alone")
+        self.cls_shortcut = bool(cls_shortcut)
         # (tokens, width, heads): ViT-B/32 runs the 64-token MFMA attention core (benchmarked); B/16 and L/14 run the
         # general LDS attention core -- functional, not tuned
         tokens, width, self._heads = {"ViT-B/32": (50, 768, 12), "ViT-B/16": (197, 768, 12),
@@ -267,4 +273,6 @@ class ClipViTPreprocessor(_PreprocessorBase):
     def process(self, obs: Dict[str, Any], *args: Any, **kwargs: Any) -> torch.Tensor:
         x = obs[self.input_uuids[0]].to(self.device, dtype=torch.float32).contiguous()
         m = self.vit
+        if self.cls_shortcut:
+            return m.embed_cls(x)
         return m.to_f32(m.forward(x), self.class_emb_only)

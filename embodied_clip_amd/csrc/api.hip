@@ -56,6 +56,7 @@ EcConfig read_config() {
     c.rgbd_joint = env_int("EC_RGBD_JOINT", 1);
     c.vit_wide = env_int("EC_VIT_WIDE", 1);
     c.vit_bm192 = env_int("EC_VIT_BM192", 1);
+    c.vit_cls_tail = env_int("EC_VIT_CLS_TAIL", -1);
     return c;
 }
 }  // namespace

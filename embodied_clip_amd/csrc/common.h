@@ -240,6 +240,9 @@ struct EcConfig {
     // --- ViT / text GEMMs (ec_gemm_bf16_ln8).  NOT part of ec_config_hash(): the profile summaries under profiles/ are keyed by the hash as it was ---
     int vit_wide;         // EC_VIT_WIDE      (1)   0: 128-wide tiles only, 2: 256-wide wherever N allows
     int vit_bm192;        // EC_VIT_BM192     (1)   0: no 192-row tiles
+    int vit_cls_tail;     // EC_VIT_CLS_TAIL  (-1)  ec_vit_embed_cls: -1 the route the library's rule picks per (tokens, frames), 0 the general route
+                          //                        (whole last block, then row 0), 1 the CLS-only last block (vit_cls.hip).  NOT part of
+                          //                        ec_config_hash(); ec_vit_plan_hash mixes it in when it is set
 };
 // Fixed since round 5 (measured winners; the A/B numbers live in docs/experiments.md): 768 persistent workgroups, residual 1x1
 // launches of K 512..2047 with < 100 256-wide tiles on 128-wide 8-wave tiles, low-fill limits 100 tiles / K >= 1024, ring-mode
@@ -428,7 +431,10 @@ void ec_tv_fwd_launch(const ec_tv_fwd_args& a, hipStream_t s);
 void ec_tv_bwd_launch(const void* u, const void* w, const float* w2, const float* dv, const float* a, const float* act, float* scratch,
                       float* dWe, float* dbe, float* dWa, float* dba, float* dw2, float* db2, const ec_tv_shape& q, hipStream_t s);
 
-#define EC_CHECK_LAUNCH()                                  \
+// vit_cls.hip: the most keys cls_attn_kernel takes (vit.hip holds it equal to the general attention core's limit)
+constexpr int EC_CLS_ATTN_MAX_TOKENS = 512;
+
+#define EC_CHECK_LAUNCH()                             \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \
         if (e__ != hipSuccess) return EC_ERR_LAUNCH;        \

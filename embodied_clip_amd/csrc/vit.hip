@@ -632,9 +632,9 @@ int build_lnfold(ec_lnfold& fold, const uint16_t* w, const float* f, int layers,
 // fold != nullptr (built by build_lnfold): ln_1 / ln_2 are folded into the QKV / c_fc GEMMs -- no LayerNorm launch, no
 // normalised copy of x: the GEMMs multiply the RAW rows against W diag(gamma) and apply (mean, rstd) in their epilogue; the rows'
 // statistics come as partial records out of the epilogue of the GEMM that produced x (out_proj / c_proj + residual), `stats`
-// holding `np` records per row on entry (the caller's: ln_pre's output rows, or row_stats_kernel).
+// holding `np` records per row on entry (the caller's: ln_pre's output rows, or row_stats_kernel) and on return (the last c_proj's).
 int run_blocks(const uint16_t*& w, const float*& f, int layers, int heads, uint16_t* x, uint16_t* hbuf, uint16_t* qkv,
-               uint16_t* att, uint16_t* mlp, int B, int L, int D, bool causal, const ec_lnfold* fold, float* stats, int np,
+               uint16_t* att, uint16_t* mlp, int B, int L, int D, bool causal, const ec_lnfold* fold, float* stats, int& np,
                ec_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const long rows = (long)B * L;
@@ -669,6 +669,56 @@ int run_blocks(const uint16_t*& w, const float*& f, int layers, int heads, uint1
         RC(ec_gemm_bf16(mlp, wpr, bpr, x, x, (int)rows, D, 4 * D, EC_ACT_NONE, stream));     // x += c_proj(...)
     }
     return EC_OK;
+}
+
+// The class rows' buffers of run_cls_block (bf16): ln_1 / q / attention / residual stream / ln_2 rows [B, D] each, the MLP's [B, 4D]
+struct cls_bufs { uint16_t *hcls, *q, *att, *x1, *h2, *mlp; };
+
+// ONE ResidualAttentionBlock of which only the class row of every frame is wanted (the last block ClipViTEmbedder runs when it
+// returns `x[:, 0, :]`): K / V for all B*L rows in one GEMM, everything else on B rows (vit_cls.hip).  w / f point at the block's
+// weights / params, x [B*L, D] is the stream after the blocks before it (read only), `stats` its np records per row; (wg, fg) the
+// block's folded copies or null.  emb f32 [B, D] receives bf16 values.  8 launches either way:
+//   folded    kv = ln8 GEMM on the raw stream (rows D..3D of Wg_qkv) | ln_1 of the class rows | q | attention | out_proj + class row |
+//             ln_2 | c_fc + QuickGELU | c_proj + residual
+//   unfolded  ln_1 of ALL rows | kv GEMM | q from the class rows of the normalised copy (pitch L D) | ... the same five
+int run_cls_block(const uint16_t* w, const float* f, int heads, const uint16_t* x, uint16_t* hbuf, uint16_t* kv, const cls_bufs& c,
+                  int B, int L, int D, const uint16_t* wg, const float* fg, const float* stats, int np, float* emb, ec_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const long rows = (long)B * L, LD = (long)L * D;
+    const size_t Dz = (size_t)D;
+    const float *ln1w = f, *ln1b = f + D, *bqkv = f + 2 * D, *bo = bqkv + 3 * D, *ln2w = bo + D, *ln2b = ln2w + D;
+    const float *bfc = ln2b + D, *bpr = bfc + 4 * D;
+    const uint16_t *wqkv = w, *wo = w + 3 * Dz * Dz, *wfc = wo + Dz * Dz, *wpr = wfc + 4 * Dz * Dz;
+    if (wg) {
+        RC(ec_gemm_bf16_ln8(x, wg + Dz * Dz, fg + 3 * Dz + Dz, nullptr, kv, (int)rows, 2 * D, D, EC_ACT_NONE, fg + Dz, stats, np, nullptr,
+                            nullptr, stream));
+        RC(ec_vit_cls_rows_ln(x, LD, ln1w, ln1b, c.hcls, B, D, stream));
+        RC(ec_gemm_rows_bf16(c.hcls, D, wqkv, bqkv, nullptr, 0, c.q, D, B, D, D, EC_ACT_NONE, 0, stream));
+    } else {
+        layernorm_launch(x, ln1w, ln1b, hbuf, rows, D, s);
+        RC(ec_gemm_bf16(hbuf, wqkv + Dz * Dz, bqkv + D, nullptr, kv, (int)rows, 2 * D, D, EC_ACT_NONE, stream));
+        RC(ec_gemm_rows_bf16(hbuf, LD, wqkv, bqkv, nullptr, 0, c.q, D, B, D, D, EC_ACT_NONE, 0, stream));
+    }
+    RC(ec_vit_cls_attn(c.q, kv, c.att, B, L, D, heads, stream));
+    RC(ec_gemm_rows_bf16(c.att, D, wo, bo, x, LD, c.x1, D, B, D, D, EC_ACT_NONE, 0, stream));                     // x1 = x[:, 0] + out_proj(...)
+    RC(ec_vit_cls_rows_ln(c.x1, D, ln2w, ln2b, c.h2, B, D, stream));
+    RC(ec_gemm_rows_bf16(c.h2, D, wfc, bfc, nullptr, 0, c.mlp, 4 * D, B, 4 * D, D, EC_ACT_QUICKGELU, 0, stream));
+    RC(ec_gemm_rows_bf16(c.mlp, 4 * D, wpr, bpr, c.x1, D, emb, D, B, D, 4 * D, EC_ACT_NONE, 1, stream));          // bf16(x1 + c_proj(...)) as f32
+    return EC_OK;
+}
+static_assert(EC_CLS_ATTN_MAX_TOKENS == MHA_GENERAL_MAX_TOKENS, "cls_attn_kernel takes every token count the towers accept");
+
+// ec_vit_embed_cls's route for `batch` frames: EC_VIT_CLS_TAIL forces it; unset, the rule below.
+// Rule (tools/bench_vit_cls.py, profiles/vit_cls_bench.txt; ms per call, tail against general): more than 64 tokens -- where the
+// last block's attention is the general core -- take the tail: 197 tokens 4.51 against 4.82-4.84 at 32 frames, 14.01-14.03 against
+// 15.14-15.19 at 128.  Up to 64 tokens the general route stays: 50 tokens 0.99-1.00 against 0.93-1.03 at 32 frames, 1.30-1.32
+// against 1.32-1.37 at 64, 1.74-1.75 against 1.74-1.75 at 128 -- no difference beyond the spread.
+inline bool cls_tail_route(const ec_vit* h, int batch) {
+    if (h->layers < 1) return false;
+    const int sw = ec_config().vit_cls_tail;
+    if (sw >= 0) return sw != 0;
+    (void)batch;
+    return h->L > 64;
 }
 }  // namespace
 
@@ -711,6 +761,9 @@ extern "C" uint64_t ec_vit_plan_hash(const ec_vit_t* h) {
     };
     mix(ec_version()); mix((long)ec_config_hash());
     mix(h->width); mix(h->layers); mix(h->heads); mix(h->patch); mix(h->res); mix(h->L); mix(h->conv8_min_tiles);
+    // ec_vit_embed_cls's route when EC_VIT_CLS_TAIL forces one (unset, the rule is the library's: ec_version covers it, and the hash --
+    // the key of the committed summaries of ec_vit_forward's plan -- is what it was)
+    if (ec_config().vit_cls_tail >= 0) mix(0x636c7300 + (ec_config().vit_cls_tail != 0));
     return x;
 }
 
@@ -721,11 +774,16 @@ extern "C" size_t ec_vit_workspace_bytes(const ec_vit_t* h, int batch) {
            al256(B * L * D * 2) + al256(B * L * 4 * D * 2) + al256(B * L * 8 * 16);   // (+ the rows' LayerNorm records: 8 x {sum, M2, count, -})
 }
 
-extern "C" int ec_vit_forward(const ec_vit_t* h, const float* rgb, int batch, void* workspace, size_t ws_bytes,
-                              void* tokens_bf16, ec_stream_t stream) {
-    if (!h || !rgb || !workspace || !tokens_bf16) return EC_ERR_ARG;
-    if (batch <= 0) return EC_ERR_SHAPE;
-    if (ws_bytes < ec_vit_workspace_bytes(h, batch)) return EC_ERR_WORKSPACE;
+namespace {
+// where vit_tower left off: the next block's weights / params, the workspace buffers, the stream's records per row
+struct vit_state {
+    const uint16_t* w; const float* f;
+    uint16_t *hbuf, *qkv, *att, *mlp;
+    float* stats; int np;
+};
+// patch embedding, token assembly + ln_pre and the first `nblocks` blocks into x [B*L, D] (arguments checked by the callers;
+// workspace: ec_vit_workspace_bytes)
+int vit_tower(const ec_vit* h, const float* rgb, int batch, void* workspace, uint16_t* x, int nblocks, vit_state& st, ec_stream_t stream) {
     const ec_min_tiles_scope mint_scope(h->conv8_min_tiles);   // this handle's dispatch threshold, for this call only
     hipStream_t s = (hipStream_t)stream;
     const int D = h->width, P = h->patch, G = h->grid, L = h->L, B = batch;
@@ -739,7 +797,6 @@ extern "C" int ec_vit_forward(const ec_vit_t* h, const float* rgb, int batch, vo
     uint16_t* att = (uint16_t*)p;     p += al256((size_t)B * L * D * 2);
     uint16_t* mlp = (uint16_t*)p;     p += al256((size_t)B * L * 4 * D * 2);
     float* stats = (float*)p;
-    uint16_t* x = (uint16_t*)tokens_bf16;   // residual stream lives in the output buffer
     const uint16_t* w = h->w;
     const float* f = h->f;
     const float *cls = f, *pos = f + D, *lnpre_w = pos + (size_t)L * D, *lnpre_b = lnpre_w + D;
@@ -757,7 +814,58 @@ extern "C" int ec_vit_forward(const ec_vit_t* h, const float* rgb, int batch, vo
     RC(ec_gemm_bf16(patches, w, nullptr, nullptr, pemb, B * G2, D, Kp, EC_ACT_NONE, stream));
     w += (size_t)D * Kp;
     assemble_launch(pemb, cls, pos, lnpre_w, lnpre_b, x, h->fold.ok ? stats : nullptr, B, L, D, s);
-    RC(run_blocks(w, f, h->layers, h->heads, x, hbuf, qkv, att, mlp, B, L, D, false, &h->fold, stats, 1, stream));
+    int np = 1;
+    RC(run_blocks(w, f, nblocks, h->heads, x, hbuf, qkv, att, mlp, B, L, D, false, &h->fold, stats, np, stream));
+    st = vit_state{w, f, hbuf, qkv, att, mlp, stats, np};
+    return EC_OK;
+}
+}  // namespace
+
+extern "C" int ec_vit_forward(const ec_vit_t* h, const float* rgb, int batch, void* workspace, size_t ws_bytes,
+                              void* tokens_bf16, ec_stream_t stream) {
+    if (!h || !rgb || !workspace || !tokens_bf16) return EC_ERR_ARG;
+    if (batch <= 0) return EC_ERR_SHAPE;
+    if (ws_bytes < ec_vit_workspace_bytes(h, batch)) return EC_ERR_WORKSPACE;
+    vit_state st;
+    RC(vit_tower(h, rgb, batch, workspace, (uint16_t*)tokens_bf16, h->layers, st, stream));   // residual stream lives in the output buffer
+    EC_CHECK_LAUNCH();
+    return EC_OK;
+}
+
+extern "C" size_t ec_vit_cls_workspace_bytes(const ec_vit_t* h, int batch) {
+    if (!h || batch <= 0) return 0;
+    const size_t D = h->width, L = h->L, B = batch;
+    // ec_vit_forward's workspace | the token stream | the class rows' buffers (cls_bufs)
+    return ec_vit_workspace_bytes(h, batch) + al256(B * L * D * 2) + 5 * al256(B * D * 2) + al256(B * 4 * D * 2);
+}
+
+extern "C" int ec_vit_embed_cls(const ec_vit_t* h, const float* rgb, int batch, void* workspace, size_t ws_bytes, float* out,
+                                ec_stream_t stream) {
+    if (!h || !rgb || !workspace || !out) return EC_ERR_ARG;
+    if (batch <= 0) return EC_ERR_SHAPE;
+    if (ws_bytes < ec_vit_cls_workspace_bytes(h, batch)) return EC_ERR_WORKSPACE;
+    const int D = h->width, L = h->L, B = batch;
+    const size_t fwd = ec_vit_workspace_bytes(h, batch);
+    unsigned char* p = (unsigned char*)workspace + fwd;
+    uint16_t* x = (uint16_t*)p; p += al256((size_t)B * L * D * 2);
+    if (!cls_tail_route(h, batch)) {
+        RC(ec_vit_forward(h, rgb, batch, workspace, fwd, x, stream));
+        return ec_bf16_to_f32(x, out, B, D, (long)L * D, stream);
+    }
+    cls_bufs c;
+    c.hcls = (uint16_t*)p; p += al256((size_t)B * D * 2);
+    c.q = (uint16_t*)p;    p += al256((size_t)B * D * 2);
+    c.att = (uint16_t*)p;  p += al256((size_t)B * D * 2);
+    c.x1 = (uint16_t*)p;   p += al256((size_t)B * D * 2);
+    c.h2 = (uint16_t*)p;   p += al256((size_t)B * D * 2);
+    c.mlp = (uint16_t*)p;
+    const ec_min_tiles_scope mint_scope(h->conv8_min_tiles);
+    vit_state st;
+    RC(vit_tower(h, rgb, batch, workspace, x, h->layers - 1, st, stream));
+    const bool folded = h->fold.ok;
+    const size_t Dz = (size_t)D, l = (size_t)h->layers - 1;
+    RC(run_cls_block(st.w, st.f, h->heads, x, st.hbuf, st.qkv, c, B, L, D, folded ? h->fold.w + l * 7 * Dz * Dz : nullptr,
+                     folded ? h->fold.f + l * 14 * Dz : nullptr, st.stats, st.np, out, stream));
     EC_CHECK_LAUNCH();
     return EC_OK;
 }
@@ -831,7 +939,8 @@ extern "C" int ec_text_forward(const ec_text_t* h, const int32_t* tokens, int ba
                        D, h->vocab);
     if (h->fold.ok)   // the embedding rows' LayerNorm records for block 0's folded ln_1
         row_stats_launch(x, stats, rows, D, s);
-    RC(run_blocks(w, f, h->layers, h->heads, x, hbuf, qkv, att, mlp, B, L, D, true, &h->fold, stats, 1, stream));
+    int np = 1;
+    RC(run_blocks(w, f, h->layers, h->heads, x, hbuf, qkv, att, mlp, B, L, D, true, &h->fold, stats, np, stream));
     hipLaunchKernelGGL(eot_layernorm_kernel, dim3((unsigned)B), dim3(64), 0, s, tokens, x, f, f + D, eot, L, D, 1e-5f);
     RC(ec_gemm_bf16(eot, w, nullptr, nullptr, emb, B, E, D, EC_ACT_NONE, stream));          // @ text_projection
     RC(ec_bf16_to_f32(emb, out, B, E, E, stream));

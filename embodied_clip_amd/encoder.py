@@ -552,6 +552,23 @@ class ViTEmbedder:
         return out
 
     @_lib.on_device
+    def embed_cls(self, rgb: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rgb device fp32 [B,R,R,3] -> the class embedding fp32 [B,D] (bf16 values): token 0 after the blocks that run
+        (``ec_vit_embed_cls``: the CLS-only last block or the whole tower, as the library's rule / ``EC_VIT_CLS_TAIL`` picks).
+        ``out`` may be a contiguous [B,D] fp32 view (a rollout slice).  Its own workspace, apart from ``forward``'s."""
+        assert rgb.is_cuda and rgb.dtype == torch.float32 and rgb.is_contiguous()
+        B = rgb.shape[0]
+        need = self.lib.ec_vit_cls_workspace_bytes(self.h, B)
+        if getattr(self, "_ws_cls", None) is None or self._ws_cls.numel() < need:
+            self._ws_cls = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = torch.empty((B, self.D), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, self.D)
+        _lib.check(self.lib.ec_vit_embed_cls(self.h, rgb.data_ptr(), B, self._ws_cls.data_ptr(), self._ws_cls.numel(),
+                                             out.data_ptr(), _lib.stream_ptr()), "ec_vit_embed_cls")
+        return out
+
+    @_lib.on_device
     def to_f32(self, tokens: torch.Tensor, class_emb_only: bool = False) -> torch.Tensor:
         B = tokens.shape[0]
         if class_emb_only:

@@ -242,8 +242,10 @@ def check_net(net: str, pooling: str, sensors, goal_ids: bool, encoder: str, dep
             raise ValueError("sensors=... belongs to net='pooled'")
         return False, None, ()
     sensors = tuple(int(k) for k in sensors)
-    if pooling not in ("attnpool", "avgpool"):
-        raise ValueError(f"pooling={pooling!r}: 'attnpool' or 'avgpool'")
+    if pooling not in ("attnpool", "avgpool", "cls"):
+        raise ValueError(f"pooling={pooling!r}: 'attnpool', 'avgpool' or 'cls'")
+    if pooling == "cls" and encoder != "vit":
+        raise ValueError(f"pooling='cls' is the ViT's class embedding ([U] ClipViTPreprocessor, class_emb_only): encoder='vit', not {encoder!r}")
     if depth and pooling != "avgpool":
         # [U] ResNetCLIPEncoder removes the attention pool when it encodes rgb + depth: the two maps are summed and average-pooled
         raise ValueError("net='pooled' with depth=True: the RGB-D encoder sums the two towers' maps and average-pools them; use pooling='avgpool'")
@@ -253,12 +255,13 @@ def check_net(net: str, pooling: str, sensors, goal_ids: bool, encoder: str, dep
         raise ValueError("net='pooled' with zeroshot=True: the zero-shot fusion policy is another net")
     if goal_in:
         raise ValueError("net='pooled' with goal_in > 0: coordinate goals reach the pooled net as sensors=(k,)")
-    if encoder == "vit":
-        raise ValueError("net='pooled' with encoder='vit': the ViT's CLS vector is not built")
+    if encoder == "vit" and pooling != "cls":
+        raise ValueError(f"net='pooled' with encoder='vit', pooling={pooling!r}: the ViT has no attention pool and no feature map to average; "
+                         "use pooling='cls' (its class embedding)")
     if encoder in IMAGENET_ENCODERS and pooling == "attnpool":
         raise ValueError("net='pooled', pooling='attnpool': the ImageNet towers have no attention pool; use pooling='avgpool'")
-    if encoder not in ("rn50",) and encoder not in IMAGENET_ENCODERS:
-        raise ValueError(f"net='pooled': encoder 'rn50' (both poolings) or an ImageNet tower ('avgpool'), not {encoder!r}")
+    if encoder not in ("rn50", "vit") and encoder not in IMAGENET_ENCODERS:
+        raise ValueError(f"net='pooled': encoder 'rn50' ('attnpool' / 'avgpool'), an ImageNet tower ('avgpool') or 'vit' ('cls'), not {encoder!r}")
     if len(sensors) > 3 or any(k < 1 for k in sensors) or sum(sensors) > 8:
         raise ValueError(f"sensors={sensors!r}: at most 3 sensors of at least one float each, 8 floats in all")
     if not goal_ids and not sensors:
@@ -455,8 +458,15 @@ class _SlicedActor:
             # BASELINE config 3 (builder-defined fusion, SURVEY.md §8d note): ClipViTEmbedder tokens, CLS dropped,
             # the 49 patch tokens are the 7x7 channels-last "feature map" [n,49,768] of the goal encoder
             sd = encoder_sd if encoder_sd is not None else syn.vit_visual_state_dict(0)
-            encs = self._encoder_handles(ns, lambda w: ViTEmbedder(sd, device=d, weights_from=w))
-            self.S, self.C = 7, encs[0].D
+            if self._embed == "cls":
+                # the pooled net over the class embedding ([U] ClipViTPreprocessor, class_emb_only): one [D] vector per frame whatever
+                # the token count, so any tower geometry of 64-wide heads (ViT-B/32, B/16, L/14) works; no token buffer
+                heads = int(sd["class_embedding"].shape[0]) // 64
+                encs = self._encoder_handles(ns, lambda w: ViTEmbedder(sd, device=d, heads=heads, weights_from=w))
+                self.S, self.C = 1, encs[0].D
+            else:
+                encs = self._encoder_handles(ns, lambda w: ViTEmbedder(sd, device=d, weights_from=w))
+                self.S, self.C = 7, encs[0].D
         else:
             raise ValueError(encoder)
         if self._embed == "avgpool":      # AdaptiveAvgPool2d(1) of the trunk output (ec_spatial_mean_bf16): D = the trunk's channels
@@ -523,8 +533,8 @@ class _SlicedActor:
             sl.feat = torch.empty((feat_steps, n, S2, self.C), dtype=torch.float32 if self._embed else torch.bfloat16, device=d)
             sl.feat2 = torch.empty_like(sl.feat) if self.dual else None      # the depth tower's features
             sl.trunk_out = (torch.empty((n, self.trunk_S, self.trunk_S, self.trunk_C), dtype=torch.bfloat16, device=d)
-                            if self._embed and not self.depth else None)      # (embed_rgbd keeps its maps in its own workspace)
-            sl.tok = (torch.empty((n, encs[i].L, encs[i].D), dtype=torch.bfloat16, device=d) if encoder == "vit" else None)
+                            if self._embed and self._embed != "cls" and not self.depth else None)   # (embed_rgbd / embed_cls keep theirs in their own workspace)
+            sl.tok = (torch.empty((n, encs[i].L, encs[i].D), dtype=torch.bfloat16, device=d) if encoder == "vit" and self._embed != "cls" else None)
             sl.ws_act = torch.empty(self.policy.workspace_bytes(1, n, False), dtype=torch.uint8, device=d)
             sl.act_tables_valid = False     # weight-derived tables in ws_act (rebuilt by the first act step after an update)
             if frames_host:   # double-buffered device staging of the slice's frames + its own copy stream (SDMA)
@@ -621,6 +631,8 @@ class _SlicedActor:
             # the pooled RGB-D agent: both frames of every pair through the plan in one pass, the two maps summed and average-pooled
             # straight into the rollout slice (the depth wire form is synthetic.normalize_depth: scale 1, shift 0)
             sl.enc.embed_rgbd(src, dep[sl.o:sl.o + sl.n], sl.feat[t].view(sl.n, self.C))
+        elif self._embed == "cls":
+            sl.enc.embed_cls(src, sl.feat[t].view(sl.n, self.C))      # the class embedding straight into the rollout slice
         elif self._embed:
             (sl.enc.forward_u8 if src.dtype == torch.uint8 else sl.enc.forward)(src, sl.trunk_out)
             if self._embed == "attnpool":
@@ -694,7 +706,13 @@ class Worker(_SlicedActor):
         action, the recurrent core.  The rollout buffer is fp32 ``[T + 1, n, 1, D]``.  Every ``loss`` mode, teacher forcing, up to
         256 actions, ``prev_actions``, ``rnn_type``, ``rnn_layers``, ``num_mini_batch``, ``sync_actions`` and checkpoints work; a
         checkpoint of another net is refused by tensor name.  ``ValueError`` before any allocation with ``zeroshot``,
-        ``goal_in``, ``encoder="vit"`` or ``pooling="attnpool"`` on an ImageNet tower.
+        ``goal_in``, ``encoder="vit"`` with ``"attnpool"`` / ``"avgpool"``, or ``pooling="attnpool"`` on an ImageNet tower.
+
+        ``net="pooled", encoder="vit", pooling="cls"``: the same net over the ViT's class embedding ([U] ``ClipViTPreprocessor``
+        with ``class_emb_only``: token 0 after ``resblocks[:-1]``; the pairing with the pooled net is this project's).  One
+        ``ViTEmbedder.embed_cls`` call per slice and env step writes fp32 ``[n, D]`` straight into the rollout slice: no token
+        buffer, D floats per frame whatever the token count, and an ``encoder_sd`` of ViT-B/16 or ViT-L/14 geometry works (heads =
+        D / 64).  ``pooling="cls"`` with any other encoder is a ``ValueError``.
 
         ``net="pooled", pooling="avgpool", depth=True`` (``encoder="rn50"``): the same net on RGB-D frames
         (readme_files/baselines_habitat.md:75; [U] habitat branch ``ResNetCLIPEncoder`` with rgb and depth, restated, parity

@@ -274,7 +274,8 @@ def main(argv=None) -> int:
     ap.add_argument("--net", default="goal_encoder", choices=("goal_encoder", "pooled", "two_view"),
                     help="pooled: the Habitat DD-PPO net over the pooled embedding (PolicyHandle.pooled); two_view: the rearrangement agent over the "
                          "current and the goal-state view (PolicyHandle.two_view)")
-    ap.add_argument("--pooling", default="attnpool", choices=("attnpool", "avgpool"), help="with --net pooled: how the tower is pooled")
+    ap.add_argument("--pooling", default="attnpool", choices=("attnpool", "avgpool", "cls"),
+                    help="with --net pooled: how the tower is pooled ('cls': the class embedding of --encoder vit)")
     ap.add_argument("--sensors", default="", metavar="K1,K2", help="with --net pooled: the widths of the env's float sensors, e.g. 2,2 (GPS, compass) or 3")
     ap.add_argument("--no-goal-ids", action="store_true", help="with --net pooled: no goal-id embedding (PointNav: --sensors 3)")
     ap.add_argument("--json", default=None, metavar="OUT", help="also write the info dict to this file")

@@ -1039,6 +1039,33 @@ int ec_vit_forward(const ec_vit_t* h, const float* rgb_nhwc, int batch, void* wo
 int ec_bf16_to_f32(const void* in, float* out, long rows, long row_len, long in_stride, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The class embedding alone ([U] allenact ClipViTEmbedder with class_emb_only: `x[:, 0, :]` after resblocks[:-1]):
+ * rgb f32 NHWC [B,R,R,3] -> out f32 [B, D], bf16 values (what ec_vit_forward + ec_bf16_to_f32 on row 0 deliver).
+ * Two routes: the general one (ec_vit_forward into the workspace, then row 0), and the CLS tail -- the last block that
+ * runs computes K / V for all tokens but q, the attention row, out_proj, ln_2 and the MLP for the B class rows only
+ * (vit_cls.hip).  EC_VIT_CLS_TAIL = 0 / 1 forces the general route / the tail; unset, the library's rule picks per
+ * (tokens, frames).  The two routes round at the same points but are not bit-identical.
+ *
+ * Stage entry points of the tail's kernels (arguments checked before any HIP call: NULL or a misaligned pointer ->
+ * EC_ERR_ARG, a bad shape or pitch -> EC_ERR_SHAPE):
+ *   ec_gemm_rows_bf16: out[M, N] = act(A[M, K] W[N, K]^T + bias (+ res)) for few rows: a workgroup owns 32 columns of up
+ *     to 128 rows and its four waves split K.  A bf16 at row pitch lda, W bf16 [N, K], bias f32 [N] or NULL, res bf16 at
+ *     row pitch ldr or NULL, out at row pitch ldo (pitches in elements).  act: EC_ACT_NONE | EC_ACT_QUICKGELU.
+ *     store: 0 bf16, 1 rounded to bf16 and written as f32, 2 f32.  K % 64 == 0, N % 32 == 0, lda % 8 == 0.
+ *   ec_vit_cls_rows_ln: nn.LayerNorm(D), eps 1e-5, of `rows` bf16 rows read at pitch `pitch` (elements) -> bf16 [rows, D].
+ *   ec_vit_cls_attn: one query per (frame, head): q bf16 [B, D], kv bf16 [B*L, 2D] (k | v) -> out bf16 [B, D];
+ *     softmax(q k^T / 8) v, D / heads == 64, 1 <= L <= 512.
+ * ---------------------------------------------------------------------- */
+size_t ec_vit_cls_workspace_bytes(const ec_vit_t* h, int batch);
+int ec_vit_embed_cls(const ec_vit_t* h, const float* rgb_nhwc, int batch, void* workspace, size_t ws_bytes, float* out,
+                     ec_stream_t stream);
+int ec_gemm_rows_bf16(const void* A, long lda, const void* W, const float* bias, const void* res, long ldr, void* out, long ldo,
+                      int M, int N, int K, int act, int store, ec_stream_t stream);
+int ec_vit_cls_rows_ln(const void* x, long pitch, const float* gamma, const float* beta, void* out, int rows, int D,
+                       ec_stream_t stream);
+int ec_vit_cls_attn(const void* q, const void* kv, void* out, int B, int L, int D, int heads, ec_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * [U] openai/CLIP AttentionPool2d.forward, the module the reference detaches and calls on the conv
  * features (primitive_probing/generate_data/thor_image_features.py:62,112): mean token + positional
  * embedding, q/k/v projections, 64-wide heads, softmax, c_proj; returns token 0 only, so only the
