@@ -13,9 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-SENT16 = 0x7FC1            # a bf16 NaN pattern no kernel here produces
-SENT32 = 0x7FC12345        # ... and an fp32 one
-GUARD = 256                # guard rows on either side: one tile
+from _guard import Guarded  # noqa: E402
+
 COL0 = 24                  # first column of a column-block output (16-byte aligned)
 
 
@@ -27,14 +26,8 @@ def run_case(R, _lib, lib, dev, case):
     res = op["res"].to(dev) if op["res"] is not None else None
     rp = res.data_ptr() if res is not None else None
     rows, N, ldo = d["rows"], d["Cout"], d["ldo"]
-    block = ldo > N
-    col0 = COL0 if block else 0
-    assert col0 + N <= ldo
-    if d["x3"]:
-        buf = torch.full((rows + 2 * GUARD, ldo), SENT32, dtype=torch.int32, device=dev)
-    else:
-        buf = torch.full((rows + 2 * GUARD, ldo), SENT16, dtype=torch.int16, device=dev)
-    out_ptr = buf.data_ptr() + (GUARD * ldo + col0) * buf.element_size()
+    o = Guarded(dev, rows, N, ldo, COL0 if ldo > N else 0, f32=d["x3"])
+    out_ptr = o.ptr
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if d["kind"] == "conv":
@@ -50,13 +43,8 @@ def run_case(R, _lib, lib, dev, case):
     _lib.check(rc, case["cmd"])
     torch.cuda.synchronize()
     gpu_s = time.perf_counter() - t0
-    o = buf.cpu()
-    body = o[GUARD:GUARD + rows, col0:col0 + N].contiguous()
+    body, guards_ok = o.read()
     got = body.view(torch.float32) if d["x3"] else body.view(torch.bfloat16)
-    sent = SENT32 if d["x3"] else SENT16
-    mask = torch.ones_like(o, dtype=torch.bool)
-    mask[GUARD:GUARD + rows, col0:col0 + N] = False
-    guards_ok = bool((o[mask] == sent).all())
     ref, bound = R.reference(case, op)
     ratio, at = R.worst_ratio(got, ref, bound)
     return dict(cmd=case["cmd"], instance=case["instance"], ratio=ratio, at=[at // N, at % N], guards_ok=guards_ok, gpu_s=gpu_s)

@@ -33,9 +33,8 @@ import zlib
 
 import torch
 
-UB = 2.0 ** -8
-U = 2.0 ** -24
-F64 = torch.float64
+from _bounds import F64, U, UB, bf16, randn as _randn, worst_ratio  # noqa: F401  (re-exported for the checks)
+
 ACT_NONE, ACT_RELU, ACT_QUICKGELU = 0, 1, 2
 CHUNK = 8192               # rows of A formed at a time
 
@@ -135,20 +134,6 @@ def cases_of(setting):
     return [c for c in CASES if c["setting"] == setting]
 
 
-def bf16(t):
-    """Round to bf16 (nearest even), keep the dtype of ``t``."""
-    return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
-
-
-def worst_ratio(got, ref, bound):
-    """-> (max |got - ref| / bound, flat index of that element), in float64 (0 / 0 counts as 0; a NaN counts as infinite)"""
-    err = (got.to(F64) - ref.to(F64)).abs()
-    r = torch.where(err == 0, torch.zeros_like(err), err / bound.to(F64))
-    r = torch.nan_to_num(r, nan=float("inf"))
-    i = int(r.argmax())
-    return float(r.reshape(-1)[i]), i
-
-
 def shape(case):
     """The command's numbers by name, the kernel rows M (before pooling), the output rows and the tile (rows MV, columns BN) of the
     case's instance."""
@@ -186,10 +171,6 @@ def reduced(case):
         M = int(f[1])
         f[1] = str(M if M <= 768 else 512 + (M % 256 or 76))
     return dict(case, cmd=" ".join(f))
-
-
-def _randn(seed, *shape_):
-    return torch.randn(*shape_, generator=torch.Generator().manual_seed(seed), dtype=torch.float32)
 
 
 def operands(case):

@@ -15,28 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-SENT16 = 0x7FC1            # a bf16 NaN pattern no kernel here produces
-SENT32 = 0x7FC12345        # ... and an fp32 one
-GUARD = 256                # guard rows on either side: one tile
-
-
-class Guarded:
-    """A [rows, n] output (bf16, or fp32 with f32=True) inside a sentinel-filled [rows + 2 GUARD, ld] buffer, from column col0 on."""
-
-    def __init__(self, dev, rows, n, ld=None, col0=0, f32=False):
-        self.rows, self.n, self.ld, self.col0, self.f32 = rows, n, ld or n, col0, f32
-        assert col0 + n <= self.ld
-        self.sent = SENT32 if f32 else SENT16
-        self.buf = torch.full((rows + 2 * GUARD, self.ld), self.sent, dtype=torch.int32 if f32 else torch.int16, device=dev)
-        self.ptr = self.buf.data_ptr() + (GUARD * self.ld + col0) * self.buf.element_size()
-
-    def read(self):
-        """-> (the output's bit patterns, guards bitwise intact)"""
-        o = self.buf.cpu()
-        body = o[GUARD:GUARD + self.rows, self.col0:self.col0 + self.n].contiguous()
-        mask = torch.ones_like(o, dtype=torch.bool)
-        mask[GUARD:GUARD + self.rows, self.col0:self.col0 + self.n] = False
-        return body, bool((o[mask] == self.sent).all())
+from _guard import SENT32, Guarded  # noqa: E402
 
 
 def _f3(values):

@@ -52,9 +52,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-UB = 2.0 ** -8
-U = 2.0 ** -24
-F64 = torch.float64
+from _bounds import F64, U, UB, bf16, worst_ratio  # noqa: F401  (worst_ratio: re-exported for the checks)
 
 SOURCES = ("stem_elementwise.hip", "stem7.hip", "stem_depth.hip", "resize.hip")        # under embodied_clip_amd/csrc
 TEMPLATES = ("stem_conv1_kernel", "stem7_pool_kernel", "stem_conv1_depth_kernel", "avgpool2_kernel", "nhwc_to_nchw_kernel",
@@ -152,11 +150,6 @@ def kernels_in_sources(root):
     return names
 
 
-def bf16(t):
-    """Round to bf16 (nearest even), keep the dtype of ``t``."""
-    return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
-
-
 def bf16_trunc(t):
     """fp32 -> bf16 by dropping the low 16 bits (the wrong rounding), as fp32."""
     return (t.to(torch.float32).contiguous().view(torch.int32) & -65536).view(torch.float32)
@@ -167,15 +160,6 @@ def f2bf_bits(t):
     u = t.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
     u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFFFFFF
     return (u >> 16).to(torch.int32).to(torch.int16)           # wraps to the same 16 bits
-
-
-def worst_ratio(got, ref, bound):
-    """-> (max |got - ref| / bound, flat index of that element), in float64 (0 / 0 counts as 0; a NaN counts as infinite)"""
-    err = (got.to(F64) - ref.to(F64)).abs()
-    r = torch.where(err == 0, torch.zeros_like(err), err / bound.to(F64))
-    r = torch.nan_to_num(r, nan=float("inf"))
-    i = int(r.argmax())
-    return float(r.reshape(-1)[i]), i
 
 
 def shape(case):

@@ -57,10 +57,8 @@ import zlib
 
 import torch
 
-U = 2.0 ** -24
-UB = 2.0 ** -8
-F64 = torch.float64
-F32 = torch.float32
+from _bounds import F32, F64, U, UB, bf16, randn as _randn, rel_l2, worst_ratio  # noqa: F401  (re-exported for the checks)
+
 GBK = 32
 A_BF16, B_BF16, RELU, ACCUMULATE, SPLIT_PARTS, P3 = 1, 2, 4, 8, 16, 32
 EC_ERR_ARG, EC_ERR_SHAPE, EC_ERR_UNSUPPORTED = -1, -2, -6
@@ -203,24 +201,6 @@ def is_gemm(name):
     return name.startswith("gemm_f32_kernel<") or name.startswith("gemm_x3_kernel<")
 
 
-def bf16(t):
-    """Round to bf16 (nearest even), keep the dtype of ``t``."""
-    return t.to(F32).to(torch.bfloat16).to(t.dtype)
-
-
-def worst_ratio(got, ref, bound):
-    """-> (max |got - ref| / bound, flat index of that element), in float64 (0 / 0 counts as 0; a NaN counts as infinite)"""
-    err = (got.to(F64) - ref.to(F64)).abs()
-    r = torch.where(err == 0, torch.zeros_like(err), err / bound.to(F64))
-    r = torch.nan_to_num(r, nan=float("inf"))
-    i = int(r.argmax())
-    return float(r.reshape(-1)[i]), i
-
-
-def rel_l2(got, ref):
-    return float((got.to(F64) - ref).norm() / ref.norm())
-
-
 def shape(case):
     """The command's numbers by name, the flags apart, the tile of the case's instance and the K slices."""
     f = case["cmd"].split()
@@ -261,10 +241,6 @@ def twin_cmd(case):
     f = case["cmd"].split()
     f[9] = str(int(f[9]) & ~P3)
     return " ".join(f)
-
-
-def _randn(seed, *shape_):
-    return torch.randn(*shape_, generator=torch.Generator().manual_seed(seed), dtype=F32)
 
 
 def operands(case):

@@ -62,7 +62,7 @@ import zlib
 
 import torch
 
-from _conv_tile_ref import UB, U, F64, bf16, worst_ratio  # noqa: F401  (worst_ratio: re-exported for the checks)
+from _bounds import F64, U, UB, bf16, randn as _randn, worst_ratio  # noqa: F401  (worst_ratio: re-exported for the checks)
 
 CHUNK = 8192
 RISK_CAP = 0.125
@@ -233,10 +233,6 @@ def reduced(case):
         return case
     f[1] = str(min(int(f[1]), 4))
     return dict(case, cmd=" ".join(f))
-
-
-def _randn(seed, *shape_):
-    return torch.randn(*shape_, generator=torch.Generator().manual_seed(seed), dtype=torch.float32)
 
 
 def _pair_of(seed, family, rows, K, N):

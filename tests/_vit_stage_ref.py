@@ -13,26 +13,11 @@ import math
 
 import torch
 
-UB = 2.0 ** -8
-U = 2.0 ** -24
+import _bounds
+from _bounds import F64, U, UB, bf16, randn as _randn  # noqa: F401
+
 EPS = 1e-5
-F64 = torch.float64
-
-
-def bf16(t):
-    """Round to bf16 (nearest even), keep the dtype of ``t`` (float32 / float64 values that are exactly bf16)."""
-    return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
-
-
-def _randn(seed, *shape):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float32)
-
-
-def worst_ratio(got, ref, bound):
-    """max |got - ref| / bound, in float64 (bound > 0 wherever it is compared; 0 / 0 counts as 0)."""
-    err = (got.to(F64) - ref.to(F64)).abs()
-    r = torch.where(err == 0, torch.zeros_like(err), err / bound.to(F64))
-    return float(r.max())
+worst_ratio = lambda got, ref, bound: _bounds.worst_ratio(got, ref, bound)[0]      # noqa: E731  (these stages report no index)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -15,15 +15,14 @@ Per case, for logits, values and the final state:
 A reuse case runs EC_POLICY_INFER and then EC_POLICY_INFER_REUSE in the same workspace on new features, goals, h0 and masks;
 both calls are checked.  The cases of a switch setting run in a child process started under that setting, one child at a
 time; after a child that exits non-zero no further child is started."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _child import GPU, json_lines  # noqa: E402
 import _act_route_ref as ref  # noqa: E402
 
 cases = ref.cases
@@ -36,7 +35,6 @@ SLICE_BOUND = 1e-5
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 _results = {}                                   # case name -> run_case() result: computed once, shared
-_child_failed = []
 
 
 def _run(name):
@@ -94,16 +92,11 @@ def test_actor_slices_are_bit_equal_on_split_parts(name):
 
 @pytest.mark.parametrize("setting", [s for s in cases.SETTINGS if s != "default"])
 def test_switch_setting_against_float64_oracle(setting):
-    assert not _child_failed, "an earlier child exited with %s: no further child is started" % _child_failed
     names = cases.cases_of(setting)
-    env = {k: v for k, v in os.environ.items() if not k.startswith("EC_") or k == "EC_AMD_LIB"}
-    env.update(cases.SETTINGS[setting])
-    r = subprocess.run([sys.executable, os.path.join(HERE, "_act_route_check.py"), *names], capture_output=True, text=True, env=env,
-                       timeout=300)
-    if r.returncode != 0:
-        _child_failed.append(r.returncode)
+    r = GPU.run([sys.executable, os.path.join(HERE, "_act_route_check.py"), *names], drop="EC_*", env=cases.SETTINGS[setting], limit=300,
+                stop_file_on_failure=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    got = [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
+    got = json_lines(r)
     assert [g["case"] for g in got] == names
     for g in got:
         _check(g["case"], g["figs"], g["equal"])

@@ -1,12 +1,12 @@
 """GPU: a plain `python bench.py` run -- set-up, warm-up, the timed steps, the outputs of the last one (--dump-outputs) and the
 headline line, nothing else (the secondary measurements need --full) -- and the reproducibility of what it dumps."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from _child import GPU, json_lines
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,12 +17,11 @@ def _plain(out_dir):
     # 64 actors = two actor slices on two streams, as at the headline size
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--actors", "64", "--rollout", "8", "--steps", "2",
            "--warmup", "1", "--dump-outputs", out_dir]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT,
-                       env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+    r = GPU.run(cmd, drop=("RANK", "WORLD_SIZE", "LOCAL_RANK"), limit=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    lines = json_lines(r)
     assert len(lines) == 1, r.stdout[-3000:]
-    return json.loads(lines[0])
+    return lines[0]
 
 
 def test_plain_bench_run_dumps_the_last_step_reproducibly(tmp_path):

@@ -2,7 +2,7 @@
 four: _conv_tile_ref.EXEMPT) against the float64 references and element-wise bounds of tests/_conv_tile_ref.py -- no margin on top of
 the derived bounds (the CPU suite checks that those bounds bite and that each case launches the instance it names:
 tests/test_conv_tile_ref.py).  One child process per switch setting (tests/_conv_tile_check.py), one at a time; a child that ends by
-signal or at its time limit stops every later setting of this file before it starts a process.
+signal or at its time limit stops every later child of the whole run before it starts a process (tests/_child.py).
 
 Measured worst |error| / bound per instance on an MI355X (every case under 1: the pass threshold is 1.0, not these figures).
 c8<BN, KS, POOL, long segments, X3, S2> = conv_igemm8_kernel, c4<BM, BN, WM, WN, KS, POOL, PF, MV, NS, ILV, S2> = conv_igemm_kernel:
@@ -26,38 +26,27 @@ element intact.  The file takes 10 s in all (setting a 5.2 s, setting b 3.2 s; l
 references and the start of the two child processes)."""
 import json
 import os
-import subprocess
 import sys
 
 import pytest
 
 import _conv_tile_ref as R
+from _child import GPU, last_json
 
 pytestmark = pytest.mark.gpu
 
 CHILD_LIMIT = 300
-FAULT_CODES = (134, 139, 124, 137)
-_faulted = []              # (setting, how the child ended): set once, read by every later setting
 
 
 @pytest.mark.parametrize("setting", list(R.SETTINGS))
 def test_conv_tiles_in_a_child_process(setting):
     """Every case of the setting once: worst |error| / bound <= 1 and every guard element (a tile of rows before and after the
     output, the columns around a column-block output) bitwise untouched."""
-    assert not _faulted, "not started: the child of setting %r ended with %s" % _faulted[0]
-    env = {k: v for k, v in os.environ.items() if k not in R.SWITCHES}
-    env.update(R.SETTINGS[setting])
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_conv_tile_check.py")
-    try:
-        p = subprocess.run([sys.executable, script, setting], env=env, capture_output=True, text=True, timeout=CHILD_LIMIT)
-    except subprocess.TimeoutExpired:
-        _faulted.append((setting, "its %d s time limit" % CHILD_LIMIT))
-        raise
+    p = GPU.run([sys.executable, script, setting], drop=R.SWITCHES, env=R.SETTINGS[setting], limit=CHILD_LIMIT)
     print("\n".join(p.stdout.splitlines()[:-1])[-20000:])
-    if p.returncode < 0 or p.returncode in FAULT_CODES:
-        _faulted.append((setting, "return code %d" % p.returncode))
     assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
-    res = json.loads(p.stdout.strip().splitlines()[-1])
+    res = last_json(p)
     cases = R.cases_of(setting)
     assert res["setting"] == setting and [c["cmd"] for c in res["cases"]] == [c["cmd"] for c in cases]
     worst = {}

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _child import GPU
 from embodied_clip_amd import synthetic as syn
 from oracle import clip_resnet as ocr
 
@@ -114,7 +115,7 @@ def test_conv_bf16_matches_oracle(dev, B, H, W, Cin, Cout, ks, pool, res, act):
 def test_conv_igemm8_pingpong_matches_oracle(dev, monkeypatch, big, B, H, W, Cin, Cout, ks, pool, res, act):
     """The 8-wave kernel's cross-wave LDS hand-offs (counted waits + raw barriers) are exercised on many tiles per
     launch and repeated launches: a race shows up as rare wrong tiles, so every output element is compared, 3 times."""
-    import subprocess, sys, os, json
+    import sys, os
     # EC_CONV_BIG is read once per process: run the case in a child process with the variable set
     code = f"""
 import sys, torch
@@ -133,8 +134,7 @@ for rep in range(3):
     worst = max(worst, T._rel(got, ref))
 print("REL", worst)
 """
-    env = dict(os.environ, EC_CONV_BIG=str(big))
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    r = GPU.run([sys.executable, "-c", code], env={"EC_CONV_BIG": str(big)}, limit=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     rel = float(r.stdout.strip().split("REL")[-1])
     assert rel < 4e-3, rel
@@ -318,7 +318,6 @@ def test_rn50_fused_layer1_boundaries_match_unfused_plan(dev, tmp_path):
     boundaries (conv_pair.hip).  Same bf16 roundings except the block-0 identity, which the fused plan keeps in fp32.
     The library reads its switches ONCE per process (ec_config), so the plain plan runs in a child process."""
     import os
-    import subprocess
     import sys
     from embodied_clip_amd.encoder import RN50Trunk
     sd = syn.rn50_visual_state_dict(0)
@@ -334,8 +333,7 @@ def test_rn50_fused_layer1_boundaries_match_unfused_plan(dev, tmp_path):
             "f = t.forward(x)\n"
             "torch.save({'feat': f.float().cpu(), 'nchw': t.to_nchw_f32(f).cpu(), 'ops': t.lib.ec_rn50_num_ops(t.h),"
             " 'hash': t.plan_hash()}, %r)\n") % (root, out)
-    r = subprocess.run([sys.executable, "-c", code], env={**os.environ, "EC_RN50_FUSE": "0"}, capture_output=True, text=True,
-                       timeout=600)
+    r = GPU.run([sys.executable, "-c", code], env={"EC_RN50_FUSE": "0"}, limit=600)
     assert r.returncode == 0, r.stderr[-2000:]
     plain = torch.load(out)
     # layer 1: 3 conv1 + 1 downsample + 1 avgpool (emitted by the layer-1 -> layer-2 boundary launch) launches gone;
@@ -352,7 +350,6 @@ def test_rn50_fused_layer1_boundaries_match_unfused_plan(dev, tmp_path):
 def _conv_in_child(env, cases, tmp_path, tag):
     """Runs ec_conv_bf16 over `cases` in a child process with extra environment switches; returns the outputs."""
     import os
-    import subprocess
     import sys
     out = str(tmp_path / f"conv_{tag}.pt")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -366,7 +363,7 @@ def _conv_in_child(env, cases, tmp_path, tag):
             "    b = torch.randn(Cout, generator=g).cuda()\n"
             "    res.append(enc.conv_bf16(x, w, b, None, ksize=ks, pool=bool(pool), act=1).cpu())\n"
             "torch.save(res, %r)\n") % (root, cases, out)
-    r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True, timeout=900)
+    r = GPU.run([sys.executable, "-c", code], env=env, limit=900)
     assert r.returncode == 0, r.stderr[-2000:]
     return torch.load(out)
 
@@ -566,7 +563,6 @@ def test_trunk_with_fused_bottlenecks_is_bit_identical_to_the_unfused_plan(dev, 
     """EC_RN50_BNECK (default 128: launches of >= 128 frames run layer3.1 .. layer3.5's conv2 + conv3 as one fused launch
     each): the same features, bit for bit, as the plan without them (child process, EC_RN50_BNECK=0), and fewer ops."""
     import os
-    import subprocess
     import sys
     from embodied_clip_amd.encoder import RN50Trunk
     sd = syn.rn50_visual_state_dict(0)
@@ -583,8 +579,7 @@ def test_trunk_with_fused_bottlenecks_is_bit_identical_to_the_unfused_plan(dev, 
             "x = syn.synthetic_rgb(21, 8).repeat(16, 1, 1, 1).roll(2, dims=1)[:128].contiguous().to('cuda:0')\n"
             "torch.save({'feat': t.forward(x).float().cpu(), 'small': t.forward(x[:5].contiguous()).float().cpu(),\n"
             "            'hash': t.plan_hash(), 'ops': t.lib.ec_rn50_num_ops(t.h)}, %r)\n") % (root, out)
-    r = subprocess.run([sys.executable, "-c", code], env={**os.environ, "EC_RN50_BNECK": "0"}, capture_output=True, text=True,
-                       timeout=600)
+    r = GPU.run([sys.executable, "-c", code], env={"EC_RN50_BNECK": "0"}, limit=600)
     assert r.returncode == 0, r.stderr[-2000:]
     got = torch.load(out)
     assert got["hash"] != base.plan_hash() and got["ops"] == base.lib.ec_rn50_num_ops(base.h) + 10    # (conv1 + conv2 + conv3 -> 1 op, five times)
@@ -719,7 +714,6 @@ def test_trunk_with_folded_downsample_convs_matches_the_chained_plan(dev, tmp_pa
     conv3 + residual -- for layer3.0 / layer4.0; the default plan has one launch less per block and never writes the downsample
     output.  Both against the fp32 oracle; the folded plan rounds once where the chained one rounds twice."""
     import os
-    import subprocess
     import sys
     from embodied_clip_amd.encoder import RN50Trunk
     sd = syn.rn50_visual_state_dict(0)
@@ -734,8 +728,7 @@ def test_trunk_with_folded_downsample_convs_matches_the_chained_plan(dev, tmp_pa
             "x = syn.synthetic_rgb(5, 3).to('cuda:0')\n"
             "f = t.forward(x)\n"
             "torch.save({'nchw': t.to_nchw_f32(f).cpu(), 'ops': t.lib.ec_rn50_num_ops(t.h), 'hash': t.plan_hash()}, %r)\n") % (root, out)
-    r = subprocess.run([sys.executable, "-c", code], env={**os.environ, "EC_RN50_DSCAT": "0"}, capture_output=True, text=True,
-                       timeout=600)
+    r = GPU.run([sys.executable, "-c", code], env={"EC_RN50_DSCAT": "0"}, limit=600)
     assert r.returncode == 0, r.stderr[-2000:]
     chained = torch.load(out)
     assert folded.lib.ec_rn50_num_ops(folded.h) == chained["ops"] - 2 and folded.plan_hash() != chained["hash"]
@@ -753,7 +746,6 @@ def test_pooled_copy_from_layer2s_last_conv3_is_bit_identical_to_the_pooling_pas
     its own pass (child process, EC_RN50_POOLOUT=0) at 128 and 44 frames (the smallest even count with >= 1024 tiles); 43 frames
     (odd: windows not a multiple of 8) and 5 frames run the pooling pass inside the same plan."""
     import os
-    import subprocess
     import sys
     from embodied_clip_amd.encoder import RN50Trunk
     sd = syn.rn50_visual_state_dict(0)
@@ -771,8 +763,7 @@ def test_pooled_copy_from_layer2s_last_conv3_is_bit_identical_to_the_pooling_pas
             "x = torch.stack([x[i].roll(shifts=5 * (i // 8), dims=0) for i in range(128)]).contiguous().to('cuda:0')\n"
             "torch.save({'f': {n: t.forward(x[:n].contiguous()).float().cpu() for n in (128, 44, 43, 5)},\n"
             "            'hash': t.plan_hash(), 'ops': t.lib.ec_rn50_num_ops(t.h)}, %r)\n") % (root, out)
-    r = subprocess.run([sys.executable, "-c", code], env={**os.environ, "EC_RN50_POOLOUT": "0"}, capture_output=True, text=True,
-                       timeout=600)
+    r = GPU.run([sys.executable, "-c", code], env={"EC_RN50_POOLOUT": "0"}, limit=600)
     assert r.returncode == 0, r.stderr[-2000:]
     got = torch.load(out)
     assert got["hash"] != base.plan_hash() and got["ops"] == base.lib.ec_rn50_num_ops(base.h)   # (the pooling op stays in the plan: skipped per launch)

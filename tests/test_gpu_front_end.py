@@ -3,8 +3,8 @@ _front_end_ref.EXEMPT) -- the RGB, depth and 7 x 7 stems, the 2 x 2 average pool
 against the float64 references and element-wise bounds of tests/_front_end_ref.py, no margin on top of the derived bounds (the CPU
 suite checks that those bounds bite and that each case launches the instance it names: tests/test_front_end_ref.py).  The MFMA
 stems are held to two references each: the tight one, of the operands rounded as the kernel rounds them, and the loose one, of the
-unrounded frame and fp32 weights.  One child process (tests/_front_end_check.py) with its own time limit, and nothing in this file
-after it: a child that ends by signal, abort code or at its limit fails the test and starts no further GPU work.
+unrounded frame and fp32 weights.  One child process (tests/_front_end_check.py) with its own time limit: a child that ends by signal, abort
+code or at its limit fails the test and stops every later child of the whole run before it starts a process (tests/_child.py).
 
 Measured worst |error| / bound per instance on an MI355X (every case under 1: the pass threshold is 1.0, not these figures):
   stem_conv1_kernel        <32, false> tight 0.941 loose 0.392   <32, true> 0.942 / 0.436   <64, false> 0.947 / 0.422
@@ -21,12 +21,12 @@ the rest is the float64 references, the copies and the start of the child proces
 """
 import json
 import os
-import subprocess
 import sys
 
 import pytest
 
 import _front_end_ref as R
+from _child import GPU, last_json
 
 pytestmark = pytest.mark.gpu
 
@@ -38,10 +38,10 @@ def test_front_end_kernels_in_a_child_process():
     every guard element (a tile of rows before and after the output, the columns around the column-block output, the words around
     the flag) bitwise untouched, the layout kernels and the flag exact."""
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_front_end_check.py")
-    p = subprocess.run([sys.executable, script], capture_output=True, text=True, timeout=CHILD_LIMIT)
+    p = GPU.run([sys.executable, script], limit=CHILD_LIMIT)
     print("\n".join(p.stdout.splitlines()[:-1])[-20000:])
-    assert p.returncode == 0, (p.returncode, p.stderr[-2000:])       # (signal, abort code, time limit: nothing runs after it here)
-    res = json.loads(p.stdout.strip().splitlines()[-1])
+    assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
+    res = last_json(p)
     assert [(c["cmd"], c["variant"]) for c in res["cases"]] == [(c["cmd"], c["variant"]) for c in R.CASES]
     worst = {}
     for c, want in zip(res["cases"], R.CASES):

@@ -22,15 +22,14 @@ after a child that exits non-zero no further child is started.
 
 Found by this test when it was written: h48_t3_n5 (3H = 144, no multiple of 32) had every gradient in front of the GRU wrong
 by ~70 % -- the transpose of the re-ordered weight_ih in Bwd::input_grad was launched with 3H / 32 row blocks, rounded down."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _child import GPU, json_lines  # noqa: E402
 import _learn_route_ref as ref  # noqa: E402
 
 cases = ref.cases
@@ -38,7 +37,6 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 _results = {}                                   # case name -> run_case() result: computed once, shared
-_child_failed = []
 
 
 def _run(name):
@@ -92,16 +90,11 @@ def test_actor_slices_agree_on_the_32_tile_step():
 
 @pytest.mark.parametrize("setting", [s for s in cases.SETTINGS if s != "default"])
 def test_setting_against_float64_oracle(setting):
-    assert not _child_failed, "an earlier child exited with %s: no further child is started" % _child_failed
     names = cases.cases_of(setting)
-    env = {k: v for k, v in os.environ.items() if not k.startswith("EC_") or k == "EC_AMD_LIB"}
-    env.update(cases.SETTINGS[setting])
-    r = subprocess.run([sys.executable, os.path.join(HERE, "_learn_route_check.py"), *names], capture_output=True, text=True, env=env,
-                       timeout=300)
-    if r.returncode != 0:
-        _child_failed.append(r.returncode)
+    r = GPU.run([sys.executable, os.path.join(HERE, "_learn_route_check.py"), *names], drop="EC_*", env=cases.SETTINGS[setting], limit=300,
+                stop_file_on_failure=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    got = [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
+    got = json_lines(r)
     assert [g["case"] for g in got] == names
     failed = []
     for g in got:

@@ -6,25 +6,23 @@ config 5's 2-GPU leg (zero-shot worker) and the a18 check proper -- HIP shard gr
 with the oracle's unsharded gradient (the 1-GPU form of it runs in tests/test_gpu_configs.py).
 At the end of the file (round 6): the a18 check and the replicas-stay-identical check with the two ranks SHARING cuda:0 and
 exchanging over gloo -- the N > 1 engine path on real HIP kernels on the driver's 1-GPU box, even and uneven (3 + 2) shards."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
+
+from _child import GPU, json_lines
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(*flags, timeout=1500):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags, "--full", "--no-cpu-baseline", "--no-h2d",
-                        "--no-traffic"],
-                       capture_output=True, text=True, timeout=timeout, cwd=ROOT,
-                       env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+    r = GPU.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags, "--full", "--no-cpu-baseline", "--no-h2d", "--no-traffic"],
+                drop=("RANK", "WORLD_SIZE", "LOCAL_RANK"), limit=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    return json_lines(r)[-1]
 
 
 def test_rccl_first_contact_at_world_size_1():
@@ -55,11 +53,10 @@ def test_overlapped_allreduce_is_the_single_allreduce(actors, slices):
     after it.  Over RCCL at world size 1 (identity SUM) the worker must end where the single-call worker and the
     no-collective worker end: a missing stream dependency (a section reduced before it is final, an optimiser step before
     the communication stream is done) shows as a parameter difference of the order of lr."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_overlap_allreduce_check.py"), str(actors), str(slices)],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT,
-                       env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+    r = GPU.run([sys.executable, os.path.join(ROOT, "tests", "_overlap_allreduce_check.py"), str(actors), str(slices)],
+                drop=("RANK", "WORLD_SIZE", "LOCAL_RANK"), limit=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    out = json_lines(r)[-1]
     assert out["moved"] > 1e-4                                    # 4 epochs of Adam at lr 3e-4 did move the weights
     assert out["max_abs_overlap_vs_single"] < 2e-6, out
     assert out["max_abs_overlap_vs_none"] < 2e-6, out
@@ -246,12 +243,11 @@ def test_bench_py_launched_as_the_driver_launches_it_with_two_ranks_sharing_one_
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--actors", "33", "--rollout", "8",
            "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-h2d", "--no-traffic", "--no-plugin",
            "--no-sync-actions"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
-                       env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+    r = GPU.run(cmd, drop=("RANK", "WORLD_SIZE", "LOCAL_RANK"), limit=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    lines = json_lines(r)
     assert len(lines) == 1, lines                              # rank 0 alone prints
-    line = json.loads(lines[0])
+    line = lines[0]
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and "TEST MODE" in line["data"]
     assert line["scaling"] == "strong" and line["config"]["global_actors"] == 33
     assert isinstance(line["allreduce_ms_per_rank"], list) and len(line["allreduce_ms_per_rank"]) == 2

@@ -3,7 +3,6 @@
 import json
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +13,7 @@ from embodied_clip_amd import synthetic as syn
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _episode_ref as er  # noqa: E402
+from _child import GPU, last_json  # noqa: E402
 import _nav_episode_ref as nr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -352,11 +352,11 @@ def test_command_line_writes_the_metrics_file(dev, tmp_path):
     fixture = os.path.join(REPO, "tests", "golden", "robothor_object_types.json")
     names = json.load(open(fixture))["object_types"]
     out = str(tmp_path / "metrics.json")
-    res = subprocess.run([sys.executable, "-m", "embodied_clip_amd.evaluate", "--actors", "4", "--steps", "3", "--chunks", "2",
-                          "--env-seed", str(env_seed), "--nav-metrics", "--object-types", fixture, "--groups", fixture,
-                          "--metrics-json", out], cwd=REPO, capture_output=True, text=True, timeout=300)
+    res = GPU.run([sys.executable, "-m", "embodied_clip_amd.evaluate", "--actors", "4", "--steps", "3", "--chunks", "2",
+                   "--env-seed", str(env_seed), "--nav-metrics", "--object-types", fixture, "--groups", fixture,
+                   "--metrics-json", out], cwd=REPO, limit=300)
     assert res.returncode == 0, res.stderr[-2000:]
-    line = json.loads(res.stdout.strip().splitlines()[-1])
+    line = last_json(res)
     assert line["episodes"] == 4 and set(line["by_object_type"]) == set(names) and set(line["groups"]) == {"seen", "unseen"}
     for key in ("spl", "soft_spl", "dist_to_goal", "path_length"):
         assert key in line

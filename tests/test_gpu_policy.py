@@ -784,15 +784,13 @@ def test_learn_pass_policy_gemm_modes_match_oracle_at_pingpong_size(fast):
     dW1 on two planes of dc1, the backward's large gradient GEMMs on three bf16x3 products) and the fp32-exact mode (0), each in
     its own process, at T*N*49 = 37,632 rows -- where c1 really takes the 8-wave ping-pong kernel -- against the oracle's forward
     and autograd gradients at the UNCHANGED tolerances: forward 2e-5, gradients 2e-4 rel-L2 per tensor."""
-    import json
     import os
-    import subprocess
     import sys
+    from _child import GPU, json_lines
     here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, os.path.join(here, "_policy_mode_check.py")], env={**os.environ, "EC_POLICY_FAST": fast},
-                       capture_output=True, text=True, timeout=900)
+    r = GPU.run([sys.executable, os.path.join(here, "_policy_mode_check.py")], env={"EC_POLICY_FAST": fast}, limit=900)
     assert r.returncode == 0, r.stderr[-2000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    out = json_lines(r)[-1]
     assert out["mode"] == fast and out["rows"] >= 256 * 128
     assert out["logits"] < 2e-5 and out["values"] < 2e-5, out
     for name, e in out["grads"].items():

@@ -1,8 +1,8 @@
 """GPU: every registered instance of gemm_f32_kernel / gemm_x3_kernel (36 of 36) through ec_gemm_f32 against the float64 references
 and element-wise bounds of tests/_policy_gemm_ref.py -- no margin on top of the derived bounds (the CPU suite checks that those
 bounds bite and that each case launches the instance it names: tests/test_policy_gemm_ref.py).  One child process per switch setting
-(tests/_policy_gemm_check.py), one at a time; a child that ends by signal or at its time limit stops every later setting of this file
-before it starts a process.  With them the two relatives of the same arithmetic: ec_split3_bf16 (the planes sum to the input exactly)
+(tests/_policy_gemm_check.py), one at a time; a child that ends by signal or at its time limit stops every later child of the whole run
+before it starts a process (tests/_child.py).  With them the two relatives of the same arithmetic: ec_split3_bf16 (the planes sum to the input exactly)
 and ec_dw_tn_x3 (dw_tn_x3_kernel<3>; dw_tn_x3_kernel<2> is reachable only through the learn pass: tests/test_gpu_learn_routes.py).
 
 Measured worst |error| / bound per instance on an MI355X (every case under 1: the pass threshold is 1.0, not these figures).
@@ -24,20 +24,18 @@ the rest is the float64 references, the emulations behind the L2 thresholds and 
 """
 import json
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
 
 import _policy_gemm_ref as R
+from _child import GPU, last_json
+from _guard import SENT16, SENT32
 
 pytestmark = pytest.mark.gpu
 
 CHILD_LIMIT = 300
-FAULT_CODES = (134, 139, 124, 137)
-SENT32 = 0x7FC12345
-_faulted = []              # (setting, how the child ended): set once, read by every later setting
 
 
 @pytest.mark.parametrize("setting", list(R.SETTINGS))
@@ -45,20 +43,11 @@ def test_policy_gemm_in_a_child_process(setting):
     """Every case of the setting once: worst |error| / bound <= 1, every guard element (a tile of rows before and after the output,
     the columns from N up to ldc) bitwise untouched, no NaN left in the written region; the plane accounting of the six-product x3
     cases; a parts case run twice is bit-identical; EC_GEMM_3PRODUCTS changes the bits of an x3 case and none of an fp32-kernel one."""
-    assert not _faulted, "not started: the child of setting %r ended with %s" % _faulted[0]
-    env = {k: v for k, v in os.environ.items() if k not in R.SWITCHES}
-    env.update(R.SETTINGS[setting])
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_policy_gemm_check.py")
-    try:
-        p = subprocess.run([sys.executable, script, setting], env=env, capture_output=True, text=True, timeout=CHILD_LIMIT)
-    except subprocess.TimeoutExpired:
-        _faulted.append((setting, "its %d s time limit" % CHILD_LIMIT))
-        raise
+    p = GPU.run([sys.executable, script, setting], drop=R.SWITCHES, env=R.SETTINGS[setting], limit=CHILD_LIMIT)
     print("\n".join(p.stdout.splitlines()[:-1])[-20000:])
-    if p.returncode < 0 or p.returncode in FAULT_CODES:
-        _faulted.append((setting, "return code %d" % p.returncode))
     assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
-    res = json.loads(p.stdout.strip().splitlines()[-1])
+    res = last_json(p)
     cases = R.cases_of(setting)
     assert res["setting"] == setting and [c["cmd"] for c in res["cases"]] == [c["cmd"] for c in cases]
     worst = {}
@@ -115,11 +104,11 @@ def test_split3_planes_sum_exactly(rows, K):
     w = _split_inputs(rows * K).view(rows, K)
     assert rows * K < 128 or bool((w == 0).any() and (w.abs() > 3e38).any() and ((w != 0) & (w.abs() < 1e-35)).any())
     n = rows * 3 * K
-    buf = torch.full((n + 128,), 0x7FC1, dtype=torch.int16, device=dev)
+    buf = torch.full((n + 128,), SENT16, dtype=torch.int16, device=dev)
     _lib.check(lib.ec_split3_bf16(w.to(dev).data_ptr(), buf.data_ptr() + 128, rows, K, _lib.stream_ptr()))
     torch.cuda.synchronize()
     o = buf.cpu()
-    assert bool((o[:64] == 0x7FC1).all() and (o[64 + n:] == 0x7FC1).all())
+    assert bool((o[:64] == SENT16).all() and (o[64 + n:] == SENT16).all())
     planes = o[64:64 + n].view(torch.bfloat16).view(rows, 3, K)
     assert torch.equal(planes.double().sum(1), w.double())
     assert torch.equal(planes[:, 0], w.to(torch.bfloat16))                 # the leading plane is the nearest-even rounding

@@ -13,7 +13,6 @@ and the reference within 3.3e-7 on the new route and 2.8e-7 under EC_POOLED_ACT=
 """
 import functools
 import os
-import subprocess
 import sys
 
 import pytest
@@ -21,6 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _pooled_net_ref as ref  # noqa: E402
+from _child import GPU  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -179,9 +179,8 @@ print("CHILD-OK")
 
 def test_chained_act_steps_on_the_general_route(dev, repo_root):
     """the same under EC_POOLED_ACT=0 (the switch is read once per process: a child process)"""
-    env = dict(os.environ, EC_POOLED_ACT="0", PYTHONPATH=repo_root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    out = subprocess.run([sys.executable, "-c", _CHILD.format(tests=os.path.dirname(os.path.abspath(__file__)))], env=env, cwd=repo_root,
-                         capture_output=True, text=True, timeout=240)
+    env = {"EC_POOLED_ACT": "0", "PYTHONPATH": repo_root + os.pathsep + os.environ.get("PYTHONPATH", "")}
+    out = GPU.run([sys.executable, "-c", _CHILD.format(tests=os.path.dirname(os.path.abspath(__file__)))], env=env, cwd=repo_root, limit=240)
     print(out.stdout[-3000:], out.stderr[-2000:])
     assert out.returncode == 0 and "CHILD-OK" in out.stdout
 

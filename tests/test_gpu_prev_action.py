@@ -299,13 +299,11 @@ def test_teacher_forcing_through_act_pa(dev):
 def test_learn_pass_without_the_reordered_weight_ih():
     """One case in a fresh child process with the re-ordered weight_ih switched off (EC_WIH_PERM=0, read once per process): at
     S = 7 the routes that keep weight_ih's column order -- the dense copy, the dense gradient added back row by row."""
-    import json
-    import subprocess
+    from _child import GPU, json_lines
     here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, os.path.join(here, "_prev_action_mode_check.py")], env={**os.environ, "EC_WIH_PERM": "0"},
-                       capture_output=True, text=True, timeout=600)
+    r = GPU.run([sys.executable, os.path.join(here, "_prev_action_mode_check.py")], env={"EC_WIH_PERM": "0"}, limit=600)
     assert r.returncode == 0, r.stderr[-2000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    out = json_lines(r)[-1]
     print(out)
     assert out["wih_perm"] == "0" and out["deterministic"]
     assert max(out["forward"]) < 2e-5 and max(out["act"]) < 2e-5, out

@@ -8,13 +8,13 @@ rel-L2 <= 7e-3 against the same maps from other launch shapes (the project's bou
 < 1e-2 for uint8 against host-normalised fp32 frames (``test_uint8_input_path_matches_normalised_fp32_path``), and no tolerance
 at all for the pairing: a changed frame changes its own row and no other."""
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+from _child import GPU
 from embodied_clip_amd import synthetic as syn
 from oracle import clip_resnet as ocr
 
@@ -173,8 +173,7 @@ def test_composed_route_in_a_child_process(dev, tmp_path):
     chunk, the pair kernel) on the same frames"""
     _, _, _, _, got, _, _ = _case(dev, SMALL)
     path = str(tmp_path / "composed.pt")
-    env = dict(os.environ, EC_RGBD_JOINT="0")
-    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, path], env=env, capture_output=True, text=True, timeout=300)
+    r = GPU.run([sys.executable, "-c", _CHILD, ROOT, path], env={"EC_RGBD_JOINT": "0"}, limit=300)
     assert r.returncode == 0, r.stderr[-2000:]
     composed = torch.load(path)
     rel = _rel(composed, got)

@@ -13,7 +13,6 @@ within 2e-5 on the stacked kernel and on the general route.
 """
 import functools
 import os
-import subprocess
 import sys
 
 import pytest
@@ -21,6 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _rnn_stack_ref as ref  # noqa: E402
+from _child import GPU  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -243,9 +243,8 @@ print("CHILD-OK")
 
 def test_chained_act_steps_on_the_general_route(dev, repo_root):
     """the same under EC_RNN_STACK=0 (the switch is read once per process: a child process)"""
-    env = dict(os.environ, EC_RNN_STACK="0", PYTHONPATH=repo_root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    out = subprocess.run([sys.executable, "-c", _CHILD.format(tests=os.path.dirname(os.path.abspath(__file__)))], env=env, cwd=repo_root,
-                         capture_output=True, text=True, timeout=240)
+    env = {"EC_RNN_STACK": "0", "PYTHONPATH": repo_root + os.pathsep + os.environ.get("PYTHONPATH", "")}
+    out = GPU.run([sys.executable, "-c", _CHILD.format(tests=os.path.dirname(os.path.abspath(__file__)))], env=env, cwd=repo_root, limit=240)
     print(out.stdout[-2000:], out.stderr[-2000:])
     assert out.returncode == 0 and "CHILD-OK" in out.stdout
 

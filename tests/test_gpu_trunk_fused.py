@@ -3,7 +3,7 @@ conv_basic.hip that a public entry point reaches (32 of 33; the other one: _trun
 and element-wise bounds of tests/_trunk_fused_ref.py -- no margin on top of the derived bounds (the CPU suite checks that those
 bounds bite and that each case launches the instance it names: tests/test_trunk_fused_ref.py).  One child process per switch
 setting (tests/_trunk_fused_check.py), one at a time, each with its own time limit; a child that ends by signal, abort code or at
-its time limit stops every later setting of this file before it starts a process.
+its time limit stops every later child of the whole run before it starts a process (tests/_child.py).
 
 Measured worst |error| / bound per instance on an MI355X (every output of every case under 1: the pass threshold is 1.0, not these
 figures; two-stage kernels: the worst of their outputs):
@@ -28,18 +28,16 @@ processes).
 """
 import json
 import os
-import subprocess
 import sys
 
 import pytest
 
 import _trunk_fused_ref as R
+from _child import GPU, last_json
 
 pytestmark = pytest.mark.gpu
 
 CHILD_LIMIT = 300
-FAULT_CODES = (134, 139, 124, 137)
-_faulted = []              # (setting, how the child ended): set once, read by every later setting
 
 
 @pytest.mark.parametrize("setting", list(R.SETTINGS))
@@ -47,20 +45,11 @@ def test_trunk_fused_kernels_in_a_child_process(setting):
     """Every case of the setting once: worst |error| / bound <= 1 on every output, every guard element (a tile of rows before and
     after each output, the columns around a column-block output) bitwise untouched, the share of bneck intermediates at risk under
     its cap, and the pooled pair kernel's outputs with y = NULL bit for bit those with y stored."""
-    assert not _faulted, "not started: the child of setting %r ended with %s" % _faulted[0]
-    env = {k: v for k, v in os.environ.items() if k not in R.SWITCHES}
-    env.update(R.SETTINGS[setting])
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_trunk_fused_check.py")
-    try:
-        p = subprocess.run([sys.executable, script, setting], env=env, capture_output=True, text=True, timeout=CHILD_LIMIT)
-    except subprocess.TimeoutExpired:
-        _faulted.append((setting, "its %d s time limit" % CHILD_LIMIT))
-        raise
+    p = GPU.run([sys.executable, script, setting], drop=R.SWITCHES, env=R.SETTINGS[setting], limit=CHILD_LIMIT)
     print("\n".join(p.stdout.splitlines()[:-1])[-20000:])
-    if p.returncode < 0 or p.returncode in FAULT_CODES:
-        _faulted.append((setting, "return code %d" % p.returncode))
     assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
-    res = json.loads(p.stdout.strip().splitlines()[-1])
+    res = last_json(p)
     cases = R.cases_of(setting)
     assert res["setting"] == setting and [c["cmd"] for c in res["cases"]] == [c["cmd"] for c in cases]
     worst = {}

@@ -13,21 +13,20 @@ Measured on an MI355X (worst |error| / bound; every case under 1, so no bound ca
   embed_cls             rel-L2 2.9e-3 .. 7.2e-3 against the emulating oracle, 3.6e-3 .. 8.1e-3 against the fp32 oracle on both
                         routes (the oracles differ by 3.5e-3 .. 8.3e-3 on these towers); the two routes 1.5e-3 .. 2.6e-3 apart"""
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
 
 import _vit_cls_ref as R
+from _child import GPU
+from _guard import SENT16, SENT32
 from _vit_cls_towers import TOWERS, golden_case, tower_case
 from embodied_clip_amd import _lib
 from oracle import clip_vit as ovit
 
 pytestmark = pytest.mark.gpu
 
-SENT16 = 0x7FC1            # a bf16 NaN pattern (as int16) no kernel here produces
-SENT32 = 0x7FC12345        # an fp32 NaN pattern likewise
 PAD = 8                    # rows behind every output that must keep the sentinel
 
 
@@ -141,12 +140,8 @@ def routes(tmp_path_factory):
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_vit_cls_route_check.py")
     got = {}
     for sw in ("1", "0", None):
-        env = dict(os.environ)
-        env.pop("EC_VIT_CLS_TAIL", None)
-        if sw is not None:
-            env["EC_VIT_CLS_TAIL"] = sw
         path = str(tmp_path_factory.mktemp("cls") / ("route_%s.pt" % sw))
-        p = subprocess.run([sys.executable, script, path], env=env, capture_output=True, text=True, timeout=300)
+        p = GPU.run([sys.executable, script, path], drop=("EC_VIT_CLS_TAIL",), env={} if sw is None else {"EC_VIT_CLS_TAIL": sw}, limit=300)
         assert p.returncode == 0, (sw, p.stderr[-2000:])
         got[sw] = torch.load(path)
     return got

@@ -13,20 +13,20 @@ Measured worst |error| / bound on an MI355X (every case under 1, so no bound car
                          (EC_VIT_WIDE=2); the same figures when the consumer reads ec_row_stats_bf16 records"""
 import json
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
 
 import _vit_stage_ref as R
+from _child import GPU, last_json
+from _guard import SENT16 as SENT
 from embodied_clip_amd import _lib
 from embodied_clip_amd import synthetic as syn
 
 pytestmark = pytest.mark.gpu
 
 SHAPE = -2
-SENT = 0x7FC1              # a bf16 NaN pattern (as int16) no kernel here produces
 PAD = 8                    # rows behind every output that must keep the sentinel
 
 
@@ -192,14 +192,10 @@ def test_ln_fold_against_float64(lib, dev, N, K):
 def test_gemm_ln_chain_in_a_child_process(setting):
     """ec_gemm_bf16_ln, producer -> consumer, per tile setting (read once per process, hence the child): default (128-wide tiles of
     192 rows), EC_VIT_BM192=0 (128 x 256), EC_VIT_WIDE=2 (256-wide: records of count 256).  np = 1, 3, 6, 8 (2, 3, 4 wide)."""
-    env = dict(os.environ)
-    for k in ("EC_VIT_BM192", "EC_VIT_WIDE"):
-        env.pop(k, None)
-    env.update(R.GEMM_SETTINGS[setting])
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_vit_gemm_ln_check.py")
-    p = subprocess.run([sys.executable, script, setting], env=env, capture_output=True, text=True, timeout=300)
+    p = GPU.run([sys.executable, script, setting], drop=("EC_VIT_BM192", "EC_VIT_WIDE"), env=R.GEMM_SETTINGS[setting], limit=300)
     assert p.returncode == 0, p.stderr[-2000:]
-    res = json.loads(p.stdout.strip().splitlines()[-1])
+    res = last_json(p)
     assert res["setting"] == setting and len(res["cases"]) == len(R.gemm_cases(setting))
     worst = {}
     for c in res["cases"]:

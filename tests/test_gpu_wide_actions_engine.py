@@ -4,7 +4,6 @@ tests/test_gpu_imitation_engine.py: the same tiny encoder, actor and step counts
 the float64 oracle (the shapes and tolerances of tests/test_gpu_policy.py: gradients 2e-4, the forward 2e-5), where its heads run
 through one packed [A + 1, H] table and two passes give equal bits."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -13,6 +12,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import _imitation_ref as iref  # noqa: E402
+from _child import GPU  # noqa: E402
 import _wide_actions_engine_check as chk  # noqa: E402
 import _wide_actions_ref as ref  # noqa: E402
 from embodied_clip_amd import synthetic as syn  # noqa: E402
@@ -130,11 +130,8 @@ def test_two_wide_workers_from_one_seed_end_bit_identical():
 
 
 def _child(num_actions, loss, path, switch):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("EC_") or k == "EC_AMD_LIB"}
-    if switch is not None:
-        env["EC_ACT_FUSED_SAMPLE"] = switch
-    r = subprocess.run([sys.executable, os.path.join(HERE, "_wide_actions_engine_check.py"), str(num_actions), loss, path],
-                       capture_output=True, text=True, env=env, timeout=240)
+    r = GPU.run([sys.executable, os.path.join(HERE, "_wide_actions_engine_check.py"), str(num_actions), loss, path], drop="EC_*",
+                env={} if switch is None else {"EC_ACT_FUSED_SAMPLE": switch}, limit=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return torch.load(path)
 
